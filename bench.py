@@ -30,6 +30,10 @@ Prints ONE JSON line on rank 0 (see the driver contract in the task statement) w
                  timings taken inside the library on the stream the kernel runs on
   cpu_baseline : the faithful CPU restatement of the reference algorithm (oracle, "port") timed on
                  this host on a bounded sample and extrapolated (rank 0, N=1 only).
+
+`--dump-outputs DIR` writes what the selected workload's last timed step returned (coefficients, iteration counts, and for cfg4 the
+PSD) as DIR/<name>.npy on rank 0.  The inputs are synthesised from fixed seeds, so two builds run with the same arguments can be
+compared output for output.
 """
 import argparse
 import json
@@ -159,6 +163,30 @@ def driver_record(o):
         prio_cpu = [(k, cpu.get(k)) for k in ("value", "unit", "cores", "kind", "sample", "admm_iters_per_sec", "cpus_visible", "threads_used", "error")]
         prio_cpu.append(("gemv_stream_GBps", cpu.get("achieved_gemv_stream_GBps")))
         o["cpu_baseline"] = _take(prio_cpu, None)
+
+
+DUMP_MAX_BYTES = 60 * 10 ** 6          # --dump-outputs: under 64 MB in all, .npy headers included
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: the arrays the timed path returned in its last step, one DIR/<name>.npy each, float64 (float32 for the f32
+    path); complex arrays gain a trailing axis of length 2 (re, im).  An output beyond its share of the 64 MB budget is replaced by a
+    fixed, seeded sample of its flat elements (<name>.npy) and the flat indices of that sample (<name>_index.npy)."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if np.iscomplexobj(a):
+            a = np.stack([a.real, a.imag], axis=-1)
+        arrs[name] = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+    share = DUMP_MAX_BYTES // max(1, len(arrs))
+    for name, a in arrs.items():
+        if a.nbytes > share:
+            keep = share // (a.itemsize + 8)
+            idx = np.sort(np.random.default_rng(0x1B5EC).choice(a.size, size=keep, replace=False))
+            np.save(os.path.join(path, name + "_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def synth_signal(N, Nf, seed, device):
@@ -466,6 +494,8 @@ def main():
     ap.add_argument("--row-sharded", action="store_true",
                     help="strong-scaling variant: one signal per step, its sample rows sharded over the ranks (one all-reduce of the Gram)")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal only: map every rank onto the visible GPUs modulo their count")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the workload's last timed step returned as DIR/<name>.npy (rank 0; same inputs every run)")
     args = ap.parse_args()
     if args.cpu_baseline_child:                           # the CPU port in a child of its own (pinned OpenMP threads); never touches the GPU
         _cpu_child(args.cpu_baseline_child)
@@ -548,14 +578,12 @@ def main():
         os._exit(args.watchdog_exit_code if (rank != 0 or state["printed"]) else 1)
 
     timer = None
-    if args.workload == "cfg4":
-        state["out"] = run_cfg4(L, args, world, rank, local, dev, cdev, dist, sync, max_over_ranks)
-    elif args.workload == "cfg2":
-        state["out"] = run_cfg2(L, args, world, rank, local, dev, cdev, dist, sync, max_over_ranks)
-    elif args.workload == "cfg5":
-        state["out"] = run_cfg5(L, args, world, rank, local, dev, cdev, dist, sync, max_over_ranks)
-    else:
-        state["out"] = run_cfg3(L, args, world, rank, local, dev, cdev, dist, sync, max_over_ranks)
+    run_main = {"cfg4": run_cfg4, "cfg2": run_cfg2, "cfg5": run_cfg5}.get(args.workload, run_cfg3)
+    state["out"] = run_main(L, args, world, rank, local, dev, cdev, dist, sync, max_over_ranks)
+    outputs = state["out"].pop("_outputs") if rank == 0 else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
+    if args.workload == "cfg3":
         timer = threading.Timer(args.sub_timeout, watchdog)
         timer.daemon = True
         timer.start()
@@ -869,14 +897,14 @@ def run_cfg4(L, args, world, rank, local, dev, cdev, dist, sync, max_over_ranks)
                                                     win_lo=lo, win_hi=hi, device=local)
         full = L.sharding.gather_units(x, nwin, dist, cdev)   # ONE all_gather of the per-window coefficients (RCCL)
         S = L.sharding.reduce_psd_in_order(full)              # S .+= abs2.(x) in window order, / k^2   src/lsfft.jl:122,125
-        return S, its
+        return S, its, full
 
     for _ in range(warmup):
         step()
     sync()
     t0 = time.perf_counter()
     for _ in range(steps):
-        S, its = step()
+        S, its, x = step()
     sync()
     elapsed = max_over_ranks(time.perf_counter() - t0)
     tm = L.windowpsd_last_timing()
@@ -944,6 +972,7 @@ def run_cfg4(L, args, world, rank, local, dev, cdev, dist, sync, max_over_ranks)
         "phase_ms_rank0": {k: v for k, v in tm.items() if k.endswith("_ms")},
         "psd_argmax": int(np.argmax(S)), "iters_min_max": [int(its.min()), int(its.max())],
         "roofline": roof,
+        "_outputs": {"psd": S, "coefficients": x, "iterations": np.asarray(its, dtype=np.float64)},   # (popped by main(): --dump-outputs)
     }
     if world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = guarded(cpu_baseline_cfg4, "cpu_baseline")
@@ -1001,6 +1030,9 @@ def run_cfg3(L, args, world, rank, local, dev, cdev, dist, sync, max_over_ranks)
     elapsed = max_over_ranks(time.perf_counter() - t0)
     if rank != 0:
         return None
+    # what the last timed step returned: the coefficients (every rank's, in rank order, when they were gathered), iterations, final |x - z|
+    outputs = {"params": np.stack([a.cpu().numpy() for a in allp]) if (dist is not None and not rowsh) else params,
+               "iterations": np.array([it], dtype=np.float64), "nxz": np.array([nxz], dtype=np.float64)}
 
     phase = {k: float(np.mean([t[k] for t in tms])) for k in ("basis_ms", "gram_ms", "reduce_rhs_ms", "factor_ms", "admm_ms", "xcorr_ms")}
     n_xcorr = int(tms[0].get("xcorr_count", 0))
@@ -1180,6 +1212,7 @@ def run_cfg3(L, args, world, rank, local, dev, cdev, dist, sync, max_over_ranks)
                              "the library's stream" % mv_info["bytes_formula"]},
         "gram_general_path": general,
         "_params_rank0": np.asarray(params).ravel() if (params is not None and not rowsh) else None,   # (popped by main(): the single-process record compares with it)
+        "_outputs": outputs,                                                                             # (popped by main(): --dump-outputs)
     }
     if world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = guarded(cpu_baseline, "cpu_baseline")
@@ -1297,6 +1330,8 @@ def run_cfg2(L, args, world, rank, local, dev, cdev, dist, sync, max_over_ranks,
                                 "dual update), replayed as hipGraph chunks of 50 iterations; iteration_us = HIP events around the ADMM loop / iterations; "
                                 "launch_us = the mat-vec alone, 500 back-to-back launches.  The floor is the dependent-kernel boundary "
                                 "(MI355X_MICROARCH.md: 1.2-1.9 us each), not the 8.4 MB the kernel reads."}}
+    if not sub:                                                        # (popped by main(): --dump-outputs)
+        out["_outputs"] = {"params": params, "iterations": np.array([it], dtype=np.float64), "nxz": np.array([nxz], dtype=np.float64)}
     if world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = guarded(cpu_baseline_cfg2, "cpu_baseline")
     return out
@@ -1391,6 +1426,9 @@ def run_cfg5(L, args, world, rank, local, dev, cdev, dist, sync, max_over_ranks,
                                 "for the column sums: ~34 + 270 MB at n = 32768); HIP events around 30 back-to-back launches on the library's stream; "
                                 "the same launch also issues n(n+128)/2 x %d signal columns x 2 products of f64 MFMA work; launch time varies by ~10 %% with the "
                                 "box and with where the 3.2 GB buffer landed (DESIGN.md 4.5.1)" % (info["bytes_formula"], info.get("signals_per_pass", 16))}}
+    if not sub:                                                        # (popped by main(): --dump-outputs); channels in rank order when gathered
+        out["_outputs"] = {"params": np.concatenate([a.cpu().numpy() for a in allp]) if dist is not None else params.T,
+                           "iterations": np.array([it], dtype=np.float64), "nxz": np.array([nxz], dtype=np.float64)}
     if world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = guarded(cpu_baseline_cfg5, "cpu_baseline")
     return out

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Extracts the positional / keyword names and default expressions of the reference's hot-path methods (src/lsfft.jl, src/lasso.jl,
-src/windows.jl of /root/reference) into tests/golden/reference_signatures.json -- data for the drop-in check of
-tests/test_julia_binding.py (names and defaults only; no source text).  Run where /root/reference exists."""
+src/windows.jl of a checkout of the reference package) into tests/golden/reference_signatures.json -- data for the drop-in check
+of tests/test_julia_binding.py (names and defaults only; no source text).  Run by hand when the reference changes:
+    python tests/golden/make_reference_signatures.py PATH/TO/LPVSpectral.jl"""
 import json
 import os
 import sys
@@ -10,13 +11,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 from _jlsig import HOT_PATH_FUNCTIONS, parse_methods   # noqa: E402
 
-REF = os.environ.get("LPVS_REFERENCE", "/root/reference")
 
-
-def extract():
+def extract(ref):
     out = {}
     for rel in ("src/lsfft.jl", "src/lasso.jl", "src/windows.jl"):
-        src = open(os.path.join(REF, rel)).read()
+        src = open(os.path.join(ref, rel)).read()
         for name, methods in parse_methods(src, HOT_PATH_FUNCTIONS).items():
             for m in methods:
                 out.setdefault(name, []).append(dict(file=rel, pos=m["pos"], kw=m["kw"], varkw=m["varkw"]))
@@ -24,6 +23,9 @@ def extract():
 
 
 if __name__ == "__main__":
+    if len(sys.argv) != 2:
+        raise SystemExit(__doc__)
+    sigs = extract(sys.argv[1])
     with open(os.path.join(HERE, "reference_signatures.json"), "w") as fh:
-        json.dump(extract(), fh, indent=1, ensure_ascii=False, sort_keys=True)
+        json.dump(sigs, fh, indent=1, ensure_ascii=False, sort_keys=True)
     print("wrote reference_signatures.json")

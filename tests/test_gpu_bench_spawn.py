@@ -186,3 +186,41 @@ def test_driver_record_fits_the_parser_and_carries_every_configuration():
     bench.driver_record(o2)
     assert o2["config"]["sub_record_errors"] == 1 and o2["config"]["first_error"].startswith("cfg5: OutOfMemory") and len(o2["config"]["first_error"]) <= 120
     _fits_the_drivers_parser(o2)
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path, monkeypatch):
+    """(CPU test.)  bench.dump_outputs: complex arrays become float64 [..., 2] (re, im), float32 stays float32, and an output beyond its share of
+    the budget is replaced by the same seeded sample of its flat elements on every call, with the flat indices beside it."""
+    sys.path.insert(0, ROOT)
+    import bench
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 3 * 4096)
+    big = np.arange(4096, dtype=np.float64)
+    arrays = {"params": np.array([1 + 2j, 3 - 4j]), "single": np.ones(3, dtype=np.float32), "big": big}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    p = np.load(tmp_path / "a" / "params.npy")
+    assert p.dtype == np.float64 and p.tolist() == [[1.0, 2.0], [3.0, -4.0]]
+    assert np.load(tmp_path / "a" / "single.npy").dtype == np.float32
+    assert not (tmp_path / "a" / "params_index.npy").exists()
+    b, idx = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "a" / "big_index.npy")
+    assert b.size == 256 and np.array_equal(b, big[idx.astype(np.int64)]) and np.all(np.diff(idx) > 0)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= bench.DUMP_MAX_BYTES + 8 * 128
+    for f in (tmp_path / "a").iterdir():
+        assert np.array_equal(np.load(f), np.load(tmp_path / "b" / f.name)), f.name
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_timed_steps_results_and_repeat(tmp_path):
+    """--dump-outputs DIR: the last timed step's coefficients, iteration count and |x - z| as .npy files; --steps sets the number of timed steps;
+    two runs with the same arguments write the same arrays."""
+    import numpy as np
+    args = ["--log2n", "16", "--iters", "60", "--steps", "3", "--no-general-path", "--no-alt-storage", "--no-concurrent"]
+    recs = [_run1(args + ["--dump-outputs", str(tmp_path / d)]) for d in ("a", "b")]
+    assert all(r["steps"] == 3 and r["ms_per_step"] > 0 for r in recs)
+    assert sorted(f.name for f in (tmp_path / "a").iterdir()) == ["iterations.npy", "nxz.npy", "params.npy"]
+    p = np.load(tmp_path / "a" / "params.npy")
+    assert p.dtype == np.float64 and p.shape == (512 * 8, 2) and np.count_nonzero(p) > 0
+    assert np.load(tmp_path / "a" / "iterations.npy").tolist() == [60.0]
+    for name in ("params.npy", "iterations.npy", "nxz.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)), name
