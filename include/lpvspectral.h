@@ -492,6 +492,32 @@ int32_t lpvs_windowcsd_f64(const double *y, const double *u, const double *t, in
  * error's systematic part leaves the iteration with the inverse's) */
 int32_t lpvs_admm_matvec_kind(lpvs_problem *h, int32_t *kind);
 
+/* ---- g1  autocov / autocor of a signal sampled at arbitrary times t                     src/autocov.jl
+ * isequidistant (src/autocov.jl:112-121): t[1] - t[0] > 0 and abs(abs(t[i]-t[i-1]) - d) < 20d*eps() for every i, eps() of Float64.
+ * N < 2 -> LPVS_EARGUMENT (the reference reads t[2]).  A device t is tested on its device, a host t on the host.
+ *
+ * lpvs_autofun: the nseg segments [seg_off[s], seg_off[s+1]) of t and y (seg_off: HOST, nseg+1 entries, seg_off[0] = 0, every segment
+ * at least 2 samples) each take their own branch -- equidistant (src/autocov.jl:37-100: acf of the index lag j, lag sums accumulated
+ * in double) or not (src/autocov.jl:125-175: y_i y_{i+j}, divided by var(y) for autocor, 1 where tau == 0) -- with the degenerate
+ * rules (zeros / ones) of each.  Every pair (i, j >= 0, i+j < n) with NOT (tau > maxlag), tau = |t[i+j]-t[i]| in the eltype of t,
+ * is returned, stably sorted by tau: the order of (tau, segment, enumeration index) that src/autocov.jl:1-12 produces (NaN maxlag
+ * keeps every pair; NaN tau sorts last, as one canonical NaN).  normalize is used by the equidistant branch only.
+ * Count protocol of lpvs_window_offsets: *count (HOST) is always set; tau_out = acf_out = NULL counts only; capacity < count ->
+ * LPVS_EARGUMENT and nothing written.  Outputs (count elements each) may be host or device memory.  Output plus scratch that does not
+ * fit in free device memory -> LPVS_ENOMEM (the pair count is in the message).  The _f32 twins take float t / y and return float tau /
+ * acf (tau computed in float; lag sums and statistics in double). */
+#define LPVS_ACF_COV 1
+#define LPVS_ACF_COR 2
+int32_t lpvs_isequidistant_f64(const double *t, int64_t N, int32_t *equidistant);
+int32_t lpvs_isequidistant_f32(const float *t, int64_t N, int32_t *equidistant);
+int32_t lpvs_autofun_f64(int32_t kind, const double *t, const double *y, const int64_t *seg_off, int64_t nseg, double maxlag,
+                         int32_t normalize, int32_t device, double *tau_out, double *acf_out, int64_t capacity, int64_t *count);
+int32_t lpvs_autofun_f32(int32_t kind, const float *t, const float *y, const int64_t *seg_off, int64_t nseg, double maxlag,
+                         int32_t normalize, int32_t device, float *tau_out, float *acf_out, int64_t capacity, int64_t *count);
+/* HIP-event phase times (ms) of the calling thread's last lpvs_autofun call, out[0..7]: statistics + row counts + scan (inputs
+ * uploaded), lag sums + generation, sort, copy-out, total, pairs, sort passes, bytes per key */
+int32_t lpvs_autofun_last_timing(double *out, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif

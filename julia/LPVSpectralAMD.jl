@@ -18,7 +18,7 @@ const PO = ProximalOperators
 
 export ls_spectral, tls_spectral, ls_sparse_spectral, ls_sparse_spectral_lpv, ls_spectral_lpv, ls_windowpsd, ls_windowcsd,
        ls_cohere, ls_windowpsd_lpv, get_fourier_regressor, check_freq, default_freqs, Windows2, Windows3, mapwindows,
-       SpectralExt, psd, reshape_params, ADMM, rect, hanning
+       SpectralExt, psd, reshape_params, ADMM, rect, hanning, autocov, autocor, isequidistant
 
 const LIB = get(ENV, "LPVSPECTRAL_LIB", joinpath(@__DIR__, "..", "lpvspectral.jl_amd", "liblpvspectral.so"))
 
@@ -693,5 +693,60 @@ function ls_windowpsd_lpv(Y::AbstractVector, X::AbstractVector, V::AbstractVecto
     end
     S
 end
+
+# ---- autocov / autocor at arbitrary sample times: src/autocov.jl (pairs, lag sums and the stable sort on the device) ----------
+# Methods of this module's own functions (StatsBase's autocov(y) is not extended here: call LPVSpectralAMD.autocov when both are loaded).
+isequidistant(v::AbstractRange) = step(v) > 0                                         # src/autocov.jl:112
+function isequidistant(v::AbstractVector{<:Real})                                     # src/autocov.jl:113-121
+    eq = Ref{Int32}(0)
+    if eltype(v) == Float32
+        v32 = Vector{Float32}(v)
+        GC.@preserve v32 check(@ccall LIB.lpvs_isequidistant_f32(v32::Ptr{Float32}, Int64(length(v32))::Int64, eq::Ref{Int32})::Int32)
+    else
+        v64 = Vector{Float64}(v)
+        GC.@preserve v64 check(@ccall LIB.lpvs_isequidistant_f64(v64::Ptr{Float64}, Int64(length(v64))::Int64, eq::Ref{Int32})::Int32)
+    end
+    eq[] != 0
+end
+
+# all segments in one call: the stable sort of (tau, segment, enumeration index) is what src/autocov.jl:1-12 returns
+function _autofun(kind::Int32, t::AbstractVector, h::AbstractVector, maxlag::Real, normalize::Bool; device::Integer=0)
+    length(t) == length(h) || throw(ArgumentError("t has $(length(t)) segments, y has $(length(h))"))
+    all(length.(t) .== length.(h)) || throw(ArgumentError("t and y must be the same length"))   # src/autocov.jl:40
+    tT = mapreduce(eltype, promote_type, t); yT = mapreduce(eltype, promote_type, h)
+    f32 = tT == Float32 && yT == Float32
+    off = Int64[0; cumsum(Int64.(length.(h)))]
+    nseg = Int64(length(h)); n = Ref{Int64}(0)
+    if f32
+        t32 = Vector{Float32}(reduce(vcat, collect.(t))); y32 = Vector{Float32}(reduce(vcat, h))
+        GC.@preserve t32 y32 off check(@ccall LIB.lpvs_autofun_f32(kind::Int32, t32::Ptr{Float32}, y32::Ptr{Float32}, off::Ptr{Int64}, nseg::Int64,
+            Float64(maxlag)::Float64, Int32(normalize)::Int32, Int32(device)::Int32, C_NULL::Ptr{Float32}, C_NULL::Ptr{Float32}, Int64(0)::Int64,
+            n::Ref{Int64})::Int32)
+        tau32 = Vector{Float32}(undef, n[]); acf32 = Vector{Float32}(undef, n[])
+        GC.@preserve t32 y32 off tau32 acf32 check(@ccall LIB.lpvs_autofun_f32(kind::Int32, t32::Ptr{Float32}, y32::Ptr{Float32}, off::Ptr{Int64},
+            nseg::Int64, Float64(maxlag)::Float64, Int32(normalize)::Int32, Int32(device)::Int32, tau32::Ptr{Float32}, acf32::Ptr{Float32},
+            Int64(length(tau32))::Int64, n::Ref{Int64})::Int32)
+        return tau32, acf32
+    end
+    tT == Float32 && throw(ArgumentError("Float32 times with $(yT) values: pass both as Float32 or both as Float64"))
+    t64 = Vector{Float64}(reduce(vcat, collect.(t))); y64 = Vector{Float64}(reduce(vcat, h))   # integer times: exact for |t| < 2^52
+    GC.@preserve t64 y64 off check(@ccall LIB.lpvs_autofun_f64(kind::Int32, t64::Ptr{Float64}, y64::Ptr{Float64}, off::Ptr{Int64}, nseg::Int64,
+        Float64(maxlag)::Float64, Int32(normalize)::Int32, Int32(device)::Int32, C_NULL::Ptr{Float64}, C_NULL::Ptr{Float64}, Int64(0)::Int64,
+        n::Ref{Int64})::Int32)
+    tau64 = Vector{Float64}(undef, n[]); acf64 = Vector{Float64}(undef, n[])
+    GC.@preserve t64 y64 off tau64 acf64 check(@ccall LIB.lpvs_autofun_f64(kind::Int32, t64::Ptr{Float64}, y64::Ptr{Float64}, off::Ptr{Int64},
+        nseg::Int64, Float64(maxlag)::Float64, Int32(normalize)::Int32, Int32(device)::Int32, tau64::Ptr{Float64}, acf64::Ptr{Float64},
+        Int64(length(tau64))::Int64, n::Ref{Int64})::Int32)
+    tT <: Integer ? round.(tT, tau64) : convert(Vector{tT}, tau64), convert(Vector{yT <: AbstractFloat ? yT : Float64}, acf64)
+end
+
+autocov(t::AbstractVector{<:Real}, y::AbstractVector{<:Real}, maxlag::Real; normalize=false, device=0) =       # src/autocov.jl:35
+    _autofun(Int32(1), [t], [y], maxlag, Bool(normalize); device=device)
+autocor(t::AbstractVector{<:Real}, y::AbstractVector{<:Real}, maxlag::Real; normalize=false, device=0) =       # src/autocov.jl:78
+    _autofun(Int32(2), [t], [y], maxlag, Bool(normalize); device=device)
+autocov(t::AbstractVector, h::AbstractVector{<:AbstractVector{<:Real}}, maxlag::Real; normalize=false, device=0) =   # src/autocov.jl:15
+    _autofun(Int32(1), t, h, maxlag, Bool(normalize); device=device)
+autocor(t::AbstractVector, h::AbstractVector{<:AbstractVector{<:Real}}, maxlag::Real; normalize=false, device=0) =   # src/autocov.jl:16
+    _autofun(Int32(2), t, h, maxlag, Bool(normalize); device=device)
 
 end # module

@@ -22,6 +22,7 @@ LPVS_EDEVICE, LPVS_EUNSUPPORTED, LPVS_ENUMERIC, LPVS_ESTATE = -5, -6, -7, -8
 PROX_L1, PROX_L0, PROX_BALL_L0, PROX_GROUP_L2 = 1, 2, 3, 4
 LINEAR_LEAST_SQUARES, LINEAR_QUADRATIC_AS_WRITTEN = 1, -1
 EST_SPARSE, EST_DENSE, EST_SPARSE_INIT = 1, 2, 3
+ACF_COV, ACF_COR = 1, 2
 # options (include/lpvspectral.h LPVS_OPT_*): name -> (option id, {value name -> value}); None / "default" = 0
 OPTIONS = {
     "storage": (1, {"mixed": 1, "split": 2, "f64": 3, "mixed32": 4}),
@@ -152,6 +153,11 @@ SIGNATURES = {
     "lpvs_window_count": (_I32, [_I64, _I64, _I64, _PI64]),
     "lpvs_window_offsets": (_I32, [_I64, _I64, _I64, _P, _I64, _PI64]),
     "lpvs_merge_f64": (_I32, [_P, _I64, _I64, _I64, _I64, _P]),
+    "lpvs_isequidistant_f64": (_I32, [_P, _I64, C.POINTER(_I32)]),
+    "lpvs_isequidistant_f32": (_I32, [_P, _I64, C.POINTER(_I32)]),
+    "lpvs_autofun_f64": (_I32, [_I32, _P, _P, _P, _I64, _F64, _I32, _I32, _P, _P, _I64, _PI64]),
+    "lpvs_autofun_f32": (_I32, [_I32, _P, _P, _P, _I64, _F64, _I32, _I32, _P, _P, _I64, _PI64]),
+    "lpvs_autofun_last_timing": (_I32, [_P, _I32]),
 }
 
 _lib = None

@@ -1266,3 +1266,147 @@ def ls_windowpsd_lpv(Y, X, V, w, Nv, nw=10, noverlap=0, in_flight=4, **kwargs):
         rp = reshape_params(se.x, len(w))
         S = S + abs2(rp.sum(axis=1))
     return S
+
+
+# --------------------------------------------------------------------------- autocov / autocor at arbitrary sample times (src/autocov.jl)
+_EXACT_INT = 2 ** 52   # integer times are carried as float64: |t| < 2^52 keeps t and every difference exact
+
+
+def _is_torch(a):
+    return hasattr(a, "data_ptr") and hasattr(a, "dtype") and hasattr(a, "is_cuda")
+
+
+def _time_kind(t):
+    """'int' (a range or integer times: tau is int64), 'f32' or 'f64'."""
+    if isinstance(t, range):
+        return "int"
+    if _is_torch(t):
+        import torch
+        return "f32" if t.dtype == torch.float32 else ("f64" if t.dtype.is_floating_point else "int")
+    a = np.asarray(t)
+    return "f32" if a.dtype == np.float32 else ("int" if a.dtype.kind in "iub" else "f64")
+
+
+def _value_kind(y):
+    if _is_torch(y):
+        import torch
+        return "f32" if y.dtype == torch.float32 else "f64"
+    return "f32" if np.asarray(y).dtype == np.float32 else "f64"
+
+
+def _is_segmented(y):
+    """The vector-of-vectors form (src/autocov.jl:1-16): a list / tuple of signals."""
+    return isinstance(y, (list, tuple)) and len(y) > 0 and (isinstance(y[0], (list, tuple, range, np.ndarray)) or _is_torch(y[0]))
+
+
+def isequidistant(t):
+    """src/autocov.jl:112-121.  A ``range`` is equidistant iff its step is positive; a vector iff ``d = t[1]-t[0] > 0`` and
+    ``abs(abs(t[i]-t[i-1]) - d) < 20d*eps()`` for every i (eps of Float64).  Fewer than 2 samples: ValueError."""
+    if isinstance(t, range):
+        return t.step > 0
+    out = C.c_int32(0)
+    if _time_kind(t) == "f32":
+        kt, pt, N = as_f32(t)
+        check(lib().lpvs_isequidistant_f32(pt, N, C.byref(out)))
+    else:
+        kt, pt, N = as_f64(t)
+        check(lib().lpvs_isequidistant_f64(pt, N, C.byref(out)))
+    return bool(out.value)
+
+
+def _segment_vec(a, kind, dev):
+    """One segment as a contiguous 1-D array of the computing eltype (float32 / float64), on the device when dev is set."""
+    if isinstance(a, range):
+        a = np.arange(a.start, a.stop, a.step, dtype=np.int64)
+    if _is_torch(a):
+        import torch
+        v = a.reshape(-1).to(torch.float32 if kind == "f32" else torch.float64)
+        return v.to(f"cuda:{dev}") if dev is not None else v.cpu().numpy()
+    v = np.ravel(np.asarray(a)).astype(np.float32 if kind == "f32" else np.float64)
+    if dev is not None:
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(v)).to(f"cuda:{dev}")
+    return np.ascontiguousarray(v)
+
+
+def _autofun(kind, t, y, maxlag, normalize, device):
+    segmented = _is_segmented(y)
+    ts, ys = (list(t), list(y)) if segmented else ([t], [y])
+    if len(ts) != len(ys):
+        raise ValueError(f"t has {len(ts)} segments, y has {len(ys)}")
+    for a, b in zip(ts, ys):
+        if len(a) != len(b):
+            raise ValueError("t and y must be the same length")        # src/autocov.jl:40
+    tk = {_time_kind(a) for a in ts}
+    yk = {_value_kind(b) for b in ys}
+    t_kind = "int" if tk == {"int"} else ("f32" if tk == {"f32"} else "f64")   # vcat's promotion of the segments' tau
+    y_kind = "f32" if yk == {"f32"} else "f64"
+    if t_kind == "f32" and y_kind != "f32":
+        raise TypeError("float32 times with float64 values: pass both as float32 or both as float64")
+    if t_kind == "int":
+        for a in ts:
+            if len(a) and max(abs(int(min(a))), abs(int(max(a)))) >= _EXACT_INT:
+                raise ValueError("integer sample times must satisfy |t| < 2^52")
+    ckind = "f32" if t_kind == "f32" else "f64"
+    on_dev = any(_is_torch(a) and a.is_cuda for a in ts + ys)
+    dev = next(a.device.index for a in ts + ys if _is_torch(a) and a.is_cuda) if on_dev else None
+    lens = [len(a) for a in ts]
+    seg_off = np.zeros(len(lens) + 1, dtype=np.int64)
+    seg_off[1:] = np.cumsum(lens)
+    tv = [_segment_vec(a, ckind, dev) for a in ts]
+    yv = [_segment_vec(b, ckind, dev) for b in ys]
+    if on_dev:
+        import torch
+        tc, yc = torch.cat(tv), torch.cat(yv)
+        torch.cuda.current_stream(tc.device).synchronize()
+        pt, py = C.c_void_p(tc.data_ptr()), C.c_void_p(yc.data_ptr())
+        device = dev
+    else:
+        tc, yc = np.concatenate(tv), np.concatenate(yv)
+        pt, py = out_ptr(tc), out_ptr(yc)
+    fn = lib().lpvs_autofun_f32 if ckind == "f32" else lib().lpvs_autofun_f64
+    n = C.c_int64(0)
+    ml = float(maxlag)
+    args = (kind, pt, py, out_ptr(seg_off), len(lens), ml, int(bool(normalize)), int(device))
+    check(fn(*args, None, None, 0, C.byref(n)))                        # count only
+    P = int(n.value)
+    if on_dev:
+        import torch
+        dt = torch.float32 if ckind == "f32" else torch.float64
+        tau, acf = torch.empty(P, dtype=dt, device=tc.device), torch.empty(P, dtype=dt, device=tc.device)
+        check(fn(*args, C.c_void_p(tau.data_ptr()), C.c_void_p(acf.data_ptr()), P, C.byref(n)))
+        if t_kind == "int":
+            tau = tau.to(torch.int64)
+        if y_kind == "f32":
+            acf = acf.to(torch.float32)
+        return tau, acf
+    dt = np.float32 if ckind == "f32" else np.float64
+    tau, acf = np.empty(P, dtype=dt), np.empty(P, dtype=dt)
+    check(fn(*args, out_ptr(tau), out_ptr(acf), P, C.byref(n)))
+    if t_kind == "int":
+        tau = tau.astype(np.int64)
+    if y_kind == "f32":
+        acf = acf.astype(np.float32)
+    return tau, acf
+
+
+def autocov(t, y, maxlag, normalize=False, device=0):
+    """src/autocov.jl:35-56, :125-147 -> ``(τ, acf)``: the autocovariance of ``y`` sampled at times ``t`` over every sample pair
+    with ``|t[i+j]-t[i]| <= maxlag``, sorted by τ (stable).  ``t`` / ``y`` may be arrays, ``range``s (t), or lists of segments (the
+    vector-of-vectors form, src/autocov.jl:1-16).  τ has the eltype of ``t`` (int64 for integer times), acf that of ``y``.  Device
+    (torch CUDA) inputs give device tensors; host inputs give numpy arrays."""
+    return _autofun(_lib.ACF_COV, t, y, maxlag, normalize, device)
+
+
+def autocor(t, y, maxlag, normalize=False, device=0):
+    """src/autocov.jl:78-100, :149-176: as :func:`autocov`, normalised (by dot(y,y) on the equidistant branch, by var(y) otherwise)."""
+    return _autofun(_lib.ACF_COR, t, y, maxlag, normalize, device)
+
+
+def autofun_last_timing():
+    """HIP-event phase times (ms) of this thread's last autocov / autocor call (the last of its two library calls: the one that wrote
+    the outputs)."""
+    o = np.zeros(8)
+    check(lib().lpvs_autofun_last_timing(out_ptr(o), 8))
+    return dict(count_ms=o[0], generate_ms=o[1], sort_ms=o[2], copy_out_ms=o[3], total_ms=o[4], pairs=int(o[5]), sort_passes=int(o[6]),
+                key_bytes=int(o[7]))
