@@ -518,6 +518,45 @@ int32_t lpvs_autofun_f32(int32_t kind, const float *t, const float *y, const int
  * uploaded), lag sums + generation, sort, copy-out, total, pairs, sort passes, bytes per key */
 int32_t lpvs_autofun_last_timing(double *out, int32_t n);
 
+/* ---- g2  spectrogram / melspectrogram / mfcc                                       DSP.spectrogram, src/mel.jl
+ * Host-only helpers, the reference's precision (Float32 unless Julia's promotion widens it):
+ *   lpvs_nextfastfft: the smallest 2*3*5*7-smooth integer >= n (1 for n <= 1).
+ *   lpvs_mel_filterbank (src/mel.jl:99-113): W, nmels x (nfft>>1)+1 floats, column-major.  wide bit0: fs was Float64 (the FFT grid is
+ *     Float64), bit1 / bit2: fmin / fmax were Float64 (the mel grid is Float64); otherwise Int / Float32 arithmetic in Float32.
+ *   lpvs_dct_matrix (src/mel.jl dct_matrix): D, nfilters x ninput floats, column-major, rows cos(i (1:2:2ninput) pi / 2ninput)
+ *     sqrt(2/ninput), i = 1 .. nfilters (no DC row).
+ * lpvs_stft: the frames of DSP.arraysplit (k = L >= n ? (L-n)/(n-noverlap) + 1 : 0; 0 <= noverlap < n else LPVS_EDOMAIN, nfft >= n),
+ * windowed (window: n values or NULL), zero-padded to nfft, one-sided power with r = fs * sum(window.^2) (fs * n without a window):
+ * row 0 |X_0|^2/r, rows 1 .. nfft/2-1 2|X_k|^2/r, the last row |X|^2/r for even nfft and 2|X|^2/r for odd.  Then by kind:
+ *   LPVS_STFT_POWER  out = power, (nfft/2+1) x k;
+ *   LPVS_STFT_MEL    out = W * power, nmels x k (W: nmels x (nfft/2+1), each band summed over its contiguous bins in ascending order;
+ *                    a frame whose power holds a non-finite value is NaN in every band -- the reference's dense product);
+ *   LPVS_STFT_MFCC   out = D * (W * power), each column divided by its 2-norm, nmfcc x k (no log; a zero column gives NaN).
+ * All outputs column-major (rows x frames).  Count protocol of lpvs_window_offsets: *nframes (HOST) is always set, out = NULL counts
+ * only, capacity < rows * k -> LPVS_EARGUMENT.  s, window, out may be host or device memory; W and D are host or device floats.
+ * nfft: 7-smooth up to 8192 in LDS, 7-smooth above by a four-step FFT, any other by Bluestein; nfft (or its Bluestein length) beyond
+ * 2^26 -> LPVS_EUNSUPPORTED.  Device arithmetic is double (the _f32 twins: float s / window / out); outputs plus the minimum scratch
+ * that do not fit -> LPVS_ENOMEM.
+ * lpvs_mel_project: out = W * power for a power matrix that already exists (nbins x frames, host or device), nmels x frames. */
+#define LPVS_STFT_POWER 1
+#define LPVS_STFT_MEL 2
+#define LPVS_STFT_MFCC 3
+int32_t lpvs_nextfastfft(int64_t n, int64_t *nfft);
+int32_t lpvs_mel_filterbank(double fs, int64_t nfft, int64_t nmels, double fmin, double fmax, int32_t wide, float *W);
+int32_t lpvs_dct_matrix(int64_t nfilters, int64_t ninput, float *D);
+int32_t lpvs_stft_f64(int32_t kind, const double *s, int64_t L, int64_t n, int64_t noverlap, int64_t nfft, double fs, const double *window,
+                      const float *W, int64_t nmels, const float *D, int64_t nmfcc, int32_t device, double *out, int64_t capacity,
+                      int64_t *nframes);
+int32_t lpvs_stft_f32(int32_t kind, const float *s, int64_t L, int64_t n, int64_t noverlap, int64_t nfft, double fs, const float *window,
+                      const float *W, int64_t nmels, const float *D, int64_t nmfcc, int32_t device, float *out, int64_t capacity,
+                      int64_t *nframes);
+int32_t lpvs_mel_project_f64(const double *power, int64_t nbins, int64_t frames, const float *W, int64_t nmels, int32_t device, double *out);
+int32_t lpvs_mel_project_f32(const float *power, int64_t nbins, int64_t frames, const float *W, int64_t nmels, int32_t device, float *out);
+/* HIP-event times (ms) of the calling thread's last lpvs_stft call, out[0..8]: device work (Bluestein kernel, frame flags, FFTs,
+ * epilogue), copy-out, total (setup + device work + copy-out), frames, path (1 LDS, 2 four-step, 3 Bluestein in LDS, 4 Bluestein
+ * four-step), FFT length, frame pairs per workgroup, output rows, setup (host tables, band ranges, uploads) */
+int32_t lpvs_stft_last_timing(double *out, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,8 @@ const PO = ProximalOperators
 
 export ls_spectral, tls_spectral, ls_sparse_spectral, ls_sparse_spectral_lpv, ls_spectral_lpv, ls_windowpsd, ls_windowcsd,
        ls_cohere, ls_windowpsd_lpv, get_fourier_regressor, check_freq, default_freqs, Windows2, Windows3, mapwindows,
-       SpectralExt, psd, reshape_params, ADMM, rect, hanning, autocov, autocor, isequidistant
+       SpectralExt, psd, reshape_params, ADMM, rect, hanning, autocov, autocor, isequidistant,
+       melspectrogram, mfcc, mel, spectrogram, Spectrogram, MelSpectrogram, MFCC, freq
 
 const LIB = get(ENV, "LPVSPECTRAL_LIB", joinpath(@__DIR__, "..", "lpvspectral.jl_amd", "liblpvspectral.so"))
 
@@ -748,5 +749,129 @@ autocov(t::AbstractVector, h::AbstractVector{<:AbstractVector{<:Real}}, maxlag::
     _autofun(Int32(1), t, h, maxlag, Bool(normalize); device=device)
 autocor(t::AbstractVector, h::AbstractVector{<:AbstractVector{<:Real}}, maxlag::Real; normalize=false, device=0) =   # src/autocov.jl:16
     _autofun(Int32(2), t, h, maxlag, Bool(normalize); device=device)
+
+# ---- spectrogram / melspectrogram / mfcc: DSP.spectrogram + src/mel.jl (STFT, mel bands and MFCC on the device) ----------------
+# The filterbank and the DCT come from the library (host C, the reference's precision); the STFT and its epilogues run on the device.
+struct Spectrogram{T,F,Ti}
+    power::Matrix{T}
+    freq::F
+    time::Ti
+end
+struct MelSpectrogram{T,F,Ti}
+    power::Matrix{T}
+    mels::F
+    time::Ti
+end
+struct MFCC{T,F,Ti}
+    mfcc::Matrix{T}
+    number::F
+    time::Ti
+end
+freq(S::Spectrogram) = S.freq
+freq(M::MelSpectrogram) = M.mels
+freq(M::MFCC) = M.number
+Base.time(S::Spectrogram) = S.time
+Base.time(M::MelSpectrogram) = M.time
+Base.time(M::MFCC) = M.time
+
+function _nextfastfft(n::Integer)
+    out = Ref{Int64}(0)
+    check(@ccall LIB.lpvs_nextfastfft(Int64(n)::Int64, out::Ref{Int64})::Int32)
+    Int(out[])
+end
+
+_hz_to_mel(f) = (m = f / (200f0 / 3); f >= 1000f0 ? (1000f0 / (200f0 / 3)) + log(f / 1000f0) / (log(6.4f0) / 27f0) : m)   # src/mel.jl:38-53
+
+function mel(fs::Real, nfft::Int; nmels::Int = 128, fmin::Real = 0f0, fmax::Real = fs/2f0)             # src/mel.jl:99-113
+    W = Matrix{Float32}(undef, nmels, (nfft >> 1) + 1)
+    wide = Int32((fs isa Float64 ? 1 : 0) | (fmin isa Float64 ? 2 : 0) | (fmax isa Float64 ? 4 : 0))
+    GC.@preserve W check(@ccall LIB.lpvs_mel_filterbank(Float64(fs)::Float64, Int64(nfft)::Int64, Int64(nmels)::Int64, Float64(fmin)::Float64,
+        Float64(fmax)::Float64, wide::Int32, W::Ptr{Float32})::Int32)
+    W
+end
+
+function dct_matrix(nfilters::Int, ninput::Int)                                                       # src/mel.jl dct_matrix
+    D = Matrix{Float32}(undef, nfilters, ninput)
+    GC.@preserve D check(@ccall LIB.lpvs_dct_matrix(Int64(nfilters)::Int64, Int64(ninput)::Int64, D::Ptr{Float32})::Int32)
+    D
+end
+
+# one STFT call: kind 1 power, 2 mel bands (W), 3 MFCC (W, D); Float32 signals take the _f32 entry point
+function _stft(kind::Int32, s::AbstractVector{<:Real}, n::Integer, noverlap::Integer, nfft::Integer, fs::Real, window, W, D; device::Integer=0)
+    nbins = nfft ÷ 2 + 1
+    rows = kind == 1 ? nbins : (kind == 2 ? size(W, 1) : size(D, 1))
+    Wv = W === nothing ? Float32[] : Matrix{Float32}(W)
+    Dv = D === nothing ? Float32[] : Matrix{Float32}(D)
+    nmels = Int64(W === nothing ? 0 : size(W, 1)); nmfcc = Int64(D === nothing ? 0 : size(D, 1))
+    k = Ref{Int64}(0)
+    if eltype(s) == Float32
+        sv = Vector{Float32}(s)
+        wv = window === nothing ? Float32[] : Vector{Float32}(window isa Function ? window(n) : window)
+        wp = window === nothing ? Ptr{Float32}(C_NULL) : pointer(wv)
+        GC.@preserve sv wv Wv Dv check(@ccall LIB.lpvs_stft_f32(kind::Int32, sv::Ptr{Float32}, Int64(length(sv))::Int64, Int64(n)::Int64,
+            Int64(noverlap)::Int64, Int64(nfft)::Int64, Float64(fs)::Float64, wp::Ptr{Float32}, Wv::Ptr{Float32}, nmels::Int64, Dv::Ptr{Float32},
+            nmfcc::Int64, Int32(device)::Int32, C_NULL::Ptr{Float32}, Int64(0)::Int64, k::Ref{Int64})::Int32)
+        out = Matrix{Float32}(undef, rows, k[])
+        GC.@preserve sv wv Wv Dv out check(@ccall LIB.lpvs_stft_f32(kind::Int32, sv::Ptr{Float32}, Int64(length(sv))::Int64, Int64(n)::Int64,
+            Int64(noverlap)::Int64, Int64(nfft)::Int64, Float64(fs)::Float64, wp::Ptr{Float32}, Wv::Ptr{Float32}, nmels::Int64, Dv::Ptr{Float32},
+            nmfcc::Int64, Int32(device)::Int32, out::Ptr{Float32}, Int64(length(out))::Int64, k::Ref{Int64})::Int32)
+    else
+        sv = Vector{Float64}(s)
+        wv = window === nothing ? Float64[] : Vector{Float64}(window isa Function ? window(n) : window)
+        wp = window === nothing ? Ptr{Float64}(C_NULL) : pointer(wv)
+        GC.@preserve sv wv Wv Dv check(@ccall LIB.lpvs_stft_f64(kind::Int32, sv::Ptr{Float64}, Int64(length(sv))::Int64, Int64(n)::Int64,
+            Int64(noverlap)::Int64, Int64(nfft)::Int64, Float64(fs)::Float64, wp::Ptr{Float64}, Wv::Ptr{Float32}, nmels::Int64, Dv::Ptr{Float32},
+            nmfcc::Int64, Int32(device)::Int32, C_NULL::Ptr{Float64}, Int64(0)::Int64, k::Ref{Int64})::Int32)
+        out = Matrix{Float64}(undef, rows, k[])
+        GC.@preserve sv wv Wv Dv out check(@ccall LIB.lpvs_stft_f64(kind::Int32, sv::Ptr{Float64}, Int64(length(sv))::Int64, Int64(n)::Int64,
+            Int64(noverlap)::Int64, Int64(nfft)::Int64, Float64(fs)::Float64, wp::Ptr{Float64}, Wv::Ptr{Float32}, nmels::Int64, Dv::Ptr{Float32},
+            nmfcc::Int64, Int32(device)::Int32, out::Ptr{Float64}, Int64(length(out))::Int64, k::Ref{Int64})::Int32)
+    end
+    out, ((0:k[]-1) .* (n - noverlap) .+ n / 2) ./ fs
+end
+
+function spectrogram(s::AbstractVector{<:Real}, n::Int = length(s) >> 3, noverlap::Int = n >> 1; nfft::Int = _nextfastfft(n), fs::Real = 1,
+                     window = nothing, device::Integer = 0)                                             # DSP.spectrogram (real s)
+    P, t = _stft(Int32(1), s, n, noverlap, nfft, fs, window, nothing, nothing; device=device)
+    Spectrogram(P, (0:nfft÷2) .* (fs / nfft), t)
+end
+
+function melspectrogram(S::Spectrogram; fs=1, nmels::Int = 128, fmin::Real = 0f0, fmax::Real = fs / 2f0, device::Integer = 0)   # src/mel.jl:133-138
+    nbins, frames = size(S.power)
+    W = mel(fs, 2nbins - 1; nmels=nmels, fmin=fmin, fmax=fmax)
+    if eltype(S.power) == Float32
+        P32 = Matrix{Float32}(S.power); out32 = Matrix{Float32}(undef, nmels, frames)
+        GC.@preserve P32 W out32 check(@ccall LIB.lpvs_mel_project_f32(P32::Ptr{Float32}, Int64(nbins)::Int64, Int64(frames)::Int64, W::Ptr{Float32},
+            Int64(nmels)::Int64, Int32(device)::Int32, out32::Ptr{Float32})::Int32)
+        return MelSpectrogram(out32, LinRange(_hz_to_mel(fmin), _hz_to_mel(fmax), nmels), S.time)
+    end
+    P64 = Matrix{Float64}(S.power); out64 = Matrix{Float64}(undef, nmels, frames)
+    GC.@preserve P64 W out64 check(@ccall LIB.lpvs_mel_project_f64(P64::Ptr{Float64}, Int64(nbins)::Int64, Int64(frames)::Int64, W::Ptr{Float32},
+        Int64(nmels)::Int64, Int32(device)::Int32, out64::Ptr{Float64})::Int32)
+    MelSpectrogram(out64, LinRange(_hz_to_mel(fmin), _hz_to_mel(fmax), nmels), S.time)
+end
+
+function melspectrogram(s, n=div(length(s), 8), args...; fs=1, nmels::Int = 128, fmin::Real = 0f0, fmax::Real = fs / 2f0, window=hanning,
+                        kwargs...)                                                                    # src/mel.jl:140-143, fused on the device
+    noverlap = isempty(args) ? get(kwargs, :noverlap, n >> 1) : args[1]
+    nfft = get(kwargs, :nfft, _nextfastfft(n))
+    device = get(kwargs, :device, 0)
+    W = mel(fs, 2(nfft ÷ 2 + 1) - 1; nmels=nmels, fmin=fmin, fmax=fmax)
+    P, t = _stft(Int32(2), s, n, noverlap, nfft, fs, window, W, nothing; device=device)
+    MelSpectrogram(P, LinRange(_hz_to_mel(fmin), _hz_to_mel(fmax), nmels), t)
+end
+
+function mfcc(s, args...; nmfcc::Int = 20, nmels::Int = 128, window=hanning, kwargs...)             # src/mel.jl:159-172
+    if nmfcc >= nmels
+        error("number of mfcc components should be less than the number of mel frequency bins")
+    end
+    n = isempty(args) ? div(length(s), 8) : args[1]
+    noverlap = length(args) > 1 ? args[2] : get(kwargs, :noverlap, n >> 1)
+    nfft = get(kwargs, :nfft, _nextfastfft(n)); fs = get(kwargs, :fs, 1)
+    fmin = get(kwargs, :fmin, 0f0); fmax = get(kwargs, :fmax, fs / 2f0); device = get(kwargs, :device, 0)
+    W = mel(fs, 2(nfft ÷ 2 + 1) - 1; nmels=nmels, fmin=fmin, fmax=fmax)
+    C, t = _stft(Int32(3), s, n, noverlap, nfft, fs, window, W, dct_matrix(nmfcc, nmels); device=device)
+    MFCC(C, 1:nmfcc, t)
+end
 
 end # module

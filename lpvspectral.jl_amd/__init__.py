@@ -9,7 +9,9 @@ from ._lib import DeviceError, DomainError, NumericError, lib as _load
 
 _load()  # fail loudly at import time if the HIP extension is missing
 
-from .api import (ADMM, Problem, autocor, autocov, autofun_last_timing, isequidistant, SpectralExt, basis_activation_func, check_freq, default_freqs,  # noqa: E402
+from .api import (MFCC, MelSpectrogram, Spectrogram, dct_matrix, fft_frequencies, freq, hz_to_mel, mel, mel_frequencies, mel_to_hz,  # noqa: E402
+                  melspectrogram, mfcc, nextfastfft, spectrogram, stft_last_timing, time,
+                  ADMM, Problem, autocor, autocov, autofun_last_timing, isequidistant, SpectralExt, basis_activation_func, check_freq, default_freqs,  # noqa: E402
                   fourier2complex, get_fourier_regressor, lpv_regressor, ls_sparse_spectral,
                   ls_cohere, ls_sparse_spectral_lpv, ls_sparse_spectral_lpv_multi, ls_sparse_spectral_lpv_rowsharded, lpv_ranges, lpv_batch_multi, lpv_signals_multi, ls_spectral, ls_spectral_lpv, tls_spectral, ls_windowcsd, ls_windowpsd, ls_windowpsd_lpv, psd,
                   reshape_params, set_default_option, get_default_option, default_options, windowpsd_sparse_batched, windowpsd_last_timing, windows_estimate, windows_estimate_multi, windowcsd_batched)
@@ -19,6 +21,8 @@ from .windows import Windows2, Windows3, hanning, mapwindows, merge, rect  # noq
 
 __all__ = [
     "autocov", "autocor", "autofun_last_timing", "isequidistant",
+    "spectrogram", "melspectrogram", "mfcc", "mel", "hz_to_mel", "mel_to_hz", "mel_frequencies", "fft_frequencies", "dct_matrix",
+    "nextfastfft", "Spectrogram", "MelSpectrogram", "MFCC", "freq", "time", "stft_last_timing",
     "ADMM", "Problem", "SpectralExt", "basis_activation_func", "check_freq", "default_freqs", "fourier2complex",
     "get_fourier_regressor", "lpv_regressor", "ls_sparse_spectral", "ls_sparse_spectral_lpv", "ls_sparse_spectral_lpv_multi", "ls_sparse_spectral_lpv_rowsharded", "lpv_ranges", "lpv_batch_multi", "lpv_signals_multi", "ls_spectral",
     "ls_spectral_lpv", "tls_spectral", "ls_windowcsd", "ls_cohere", "ls_windowpsd", "ls_windowpsd_lpv", "psd", "reshape_params", "IndBallL0", "LeastSquares",

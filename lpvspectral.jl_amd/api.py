@@ -21,7 +21,7 @@ import numpy as np
 from . import _lib
 from ._lib import as_f32, is_f32, as_f64, check, lib, out_ptr
 from .prox import IndBallL0, LeastSquares, NormL0, NormL1, NormL2, Quadratic, SlicedSeparableSum
-from .windows import Windows2, Windows3, rect
+from .windows import Windows2, Windows3, hanning, rect
 
 log = logging.getLogger("lpvspectral")
 
@@ -1410,3 +1410,256 @@ def autofun_last_timing():
     check(lib().lpvs_autofun_last_timing(out_ptr(o), 8))
     return dict(count_ms=o[0], generate_ms=o[1], sort_ms=o[2], copy_out_ms=o[3], total_ms=o[4], pairs=int(o[5]), sort_passes=int(o[6]),
                 key_bytes=int(o[7]))
+
+
+# --------------------------------------------------------------------------- spectrogram / melspectrogram / mfcc (DSP.spectrogram, src/mel.jl)
+class Spectrogram:
+    """DSP.Periodograms.Spectrogram: ``power`` ((nfft÷2+1) × frames), ``freq`` and ``time``."""
+
+    def __init__(self, power, freq, time):
+        self.power, self.freq, self.time = power, freq, time
+
+
+class MelSpectrogram:
+    """src/mel.jl MelSpectrogram: ``power`` (nmels × frames), ``mels`` and ``time``."""
+
+    def __init__(self, power, mels, time):
+        self.power, self.mels, self.time = power, mels, time
+
+
+class MFCC:
+    """src/mel.jl MFCC: ``mfcc`` (nmfcc × frames), ``number`` (1:nmfcc) and ``time``."""
+
+    def __init__(self, mfcc, number, time):
+        self.mfcc, self.number, self.time = mfcc, number, time
+
+
+def freq(M):
+    """DSP.freq: the frequencies of a Spectrogram, the mels of a MelSpectrogram, the coefficient numbers of an MFCC."""
+    return M.freq if isinstance(M, Spectrogram) else (M.mels if isinstance(M, MelSpectrogram) else M.number)
+
+
+def time(M):
+    """Base.time of a time-frequency representation: the frame centres."""
+    return M.time
+
+
+def _wide(x):
+    """Julia's promotion of a mel argument: Python floats / np.float64 are Float64; ints and np.float32 stay Float32."""
+    return isinstance(x, (float, np.floating)) and not isinstance(x, (np.float32, np.float16))
+
+
+def nextfastfft(n):
+    """DSP.nextfastfft: the smallest 2·3·5·7-smooth integer >= n."""
+    out = C.c_int64(0)
+    check(lib().lpvs_nextfastfft(int(n), C.byref(out)))
+    return int(out.value)
+
+
+def fft_frequencies(fs, nfft):
+    """src/mel.jl: LinRange(0f0, fs/2f0, nfft>>1 + 1) (Float64 when fs is)."""
+    dt = np.float64 if _wide(fs) else np.float32
+    nb = (int(nfft) >> 1) + 1
+    stop = dt(dt(fs) / dt(2))
+    t = np.arange(nb) / max(nb - 1, 1)
+    return ((1 - t) * 0.0 + t * np.float64(stop)).astype(dt)
+
+
+def hz_to_mel(frequencies):
+    """src/mel.jl:38-53 (Slaney): linear below 1 kHz, logarithmic above; Float32 constants, Float64 inputs widen."""
+    f = np.atleast_1d(np.asarray(frequencies))
+    dt = np.float64 if f.dtype == np.float64 else np.float32
+    f = f.astype(dt)
+    f_sp = np.float32(200) / np.float32(3)
+    min_log_hz = np.float32(1000)
+    min_log_mel = min_log_hz / f_sp
+    logstep = np.float32(np.log(np.float64(np.float32(6.4)))) / np.float32(27)
+    mels = (f - dt(0)) / dt(f_sp)
+    hi = f >= min_log_hz
+    mels[hi] = dt(min_log_mel) + np.log((f[hi] / dt(min_log_hz)).astype(np.float64)).astype(dt) / dt(logstep)
+    return mels
+
+
+def mel_to_hz(mels):
+    """src/mel.jl:56-71, the inverse of :func:`hz_to_mel`."""
+    m = np.atleast_1d(np.asarray(mels))
+    dt = np.float64 if m.dtype == np.float64 else np.float32
+    m = m.astype(dt)
+    f_sp = np.float32(200) / np.float32(3)
+    min_log_hz = np.float32(1000)
+    min_log_mel = min_log_hz / f_sp
+    logstep = np.float32(np.log(np.float64(np.float32(6.4)))) / np.float32(27)
+    f = dt(0) + dt(f_sp) * m
+    hi = m >= min_log_mel
+    f[hi] = dt(min_log_hz) * np.exp((dt(logstep) * (m[hi] - dt(min_log_mel))).astype(np.float64)).astype(dt)
+    return f
+
+
+def _scalar_mel(x):
+    return hz_to_mel(np.float64(x) if _wide(x) else np.float32(x))[0]
+
+
+def mel_frequencies(nmels=128, fmin=np.float32(0), fmax=np.float32(11025)):
+    """src/mel.jl:73-79: nmels points equally spaced in mel between fmin and fmax, in Hz."""
+    lo, hi = _scalar_mel(fmin), _scalar_mel(fmax)
+    dt = np.float64 if (lo.dtype == np.float64 or hi.dtype == np.float64) else np.float32
+    t = np.arange(nmels) / max(nmels - 1, 1)
+    return mel_to_hz(((1 - t) * np.float64(lo) + t * np.float64(hi)).astype(dt))
+
+
+def mel(fs, nfft, nmels=128, fmin=np.float32(0), fmax=None):
+    """src/mel.jl:99-113: the Float32 nmels × (nfft>>1 + 1) filterbank (Slaney mel scale, area-normalised triangles), computed by the
+    library on the host in the reference's precision (Float64 where fs / fmin / fmax are)."""
+    if fmax is None:
+        fmax = float(fs) / 2 if _wide(fs) else np.float32(np.float32(fs) / np.float32(2))
+    nfft, nmels = int(nfft), int(nmels)
+    W = np.empty((nmels, (nfft >> 1) + 1), dtype=np.float32, order="F")
+    wide = (1 if _wide(fs) else 0) | (2 if _wide(fmin) else 0) | (4 if _wide(fmax) else 0)
+    check(lib().lpvs_mel_filterbank(float(fs), nfft, nmels, float(fmin), float(fmax), wide, out_ptr(W)))
+    return W
+
+
+def dct_matrix(nfilters, ninput):
+    """src/mel.jl dct_matrix: Float32 rows cos(i (1:2:2ninput) π / 2ninput) · sqrt(2/ninput), i = 1 … nfilters (no DC row)."""
+    D = np.empty((int(nfilters), int(ninput)), dtype=np.float32, order="F")
+    check(lib().lpvs_dct_matrix(int(nfilters), int(ninput), out_ptr(D)))
+    return D
+
+
+def _stft_input(s):
+    """(keepalive, pointer, length, f32, device index or None) of a real signal."""
+    if _is_torch(s):
+        if s.is_complex():
+            raise ValueError("spectrogram: the signal must be real (the two-sided spectrogram of a complex signal is not built)")
+        f32 = s.dtype == __import__("torch").float32
+    else:
+        a = np.asarray(s)
+        if np.iscomplexobj(a):
+            raise ValueError("spectrogram: the signal must be real (the two-sided spectrogram of a complex signal is not built)")
+        f32 = a.dtype == np.float32
+    keep, ptr, L = (as_f32 if f32 else as_f64)(s)
+    dev = s.device.index if _is_torch(s) and s.is_cuda else None
+    return keep, ptr, L, f32, dev
+
+
+def _stft(kind, s, n, noverlap, nfft, fs, window, W=None, D=None, device=0):
+    keep, ptr, L, f32, dev = _stft_input(s)
+    n = L >> 3 if n is None else int(n)
+    noverlap = n >> 1 if noverlap is None else int(noverlap)
+    nfft = nextfastfft(n) if nfft is None else int(nfft)
+    if noverlap < 0 or noverlap >= n:
+        raise _lib.DomainError(f"noverlap must satisfy 0 <= noverlap < n (noverlap = {noverlap}, n = {n})")   # DSP.arraysplit
+    if nfft < n:
+        raise ValueError(f"nfft must be >= n (nfft = {nfft}, n = {n})")
+    dt = np.float32 if f32 else np.float64
+    win = None
+    if window is not None:
+        win = np.ascontiguousarray(np.asarray(window(n) if callable(window) else window, dtype=np.float64).ravel())
+        if len(win) != n:
+            raise ValueError(f"window has {len(win)} values, the frames {n}")
+        win = win.astype(dt)
+    nmels = 0 if W is None else W.shape[0]
+    nmfcc = 0 if D is None else D.shape[0]
+    rows = {_lib.STFT_POWER: nfft // 2 + 1, _lib.STFT_MEL: nmels, _lib.STFT_MFCC: nmfcc}[kind]
+    fn = lib().lpvs_stft_f32 if f32 else lib().lpvs_stft_f64
+    device = dev if dev is not None else device
+    wp = out_ptr(win) if win is not None else None
+    Wp = out_ptr(W) if W is not None else None
+    Dp = out_ptr(D) if D is not None else None
+    k = C.c_int64(0)
+    args = (kind, ptr, L, n, noverlap, nfft, float(fs), wp, Wp, nmels, Dp, nmfcc, int(device))
+    check(fn(*args, None, 0, C.byref(k)))                                     # count only
+    k = int(k.value)
+    if dev is not None:
+        import torch
+        o = torch.empty((k, rows), dtype=torch.float32 if f32 else torch.float64, device=s.device)
+        check(fn(*args, C.c_void_p(o.data_ptr()), k * rows, C.byref(C.c_int64(0))))
+        out = o.T                                                              # rows × frames, column-major storage
+    else:
+        out = np.empty((rows, k), dtype=dt, order="F")
+        check(fn(*args, out_ptr(out), k * rows, C.byref(C.c_int64(0))))
+    del keep
+    tm = (n / 2 + np.arange(k) * (n - noverlap)) / fs
+    return out, nfft, tm
+
+
+def spectrogram(s, n=None, noverlap=None, nfft=None, fs=1, window=None, device=0):
+    """DSP.spectrogram of a real signal: the one-sided power of the frames of DSP.arraysplit(s, n, noverlap), windowed and
+    zero-padded to nfft (default nextfastfft(n)); n defaults to len(s)>>3, noverlap to n>>1.  ``window`` is a function of n, a vector
+    or None.  Torch device tensors give device tensors, host arrays numpy arrays (f32 in, f32 out)."""
+    P, nfft, tm = _stft(_lib.STFT_POWER, s, n, noverlap, nfft, fs, window, device=device)
+    return Spectrogram(P, np.arange(nfft // 2 + 1) * fs / nfft, tm)
+
+
+def _mel_axis(nmels, fmin, fmax):
+    lo, hi = _scalar_mel(fmin), _scalar_mel(fmax)
+    dt = np.float64 if (lo.dtype == np.float64 or hi.dtype == np.float64) else np.float32
+    return np.linspace(np.float64(lo), np.float64(hi), int(nmels)).astype(dt)
+
+
+def melspectrogram(s, n=None, *args, fs=1, nmels=128, fmin=np.float32(0), fmax=None, window=hanning, device=0, **kwargs):
+    """src/mel.jl:133-143.  ``melspectrogram(s, n, noverlap; fs, nmels, fmin, fmax, window=hanning, nfft)``: the Float32 filterbank
+    mel(fs, 2·size(S.power,1) - 1) applied to the spectrogram's power (for odd nfft its grid runs to exactly fs/2, the reference's quirk),
+    fused into the STFT on the device.  ``melspectrogram(S::Spectrogram; fs, nmels, fmin, fmax)`` projects an existing spectrogram."""
+    if fmax is None:
+        fmax = float(fs) / 2 if _wide(fs) else np.float32(np.float32(fs) / np.float32(2))
+    if isinstance(s, Spectrogram):
+        P = s.power
+        nbins, frames = int(P.shape[0]), int(P.shape[1])
+        W = mel(fs, 2 * nbins - 1, nmels=nmels, fmin=fmin, fmax=fmax)
+        if _is_torch(P) and P.is_cuda:
+            import torch
+            f32 = P.dtype == torch.float32
+            src = P.T.contiguous()                                             # frames × nbins row-major = nbins × frames column-major
+            torch.cuda.current_stream(src.device).synchronize()
+            o = torch.empty((frames, int(nmels)), dtype=src.dtype, device=src.device)
+            fn = lib().lpvs_mel_project_f32 if f32 else lib().lpvs_mel_project_f64
+            check(fn(C.c_void_p(src.data_ptr()), nbins, frames, out_ptr(W), int(nmels), src.device.index, C.c_void_p(o.data_ptr())))
+            out = o.T
+        else:
+            f32 = isinstance(P, np.ndarray) and P.dtype == np.float32
+            dt = np.float32 if f32 else np.float64
+            src = np.asfortranarray(np.asarray(P, dtype=dt))
+            out = np.empty((int(nmels), frames), dtype=dt, order="F")
+            fn = lib().lpvs_mel_project_f32 if f32 else lib().lpvs_mel_project_f64
+            check(fn(out_ptr(src), nbins, frames, out_ptr(W), int(nmels), int(device), out_ptr(out)))
+        return MelSpectrogram(out, _mel_axis(nmels, fmin, fmax), s.time)
+    noverlap = args[0] if args else kwargs.pop("noverlap", None)
+    nfft = kwargs.pop("nfft", None)
+    if kwargs:
+        raise TypeError(f"melspectrogram: unknown keywords {sorted(kwargs)}")
+    L_ = len(s) if not _is_torch(s) else s.numel()
+    n_ = L_ >> 3 if n is None else int(n)
+    nfft_ = nextfastfft(n_) if nfft is None else int(nfft)
+    W = mel(fs, 2 * (nfft_ // 2 + 1) - 1, nmels=nmels, fmin=fmin, fmax=fmax)
+    out, _, tm = _stft(_lib.STFT_MEL, s, n_, noverlap, nfft_, fs, window, W=W, device=device)
+    return MelSpectrogram(out, _mel_axis(nmels, fmin, fmax), tm)
+
+
+def mfcc(s, *args, nmfcc=20, nmels=128, window=hanning, fs=1, fmin=np.float32(0), fmax=None, device=0, **kwargs):
+    """src/mel.jl:159-172: dct_matrix(nmfcc, nmels) * power(melspectrogram(s, args...)), every column divided by its 2-norm.  As the
+    reference: no log before the DCT, the DC row is skipped, and a zero column gives 0/0 = NaN."""
+    if nmfcc >= nmels:
+        raise ValueError("number of mfcc components should be less than the number of mel frequency bins")
+    if fmax is None:
+        fmax = float(fs) / 2 if _wide(fs) else np.float32(np.float32(fs) / np.float32(2))
+    n = args[0] if args else kwargs.pop("n", None)
+    noverlap = args[1] if len(args) > 1 else kwargs.pop("noverlap", None)
+    nfft = kwargs.pop("nfft", None)
+    if kwargs:
+        raise TypeError(f"mfcc: unknown keywords {sorted(kwargs)}")
+    L_ = len(s) if not _is_torch(s) else s.numel()
+    n_ = L_ >> 3 if n is None else int(n)
+    nfft_ = nextfastfft(n_) if nfft is None else int(nfft)
+    W = mel(fs, 2 * (nfft_ // 2 + 1) - 1, nmels=nmels, fmin=fmin, fmax=fmax)
+    D = dct_matrix(nmfcc, nmels)
+    out, _, tm = _stft(_lib.STFT_MFCC, s, n_, noverlap, nfft_, fs, window, W=W, D=D, device=device)
+    return MFCC(out, np.arange(1, int(nmfcc) + 1), tm)
+
+
+def stft_last_timing():
+    """HIP-event times (ms) and plan of this thread's last spectrogram / melspectrogram / mfcc call."""
+    o = np.zeros(9)
+    check(lib().lpvs_stft_last_timing(out_ptr(o), 9))
+    return dict(fft_ms=o[0], copy_out_ms=o[1], total_ms=o[2], frames=int(o[3]), path=int(o[4]), fft_length=int(o[5]),
+                pairs_per_workgroup=int(o[6]), rows=int(o[7]), setup_ms=o[8])
