@@ -6,9 +6,15 @@ A step = one complete solve of one synthetic signal whose inputs (y, X, V, w) ar
 in HBM: basis tables -> Gram + rhs -> factorisation of (G + I/mu) -> 2000 ADMM iterations (tol = 0,
 so exactly 2000) -> parameter read-back.  The workload's w is the reference's uniform grid, so the
 library takes its structured Gram (nudft.hip, VALU f64 -- the MFMA Gram is NOT on this workload's path);
-the dense f64-MFMA Gram used for arbitrary w is measured once more outside the timed region and reported
-under "gram_general_path".  Ranks solve independent signals (weak scaling, no data-path collective);
+with `--full` the dense f64-MFMA Gram used for arbitrary w is measured once more outside the timed region and
+reported under "gram_general_path".  Ranks solve independent signals (weak scaling, no data-path collective);
 RCCL is used only for the final gather of the coefficient vectors.
+
+A plain run (no `--full`) does only what the headline figure needs: it sets up, warms up, times the steps, writes
+`--dump-outputs` if asked, and prints the line (the contract's fields, the phase times the timed steps' own timers
+recorded, the configuration).  `--full` adds everything else this file measures: the roofline of the dominant kernel,
+the other storages and precisions of the inverse, the dense Gram, two solves in flight, the CPU baseline, and with
+the default workload the sub-records of the other configurations described below.
 
 `--workload cfg4` is BASELINE.json's batched-window configuration (ls_windowpsd with the sparse estimator,
 1024 windows x 2^16 samples, Nf = 256): a step = all 1024 windows, the window range is sharded over the
@@ -18,14 +24,14 @@ ranks (strong scaling), one RCCL all_gather of the per-window coefficients, PSD 
 8 channels per GPU sharing (X, V), N = 2^20, Nf = 1024, Nv = 16 -> n = 32768, IndBallL0(32)) are BASELINE.json's other two GPU
 configurations, each with its own `roofline` and `cpu_baseline`.
 
-With the default workload every run ALSO measures cfg4 with the window range sharded over the ranks and puts it on the same JSON line
-as `cfg4_strong` (windows/s, per-rank window counts, the collective's backend and rank count): the driver's fixed command
-`bench.py --gpus N` thus yields both curves north_star asks for -- independent signals (weak) and batched windows (strong).
+With the default workload a `--full` run ALSO measures cfg4 with the window range sharded over the ranks and puts it on the same JSON
+line as `cfg4_strong` (windows/s, per-rank window counts, the collective's backend and rank count): `bench.py --gpus N --full` thus
+yields both curves north_star asks for -- independent signals (weak) and batched windows (strong).
 
 `python3 bench.py --gpus N` starts the N ranks itself (a torch.distributed.run CHILD process, started before this process touches
 the GPU) when it was not launched by one; under a profiler preload it refuses to (profile single-rank runs).
 
-Prints ONE JSON line on rank 0 (see the driver contract in the task statement) with
+Prints ONE JSON line on rank 0 (see the driver contract in the task statement); with `--full` it also holds
   roofline     : the dominant kernel (the ADMM mat-vec, HBM-bound) against the HBM peak, from HIP-event
                  timings taken inside the library on the stream the kernel runs on
   cpu_baseline : the faithful CPU restatement of the reference algorithm (oracle, "port") timed on
@@ -464,6 +470,9 @@ def main():
                     help="cfg3 (default, the judged line): one LPV group-lasso signal per GPU per step (+ the cfg4_strong sub-record); cfg4: 1024 "
                          "batched windows per step, window range sharded over the ranks; cfg2: ls_sparse_spectral NormL1 N=2^18 Nf=512, 5000 "
                          "iterations; cfg5: multichannel LPV n=32768 IndBallL0(32), 8 channels per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline figure too: rooflines, other storages / precisions, the dense Gram, solves in "
+                         "flight, CPU baselines and (cfg3) the sub-records of the other configurations; the --no-* flags below trim a --full run")
     ap.add_argument("--no-cfg4-strong", action="store_true", help="cfg3 runs: skip the cfg4 strong-scaling sub-record")
     ap.add_argument("--no-baseline-configs", action="store_true", help="cfg3 runs: skip the compact cfg2 / cfg5 records")
     ap.add_argument("--no-row-sharded", action="store_true", help="cfg3 runs with several ranks: skip the row-sharded-Gram sub-record (SURVEY 8(e)(2))")
@@ -583,7 +592,7 @@ def main():
     outputs = state["out"].pop("_outputs") if rank == 0 else None
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, outputs)
-    if args.workload == "cfg3":
+    if args.workload == "cfg3" and args.full:
         timer = threading.Timer(args.sub_timeout, watchdog)
         timer.daemon = True
         timer.start()
@@ -908,22 +917,25 @@ def run_cfg4(L, args, world, rank, local, dev, cdev, dist, sync, max_over_ranks)
     sync()
     elapsed = max_over_ranks(time.perf_counter() - t0)
     tm = L.windowpsd_last_timing()
-    # dominant kernel of the step (the batch mat-vec, one launch per iteration for all windows of the shard): its launch time from
-    # one extra UNTIMED call that appends 200 back-to-back launches after its last pass (HIP events on the library's stream)
-    os.environ["LPVS_WINDOW_MATVEC_TIMING"] = "1"
-    try:
-        L.windowpsd_sparse_batched(y, t, f, n, 0, None, λ=CFG4["lam"], μ=CFG4["mu"], tol=0.0, iters=8, win_lo=lo, win_hi=hi, device=local)
-        tm_mv = L.windowpsd_last_timing()
-    finally:
-        del os.environ["LPVS_WINDOW_MATVEC_TIMING"]
-    if dist is not None:
-        dist.barrier()
+    tm_mv = {}
+    if args.full:
+        # dominant kernel of the step (the batch mat-vec, one launch per iteration for all windows of the shard): its launch time from
+        # one extra UNTIMED call that appends 200 back-to-back launches after its last pass (HIP events on the library's stream)
+        os.environ["LPVS_WINDOW_MATVEC_TIMING"] = "1"
+        try:
+            L.windowpsd_sparse_batched(y, t, f, n, 0, None, λ=CFG4["lam"], μ=CFG4["mu"], tol=0.0, iters=8, win_lo=lo, win_hi=hi, device=local)
+            tm_mv = L.windowpsd_last_timing()
+        finally:
+            del os.environ["LPVS_WINDOW_MATVEC_TIMING"]
+        if dist is not None:
+            dist.barrier()
     if rank != 0:
         return None
-    tm["matvec_us_per_iteration"] = tm_mv.get("matvec_us_per_iteration")
-    tm["matvec_windows"] = tm_mv.get("matvec_windows")
+    if args.full:
+        tm["matvec_us_per_iteration"] = tm_mv.get("matvec_us_per_iteration")
+        tm["matvec_windows"] = tm_mv.get("matvec_windows")
     st = L.get_default_option("storage") or os.environ.get("LPVS_M_STORAGE", "mixed")   # storage of the packed inverses (admm.hip)
-    mv_us = tm.get("matvec_us_per_iteration")
+    mv_us = tm.get("matvec_us_per_iteration") if args.full else None                  # (a plain run times no extra launches: no roofline)
     one_launch = bool(tm_mv.get("one_launch_iteration"))
     mv_only_us = mv_us
     if one_launch and mv_us:
@@ -971,11 +983,12 @@ def run_cfg4(L, args, world, rank, local, dev, cdev, dist, sync, max_over_ranks)
         "admm_iters_per_sec": nwin * iters * steps / elapsed,
         "phase_ms_rank0": {k: v for k, v in tm.items() if k.endswith("_ms")},
         "psd_argmax": int(np.argmax(S)), "iters_min_max": [int(its.min()), int(its.max())],
-        "roofline": roof,
         "_outputs": {"psd": S, "coefficients": x, "iterations": np.asarray(its, dtype=np.float64)},   # (popped by main(): --dump-outputs)
     }
-    if world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = guarded(cpu_baseline_cfg4, "cpu_baseline")
+    if args.full:
+        out["roofline"] = roof
+        if world == 1 and not args.no_cpu_baseline:
+            out["cpu_baseline"] = guarded(cpu_baseline_cfg4, "cpu_baseline")
     return out
 
 
@@ -1038,6 +1051,35 @@ def run_cfg3(L, args, world, rank, local, dev, cdev, dist, sync, max_over_ranks)
     n_xcorr = int(tms[0].get("xcorr_count", 0))
     n_nib = int(tms[0].get("nibble_refreshes", 0))
     form = tms[0]["gram_form"]
+    out = {
+        "metric": "signals/sec, ls_sparse_spectral_lpv group lasso N=2^%d Nf=%d Nv=%d (%d ADMM iters; iters/sec in admm_iters_per_sec)" % (args.log2n, NF, NV, iters),
+        "value": (1 if rowsh else world) * steps / elapsed, "unit": "signals/s", "n_gpus": world, "steps": steps,
+        "warmup": warmup, "ms_per_step": elapsed / steps * 1e3, "higher_is_better": True,
+        "scaling": "strong" if rowsh else "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+        "config": {"workload": "cfg3 ls_sparse_spectral_lpv group lasso N=2^%d Nf=%d Nv=%d n=%d lam=%g mu=%g iters=%d tol=0; 1 signal/GPU"
+                               % (args.log2n, NF, NV, 2 * NF * NV, LAMBDA, MU, iters),
+                   "signals_per_step_per_gpu": 1.0 / world if rowsh else 1, "gram_form": form,
+                   "gram": ("structured, slot sums by a non-uniform FFT (nufft.hip); MFMA path not taken" if form == "ap-nufft" else
+                            "structured (VALU f64, nudft.hip); MFMA path not taken" if form == "ap" else "dense f64 MFMA (%s)" % form),
+                   "xupdate_corrections_per_solve": n_xcorr, "nibble_refreshes_per_solve": n_nib,
+                   "xupdate_correction": "after iterations 16, 128, 256, 512, 1024, ...: one step of iterative refinement of the x-update's offset vector, residual in twice the mantissa (DESIGN 6.1)",
+                   "concurrent_solves_per_gpu": args.streams,
+                   "sharding": "sample rows of one signal over the ranks, one all-reduce of the Gram (SURVEY 8(e)(2))" if rowsh else "independent signals",
+                   "final_gather": "none" if (world == 1 or rowsh) else ("rccl" if args.backend == "nccl" else args.backend) + " all_gather"},
+        "admm_iters_per_sec": iters / (phase["admm_ms"] * 1e-3),
+        "phase_ms": phase,
+        "factor_ms": phase["factor_ms"],
+        "factorisation": {"bound": "mfma", "kernel": "rank_updatem_kernel + pivot chain (blocked symmetric sweep, two 128-wide steps per pass over A, v_mfma_f64_16x16x4_f64)",
+                          "flops": float(2 * NF * NV) ** 3, "ms": phase["factor_ms"],
+                          "achieved": float(2 * NF * NV) ** 3 / (phase["factor_ms"] * 1e-3) * 1e-12, "peak": F64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                          "frac": float(2 * NF * NV) ** 3 / (phase["factor_ms"] * 1e-3) * 1e-12 / F64_MFMA_PEAK_TFLOPS,
+                          "note": "n^3 flop on the lower triangle for M = (G + I/mu)^-1; whole phase incl. the pivot chains and hand-overs"},
+        "final_nxz": nxz,
+        "_params_rank0": np.asarray(params).ravel() if (params is not None and not rowsh) else None,   # (popped by main(): the single-process record compares with it)
+        "_outputs": outputs,                                                                             # (popped by main(): --dump-outputs)
+    }
+    if not args.full:                                  # a plain run: the headline figure and what the timed steps recorded, nothing else
+        return out
     # ---- the same signals with TWO solves in flight per GPU (two host threads, each handle its own stream): the matrix-core-bound
     # factorisation of one solve runs under the HBM-bound iterations of the other.  Reported beside the judged line (whose `value`,
     # ms_per_step and roofline are the one-solve-at-a-time figures above); not part of the timed region.
@@ -1170,30 +1212,9 @@ def run_cfg3(L, args, world, rank, local, dev, cdev, dist, sync, max_over_ranks)
                         "flops than the n x n lower triangle N*n*(n+1) that achieved_algorithmic is priced with); issue ceiling measured "
                         "by tools/mfma_f64_peak.hip: 66-67 TFLOP/s"}
     general = guarded(_general, "gram_general_path") if (not args.no_general_path and not rowsh) else None
-    out = {
-        "metric": "signals/sec, ls_sparse_spectral_lpv group lasso N=2^%d Nf=%d Nv=%d (%d ADMM iters; iters/sec in admm_iters_per_sec)" % (args.log2n, NF, NV, iters),
-        "value": (1 if rowsh else world) * steps / elapsed, "unit": "signals/s", "n_gpus": world, "steps": steps,
-        "warmup": warmup, "ms_per_step": elapsed / steps * 1e3, "higher_is_better": True,
-        "scaling": "strong" if rowsh else "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-        "config": {"workload": "cfg3 ls_sparse_spectral_lpv group lasso N=2^%d Nf=%d Nv=%d n=%d lam=%g mu=%g iters=%d tol=0; 1 signal/GPU"
-                               % (args.log2n, NF, NV, 2 * NF * NV, LAMBDA, MU, iters),
-                   "signals_per_step_per_gpu": 1.0 / world if rowsh else 1, "gram_form": form,
-                   "gram": ("structured, slot sums by a non-uniform FFT (nufft.hip); MFMA path not taken" if form == "ap-nufft" else
-                            "structured (VALU f64, nudft.hip); MFMA path not taken" if form == "ap" else "dense f64 MFMA (%s)" % form),
-                   "matvec_storage": mv_info["storage"], "xupdate_corrections_per_solve": n_xcorr, "nibble_refreshes_per_solve": n_nib, "nibble_refresh_us": nib_us,
-                   "xupdate_correction": "after iterations 16, 128, 256, 512, 1024, ...: one step of iterative refinement of the x-update's offset vector, residual in twice the mantissa (DESIGN 6.1)",
-                   "whole_step_with_8_byte_storage": alt_step, "whole_step_with_36_bit_reads": alt36_step, "from_host_arrays": host_step, "concurrent_solves_per_gpu": args.streams, "two_solves_in_flight": two_in_flight,
-                   "sharding": "sample rows of one signal over the ranks, one all-reduce of the Gram (SURVEY 8(e)(2))" if rowsh else "independent signals",
-                   "final_gather": "none" if (world == 1 or rowsh) else ("rccl" if args.backend == "nccl" else args.backend) + " all_gather"},
-        "admm_iters_per_sec": iters / (phase["admm_ms"] * 1e-3),
-        "phase_ms": phase,
-        "factor_ms": phase["factor_ms"],
-        "factorisation": {"bound": "mfma", "kernel": "rank_updatem_kernel + pivot chain (blocked symmetric sweep, two 128-wide steps per pass over A, v_mfma_f64_16x16x4_f64)",
-                          "flops": float(2 * NF * NV) ** 3, "ms": phase["factor_ms"],
-                          "achieved": float(2 * NF * NV) ** 3 / (phase["factor_ms"] * 1e-3) * 1e-12, "peak": F64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                          "frac": float(2 * NF * NV) ** 3 / (phase["factor_ms"] * 1e-3) * 1e-12 / F64_MFMA_PEAK_TFLOPS,
-                          "note": "n^3 flop on the lower triangle for M = (G + I/mu)^-1; whole phase incl. the pivot chains and hand-overs"},
-        "final_nxz": nxz,
+    out["config"].update({"matvec_storage": mv_info["storage"], "nibble_refresh_us": nib_us, "whole_step_with_8_byte_storage": alt_step,
+                          "whole_step_with_36_bit_reads": alt36_step, "from_host_arrays": host_step, "two_solves_in_flight": two_in_flight})
+    out.update({
         "roofline": {"bound": "hbm", "kernel": mv_info["kernel"] + " (ADMM mat-vec with the tile-packed lower triangle of (G + I/mu)^-1)",
                      "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", **roof_fracs(achieved),
                      "traffic": traffic, "traffic_source": traffic_src, "algorithmic_bytes_per_launch": mv_bytes,
@@ -1211,9 +1232,7 @@ def run_cfg3(L, args, world, rank, local, dev, cdev, dist, sync, max_over_ranks)
                              "algorithmic bytes = %s; M is read once per iteration; duration = HIP events around 300 back-to-back launches on "
                              "the library's stream" % mv_info["bytes_formula"]},
         "gram_general_path": general,
-        "_params_rank0": np.asarray(params).ravel() if (params is not None and not rowsh) else None,   # (popped by main(): the single-process record compares with it)
-        "_outputs": outputs,                                                                             # (popped by main(): --dump-outputs)
-    }
+    })
     if world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = guarded(cpu_baseline, "cpu_baseline")
     return out
@@ -1276,6 +1295,17 @@ def run_cfg2(L, args, world, rank, local, dev, cdev, dist, sync, max_over_ranks,
     if rank != 0:
         return None
     phase = {k: float(np.mean([q[k] for q in tms])) for k in ("basis_ms", "gram_ms", "reduce_rhs_ms", "factor_ms", "admm_ms")}
+    out = {"metric": "signals/sec, ls_sparse_spectral NormL1(%g) N=2^%d Nf=%d (%d ADMM iters; iters/sec in admm_iters_per_sec)" % (CFG2["lam"], CFG2["log2n"], Nf, iters),
+           "value": world * steps / elapsed, "unit": "signals/s", "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": elapsed / steps * 1e3,
+           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+           "config": {"workload": "cfg2: ls_sparse_spectral NormL1(%g), N=2^%d non-equidistant, Nf=%d (no zero frequency, n=%d), mu=%g, iters=%d, tol=0, one signal per GPU"
+                                  % (CFG2["lam"], CFG2["log2n"], Nf, 2 * Nf, CFG2["mu"], iters), "gram_form": tms[0]["gram_form"]},
+           "admm_iters_per_sec": iters / (phase["admm_ms"] * 1e-3), "phase_ms": phase, "final_nxz": nxz,
+           "peaks_1based": sorted((np.argsort(-np.abs(params))[:5] + 1).tolist())}
+    if not sub:                                                        # (popped by main(): --dump-outputs)
+        out["_outputs"] = {"params": params, "iterations": np.array([it], dtype=np.float64), "nxz": np.array([nxz], dtype=np.float64)}
+    if not args.full:                                                  # a plain run: the headline figure and what the timed steps recorded
+        return out
     # ---- several of these latency-bound solves in flight (host threads, each handle its own stream: the dependent-launch gaps of one
     # solve's iterations are filled by the others' launches); beside the judged one-at-a-time line, not part of the timed region
     in_flight = None
@@ -1307,15 +1337,8 @@ def run_cfg2(L, args, world, rank, local, dev, cdev, dist, sync, max_over_ranks,
     achieved = mv_bytes / (mv_us * 1e-6) * 1e-9
     traffic2, traffic2_src = pmc_traffic("admm_small_iter_kernel<1" if one_launch else "symv_kernel", "cfg2")
     npad = -(-2 * Nf // 128) * 128
-    out = {"metric": "signals/sec, ls_sparse_spectral NormL1(%g) N=2^%d Nf=%d (%d ADMM iters; iters/sec in admm_iters_per_sec)" % (CFG2["lam"], CFG2["log2n"], Nf, iters),
-           "value": world * steps / elapsed, "unit": "signals/s", "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": elapsed / steps * 1e3,
-           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-           "config": {"workload": "cfg2: ls_sparse_spectral NormL1(%g), N=2^%d non-equidistant, Nf=%d (no zero frequency, n=%d), mu=%g, iters=%d, tol=0, one signal per GPU"
-                                  % (CFG2["lam"], CFG2["log2n"], Nf, 2 * Nf, CFG2["mu"], iters), "gram_form": tms[0]["gram_form"], "matvec_storage": info["storage"],
-                      "solves_in_flight": in_flight},
-           "admm_iters_per_sec": iters / (phase["admm_ms"] * 1e-3), "phase_ms": phase, "final_nxz": nxz,
-           "peaks_1based": sorted((np.argsort(-np.abs(params))[:5] + 1).tolist()),
-           "roofline": {"bound": "hbm", "kernel": info["kernel"] + " (full symmetric (G + I/mu)^-1, n = 1024: 8.4 MB, Infinity-Cache resident)",
+    out["config"].update({"matvec_storage": info["storage"], "solves_in_flight": in_flight})
+    out["roofline"] = {"bound": "hbm", "kernel": info["kernel"] + " (full symmetric (G + I/mu)^-1, n = 1024: 8.4 MB, Infinity-Cache resident)",
                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", **roof_fracs(achieved), "traffic": traffic2, "traffic_source": traffic2_src,
                         "algorithmic_bytes_per_launch": mv_bytes, "launch_us": mv_us, "launches_per_step": iters, "iteration_us": it_us,
                         "matvec_only_launch_us": mv_only_us,
@@ -1329,9 +1352,7 @@ def run_cfg2(L, args, world, rank, local, dev, cdev, dist, sync, max_over_ranks,
                                 "launch-latency bound, not bandwidth bound: an iteration is two dependent launches of a few microseconds (mat-vec + prox / "
                                 "dual update), replayed as hipGraph chunks of 50 iterations; iteration_us = HIP events around the ADMM loop / iterations; "
                                 "launch_us = the mat-vec alone, 500 back-to-back launches.  The floor is the dependent-kernel boundary "
-                                "(MI355X_MICROARCH.md: 1.2-1.9 us each), not the 8.4 MB the kernel reads."}}
-    if not sub:                                                        # (popped by main(): --dump-outputs)
-        out["_outputs"] = {"params": params, "iterations": np.array([it], dtype=np.float64), "nxz": np.array([nxz], dtype=np.float64)}
+                                "(MI355X_MICROARCH.md: 1.2-1.9 us each), not the 8.4 MB the kernel reads."}
     if world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = guarded(cpu_baseline_cfg2, "cpu_baseline")
     return out
@@ -1388,12 +1409,28 @@ def run_cfg5(L, args, world, rank, local, dev, cdev, dist, sync, max_over_ranks,
     if rank != 0:
         return None
     phase = {k: float(np.mean([q[k] for q in tms])) for k in ("basis_ms", "gram_ms", "reduce_rhs_ms", "factor_ms", "admm_ms")}
+    n = 2 * Nf * Nv
+    out = {"metric": "signals/sec, multichannel ls_sparse_spectral_lpv IndBallL0(%d) N=2^%d Nf=%d Nv=%d, %d channels per GPU (%d ADMM iters)"
+                     % (CFG5["r"], log2n, Nf, Nv, ns, iters),
+           "value": world * ns * steps / elapsed, "unit": "signals/s", "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": elapsed / steps * 1e3,
+           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+           "config": {"workload": "cfg5: %d channels per GPU sharing (X, V), N=2^%d, Nf=%d, Nv=%d (n=%d), IndBallL0(%d), mu=%g, iters=%d, tol=0"
+                                  % (ns, log2n, Nf, Nv, n, CFG5["r"], CFG5["mu"], iters), "gram_form": tms[0]["gram_form"],
+                      "sharding": "disjoint channel ranges per rank", "final_gather": "none" if world == 1 else "all_gather of the coefficients"},
+           "admm_iters_per_sec": iters / (phase["admm_ms"] * 1e-3), "iteration_ms_all_channels": phase["admm_ms"] / iters,
+           "phase_ms": phase, "final_nxz": nxz, "nnz_per_channel": [int(np.count_nonzero(params[:, q])) for q in range(ns)],
+           "factorisation": {"flops": float(n) ** 3, "ms": phase["factor_ms"], "achieved_TFLOPs": float(n) ** 3 / (phase["factor_ms"] * 1e-3) * 1e-12,
+                             "frac_of_f64_mfma_peak": float(n) ** 3 / (phase["factor_ms"] * 1e-3) * 1e-12 / F64_MFMA_PEAK_TFLOPS}}
+    if not sub:                                                        # (popped by main(): --dump-outputs); channels in rank order when gathered
+        out["_outputs"] = {"params": np.concatenate([a.cpu().numpy() for a in allp]) if dist is not None else params.T,
+                           "iterations": np.array([it], dtype=np.float64), "nxz": np.array([nxz], dtype=np.float64)}
+    if not args.full:                                                  # a plain run: the headline figure and what the timed steps recorded
+        return out
     with L.Problem.lpv_multi(Y, X, V, w, Nv, True, False, device=local) as p:
         p.set_prox(L.IndBallL0(CFG5["r"]))
         p.admm_init(None, μ=CFG5["mu"], tol=0.0)
         mv_us, mv_bytes = p.time_matvec(30)
         info = p.matvec_info()
-    n = 2 * Nf * Nv
     # the launch also WRITES its tile partials: one record per run of tiles for the row sums, one per tile for the
     # column sums, 128 rows x `signals_per_pass` doubles each -- algorithmic bytes of the kernel as built, counted from this round on
     nblk5 = n // 128
@@ -1405,18 +1442,8 @@ def run_cfg5(L, args, world, rank, local, dev, cdev, dist, sync, max_over_ranks,
     mv_bytes = tile_bytes + partial_bytes
     achieved = mv_bytes / (mv_us * 1e-6) * 1e-9
     traffic5, traffic5_src = pmc_traffic("symv_tile_mfma_ws_kernel", "cfg5") if (log2n == CFG5["log2n"] and n == 32768) else (None, None)
-    out = {"metric": "signals/sec, multichannel ls_sparse_spectral_lpv IndBallL0(%d) N=2^%d Nf=%d Nv=%d, %d channels per GPU (%d ADMM iters)"
-                     % (CFG5["r"], log2n, Nf, Nv, ns, iters),
-           "value": world * ns * steps / elapsed, "unit": "signals/s", "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": elapsed / steps * 1e3,
-           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-           "config": {"workload": "cfg5: %d channels per GPU sharing (X, V), N=2^%d, Nf=%d, Nv=%d (n=%d), IndBallL0(%d), mu=%g, iters=%d, tol=0"
-                                  % (ns, log2n, Nf, Nv, n, CFG5["r"], CFG5["mu"], iters), "gram_form": tms[0]["gram_form"],
-                      "matvec_storage": info["storage"], "sharding": "disjoint channel ranges per rank", "final_gather": "none" if world == 1 else "all_gather of the coefficients"},
-           "admm_iters_per_sec": iters / (phase["admm_ms"] * 1e-3), "iteration_ms_all_channels": phase["admm_ms"] / iters,
-           "phase_ms": phase, "final_nxz": nxz, "nnz_per_channel": [int(np.count_nonzero(params[:, q])) for q in range(ns)],
-           "factorisation": {"flops": float(n) ** 3, "ms": phase["factor_ms"], "achieved_TFLOPs": float(n) ** 3 / (phase["factor_ms"] * 1e-3) * 1e-12,
-                             "frac_of_f64_mfma_peak": float(n) ** 3 / (phase["factor_ms"] * 1e-3) * 1e-12 / F64_MFMA_PEAK_TFLOPS},
-           "roofline": {"bound": "hbm", "kernel": info["kernel"] + " (tile product of the packed (G + I/mu)^-1 with all channels on %s)" % info.get("mfma", "the matrix cores"),
+    out["config"]["matvec_storage"] = info["storage"]
+    out["roofline"] = {"bound": "hbm", "kernel": info["kernel"] + " (tile product of the packed (G + I/mu)^-1 with all channels on %s)" % info.get("mfma", "the matrix cores"),
                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", **roof_fracs(achieved), "traffic": traffic5, "traffic_source": traffic5_src,
                         "algorithmic_bytes_per_launch": mv_bytes, "tile_bytes_per_launch": tile_bytes, "partial_bytes_written_per_launch": partial_bytes,
                         "achieved_on_tile_bytes_only": tile_bytes / (mv_us * 1e-6) * 1e-9, "launch_us": mv_us, "launches_per_step": iters,
@@ -1425,10 +1452,7 @@ def run_cfg5(L, args, world, rank, local, dev, cdev, dist, sync, max_over_ranks,
                         "note": "algorithmic bytes = %s + the tile partials the launch writes (one record per run of tiles for the row sums, one per tile "
                                 "for the column sums: ~34 + 270 MB at n = 32768); HIP events around 30 back-to-back launches on the library's stream; "
                                 "the same launch also issues n(n+128)/2 x %d signal columns x 2 products of f64 MFMA work; launch time varies by ~10 %% with the "
-                                "box and with where the 3.2 GB buffer landed (DESIGN.md 4.5.1)" % (info["bytes_formula"], info.get("signals_per_pass", 16))}}
-    if not sub:                                                        # (popped by main(): --dump-outputs); channels in rank order when gathered
-        out["_outputs"] = {"params": np.concatenate([a.cpu().numpy() for a in allp]) if dist is not None else params.T,
-                           "iterations": np.array([it], dtype=np.float64), "nxz": np.array([nxz], dtype=np.float64)}
+                                "box and with where the 3.2 GB buffer landed (DESIGN.md 4.5.1)" % (info["bytes_formula"], info.get("signals_per_pass", 16))}
     if world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = guarded(cpu_baseline_cfg5, "cpu_baseline")
     return out

@@ -65,7 +65,7 @@ def test_bench_sub_records_cannot_cost_the_main_line():
     with cfg4_strong = {"error": ...}; (b) a rank that hangs in a sub-record -> the watchdog ends the run, rank 0 prints the main
     line it already holds; (c) without faults, rank 0 alone drives the devices of all ranks ([0, 0] on this box) through the
     C-ABI's several-device drivers: the single_process_{cfg3,cfg4,cfg5} records."""
-    base = ["--log2n", "16", "--iters", "70", "--nwin", "32", "--rehearse-sub-records"]
+    base = ["--full", "--log2n", "16", "--iters", "70", "--nwin", "32", "--rehearse-sub-records"]
     rec = _run(base)
     assert rec["n_gpus"] == 2 and rec["value"] > 0
     assert rec["cfg4_strong"]["windows_per_gpu"] == [16, 16] and rec["cfg4_strong"]["psd_argmax"] == 33
@@ -123,23 +123,38 @@ def _run1(extra):
 
 @pytest.mark.gpu
 def test_bench_single_rank_lines_of_every_workload():
-    """One rank, reduced sizes / iteration counts: every workload prints ONE line with the contract's fields, a roofline record and the
+    """One rank, reduced sizes / iteration counts, --full: every workload prints ONE line with the contract's fields, a roofline record and the
     sub-records the full-size runs carry (two solves in flight through Python threads and through lpvs_lpv_signals_multi_f64)."""
     need = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline"}
-    r3 = _run1(["--log2n", "16", "--iters", "60", "--no-general-path", "--no-alt-storage"])
+    r3 = _run1(["--full", "--log2n", "16", "--iters", "60", "--no-general-path", "--no-alt-storage"])
     assert need <= set(r3) and r3["n_gpus"] == 1 and r3["roofline"]["bound"] == "hbm"
     # (at N = 2^16 the inverse is not diagonally dominant enough for the mixed storage: the uniform 6-byte kernel runs)
     assert r3["roofline"]["kernel"].split(" ")[0] in ("admm_iter_mixed_kernel", "symv_tile_split_kernel", "symv_tile_mixed_kernel")
     _fits_the_drivers_parser(r3)
     two = r3["detail"]["config"]["two_solves_in_flight"]
     assert two["value"] > 0 and two["through_lpvs_lpv_signals_multi_f64"]["same_coefficients_as_the_timed_steps"] is True
-    r2 = _run1(["--workload", "cfg2", "--iters", "200"])
+    r2 = _run1(["--full", "--workload", "cfg2", "--iters", "200"])
     assert need <= set(r2) and r2["unit"] == "signals/s" and r2["roofline"]["launch_us"] > 0
     _fits_the_drivers_parser(r2)
-    r5 = _run1(["--workload", "cfg5", "--log2n", "17", "--iters", "30", "--channels", "3", "--steps", "1"])
+    r5 = _run1(["--full", "--workload", "cfg5", "--log2n", "17", "--iters", "30", "--channels", "3", "--steps", "1"])
     assert need <= set(r5) and r5["roofline"]["kernel"] == "symv_tile_mfma_ws_kernel" and "4x4x4" in r5["detail"]["roofline"]["kernel"]
     _fits_the_drivers_parser(r5)
     assert len(r5["nnz_per_channel"]) == 3 and r5["factorisation"]["ms"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_carries_the_headline_and_nothing_measured_beside_it():
+    """Without --full a run only sets up, warms up, times its steps and prints the line: the contract's fields and what the timed steps'
+    own timers recorded, but no roofline, CPU baseline, solves in flight, other storages or sub-records (each of those takes runs of its own)."""
+    need = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config", "phase_ms"}
+    moved = {"roofline", "cpu_baseline", "gram_general_path", "cfg4_strong", "cfg2", "cfg5", "single_process", "cfg3_row_sharded"}
+    r3 = _run1(["--log2n", "16", "--iters", "60"])
+    assert need <= set(r3) and not moved & set(r3), sorted(set(r3))
+    assert r3["steps"] == 2 and r3["value"] > 0 and r3["ms_per_step"] > 0 and r3["higher_is_better"] is True and r3["dtype"] == "f64"
+    assert not {"two_solves_in_flight", "whole_step_with_8_byte_storage", "from_host_arrays"} & set(r3["detail"]["config"])
+    _fits_the_drivers_parser(r3)
+    r4 = _run1(["--workload", "cfg4", "--iters", "50", "--nwin", "8"])
+    assert need - {"phase_ms"} <= set(r4) and not moved & set(r4) and r4["psd_argmax"] == 33
 
 
 def test_bench_refuses_to_spawn_under_a_profiler_preload():
