@@ -554,7 +554,8 @@ int32_t lpvs_mel_project_f64(const double *power, int64_t nbins, int64_t frames,
 int32_t lpvs_mel_project_f32(const float *power, int64_t nbins, int64_t frames, const float *W, int64_t nmels, int32_t device, float *out);
 /* HIP-event times (ms) of the calling thread's last lpvs_stft call, out[0..8]: device work (Bluestein kernel, frame flags, FFTs,
  * epilogue), copy-out, total (setup + device work + copy-out), frames, path (1 LDS, 2 four-step, 3 Bluestein in LDS, 4 Bluestein
- * four-step), FFT length, frame pairs per workgroup, output rows, setup (host tables, band ranges, uploads) */
+ * four-step), FFT length, frame pairs per workgroup (0 on the LDS fallback, which sends the power through global memory when the
+ * epilogue's LDS regions do not fit next to one frame pair), output rows, setup (host tables, band ranges, uploads) */
 int32_t lpvs_stft_last_timing(double *out, int32_t n);
 
 #ifdef __cplusplus

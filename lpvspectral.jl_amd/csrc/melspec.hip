@@ -173,7 +173,8 @@ template <class T> struct FftJob {
     int in_mode = IN_SIGNAL;
     const T *s = nullptr, *win = nullptr;
     int64_t n = 0, hop = 0, frame0 = 0, nframes = 0;   // frame length, hop, first frame pair's frame, frames of the call
-    const int32_t *fbad = nullptr;    // four-step: frames holding a non-finite sample (loaded as zeros, their power is NaN)
+    const int32_t *fbad = nullptr;    // four-step / fallback: frame_bad_kernel's flags (a flagged frame loads as zeros) ...
+    const int32_t *fexp = nullptr;    // ... and max-abs exponents (the quieter frame of a pair is equalised to its partner)
     int chirp_in = 0;                 // Bluestein: x_t * chirp_t for t < nfft (the frame's logical length), 0 above
     int64_t blue_n = 0;
     RootTab chirp;
@@ -252,56 +253,105 @@ template <class T> __device__ inline void run_fft(double2 *buf, const FftJob<T> 
     }
 }
 
-// element t of frame pair p as one complex value (frame 2p real, 2p+1 imaginary), windowed, zero past the frame
+// frame flags: a non-finite windowed sample (the frame loads as zeros, its power is NaN), or every windowed sample zero (its power is
+// exactly 0: the shared FFT would give it its partner's rounding noise)
+enum : int { FRAME_OK = 0, FRAME_NONFINITE = 1, FRAME_ZERO = 2 };
+// The rounding error of the shared FFT follows the pair's combined size.  So the quieter frame of a pair is scaled up by 2^s, s the
+// difference of the two frames' max-abs exponents, and its power is scaled back by 2^-2s after the split.  Both scales are exact, so
+// each frame's error follows its own size and the result does not depend on the partner.
+__host__ __device__ inline int pair_shift(int flag, int e, int flag_partner, int e_partner) {
+    return (flag == FRAME_OK && flag_partner == FRAME_OK && e_partner > e) ? e_partner - e : 0;
+}
+__device__ inline int max_exponent(double m) { int e = 0; (void)frexp(m, &e); return e; }
+// one bin's power of one frame from its split parts: NaN for a non-finite frame, 0 for an all-zero one, else scaled back by 2^-2s
+__device__ inline double frame_power(int flag, int s, double re, double im, double sc) {
+    if (flag == FRAME_NONFINITE) return __builtin_nan("");
+    if (flag == FRAME_ZERO) return 0.0;
+    return ldexp((re * re + im * im) * sc, -2 * s);
+}
+
+// element t of frame pair p as one complex value (frame 2p real, 2p+1 imaginary), windowed, zero past the frame; with the flags of
+// frame_bad_kernel also zeroed where flagged and equalised (pair_shift)
 template <class T> __device__ inline double2 signal_value(const FftJob<T> &J, int64_t p, int64_t t) {
     if (t >= J.n) return make_double2(0.0, 0.0);
     const int64_t fa = J.frame0 + 2 * p, fb = fa + 1;
+    const bool hb = fb < J.nframes;
     const double w = J.win ? (double)J.win[t] : 1.0;
-    const double a = (J.fbad && J.fbad[fa]) ? 0.0 : (double)J.s[fa * J.hop + t] * w;
-    const double b = fb < J.nframes && !(J.fbad && J.fbad[fb]) ? (double)J.s[fb * J.hop + t] * w : 0.0;
+    double a = (double)J.s[fa * J.hop + t] * w;
+    double b = hb ? (double)J.s[fb * J.hop + t] * w : 0.0;
+    if (J.fbad) {
+        const int la = J.fbad[fa], lb = hb ? J.fbad[fb] : FRAME_ZERO;
+        a = la != FRAME_OK ? 0.0 : ldexp(a, pair_shift(la, J.fexp[fa], lb, hb ? J.fexp[fb] : 0));
+        b = lb != FRAME_OK ? 0.0 : ldexp(b, pair_shift(lb, J.fexp[fb], la, J.fexp[fa]));
+    }
     return make_double2(a, b);
 }
 
 template <class T>
 __global__ void __launch_bounds__(kThreads) stft_fft_kernel(FftJob<T> J) {
     __shared__ double2 buf[kFftMax];
-    __shared__ int bad[2 * kMaxPairs];   // frames with a non-finite sample or a non-finite power value
+    __shared__ int bad[2 * kMaxPairs];   // frame flags (FRAME_*; a non-finite power value counts as FRAME_NONFINITE)
+    __shared__ int shift[2 * kMaxPairs];  // pair_shift of each frame
+    __shared__ double red[2 * (kThreads / 64)];
     const int N = J.N, tid = (int)threadIdx.x;
     const int64_t q0 = (J.blk0 + (int64_t)blockIdx.x) * J.B;
     const int nb = (int)min<int64_t>(J.B, J.nseq - q0);
-    const bool whole = J.in_mode == IN_SIGNAL && J.nsub == 1;   // each sequence is one whole frame pair: flag its frames here
-    for (int i = tid; i < 2 * kMaxPairs; i += kThreads) bad[i] = 0;
+    // each sequence is one whole frame pair and no frame_bad_kernel pass ran: flag and equalise its frames here
+    const bool local = J.in_mode == IN_SIGNAL && J.nsub == 1 && !J.fbad;
+    for (int i = tid; i < 2 * kMaxPairs; i += kThreads) { bad[i] = FRAME_OK; shift[i] = 0; }
     __syncthreads();
-    // ---- load
-    int any_bad = 0;
+    // ---- load (local: the windowed samples alone; the flags, the equalisation and the chirp follow once the pair is known)
     for (int i = tid; i < nb * N; i += kThreads) {
         const int b = i / N, e = i - b * N;
         const int64_t q = q0 + b, p = q / J.nsub, c = q - p * J.nsub;
         double2 v;
         if (J.in_mode == IN_SIGNAL) {
             const int64_t t = (int64_t)e * J.nsub + c;
-            const double2 x = signal_value(J, p, t);
-            // flag on the windowed samples themselves: the chirp product below mixes the two frames' parts
-            if (whole && !(isfinite(x.x) && isfinite(x.y))) {   // a plain store of 1: the same value from every writer
-                if (!isfinite(x.x)) bad[2 * b] = 1;
-                if (!isfinite(x.y)) bad[2 * b + 1] = 1;
-                any_bad = 1;
-            }
-            if (J.chirp_in) v = t < J.blue_n ? cmul(x, chirp_of(J.chirp, t)) : make_double2(0.0, 0.0);
-            else v = x;
+            v = signal_value(J, p, t);
+            // flag on the windowed samples themselves: the chirp product mixes the two frames' parts
+            if (local) {   // a plain store of 1: the same value from every writer
+                if (!isfinite(v.x)) bad[2 * b] = FRAME_NONFINITE;
+                if (!isfinite(v.y)) bad[2 * b + 1] = FRAME_NONFINITE;
+            } else if (J.chirp_in)
+                v = t < J.blue_n ? cmul(v, chirp_of(J.chirp, t)) : make_double2(0.0, 0.0);
         } else
             v = J.gin[p * J.in_ps + c * J.in_cs + (int64_t)e * J.in_es];
         buf[i] = v;
     }
     for (int i = nb * N + tid; i < J.B * N; i += kThreads) buf[i] = make_double2(0.0, 0.0);
-    if (__syncthreads_or(any_bad)) {   // a non-finite sample would spread into the partner frame: zero that frame, its power is NaN
+    __syncthreads();
+    if (local) {
+        // the two frames' max |sample| per pair: G threads per pair (a power of two), a butterfly within the wave, then across waves
+        int G = 1;
+        while (2 * G * J.B <= kThreads) G *= 2;
+        const int b = tid / G, l = tid - b * G;
+        double ma = 0.0, mb = 0.0;
+        if (b < nb)
+            for (int e = l; e < N; e += G) { const double2 v = buf[b * N + e]; ma = fmax(ma, fabs(v.x)); mb = fmax(mb, fabs(v.y)); }
+        for (int o = 1; o < G && o < 64; o *= 2) { ma = fmax(ma, __shfl_xor(ma, o)); mb = fmax(mb, __shfl_xor(mb, o)); }
+        if (G > 64) {   // a pair spans G / 64 waves
+            const int w = tid / 64;
+            if ((tid & 63) == 0) { red[2 * w] = ma; red[2 * w + 1] = mb; }
+            __syncthreads();
+            if (l == 0)
+                for (int u = 1; u < G / 64; ++u) { ma = fmax(ma, red[2 * (w + u)]); mb = fmax(mb, red[2 * (w + u) + 1]); }
+        }
+        if (l == 0 && b < nb) {
+            const int fa = bad[2 * b] != FRAME_OK ? bad[2 * b] : (ma == 0.0 ? FRAME_ZERO : FRAME_OK);
+            const int fb = bad[2 * b + 1] != FRAME_OK ? bad[2 * b + 1] : (mb == 0.0 ? FRAME_ZERO : FRAME_OK);
+            const int ea = max_exponent(ma), eb = max_exponent(mb);
+            bad[2 * b] = fa; bad[2 * b + 1] = fb;
+            shift[2 * b] = pair_shift(fa, ea, fb, eb); shift[2 * b + 1] = pair_shift(fb, eb, fa, ea);
+        }
+        __syncthreads();
+        // a flagged frame loads as zeros (a non-finite sample would spread into its partner), the quieter frame is scaled, then the chirp
         for (int i = tid; i < nb * N; i += kThreads) {
             const int b = i / N, e = i - b * N;
-            if (!bad[2 * b] && !bad[2 * b + 1]) continue;
-            double2 x = signal_value(J, q0 + b, e);   // whole frame pairs only: sequence q0 + b is pair q0 + b, element e is sample e
-            if (bad[2 * b]) x.x = 0.0;
-            if (bad[2 * b + 1]) x.y = 0.0;
-            buf[i] = !J.chirp_in ? x : (e < J.blue_n ? cmul(x, chirp_of(J.chirp, e)) : make_double2(0.0, 0.0));
+            double2 x = buf[i];
+            x.x = bad[2 * b] != FRAME_OK ? 0.0 : ldexp(x.x, shift[2 * b]);
+            x.y = bad[2 * b + 1] != FRAME_OK ? 0.0 : ldexp(x.y, shift[2 * b + 1]);
+            if (J.chirp_in) x = e < J.blue_n ? cmul(x, chirp_of(J.chirp, e)) : make_double2(0.0, 0.0);
+            buf[i] = x;
         }
         __syncthreads();
     }
@@ -352,8 +402,8 @@ __global__ void __launch_bounds__(kThreads) stft_fft_kernel(FftJob<T> J) {
             const double ar = (zk.x + zm.x) * 0.5, ai = (zk.y - zm.y) * 0.5;
             const double br = (zk.y + zm.y) * 0.5, bi = (zm.x - zk.x) * 0.5;
             const double sc = row_scale(k, nbins, nf, E.m1, E.m2);
-            pa[u] = bad[2 * b] ? __builtin_nan("") : (ar * ar + ai * ai) * sc;
-            pb[u] = bad[2 * b + 1] ? __builtin_nan("") : (br * br + bi * bi) * sc;
+            pa[u] = frame_power(bad[2 * b], shift[2 * b], ar, ai, sc);
+            pb[u] = frame_power(bad[2 * b + 1], shift[2 * b + 1], br, bi, sc);
         }
     }
     __syncthreads();   // every Z read before the power overwrites the buffer
@@ -370,8 +420,8 @@ __global__ void __launch_bounds__(kThreads) stft_fft_kernel(FftJob<T> J) {
             } else {
                 pw[(2 * b) * nbins + k] = pa[u];
                 pw[(2 * b + 1) * nbins + k] = pb[u];
-                if (!isfinite(pa[u])) bad[2 * b] = 1;        // a plain store of 1: the same value from every writer
-                if (!isfinite(pb[u])) bad[2 * b + 1] = 1;
+                if (!isfinite(pa[u])) bad[2 * b] = FRAME_NONFINITE;        // a plain store: the same value from every writer
+                if (!isfinite(pb[u])) bad[2 * b + 1] = FRAME_NONFINITE;
             }
         }
     }
@@ -383,7 +433,7 @@ __global__ void __launch_bounds__(kThreads) stft_fft_kernel(FftJob<T> J) {
         const int f = it / E.nmels, i = it - f * E.nmels;
         const int64_t g = J.frame0 + 2 * q0 + f;
         if (g >= E.nframes) continue;
-        const double v = bad[f] ? __builtin_nan("") : mel_band(E.W + E.woff[i], E.blo[i], E.bhi[i], pw + (int64_t)f * nbins);
+        const double v = bad[f] == FRAME_NONFINITE ? __builtin_nan("") : mel_band(E.W + E.woff[i], E.blo[i], E.bhi[i], pw + (int64_t)f * nbins);
         if (E.kind == LPVS_STFT_MEL) E.out[g * E.nmels + i] = (T)v;
         else mel[it] = v;
     }
@@ -411,11 +461,13 @@ inline unsigned frame_blocks(int64_t count) { return (unsigned)std::min<int64_t>
 template <class T>
 __global__ void __launch_bounds__(kEpiThreads) split_power_kernel(const double2 *Z, int64_t zps, int64_t nfft, int64_t nbins, double m1, double m2,
                                                                   int blue, RootTab chirp, int64_t m, int64_t frame0, int64_t nframes,
-                                                                  const int32_t *fbad, T *pw, int64_t pw_frame0, int64_t npairs) {
+                                                                  const int32_t *fbad, const int32_t *fexp, T *pw, int64_t pw_frame0, int64_t npairs) {
   for (int64_t p = blockIdx.x; p < npairs; p += gridDim.x) {
     const int64_t fa = frame0 + 2 * p, fb = fa + 1;
     const double2 *z = Z + p * zps;
-    const bool bada = fbad && fbad[fa], badb = fbad && fb < nframes && fbad[fb];
+    const bool hb = fb < nframes;
+    const int la = fbad[fa], lb = hb ? fbad[fb] : FRAME_ZERO;
+    const int sa = pair_shift(la, fexp[fa], lb, hb ? fexp[fb] : 0), sb = hb ? pair_shift(lb, fexp[fb], la, fexp[fa]) : 0;
     for (int64_t k = threadIdx.x; k < nbins; k += kEpiThreads) {
         const int64_t km = k == 0 ? 0 : nfft - k;
         double2 zk = z[k], zm = z[km];
@@ -426,8 +478,8 @@ __global__ void __launch_bounds__(kEpiThreads) split_power_kernel(const double2 
         const double ar = (zk.x + zm.x) * 0.5, ai = (zk.y - zm.y) * 0.5;
         const double br = (zk.y + zm.y) * 0.5, bi = (zm.x - zk.x) * 0.5;
         const double sc = row_scale(k, nbins, nfft, m1, m2);
-        pw[(fa - pw_frame0) * nbins + k] = (T)(bada ? __builtin_nan("") : (ar * ar + ai * ai) * sc);
-        if (fb < nframes) pw[(fb - pw_frame0) * nbins + k] = (T)(badb ? __builtin_nan("") : (br * br + bi * bi) * sc);
+        pw[(fa - pw_frame0) * nbins + k] = (T)frame_power(la, sa, ar, ai, sc);
+        if (hb) pw[(fb - pw_frame0) * nbins + k] = (T)frame_power(lb, sb, br, bi, sc);
     }
   }
 }
@@ -460,14 +512,29 @@ __global__ void __launch_bounds__(kEpiThreads) epilogue_kernel(const P *pw, int6
     }
 }
 
-// frames holding a non-finite sample (a workgroup per frame, striding over the frames; the paths whose sequences hold parts of a frame)
+// each frame's flag (FRAME_*) and max-abs exponent, on the windowed samples (a workgroup per frame, striding over the frames; the
+// paths whose sequences do not hold whole frame pairs in one workgroup)
 template <class T>
-__global__ void __launch_bounds__(kEpiThreads) frame_bad_kernel(const T *s, int64_t n, int64_t hop, int32_t *fbad, int64_t nframes) {
+__global__ void __launch_bounds__(kEpiThreads) frame_bad_kernel(const T *s, const T *win, int64_t n, int64_t hop, int32_t *fbad, int32_t *fexp,
+                                                                int64_t nframes) {
+    __shared__ double red[kEpiThreads / 64];
     for (int64_t f = blockIdx.x; f < nframes; f += gridDim.x) {
         int bad = 0;
-        for (int64_t t = threadIdx.x; t < n; t += kEpiThreads) bad |= !isfinite((double)s[f * hop + t]);
+        double mx = 0.0;
+        for (int64_t t = threadIdx.x; t < n; t += kEpiThreads) {
+            const double v = (double)s[f * hop + t] * (win ? (double)win[t] : 1.0);   // as signal_value
+            bad |= !isfinite(v);
+            mx = fmax(mx, fabs(v));
+        }
+        for (int o = 1; o < 64; o *= 2) mx = fmax(mx, __shfl_xor(mx, o));
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x / 64] = mx;
         bad = __syncthreads_or(bad);
-        if (threadIdx.x == 0) fbad[f] = bad;
+        if (threadIdx.x == 0) {
+            for (int w = 1; w < kEpiThreads / 64; ++w) mx = fmax(mx, red[w]);
+            fbad[f] = bad ? FRAME_NONFINITE : (mx == 0.0 ? FRAME_ZERO : FRAME_OK);
+            fexp[f] = bad ? 0 : max_exponent(mx);
+        }
+        __syncthreads();   // red is rewritten by the next frame
     }
 }
 
@@ -710,7 +777,7 @@ int32_t stft_impl(int32_t kind, const T *s_in, int64_t L, int64_t n, int64_t nov
         const size_t avail = fr + pool_cached_bytes(device);
         const size_t need = (dev_out ? 0 : sizeof(T) * (size_t)(k * rows)) + (device_of_ptr(s_in) == device ? 0 : sizeof(T) * (size_t)L) +
                             per_pair + power_per_pair + (blue ? sizeof(double2) * (size_t)m * 3 : 0) +
-                            (lds && !fallback ? 0 : sizeof(int32_t) * (size_t)k) +                        // frame flags
+                            (lds && !fallback ? 0 : 2 * sizeof(int32_t) * (size_t)k) +                    // frame flags, exponents
                             (fallback ? sizeof(double) * (size_t)(k * nbins) + sizeof(double2) * (size_t)(npair_all * flen) : 0);
         if (need > avail) {
             set_error("spectrogram: %lld frames of nfft %lld need %.2f GB of device memory, %.2f GB are free", (long long)k, (long long)nfft,
@@ -720,7 +787,7 @@ int32_t stft_impl(int32_t kind, const T *s_in, int64_t L, int64_t n, int64_t nov
     }
     LPVS_HIP(hipEventRecord(ev.e[0], s));   // setup: host tables, band ranges, uploads (the stream is idle until e[1])
     Staged<T> ds, dw;
-    DevBuf dout, tmp, zbuf, pwbuf, bvec, btmp, bhat, fbad;
+    DevBuf dout, tmp, zbuf, pwbuf, bvec, btmp, bhat, fbad, fexp;
     DrainOnExit drain(s);
     LPVS_TRY(ds.set(s_in, L, device, s));
     if (window) {
@@ -745,12 +812,13 @@ int32_t stft_impl(int32_t kind, const T *s_in, int64_t L, int64_t n, int64_t nov
     FftJob<T> J;
     J.in_mode = IN_SIGNAL; J.s = ds.p; J.win = dw.p; J.n = n; J.hop = hop; J.nframes = k;
     if (blue) { J.chirp_in = 1; J.blue_n = nfft; J.chirp = chirp.tab; }
-    // the four-step's sequences (and the LDS fallback's split) do not see whole frames: flag the frames with a non-finite sample first
+    // the four-step's sequences (and the LDS fallback's split) do not see whole frames: flag the frames and take their max-abs exponents first
     auto flag_frames = [&]() -> int32_t {
         LPVS_TRY(fbad.alloc(sizeof(int32_t) * (size_t)k));
-        frame_bad_kernel<T><<<frame_blocks(k), kEpiThreads, 0, s>>>(ds.p, n, hop, fbad.as<int32_t>(), k);
+        LPVS_TRY(fexp.alloc(sizeof(int32_t) * (size_t)k));
+        frame_bad_kernel<T><<<frame_blocks(k), kEpiThreads, 0, s>>>(ds.p, dw.p, n, hop, fbad.as<int32_t>(), fexp.as<int32_t>(), k);
         LPVS_HIP(hipGetLastError());
-        J.fbad = fbad.as<int32_t>();
+        J.fbad = fbad.as<int32_t>(); J.fexp = fexp.as<int32_t>();
         return LPVS_OK;
     };
 
@@ -791,11 +859,12 @@ int32_t stft_impl(int32_t kind, const T *s_in, int64_t L, int64_t n, int64_t nov
             LPVS_TRY(zbuf.alloc(sizeof(double2) * (size_t)(npair_all * flen)));
             J.gout = zbuf.as<double2>(); J.out_ps = flen; J.out_cs = 0; J.out_es = 1;
             LPVS_TRY(launch_fft(J, s));
+            B = 0;
             // Z (already through the Bluestein inverse when blue) -> power
             split_power_kernel<double><<<frame_blocks(npair_all), kEpiThreads, 0, s>>>(zbuf.as<double2>(), flen, nfft, nbins, E.m1, E.m2, 0, RootTab{},
-                                                                                      1, 0, k, J.fbad, pwbuf.as<double>(), 0, npair_all);
+                                                                                      1, 0, k, J.fbad, J.fexp, pwbuf.as<double>(), 0, npair_all);
             LPVS_HIP(hipGetLastError());
-            const size_t shb = sizeof(double) * (size_t)(nmels + nmfcc);
+            const size_t shb = kind == LPVS_STFT_MFCC ? sizeof(double) * (size_t)(nmels + nmfcc) : 0;
             epilogue_kernel<double, T><<<frame_blocks(k), kEpiThreads, shb, s>>>(pwbuf.as<double>(), 0, E, 0, k);
             LPVS_HIP(hipGetLastError());
         }
@@ -822,11 +891,11 @@ int32_t stft_impl(int32_t kind, const T *s_in, int64_t L, int64_t n, int64_t nov
                 LPVS_TRY(four_step(A, lt, np, tmp.as<double2>(), zbuf.as<double2>(), flen, s, nullptr));
             if (kind == LPVS_STFT_POWER) {
                 split_power_kernel<T><<<frame_blocks(np), kEpiThreads, 0, s>>>(zbuf.as<double2>(), flen, nfft, nbins, E.m1, E.m2, blue, chirp.tab, m,
-                                                                               f0, k, fbad.as<int32_t>(), dst, 0, np);
+                                                                               f0, k, fbad.as<int32_t>(), fexp.as<int32_t>(), dst, 0, np);
                 LPVS_HIP(hipGetLastError());
             } else {
                 split_power_kernel<double><<<frame_blocks(np), kEpiThreads, 0, s>>>(zbuf.as<double2>(), flen, nfft, nbins, E.m1, E.m2, blue,
-                                                                                    chirp.tab, m, f0, k, fbad.as<int32_t>(), pwbuf.as<double>(), f0, np);
+                                                                                    chirp.tab, m, f0, k, fbad.as<int32_t>(), fexp.as<int32_t>(), pwbuf.as<double>(), f0, np);
                 LPVS_HIP(hipGetLastError());
                 const int64_t nfr = std::min<int64_t>(2 * np, k - f0);
                 const size_t shb = kind == LPVS_STFT_MFCC ? sizeof(double) * (size_t)(nmels + nmfcc) : 0;
@@ -843,7 +912,7 @@ int32_t stft_impl(int32_t kind, const T *s_in, int64_t L, int64_t n, int64_t nov
     for (int i = 0; i < 3; ++i) LPVS_HIP(hipEventElapsedTime(&ms[i], ev.e[i], ev.e[i + 1]));
     // [0] device work: Bluestein kernel, frame flags, FFTs, epilogue, [1] copy-out, [2] total (setup + [0] + [1]), [3] frames,
     // [4] path (1 LDS, 2 four-step, 3 Bluestein in LDS, 4 Bluestein four-step), [5] FFT length, [6] frame pairs per workgroup (LDS
-    // paths), [7] rows, [8] setup: host tables, band ranges and uploads
+    // paths; 0 on the LDS fallback through global power columns), [7] rows, [8] setup: host tables, band ranges and uploads
     g_timing[0] = ms[1]; g_timing[1] = ms[2]; g_timing[2] = (double)ms[0] + ms[1] + ms[2]; g_timing[3] = (double)k; g_timing[4] = path;
     g_timing[5] = (double)flen; g_timing[6] = B; g_timing[7] = (double)rows; g_timing[8] = ms[0];
     return LPVS_OK;

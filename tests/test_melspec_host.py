@@ -96,3 +96,86 @@ def test_device_entries_raise_without_a_device(L):
     S = L.Spectrogram(np.ones((63, 4)), np.arange(63.0), np.arange(4.0))
     with pytest.raises(L.DeviceError):
         L.melspectrogram(S)
+
+
+@pytest.mark.parametrize("nfft", [7 ** 9, 5 ** 11, 2 ** 25 + 1])
+def test_unsupported_lengths_raise_before_any_device(L, nfft):
+    """7^9 and 5^11 are 7-smooth with no split into two factors <= 8192; 2^25 + 1 (3·11·251·4051) needs a Bluestein length above 2^26.
+    The count-only call decides this before it looks for a device."""
+    with pytest.raises(NotImplementedError):
+        L.spectrogram(np.zeros(16), 16, 0, nfft=nfft)
+    with pytest.raises(NotImplementedError):
+        L.spectrogram(np.zeros(16, dtype=np.float32), 16, 0, nfft=nfft)
+
+
+# ---- the long-double reference and its bound (tests/_melspec_ref.py: power_ld, power_bound) -------------------------------------------
+@pytest.mark.parametrize("nfft", [1, 2, 3, 7, 11, 64, 97, 100, 127, 343, 1000, 1009, 4096, 4099, 8191, 8192])
+def test_power_ld_matches_numpy(nfft):
+    rng = np.random.default_rng(nfft)
+    n = max(1, nfft - nfft // 5)
+    y = rng.standard_normal(4 * n + 3)
+    for window, fs in ((None, 1), (rng.random(n), 3.5)):
+        P, Pt, r_err = R.power_ld(y, n, n // 3, nfft, fs=fs, window=window)
+        Pn = R.power(y, n, n // 3, nfft, fs=fs, window=window)
+        assert P.shape == Pn.shape and np.allclose(Pt, Pn.sum(axis=0), rtol=1e-13, atol=0)
+        assert r_err < 1e-13
+        np.testing.assert_allclose(P, Pn, rtol=0, atol=1e-13 * Pt.max())
+        idx = [0, P.shape[1] - 1]
+        Pi, Pti, _ = R.power_ld(y, n, n // 3, nfft, fs=fs, window=window, idx=idx)
+        assert np.array_equal(Pi, P[:, idx]) and np.array_equal(Pti, Pt[idx])
+
+
+@pytest.mark.parametrize("nfft", [2 ** 16, 3 * 2 ** 16, 5 ** 8])
+def test_numpy_fft_within_c_np(nfft):
+    """The largest lengths check the device against numpy's f64 FFT with C_NP added to c: numpy itself must be within C_NP."""
+    y = np.random.default_rng(nfft).standard_normal(2 * nfft)
+    P, Pt, r_err = R.power_ld(y, nfft, 0, nfft)
+    Pn, _, _ = R.power_ld(y, nfft, 0, nfft, ld=False)
+    assert (np.abs(Pn - P) <= R.power_bound(P, Pt, nfft, R.C_NP, r_err)).all()
+
+
+def test_c_needed_inverts_the_bound():
+    rng = np.random.default_rng(1)
+    P = rng.random((33, 4)) ** 4
+    Pt = P.sum(axis=0)
+    for c in (0.01, 1.0, 7.0):
+        b = R.power_bound(P, Pt, 64, c)
+        np.testing.assert_allclose(R.c_needed(b, P, Pt, 64), c, rtol=1e-9)
+    assert (R.c_needed(np.zeros_like(P), P, Pt, 64) == 0).all()
+
+
+@pytest.mark.parametrize("nfft", [1000, 4099, 8192])
+def test_bound_is_sharp(nfft):
+    """One bin perturbed by 1e-12 relative fails the bound at the largest c of any path, and the old 1e-12·Ptot check misses it."""
+    y = np.random.default_rng(nfft).standard_normal(3 * nfft)
+    P, Pt, r_err = R.power_ld(y, nfft, 0, nfft)
+    Pn = R.power(y, nfft, 0, nfft)
+    cmax = 14.0                                                       # the largest per-path c of tests/test_gpu_stft_paths.py (LDS)
+    bound = R.power_bound(P, Pt, nfft, cmax, r_err)
+    assert (np.abs(Pn - P) <= bound).all()
+    k = int(np.argmax(P[:, 1]))
+    Pp = Pn.copy()
+    Pp[k, 1] *= 1 + 1e-12
+    assert not (np.abs(Pp - P) <= bound).all()
+    assert (np.abs(Pp - P) <= 1e-12 * Pt).all()
+    for c in (1e-2, 1.0):                                             # a zero frame's bound is exactly 0
+        assert (R.power_bound(np.zeros((5, 1)), np.zeros(1), 64, c) == 0).all()
+
+
+def test_mel_and_mfcc_bounds_cover_their_own_rounding(L):
+    """The reference's own mel and MFCC, recomputed from numpy's power, stay inside the bounds carried from the power bound."""
+    nfft, nmels, nmfcc = 1024, 40, 13
+    y = np.random.default_rng(3).standard_normal(5 * nfft)
+    P, Pt, r_err = R.power_ld(y, nfft, 0, nfft)
+    Pn = R.power(y, nfft, 0, nfft)
+    W = R.mel(1, 2 * (nfft // 2 + 1) - 1, nmels=nmels)
+    pb = R.power_bound(P, Pt, nfft, 14.0, r_err)
+    M, Mn = R.project(W, P), R.project(W, Pn)
+    mb = R.mel_bound(W, P, pb)
+    assert (np.abs(Mn - M) <= mb).all()
+    D = R.dct_matrix(nmfcc, nmels)
+    Cb = R.mfcc_bound(D, M, mb)
+    assert (np.abs(R.mfcc_from_mel(D, Mn) - R.mfcc_from_mel(D, M)) <= Cb).all()
+    M2 = M.copy()
+    M2[3, 2] *= 1 + 1e-9                                              # a 1e-9 relative error in one band is caught
+    assert not (np.abs(M2 - M) <= mb).all()
