@@ -558,6 +558,41 @@ int32_t lpvs_mel_project_f32(const float *power, int64_t nbins, int64_t frames, 
  * epilogue's LDS regions do not fit next to one frame pair), output rows, setup (host tables, band ranges, uploads) */
 int32_t lpvs_stft_last_timing(double *out, int32_t n);
 
+/* ---- g3  ComplexNormal sampling and the Monte-Carlo bands of the SpectralExt recipe   src/utilities.jl:80-174, src/plotting.jl:54-97
+ * Double precision only: the covariance of ls_spectral_lpv is always Float64, so these entry points have no _f32 twins.
+ * All matrices column-major; V, R, Phi_g and the outputs may be host or device memory unless stated otherwise.
+ *   lpvs_cholesky_upper_f64: U (n2 x n2, upper, strict lower triangle exactly zero) with U'U = V.  Only the upper triangle of V is
+ *     read (Hermitian(...) is :U).  A pivot that is not positive -> LPVS_ENUMERIC with its 0-based index in lpvs_last_error (Julia's
+ *     PosDefException); U_out is not written then.  Blocked, panels of 128, fixed summation order: bit-reproducible.
+ *   lpvs_randn_f64: rows row0 .. row0+rows-1 and columns 0 .. cols-1 of the standard-normal matrix of `seed` (rows x cols).
+ *     Element (i, j) depends on (seed, i, j) only: Philox4x32-10 with key (seed low word, seed high word) and counter (i low, i high,
+ *     p low, p high), p = j / 2; from its words w0..w3: a = (w0 >> 5) 2^26 + (w1 >> 6), b = (w2 >> 5) 2^26 + (w3 >> 6),
+ *     u1 = (a + 1) 2^-53 in (0, 1], r = sqrt(-2 log u1), t = b 2^-52 in [0, 2); column 2p is r cospi(t), column 2p+1 is r sinpi(t).
+ *   lpvs_cov_f64: mean (cols) and corrected covariance (cols x cols, both triangles) of the columns of A (rows x cols, rows >= 2,
+ *     cols <= 64), fixed-order reductions; mean_out and C_out are HOST arrays.
+ *   lpvs_cn_create_f64: a handle (*cn, an id) of the distribution with mean m_re + i m_im (n each) and the real 2n x 2n covariance V
+ *     in [re; im] order (the Sigma of ls_spectral_lpv); V is factored once and the factor stays on `device`.  lpvs_cn_destroy frees it
+ *     (an unknown id is ignored).
+ *   lpvs_cn_rand_f64: Z = m' .+ R U (src/utilities.jl:168-174), s draws: Z_re_out / Z_im_out are s x n (columns 1:n and n+1:2n).
+ *     R (s x 2n) or NULL: the normals of lpvs_randn_f64(seed, 0, s, 2n), generated on the fly (seed is ignored when R is given).
+ *   lpvs_cn_bands_f64: the draws of lpvs_cn_rand_f64(nMC), then for every frequency j < Nf and grid point i < G
+ *     d = dot(z[j + v Nf], Phi_g[i, v]) over v < nb (Julia's dot: z conjugated; n = Nf nb, Phi_g is G x nb) for every draw,
+ *     Fl / Fu = the 0-based order statistics nMC/10 - 1 and nMC - nMC/10 - 1 of |d|, Fm their mean (fixed-order sum); Pl / Pu / Pm the
+ *     same of angle(d) when phase != 0 (else they may be NULL and are not written).  Outputs Nf x G.
+ *     nMC < 10 -> LPVS_EARGUMENT (the reference indexes FB[:,:,0]); nMC > 16384 or nb > 1024 -> LPVS_EUNSUPPORTED (the draws of one
+ *     cell are sorted in one workgroup's LDS).
+ *   lpvs_cn_last_timing: HIP-event times (ms) of the calling thread's last calls, out[0..6]: factor (lpvs_cn_create_f64), sample,
+ *     bands, sample + bands, 2n, draws, cells. */
+int32_t lpvs_cholesky_upper_f64(const double *V, int64_t n2, int32_t device, double *U_out);
+int32_t lpvs_randn_f64(int64_t seed, int64_t row0, int64_t rows, int64_t cols, int32_t device, double *R_out);
+int32_t lpvs_cov_f64(const double *A, int64_t rows, int64_t cols, int32_t device, double *mean_out, double *C_out);
+int32_t lpvs_cn_create_f64(const double *m_re, const double *m_im, const double *V, int64_t n, int32_t device, int64_t *cn);
+int32_t lpvs_cn_destroy(int64_t cn);
+int32_t lpvs_cn_rand_f64(int64_t cn, int64_t s, int64_t seed, const double *R, double *Z_re_out, double *Z_im_out);
+int32_t lpvs_cn_bands_f64(int64_t cn, int64_t Nf, int64_t nb, const double *Phi_g, int64_t G, int64_t nMC, int64_t seed, const double *R,
+                          int32_t phase, double *Fl, double *Fu, double *Fm, double *Pl, double *Pu, double *Pm);
+int32_t lpvs_cn_last_timing(double *out, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif

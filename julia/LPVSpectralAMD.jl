@@ -19,7 +19,7 @@ const PO = ProximalOperators
 export ls_spectral, tls_spectral, ls_sparse_spectral, ls_sparse_spectral_lpv, ls_spectral_lpv, ls_windowpsd, ls_windowcsd,
        ls_cohere, ls_windowpsd_lpv, get_fourier_regressor, check_freq, default_freqs, Windows2, Windows3, mapwindows,
        SpectralExt, psd, reshape_params, ADMM, rect, hanning, autocov, autocor, isequidistant,
-       melspectrogram, mfcc, mel, spectrogram, Spectrogram, MelSpectrogram, MFCC, freq
+       melspectrogram, mfcc, mel, spectrogram, Spectrogram, MelSpectrogram, MFCC, freq, rand_cn, schedfunc
 
 const LIB = get(ENV, "LPVSPECTRAL_LIB", joinpath(@__DIR__, "..", "lpvspectral.jl_amd", "liblpvspectral.so"))
 
@@ -749,6 +749,83 @@ autocov(t::AbstractVector, h::AbstractVector{<:AbstractVector{<:Real}}, maxlag::
     _autofun(Int32(1), t, h, maxlag, Bool(normalize); device=device)
 autocor(t::AbstractVector, h::AbstractVector{<:AbstractVector{<:Real}}, maxlag::Real; normalize=false, device=0) =   # src/autocov.jl:16
     _autofun(Int32(2), t, h, maxlag, Bool(normalize); device=device)
+
+# ---- ComplexNormal draws and the Monte-Carlo bands of the SpectralExt recipe: src/utilities.jl:168-174, src/plotting.jl:54-106 --------
+# The reference's ComplexNormal type stays the reference's (small host algebra); these two entry points take what it holds.
+# rand_cn(m, V, s): s draws of the complex normal with mean m (complex n) and real 2n x 2n covariance V ([re; im] order), s x n.
+# normals (s x 2n) replaces the library's own counter-based stream of `seed` (Julia's randn stream is not reproduced).
+function _cn_create(m::AbstractVector{<:Complex}, V::AbstractMatrix{<:Real}, device::Integer)
+    mre = Vector{Float64}(real.(m)); mim = Vector{Float64}(imag.(m)); V64 = Matrix{Float64}(V)
+    size(V64) == (2length(mre), 2length(mre)) || throw(ArgumentError("V must be $(2length(mre)) x $(2length(mre))"))
+    h = Ref{Int64}(0)
+    GC.@preserve mre mim V64 check(@ccall LIB.lpvs_cn_create_f64(mre::Ptr{Float64}, mim::Ptr{Float64}, V64::Ptr{Float64},
+        Int64(length(mre))::Int64, Int32(device)::Int32, h::Ref{Int64})::Int32)
+    h[]
+end
+_cn_destroy(h::Int64) = (@ccall LIB.lpvs_cn_destroy(h::Int64)::Int32; nothing)
+
+function rand_cn(m::AbstractVector{<:Complex}, V::AbstractMatrix{<:Real}, s::Integer; seed::Integer=0, normals=nothing, device::Integer=0)
+    n = length(m)
+    h = _cn_create(m, V, device)
+    zre = Matrix{Float64}(undef, s, n); zim = Matrix{Float64}(undef, s, n)
+    try
+        if normals === nothing
+            GC.@preserve zre zim check(@ccall LIB.lpvs_cn_rand_f64(h::Int64, Int64(s)::Int64, Int64(seed)::Int64, C_NULL::Ptr{Float64},
+                zre::Ptr{Float64}, zim::Ptr{Float64})::Int32)
+        else
+            R64 = Matrix{Float64}(normals)
+            size(R64) == (s, 2n) || throw(ArgumentError("normals must be $s x $(2n)"))
+            GC.@preserve R64 zre zim check(@ccall LIB.lpvs_cn_rand_f64(h::Int64, Int64(s)::Int64, Int64(seed)::Int64, R64::Ptr{Float64},
+                zre::Ptr{Float64}, zim::Ptr{Float64})::Int32)
+        end
+    finally
+        _cn_destroy(h)
+    end
+    complex.(zre, zim)                                                                   # src/utilities.jl:173
+end
+
+# schedfunc(se; ...): the numbers of the plot recipe as a NamedTuple (w, v, F, P, FBl, FBu, FBm, PBl, PBu, PBm); the bands are `nothing`
+# without bounds or without se.Σ, PB* stay zero unless phase, and normalization divides F only (src/plotting.jl:99-106, as written).
+function schedfunc(se::SpectralExt; normalization=:none, normdim=:freq, bounds=true, nMC=5_000, phase=false, mcmean=false,
+                   seed::Integer=0, normals=nothing, device::Integer=0)
+    w = se.w[:]; Nf = length(w)
+    x = reshape_params(ComplexF64.(se.x), Nf); nb = size(x, 2)
+    G = Nf == 100 ? 101 : 100
+    vg = Vector{Float64}(collect(LinRange(minimum(se.V), maximum(se.V), G)))             # src/plotting.jl:62
+    Φg = Matrix{Float64}(undef, G, nb)
+    GC.@preserve vg Φg check(@ccall LIB.lpvs_basis_activation_f64(vg::Ptr{Float64}, Int64(G)::Int64, Int64(se.Nv)::Int64,
+        Int32(se.normalize)::Int32, Int32(se.coulomb)::Int32, Φg::Ptr{Float64})::Int32)
+    d = conj.(x) * transpose(Φg)                                                         # dot(x[j,:], ϕ) conjugates x (:76)
+    F = abs.(d); P = angle.(d)
+    FBl = FBu = FBm = PBl = PBu = PBm = nothing
+    if bounds && se.Σ !== nothing
+        nMC >= 10 || throw(ArgumentError("nMC must be at least 10, got $nMC"))
+        h = _cn_create(ComplexF64.(se.x[:]), se.Σ, device)
+        FBl = zeros(Nf, G); FBu = zeros(Nf, G); FBm = zeros(Nf, G); PBl = zeros(Nf, G); PBu = zeros(Nf, G); PBm = zeros(Nf, G)
+        try
+            if normals === nothing
+                GC.@preserve Φg FBl FBu FBm PBl PBu PBm check(@ccall LIB.lpvs_cn_bands_f64(h::Int64, Int64(Nf)::Int64, Int64(nb)::Int64,
+                    Φg::Ptr{Float64}, Int64(G)::Int64, Int64(nMC)::Int64, Int64(seed)::Int64, C_NULL::Ptr{Float64}, Int32(phase)::Int32,
+                    FBl::Ptr{Float64}, FBu::Ptr{Float64}, FBm::Ptr{Float64}, PBl::Ptr{Float64}, PBu::Ptr{Float64}, PBm::Ptr{Float64})::Int32)
+            else
+                R64 = Matrix{Float64}(normals)
+                size(R64) == (nMC, 2Nf * nb) || throw(ArgumentError("normals must be $nMC x $(2Nf * nb)"))
+                GC.@preserve Φg R64 FBl FBu FBm PBl PBu PBm check(@ccall LIB.lpvs_cn_bands_f64(h::Int64, Int64(Nf)::Int64, Int64(nb)::Int64,
+                    Φg::Ptr{Float64}, Int64(G)::Int64, Int64(nMC)::Int64, Int64(seed)::Int64, R64::Ptr{Float64}, Int32(phase)::Int32,
+                    FBl::Ptr{Float64}, FBu::Ptr{Float64}, FBm::Ptr{Float64}, PBl::Ptr{Float64}, PBu::Ptr{Float64}, PBm::Ptr{Float64})::Int32)
+            end
+        finally
+            _cn_destroy(h)
+        end
+    end
+    nd = normdim == :freq ? 1 : 2                                                        # :99
+    if normalization == :sum
+        F = F ./ (sum(F, dims=nd) / size(F, nd))                                         # :102
+    elseif normalization == :max
+        F = F ./ maximum(F, dims=nd)                                                     # :104
+    end
+    (w=w, v=vg, F=F, P=P, FBl=FBl, FBu=FBu, FBm=FBm, PBl=PBl, PBu=PBu, PBm=PBm, line=(mcmean && FBm !== nothing) ? FBm : F)
+end
 
 # ---- spectrogram / melspectrogram / mfcc: DSP.spectrogram + src/mel.jl (STFT, mel bands and MFCC on the device) ----------------
 # The filterbank and the DCT come from the library (host C, the reference's precision); the STFT and its epilogues run on the device.

@@ -167,6 +167,14 @@ SIGNATURES = {
     "lpvs_mel_project_f64": (_I32, [_P, _I64, _I64, _P, _I64, _I32, _P]),
     "lpvs_mel_project_f32": (_I32, [_P, _I64, _I64, _P, _I64, _I32, _P]),
     "lpvs_stft_last_timing": (_I32, [_P, _I32]),
+    "lpvs_cholesky_upper_f64": (_I32, [_P, _I64, _I32, _P]),
+    "lpvs_randn_f64": (_I32, [_I64, _I64, _I64, _I64, _I32, _P]),
+    "lpvs_cov_f64": (_I32, [_P, _I64, _I64, _I32, _P, _P]),
+    "lpvs_cn_create_f64": (_I32, [_P, _P, _P, _I64, _I32, _PI64]),
+    "lpvs_cn_destroy": (_I32, [_I64]),
+    "lpvs_cn_rand_f64": (_I32, [_I64, _I64, _I64, _P, _P, _P]),
+    "lpvs_cn_bands_f64": (_I32, [_I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _I32, _P, _P, _P, _P, _P, _P]),
+    "lpvs_cn_last_timing": (_I32, [_P, _I32]),
 }
 
 _lib = None

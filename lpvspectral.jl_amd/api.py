@@ -1663,3 +1663,384 @@ def stft_last_timing():
     check(lib().lpvs_stft_last_timing(out_ptr(o), 9))
     return dict(fft_ms=o[0], copy_out_ms=o[1], total_ms=o[2], frames=int(o[3]), path=int(o[4]), fft_length=int(o[5]),
                 pairs_per_workgroup=int(o[6]), rows=int(o[7]), setup_ms=o[8])
+
+
+# --------------------------------------------------------------------------- ComplexNormal, the SpectralExt recipe's numbers, detrend
+# (src/utilities.jl:1-17, :80-174, src/plotting.jl:54-106; csrc/cnormal.hip)
+def _herm_upper(A):
+    """``Hermitian(A)`` / ``Symmetric(A)`` for real A: the upper triangle decides (Julia's default ``:U``)."""
+    A = np.asarray(A)
+    U = np.triu(A, 1)
+    return U + U.conj().T + np.diag(np.diag(A).real)
+
+
+def _sym_upper(A):
+    """``Symmetric(A)`` (no conjugation, also for complex A)."""
+    A = np.asarray(A)
+    return np.triu(A) + np.triu(A, 1).T
+
+
+def _chol_upper(A):
+    """``cholesky(A).U`` of a small dense host matrix: U'U = A (numpy's factor is the lower one)."""
+    try:
+        return np.linalg.cholesky(_herm_upper(A)).conj().T
+    except np.linalg.LinAlgError as e:
+        raise _lib.NumericError(f"matrix is not positive definite (PosDefException): {e}") from None
+
+
+def _gamma_c(a, C=None):
+    """(Γ, C) of a call ``f(Γ, C)`` or ``f(cn)`` (src/utilities.jl:141-143)."""
+    if isinstance(a, ComplexNormal):
+        return a.Γ, a.C
+    return np.asarray(a), np.asarray(C)
+
+
+def cn_V2ΓC(V):
+    """src/utilities.jl:113-124 -> ``(Γ, C)`` as matrices.  The reference factors Γ here; this mirror keeps the matrix and factors it
+    when :func:`pdf` asks (an 8192 × 8192 Σ costs nothing until then), so ``Matrix(Γ)`` is Γ itself, not the product of its rounded factors."""
+    V = _sym_upper(np.asarray(V, dtype=np.float64))
+    n = V.shape[0] // 2
+    Vxx, Vyy, Vxy, Vyx = V[:n, :n], V[n:, n:], V[:n, n:], V[n:, :n]
+    return (Vxx + Vyy) + 1j * (Vyx - Vxy), _sym_upper((Vxx - Vyy) + 1j * (Vyx + Vxy))
+
+
+def cn_fVxx(Γ, C=None):
+    Γ, C = _gamma_c(Γ, C)
+    return (Γ + C).real / 2          # src/utilities.jl:131
+
+
+def cn_fVyy(Γ, C=None):
+    Γ, C = _gamma_c(Γ, C)
+    return (Γ - C).real / 2          # :132
+
+
+def cn_fVxy(Γ, C=None):
+    Γ, C = _gamma_c(Γ, C)
+    return (-Γ + C).imag / 2         # :133
+
+
+def cn_fVyx(Γ, C=None):
+    Γ, C = _gamma_c(Γ, C)
+    return (Γ + C).imag / 2          # :134
+
+
+def cn_Vxx(Γ, C=None):
+    """src/utilities.jl:126-129: the upper Cholesky factor of the block (Julia returns the ``Cholesky`` object)."""
+    return _chol_upper(cn_fVxx(Γ, C))
+
+
+def cn_Vyy(Γ, C=None):
+    return _chol_upper(cn_fVyy(Γ, C))
+
+
+def cn_Vxy(Γ, C=None):
+    return _chol_upper(cn_fVxy(Γ, C))
+
+
+def cn_Vyx(Γ, C=None):
+    return _chol_upper(cn_fVyx(Γ, C))
+
+
+def cn_Vs(Γ, C=None):
+    return cn_Vxx(Γ, C), cn_Vyy(Γ, C), cn_Vxy(Γ, C), cn_Vyx(Γ, C)   # :136
+
+
+def cn_fV(Γ, C=None):
+    return np.block([[cn_fVxx(Γ, C), cn_fVxy(Γ, C)], [cn_fVyx(Γ, C), cn_fVyy(Γ, C)]])   # :137
+
+
+def cn_V(Γ, C=None):
+    """src/utilities.jl:138: ``cholesky(Hermitian(cn_fV(Γ,C)))``, its upper factor (host; :func:`rand` factors on the device)."""
+    return _chol_upper(cn_fV(Γ, C))
+
+
+def Σ(cn):
+    """src/utilities.jl:139, as written (the reference's own ``# TODO: check this``): ``Matrix(cn.Γ)``."""
+    return np.array(cn.Γ, copy=True)
+
+
+_COV_DEVICE_ROWS = 4096   # sample matrices with at least this many rows are centred and reduced on the device (lpvs_cov_f64)
+
+
+def _cov_columns(A, device):
+    """``mean(A, dims=1)`` and ``cov(A)`` (corrected) of a tall matrix.  A few rows are small dense host algebra; the reference's own
+    10⁶ × 6 case goes through the fixed-order reduction kernels of csrc/cnormal.hip."""
+    A = np.asfortranarray(A, dtype=np.float64)
+    rows, cols = A.shape
+    if rows < _COV_DEVICE_ROWS:
+        return A.mean(axis=0), np.atleast_2d(np.cov(A, rowvar=False, ddof=1))
+    mean, Cm = np.zeros(cols), np.zeros((cols, cols), order="F")
+    check(lib().lpvs_cov_f64(out_ptr(A), rows, cols, int(device), out_ptr(mean), out_ptr(Cm)))
+    return mean, Cm
+
+
+class ComplexNormal:
+    """src/utilities.jl:83-111.  Fields ``m`` (complex n), ``Γ`` (n × n, Hermitian; kept as a matrix and factored lazily) and ``C``
+    (n × n, complex symmetric).  The reference's four constructors:
+
+    * ``ComplexNormal(X, Y)``: real sample matrices of equal shape (rows are samples), ``V = cov([X Y])``;
+    * ``ComplexNormal(Xc)``: a complex sample matrix;
+    * ``ComplexNormal(m, V)``: a real mean of length 2n (``[re; im]``) and the real 2n × 2n covariance;
+    * ``ComplexNormal(mc, V)``: a complex mean of length n and the same V.
+
+    Built from V, the instance remembers V: :func:`rand` factors it directly (``cn_fV(cn_V2ΓC(V)) == V`` to rounding)."""
+
+    def __init__(self, a, b=None, device=0):
+        self._V = None
+        a = _host_c(a)
+        if b is None:
+            if not np.iscomplexobj(a):
+                raise TypeError("ComplexNormal(X): X must be complex (use ComplexNormal(X, Y) for real sample matrices)")
+            a, b = a.real, a.imag                                             # :97-99
+        else:
+            b = _host_c(b)
+        if a.shape == b.shape and not (a.ndim == 1 and b.ndim == 2):          # (X, Y)  :89-95
+            X, Y = np.atleast_2d(a.T).T, np.atleast_2d(b.T).T
+            mean, V = _cov_columns(np.concatenate([X, Y], axis=1), device)
+            n = X.shape[1]
+            self.m = mean[:n] + 1j * mean[n:]
+            self._V = _sym_upper(V)
+        else:                                                                 # (m, V)  :101-111
+            if a.ndim != 1 or b.ndim != 2 or b.shape[0] != b.shape[1]:
+                raise ValueError("ComplexNormal(m, V): m must be a vector and V a square matrix")
+            if np.iscomplexobj(a):
+                self.m = np.array(a, dtype=np.complex128)
+            else:
+                if len(a) % 2:
+                    raise ValueError("ComplexNormal(m, V): a real mean needs an even length ([re; im])")   # Int(length(m)/2): InexactError
+                n = len(a) // 2
+                self.m = a[:n] + 1j * a[n:]
+            if b.shape[0] != 2 * len(self.m):
+                raise ValueError(f"ComplexNormal(m, V): V is {b.shape[0]} x {b.shape[1]}, the mean has {len(self.m)} complex components")
+            self._V = _sym_upper(np.asarray(b, dtype=np.float64))
+        self.Γ, self.C = cn_V2ΓC(self._V)
+
+    @classmethod
+    def from_parts(cls, m, Γ, C):
+        """The inner constructor ``ComplexNormal(m, Γ, C)`` (:83-87)."""
+        self = cls.__new__(cls)
+        self._V = None
+        self.m, self.Γ, self.C = np.asarray(m, dtype=np.complex128), _herm_upper(np.asarray(Γ, dtype=np.complex128)), _sym_upper(np.asarray(C, dtype=np.complex128))
+        return self
+
+    def covariance(self):
+        """The real 2n × 2n covariance in ``[re; im]`` order: the V the instance was built from, else ``cn_fV(Γ, C)``."""
+        return self._V if self._V is not None else cn_fV(self.Γ, self.C)
+
+
+def _host_c(a):
+    """A host array that keeps a complex eltype."""
+    if hasattr(a, "detach"):
+        a = a.detach().cpu().numpy()
+    a = np.asarray(a)
+    return a if np.iscomplexobj(a) else a.astype(np.float64, copy=False)
+
+
+def pdf(cn, z):
+    """src/utilities.jl:151-163, the formula as written (``conj(Γ) = Γ`` is the reference's own remark)."""
+    Γ, Cc, m = cn.Γ, cn.C, cn.m
+    z = np.asarray(z, dtype=np.complex128)
+    k = len(m)
+    U = _chol_upper(Γ)                                                        # the lazily taken factor: PosDefException here
+    Γinv = np.linalg.inv(Γ)
+    R = np.conj(Cc).conj().T @ Γinv
+    P = Γ - R @ Cc
+    zmm, czmm = z - m, np.conj(z) - np.conj(m)
+    ld = np.concatenate([np.conj(czmm), np.conj(zmm)])
+    rd = np.concatenate([zmm, czmm])
+    S = np.block([[Γ, Cc], [np.conj(Cc), Γ]])
+    detΓ = float(np.prod(np.diag(U).real) ** 2)                               # det(::Cholesky)
+    return 1 / (np.pi ** k * np.sqrt(detΓ * np.linalg.det(P) + 0j)) * np.exp(-0.5 * (ld @ np.linalg.solve(S, rd)))
+
+
+def affine_transform(cn, A, b):
+    """src/utilities.jl:165."""
+    A = np.asarray(A)
+    return ComplexNormal.from_parts(A @ cn.m + np.asarray(b), A @ cn.Γ @ np.conj(A.T), A @ cn.C @ A.T)
+
+
+def _normals_arg(normals, s, n2):
+    """(keepalive, pointer) of a caller-supplied s × 2n matrix of standard normals, column-major on its own side (host or device)."""
+    if normals is None:
+        return None, None
+    if tuple(normals.shape) != (s, n2):
+        raise ValueError(f"normals must be {s} x {n2}, got {tuple(normals.shape)}")
+    if _lib.is_device_array(normals):
+        k, p, _ = as_f64(normals.t().contiguous())                           # row-major 2n × s == column-major s × 2n
+        return k, p
+    k, p, _ = as_f64(normals)
+    return k, p
+
+
+class _CnHandle:
+    """The device side of a ComplexNormal: V factored once, the factor resident (lpvs_cn_create_f64)."""
+
+    def __init__(self, m, V, device):
+        m = np.asarray(m, dtype=np.complex128)
+        self.n = len(m)
+        mre, mim = np.ascontiguousarray(m.real), np.ascontiguousarray(m.imag)
+        kv, pv, cnt = as_f64(V)
+        if cnt != 4 * self.n * self.n:
+            raise ValueError(f"the covariance must be {2 * self.n} x {2 * self.n}")
+        h = C.c_int64(0)
+        check(lib().lpvs_cn_create_f64(out_ptr(mre), out_ptr(mim), pv, self.n, int(device), C.byref(h)))
+        self.h = h.value
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        if self.h:
+            lib().lpvs_cn_destroy(C.c_int64(self.h))
+            self.h = 0
+        return False
+
+
+def rand(cn, s, seed=0, normals=None, device=0):
+    """``rand(cn, s)`` (src/utilities.jl:168-174): s draws, an s × n complex matrix.  ``z = m' .+ R·U`` with U the upper Cholesky
+    factor of the real covariance, on the device.  R is ``normals`` (s × 2n, numpy or a float64 device tensor) or, when ``None``, the
+    library's own counter-based stream of ``seed`` (:func:`randn`); Julia's ``randn`` stream is not reproduced."""
+    s = int(s)
+    if s < 1:
+        raise ValueError("the number of draws must be positive")
+    kr, pr = _normals_arg(normals, s, 2 * len(cn.m))
+    with _CnHandle(cn.m, cn.covariance(), device) as h:
+        zr, zi = np.zeros((s, h.n), order="F"), np.zeros((s, h.n), order="F")
+        check(lib().lpvs_cn_rand_f64(h.h, s, int(seed), pr, out_ptr(zr), out_ptr(zi)))
+    return zr + 1j * zi
+
+
+def randn(rows, cols, seed=0, row0=0, device=0):
+    """Rows ``row0 … row0+rows−1`` of the library's standard-normal matrix of ``seed`` (numpy, rows × cols): element (i, j) depends on
+    (seed, i, j) only -- Philox4x32-10, Box–Muller (include/lpvspectral.h g3)."""
+    R = np.zeros((int(rows), int(cols)), order="F")
+    check(lib().lpvs_randn_f64(int(seed), int(row0), int(rows), int(cols), int(device), out_ptr(R)))
+    return R
+
+
+def cholesky_upper(V, device=0):
+    """U (upper, U'U = V) of a symmetric positive definite matrix on the device; only the upper triangle of V is read.
+    :class:`NumericError` (PosDefException) when a pivot is not positive."""
+    kv, pv, cnt = as_f64(V)
+    n2 = int(round(np.sqrt(cnt)))
+    if n2 * n2 != cnt or n2 < 1:
+        raise ValueError("V must be a square matrix")
+    U = np.zeros((n2, n2), order="F")
+    check(lib().lpvs_cholesky_upper_f64(pv, n2, int(device), out_ptr(U)))
+    return U
+
+
+def cn_last_timing():
+    """HIP-event times (ms) of this thread's last ComplexNormal device calls."""
+    o = np.zeros(8)
+    check(lib().lpvs_cn_last_timing(out_ptr(o), 8))
+    return dict(factor_ms=o[0], sample_ms=o[1], bands_ms=o[2], total_ms=o[3], n2=int(o[4]), draws=int(o[5]), cells=int(o[6]))
+
+
+@dataclass
+class SchedFunc:
+    """What the ``SpectralExt`` plot recipe computes (src/plotting.jl:54-106): ``F``/``P`` the amplitude and phase of the estimated
+    dependence on the grid ``v`` (Nf × G), ``FBl``/``FBu``/``FBm`` the 10 % / 90 % Monte-Carlo bands and the mean of the draws,
+    ``PB*`` the same of the phase.  ``line`` is what the recipe plots (``FBm`` when ``mcmean`` and bands exist, else ``F``)."""
+    w: Any
+    v: Any
+    F: Any
+    P: Any
+    FBl: Any
+    FBu: Any
+    FBm: Any
+    PBl: Any
+    PBu: Any
+    PBm: Any
+    mcmean: bool = False
+
+    @property
+    def line(self):
+        return self.FBm if (self.mcmean and self.FBm is not None) else self.F   # src/plotting.jl:129
+
+
+def _linrange(a, b, n):
+    """``LinRange(a, b, n)``: element i is ``(1 - t) a + t b`` with ``t = i / (n - 1)`` (Julia's lerpi)."""
+    t = np.arange(n) / (n - 1)
+    return (1 - t) * a + t * b
+
+
+def schedfunc(se, normalization="none", normdim="freq", bounds=True, nMC=5000, phase=False, mcmean=False, seed=0, normals=None, device=0):
+    """The numbers of ``plot(se::SpectralExt; normalization, normdim, bounds, nMC, phase, mcmean)`` (src/plotting.jl:54-106) ->
+    :class:`SchedFunc`.  The grid is ``LinRange(min V, max V, 101 if Nf == 100 else 100)``; ``F[j,i] = |dot(x[j,:], ϕ(v_i))|`` and
+    ``P = angle(...)`` (Julia's ``dot`` conjugates its first argument).  With ``bounds`` and ``se.Σ``: nMC draws of
+    ``ComplexNormal(se.x, se.Σ)`` on the device, the 0-based order statistics ``nMC//10 − 1`` and ``nMC − nMC//10 − 1`` and the mean
+    per (frequency, grid point), selected in LDS -- the ``FB[Nf, G, nMC]`` array of the reference never exists.  Bands are ``None``
+    without ``bounds`` or without Σ; ``PB*`` stay zero unless ``phase`` (as the reference leaves them).
+
+    As in the reference (:99-106), ``normalization`` (``"sum"`` / ``"max"`` along ``normdim`` ``"freq"`` / ``"v"``) divides ``F`` only:
+    the bands are NOT normalised there, and are not here.
+
+    ``normals`` (nMC × 2n) replaces the library's own stream of ``seed``."""
+    w = _host_vec(se.w)
+    Nf, Nv = len(w), int(se.Nv)
+    x = reshape_params(np.asarray(se.x, dtype=np.complex128), Nf)
+    nb = x.shape[1]
+    Vh = _host(se.V)
+    G = 101 if Nf == 100 else 100
+    vg = _linrange(float(Vh.min()), float(Vh.max()), G)
+    # the grid has the minimum, maximum and largest magnitude of V, so the activation kernel places the centres of K = basis_activation_func(V, ...)
+    Φg = basis_activation_func(vg, Nv, se.normalize, se.coulomb)
+    if Φg.shape[1] != nb:
+        raise ValueError(f"se.x has {nb} coefficients per frequency, the basis has {Φg.shape[1]} functions")
+    d = np.conj(x) @ Φg.T
+    F, P = np.abs(d), np.angle(d)
+    nMC = int(nMC)
+    FBl = FBu = FBm = PBl = PBu = PBm = None
+    if bounds and se.Σ is not None:
+        if nMC < 10:
+            raise ValueError(f"nMC must be at least 10 (the lower band is draw nMC ÷ 10 of the sort), got {nMC}")
+        kr, pr = _normals_arg(normals, nMC, 2 * Nf * nb)
+        out = [np.zeros((Nf, G), order="F") for _ in range(6)]
+        with _CnHandle(np.asarray(se.x, dtype=np.complex128).ravel(), se.Σ, device) as h:
+            ptrs = [out_ptr(o) for o in out[:3]] + [out_ptr(o) if phase else None for o in out[3:]]
+            check(lib().lpvs_cn_bands_f64(h.h, Nf, nb, out_ptr(Φg), G, nMC, int(seed), pr, int(bool(phase)), *ptrs))
+        FBl, FBu, FBm, PBl, PBu, PBm = out
+    if normalization != "none":
+        nd = 0 if normdim == "freq" else 1
+        if normalization == "sum":
+            F = F / (F.sum(axis=nd, keepdims=True) / F.shape[nd])
+        elif normalization == "max":
+            F = F / F.max(axis=nd, keepdims=True)
+        else:
+            raise ValueError(f"normalization must be 'none', 'sum' or 'max', got {normalization!r}")
+    return SchedFunc(w, vg, F, P, FBl, FBu, FBm, PBl, PBu, PBm, bool(mcmean))
+
+
+def detrend_(x, order=0, t=None):
+    """``detrend!(x, order=0, t=1:length(x))`` (src/utilities.jl:1-8), in place on a numpy array or a torch tensor (on its own
+    device).  Order 1 is the reference AS WRITTEN (:4-5): ``k = x \\ t`` is the scalar ``(x·t)/(x·x)`` of the centred x and
+    ``x -= k·t`` -- this is not the least-squares slope of x over t."""
+    if hasattr(x, "detach") and hasattr(x, "dtype") and not isinstance(x, np.ndarray):
+        import torch
+        x -= x.mean()
+        if order == 1:
+            tt = torch.arange(1, x.numel() + 1, dtype=x.dtype, device=x.device) if t is None else torch.as_tensor(t, dtype=x.dtype, device=x.device)
+            x -= (torch.dot(x, tt) / torch.dot(x, x)) * tt
+        return x
+    if not isinstance(x, np.ndarray) or x.ndim != 1:
+        raise TypeError("detrend_ works in place on a 1-D numpy array or torch tensor")
+    xf = x.astype(np.float64) - np.mean(x)
+    if order == 1:
+        tt = np.arange(1, len(x) + 1, dtype=np.float64) if t is None else np.asarray(t, dtype=np.float64)
+        xf = xf - (np.dot(xf, tt) / np.dot(xf, xf)) * tt
+    if x.dtype.kind in "iu":
+        if not np.array_equal(np.rint(xf), xf):
+            raise ValueError("InexactError: the detrended values are not integers (detrend! on an integer vector)")
+    x[:] = xf
+    return x
+
+
+def detrend(x, order=0, t=None):
+    """``detrend(x, order=0, t=1:length(x))`` (src/utilities.jl:14-17): a detrended copy; see :func:`detrend_` for order 1."""
+    if hasattr(x, "clone"):
+        return detrend_(x.clone(), order, t)
+    y = np.array(x, copy=True)
+    if y.dtype.kind not in "iuf":
+        y = y.astype(np.float64)
+    return detrend_(y, order, t)
