@@ -558,6 +558,37 @@ int32_t lpvs_mel_project_f32(const float *power, int64_t nbins, int64_t frames, 
  * epilogue's LDS regions do not fit next to one frame pair), output rows, setup (host tables, band ranges, uploads) */
 int32_t lpvs_stft_last_timing(double *out, int32_t n);
 
+/* ---- g2b  welch_pgram / periodogram and the heat-map quantile clamp          DSP.welch_pgram, DSP.periodogram, src/plotting.jl:38-47
+ * lpvs_welch: the mean over the k frames of the one-sided power of lpvs_stft(LPVS_STFT_POWER, ...), S = (1/k) sum_f P_f: the same frames,
+ * window, zero-padding, scale and doubling of the interior bins.  out: nfft/2+1 values, or nfft values when onesided == 0 (bins j and
+ * nfft-j both hold the undoubled value; real input only).  L < n (no frame) -> LPVS_EDOMAIN; noverlap and nfft as lpvs_stft; *nframes
+ * (HOST) is set to k.  No power matrix is written on the LDS paths: every workgroup adds the power columns of its frames in ascending
+ * order into per-bin sums it keeps on the chip and writes one slab of partial sums; the slabs are added in a fixed pairwise tree (no
+ * floating-point atomics: bitwise reproducible).  The longest chain of dependent additions behind one bin is out[9] of
+ * lpvs_stft_last_timing (at most 1023 + ceil(log2 slabs)), the slabs out[10]; out[0..8] are set as by lpvs_stft.  s, window, out: host
+ * or device memory.  A frame with a non-finite windowed sample makes every bin NaN; an all-zero frame adds exact zeros.
+ * LPVS_STFT_WELCH names this epilogue inside the engine; lpvs_stft rejects it.
+ * lpvs_compress: compress(x, q) of src/plotting.jl for the column-major sub-matrix x (rows x cols, leading dimension ld >= rows):
+ * out = clamp(v, t0, t1) element by element with v = x (take_log == 0) or log(x) (logf for the _f32 twin), t0 / t1 the quantiles qlo /
+ * qhi (swapped when qlo > qhi; outside [0, 1] -> LPVS_EARGUMENT) of all m = rows cols values v by Julia's default definition (type 7):
+ * aleph = m p + (1 - p), j = clamp(trunc(aleph), 1, m-1), g = clamp(aleph - j, 0, 1), a = v_(j), b = v_(j+1) of the sorted values
+ * (isless order: -0.0 < +0.0), a + g (b - a) if both are finite, else (1 - g) a + g b; m == 1 gives the element.  m == 0 or a NaN among
+ * the values v (take_log: a NaN or a negative x) -> LPVS_EDOMAIN (Julia's quantile throws).  The order statistics come from an exact radix select on order-preserving
+ * 64-bit keys (8-bit digits from the top, integer histograms), not from a sort.  _f32: the order statistics are the float values, the
+ * interpolation runs in double, the output is float (a clamped element is the threshold rounded to float).  x and out (leading
+ * dimension out_ld >= rows) may be host or device memory; thresholds (HOST, 2 doubles, may be NULL) receives t0, t1.
+ * lpvs_compress_last_timing, out[0..4]: histogram passes, select ms, clamp ms, total ms, digits skipped (all surviving keys agreed). */
+#define LPVS_STFT_WELCH 4
+int32_t lpvs_welch_f64(const double *s, int64_t L, int64_t n, int64_t noverlap, int64_t nfft, double fs, const double *window, int32_t onesided,
+                       int32_t device, double *out, int64_t *nframes);
+int32_t lpvs_welch_f32(const float *s, int64_t L, int64_t n, int64_t noverlap, int64_t nfft, double fs, const float *window, int32_t onesided,
+                       int32_t device, float *out, int64_t *nframes);
+int32_t lpvs_compress_f64(const double *x, int64_t rows, int64_t cols, int64_t ld, int32_t take_log, double qlo, double qhi, int32_t device,
+                          double *out, int64_t out_ld, double *thresholds);
+int32_t lpvs_compress_f32(const float *x, int64_t rows, int64_t cols, int64_t ld, int32_t take_log, double qlo, double qhi, int32_t device,
+                          float *out, int64_t out_ld, double *thresholds);
+int32_t lpvs_compress_last_timing(double *out, int32_t n);
+
 /* ---- g3  ComplexNormal sampling and the Monte-Carlo bands of the SpectralExt recipe   src/utilities.jl:80-174, src/plotting.jl:54-97
  * Double precision only: the covariance of ls_spectral_lpv is always Float64, so these entry points have no _f32 twins.
  * All matrices column-major; V, R, Phi_g and the outputs may be host or device memory unless stated otherwise.

@@ -19,7 +19,8 @@ const PO = ProximalOperators
 export ls_spectral, tls_spectral, ls_sparse_spectral, ls_sparse_spectral_lpv, ls_spectral_lpv, ls_windowpsd, ls_windowcsd,
        ls_cohere, ls_windowpsd_lpv, get_fourier_regressor, check_freq, default_freqs, Windows2, Windows3, mapwindows,
        SpectralExt, psd, reshape_params, ADMM, rect, hanning, autocov, autocor, isequidistant,
-       melspectrogram, mfcc, mel, spectrogram, Spectrogram, MelSpectrogram, MFCC, freq, rand_cn, schedfunc
+       melspectrogram, mfcc, mel, spectrogram, Spectrogram, MelSpectrogram, MFCC, freq, rand_cn, schedfunc,
+       Periodogram, welch_pgram, periodogram, compress, heatmap
 
 const LIB = get(ENV, "LPVSPECTRAL_LIB", joinpath(@__DIR__, "..", "lpvspectral.jl_amd", "liblpvspectral.so"))
 
@@ -950,5 +951,76 @@ function mfcc(s, args...; nmfcc::Int = 20, nmels::Int = 128, window=hanning, kwa
     C, t = _stft(Int32(3), s, n, noverlap, nfft, fs, window, W, dct_matrix(nmfcc, nmels); device=device)
     MFCC(C, 1:nmfcc, t)
 end
+
+# ---- welch_pgram / periodogram (DSP.jl) and the numbers of the heat-map recipes (src/plotting.jl:15-47) -------------------------------
+# The frame average is summed on the device without the power matrix; compress selects its order statistics by an exact radix select.
+struct Periodogram{T,F}
+    power::Vector{T}
+    freq::F
+end
+freq(P::Periodogram) = P.freq
+
+function _welch(s::AbstractVector{<:Real}, n::Integer, noverlap::Integer, nfft::Integer, fs::Real, window, onesided::Bool; device::Integer=0)
+    rows = onesided ? nfft ÷ 2 + 1 : nfft
+    k = Ref{Int64}(0)
+    if eltype(s) == Float32
+        sv = Vector{Float32}(s)
+        wv = window === nothing ? Float32[] : Vector{Float32}(window isa Function ? window(n) : window)
+        wp = window === nothing ? Ptr{Float32}(C_NULL) : pointer(wv)
+        out = Vector{Float32}(undef, rows)
+        GC.@preserve sv wv out check(@ccall LIB.lpvs_welch_f32(sv::Ptr{Float32}, Int64(length(sv))::Int64, Int64(n)::Int64, Int64(noverlap)::Int64,
+            Int64(nfft)::Int64, Float64(fs)::Float64, wp::Ptr{Float32}, Int32(onesided)::Int32, Int32(device)::Int32, out::Ptr{Float32},
+            k::Ref{Int64})::Int32)
+    else
+        sv = Vector{Float64}(s)
+        wv = window === nothing ? Float64[] : Vector{Float64}(window isa Function ? window(n) : window)
+        wp = window === nothing ? Ptr{Float64}(C_NULL) : pointer(wv)
+        out = Vector{Float64}(undef, rows)
+        GC.@preserve sv wv out check(@ccall LIB.lpvs_welch_f64(sv::Ptr{Float64}, Int64(length(sv))::Int64, Int64(n)::Int64, Int64(noverlap)::Int64,
+            Int64(nfft)::Int64, Float64(fs)::Float64, wp::Ptr{Float64}, Int32(onesided)::Int32, Int32(device)::Int32, out::Ptr{Float64},
+            k::Ref{Int64})::Int32)
+    end
+    f = onesided ? (0:nfft÷2) .* (fs / nfft) : [(j <= (nfft - 1) ÷ 2 ? j : j - nfft) * (fs / nfft) for j in 0:nfft-1]
+    Periodogram(out, f)
+end
+
+function welch_pgram(s::AbstractVector{<:Real}, n::Int = length(s) >> 3, noverlap::Int = n >> 1; onesided::Bool = true, nfft::Int = _nextfastfft(n),
+                     fs::Real = 1, window = nothing, device::Integer = 0)                                 # DSP.welch_pgram (real s)
+    _welch(s, n, noverlap, nfft, fs, window, onesided; device=device)
+end
+
+function periodogram(s::AbstractVector{<:Real}; onesided::Bool = true, nfft::Int = _nextfastfft(length(s)), fs::Real = 1, window = nothing,
+                     device::Integer = 0)                                                                 # DSP.periodogram (real s)
+    _welch(s, length(s), 0, nfft, fs, window, onesided; device=device)
+end
+
+_quantile_pair(q::Number) = (q = q < 0.5 ? q : 1 - q; (Float64(q), Float64(1 - q)))                      # src/plotting.jl:39-44
+_quantile_pair(q) = (Float64(min(q...)), Float64(max(q...)))
+
+# clamp of x (take_log: of log.(x)) to its own quantiles; x is a column-major matrix or a view of one with unit row stride
+function _compress(x::AbstractVecOrMat{<:Real}, q, take_log::Bool; device::Integer = 0)
+    qlo, qhi = _quantile_pair(q)
+    rows, cols = size(x, 1), size(x, 2)
+    th = zeros(Float64, 2)
+    if eltype(x) == Float32
+        xv = Matrix{Float32}(reshape(x, rows, cols)); out32 = Matrix{Float32}(undef, rows, cols)
+        GC.@preserve xv out32 th check(@ccall LIB.lpvs_compress_f32(xv::Ptr{Float32}, Int64(rows)::Int64, Int64(cols)::Int64, Int64(rows)::Int64,
+            Int32(take_log)::Int32, qlo::Float64, qhi::Float64, Int32(device)::Int32, out32::Ptr{Float32}, Int64(rows)::Int64, th::Ptr{Float64})::Int32)
+        return (x isa AbstractVector ? vec(out32) : out32), (th[1], th[2])
+    end
+    xw = Matrix{Float64}(reshape(x, rows, cols)); out64 = Matrix{Float64}(undef, rows, cols)
+    GC.@preserve xw out64 th check(@ccall LIB.lpvs_compress_f64(xw::Ptr{Float64}, Int64(rows)::Int64, Int64(cols)::Int64, Int64(rows)::Int64,
+        Int32(take_log)::Int32, qlo::Float64, qhi::Float64, Int32(device)::Int32, out64::Ptr{Float64}, Int64(rows)::Int64, th::Ptr{Float64})::Int32)
+    (x isa AbstractVector ? vec(out64) : out64), (th[1], th[2])
+end
+
+compress(x, q; device::Integer = 0) = _compress(x, q, false; device=device)[1]                            # src/plotting.jl:38-47
+
+# the numbers of plot_spectrogram and of the MelSpectrogram recipe: (time, frequencies[2:end], compress(log.(power)[2:end, :], compression))
+heatmap(S::Spectrogram; compression = (0.005, 1), device::Integer = 0) =
+    (S.time, S.freq[2:end], _compress(S.power[2:end, :], compression, true; device=device)[1])
+_mel_to_hz(m) = m >= 1000f0 / (200f0 / 3) ? 1000f0 * exp((log(6.4f0) / 27f0) * (m - 1000f0 / (200f0 / 3))) : (200f0 / 3) * m   # src/mel.jl:56-71
+heatmap(M::MelSpectrogram; compression = (0.005, 1), device::Integer = 0) =
+    (M.time, _mel_to_hz.(M.mels)[2:end], _compress(M.power[2:end, :], compression, true; device=device)[1])
 
 end # module

@@ -23,7 +23,7 @@ PROX_L1, PROX_L0, PROX_BALL_L0, PROX_GROUP_L2 = 1, 2, 3, 4
 LINEAR_LEAST_SQUARES, LINEAR_QUADRATIC_AS_WRITTEN = 1, -1
 EST_SPARSE, EST_DENSE, EST_SPARSE_INIT = 1, 2, 3
 ACF_COV, ACF_COR = 1, 2
-STFT_POWER, STFT_MEL, STFT_MFCC = 1, 2, 3
+STFT_POWER, STFT_MEL, STFT_MFCC, STFT_WELCH = 1, 2, 3, 4
 # options (include/lpvspectral.h LPVS_OPT_*): name -> (option id, {value name -> value}); None / "default" = 0
 OPTIONS = {
     "storage": (1, {"mixed": 1, "split": 2, "f64": 3, "mixed32": 4}),
@@ -167,6 +167,11 @@ SIGNATURES = {
     "lpvs_mel_project_f64": (_I32, [_P, _I64, _I64, _P, _I64, _I32, _P]),
     "lpvs_mel_project_f32": (_I32, [_P, _I64, _I64, _P, _I64, _I32, _P]),
     "lpvs_stft_last_timing": (_I32, [_P, _I32]),
+    "lpvs_welch_f64": (_I32, [_P, _I64, _I64, _I64, _I64, _F64, _P, _I32, _I32, _P, _PI64]),
+    "lpvs_welch_f32": (_I32, [_P, _I64, _I64, _I64, _I64, _F64, _P, _I32, _I32, _P, _PI64]),
+    "lpvs_compress_f64": (_I32, [_P, _I64, _I64, _I64, _I32, _F64, _F64, _I32, _P, _I64, _P]),
+    "lpvs_compress_f32": (_I32, [_P, _I64, _I64, _I64, _I32, _F64, _F64, _I32, _P, _I64, _P]),
+    "lpvs_compress_last_timing": (_I32, [_P, _I32]),
     "lpvs_cholesky_upper_f64": (_I32, [_P, _I64, _I32, _P]),
     "lpvs_randn_f64": (_I32, [_I64, _I64, _I64, _I64, _I32, _P]),
     "lpvs_cov_f64": (_I32, [_P, _I64, _I64, _I32, _P, _P]),

@@ -1434,9 +1434,16 @@ class MFCC:
         self.mfcc, self.number, self.time = mfcc, number, time
 
 
+class Periodogram:
+    """DSP.Periodograms.Periodogram: ``power`` (nfft÷2+1 values one-sided, nfft two-sided) and ``freq``."""
+
+    def __init__(self, power, freq):
+        self.power, self.freq = power, freq
+
+
 def freq(M):
-    """DSP.freq: the frequencies of a Spectrogram, the mels of a MelSpectrogram, the coefficient numbers of an MFCC."""
-    return M.freq if isinstance(M, Spectrogram) else (M.mels if isinstance(M, MelSpectrogram) else M.number)
+    """DSP.freq: the frequencies of a Spectrogram or Periodogram, the mels of a MelSpectrogram, the coefficient numbers of an MFCC."""
+    return M.freq if isinstance(M, (Spectrogram, Periodogram)) else (M.mels if isinstance(M, MelSpectrogram) else M.number)
 
 
 def time(M):
@@ -1658,11 +1665,161 @@ def mfcc(s, *args, nmfcc=20, nmels=128, window=hanning, fs=1, fmin=np.float32(0)
 
 
 def stft_last_timing():
-    """HIP-event times (ms) and plan of this thread's last spectrogram / melspectrogram / mfcc call."""
-    o = np.zeros(9)
-    check(lib().lpvs_stft_last_timing(out_ptr(o), 9))
+    """HIP-event times (ms) and plan of this thread's last spectrogram / melspectrogram / mfcc / welch_pgram / periodogram call.
+    ``sum_chain`` is the longest chain of dependent additions behind one bin of a frame average (D of DESIGN.md §4.10) and ``slabs``
+    the partial-sum slabs it was built from; both are 0 after the other calls."""
+    o = np.zeros(11)
+    check(lib().lpvs_stft_last_timing(out_ptr(o), 11))
     return dict(fft_ms=o[0], copy_out_ms=o[1], total_ms=o[2], frames=int(o[3]), path=int(o[4]), fft_length=int(o[5]),
-                pairs_per_workgroup=int(o[6]), rows=int(o[7]), setup_ms=o[8])
+                pairs_per_workgroup=int(o[6]), rows=int(o[7]), setup_ms=o[8], sum_chain=int(o[9]), slabs=int(o[10]))
+
+
+# --------------------------------------------------------------------------- welch_pgram / periodogram (DSP.jl), compress / heatmap
+# (src/plotting.jl:8-47: the numbers of plot_periodogram, plot_spectrogram and the MelSpectrogram recipe; csrc/melspec.hip, csrc/compress.hip)
+def _welch(s, n, noverlap, nfft, fs, window, onesided, device):
+    keep, ptr, L, f32, dev = _stft_input(s)
+    n = L >> 3 if n is None else int(n)
+    noverlap = n >> 1 if noverlap is None else int(noverlap)
+    nfft = nextfastfft(n) if nfft is None else int(nfft)
+    if n < 1 or L < n:
+        raise _lib.DomainError(f"the signal ({L} samples) holds no frame of n = {n} samples: the mean over no frame is undefined")
+    if noverlap < 0 or noverlap >= n:
+        raise _lib.DomainError(f"noverlap must satisfy 0 <= noverlap < n (noverlap = {noverlap}, n = {n})")   # DSP.arraysplit
+    if nfft < n:
+        raise ValueError(f"nfft must be >= n (nfft = {nfft}, n = {n})")
+    dt = np.float32 if f32 else np.float64
+    win = None
+    if window is not None:
+        win = np.ascontiguousarray(np.asarray(window(n) if callable(window) else window, dtype=np.float64).ravel())
+        if len(win) != n:
+            raise ValueError(f"window has {len(win)} values, the frames {n}")
+        win = win.astype(dt)
+    rows = nfft // 2 + 1 if onesided else nfft
+    fn = lib().lpvs_welch_f32 if f32 else lib().lpvs_welch_f64
+    device = dev if dev is not None else device
+    wp = out_ptr(win) if win is not None else None
+    k = C.c_int64(0)
+    args = (ptr, L, n, noverlap, nfft, float(fs), wp, 1 if onesided else 0, int(device))
+    if dev is not None:
+        import torch
+        out = torch.empty(rows, dtype=torch.float32 if f32 else torch.float64, device=s.device)
+        check(fn(*args, C.c_void_p(out.data_ptr()), C.byref(k)))
+    else:
+        out = np.empty(rows, dtype=dt)
+        check(fn(*args, out_ptr(out), C.byref(k)))
+    del keep
+    f = np.arange(nfft // 2 + 1) * fs / nfft if onesided else np.fft.fftfreq(nfft, 1.0 / fs)
+    return Periodogram(out, f)
+
+
+def welch_pgram(s, n=None, noverlap=None, onesided=True, nfft=None, fs=1, window=None, device=0):
+    """DSP.welch_pgram of a real signal: the mean over the frames of DSP.arraysplit(s, n, noverlap) of their power (the columns of
+    :func:`spectrogram`), summed on the device without the power matrix.  n defaults to len(s)>>3, noverlap to n>>1, nfft to
+    nextfastfft(n).  ``onesided=False`` gives all nfft bins (bins k and nfft-k hold the same, undoubled value).  A signal shorter than
+    one frame raises DomainError.  Torch device tensors give device tensors, host arrays numpy arrays (f32 in, f32 out)."""
+    return _welch(s, n, noverlap, nfft, fs, window, onesided, device)
+
+
+def periodogram(s, onesided=True, nfft=None, fs=1, window=None, device=0):
+    """DSP.periodogram of a real signal: the one-frame case of :func:`welch_pgram` (n = len(s), nfft = nextfastfft(len(s)))."""
+    L = s.numel() if _is_torch(s) else np.asarray(s).size
+    return _welch(s, L, 0, nfft, fs, window, onesided, device)
+
+
+def _quantile_pair(q):
+    """compress's q (src/plotting.jl:39-44): a number q -> (q', 1-q') with q' = q < 0.5 ? q : 1-q; a pair -> (min, max)."""
+    if isinstance(q, (int, float, np.integer, np.floating)):
+        q = float(q)
+        q = q if q < 0.5 else 1 - q
+        q = (q, 1 - q)
+    else:
+        q = tuple(float(v) for v in q)
+        if len(q) < 1:
+            raise ValueError("compress: q must be a number or a non-empty collection of numbers")
+        q = (min(q), max(q))
+    if not (0 <= q[0] <= 1 and 0 <= q[1] <= 1):
+        raise ValueError(f"compress: quantile levels must lie in [0, 1], got {q}")       # Julia's quantile: ArgumentError
+    return q
+
+
+def _compress(x, q, take_log, device=0):
+    qlo, qhi = _quantile_pair(q)
+    th = np.zeros(2)
+    if _is_torch(x) and x.is_cuda:
+        import torch
+        if x.is_complex() or x.dim() not in (1, 2):
+            raise ValueError("compress: x must be a real vector or matrix")
+        v = x if x.dim() == 2 else x.reshape(-1, 1)
+        if v.dtype not in (torch.float32, torch.float64):
+            v = v.to(torch.float64)
+        rows, cols = int(v.shape[0]), int(v.shape[1])
+        if rows * cols == 0:
+            raise _lib.DomainError("compress: the quantiles of an empty collection are undefined")
+        if not ((rows == 1 or v.stride(0) == 1) and (cols == 1 or v.stride(1) >= rows)):
+            v = v.T.contiguous().T                                             # column-major copy
+        ld = rows if cols == 1 else int(v.stride(1))
+        f32 = v.dtype == torch.float32
+        torch.cuda.current_stream(v.device).synchronize()
+        o = torch.empty((cols, rows), dtype=v.dtype, device=v.device)
+        fn = lib().lpvs_compress_f32 if f32 else lib().lpvs_compress_f64
+        check(fn(C.c_void_p(v.data_ptr()), rows, cols, ld, int(take_log), qlo, qhi, v.device.index, C.c_void_p(o.data_ptr()), rows, out_ptr(th)))
+        out = o.T if x.dim() == 2 else o.reshape(-1)
+        return out, (float(th[0]), float(th[1]))
+    if hasattr(x, "detach") and hasattr(x, "numpy"):
+        x = x.detach().numpy()
+    a = np.asarray(x)
+    if np.iscomplexobj(a) or a.ndim not in (1, 2):
+        raise ValueError("compress: x must be a real vector or matrix")
+    dt = np.float32 if a.dtype == np.float32 else np.float64
+    v = a.astype(dt, copy=False)
+    v = v if v.ndim == 2 else v.reshape(-1, 1)
+    rows, cols = v.shape
+    if rows * cols == 0:
+        raise _lib.DomainError("compress: the quantiles of an empty collection are undefined")
+    isz = v.itemsize
+    if not ((rows == 1 or v.strides[0] == isz) and (cols == 1 or (v.strides[1] % isz == 0 and v.strides[1] // isz >= rows))):
+        v = np.asfortranarray(v)
+    ld = rows if cols == 1 else v.strides[1] // isz
+    out = np.empty((rows, cols), dtype=dt, order="F")
+    fn = lib().lpvs_compress_f32 if dt is np.float32 else lib().lpvs_compress_f64
+    check(fn(C.c_void_p(v.ctypes.data), rows, cols, ld, int(take_log), qlo, qhi, int(device), out_ptr(out), rows, out_ptr(th)))
+    return (out if a.ndim == 2 else out.reshape(-1)), (float(th[0]), float(th[1]))
+
+
+def compress(x, q, device=0):
+    """src/plotting.jl:38-47: ``clamp.(x, quantile(vec(x), q)...)`` with q a number (-> (q', 1-q'), q' = q < 0.5 ? q : 1-q) or a pair
+    (-> (min, max)); Julia's default quantile definition.  The order statistics come from an exact radix select on the device, so the
+    thresholds equal those of a sort.  x: a real vector or matrix, host array or torch device tensor (a column-major view such as
+    ``power[1:, :]`` is read in place).  float32 in gives float32 out: the order statistics are the float values, the interpolation runs
+    in double and a clamped element is the threshold rounded to float (the reference would widen the whole matrix to Float64).  An
+    empty x or a NaN in it raises DomainError, as Julia's quantile throws."""
+    return _compress(x, q, 0, device)[0]
+
+
+def compress_thresholds(x, q, take_log=False, device=0):
+    """(clamped matrix, (lower, upper) thresholds) of :func:`compress`, of ``log(x)`` when take_log (the log is fused on the device)."""
+    return _compress(x, q, 1 if take_log else 0, device)
+
+
+def heatmap(S, compression=(0.005, 1), device=0):
+    """The numbers of the reference's heat-map recipes (src/plotting.jl:15-36): for a Spectrogram ``(time, freq[1:], z)``, for a
+    MelSpectrogram ``(time, mel_to_hz(mels)[1:], z)``, z = compress(log(power)[1:, :], compression) -- log, selection and clamp on the
+    device, row 0 skipped in place.  A zero power gives -Inf and is legal; a NaN (or negative) power raises DomainError."""
+    if isinstance(S, Spectrogram):
+        axis = S.freq[1:]
+    elif isinstance(S, MelSpectrogram):
+        axis = mel_to_hz(S.mels)[1:]
+    else:
+        raise TypeError("heatmap: a Spectrogram or a MelSpectrogram is needed")
+    z, _ = _compress(S.power[1:, :], compression, 1, device)
+    return S.time, axis, z
+
+
+def compress_last_timing():
+    """Plan and HIP-event times (ms) of this thread's last compress / heatmap call."""
+    o = np.zeros(5)
+    check(lib().lpvs_compress_last_timing(out_ptr(o), 5))
+    return dict(passes=int(o[0]), select_ms=o[1], clamp_ms=o[2], total_ms=o[3], digits_skipped=int(o[4]))
 
 
 # --------------------------------------------------------------------------- ComplexNormal, the SpectralExt recipe's numbers, detrend

@@ -1,4 +1,5 @@
-// melspec.hip -- spectrogram / melspectrogram / mfcc (DSP.spectrogram + src/mel.jl) on gfx950: one STFT engine, three epilogues.
+// melspec.hip -- spectrogram / melspectrogram / mfcc / welch_pgram (DSP.spectrogram, DSP.welch_pgram + src/mel.jl) on gfx950: one STFT
+// engine, four epilogues.
 //
 // Frames are DSP.arraysplit's (k = (L-n) / (n-noverlap) + 1), windowed and zero-padded to nfft.  Two real frames travel as one complex
 // sequence z = a + i b (frame 2p real, frame 2p+1 imaginary); after the FFT X_a[k] = (Z_k + conj Z_{N-k}) / 2 and
@@ -12,6 +13,14 @@
 //     exp(-i pi k^2 / nfft) is reduced as k^2 mod 2 nfft in 64-bit integers before the table lookup.
 // Twiddles come from host tables with exact argument reduction (octant, long double).  All device arithmetic is double, products are
 // rounded (-ffp-contract=off), and nothing is accumulated by atomics: the outputs are bitwise reproducible.
+// The fourth epilogue (LPVS_STFT_WELCH) is the mean of the power over the frames.  On the LDS paths workgroup g of S adds the power
+// columns of its batch (in LDS, never a power matrix in HBM) in ascending frame order to slab g of nbins partial sums; batch g + S, g + 2 S, ...
+// follow in further launches of the same S workgroups, so a slab is only ever touched by one workgroup at a time, in frame order.  (One
+// launch whose workgroups loop over their batches with the sums in LDS was measured at 3x the time: the FFT already fills the register
+// file, and the loop's live state spills.)  On the four-step paths a chunk's spectra already sit in global scratch: the split, the power
+// and the sum over slabs of kWelchChunkFrames frames are one kernel, a thread per bin.
+// A second kernel adds the slabs in a fixed pairwise tree and a third divides by the frame count.  The longest chain of dependent
+// additions behind one bin is D = F - 1 + ceil(log2 S), F the most frames behind one slab (<= kWelchChain), S the slabs.
 #include "lpvs_internal.h"
 
 #include <algorithm>
@@ -31,6 +40,9 @@ constexpr int64_t kMaxLen = 1ll << 26;
 constexpr int64_t kRootB = 8192;     // two-table roots: r = hi * kRootB + lo
 constexpr int kEpiThreads = 256;
 constexpr size_t kScratchBudget = (size_t)1 << 30;   // bytes of four-step scratch per chunk of frame pairs
+constexpr int64_t kWelchChain = 1024;        // most frames one workgroup adds sequentially into its slab (LDS paths)
+constexpr int64_t kWelchSlabs = 1024;        // slabs launched when the frames allow it (more when kWelchChain asks for it)
+constexpr int64_t kWelchChunkFrames = 256;   // frames per slab on the four-step paths
 
 enum : int { IN_SIGNAL = 0, IN_GLOBAL = 1 };
 enum : int { POST_NONE = 0, POST_TWIDDLE = 1, POST_BLUE_MUL = 2, POST_BLUESTEIN_LDS = 3 };
@@ -129,6 +141,7 @@ template <class T> struct Epi {
     int nmfcc = 0;
     T *out = nullptr;                 // rows x frames, column-major
     int64_t nframes = 0;              // frames of the whole call (global frame indices)
+    double *wslab = nullptr;          // LPVS_STFT_WELCH: gridDim.x slabs of nbins partial sums
 };
 
 __device__ inline double row_scale(int64_t k, int64_t nbins, int64_t nfft, double m1, double m2) {
@@ -287,14 +300,12 @@ template <class T> __device__ inline double2 signal_value(const FftJob<T> &J, in
     return make_double2(a, b);
 }
 
-template <class T>
-__global__ void __launch_bounds__(kThreads) stft_fft_kernel(FftJob<T> J) {
-    __shared__ double2 buf[kFftMax];
-    __shared__ int bad[2 * kMaxPairs];   // frame flags (FRAME_*; a non-finite power value counts as FRAME_NONFINITE)
-    __shared__ int shift[2 * kMaxPairs];  // pair_shift of each frame
-    __shared__ double red[2 * (kThreads / 64)];
+// one workgroup's batch `blk` of J.B sequences: load, FFT, what follows it, output or epilogue.  WELCH: the power columns of the batch
+// are added, in ascending frame order, to the per-bin sums wacc (taken as zero when `first`)
+template <class T, bool WELCH>
+__device__ __forceinline__ void stft_batch(const FftJob<T> &J, int64_t blk, double2 *buf, int *bad, int *shift, double *red, double *wacc, bool first) {
     const int N = J.N, tid = (int)threadIdx.x;
-    const int64_t q0 = (J.blk0 + (int64_t)blockIdx.x) * J.B;
+    const int64_t q0 = blk * J.B;
     const int nb = (int)min<int64_t>(J.B, J.nseq - q0);
     // each sequence is one whole frame pair and no frame_bad_kernel pass ran: flag and equalise its frames here
     const bool local = J.in_mode == IN_SIGNAL && J.nsub == 1 && !J.fbad;
@@ -428,6 +439,16 @@ __global__ void __launch_bounds__(kThreads) stft_fft_kernel(FftJob<T> J) {
     if (E.kind == LPVS_STFT_POWER) return;
     __syncthreads();
     const int nfr = 2 * nb;
+    if constexpr (WELCH) {
+        // frames beyond the call's last one (the partner of an odd count's last frame) are skipped; an all-zero frame adds exact zeros
+        const int nadd = (int)min<int64_t>((int64_t)nfr, E.nframes - (J.frame0 + 2 * q0));
+        for (int k = tid; k < (int)nbins; k += kThreads) {
+            double a = first ? 0.0 : wacc[k];
+            for (int f = 0; f < nadd; ++f) a = a + pw[(int64_t)f * nbins + k];
+            wacc[k] = a;
+        }
+        return;
+    }
     double *mel = pw + (int64_t)nfr * nbins;
     for (int it = tid; it < nfr * E.nmels; it += kThreads) {
         const int f = it / E.nmels, i = it - f * E.nmels;
@@ -454,10 +475,72 @@ __global__ void __launch_bounds__(kThreads) stft_fft_kernel(FftJob<T> J) {
     }
 }
 
+template <class T>
+__global__ void __launch_bounds__(kThreads) stft_fft_kernel(FftJob<T> J) {
+    __shared__ double2 buf[kFftMax];
+    __shared__ int bad[2 * kMaxPairs];   // frame flags (FRAME_*; a non-finite power value counts as FRAME_NONFINITE)
+    __shared__ int shift[2 * kMaxPairs];  // pair_shift of each frame
+    __shared__ double red[2 * (kThreads / 64)];
+    stft_batch<T, false>(J, J.blk0 + (int64_t)blockIdx.x, buf, bad, shift, red, nullptr, true);
+}
+
+// LPVS_STFT_WELCH on the LDS paths: launch r gives batch r gridDim.x + g to workgroup g, which adds the batch's power columns to slab g
+// (its own: read and written by this workgroup alone, launch after launch in stream order; the first launch starts from zero)
+template <class T>
+__global__ void __launch_bounds__(kThreads) stft_welch_kernel(FftJob<T> J) {
+    __shared__ double2 buf[kFftMax];
+    __shared__ int bad[2 * kMaxPairs];
+    __shared__ int shift[2 * kMaxPairs];
+    __shared__ double red[2 * (kThreads / 64)];
+    stft_batch<T, true>(J, J.blk0 + (int64_t)blockIdx.x, buf, bad, shift, red, J.epi.wslab + (int64_t)blockIdx.x * J.epi.nbins, J.blk0 == 0);
+}
+
+// two levels of the pairwise tree over S slabs, in place: slab i <- (slab i + slab i+st) + (slab i+2st + slab i+3st), i = 0, 4 st, ...
+__global__ void __launch_bounds__(kEpiThreads) welch_tree_kernel(double *slab, int64_t S, int64_t nbins, int64_t st, int64_t groups) {
+    const int64_t idx = (int64_t)blockIdx.x * kEpiThreads + threadIdx.x;
+    if (idx >= groups * nbins) return;
+    const int64_t g = idx / nbins, k = idx - g * nbins, i = g * 4 * st;
+    double v = slab[i * nbins + k];
+    if (i + st < S) v = v + slab[(i + st) * nbins + k];
+    if (i + 2 * st < S) {
+        double w = slab[(i + 2 * st) * nbins + k];
+        if (i + 3 * st < S) w = w + slab[(i + 3 * st) * nbins + k];
+        v = v + w;
+    }
+    slab[i * nbins + k] = v;
+}
+// the mean; two-sided: bins k and nfft - k both get the undoubled value (half the one-sided one, exact)
+template <class T>
+__global__ void __launch_bounds__(kEpiThreads) welch_finish_kernel(const double *sum, int64_t nbins, int64_t nfft, double frames, int twosided, T *out) {
+    const int64_t k = (int64_t)blockIdx.x * kEpiThreads + threadIdx.x;
+    if (k >= nbins) return;
+    const double v = sum[k] / frames;
+    if (!twosided) { out[k] = (T)v; return; }
+    const bool edge = k == 0 || ((nfft & 1) == 0 && k == nbins - 1);
+    const T h = (T)(edge ? v : 0.5 * v);
+    out[k] = h;
+    if (!edge) out[nfft - k] = h;
+}
+
 constexpr int64_t kMaxFrameBlocks = 65536;   // per-frame kernels stride over the frames beyond this many workgroups
 inline unsigned frame_blocks(int64_t count) { return (unsigned)std::min<int64_t>(std::max<int64_t>(count, 1), kMaxFrameBlocks); }
 
 // ---- four-step / Bluestein tail: split + power of a global Z (a workgroup per frame pair, striding over the pairs) ----------------
+// bin k of the two frames of one pair from its spectrum z (blue: the inverse FFT by conj-FFT-conj is finished here, then the chirp)
+__device__ inline void pair_power(const double2 *z, int64_t k, int64_t nfft, int64_t nbins, double m1, double m2, int blue, const RootTab &chirp,
+                                  int64_t m, int la, int sa, int lb, int sb, double &pa, double &pb) {
+    const int64_t km = k == 0 ? 0 : nfft - k;
+    double2 zk = z[k], zm = z[km];
+    if (blue) {
+        zk = conjd(zk); zk.x = zk.x / (double)m; zk.y = zk.y / (double)m; zk = cmul(zk, chirp_of(chirp, k));
+        zm = conjd(zm); zm.x = zm.x / (double)m; zm.y = zm.y / (double)m; zm = cmul(zm, chirp_of(chirp, km));
+    }
+    const double ar = (zk.x + zm.x) * 0.5, ai = (zk.y - zm.y) * 0.5;
+    const double br = (zk.y + zm.y) * 0.5, bi = (zm.x - zk.x) * 0.5;
+    const double sc = row_scale(k, nbins, nfft, m1, m2);
+    pa = frame_power(la, sa, ar, ai, sc);
+    pb = frame_power(lb, sb, br, bi, sc);
+}
 template <class T>
 __global__ void __launch_bounds__(kEpiThreads) split_power_kernel(const double2 *Z, int64_t zps, int64_t nfft, int64_t nbins, double m1, double m2,
                                                                   int blue, RootTab chirp, int64_t m, int64_t frame0, int64_t nframes,
@@ -469,19 +552,34 @@ __global__ void __launch_bounds__(kEpiThreads) split_power_kernel(const double2 
     const int la = fbad[fa], lb = hb ? fbad[fb] : FRAME_ZERO;
     const int sa = pair_shift(la, fexp[fa], lb, hb ? fexp[fb] : 0), sb = hb ? pair_shift(lb, fexp[fb], la, fexp[fa]) : 0;
     for (int64_t k = threadIdx.x; k < nbins; k += kEpiThreads) {
-        const int64_t km = k == 0 ? 0 : nfft - k;
-        double2 zk = z[k], zm = z[km];
-        if (blue) {   // inverse FFT by conj-FFT-conj, then the chirp
-            zk = conjd(zk); zk.x = zk.x / (double)m; zk.y = zk.y / (double)m; zk = cmul(zk, chirp_of(chirp, k));
-            zm = conjd(zm); zm.x = zm.x / (double)m; zm.y = zm.y / (double)m; zm = cmul(zm, chirp_of(chirp, km));
-        }
-        const double ar = (zk.x + zm.x) * 0.5, ai = (zk.y - zm.y) * 0.5;
-        const double br = (zk.y + zm.y) * 0.5, bi = (zm.x - zk.x) * 0.5;
-        const double sc = row_scale(k, nbins, nfft, m1, m2);
-        pw[(fa - pw_frame0) * nbins + k] = (T)frame_power(la, sa, ar, ai, sc);
-        if (hb) pw[(fb - pw_frame0) * nbins + k] = (T)frame_power(lb, sb, br, bi, sc);
+        double pa, pb;
+        pair_power(z, k, nfft, nbins, m1, m2, blue, chirp, m, la, sa, lb, sb, pa, pb);
+        pw[(fa - pw_frame0) * nbins + k] = (T)pa;
+        if (hb) pw[(fb - pw_frame0) * nbins + k] = (T)pb;
     }
   }
+}
+
+// LPVS_STFT_WELCH on the four-step paths: slab j of a chunk = the power of its frame pairs [j P, (j + 1) P), split from Z and added bin
+// by bin in ascending frame order (a thread per bin; no power columns are written)
+__global__ void __launch_bounds__(kEpiThreads) welch_split_sum_kernel(const double2 *Z, int64_t zps, int64_t nfft, int64_t nbins, double m1, double m2,
+                                                                      int blue, RootTab chirp, int64_t m, int64_t frame0, int64_t nframes,
+                                                                      const int32_t *fbad, const int32_t *fexp, int64_t npairs, int64_t P, double *slab) {
+    const int64_t k = (int64_t)blockIdx.x * kEpiThreads + threadIdx.x, j = blockIdx.y;
+    if (k >= nbins) return;
+    const int64_t p1 = min((j + 1) * P, npairs);
+    double acc = 0.0;
+    for (int64_t p = j * P; p < p1; ++p) {
+        const int64_t fa = frame0 + 2 * p, fb = fa + 1;
+        const bool hb = fb < nframes;
+        const int la = fbad[fa], lb = hb ? fbad[fb] : FRAME_ZERO;
+        const int sa = pair_shift(la, fexp[fa], lb, hb ? fexp[fb] : 0), sb = hb ? pair_shift(lb, fexp[fb], la, fexp[fa]) : 0;
+        double pa, pb;
+        pair_power(Z + p * zps, k, nfft, nbins, m1, m2, blue, chirp, m, la, sa, lb, sb, pa, pb);
+        acc = acc + pa;
+        if (hb) acc = acc + pb;
+    }
+    slab[j * nbins + k] = acc;
 }
 
 // ---- mel / MFCC epilogue from power columns in global memory (a workgroup per frame, striding over the frames) -------------------
@@ -546,7 +644,8 @@ __global__ void bluestein_b_kernel(RootTab chirp, int64_t n, int64_t m, double2 
 }
 
 // ---- host plumbing ---------------------------------------------------------------------------------------------------------------
-thread_local double g_timing[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+constexpr int kTimingSlots = 11;
+thread_local double g_timing[kTimingSlots] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
 struct StreamHolder {
     hipStream_t s = nullptr;
@@ -700,22 +799,25 @@ struct EpiTables {   // W compacted band by band (each band's weights of its bin
 
 template <class T>
 int32_t stft_impl(int32_t kind, const T *s_in, int64_t L, int64_t n, int64_t noverlap, int64_t nfft, double fs, const T *window, const float *W,
-                  int64_t nmels, const float *D, int64_t nmfcc, int32_t device, T *out, int64_t capacity, int64_t *nframes) {
+                  int64_t nmels, const float *D, int64_t nmfcc, int32_t device, T *out, int64_t capacity, int64_t *nframes, int twosided = 0) {
     // ---- arguments (before any device is needed)
-    if (kind != LPVS_STFT_POWER && kind != LPVS_STFT_MEL && kind != LPVS_STFT_MFCC) { set_error("kind must be LPVS_STFT_POWER, _MEL or _MFCC, got %d", kind); return LPVS_EARGUMENT; }
+    const bool welch = kind == LPVS_STFT_WELCH;   // lpvs_welch only: out holds the mean over the frames, nbins values (nfft two-sided)
+    if (kind != LPVS_STFT_POWER && kind != LPVS_STFT_MEL && kind != LPVS_STFT_MFCC && !welch) { set_error("kind must be LPVS_STFT_POWER, _MEL or _MFCC, got %d", kind); return LPVS_EARGUMENT; }
     if (!nframes || (!s_in && L > 0)) { set_error("NULL argument"); return LPVS_EARGUMENT; }
     if (L < 0 || n < 1) { set_error("need L >= 0 and n >= 1 (L = %lld, n = %lld)", (long long)L, (long long)n); return LPVS_EARGUMENT; }
     if (noverlap < 0 || noverlap >= n) { set_error("noverlap must satisfy 0 <= noverlap < n (noverlap = %lld, n = %lld)", (long long)noverlap, (long long)n); return LPVS_EDOMAIN; }
     if (nfft < n) { set_error("nfft must be >= n (nfft = %lld, n = %lld)", (long long)nfft, (long long)n); return LPVS_EARGUMENT; }
     if (nfft > kMaxLen) { set_error("nfft = %lld exceeds the supported 2^26", (long long)nfft); return LPVS_EUNSUPPORTED; }
     const int64_t nbins = nfft / 2 + 1;
-    if (kind != LPVS_STFT_POWER && (!W || nmels < 1)) { set_error("the mel and MFCC kinds need W and nmels >= 1"); return LPVS_EARGUMENT; }
+    if ((kind == LPVS_STFT_MEL || kind == LPVS_STFT_MFCC) && (!W || nmels < 1)) { set_error("the mel and MFCC kinds need W and nmels >= 1"); return LPVS_EARGUMENT; }
     if (kind == LPVS_STFT_MFCC && (!D || nmfcc < 1)) { set_error("the MFCC kind needs D and nmfcc >= 1"); return LPVS_EARGUMENT; }
     if (kind == LPVS_STFT_MFCC && nmels + nmfcc > 16384) { set_error("nmels + nmfcc = %lld exceeds 16384", (long long)(nmels + nmfcc)); return LPVS_EUNSUPPORTED; }
     const int64_t hop = n - noverlap;
     const int64_t k = L >= n ? (L - n) / hop + 1 : 0;
-    const int64_t rows = kind == LPVS_STFT_POWER ? nbins : (kind == LPVS_STFT_MEL ? nmels : nmfcc);
+    const int64_t rows = welch ? (twosided ? nfft : nbins) : (kind == LPVS_STFT_POWER ? nbins : (kind == LPVS_STFT_MEL ? nmels : nmfcc));
+    const int64_t nout = welch ? rows : k * rows;   // output values
     *nframes = k;
+    if (welch && k == 0) { set_error("welch_pgram: the signal (L = %lld) is shorter than one frame (n = %lld): the mean over no frame is undefined", (long long)L, (long long)n); return LPVS_EDOMAIN; }
     // Bluestein length: the smallest 7-smooth m >= 2 nfft - 1 the engine runs
     const bool blue = !is_smooth(nfft);
     Plan pl = plan_length(nfft);
@@ -731,7 +833,7 @@ int32_t stft_impl(int32_t kind, const T *s_in, int64_t L, int64_t n, int64_t nov
     }
     LPVS_TRY(need_device());
     if (!out) return LPVS_OK;   // count only
-    if (capacity < k * rows) { set_error("capacity %lld < %lld outputs (%lld rows x %lld frames)", (long long)capacity, (long long)(k * rows), (long long)rows, (long long)k); return LPVS_EARGUMENT; }
+    if (capacity < nout) { set_error("capacity %lld < %lld outputs (%lld rows x %lld frames)", (long long)capacity, (long long)nout, (long long)rows, (long long)(welch ? 1 : k)); return LPVS_EARGUMENT; }
     if (k == 0) return LPVS_OK;
     LPVS_HIP(hipSetDevice(device));
 
@@ -758,7 +860,7 @@ int32_t stft_impl(int32_t kind, const T *s_in, int64_t L, int64_t n, int64_t nov
     const int64_t flen = pl.len;                             // FFT length: nfft, or m for Bluestein
     const bool lds = flen <= kFftMax;
     const size_t per_pair = lds ? 0 : 2 * sizeof(double2) * (size_t)flen;   // tmp + Z
-    const size_t power_per_pair = (kind == LPVS_STFT_POWER) ? 0 : 2 * sizeof(double) * (size_t)nbins;
+    const size_t power_per_pair = (kind == LPVS_STFT_POWER || welch) ? 0 : 2 * sizeof(double) * (size_t)nbins;
     // LDS paths: frame pairs per workgroup -- the FFT buffer, the power / mel / DCT regions of the epilogue (doubles) and the split's
     // registers must fit; 0 means the epilogue's regions do not fit next to one pair (the fallback through global power columns)
     int64_t lds_b = 0;
@@ -771,11 +873,28 @@ int32_t stft_impl(int32_t kind, const T *s_in, int64_t L, int64_t n, int64_t nov
         lds_b = std::max<int64_t>(lds_b, 0);
     }
     const bool fallback = lds && lds_b < 1;
+    // frame averaging: S slabs of nbins partial sums, at most F frames behind one slab (the header comment has the rule)
+    int64_t wS = 0, wF = 0, wcp = 0;
+    if (welch && lds) {
+        const int64_t nbatch = ceil_div(npair_all, lds_b), bpw = std::max<int64_t>(1, kWelchChain / (2 * lds_b));
+        wS = std::max<int64_t>(std::min<int64_t>(nbatch, kWelchSlabs), ceil_div(nbatch, bpw));
+        wF = ceil_div(nbatch, wS) * 2 * lds_b - ((nbatch - 1) % wS == 0 ? 2 * lds_b * nbatch - k : 0);
+    } else if (welch) {
+        wcp = std::max<int64_t>(1, std::min<int64_t>(npair_all, (int64_t)(kScratchBudget / per_pair)));
+        for (int64_t p0 = 0; p0 < npair_all; p0 += wcp) {
+            const int64_t nfr = std::min<int64_t>(2 * std::min<int64_t>(wcp, npair_all - p0), k - 2 * p0);
+            wS += ceil_div(nfr, kWelchChunkFrames);
+            wF = std::max<int64_t>(wF, std::min<int64_t>(nfr, kWelchChunkFrames));
+        }
+    }
+    if (wS > ((int64_t)1 << 30)) { set_error("welch_pgram: %lld frames need more than 2^30 slabs", (long long)k); return LPVS_EUNSUPPORTED; }
+    int64_t wdepth = 0;
+    while (((int64_t)1 << wdepth) < wS) ++wdepth;
     {
         size_t fr = 0, tot = 0;
         LPVS_HIP(hipMemGetInfo(&fr, &tot));
         const size_t avail = fr + pool_cached_bytes(device);
-        const size_t need = (dev_out ? 0 : sizeof(T) * (size_t)(k * rows)) + (device_of_ptr(s_in) == device ? 0 : sizeof(T) * (size_t)L) +
+        const size_t need = (dev_out ? 0 : sizeof(T) * (size_t)nout) + sizeof(double) * (size_t)(wS * nbins) + (device_of_ptr(s_in) == device ? 0 : sizeof(T) * (size_t)L) +
                             per_pair + power_per_pair + (blue ? sizeof(double2) * (size_t)m * 3 : 0) +
                             (lds && !fallback ? 0 : 2 * sizeof(int32_t) * (size_t)k) +                    // frame flags, exponents
                             (fallback ? sizeof(double) * (size_t)(k * nbins) + sizeof(double2) * (size_t)(npair_all * flen) : 0);
@@ -787,7 +906,7 @@ int32_t stft_impl(int32_t kind, const T *s_in, int64_t L, int64_t n, int64_t nov
     }
     LPVS_HIP(hipEventRecord(ev.e[0], s));   // setup: host tables, band ranges, uploads (the stream is idle until e[1])
     Staged<T> ds, dw;
-    DevBuf dout, tmp, zbuf, pwbuf, bvec, btmp, bhat, fbad, fexp;
+    DevBuf dout, tmp, zbuf, pwbuf, bvec, btmp, bhat, fbad, fexp, wslab;
     DrainOnExit drain(s);
     LPVS_TRY(ds.set(s_in, L, device, s));
     if (window) {
@@ -796,9 +915,10 @@ int32_t stft_impl(int32_t kind, const T *s_in, int64_t L, int64_t n, int64_t nov
         dw.p = dw.own.template as<T>();
     }
     T *dst = out;
-    if (!dev_out) { LPVS_TRY(dout.alloc(sizeof(T) * (size_t)(k * rows))); dst = dout.as<T>(); }
+    if (!dev_out) { LPVS_TRY(dout.alloc(sizeof(T) * (size_t)nout)); dst = dout.as<T>(); }
+    if (welch) LPVS_TRY(wslab.alloc(sizeof(double) * (size_t)(wS * nbins)));
     EpiTables et;
-    if (kind != LPVS_STFT_POWER) LPVS_TRY(et.make(W, nmels, nbins, kind == LPVS_STFT_MFCC ? D : nullptr, nmfcc, device, s));
+    if (kind == LPVS_STFT_MEL || kind == LPVS_STFT_MFCC) LPVS_TRY(et.make(W, nmels, nbins, kind == LPVS_STFT_MFCC ? D : nullptr, nmfcc, device, s));
     LengthTables lt;
     LPVS_TRY(lt.make(pl, s));
     HostRootTab chirp;
@@ -807,7 +927,7 @@ int32_t stft_impl(int32_t kind, const T *s_in, int64_t L, int64_t n, int64_t nov
     Epi<T> E;
     E.kind = kind; E.nfft = nfft; E.nbins = nbins; E.m1 = 1.0 / r; E.m2 = 2.0 / r;
     E.W = et.w.as<float>(); E.blo = et.lo.as<int64_t>(); E.bhi = et.hi.as<int64_t>(); E.woff = et.off.as<int64_t>(); E.nmels = (int)nmels;
-    E.D = et.d.as<float>(); E.nmfcc = (int)nmfcc; E.out = dst; E.nframes = k;
+    E.D = et.d.as<float>(); E.nmfcc = (int)nmfcc; E.out = dst; E.nframes = k; E.wslab = wslab.as<double>();
 
     FftJob<T> J;
     J.in_mode = IN_SIGNAL; J.s = ds.p; J.win = dw.p; J.n = n; J.hop = hop; J.nframes = k;
@@ -847,7 +967,16 @@ int32_t stft_impl(int32_t kind, const T *s_in, int64_t L, int64_t n, int64_t nov
         path = blue ? 3 : 1;
         set_fft(J, (int)flen, lt.r1, lt.t1.buf.as<double2>(), 1, npair_all, 1);
         if (blue) { J.post = POST_BLUESTEIN_LDS; J.bhat = bhat.as<double2>(); J.bhat_cs = 0; J.bhat_es = 1; J.blue_m = m; }
-        if (b >= 1) {   // everything in one launch
+        if (welch) {    // wS workgroups a launch, batch after batch into their slabs
+            J.B = (int)b; J.out_mode = OUT_EPI; J.epi = E;
+            const int64_t nbatch = ceil_div(npair_all, b);
+            for (int64_t b0 = 0; b0 < nbatch; b0 += wS) {
+                J.blk0 = b0;
+                stft_welch_kernel<T><<<(unsigned)std::min<int64_t>(wS, nbatch - b0), kThreads, 0, s>>>(J);
+                LPVS_HIP(hipGetLastError());
+            }
+            B = (int)b;
+        } else if (b >= 1) {   // everything in one launch
             J.B = (int)b; J.out_mode = OUT_EPI; J.epi = E;
             LPVS_TRY(launch_fft(J, s));
             B = (int)b;
@@ -873,9 +1002,10 @@ int32_t stft_impl(int32_t kind, const T *s_in, int64_t L, int64_t n, int64_t nov
         LPVS_TRY(flag_frames());
         // chunks of frame pairs: tmp + Z of a chunk within the scratch budget (at least one pair)
         const int64_t cp = std::max<int64_t>(1, std::min<int64_t>(npair_all, (int64_t)(kScratchBudget / per_pair)));
+        int64_t wbase = 0;   // slabs written by the chunks so far
         LPVS_TRY(tmp.alloc(sizeof(double2) * (size_t)(cp * flen)));
         LPVS_TRY(zbuf.alloc(sizeof(double2) * (size_t)(cp * flen)));
-        if (kind != LPVS_STFT_POWER) LPVS_TRY(pwbuf.alloc(sizeof(double) * (size_t)(2 * cp * nbins)));
+        if (kind != LPVS_STFT_POWER && !welch) LPVS_TRY(pwbuf.alloc(sizeof(double) * (size_t)(2 * cp * nbins)));
         for (int64_t p0 = 0; p0 < npair_all; p0 += cp) {
             const int64_t np = std::min<int64_t>(cp, npair_all - p0), f0 = 2 * p0;
             FftJob<T> A = J;
@@ -889,7 +1019,14 @@ int32_t stft_impl(int32_t kind, const T *s_in, int64_t L, int64_t n, int64_t nov
                 LPVS_TRY(four_step(I, lt, np, tmp.as<double2>(), zbuf.as<double2>(), flen, s, nullptr));
             } else
                 LPVS_TRY(four_step(A, lt, np, tmp.as<double2>(), zbuf.as<double2>(), flen, s, nullptr));
-            if (kind == LPVS_STFT_POWER) {
+            if (welch) {
+                const int64_t ns = ceil_div(np, kWelchChunkFrames / 2);
+                welch_split_sum_kernel<<<dim3((unsigned)ceil_div(nbins, kEpiThreads), (unsigned)ns), kEpiThreads, 0, s>>>(
+                    zbuf.as<double2>(), flen, nfft, nbins, E.m1, E.m2, blue, chirp.tab, m, f0, k, fbad.as<int32_t>(), fexp.as<int32_t>(), np,
+                    kWelchChunkFrames / 2, wslab.as<double>() + wbase * nbins);
+                LPVS_HIP(hipGetLastError());
+                wbase += ns;
+            } else if (kind == LPVS_STFT_POWER) {
                 split_power_kernel<T><<<frame_blocks(np), kEpiThreads, 0, s>>>(zbuf.as<double2>(), flen, nfft, nbins, E.m1, E.m2, blue, chirp.tab, m,
                                                                                f0, k, fbad.as<int32_t>(), fexp.as<int32_t>(), dst, 0, np);
                 LPVS_HIP(hipGetLastError());
@@ -904,8 +1041,17 @@ int32_t stft_impl(int32_t kind, const T *s_in, int64_t L, int64_t n, int64_t nov
             }
         }
     }
+    if (welch) {   // the slabs in a fixed pairwise tree (two levels a launch), then the mean
+        for (int64_t st = 1; st < wS; st *= 4) {
+            const int64_t groups = ceil_div(wS, 4 * st);
+            welch_tree_kernel<<<(unsigned)ceil_div(groups * nbins, kEpiThreads), kEpiThreads, 0, s>>>(wslab.as<double>(), wS, nbins, st, groups);
+            LPVS_HIP(hipGetLastError());
+        }
+        welch_finish_kernel<T><<<(unsigned)ceil_div(nbins, kEpiThreads), kEpiThreads, 0, s>>>(wslab.as<double>(), nbins, nfft, (double)k, twosided, dst);
+        LPVS_HIP(hipGetLastError());
+    }
     LPVS_HIP(hipEventRecord(ev.e[2], s));
-    if (!dev_out) LPVS_HIP(hipMemcpyAsync(out, dst, sizeof(T) * (size_t)(k * rows), hipMemcpyDefault, s));
+    if (!dev_out) LPVS_HIP(hipMemcpyAsync(out, dst, sizeof(T) * (size_t)nout, hipMemcpyDefault, s));
     LPVS_HIP(hipEventRecord(ev.e[3], s));
     LPVS_HIP(hipStreamSynchronize(s));
     float ms[3] = {0, 0, 0};
@@ -915,6 +1061,8 @@ int32_t stft_impl(int32_t kind, const T *s_in, int64_t L, int64_t n, int64_t nov
     // paths; 0 on the LDS fallback through global power columns), [7] rows, [8] setup: host tables, band ranges and uploads
     g_timing[0] = ms[1]; g_timing[1] = ms[2]; g_timing[2] = (double)ms[0] + ms[1] + ms[2]; g_timing[3] = (double)k; g_timing[4] = path;
     g_timing[5] = (double)flen; g_timing[6] = B; g_timing[7] = (double)rows; g_timing[8] = ms[0];
+    // [9] LPVS_STFT_WELCH: the longest chain of dependent additions behind one bin, D = F - 1 + ceil(log2 S); [10] its slabs S (0 otherwise)
+    g_timing[9] = welch ? (double)(wF - 1 + wdepth) : 0.0; g_timing[10] = (double)wS;
     return LPVS_OK;
 }
 
@@ -1041,6 +1189,7 @@ int32_t lpvs_dct_matrix(int64_t nfilters, int64_t ninput, float *D) {
 int32_t lpvs_stft_f64(int32_t kind, const double *s, int64_t L, int64_t n, int64_t noverlap, int64_t nfft, double fs, const double *window,
                       const float *W, int64_t nmels, const float *D, int64_t nmfcc, int32_t device, double *out, int64_t capacity,
                       int64_t *nframes) {
+    if (kind == LPVS_STFT_WELCH) { set_error("LPVS_STFT_WELCH is the epilogue of lpvs_welch (lpvs_stft has no frame-averaged output)"); return LPVS_EARGUMENT; }
     try {
         return stft_impl(kind, s, L, n, noverlap, nfft, fs, window, W, nmels, D, nmfcc, device, out, capacity, nframes);
     } catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
@@ -1048,8 +1197,25 @@ int32_t lpvs_stft_f64(int32_t kind, const double *s, int64_t L, int64_t n, int64
 int32_t lpvs_stft_f32(int32_t kind, const float *s, int64_t L, int64_t n, int64_t noverlap, int64_t nfft, double fs, const float *window,
                       const float *W, int64_t nmels, const float *D, int64_t nmfcc, int32_t device, float *out, int64_t capacity,
                       int64_t *nframes) {
+    if (kind == LPVS_STFT_WELCH) { set_error("LPVS_STFT_WELCH is the epilogue of lpvs_welch (lpvs_stft has no frame-averaged output)"); return LPVS_EARGUMENT; }
     try {
         return stft_impl(kind, s, L, n, noverlap, nfft, fs, window, W, nmels, D, nmfcc, device, out, capacity, nframes);
+    } catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
+}
+int32_t lpvs_welch_f64(const double *s, int64_t L, int64_t n, int64_t noverlap, int64_t nfft, double fs, const double *window, int32_t onesided,
+                       int32_t device, double *out, int64_t *nframes) {
+    if (!out) { set_error("NULL argument"); return LPVS_EARGUMENT; }
+    try {
+        return stft_impl(LPVS_STFT_WELCH, s, L, n, noverlap, nfft, fs, window, nullptr, 0, nullptr, 0, device, out, onesided ? nfft / 2 + 1 : nfft,
+                         nframes, onesided ? 0 : 1);
+    } catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
+}
+int32_t lpvs_welch_f32(const float *s, int64_t L, int64_t n, int64_t noverlap, int64_t nfft, double fs, const float *window, int32_t onesided,
+                       int32_t device, float *out, int64_t *nframes) {
+    if (!out) { set_error("NULL argument"); return LPVS_EARGUMENT; }
+    try {
+        return stft_impl(LPVS_STFT_WELCH, s, L, n, noverlap, nfft, fs, window, nullptr, 0, nullptr, 0, device, out, onesided ? nfft / 2 + 1 : nfft,
+                         nframes, onesided ? 0 : 1);
     } catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
 }
 int32_t lpvs_mel_project_f64(const double *power, int64_t nbins, int64_t frames, const float *W, int64_t nmels, int32_t device, double *out) {
@@ -1062,7 +1228,7 @@ int32_t lpvs_mel_project_f32(const float *power, int64_t nbins, int64_t frames, 
 }
 int32_t lpvs_stft_last_timing(double *out, int32_t n) {
     if (!out || n < 0) { set_error("NULL argument"); return LPVS_EARGUMENT; }
-    for (int32_t k = 0; k < n && k < 9; ++k) out[k] = g_timing[k];
+    for (int32_t k = 0; k < n && k < kTimingSlots; ++k) out[k] = g_timing[k];
     return LPVS_OK;
 }
 
