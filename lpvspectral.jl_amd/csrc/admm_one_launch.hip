@@ -4,6 +4,7 @@
 #include "lpvs_internal.h"
 #include "admm_device.h"
 #include "admm_host.h"
+#include "tile_order.h"
 
 #include <algorithm>
 #include <map>
@@ -187,7 +188,7 @@ __device__ __forceinline__ void fi_fixed_product(const FixRaw &fr, const double 
 #if defined(LPVS_TIMELINE) && LPVS_TIMELINE < 3
 // Debug build only (make timeline -> liblpvspectral_timeline.so; tools/iter_timeline.py): every workgroup of the single-problem one-launch
 // iteration leaves wall-clock stamps (s_memrealtime, 100 MHz) of its phases, 8 words per workgroup and launch parity:
-//   {g, entry, update done, prologue barrier passed, tile consumed, last atomic issued, XCC_ID, HW_ID}
+//   {g, entry, update done, prologue barrier passed, tile consumed, last atomic issued, XCC_ID | tile << 8, HW_ID}
 __device__ unsigned long long *g_lpvs_tl = nullptr;
 extern "C" int32_t lpvs_debug_set_timeline(unsigned long long *dev_buf) {
     return hipMemcpyToSymbol(HIP_SYMBOL(g_lpvs_tl), &dev_buf, sizeof(dev_buf)) == hipSuccess ? LPVS_OK : LPVS_EDEVICE;
@@ -219,7 +220,6 @@ fi_one_tile_body(const AdmmParams &p, const unsigned char *__restrict__ Mp, cons
     unsigned long long *tl_rec = tl_on ? g_lpvs_tl + ((size_t)(g & 1) * (size_t)ntiles + blockIdx.x) * 8 : nullptr;
     if (tl_on && threadIdx.x == 0) {
         tl_rec[0] = (unsigned long long)g; tl_rec[1] = __builtin_amdgcn_s_memrealtime();
-        tl_rec[6] = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20);      // HW_REG_XCC_ID[3:0]
         tl_rec[7] = __builtin_amdgcn_s_getreg((32 - 1) << 11 | 0 << 6 | 4);      // HW_REG_HW_ID
     }
 #endif
@@ -233,16 +233,23 @@ fi_one_tile_body(const AdmmParams &p, const unsigned char *__restrict__ Mp, cons
     // Launch order: the diagonal tiles first.  Their workgroups own the row blocks' state (the longest prologue) and at cfg3 they are
     // the float-head tiles (96 KB, loaded in two halves after the prologue): dealt out in tile order the last workgroup of the launch
     // would be the slowest one.
+    // Single problems walk the tiles below the diagonal backwards, in groups of eight, on every other launch (tile_order.h): the first
+    // workgroups of a launch then ask for the lines the launch before it left in the XCDs' L2s.  The parity is that of the absolute
+    // iteration index: the order does not depend on the chunking.  (Any bijection gives the same bits: the sums are integer atomics.)
+    const int bx = (MODE == FI_LAST || BATCH) ? (int)blockIdx.x : tile_order_index((int)blockIdx.x, nblk, p.tile_order & (int)(g & 1));
     int I, J;
-    if (MODE == FI_LAST || (int)blockIdx.x < nblk) { I = J = blockIdx.x; }
+    if (MODE == FI_LAST || bx < nblk) { I = J = bx; }
     else {
-        const int k = (int)blockIdx.x - nblk;                           // k-th tile below the diagonal: k = I (I - 1) / 2 + J, J < I
+        const int k = bx - nblk;                                        // k-th tile below the diagonal: k = I (I - 1) / 2 + J, J < I
         I = (int)((1.0 + sqrt(1.0 + 8.0 * (double)k)) * 0.5);
         while (I * (I - 1) / 2 > k) --I;
         while ((I + 1) * I / 2 <= k) ++I;
         J = k - I * (I - 1) / 2;
     }
     const int t = I * (I + 1) / 2 + J;
+#if defined(LPVS_TIMELINE) && LPVS_TIMELINE < 3
+    if (tl_on && threadIdx.x == 0) tl_rec[6] = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20) | (unsigned long long)t << 8;   // HW_REG_XCC_ID[3:0], the tile above it
+#endif
     const unsigned char *tile = Mp + (size_t)t * (F32 ? (size_t)TS * TS * 4 : kSplitTileBytes);
     const unsigned char ttype = (MODE == FI_LAST || F32) ? 0 : types[t];
     AdmmStatus *status = p.status + sg;

@@ -494,6 +494,10 @@ AdmmParams make_params(const lpvs_problem *h) {
     p.fi_R = h->fi_R; p.fi_xbmax = h->fi_xbmax;
     p.fi_prefetch_all = sym && h->Mp_mode == kMpMixed && h->Mp_fixed_tiles == (int64_t)(symv_packed_doubles(h->np) / (128 * 128)) ? 1 : 0;
     p.opt_iteration = h->opt[LPVS_OPT_ITERATION]; p.opt_nt_loads = h->opt[LPVS_OPT_NT_LOADS];
+    {   // single problems on the one-launch iteration: mirrored tile order on odd launches (LPVS_TILE_ORDER=forward: the same order every launch, for A/B runs; read per call)
+        const char *e = experiment_env("LPVS_TILE_ORDER");
+        p.tile_order = p.fi != nullptr && !(e && std::string(e) == "forward") ? 1 : 0;
+    }
     p.sm_ctl = !sym && h->sm_ctl.p ? h->sm_ctl.as<int>() : nullptr;
     return p;
 }

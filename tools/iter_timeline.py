@@ -66,8 +66,11 @@ def describe(name, v):
 
 for tag, R in (("launch A", A), ("launch B", B)):
     t0 = R[:, 1].min()
+    tile = R[:, 6] >> 8                           # t = I (I + 1) / 2 + J of the workgroup's tile (csrc/tile_order.h deals them)
+    gpar = int(R[0, 0]) & 1
     ent, upd, bar, cons, end = (R[:, k] - t0 for k in (1, 2, 3, 4, 5))
-    print(f"\n== {tag}: span (first entry -> last workgroup's last atomic) {end.max() * TICK_US:.2f} us")
+    print(f"\n== {tag}: g = {int(R[0, 0])}, parity {gpar} ({'forward' if int(tile[nblk]) == 1 else 'mirrored'} "   # (forward: the first workgroup below the diagonal takes tile (1, 0), t = 1)
+          f"tile order): span (first entry -> last workgroup's last atomic) {end.max() * TICK_US:.2f} us")
     describe("entry (after the launch's first entry)", ent)
     if FULL:
         describe("update done - entry (state loads, prox, dual step)", upd - ent)
@@ -89,7 +92,12 @@ for tag, R in (("launch A", A), ("launch B", B)):
     xcc = R[:, 6] & 0xF
     print("per XCD: workgroups / last end (us): " + "  ".join(f"x{int(k)}: {int((xcc == k).sum())} / {end[xcc == k].max() * TICK_US:.2f}" for k in np.unique(xcc)))
     print(f"workgroup index -> XCD of the first 16: {[int(k) for k in xcc[:16]]}")
+    print(f"workgroup index -> tile: first 4 below the diagonal {[(int(i), int(tile[i])) for i in range(nblk, nblk + 4)]}, last 4 {[(int(i), int(tile[i])) for i in range(ntiles - 4, ntiles)]}")
+    # the first workgroups below the diagonal ask for what the launch before it read last: lifetimes by place in the launch order
+    for lo in range(nblk, ntiles, 252):
+        sel = np.arange(lo, min(lo + 252, ntiles))
+        describe(f"  workgroups {sel[0]} .. {sel[-1]} (tiles {int(tile[sel].min())} .. {int(tile[sel].max())}): lifetime", (end - ent)[sel])
     last = np.argsort(end)[-8:]
-    print("the 8 last workgroups to finish (index, entry, lifetime us): " + "  ".join(f"({int(i)}, {ent[i] * TICK_US:.2f}, {(end - ent)[i] * TICK_US:.2f})" for i in last))
+    print("the 8 last workgroups to finish (index, tile, entry, lifetime us): " + "  ".join(f"({int(i)}, {int(tile[i])}, {ent[i] * TICK_US:.2f}, {(end - ent)[i] * TICK_US:.2f})" for i in last))
 gap = B[:, 1].min() - A[:, 5].max()
 print(f"\nlaunch boundary: first entry of launch B - last atomic of launch A = {gap * TICK_US:.2f} us;  launch period (first entry to first entry) = {(B[:, 1].min() - A[:, 1].min()) * TICK_US:.2f} us")

@@ -2,10 +2,13 @@
 // 256 MiB Infinity Cache between two ADMM iterations, and what is the ceiling of a plain streaming read at that size?)
 // Tile-shaped access like the mat-vec: workgroup b reads a contiguous chunk of `chunk` bytes with 16-B loads per lane.
 // build + run on the GPU box:  hipcc --offload-arch=gfx950 -O2 tools/stream_read.hip -o /tmp/stream_read && /tmp/stream_read
+//   /tmp/stream_read carry      the L2 carry-over probe alone (carry-pmc: its launches only, for a counter pass)
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
 #include <vector>
+#include <cstring>
+#include "../lpvspectral.jl_amd/csrc/tile_order.h"
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 template <int UNROLL>
@@ -275,7 +278,93 @@ __global__ void __launch_bounds__(256, 3) persist_tiles(const u32x4 *__restrict_
     }
 }
 
-int main() {
+// Do clean L2 lines survive the boundary between two dependent launches?  (`stream_read carry`, profiles/r07_l2_carryover_probe.txt.)
+// read_tiles's access (one workgroup per tile, 18 16-byte loads per lane up front, 3 workgroups per CU) over the cfg3 inverse's
+// 2080 slots of 98 304 bytes, launch after launch on one stream; every workgroup reads a word the launch before it wrote and leaves
+// the XCD it ran on (HW_REG_XCC_ID) for the next.  ORDER 0: every launch walks the slots in the same order;  1: odd launches in the
+// XCD-preserving mirrored order of csrc/tile_order.h (first `nfixed` slots fixed);  2: odd launches plainly reversed (slot mod 8 NOT
+// kept: what the XCD affinity is worth).
+template <int ORDER>
+__global__ void __launch_bounds__(256, 3) read_tiles_carry(const u32x4 *__restrict__ src, int64_t slot16, int nfixed, int odd, const unsigned *__restrict__ prev,
+                                                           unsigned *__restrict__ cur, unsigned *sink) {
+    const int bx = blockIdx.x, n = gridDim.x;
+    int t = bx;
+    if (ORDER == 1) t = lpvs::tile_order_index(bx, nfixed, odd);
+    if (ORDER == 2 && odd && bx >= nfixed) t = nfixed + (n - 1 - bx);
+    const u32x4 *p = src + (int64_t)t * slot16;
+    const unsigned dep = prev[bx];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, c = lane & 15;
+    u32x4 v[18];
+#pragma unroll
+    for (int rg = 0; rg < 8; ++rg) {
+        const int base = ((wave * 32 + g + 4 * rg) * 128 + 4 * c) / 4;
+        v[2 * rg] = p[base];
+        v[2 * rg + 1] = p[base + 16];
+    }
+    v[16] = p[4096 + (wave * 64 + lane) * 2];
+    v[17] = p[4096 + (wave * 64 + lane) * 2 + 1];
+    u32x4 acc = {dep, 0, 0, 0};
+#pragma unroll
+    for (int u = 0; u < 18; ++u) acc ^= v[u];
+    if (threadIdx.x == 0) cur[bx] = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20);      // HW_REG_XCC_ID[3:0]
+    if ((acc.x ^ acc.y ^ acc.z ^ acc.w) == 0x12345678u) sink[0] = 1;
+}
+static void carry_launch(int order, int n, const u32x4 *buf, int64_t slot16, int nfixed, int g, unsigned *xcc, unsigned *sink) {
+    const unsigned *prev = xcc + ((g + 1) & 1) * n;
+    unsigned *cur = xcc + (g & 1) * n;
+    if (order == 0) hipLaunchKernelGGL(read_tiles_carry<0>, dim3(n), dim3(256), 0, 0, buf, slot16, nfixed, g & 1, prev, cur, sink);
+    else if (order == 1) hipLaunchKernelGGL(read_tiles_carry<1>, dim3(n), dim3(256), 0, 0, buf, slot16, nfixed, g & 1, prev, cur, sink);
+    else hipLaunchKernelGGL(read_tiles_carry<2>, dim3(n), dim3(256), 0, 0, buf, slot16, nfixed, g & 1, prev, cur, sink);
+}
+// `carry`: five repetitions of 400 launches per order, interleaved, HIP events around each; where the workgroups ran.
+// `carry-pmc`: 40 launches per order and nothing else (for rocprofv3 --pmc: the three orders are three kernel names).
+static int carry_main(bool pmc_only) {
+    const int nblk = 64, n = nblk * (nblk + 1) / 2;  // cfg3: 2080 tiles
+    const int64_t slot = 98304;
+    static const char *const names[3] = {"same order              ", "mirrored, slot mod 8 kept", "plainly reversed         "};
+    u32x4 *buf; unsigned *xcc, *sink;
+    if (hipMalloc(&buf, n * slot) != hipSuccess || hipMalloc(&xcc, 2 * n * 4) != hipSuccess || hipMalloc(&sink, 4) != hipSuccess) { printf("allocation failed\n"); return 1; }
+    hipMemset(buf, 1, n * slot); hipMemset(xcc, 0, 2 * n * 4);
+    hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
+    if (pmc_only) {
+        for (int order = 0; order < 3; ++order)
+            for (int g = 0; g < 40; ++g) carry_launch(order, n, buf, slot / 16, nblk, g, xcc, sink);
+        return hipDeviceSynchronize() == hipSuccess ? 0 : 1;
+    }
+    printf("%d slots of %lld bytes (73 728 read per slot: %.1f MB per launch), first %d slots fixed, 400 launches per figure\n", n, (long long)slot, n * 73728e-6, nblk);
+    for (int g = 0; g < 20; ++g) carry_launch(0, n, buf, slot / 16, nblk, g, xcc, sink);
+    for (int rep = 0; rep < 5; ++rep)
+        for (int order = 0; order < 3; ++order) {
+            const int reps = 400;
+            hipEventRecord(e0, 0);
+            for (int g = 0; g < reps; ++g) carry_launch(order, n, buf, slot / 16, nblk, g, xcc, sink);
+            hipEventRecord(e1, 0);
+            if (hipEventSynchronize(e1) != hipSuccess) { printf("launch failed\n"); return 1; }
+            float ms; hipEventElapsedTime(&ms, e0, e1);
+            printf("rep %d  %s: %7.2f us per launch\n", rep, names[order], ms * 1e3 / reps);
+        }
+    // where the workgroups of the last two launches (an even and an odd one) ran
+    std::vector<unsigned> h(2 * n);
+    hipMemcpy(h.data(), xcc, 2 * n * 4, hipMemcpyDeviceToHost);
+    int moved = 0, off_class = 0;
+    int hist[8][16] = {};
+    for (int b = 0; b < n; ++b) {
+        moved += h[b] != h[n + b];
+        hist[b & 7][h[b] & 15]++; hist[b & 7][h[n + b] & 15]++;
+    }
+    for (int cl = 0; cl < 8; ++cl) {
+        int best = 0;
+        for (int x = 0; x < 16; ++x) if (hist[cl][x] > hist[cl][best]) best = x;
+        printf("blockIdx mod 8 = %d: ", cl);
+        for (int x = 0; x < 16; ++x) if (hist[cl][x]) { printf(" XCC %d x %d", x, hist[cl][x]); if (x != best) off_class += hist[cl][x]; }
+        printf("\n");
+    }
+    printf("workgroups on a different XCC in the two launches: %d of %d; workgroups off their class's XCC: %d of %d\n", moved, n, off_class, 2 * n);
+    return 0;
+}
+
+int main(int argc, char **argv) {
+    if (argc > 1 && !strncmp(argv[1], "carry", 5)) return carry_main(!strcmp(argv[1], "carry-pmc"));
     const int64_t chunk = 74240;                       // one fixed-point tile
     unsigned *sink; hipMalloc(&sink, 4);
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
