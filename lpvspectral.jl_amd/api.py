@@ -484,10 +484,12 @@ class Problem:
         check(lib().lpvs_admm_get_offset_f64(self._h, out_ptr(xb), int(xb.size)))
         return xb
 
-    def admm_get(self):
+    def admm_get(self, f64=False):
+        """``(x, z, u)`` in the handle's I/O type; ``f64=True``: the double state itself, of ``_f32`` handles too."""
         shape = self.n if self.ns == 1 else (self.n, self.ns)
-        x, z, u = (np.zeros(shape, order="F", dtype=np.float32 if self.f32 else np.float64) for _ in range(3))
-        fn = lib().lpvs_admm_get_f32 if self.f32 else lib().lpvs_admm_get_f64
+        f32 = self.f32 and not f64
+        x, z, u = (np.zeros(shape, order="F", dtype=np.float32 if f32 else np.float64) for _ in range(3))
+        fn = lib().lpvs_admm_get_f32 if f32 else lib().lpvs_admm_get_f64
         check(fn(self._h, out_ptr(x), out_ptr(z), out_ptr(u)))
         return x, z, u
 

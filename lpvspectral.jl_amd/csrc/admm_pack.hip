@@ -78,14 +78,15 @@ pack_tiles_split_kernel(const double *__restrict__ M, int64_t np, unsigned char 
     }
 }
 
-// max|M| of a symmetric positive definite matrix sits on its diagonal (|m_ij| <= sqrt(m_ii m_jj)): np loads instead of a pass over np^2
-// entries (0.2 ms at n = 8192).  Every matrix packed here is the inverse of G + shift I, G a Gram matrix.
+// max|M| of a symmetric positive definite matrix sits on its diagonal (|m_ij| <= sqrt(m_ii m_jj)): n loads instead of a pass over np^2
+// entries (0.2 ms at n = 8192).  Every matrix packed here is the inverse of G + shift I, G a Gram matrix.  Valid rows only: a pad row holds
+// a 1 on its diagonal (add_diag_kernel), and M <= mu I -- counted, it would make max|M| = 1 and loosen the admission limit by 1 / mu.
 __global__ void __launch_bounds__(256)
-absmax_kernel(const double *__restrict__ M, int64_t np, unsigned long long *__restrict__ out) {
+absmax_kernel(const double *__restrict__ M, int64_t np, int64_t n, unsigned long long *__restrict__ out) {
     M += (int64_t)blockIdx.y * np * np;              // blockIdx.y = matrix of a batch
     out += blockIdx.y;
     double m = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < np; i += (int64_t)gridDim.x * 256) m = fmax(m, fabs(M[i * np + i]));
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) m = fmax(m, fabs(M[i * np + i]));
 #pragma unroll
     for (int w = 32; w >= 1; w >>= 1) m = fmax(m, __shfl_xor(m, w, 64));
     if ((threadIdx.x & 63) == 0 && m > 0.0) atomicMax(out, (unsigned long long)__double_as_longlong(m));   // positive doubles order like integers
@@ -245,12 +246,14 @@ int32_t launch_pack_tiles_mixed(const double *M, int64_t np, unsigned char *Mp, 
     return launch_pack_tiles_mixed_batch(M, np, 1, Mp, types, absmax, s, diag_float, abs_part, n_valid, rows_scratch, fix_bits);
 }
 
-// ... of nbatch matrices: types = [nbatch][ntiles] bytes, absmax = nbatch * 8 bytes of device scratch
+// ... of nbatch matrices: types = [nbatch][ntiles] bytes, absmax = nbatch * 8 bytes of device scratch; n_valid = rows of M that are not
+// padding (0: all np) -- max|M| of the admission rule is taken over them
 int32_t launch_pack_tiles_mixed_batch(const double *M, int64_t np, int nbatch, unsigned char *Mp, unsigned char *types, unsigned long long *absmax,
                                       hipStream_t s, bool diag_float, double *abs_part, int64_t n_valid, double *rows_scratch, int fix_bits) {
     const int nblk = (int)(np / TS);
     LPVS_HIP(hipMemsetAsync(absmax, 0, sizeof(unsigned long long) * ((size_t)nbatch + (abs_part ? 1 : 0)), s));
-    hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)std::min<int64_t>(16, ceil_div(np, 256)), (unsigned)nbatch), dim3(256), 0, s, M, np, absmax);
+    hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)std::min<int64_t>(16, ceil_div(np, 256)), (unsigned)nbatch), dim3(256), 0, s, M, np,
+                       n_valid > 0 && n_valid < np ? n_valid : np, absmax);
     const double step_scale = 0x1p-44 * std::sqrt(8192.0 / (double)np);
     hipLaunchKernelGGL(pack_tiles_mixed_kernel, dim3((unsigned)(nblk * (nblk + 1) / 2), (unsigned)nbatch), dim3(256), 0, s, M, np, Mp, types, absmax, step_scale, diag_float ? 1 : 0,
                        abs_part, abs_part ? abs_part + (size_t)(nblk * (nblk + 1) / 2) * TS : nullptr,

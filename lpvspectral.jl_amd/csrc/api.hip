@@ -1330,7 +1330,7 @@ int32_t lpvs_admm_init_f64(lpvs_problem *h, const double *x0, double mu, double 
             if (!h->corr.p) LPVS_TRY(h->corr.alloc(3 * v));
             LPVS_HIP(hipMemcpyAsync(h->xb0.p, h->xb.p, v, hipMemcpyDeviceToDevice, s));
         }
-        if (h->nib_period > 0 && h->Mp_mode == kMpMixed) {   // the offset vector without its nibble term: none yet (the first refresh follows launch 1)
+        if (h->nib_period > 0 && h->Mp_mode == kMpMixed) {   // the offset vector without its nibble term: none yet (the first refresh is that of launch 0, committed before x_0 is formed)
             if (!h->xb_corr.p) LPVS_TRY(h->xb_corr.alloc(v));
             if (!h->nib_rhs.p) LPVS_TRY(h->nib_rhs.alloc(v));
             if (!h->nib_acc.p) LPVS_TRY(h->nib_acc.alloc(v));
@@ -2012,7 +2012,8 @@ int32_t windows_engine(const WinJob &a, Sink sink) {
                 const size_t types_bytes = ((nt * (size_t)bw + 255) / 256) * 256;
                 if (mixed && ns == 1 && 6 * symv_packed_doubles(np) * (size_t)bw + types_bytes + 8 * (size_t)bw <= Mp.bytes) {
                     LPVS_TRY(launch_pack_tiles_mixed_batch(M.as<double>(), np, nb_, Mp.as<unsigned char>(), types,
-                                                           reinterpret_cast<unsigned long long *>(types + types_bytes), s));
+                                                           reinterpret_cast<unsigned long long *>(types + types_bytes), s,
+                                                           /*diag_float=*/false, /*abs_part=*/nullptr, /*n_valid=*/nreg));
                     ab.mp_types = types;
                 } else
                 LPVS_TRY(launch_pack_tiles_split_batch(M.as<double>(), np, nb_, Mp.as<unsigned char>(), s));

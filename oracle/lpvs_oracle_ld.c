@@ -142,3 +142,61 @@ int64_t lpvo_admm_gram_ld(const double *G, int64_t n, const double *b, const dou
     free(L); free(Lt); free(x); free(z); free(u); free(t);
     return it;
 }
+
+/* (G + I/mu)^-1 in extended precision, rounded to double once -> Minv_out [n][n]; b != NULL: xb = (G + I/mu)^-1 b, solved in extended
+ * precision, as the double pair xb_hi + xb_lo (xb_lo may be NULL).  Returns 0, or < 0. */
+int64_t lpvo_inverse_ld(const double *G, int64_t n, double mu, double *Minv_out, const double *b, double *xb_hi, double *xb_lo) {
+    if (!(mu > 0) || n < 1) return -2;
+    ld *L = (ld *)malloc(sizeof(ld) * n * n), *Lt = (ld *)malloc(sizeof(ld) * n * n), *t = (ld *)calloc(n, sizeof(ld));
+    if (!L || !Lt || !t) { free(L); free(Lt); free(t); return -4; }
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t k = 0; k < n; ++k) L[i * n + k] = k <= i ? (ld)G[i * n + k] + (i == k ? (ld)1 / (ld)mu : (ld)0) : (ld)0;
+    if (chol_lower_ld(L, n, 0)) { free(L); free(Lt); free(t); return -3; }
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t k = 0; k < n; ++k) Lt[i * n + k] = k >= i ? L[k * n + i] : (ld)0;
+    for (int64_t j = 0; j < n; ++j) {
+        for (int64_t k = 0; k < n; ++k) t[k] = k == j ? (ld)1 : (ld)0;
+        chol_solve_ld(L, Lt, n, t);
+        for (int64_t k = 0; k < n; ++k) Minv_out[k * n + j] = (double)t[k];
+    }
+    if (b && xb_hi) {
+        for (int64_t k = 0; k < n; ++k) t[k] = (ld)b[k];
+        chol_solve_ld(L, Lt, n, t);
+        for (int64_t k = 0; k < n; ++k) { xb_hi[k] = (double)t[k]; if (xb_lo) xb_lo[k] = (double)(t[k] - (ld)xb_hi[k]); }
+    }
+    free(L); free(Lt); free(t);
+    return 0;
+}
+
+/* The ADMM of lpvo_admm_gram_ld with the x-update in the offset form a device handle runs: x = xb + Mt ((z - u) / mu) for a GIVEN
+ * matrix Mt [n][n] (a reduced-precision copy of the inverse, as doubles) and offset vector xb = xb_hi + xb_lo (xb_lo may be NULL);
+ * every product, sum and prox in extended precision.  Same start, snapshots and return value as lpvo_admm_gram_ld. */
+int64_t lpvo_admm_minv_ld(const double *Mt, int64_t n, const double *xb_hi, const double *xb_lo, const double *x0, int prox_kind, double prox_param,
+                          int64_t glen, double mu, const int64_t *snaps, int64_t nsnap, double *x_out, double *z_out, double *u_out) {
+    if (!(mu > 0 && mu <= 1) || nsnap < 1) return -2;
+    ld *x = (ld *)calloc(n, sizeof(ld)), *z = (ld *)calloc(n, sizeof(ld)), *u = (ld *)calloc(n, sizeof(ld)), *t = (ld *)calloc(n, sizeof(ld));
+    if (!x || !z || !u || !t) { free(x); free(z); free(u); free(t); return -4; }
+    if (x0) for (int64_t k = 0; k < n; ++k) x[k] = z[k] = x0[k];
+    int64_t it = 0, snap = 0;
+    const int64_t iters = snaps[nsnap - 1];
+    for (int64_t i = 1; i <= iters; ++i) {
+        for (int64_t k = 0; k < n; ++k) t[k] = (z[k] - u[k]) / (ld)mu;
+#pragma omp parallel for schedule(static)
+        for (int64_t r = 0; r < n; ++r) {
+            ld s = 0;
+            const double *row = Mt + r * n;
+            for (int64_t k = 0; k < n; ++k) s += (ld)row[k] * t[k];
+            x[r] = ((ld)xb_hi[r] + (xb_lo ? (ld)xb_lo[r] : (ld)0)) + s;
+        }
+        for (int64_t k = 0; k < n; ++k) t[k] = x[k] + u[k];
+        prox_ld(prox_kind, z, t, n, prox_param, glen, mu);
+        for (int64_t k = 0; k < n; ++k) u[k] += x[k] - z[k];
+        it = i;
+        while (snap < nsnap && snaps[snap] == i) {
+            for (int64_t k = 0; k < n; ++k) { x_out[snap * n + k] = (double)x[k]; z_out[snap * n + k] = (double)z[k]; u_out[snap * n + k] = (double)u[k]; }
+            ++snap;
+        }
+    }
+    free(x); free(z); free(u); free(t);
+    return it;
+}

@@ -259,20 +259,63 @@ _LIB_LD = None
 def admm_gram_ld(G, b, proxg, snaps, x0=None, mu=0.05, verbose=False):
     """lpvs_oracle_ld.c: admm_gram carried in x87 extended precision (64-bit mantissa) -- the adjudicator between two f64
     paths.  Returns {iteration count: (x, z, u)} for the ascending counts in `snaps` (tol = 0: no stopping test)."""
-    global _LIB_LD
-    if _LIB_LD is None:
-        _LIB_LD = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "liblpvs_oracle_ld.so"))
-        _LIB_LD.lpvo_admm_gram_ld.restype = C.c_int64
-        assert _LIB_LD.lpvo_ld_mantissa_bits() == 64, "long double is not the x87 extended format on this host"
     G = np.asfortranarray(G, dtype=np.float64)
     b = _f64(b)
     n = len(b)
     snaps = np.ascontiguousarray(sorted(int(s) for s in snaps), dtype=np.int64)
     xs, zs, us = (np.zeros((len(snaps), n)) for _ in range(3))
     x0a = _f64(x0) if x0 is not None else None
-    it = _LIB_LD.lpvo_admm_gram_ld(_p(G), C.c_int64(n), _p(b), _p(x0a) if x0a is not None else None, C.c_int(proxg.kind),
+    it = _lib_ld().lpvo_admm_gram_ld(_p(G), C.c_int64(n), _p(b), _p(x0a) if x0a is not None else None, C.c_int(proxg.kind),
                                    C.c_double(proxg.param), C.c_int64(proxg.glen), C.c_double(mu), _p(snaps), C.c_int64(len(snaps)),
                                    _p(xs), _p(zs), _p(us), C.c_int(1 if verbose else 0))
+    assert it == snaps[-1], it
+    return {int(s): (xs[k], zs[k], us[k]) for k, s in enumerate(snaps)}
+
+
+def _lib_ld():
+    global _LIB_LD
+    if _LIB_LD is None:
+        so = os.path.join(_HERE, "liblpvs_oracle_ld.so")
+        src = os.path.join(_HERE, "lpvs_oracle_ld.c")
+        if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
+            subprocess.check_call(["make", "-s", "-C", _HERE, "liblpvs_oracle_ld.so"])
+        _LIB_LD = C.CDLL(so)
+        for fn in ("lpvo_admm_gram_ld", "lpvo_admm_minv_ld", "lpvo_inverse_ld"):
+            getattr(_LIB_LD, fn).restype = C.c_int64
+        assert _LIB_LD.lpvo_ld_mantissa_bits() == 64, "long double is not the x87 extended format on this host"
+    return _LIB_LD
+
+
+def inverse_ld(G, mu, b=None):
+    """(G + I/mu)^-1 from an extended-precision Cholesky factor, rounded to double once (row-major n x n); with `b` also
+    xb = (G + I/mu)^-1 b solved in extended precision, as a pair of doubles (hi, lo)."""
+    G = np.ascontiguousarray(G, dtype=np.float64)
+    n = G.shape[0]
+    M = np.zeros((n, n))
+    if b is None:
+        assert _lib_ld().lpvo_inverse_ld(_p(G), C.c_int64(n), C.c_double(mu), _p(M), None, None, None) == 0
+        return M
+    b = _f64(b)
+    hi, lo = np.zeros(n), np.zeros(n)
+    assert _lib_ld().lpvo_inverse_ld(_p(G), C.c_int64(n), C.c_double(mu), _p(M), _p(b), _p(hi), _p(lo)) == 0
+    return M, hi, lo
+
+
+def admm_minv_ld(Mt, xb, proxg, snaps, xb_lo=None, x0=None, mu=0.05):
+    """lpvs_oracle_ld.c: the ADMM of admm_gram_ld with x = xb + Mt (z - u)/mu for a GIVEN matrix Mt (row-major doubles: a packed
+    copy of the inverse as a device handle streams it) and offset vector xb (+ xb_lo), everything else in extended precision --
+    the exact model of a handle's iterates.  Returns {iteration count: (x, z, u)}."""
+    Mt = np.ascontiguousarray(Mt, dtype=np.float64)
+    xb = _f64(xb)
+    n = len(xb)
+    assert Mt.shape == (n, n)
+    lo = _f64(xb_lo) if xb_lo is not None else None
+    snaps = np.ascontiguousarray(sorted(int(s) for s in snaps), dtype=np.int64)
+    xs, zs, us = (np.zeros((len(snaps), n)) for _ in range(3))
+    x0a = _f64(x0) if x0 is not None else None
+    it = _lib_ld().lpvo_admm_minv_ld(_p(Mt), C.c_int64(n), _p(xb), _p(lo) if lo is not None else None, _p(x0a) if x0a is not None else None,
+                                     C.c_int(proxg.kind), C.c_double(proxg.param), C.c_int64(proxg.glen), C.c_double(mu), _p(snaps),
+                                     C.c_int64(len(snaps)), _p(xs), _p(zs), _p(us))
     assert it == snaps[-1], it
     return {int(s): (xs[k], zs[k], us[k]) for k, s in enumerate(snaps)}
 
