@@ -371,11 +371,11 @@ admm_prox_kernel(AdmmParams p) {
 
     const bool offset_form = p.xb != nullptr;   // x = xb + M (z-u)/mu: the right-hand side carries no b
     auto finish = [&](int64_t i, double xi, double ui, double bi, double zi) {
-        const double d = xi - zi;              // tmp = x - z            src/lasso.jl:154
-        const double un = ui + d;              // u += tmp               src/lasso.jl:155
-        Z[i] = zi; U[i] = un;
-        R[i] = offset_form ? (zi - un) / mu : bi + (zi - un) / mu;   // next x-update: b + (z-u)/mu
-        ss = fma(d, d, ss);
+        Z[i] = zi;                             // (ahead of the division: with the stores behind it this kernel spills two SGPRs)
+        const DualStep t = dual_step(xi, ui, zi, bi, mu, true, offset_form);
+        U[i] = t.un;
+        R[i] = t.rhs;                          // next x-update: b + (z-u)/mu
+        ss = fma(t.d, t.d, ss);
     };
 
     const int kind = p.prox_kind;
@@ -421,9 +421,7 @@ admm_prox_kernel(AdmmParams p) {
             for (int64_t g = threadIdx.x; g < gcount; g += 1024) {
                 double s2 = 0;
                 for (int64_t q = 0; q < gl; ++q) s2 += sq[g * gl + q];   // sequential, as norm() on a short slice
-                double scale = 1.0 - lm / sqrt(s2);                    // s2 == 0 -> -inf -> 0
-                if (!(scale > 0)) scale = 0.0;
-                gscale[g] = scale;
+                gscale[g] = group_scale(s2, lm);
             }
             __syncthreads();
 #pragma unroll
@@ -451,8 +449,8 @@ admm_prox_kernel(AdmmParams p) {
                     if (i >= n) continue;
                     const double v = xv[k] + uv[k];
                     double zi;
-                    if (kind == LPVS_PROX_L1) zi = v + (v <= -thr_l1 ? thr_l1 : (v >= thr_l1 ? -thr_l1 : -v));
-                    else if (kind == LPVS_PROX_L0) zi = fabs(v) > thr_l0 ? v : 0.0;
+                    if (kind == LPVS_PROX_L1) zi = prox_l1(v, thr_l1);
+                    else if (kind == LPVS_PROX_L0) zi = prox_l0(v, thr_l0);
                     else zi = ball_r >= n ? v : 0.0;
                     finish(i, xv[k], uv[k], bv[k], zi);
                 }
@@ -500,12 +498,7 @@ admm_prox_kernel(AdmmParams p) {
     }
 
     const double tot = block_sum_1024(ss, sh);
-    if (threadIdx.x == 0) {
-        const double nxz = sqrt(tot);          // norm(tmp)               src/lasso.jl:157
-        status->iters += 1;
-        status->nxz = nxz;
-        if (nxz < p.tol) status->converged = 1;  //                      src/lasso.jl:164
-    }
+    if (threadIdx.x == 0) commit_iteration(status, sqrt(tot), p.tol);   // norm(tmp)   src/lasso.jl:157
 }
 
 template <typename T> struct Pair;
@@ -1128,34 +1121,8 @@ admm_fused_update_kernel(AdmmParams p, const double *__restrict__ part1_all, con
     const double ui = ok ? p.u[gi] : 0.0, bi = ok ? (offset_form ? p.xb[gi] : p.b[gi]) : 0.0;   // in flight together with the partials
     double xi = gather_x4(part1, part2, nblk, I, sh);
     if (offset_form) xi += bi;                                   // (bi holds xb here)
-    const double v = xi + ui;
-    double zi = 0.0, d2 = 0.0;
-    if (p.prox_kind == LPVS_PROX_L1) {
-        const double gl = p.mu * p.prox_param;
-        zi = v + (v <= -gl ? gl : (v >= gl ? -gl : -v));
-    } else if (p.prox_kind == LPVS_PROX_L0) {
-        zi = fabs(v) > sqrt(2.0 * p.mu * p.prox_param) ? v : 0.0;
-    } else {  // group: block soft-threshold, norms through LDS
-        const int gl = (int)p.group_len;
-        if (row) sq[i] = v * v;
-        __syncthreads();
-        if (threadIdx.x < TS / gl) {
-            double s2 = 0;
-            for (int q = 0; q < gl; ++q) s2 += sq[threadIdx.x * gl + q];   // sequential, as norm() on the slice
-            double scale = 1.0 - p.prox_param * p.mu / sqrt(s2);           // s2 == 0 -> -inf -> 0
-            if (!(scale > 0)) scale = 0.0;
-            gs[threadIdx.x] = scale;
-        }
-        __syncthreads();
-        if (row) zi = gs[i / gl] * v;
-    }
-    if (row) {
-        if (!ok) zi = 0.0;
-        const double d = xi - zi, un = ui + d;     // src/lasso.jl:154-155
-        p.x[gi] = xi; p.z[gi] = zi; p.u[gi] = un;
-        p.rhs[gi] = ok ? (offset_form ? (zi - un) / p.mu : bi + (zi - un) / p.mu) : 0.0;
-        d2 = ok ? d * d : 0.0;
-    }
+    const double zi = block_prox(p, xi + ui, row, i, sq, gs);
+    const double d2 = row ? row_update(p, gi, xi, ui, bi, zi, ok, offset_form) : 0.0;
     // block sum of d2: the two row waves reduce by shuffles (fixed pattern -> reproducible)
     const double wsum = wave_sum(d2);
     __syncthreads();
@@ -1172,18 +1139,13 @@ admm_fused_update_kernel(AdmmParams p, const double *__restrict__ part1_all, con
     if (last) {  // every other workgroup has published its block norm
         if (threadIdx.x == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         __syncthreads();
-        if (threadIdx.x < 64) {   // lane q sums blocks q, q+64, ...; then the wave's fixed shuffle pattern
-            double part = 0;
-            for (int q = threadIdx.x; q < nblk; q += 64) part += __hip_atomic_load(&blocknorm[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const double w = wave_sum(part);
+        if (threadIdx.x < 64) {
+            const double w = block_norm_sum(blocknorm, nblk, /*agent_loads=*/true);
             if (threadIdx.x == 0) sq[0] = w;
         }
         __syncthreads();
         if (threadIdx.x == 0) {
-            const double nxz = sqrt(sq[0]);                               // norm(tmp)   src/lasso.jl:157
-            status->iters += 1;
-            status->nxz = nxz;
-            if (nxz < p.tol) status->converged = 1;                       //             src/lasso.jl:164
+            commit_iteration(status, sqrt(sq[0]), p.tol);                 // norm(tmp)   src/lasso.jl:157
             __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
@@ -1253,22 +1215,14 @@ admm_fused_update2_kernel(AdmmParams p, const double *__restrict__ part1_all, co
 #pragma unroll
     for (int q = 0; q < 16; ++q) pre[q] = e0 + q < e1 ? pre[q] : 0.0;
     if (commit_prev) {                                               // uniform (host-known): commit the previous iteration
-        if (threadIdx.x < 64) {   // lane q sums blocks q, q+64, ...; then the wave's fixed shuffle pattern (as pending_norm)
-            double part = 0;
-            part += lane64 < nblk ? bn_raw : 0.0;
-            for (int q = lane64 + 64; q < nblk; q += 64) part += bn_prev[q];
-            const double w = wave_sum(part);
+        if (threadIdx.x < 64) {   // (as pending_norm, the lane's first block norm preloaded)
+            const double w = block_norm_sum(bn_prev, nblk, false, &bn_raw);
             if (threadIdx.x == 0) slot = w;
         }
         __syncthreads();
         const double nxz = sqrt(slot);                               // norm(tmp)   src/lasso.jl:157
-        const bool conv = nxz < p.tol;                               //             src/lasso.jl:164
-        if (I == 0 && threadIdx.x == 0) {
-            status->iters += 1;
-            status->nxz = nxz;
-            if (conv) status->converged = 1;
-        }
-        if (conv) return;                                            // every workgroup takes the same decision
+        if (I == 0 && threadIdx.x == 0) commit_iteration(status, nxz, p.tol);
+        if (nxz < p.tol) return;                                     // every workgroup takes the same decision     src/lasso.jl:164
     }
     double xi;
     {   // same summation order as gather_x4: the quarter's contributions in order, then the four quarters in order
@@ -1289,34 +1243,8 @@ admm_fused_update2_kernel(AdmmParams p, const double *__restrict__ part1_all, co
         xi = gq == 0 ? ((sacc + sh[i]) + sh[TS + i]) + sh[2 * TS + i] : 0.0;
     }
     if (offset_form) xi += bi;                                       // (bi holds xb here)
-    const double v = xi + ui;
-    double zi = 0.0, d2 = 0.0;
-    if (p.prox_kind == LPVS_PROX_L1) {
-        const double gl = p.mu * p.prox_param;
-        zi = v + (v <= -gl ? gl : (v >= gl ? -gl : -v));
-    } else if (p.prox_kind == LPVS_PROX_L0) {
-        zi = fabs(v) > sqrt(2.0 * p.mu * p.prox_param) ? v : 0.0;
-    } else {  // group: block soft-threshold, norms through LDS
-        const int gl = (int)p.group_len;
-        if (row) sq[i] = v * v;
-        __syncthreads();
-        if (threadIdx.x < TS / gl) {
-            double s2 = 0;
-            for (int q = 0; q < gl; ++q) s2 += sq[threadIdx.x * gl + q];   // sequential, as norm() on the slice
-            double scale = 1.0 - p.prox_param * p.mu / sqrt(s2);           // s2 == 0 -> -inf -> 0
-            if (!(scale > 0)) scale = 0.0;
-            gs[threadIdx.x] = scale;
-        }
-        __syncthreads();
-        if (row) zi = gs[i / gl] * v;
-    }
-    if (row) {
-        if (!ok) zi = 0.0;
-        const double d = xi - zi, un = ui + d;     // src/lasso.jl:154-155
-        p.x[gi] = xi; p.z[gi] = zi; p.u[gi] = un;
-        p.rhs[gi] = ok ? (offset_form ? (zi - un) / p.mu : bi + (zi - un) / p.mu) : 0.0;
-        d2 = ok ? d * d : 0.0;
-    }
+    const double zi = block_prox(p, xi + ui, row, i, sq, gs);
+    const double d2 = row ? row_update(p, gi, xi, ui, bi, zi, ok, offset_form) : 0.0;
     const double wsum = wave_sum(d2);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = wsum;
@@ -1332,11 +1260,7 @@ admm_commit_kernel(AdmmParams p, int nblk, double *__restrict__ blocknorm_all, i
     if (status->converged) return;   // otherwise the chunk's last iteration is pending (the host launches this only after >= 1 iteration)
     __shared__ double slot;
     const double nxz = pending_norm(blocknorm_all + ((int64_t)sg * 2 + parity_last) * nblk, nblk, &slot);
-    if (threadIdx.x == 0) {
-        status->iters += 1;
-        status->nxz = nxz;
-        if (nxz < p.tol) status->converged = 1;
-    }
+    if (threadIdx.x == 0) commit_iteration(status, nxz, p.tol);
 }
 
 // Small systems of a batch (np <= 1024, e.g. the windows of ls_windowpsd): ONE workgroup per problem does what
@@ -1362,41 +1286,14 @@ admm_window_update_kernel(AdmmParams p, const double *__restrict__ part1_all, co
     for (int e = 1; e < 8; ++e) xi += a[e];                    // fixed order: tile column 0, 1, ...
     const bool offset_form = p.xb != nullptr;                  // x = xb + M~ (z-u)/mu (reduced-precision copy of M, see the split kernel)
     if (offset_form) xi += ok ? p.xb[gi] : 0.0;
-    const double v = xi + ui;
-    double zi = 0.0;
-    if (p.prox_kind == LPVS_PROX_L1) {
-        const double gl = p.mu * p.prox_param;
-        zi = v + (v <= -gl ? gl : (v >= gl ? -gl : -v));
-    } else if (p.prox_kind == LPVS_PROX_L0) {
-        zi = fabs(v) > sqrt(2.0 * p.mu * p.prox_param) ? v : 0.0;
-    } else {  // group: block soft-threshold, norms through LDS (128 % group_len == 0)
-        const int gl = (int)p.group_len;
-        sq[threadIdx.x] = v * v;
-        __syncthreads();
-        if (i < TS / gl) {
-            double s2 = 0;
-            for (int q = 0; q < gl; ++q) s2 += sq[I * TS + i * gl + q];
-            double scale = 1.0 - p.prox_param * p.mu / sqrt(s2);
-            if (!(scale > 0)) scale = 0.0;
-            gs[I * TS + i] = scale;
-        }
-        __syncthreads();
-        zi = gs[I * TS + i / gl] * v;
-    }
-    if (!ok) zi = 0.0;
-    const double d = xi - zi, un = ui + d;                       // src/lasso.jl:154-155
-    p.x[gi] = xi; p.z[gi] = zi; p.u[gi] = un;
-    p.rhs[gi] = ok ? (offset_form ? (zi - un) / p.mu : bi + (zi - un) / p.mu) : 0.0;
-    const double w = wave_sum(ok ? d * d : 0.0);
+    const double zi = block_prox(p, xi + ui, true, i, sq + I * TS, gs + I * TS);   // (every thread holds a row; its row block's slices)
+    const double w = wave_sum(row_update(p, gi, xi, ui, bi, zi, ok, offset_form));
     if ((threadIdx.x & 63) == 0) wsum_s[threadIdx.x >> 6] = w;
     __syncthreads();
     if (threadIdx.x == 0) {
         double tot = 0;
         for (int q = 0; q < 2 * nblk; ++q) tot += wsum_s[q];     // wave order = row order
-        const double nxz = sqrt(tot);                            // norm(tmp)   src/lasso.jl:157
-        status->iters += 1;
-        status->nxz = nxz;
-        if (nxz < p.tol) status->converged = 1;                  //             src/lasso.jl:164
+        commit_iteration(status, sqrt(tot), p.tol);              // norm(tmp)   src/lasso.jl:157
     }
 }
 
@@ -1450,10 +1347,11 @@ admm_batch_prox_kernel(AdmmBatch p) {
     double *__restrict__ R = p.rhs + o;
     double ss = 0;
     auto finish = [&](int64_t i, double xi, double ui, double zi) {
-        const double d = xi - zi, un = ui + d;
-        Z[i] = zi; U[i] = un;
-        R[i] = B[i] + (zi - un) / mu;
-        ss = fma(d, d, ss);
+        Z[i] = zi;
+        const DualStep t = dual_step(xi, ui, zi, B[i], mu, true, false);
+        U[i] = t.un;
+        R[i] = t.rhs;
+        ss = fma(t.d, t.d, ss);
     };
     if (p.prox_kind == LPVS_PROX_GROUP_L2) {
         const int64_t gl = p.group_len, ng = n / gl;
@@ -1461,8 +1359,7 @@ admm_batch_prox_kernel(AdmmBatch p) {
         for (int64_t g = threadIdx.x; g < ng; g += 256) {
             double s2 = 0;
             for (int64_t k = 0; k < gl; ++k) { const double v = X[g * gl + k] + U[g * gl + k]; s2 += v * v; }
-            double scale = 1.0 - lm / sqrt(s2);
-            if (!(scale > 0)) scale = 0.0;
+            const double scale = group_scale(s2, lm);
             for (int64_t k = 0; k < gl; ++k) {
                 const int64_t i = g * gl + k;
                 const double xi = X[i], ui = U[i];
@@ -1474,7 +1371,7 @@ admm_batch_prox_kernel(AdmmBatch p) {
         const double gl1 = mu * p.prox_param, th0 = sqrt(2.0 * mu * p.prox_param);
         for (int64_t i = threadIdx.x; i < n; i += 256) {
             const double xi = X[i], ui = U[i], v = xi + ui;
-            const double zi = p.prox_kind == LPVS_PROX_L1 ? v + (v <= -gl1 ? gl1 : (v >= gl1 ? -gl1 : -v)) : (fabs(v) > th0 ? v : 0.0);
+            const double zi = p.prox_kind == LPVS_PROX_L1 ? prox_l1(v, gl1) : prox_l0(v, th0);
             finish(i, xi, ui, zi);
         }
     }
@@ -1482,10 +1379,7 @@ admm_batch_prox_kernel(AdmmBatch p) {
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = w;
     __syncthreads();
     if (threadIdx.x == 0) {
-        const double nxz = sqrt(((sh[0] + sh[1]) + sh[2]) + sh[3]);
-        p.status[q].iters += 1;
-        p.status[q].nxz = nxz;
-        if (nxz < p.tol) p.status[q].converged = 1;
+        commit_iteration(p.status + q, sqrt(((sh[0] + sh[1]) + sh[2]) + sh[3]), p.tol);
     }
 }
 
@@ -1607,9 +1501,6 @@ int32_t launch_admm_restate(const AdmmParams &p, int64_t iters, hipStream_t s) {
 }
 
 bool admm_batch_uses_tiles(const AdmmBatch &p) {
-    AdmmParams q{p.M, p.np, p.n, p.b, p.x, p.z, p.u, p.rhs, p.mu, p.tol, p.prox_kind, p.prox_param, p.group_len, p.status,
-                 nullptr, p.part, p.Mp, p.nbatch};
-    (void)q;
     return p.Mp != nullptr && p.part != nullptr;          // (launch_admm_batch_iterations' own test: non-fusable prox operators ride the tiles too)
 }
 

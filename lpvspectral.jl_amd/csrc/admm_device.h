@@ -285,48 +285,79 @@ __device__ __forceinline__ void split_tile_product(const SplitRaw &w, const doub
         }
         v[rg] = a0 + a1;
     }
-    // row sums: halving butterfly over the 16 column lanes (after the step with mask m a lane keeps the row groups whose
-    // bit matches its own), then the last pair
-#pragma unroll
-    for (int m = 8, cnt = 4; m >= 2; m >>= 1, cnt >>= 1) {
-        const bool up = (c & m) != 0;
-#pragma unroll
-        for (int k = 0; k < cnt; ++k) {
-            const double lo_ = opaque(v[k]), hi_ = opaque(v[k + cnt]);
-            v[k] = (up ? hi_ : lo_) + __shfl_xor(up ? lo_ : hi_, m, 64);
-        }
+    tile_reduce_store(v, tc, sT, offdiag, part1, part2);
+}
+
+// ---- the second half of the ADMM step, shared by every update kernel -----------------------------------------------
+// z = prox(x + u), u += x - z, rhs = [b +] (z - u)/mu, ||x - z||, commit.  The kernels keep their own thread layouts, their staging of
+// the group norms and their order of summing ||x - z||^2 (all part of the tested bits); the arithmetic is here, once.
+__device__ __forceinline__ double prox_l1(double v, double t) { return v + (v <= -t ? t : (v >= t ? -t : -v)); }   // soft threshold, t = mu * lambda
+__device__ __forceinline__ double prox_l0(double v, double t) { return fabs(v) > t ? v : 0.0; }                    // t = sqrt(2 mu lambda); the tie gives 0
+__device__ __forceinline__ double group_scale(double s2, double lm) {   // block soft threshold of a group with sum of squares s2, lm = lambda * mu
+    const double scale = 1.0 - lm / sqrt(s2);                           // s2 == 0 -> -inf -> 0
+    return scale > 0 ? scale : 0.0;
+}
+
+// u += x - z and the next right-hand side b + (z - u)/mu (offset form: (z - u)/mu alone; rows past n: 0)     src/lasso.jl:154-155
+struct DualStep { double d, un, rhs; };
+__device__ __forceinline__ DualStep dual_step(double xi, double ui, double zi, double bi, double mu, bool ok, bool offset_form) {
+    const double d = xi - zi, un = ui + d;
+    return {d, un, ok ? (offset_form ? (zi - un) / mu : bi + (zi - un) / mu) : 0.0};
+}
+
+// the prox of one 128-row block held one element per thread (`row`: this thread holds element i of the block; sq / gs: TS doubles of
+// LDS each).  Element-wise for L1 / L0; for groups (128 % group_len == 0) the squares go through LDS and one lane per group sums them
+// sequentially, as norm() on the slice.  Every thread of the workgroup calls it (two barriers in the group branch).
+__device__ __forceinline__ double block_prox(const AdmmParams &p, double v, bool row, int i, double *sq, double *gs) {
+    if (p.prox_kind == LPVS_PROX_L1) return prox_l1(v, p.mu * p.prox_param);
+    if (p.prox_kind == LPVS_PROX_L0) return prox_l0(v, sqrt(2.0 * p.mu * p.prox_param));
+    const int gl = (int)p.group_len;
+    if (row) sq[i] = v * v;
+    __syncthreads();
+    if (row & (i < TS / gl)) {                              // one lane per group (a single branch)
+        double s2 = 0;
+        for (int q = 0; q < gl; ++q) s2 += sq[i * gl + q];
+        gs[i] = group_scale(s2, p.prox_param * p.mu);
     }
-    v[0] += __shfl_xor(v[0], 1, 64);
-    if ((c & 1) == 0) {
-        const int rg = ((c & 8) ? 4 : 0) + ((c & 4) ? 2 : 0) + ((c & 2) ? 1 : 0);
-        part1[wave * 32 + 4 * rg + g] = v[0];
-    }
-    if (offdiag) {
-        // column sums: over the wave's four row lanes g (masks 32, 16), then over the four waves through LDS
-#pragma unroll
-        for (int m = 32, cnt = 4; m >= 16; m >>= 1, cnt >>= 1) {
-            const bool up = (lane & m) != 0;
-#pragma unroll
-            for (int k = 0; k < cnt; ++k) {
-                const double lo_ = opaque(tc[k]), hi_ = opaque(tc[k + cnt]);
-                tc[k] = (up ? hi_ : lo_) + __shfl_xor(up ? lo_ : hi_, m, 64);
-            }
-        }
-        const int col = ((lane & 32) ? 64 : 0) + 4 * c + ((lane & 16) ? 2 : 0);
-        sT[wave][col] = tc[0]; sT[wave][col + 1] = tc[1];
-        __syncthreads();
-        if (threadIdx.x < TS)
-            part2[threadIdx.x] = ((sT[0][threadIdx.x] + sT[1][threadIdx.x]) + sT[2][threadIdx.x]) + sT[3][threadIdx.x];
-    }
+    __syncthreads();
+    return row ? gs[i / gl] * v : 0.0;
+}
+
+// the row tail of the block kernels: dual step, the four stores of row gi, and the row's (x - z)^2 (0 past n)
+__device__ __forceinline__ double row_update(const AdmmParams &p, int64_t gi, double xi, double ui, double bi, double zi, bool ok, bool offset_form) {
+    if (!ok) zi = 0.0;
+    p.x[gi] = xi; p.z[gi] = zi;
+    const DualStep s = dual_step(xi, ui, zi, bi, p.mu, ok, offset_form);
+    p.u[gi] = s.un;
+    p.rhs[gi] = s.rhs;
+    return ok ? s.d * s.d : 0.0;
+}
+
+// the one thread that keeps a problem's status commits an iteration; returns whether it stopped     src/lasso.jl:157,164
+__device__ __forceinline__ bool commit_iteration(AdmmStatus *status, double nxz, double tol) {
+    status->iters += 1;
+    status->nxz = nxz;
+    const bool conv = nxz < tol;
+    if (conv) status->converged = 1;
+    return conv;
+}
+
+// sum of the block norms bn[0 .. nblk) over the 64 lanes of wave 0: lane q sums blocks q, q + 64, ...; then the wave's fixed shuffle
+// pattern.  `first`: the lane's bn[q] (anything for q >= nblk) if the caller has loaded it already; `agent_loads`: atomic loads at
+// agent scope (block norms published by other workgroups of the SAME launch).
+__device__ __forceinline__ double block_norm_sum(const double *__restrict__ bn, int nblk, bool agent_loads = false, const double *first = nullptr) {
+    int q = threadIdx.x;
+    double part = 0;
+    if (first != nullptr) { part += q < nblk ? *first : 0.0; q += 64; }
+    for (; q < nblk; q += 64) part += agent_loads ? __hip_atomic_load(&bn[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : bn[q];
+    return wave_sum(part);
 }
 
 // ||x - z|| of the iteration whose block norms are in bn[0 .. nblk): every caller (the deferred commit of the two-launch update, the commit kernels of the
 // one-launch iteration) sums them in the SAME fixed order, so that all workgroups take the same stopping decision (src/lasso.jl:157,164)
 __device__ __forceinline__ double pending_norm(const double *__restrict__ bn, int nblk, double *slot) {
-    if (threadIdx.x < 64) {   // lane q sums blocks q, q+64, ...; then the wave's fixed shuffle pattern
-        double part = 0;
-        for (int q = threadIdx.x; q < nblk; q += 64) part += bn[q];
-        const double w = wave_sum(part);
+    if (threadIdx.x < 64) {
+        const double w = block_norm_sum(bn, nblk);
         if (threadIdx.x == 0) *slot = w;
     }
     __syncthreads();

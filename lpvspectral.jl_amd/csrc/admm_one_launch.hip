@@ -336,11 +336,7 @@ fi_one_tile_body(const AdmmParams &p, const unsigned char *__restrict__ Mp, cons
         for (int k = 0; k < NK; ++k) part += lane + 64 * k < nblk ? bnv[k] : 0.0;
         const double nxz = sqrt(wave_sum(part));                       // every wave, identically     norm(tmp)   src/lasso.jl:157
         const bool conv = nxz < p.tol;                                 //                             src/lasso.jl:164
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
-            status->iters += 1;
-            status->nxz = nxz;
-            if (conv) status->converged = 1;
-        }
+        if (blockIdx.x == 0 && threadIdx.x == 0) commit_iteration(status, nxz, p.tol);
         if (conv) return;                                              // every workgroup takes the same decision
     }
     // ---- update u_{g-1} for this thread's element (threads < 128: block I, the others: block J)
@@ -352,10 +348,9 @@ fi_one_tile_body(const AdmmParams &p, const unsigned char *__restrict__ Mp, cons
         const double v = xi + ui;
         double zi = 0.0;
         if (p.prox_kind == LPVS_PROX_L1) {
-            const double gl = p.mu * p.prox_param;
-            zi = v + (v <= -gl ? gl : (v >= gl ? -gl : -v));
+            zi = prox_l1(v, p.mu * p.prox_param);
         } else if (p.prox_kind == LPVS_PROX_L0) {
-            zi = fabs(v) > sqrt(2.0 * p.mu * p.prox_param) ? v : 0.0;
+            zi = prox_l0(v, sqrt(2.0 * p.mu * p.prox_param));
         } else {  // group: block soft-threshold, norms through LDS (as admm_fused_update2_kernel)
             // every lane sums its own group (LDS broadcast reads, the same sequential order as norm() on the slice): one barrier
             // instead of two, no lanes idling behind eight of them
@@ -365,13 +360,12 @@ fi_one_tile_body(const AdmmParams &p, const unsigned char *__restrict__ Mp, cons
             const double *grp = sq + (threadIdx.x & TS) + (i / gl) * gl;
             double s2 = 0;
             for (int q = 0; q < gl; ++q) s2 += grp[q];
-            double scale = 1.0 - p.prox_param * p.mu / sqrt(s2);                          // s2 == 0 -> -inf -> 0
-            if (!(scale > 0)) scale = 0.0;
-            zi = scale * v;
+            zi = group_scale(s2, p.prox_param * p.mu) * v;
         }
         if (!ok) zi = 0.0;
-        const double d = xi - zi, un = ui + d;                         // src/lasso.jl:154-155
-        rhs_v = ok ? (zi - un) / p.mu : 0.0;
+        const DualStep t = dual_step(xi, ui, zi, 0.0, p.mu, ok, /*offset_form=*/true);
+        const double d = t.d, un = t.un;
+        rhs_v = t.rhs;
         if (I == J) {                                                  // the block's owner (uniform): state, norm, maxima, next accumulator
             const bool own = threadIdx.x < TS;
             if (own) {
@@ -624,11 +618,7 @@ fi_commit_kernel(AdmmParams p, int nblk, int par) {
     const FiBufs f = fi_views(p.fi, (int64_t)nprob * p.np, nprob * nblk, nprob);
     __shared__ double slot;
     const double nxz = pending_norm(f.bn + (int64_t)par * nprob * nblk + (int64_t)sg * nblk, nblk, &slot);
-    if (threadIdx.x == 0) {
-        status->iters += 1;
-        status->nxz = nxz;
-        if (nxz < p.tol) status->converged = 1;
-    }
+    if (threadIdx.x == 0) commit_iteration(status, nxz, p.tol);
 }
 
 int32_t fi_read_consts(const AdmmParams &p, double out[2], hipStream_t s) {

@@ -95,16 +95,14 @@ admm_small_iter_kernel(AdmmParams p, int j /* launch of the chunk: 0 = first */)
                 const int i = threadIdx.x + NT * k;
                 double s2 = 0;
                 if (i < n) { const double *grp = sv + (i / gl) * gl; for (int q = 0; q < gl; ++q) s2 += grp[q]; }   // the same sequential order as norm() on the slice
-                double scale = 1.0 - p.prox_param * p.mu / sqrt(s2);
-                if (!(scale > 0)) scale = 0.0;
-                zv[k] = i < n ? scale * vv[k] : 0.0;
+                zv[k] = i < n ? group_scale(s2, p.prox_param * p.mu) * vv[k] : 0.0;
             }
         } else {
             const double gl1 = p.mu * p.prox_param, th0 = sqrt(2.0 * p.mu * p.prox_param);
 #pragma unroll
             for (int k = 0; k < EPT; ++k) {
                 const double v = vv[k];
-                zv[k] = p.prox_kind == LPVS_PROX_L1 ? v + (v <= -gl1 ? gl1 : (v >= gl1 ? -gl1 : -v)) : (fabs(v) > th0 ? v : 0.0);
+                zv[k] = p.prox_kind == LPVS_PROX_L1 ? prox_l1(v, gl1) : prox_l0(v, th0);
             }
         }
         double ss = 0, un[EPT], rh[EPT];
@@ -112,10 +110,10 @@ admm_small_iter_kernel(AdmmParams p, int j /* launch of the chunk: 0 = first */)
         for (int k = 0; k < EPT; ++k) {
             const int i = threadIdx.x + NT * k;
             const bool ok = i < n;
-            const double xi = ok ? xv[k] : 0.0, d = xi - zv[k];
-            un[k] = (ok ? uv[k] : 0.0) + d;
-            rh[k] = ok ? bv[k] + (zv[k] - un[k]) / p.mu : 0.0;
-            ss = fma(d, d, ss);
+            const DualStep t = dual_step(ok ? xv[k] : 0.0, ok ? uv[k] : 0.0, zv[k], bv[k], p.mu, ok, false);
+            un[k] = t.un;
+            rh[k] = t.rhs;
+            ss = fma(t.d, t.d, ss);
             srhs[i] = rh[k];
         }
         double nxz = 0.0;
@@ -130,9 +128,7 @@ admm_small_iter_kernel(AdmmParams p, int j /* launch of the chunk: 0 = first */)
         }
         const bool conv = nxz < p.tol;                                        //                                  src/lasso.jl:164
         if (blockIdx.x == 0 && threadIdx.x == 0) {
-            status->iters += 1;
-            status->nxz = nxz;
-            if (conv) { status->converged = 1; ctl[2] = j; }
+            if (commit_iteration(status, nxz, p.tol)) ctl[2] = j;
             ctl[j & 1] = conv ? 1 : 0;
         }
         // the owner of elements [NW b, NW b + NW) writes their z and u (and the right-hand side when the chunk -- or the run -- ends here)
