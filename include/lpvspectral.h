@@ -282,7 +282,9 @@ int32_t lpvs_problem_pack_params_f64(lpvs_problem *h, const double *coef, double
  * corrections inside out[4] (HIP events around each), out[10] their count; out[11] the refreshes of the stale nibble product
  * enqueued inside out[4] (LPVS_STORAGE_MIXED32), out[12] the duration of one (us) where a refresh is three kernels of its own (the two-launch
  * iteration; measured stand-alone by lpvs_admm_time_matvec) -- 0 before that call and for the one-launch iteration, whose refresh is part
- * of the launch it follows (that launch also multiplies the 4-bit planes) plus one vector kernel. */
+ * of the launch it follows (that launch also multiplies the 4-bit planes) plus one vector kernel; out[13] the samples per stage of the
+ * dense Gram kernel instance that was launched (gram_kernel<MODE, BK>: 32, 16 or 8) and out[14] the number of sample chunks its tiles were
+ * split into -- both 0 for a given or structured Gram.  n_out values are written (at most 15): a caller asking for 13 gets the first 13. */
 int32_t lpvs_problem_get_timing(lpvs_problem *h, double *out, int32_t n_out);
 
 /* average duration (microseconds) of the ADMM mat-vec kernel of this handle over `reps` back-to-back launches, from

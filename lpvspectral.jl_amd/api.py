@@ -575,13 +575,14 @@ class Problem:
         return re + 1j * im
 
     def timing(self):
-        t = np.zeros(13)
-        check(lib().lpvs_problem_get_timing(self._h, out_ptr(t), 13))
+        t = np.zeros(15)
+        check(lib().lpvs_problem_get_timing(self._h, out_ptr(t), 15))
         return dict(basis_ms=t[0], gram_ms=t[1], reduce_rhs_ms=t[2], factor_ms=t[3], admm_ms=t[4],
                     gram_issued_flops=t[5], gram_flops=t[6], admm_iters=t[7],
                     gram_form=("given", "kr", "krs", "panel", "ap", "ap-nufft")[int(t[8])],
                     xcorr_ms=t[9], xcorr_count=int(t[10]),      # the x-update corrections inside admm_ms
-                    nibble_refreshes=int(t[11]), nibble_refresh_us=t[12])   # the stale nibble product's refreshes inside admm_ms; one of them, stand-alone
+                    nibble_refreshes=int(t[11]), nibble_refresh_us=t[12],   # the stale nibble product's refreshes inside admm_ms; one of them, stand-alone
+                    gram_stage=int(t[13]), gram_ksplit=int(t[14]))          # dense Gram: samples per stage of the gram_kernel instance, sample chunks (0: given / structured)
 
 
 # --------------------------------------------------------------------------- ADMM driver

@@ -393,6 +393,7 @@ struct lpvs_problem {
     double mu = 0.05, tol = 1e-5; int sign = 1; bool inited = false;
     // timing (ms) -- see lpvs_problem_get_timing
     double t_basis = 0, t_gram = 0, t_reduce = 0, t_factor = 0, t_admm = 0, gram_launches = 0, gram_flops = 0, admm_iters_timed = 0, gram_form = 0;
+    int gram_stage = 0, gram_ksplit = 0;   // dense Gram: samples per stage of the gram_kernel instance launched, sample chunks (0: given / structured Gram)
     double t_xcorr = 0, n_xcorr = 0;       // the x-update corrections inside t_admm: their time (HIP events around each) and count
     std::vector<hipEvent_t> xc_ev;         // event pairs of the corrections of the running lpvs_admm_run call (read after its final synchronisation, then reused)
     EventPair ev[4];          // copies of the bundle's events (owned by `res`)
@@ -563,7 +564,7 @@ static int32_t create_panel_problem(lpvs_problem *h, const double *y, const doub
     LPVS_TRY(slab.alloc(pl.slab_bytes));
     LPVS_TRY(scr.alloc(rhs_scratch_bytes(N, h->n)));
     LPVS_HIP(hipEventRecord(h->ev[1].a, s));
-    LPVS_TRY(launch_gram_panel(pl, P.as<double>(), ld, Wdev, slab.as<double>(), s));
+    LPVS_TRY(launch_gram_panel(pl, P.as<double>(), ld, Wdev, slab.as<double>(), s, &h->gram_stage));
     LPVS_HIP(hipEventRecord(h->ev[1].b, s));
     LPVS_HIP(hipEventRecord(h->ev[2].a, s));
     LPVS_TRY(launch_gram_reduce(pl, slab.as<double>(), h->G.as<double>(), h->np, s));
@@ -572,7 +573,7 @@ static int32_t create_panel_problem(lpvs_problem *h, const double *y, const doub
     LPVS_HIP(hipStreamSynchronize(s));
     h->t_basis = h->ev[0].ms(); h->t_gram = h->ev[1].ms(); h->t_reduce = h->ev[2].ms();
     h->gram_launches = (double)pl.tiles * 128.0 * 256.0 * 2.0 * (double)(pl.ksplit * pl.rows_per_chunk);   // flops the MFMA core issues
-    h->gram_form = 3;
+    h->gram_form = 3; h->gram_ksplit = (int)pl.ksplit;
     h->gram_flops = (double)N * (double)h->n * (double)(h->n + 1);
     return LPVS_OK;
 }
@@ -940,8 +941,8 @@ static int32_t create_lpv_impl(const double *y, int64_t ns, const double *X, con
     LPVS_HIP(hipEventRecord(side.ready, s));                 // tables are complete at this point of the main stream
     LPVS_HIP(hipStreamWaitEvent(side.s, side.ready, 0));
     LPVS_HIP(hipEventRecord(h->ev[1].a, s));
-    if (krs) LPVS_TRY(launch_gram_krs(pl, T.as<double2>(), Nf, KK.as<double>(), nb, slab.as<double>(), s));
-    else LPVS_TRY(launch_gram_kr(pl, T.as<double2>(), Nf, K.as<double>(), ldk, nb, slab.as<double>(), s));
+    if (krs) LPVS_TRY(launch_gram_krs(pl, T.as<double2>(), Nf, KK.as<double>(), nb, slab.as<double>(), s, &h->gram_stage));
+    else LPVS_TRY(launch_gram_kr(pl, T.as<double2>(), Nf, K.as<double>(), ldk, nb, slab.as<double>(), s, &h->gram_stage));
     LPVS_HIP(hipEventRecord(h->ev[1].b, s));
     for (int64_t q = 0; q < ns; ++q)   // b_q = Phi' y_q for every signal sharing the regressor
         LPVS_TRY(launch_rhs_kr(T.as<double2>(), Nf, K.as<double>(), ldk, nb, dy.p + q * N, N, h->b.as<double>() + q * h->np, scr.as<double>(), scr.bytes, side.s));
@@ -954,7 +955,7 @@ static int32_t create_lpv_impl(const double *y, int64_t ns, const double *X, con
     LPVS_HIP(hipStreamSynchronize(s));
     h->t_basis = h->ev[0].ms(); h->t_gram = h->ev[1].ms(); h->t_reduce = h->ev[2].ms();
     h->gram_launches = (double)pl.tiles * 128.0 * 256.0 * 2.0 * (double)(pl.ksplit * pl.rows_per_chunk); h->gram_flops = (double)N * (double)h->n * (double)(h->n + 1);
-    h->gram_form = krs ? 2 : 1;
+    h->gram_form = krs ? 2 : 1; h->gram_ksplit = (int)pl.ksplit;
     guard.h = nullptr;
     *out = h;
     return LPVS_OK;
@@ -1635,9 +1636,9 @@ int32_t lpvs_problem_pack_params_f64(lpvs_problem *h, const double *coef, double
 
 int32_t lpvs_problem_get_timing(lpvs_problem *h, double *out, int32_t n_out) {
     if (!h || !out) { set_error("NULL argument"); return LPVS_EARGUMENT; }
-    const double v[13] = {h->t_basis, h->t_gram, h->t_reduce, h->t_factor, h->t_admm, h->gram_launches, h->gram_flops, h->admm_iters_timed, h->gram_form,
-                          h->t_xcorr, h->n_xcorr, h->n_nib, h->nib_us};
-    for (int i = 0; i < n_out && i < 13; ++i) out[i] = v[i];
+    const double v[15] = {h->t_basis, h->t_gram, h->t_reduce, h->t_factor, h->t_admm, h->gram_launches, h->gram_flops, h->admm_iters_timed, h->gram_form,
+                          h->t_xcorr, h->n_xcorr, h->n_nib, h->nib_us, (double)h->gram_stage, (double)h->gram_ksplit};
+    for (int i = 0; i < n_out && i < 15; ++i) out[i] = v[i];
     return LPVS_OK;
 }
 

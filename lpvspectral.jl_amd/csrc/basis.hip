@@ -173,19 +173,23 @@ minmax_kernel(const double *__restrict__ V, int64_t N, double *__restrict__ part
 }
 
 // ---- a4+a5 materialised: Phi column-major N x 2*Nf*nb -------------------------------------
-// One block = 64 samples x one frequency; the T / K rows are staged through LDS so that both
-// the table reads (along f / j) and the Phi stores (along n) are coalesced.
+// One block = 64 samples x one frequency x up to REG_JC basis functions (blockIdx.z); the T / K rows are
+// staged through LDS so that both the table reads (along f / j) and the Phi stores (along n) are coalesced.
+// The LDS image is 64 * min(nb, REG_JC) + 128 doubles (33 KiB at most) whatever nb is.
+constexpr int REG_JC = 64;
 __global__ void __launch_bounds__(256)
 lpv_regressor_colmajor_kernel(const double2 *__restrict__ T, const double *__restrict__ K, int64_t ldk,
                               int64_t N, int64_t Nf, int64_t nb, int permuted,
                               double *__restrict__ Phi) {
-    extern __shared__ double sh[];  // [64][nb] activations, then [64] cos, [64] -sin
+    extern __shared__ double sh[];  // [64][jn] activations, then [64] cos, [64] -sin
     const int64_t n0 = (int64_t)blockIdx.x * 64;
     const int64_t fn = blockIdx.y;
-    double *sK = sh, *sc = sh + 64 * nb, *ss = sc + 64;
-    for (int64_t i = threadIdx.x; i < 64 * nb; i += 256) {
-        const int64_t r = i / nb, j = i - r * nb;
-        sK[i] = (n0 + r < N) ? K[(n0 + r) * ldk + j] : 0.0;
+    const int64_t j0 = (int64_t)blockIdx.z * REG_JC;
+    const int64_t jn = nb - j0 < REG_JC ? nb - j0 : REG_JC;
+    double *sK = sh, *sc = sh + 64 * jn, *ss = sc + 64;
+    for (int64_t i = threadIdx.x; i < 64 * jn; i += 256) {
+        const int64_t r = i / jn, j = i - r * jn;
+        sK[i] = (n0 + r < N) ? K[(n0 + r) * ldk + j0 + j] : 0.0;
     }
     if (threadIdx.x < 64 && n0 + threadIdx.x < N) {
         const double2 tv = T[(n0 + threadIdx.x) * Nf + fn];
@@ -195,12 +199,13 @@ lpv_regressor_colmajor_kernel(const double2 *__restrict__ T, const double *__res
     __syncthreads();
     const int r = threadIdx.x & 63;
     if (n0 + r >= N) return;
-    for (int64_t c = threadIdx.x >> 6; c < 2 * nb; c += 4) {
-        const int64_t j = c < nb ? c : c - nb;
-        const double val = (c < nb ? sc[r] : ss[r]) * sK[r * nb + j];
+    for (int64_t c = threadIdx.x >> 6; c < 2 * jn; c += 4) {
+        const bool im = c >= jn;
+        const int64_t jl = im ? c - jn : c, j = j0 + jl;
+        const double val = (im ? ss[r] : sc[r]) * sK[r * jn + jl];
         int64_t col;
-        if (permuted) col = fn * 2 * nb + c;                       // inds of src/lasso.jl:47
-        else col = (c < nb ? 0 : Nf * nb) + fn + j * Nf;           // [Re As, Im As]
+        if (permuted) col = fn * 2 * nb + (im ? nb : 0) + j;       // inds of src/lasso.jl:47
+        else col = (im ? Nf * nb : 0) + fn + j * Nf;               // [Re As, Im As]
         Phi[(n0 + r) + col * N] = val;
     }
 }
@@ -307,8 +312,8 @@ int32_t device_minmax(const double *V, int64_t N, double *lo, double *hi, double
 int32_t launch_lpv_regressor_colmajor(const double2 *T, const double *K, int64_t ldk, int64_t N, int64_t Nf,
                                       int64_t nb, int permuted, double *Phi, hipStream_t s) {
     if (N == 0 || Nf == 0) return LPVS_OK;
-    const size_t lds = sizeof(double) * (64 * nb + 128);
-    dim3 grid((unsigned)ceil_div(N, 64), (unsigned)Nf);
+    const size_t lds = sizeof(double) * (64 * (nb < REG_JC ? nb : REG_JC) + 128);
+    dim3 grid((unsigned)ceil_div(N, 64), (unsigned)Nf, (unsigned)ceil_div(nb, REG_JC));
     hipLaunchKernelGGL(lpv_regressor_colmajor_kernel, grid, dim3(256), lds, s, T, K, ldk, N, Nf, nb, permuted, Phi);
     LPVS_HIP(hipGetLastError());
     return LPVS_OK;

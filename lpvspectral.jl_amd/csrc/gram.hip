@@ -583,30 +583,30 @@ static int32_t launch_gram_t(const GramArgs &a, unsigned grid, size_t lds, hipSt
 constexpr size_t kLdsBudget = 160 * 1024;
 
 int32_t launch_gram_kr(const GramPlan &pl, const double2 *T, int64_t Nf, const double *K, int64_t ldk,
-                       int64_t nb, double *slab, hipStream_t s) {
+                       int64_t nb, double *slab, hipStream_t s, int *stage) {
     GramArgs a{};
     a.n = pl.n; a.rows_per_chunk = pl.rows_per_chunk; a.ksplit = (int)pl.ksplit;
     LPVS_TRY(get_tiles(pl.n, 0, s, &a.tiles, &a.ntiles));
     a.slab = slab; a.T = T; a.K = K; a.Nf = (int)Nf; a.nb = (int)nb; a.ldk = (int)ldk;
     const unsigned grid = (unsigned)(pl.tiles * pl.ksplit);
     // deepest stage whose two LDS images fit (few basis functions -> many frequencies per tile)
-    if (gram_lds_bytes(0, 32, nb, ldk) <= kLdsBudget) return launch_gram_t<0, 32>(a, grid, gram_lds_bytes(0, 32, nb, ldk), s);
-    if (gram_lds_bytes(0, 16, nb, ldk) <= kLdsBudget) return launch_gram_t<0, 16>(a, grid, gram_lds_bytes(0, 16, nb, ldk), s);
-    if (gram_lds_bytes(0, 8, nb, ldk) <= kLdsBudget) return launch_gram_t<0, 8>(a, grid, gram_lds_bytes(0, 8, nb, ldk), s);
+    if (gram_lds_bytes(0, 32, nb, ldk) <= kLdsBudget) { if (stage) *stage = 32; return launch_gram_t<0, 32>(a, grid, gram_lds_bytes(0, 32, nb, ldk), s); }
+    if (gram_lds_bytes(0, 16, nb, ldk) <= kLdsBudget) { if (stage) *stage = 16; return launch_gram_t<0, 16>(a, grid, gram_lds_bytes(0, 16, nb, ldk), s); }
+    if (gram_lds_bytes(0, 8, nb, ldk) <= kLdsBudget) { if (stage) *stage = 8; return launch_gram_t<0, 8>(a, grid, gram_lds_bytes(0, 8, nb, ldk), s); }
     set_error("gram_kr: LDS image exceeds 160 KiB even at 8 samples per stage (nb=%lld)", (long long)nb);
     return LPVS_EUNSUPPORTED;
 }
 
 int32_t launch_gram_krs(const GramPlan &pl, const double2 *T, int64_t Nf, const double *KK, int64_t nb, double *slab,
-                        hipStream_t s) {
+                        hipStream_t s, int *stage) {
     GramArgs a{};
     a.n = pl.n; a.rows_per_chunk = pl.rows_per_chunk; a.ksplit = (int)pl.ksplit;
     LPVS_TRY(get_tiles(pl.np2, pl.pairs, s, &a.tiles, &a.ntiles));
     a.slab = slab; a.T = T; a.K = KK; a.Nf = (int)Nf; a.nb = (int)nb; a.ldk = (int)pl.pairs; a.npair = (int)pl.pairs;
     a.nq = pl.np2 * pl.pairs;
     const unsigned grid = (unsigned)(pl.tiles * pl.ksplit);
-    if (gram_lds_bytes(2, 32, nb, pl.pairs) <= kLdsBudget) return launch_gram_t<2, 32>(a, grid, gram_lds_bytes(2, 32, nb, pl.pairs), s);
-    if (gram_lds_bytes(2, 16, nb, pl.pairs) <= kLdsBudget) return launch_gram_t<2, 16>(a, grid, gram_lds_bytes(2, 16, nb, pl.pairs), s);
+    if (gram_lds_bytes(2, 32, nb, pl.pairs) <= kLdsBudget) { if (stage) *stage = 32; return launch_gram_t<2, 32>(a, grid, gram_lds_bytes(2, 32, nb, pl.pairs), s); }
+    if (gram_lds_bytes(2, 16, nb, pl.pairs) <= kLdsBudget) { if (stage) *stage = 16; return launch_gram_t<2, 16>(a, grid, gram_lds_bytes(2, 16, nb, pl.pairs), s); }
     set_error("gram_krs: LDS image exceeds 160 KiB (nb=%lld)", (long long)nb);
     return LPVS_EUNSUPPORTED;
 }
@@ -638,11 +638,12 @@ int32_t launch_gram_reduce_krs(const GramPlan &pl, const double *slab, int64_t n
 }
 
 int32_t launch_gram_panel(const GramPlan &pl, const double *P, int64_t ld, const double *W, double *slab,
-                          hipStream_t s) {
+                          hipStream_t s, int *stage) {
     GramArgs a{};
     a.n = pl.n; a.rows_per_chunk = pl.rows_per_chunk; a.ksplit = (int)pl.ksplit;
     LPVS_TRY(get_tiles(pl.n, 0, s, &a.tiles, &a.ntiles));
     a.slab = slab; a.P = P; a.W = W; a.ld = ld;
+    if (stage) *stage = 16;
     return launch_gram_t<1, 16>(a, (unsigned)(pl.tiles * pl.ksplit), gram_lds_bytes(1, 16, 0, 0), s);  // 2 x 48 KiB
 }
 

@@ -141,16 +141,17 @@ GramPlan make_gram_plan_pairs(int64_t Nf, int64_t nb, int64_t N);
 bool gram_krs_fits(int64_t nb);   // does the symmetric-pair form fit LDS for this many basis functions?
 // symmetric-pair form of the LPV Gram (see gram.hip): KK = pair products of the activation table
 int32_t launch_pair_table(const double *K, int64_t ldk, int64_t nb, int64_t Npad, double *KK, hipStream_t s);
+// (stage, where not NULL: the samples per stage of the gram_kernel instance that was launched)
 int32_t launch_gram_krs(const GramPlan &pl, const double2 *T, int64_t Nf, const double *KK, int64_t nb,
-                        double *slab, hipStream_t s);
+                        double *slab, hipStream_t s, int *stage = nullptr);
 int32_t launch_gram_reduce_krs(const GramPlan &pl, const double *slab, int64_t nb, double *G3, double *G,
                                int64_t ldg, hipStream_t s);
 // Khatri-Rao form: Phi[k][f*2nb + c] = T[k][f][c>=nb] * K[k][c mod nb]
 int32_t launch_gram_kr(const GramPlan &pl, const double2 *T, int64_t Nf, const double *K,
-                       int64_t ldk, int64_t nb, double *slab, hipStream_t s);
+                       int64_t ldk, int64_t nb, double *slab, hipStream_t s, int *stage = nullptr);
 // panel form: Phi[k][c] = P[k*ld + c], optional row weights W (applied once: G = P' diag(W) P)
 int32_t launch_gram_panel(const GramPlan &pl, const double *P, int64_t ld, const double *W,
-                          double *slab, hipStream_t s);
+                          double *slab, hipStream_t s, int *stage = nullptr);
 int32_t launch_gram_panel_batch(const GramPlan &pl, int nbatch, const double *P, int64_t batch_stride_P, int64_t ld,
                                 const double *W, double *slab, hipStream_t s);
 int32_t launch_gram_reduce_batch(const GramPlan &pl, int nbatch, const double *slab, double *G, int64_t ldg, hipStream_t s);

@@ -200,3 +200,96 @@ int64_t lpvo_admm_minv_ld(const double *Mt, int64_t n, const double *xb_hi, cons
     free(x); free(z); free(u); free(t);
     return it;
 }
+
+/* Gram of an f64 regressor in extended precision -- the reference the dense Gram kernels are held to entry by entry.
+ * Phi: N x n column-major (column a contiguous), W: N row weights or NULL, Y: ns right-hand sides of N samples each ([ns][N]) or NULL.
+ *   G[a][b] = sum_k W_k Phi_ka Phi_kb          S[a][b] = sum_k |W_k Phi_ka Phi_kb|          (n x n, both halves written)
+ *   b[q][a] = sum_k W_k Phi_ka Y_qk            s[q][a] = sum_k |W_k Phi_ka Y_qk|            ([ns][n])
+ * Every product and sum is a long double (64-bit mantissa: products of doubles round at 2^-64, integer data below 2^63 is exact);
+ * each output is rounded to double once.  S and s are the scales of the a-priori bound |fl(sum) - sum| <= N u sum|terms| that holds
+ * for ANY order of summation.  G or b (with their scales) may be NULL.  OpenMP over rows of G.  Returns 0, or < 0. */
+int64_t lpvo_gram_ld(const double *Phi, int64_t N, int64_t n, const double *W, const double *Y, int64_t ns,
+                     double *G, double *S, double *b, double *s) {
+    if (N < 1 || n < 1 || !Phi || (G && !S) || (b && (!s || !Y || ns < 1))) return -2;
+    int fail = 0;
+#pragma omp parallel
+    {
+        ld *wa = (ld *)malloc(sizeof(ld) * (size_t)N);
+        if (!wa) {
+#pragma omp atomic write
+            fail = 1;
+        }
+#pragma omp for schedule(dynamic, 4)
+        for (int64_t ar = 0; ar < n; ++ar) {
+            if (!wa) continue;
+            const int64_t a = n - 1 - ar;                  /* longest rows first */
+            const double *ca = Phi + a * N;
+            for (int64_t k = 0; k < N; ++k) wa[k] = W ? (ld)W[k] * (ld)ca[k] : (ld)ca[k];
+            for (int64_t c = 0; G && c <= a; ++c) {
+                const double *cb = Phi + c * N;
+                ld g0 = 0, g1 = 0, g2 = 0, g3 = 0, s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+                int64_t k = 0;
+                for (; k + 4 <= N; k += 4) {
+                    const ld p0 = wa[k] * (ld)cb[k], p1 = wa[k + 1] * (ld)cb[k + 1], p2 = wa[k + 2] * (ld)cb[k + 2], p3 = wa[k + 3] * (ld)cb[k + 3];
+                    g0 += p0; g1 += p1; g2 += p2; g3 += p3;
+                    s0 += fabsl(p0); s1 += fabsl(p1); s2 += fabsl(p2); s3 += fabsl(p3);
+                }
+                for (; k < N; ++k) { const ld p = wa[k] * (ld)cb[k]; g0 += p; s0 += fabsl(p); }
+                G[a * n + c] = G[c * n + a] = (double)((g0 + g1) + (g2 + g3));
+                S[a * n + c] = S[c * n + a] = (double)((s0 + s1) + (s2 + s3));
+            }
+            for (int64_t q = 0; b && q < ns; ++q) {
+                const double *yq = Y + q * N;
+                ld g = 0, sa = 0;
+                for (int64_t k = 0; k < N; ++k) { const ld p = wa[k] * (ld)yq[k]; g += p; sa += fabsl(p); }
+                b[q * n + a] = (double)g;
+                s[q * n + a] = (double)sa;
+            }
+        }
+        free(wa);
+    }
+    return fail ? -4 : 0;
+}
+
+/* Gram of a trigonometric regressor whose PHASES w_f x_k are formed in extended precision (the structured Gram forms -- nudft.hip,
+ * nufft.hip -- do not round the phase to a double as the regressor kernels do, so they are held to this one).
+ *   kind 0 (LPV, permuted columns): Phi[k][f*2nb + c*nb + j] = (c ? -sin : cos)(w_f x_k) K[k][j],  K: N x nb column-major doubles
+ *   kind 1 (Fourier): Phi[k][f] = cos(w_f x_k) dd, Phi[k][Nf - zf + f] = -sin(w_f x_k) dd (f >= zf), dd = 1/sqrt(2 Nf), w_f given (2 pi f
+ *           as the library rounds it), zf = 1 when the first frequency is zero; K unused, nb = 1
+ * G[a][b] = sum_k W_k Phi_ka Phi_kb (W NULL: 1), n x n, both halves, every quantity a long double, rounded to double once.  Returns n or < 0. */
+int64_t lpvo_gram_phase_ld(int kind, const double *x, int64_t N, const double *w, int64_t Nf, const double *K, int64_t nb, int zf,
+                           const double *W, double *G) {
+    if (N < 1 || Nf < 1 || nb < 1 || !x || !w || !G || (kind == 0 && !K)) return -2;
+    const int64_t n = kind == 0 ? 2 * Nf * nb : 2 * Nf - (zf ? 1 : 0);
+    ld *Phi = (ld *)malloc(sizeof(ld) * (size_t)N * (size_t)n);      /* column-major */
+    if (!Phi) return -4;
+    const ld dd = 1 / sqrtl((ld)(2 * Nf));
+#pragma omp parallel for schedule(static)
+    for (int64_t f = 0; f < Nf; ++f)
+        for (int64_t k = 0; k < N; ++k) {
+            const ld ph = (ld)w[f] * (ld)x[k], c = cosl(ph), s = -sinl(ph);
+            if (kind == 0) {
+                for (int64_t j = 0; j < nb; ++j) {
+                    Phi[(f * 2 * nb + j) * N + k] = c * (ld)K[j * N + k];
+                    Phi[(f * 2 * nb + nb + j) * N + k] = s * (ld)K[j * N + k];
+                }
+            } else {
+                Phi[f * N + k] = c * dd;
+                if (!(zf && f == 0)) Phi[(Nf - (zf ? 1 : 0) + f) * N + k] = s * dd;
+            }
+        }
+#pragma omp parallel
+    {
+        ld *wa = (ld *)malloc(sizeof(ld) * (size_t)N);
+#pragma omp for schedule(dynamic, 4)
+        for (int64_t ar = 0; ar < n; ++ar) {
+            const int64_t a = n - 1 - ar;
+            if (!wa) { G[a * n + a] = NAN; continue; }
+            for (int64_t k = 0; k < N; ++k) wa[k] = W ? (ld)W[k] * Phi[a * N + k] : Phi[a * N + k];
+            for (int64_t c = 0; c <= a; ++c) G[a * n + c] = G[c * n + a] = (double)dot_ld(wa, Phi + c * N, N);
+        }
+        free(wa);
+    }
+    free(Phi);
+    return n;
+}

@@ -280,7 +280,7 @@ def _lib_ld():
         if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
             subprocess.check_call(["make", "-s", "-C", _HERE, "liblpvs_oracle_ld.so"])
         _LIB_LD = C.CDLL(so)
-        for fn in ("lpvo_admm_gram_ld", "lpvo_admm_minv_ld", "lpvo_inverse_ld"):
+        for fn in ("lpvo_admm_gram_ld", "lpvo_admm_minv_ld", "lpvo_inverse_ld", "lpvo_gram_ld", "lpvo_gram_phase_ld"):
             getattr(_LIB_LD, fn).restype = C.c_int64
         assert _LIB_LD.lpvo_ld_mantissa_bits() == 64, "long double is not the x87 extended format on this host"
     return _LIB_LD
@@ -299,6 +299,47 @@ def inverse_ld(G, mu, b=None):
     hi, lo = np.zeros(n), np.zeros(n)
     assert _lib_ld().lpvo_inverse_ld(_p(G), C.c_int64(n), C.c_double(mu), _p(M), _p(b), _p(hi), _p(lo)) == 0
     return M, hi, lo
+
+
+def gram_ld(Phi, y=None, W=None):
+    """lpvs_oracle_ld.c: the Gram of the f64 regressor ``Phi`` (N x n), optional row weights ``W`` and right-hand sides ``y`` (N, or N x ns
+    with one signal per column), every product and sum in x87 extended precision, rounded to double once.  Returns ``(G, S, b, s)``:
+    G = Phi' diag(W) Phi and b = Phi' (W .* y) with the sums of the ABSOLUTE values of their terms S (n x n) and s -- the scale of the
+    worst-case bound N u S that any order of summation in doubles meets.  ``b, s`` are ``None`` without ``y``; n x ns for a 2-d ``y``."""
+    Phi = np.asfortranarray(Phi, dtype=np.float64)
+    N, n = Phi.shape
+    G, S = np.zeros((n, n)), np.zeros((n, n))
+    WW = _f64(W) if W is not None else None
+    assert WW is None or len(WW) == N
+    Y = b = s = None
+    ns = 0
+    if y is not None:
+        Y = np.asfortranarray(np.asarray(y, dtype=np.float64).reshape(N, -1))
+        ns = Y.shape[1]
+        b, s = np.zeros((ns, n)), np.zeros((ns, n))
+    rc = _lib_ld().lpvo_gram_ld(_p(Phi), C.c_int64(N), C.c_int64(n), _p(WW) if WW is not None else None, _p(Y) if Y is not None else None,
+                                C.c_int64(ns), _p(G), _p(S), _p(b) if b is not None else None, _p(s) if s is not None else None)
+    assert rc == 0, rc
+    if y is not None:
+        b, s = (b[0].copy(), s[0].copy()) if np.ndim(y) == 1 else (b.T.copy(), s.T.copy())
+    return G, S, b, s
+
+
+def gram_phase_ld(x, w, K=None, zerofreq=False, W=None):
+    """lpvs_oracle_ld.c: the Gram of the trigonometric regressor with the phases ``w_f x_k`` formed in extended precision -- what the
+    structured Gram forms, which never round a phase to a double, are held to.  With an activation table ``K`` (N x nb) the LPV regressor in
+    permuted column order; without, the Fourier regressor for the angular frequencies ``w`` (pass ``6.283185307179586 * f``)."""
+    x, w = _f64(x), _f64(w)
+    N, Nf = len(x), len(w)
+    Kf = np.asfortranarray(K, dtype=np.float64) if K is not None else None
+    nb = Kf.shape[1] if Kf is not None else 1
+    n = 2 * Nf * nb if Kf is not None else 2 * Nf - (1 if zerofreq else 0)
+    G = np.zeros((n, n))
+    WW = _f64(W) if W is not None else None
+    rc = _lib_ld().lpvo_gram_phase_ld(C.c_int(0 if Kf is not None else 1), _p(x), C.c_int64(N), _p(w), C.c_int64(Nf), _p(Kf) if Kf is not None else None,
+                                      C.c_int64(nb), C.c_int(1 if zerofreq else 0), _p(WW) if WW is not None else None, _p(G))
+    assert rc == n, rc
+    return G
 
 
 def admm_minv_ld(Mt, xb, proxg, snaps, xb_lo=None, x0=None, mu=0.05):
