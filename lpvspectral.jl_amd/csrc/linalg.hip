@@ -9,6 +9,7 @@
 // kept current during the sweeps (row panels are read transposed from it); one pass at the end
 // negates and mirrors it, so the result is exactly symmetric.
 #include "lpvs_internal.h"
+#include "factor_plan.h"
 
 #include <cstdlib>
 #include <map>
@@ -1071,7 +1072,19 @@ symm_matmul_kernel(const double *__restrict__ A, const double *__restrict__ B, d
 
 }  // namespace
 
-constexpr int64_t kTwoLevelMinNp = 1024;
+// np is a multiple of 128 (spd_inverse_impl refuses anything else) and the trailing update's tiles are 128 x 128: the panels' leading
+// dimension ldp = round_up(np, RU_TN) is np itself, and a 128- or 256-wide pivot band is whole tile rows and columns.
+static_assert(RU_TM == 128 && RU_TN == 128, "the two-level schedules assume 128 x 128 trailing-update tiles");
+
+// Workspace of the two-level schedules, in doubles:  panels | P (KW x KW) | workspace of the sweep of a 256-wide pivot block | tile list.
+// The panel region holds {Bk, Ck} pairs: three of KW x ldp each for the steps schedules (depth-2 look-ahead rotates three), 2 x kMaxGroup
+// slots of 128 x ldp each for the group schedule (groups of four steps, two groups in flight).
+constexpr int kStepPairs = 3, kGroupSlots = 2 * kMaxGroup;
+constexpr int64_t kStepPairRows = 2 * KW, kGroupSlotRows = 2 * 128;   // rows of ldp doubles in one pair / one slot
+constexpr int64_t kPanelRows = kGroupSlots * kGroupSlotRows;
+static_assert(kStepPairs * kStepPairRows <= kPanelRows, "the steps schedules' panel pairs must fit the panel region");
+static_assert((kGroupSlots & (kGroupSlots - 1)) == 0, "slot = pivot block & (kGroupSlots - 1)");
+static_assert(kMaxGroup == kFactorGroupMax, "the plan's largest group is what RuGroup holds");
 
 static size_t sweep64_work_doubles(int64_t np) { return (size_t)(2 * np * NB + NB * NB); }
 static size_t ru_tile_capacity(int64_t np) { const int64_t nr = np / RU_TM, nc = ceil_div(np, RU_TN); return (size_t)(nr * nc); }
@@ -1080,7 +1093,7 @@ size_t spd_inverse_work_bytes(int64_t np) {
     size_t d = sweep64_work_doubles(np);
     if (np >= kTwoLevelMinNp) {
         const int64_t ldp = round_up(np, RU_TN);
-        const size_t two = (size_t)(8 * KW * ldp + KW * KW) + sweep64_work_doubles(KW) + ru_tile_capacity(np);   // 8 panel slots (groups of four steps, two groups in flight)   // int2 = one double
+        const size_t two = (size_t)(kPanelRows * ldp + KW * KW) + sweep64_work_doubles(KW) + ru_tile_capacity(np);   // int2 = one double
         if (two > d) d = two;
     }
     return sizeof(double) * d;
@@ -1152,245 +1165,284 @@ SweepAux::~SweepAux() {
     if (second) (void)hipEventDestroy(second);
 }
 
+// ---- the two-level factorisation: factor_plan.h decides, the functions below launch ------------------------------------------------
 // Step k of the outer sweep:  chain_k = { P = inv(A_kk); Bk = A[:,k]; Ck = -(Bk' P)'; A[:,k] = C; A_kk = -P },
 // then the trailing update U_k.  With look-ahead U_k is split: the tiles that intersect the NEXT pivot band run first
 // on the side stream, followed by chain_{k+1} (into the other panel buffer), while the rest of U_k runs on the main
 // stream; U_{k+1} starts when both are done.  The pivot chain (latency-bound, one workgroup) thus hides under the
 // MFMA-bound bulk update.
-static int32_t spd_inverse_two_level(double *A, int64_t np, double *work, int *status_dev, hipStream_t s, SweepAux *aux) {
-    const int64_t ldp = round_up(np, RU_TN);
-    double *panelbuf[3] = {work, work + 2 * KW * ldp, work + 4 * KW * ldp};   // {Bk, Ck} x 3 (depth-2 look-ahead rotates three)
-    double *P = work + 8 * KW * ldp, *inner = P + KW * KW;
-    int2 *tiles = reinterpret_cast<int2 *>(inner + sweep64_work_doubles(KW));
-    const std::vector<int2> &ht = ru_tiles(np);   // persistent host copy: the async upload may outlive this call
-    LPVS_HIP(hipMemcpyAsync(tiles, ht.data(), sizeof(int2) * ht.size(), hipMemcpyHostToDevice, s));
-    const size_t lds = sizeof(double) * 2 * RU_BK * (RU_TM + RU_TN);
-    const bool single_wg_pivot = [] { const char *e = experiment_env("LPVS_PIVOT"); return !(e && std::string(e) == "sweep64"); }();
-    const bool lookahead_on = [] { const char *e = experiment_env("LPVS_LOOKAHEAD"); return !(e && e[0] == '0'); }();
-    LPVS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&rank_update_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    // 128-wide pivot blocks (one-workgroup inverse) up to np ~ 12k; beyond, the bulk update is long enough to hide the
-    // 256-wide chain (pivot block by the 64-wide sweep) and the deeper update runs closer to the MFMA peak
-    const int kw_env = [] { const char *e = experiment_env("LPVS_KW"); return e ? atoi(e) : 0; }();
-    // (the group schedule below runs 128-wide steps: 39.9 ms against 47.5 with 256-wide steps at np = 12288, 89.5 / 93.5 at 16384, equal at 32768)
-    const bool steps_scheme = [] { const char *e = experiment_env("LPVS_FACTOR_SCHEME"); return e && std::string(e) == "steps"; }();
-    const int kw_outer = kw_env == 128 || kw_env == 256 ? kw_env : ((steps_scheme && np >= 12288) ? 256 : 128);
-    const bool la = lookahead_on && aux != nullptr && np > kw_outer;
-    if (la) LPVS_TRY(aux->ensure());
 
-    auto width = [&](int64_t k0) { return (int)(np - k0 < kw_outer ? np - k0 : kw_outer); };   // with 256: 128 for a ragged last block
-    auto chain = [&](int64_t k0, double *Bk, double *Ck, hipStream_t st) {
-        const int kw = width(k0);
-        if (single_wg_pivot && kw == 128) {
-            hipLaunchKernelGGL(pivot_inverse_kernel<128>, dim3(1), dim3(192), 0, st, A, np, k0, P, status_dev);
-        } else {
-            hipLaunchKernelGGL(pivot_extract_kernel, dim3((unsigned)kw), dim3(256), 0, st, A, np, k0, kw, P);
-            sweep64(P, kw, 1, inner, status_dev, st);
-            hipLaunchKernelGGL(negate_mirror_kernel, dim3((unsigned)(kw / 32), (unsigned)(kw / 32), 1u), dim3(256), 0, st, P, (int64_t)kw);
-        }
-        hipLaunchKernelGGL(panel_gather_kernel, dim3((unsigned)(ldp / 64)), dim3(256), 0, st, A, np, ldp, k0, kw, Bk);
-        hipLaunchKernelGGL(panel_gemm_kernel, dim3((unsigned)(ldp / (32 * (4 / (kw / 64))))), dim3(256), 0, st, A, np, ldp, k0, kw, P, Bk, Ck);
-    };
-    auto update = [&](int64_t k0, const double *Bk, const double *Ck, int which, hipStream_t st) {
-        const int kw = width(k0);
-        const int64_t n0 = k0 + kw;
-        const int nw = n0 < np ? width(n0) : 0;
-        const int64_t n1 = n0 + nw;
-        const int nw1 = (nw > 0 && n1 < np) ? width(n1) : 0;
-        // a 128-wide band is one tile row + one tile column: launch just those (32k early-exit workgroups cost 0.3 ms at np = 32768)
-        const bool direct1 = which == 1 && nw % RU_TM == 0 && nw > 0 && RU_TM == RU_TN;
-        const bool direct3 = which == 3 && nw1 % RU_TM == 0 && nw1 > 0 && RU_TM == RU_TN;
-        const unsigned grid = direct1 ? (unsigned)(np / RU_TM * (nw / RU_TM)) : (direct3 ? (unsigned)(np / RU_TM * (nw1 / RU_TM)) : (unsigned)ht.size());
-        const int band_tile = direct1 ? (int)(n0 / RU_TM) : (direct3 ? (int)(n1 / RU_TM) : -1);
-        hipLaunchKernelGGL(rank_update_kernel, dim3(grid), dim3(RU_THREADS), lds, st, A, np, ldp, k0,
-                           kw, Ck, Bk, tiles, (int)ht.size(), which, n0, nw, band_tile, n1, nw1);
-    };
+// what every schedule works on: the matrix, the carved-up workspace (see kPanelRows), the tile list, the streams
+struct FactorCtx {
+    double *A;
+    int64_t np, ldp;
+    double *panels, *P, *inner;
+    int2 *tiles;
+    int ntiles;
+    int *status_dev;
+    hipStream_t s;                 // the caller's stream
+    SweepAux *aux;                 // side streams and events (ensured unless the schedule is serial)
+    double *stepB(int i) const { return panels + i * kStepPairRows * ldp; }                    // pair i of the steps schedules
+    double *stepC(int i) const { return stepB(i) + KW * ldp; }
+    double *slotB(int blk) const { return panels + (int64_t)(blk & (kGroupSlots - 1)) * (kGroupSlotRows * ldp); }   // slot = pivot block mod 8
+    double *slotC(int blk) const { return slotB(blk) + 128 * ldp; }
+};
 
-    // ---- groups of up to four 128-wide steps: the trailing update takes the group's panels in ONE pass (rank_updatem_kernel) --------
-    // Per group (pivot blocks kb .. kb + mg - 1; panel kb is ready when the group starts; the next group starts at block nb0):
-    //   side:  for j = 1 .. mg-1:  band j += panels [.., j)  ->  chain kb+j        ->  [event panels]
-    //          [wait: previous group's rest]  the NEXT group's bands += this group's panels (priority)  ->  chain nb0  (the next group's first panel)
-    //   main:  [wait panels]  every tile outside the next group's bands += this group's panels                 ->  [event rest]
-    // The side stream (high priority) thus owns everything the pivot chains wait for -- its priority launch shares the chip with the
-    // main stream's pass instead of running ahead of it --, and the main stream is one deep pass per group.  Band / priority tiles are
-    // disjoint from the rest launch's; the priority tiles were last written by the previous group's rest launch (hence the wait).
-    // Panels live in 2 x kMaxGroup slots (slot = pivot block mod 8): chain nb0 and the next group's chains write the other half
-    // while this group's launches still read theirs; a half is rewritten two groups later, behind the events above.
-    const int group_env = [] { const char *e = experiment_env("LPVS_FACTOR_GROUP"); return e ? atoi(e) : 0; }();   // 1 .. 4 panels per pass (diagnostic)
-    // Measured at np = 8192 (tools/factor_ab3.sh): 1 panel per pass 16.2 ms, 2: 14.0, 3: 15.0, 4: 15.4 (round 2's schedule: 17.8).  Deeper
-    // passes amortise the per-tile overhead further, but the side stream's share of the matrix work grows with the group (bands of
-    // depth 128 .. 128 (mg - 1) and a priority launch of mg bands: 15 % of the flops at mg = 2, 30 % at mg = 4) and its workgroups
-    // queue behind 170-us workgroups of the main pass: from mg = 3 the side stream is the critical path again.
-    // From np = 12288 the main pass is long enough to cover a four-step side chain: 84.5 ms with groups of four (and the 8-pivot
-    // stages below) against 89.6 with pairs at np = 16384 (tools/factor_ab4.sh).
-    const int mgmax = group_env >= 1 && group_env <= kMaxGroup ? group_env : (np >= 12288 ? 4 : 2);
-    const bool groups_on = [] { const char *e = experiment_env("LPVS_FACTOR_SCHEME"); return !(e && std::string(e) == "steps"); }();
-    const bool fused_chain = [] { const char *e = experiment_env("LPVS_CHAIN"); return !(e && std::string(e) == "split"); }();
-    const bool mfma_pivot = [] { const char *e = experiment_env("LPVS_PIVOT"); return !(e && std::string(e) == "regs"); }();   // regs: the register kernel
-    if (la && groups_on && single_wg_pivot && kw_outer == 128 && np >= 2048 && np % 128 == 0 && ldp == np) {
-        hipStream_t side = aux->side;
-        // LPVS_RU_STAGE=8: 8-pivot LDS stages (32 KB per workgroup) and a register budget for three workgroups per CU
-        // (np = 8192: 14.65 ms against 13.3 with 16-pivot stages and two workgroups per CU; np = 16384: 84.5 against 86.5 -- default from 12288)
-        const int stage_env = [] { const char *e = experiment_env("LPVS_RU_STAGE"); return e ? atoi(e) : 0; }();
-        const bool bk8 = stage_env == 8 || (stage_env != 16 && np >= 12288);
-        const size_t ldsm = bk8 ? lds / 2 : lds;
-        auto ru_kernel = bk8 ? rank_updatem_kernel<8, 3> : rank_updatem_kernel<16, 2>;
-        LPVS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ru_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsm));
-        const int nblocks = (int)(np / 128);
-        auto slotB = [&](int blk) { return work + (int64_t)(blk & (2 * kMaxGroup - 1)) * (2 * 128 * ldp); };
-        auto slotC = [&](int blk) { return slotB(blk) + 128 * ldp; };
-        // The one-workgroup pivot inverse asks for the rest of a CU's LDS (unused): it can then only be placed on a CU that holds no other
-        // workgroup -- one of those the deep passes' CU mask leaves out -- and nothing joins it there (np = 8192: 13.5 -> 13.2 ms; with three
-        // update workgroups per CU, from np = 12288, it waits too long for an empty CU: 84.5 -> 86.3 ms at 16384).  LPVS_PIVOT_ALONE=0/1.
-        const int alone_env = [] { const char *e = experiment_env("LPVS_PIVOT_ALONE"); return e ? atoi(e) : -1; }();
-        const bool pivot_alone = alone_env >= 0 ? alone_env != 0 : np < 12288;
-        const size_t pivot_pad = (pivot_alone && aux->bulk) ? (size_t)(160 * 1024 - 40 * 1024) : 0;
-        if (pivot_pad) LPVS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(pivot_inverse_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pivot_pad));
-        auto chain128 = [&](int blk, hipStream_t st) {
-            const int64_t k0 = (int64_t)blk * 128;
-            if (mfma_pivot) hipLaunchKernelGGL(pivot_inverse_mfma_kernel, dim3(1), dim3(256), pivot_pad, st, A, np, k0, P, status_dev);
-            else hipLaunchKernelGGL(pivot_inverse_kernel<128>, dim3(1), dim3(192), 0, st, A, np, k0, P, status_dev);
-            if (fused_chain) {
-                hipLaunchKernelGGL(panel_fused_kernel, dim3((unsigned)(ldp / 16)), dim3(256), 0, st, A, np, ldp, k0, (const double *)P, slotB(blk), slotC(blk));
-            } else {
-                hipLaunchKernelGGL(panel_gather_kernel, dim3((unsigned)(ldp / 64)), dim3(256), 0, st, A, np, ldp, k0, 128, slotB(blk));
-                hipLaunchKernelGGL(panel_gemm_kernel, dim3((unsigned)(ldp / 64)), dim3(256), 0, st, A, np, ldp, k0, 128, P, slotB(blk), slotC(blk));
-            }
-        };
-        auto group_of = [&](int kb, int mg) {
-            RuGroup g{};
-            for (int i = 0; i < kMaxGroup; ++i) { g.Ck[i] = slotC(kb + (i < mg ? i : 0)); g.Bk[i] = slotB(kb + (i < mg ? i : 0)); }
-            g.kb = kb; g.mg = mg;
-            return g;
-        };
-        const int nr = (int)(np / RU_TM);
-        // band launches on 64 x 64 tiles (rank_updateb_kernel) below np = 8192: 4.31 -> 3.98 ms at 4096; from 8192 the deep pass is the
-        // critical path either way (side chain 445 -> 390 us per pair against a 393-us deep pass; 12.9-13.1 ms with 128 x 128 band tiles,
-        // 13.1-13.3 with 64 x 64).  LPVS_BAND_TILE=64|128 forces one.
-        const int band_env = [] { const char *e = experiment_env("LPVS_BAND_TILE"); return e ? atoi(e) : 0; }();
-        const bool band64 = band_env == 64 || (band_env != 128 && np < 8192);
-        auto launch_bands = [&](hipStream_t st, const RuGroup &g, int e0, int nsl, int band) {   // the tiles of bands e0 .. e0 + nsl - 1
-            if (band64)
-                hipLaunchKernelGGL(rank_updateb_kernel<16>, dim3((unsigned)(4 * nr * nsl)), dim3(256), 2 * 16 * 128 * sizeof(double), st, A, np, ldp, g, e0, nsl, band);
-            else
-                hipLaunchKernelGGL(ru_kernel, dim3((unsigned)(nr * nsl)), dim3(RU_THREADS), ldsm, st, A, np, ldp, g, tiles, (int)ht.size(), 1, e0, nsl, band, 0, 0);
-        };
-        auto launch_rest = [&](hipStream_t st, const RuGroup &g, int skip0, int nskip) {
-            hipLaunchKernelGGL(ru_kernel, dim3((unsigned)ht.size()), dim3(RU_THREADS), ldsm, st, A, np, ldp, g, tiles, (int)ht.size(), 0, 0, 0, -1, skip0, nskip);
-        };
-        hipStream_t mb = aux->bulk ? aux->bulk : s;             // the deep passes' stream (CU-masked: see SweepAux::ensure)
-        LPVS_HIP(hipEventRecord(aux->rest, s));                 // A is ready on the caller's stream
-        LPVS_HIP(hipStreamWaitEvent(side, aux->rest, 0));
-        if (mb != s) LPVS_HIP(hipStreamWaitEvent(mb, aux->rest, 0));
-        chain128(0, side);
-        bool rest_pending = false;                               // a rest launch of an earlier group is recorded in aux->second
-        for (int kb = 0; kb < nblocks;) {
-            const int mg = nblocks - kb < mgmax ? nblocks - kb : mgmax, nb0 = kb + mg;
-            const int mgn = nblocks - nb0 < mgmax ? nblocks - nb0 : mgmax;       // bands of the next group (0: this is the last)
-            const RuGroup g = group_of(kb, mg);
-            for (int j = 1; j < mg; ++j) {
-                launch_bands(side, g, kb + j, 1, j);             // band j += the group's earlier panels, then its chain
-                chain128(kb + j, side);
-            }
-            LPVS_HIP(hipEventRecord(aux->panel, side));         // the group's panels are complete
-            LPVS_HIP(hipStreamWaitEvent(mb, aux->panel, 0));
-            launch_rest(mb, g, nb0, mgn);
-            if (mgn > 0) {
-                if (rest_pending) LPVS_HIP(hipStreamWaitEvent(side, aux->second, 0));   // the previous group's rest wrote the tiles of these bands
-                launch_bands(side, g, nb0, mgn, -1);             // priority: the next group's pivot bands
-                chain128(nb0, side);
-            }
-            LPVS_HIP(hipEventRecord(aux->second, mb));          // this group's rest
-            rest_pending = true;
-            LPVS_HIP(hipGetLastError());
-            kb = nb0;
-        }
-        if (mb != s) {
-            LPVS_HIP(hipEventRecord(aux->bulkdone, mb));
-            LPVS_HIP(hipStreamWaitEvent(s, aux->bulkdone, 0));
-        }
-        LPVS_HIP(hipEventRecord(aux->rest, side));              // neither helper stream has anything pending when the caller goes on
-        LPVS_HIP(hipStreamWaitEvent(s, aux->rest, 0));
-        return LPVS_OK;
-    }
+constexpr size_t kRuLds = sizeof(double) * 2 * RU_BK * (RU_TM + RU_TN);
 
-    if (!la) {
-        for (int64_t k0 = 0; k0 < np; k0 += kw_outer) {
-            chain(k0, panelbuf[0], panelbuf[0] + KW * ldp, s);
-            update(k0, panelbuf[0], panelbuf[0] + KW * ldp, 0, s);
-            LPVS_HIP(hipGetLastError());
-        }
-        return LPVS_OK;
+// ---- steps: one outer pivot block per pass of rank_update_kernel ---------------------------------------------------------------------
+static int step_width(const FactorCtx &c, const FactorPlan &plan, int64_t k0) {   // with 256: 128 for a ragged last block
+    return (int)(c.np - k0 < plan.kw_outer ? c.np - k0 : plan.kw_outer);
+}
+
+static void step_chain(const FactorCtx &c, const FactorPlan &plan, int64_t k0, double *Bk, double *Ck, hipStream_t st) {
+    const int kw = step_width(c, plan, k0);
+    if (plan.pivot == PivotKernel::regs && kw == 128) {
+        hipLaunchKernelGGL(pivot_inverse_kernel<128>, dim3(1), dim3(192), 0, st, c.A, c.np, k0, c.P, c.status_dev);
+    } else {
+        hipLaunchKernelGGL(pivot_extract_kernel, dim3((unsigned)kw), dim3(256), 0, st, c.A, c.np, k0, kw, c.P);
+        sweep64(c.P, kw, 1, c.inner, c.status_dev, st);
+        hipLaunchKernelGGL(negate_mirror_kernel, dim3((unsigned)(kw / 32), (unsigned)(kw / 32), 1u), dim3(256), 0, st, c.P, (int64_t)kw);
     }
-    hipStream_t side = aux->side;
-    LPVS_HIP(hipEventRecord(aux->rest, s));                 // A is ready on the main stream
-    LPVS_HIP(hipStreamWaitEvent(side, aux->rest, 0));
-    chain(0, panelbuf[0], panelbuf[0] + KW * ldp, side);
-    LPVS_HIP(hipEventRecord(aux->panel, side));
-    // measured at np = 8192: 18.4 -> 17.8 ms; neutral at 16384, slightly slower at 4096 (5.6 -> 5.8 ms): used from np = 6144
-    const bool depth2 = np >= 6144 && [] { const char *e = experiment_env("LPVS_LOOKAHEAD"); return !(e && e[0] == '1'); }();   // LPVS_LOOKAHEAD=1: depth one
-    if (depth2) {
-        // Depth-2 look-ahead.  With depth one the main stream alternates  band_k | bulk_k  (the band of step k, which the next
-        // pivot chain waits for, runs alone on the chip and two event hand-overs sit between consecutive bulks: 57 of 286 us
-        // per step at np = 8192; profiles/r02_factor_timeline.txt).  Here the side stream owns everything the pivot chains need
-        // and never blocks the bulk (the second-band launch costs the main stream 38 us, so the step shrinks to 278 us only):
-        //   side:  band_k (tile row / column k+1, needs panel_k and second_{k-1})  ->  chain_{k+1}  ->  panel_{k+1}
-        //   main:  bulk_k = { second band (tile row / column k+2) -> event second_k ;  everything else }   (needs panel_k)
-        // band_k's tiles received the updates of steps < k as the "second band" of step k-1; the side stream may run a whole
-        // step ahead, so the panels rotate through three buffers (chain_{k+1} writes while bulk_{k-1} may still read its own).
-        int cur = 0;
-        for (int64_t k0 = 0; k0 < np; k0 += kw_outer, cur = (cur + 1) % 3) {
-            double *Bk = panelbuf[cur], *Ck = Bk + KW * ldp;
-            const int64_t n0 = k0 + width(k0);
-            const bool next = n0 < np;
-            LPVS_HIP(hipStreamWaitEvent(s, aux->panel, 0));     // panel k (captured before the side stream re-records the event)
-            if (next) {
-                if (k0 > 0) LPVS_HIP(hipStreamWaitEvent(side, aux->second, 0));   // second band of step k-1 = this step's band tiles
-                update(k0, Bk, Ck, 1, side);
-                double *Bn = panelbuf[(cur + 1) % 3];
-                chain(n0, Bn, Bn + KW * ldp, side);
-                LPVS_HIP(hipEventRecord(aux->panel, side));
-                if (n0 + width(n0) < np) update(k0, Bk, Ck, 3, s);
-                LPVS_HIP(hipEventRecord(aux->second, s));
-                update(k0, Bk, Ck, 4, s);
-            } else {
-                update(k0, Bk, Ck, 0, s);
-            }
-            LPVS_HIP(hipGetLastError());
-        }
-        LPVS_HIP(hipEventRecord(aux->rest, side));              // the side stream has nothing pending when the caller goes on
-        LPVS_HIP(hipStreamWaitEvent(s, aux->rest, 0));
-        return LPVS_OK;
+    hipLaunchKernelGGL(panel_gather_kernel, dim3((unsigned)(c.ldp / 64)), dim3(256), 0, st, c.A, c.np, c.ldp, k0, kw, Bk);
+    hipLaunchKernelGGL(panel_gemm_kernel, dim3((unsigned)(c.ldp / (32 * (4 / (kw / 64))))), dim3(256), 0, st, c.A, c.np, c.ldp, k0, kw, c.P, Bk, Ck);
+}
+
+static void step_update(const FactorCtx &c, const FactorPlan &plan, int64_t k0, const double *Bk, const double *Ck, int which, hipStream_t st) {
+    const int kw = step_width(c, plan, k0);
+    const int64_t n0 = k0 + kw;
+    const int nw = n0 < c.np ? step_width(c, plan, n0) : 0;
+    const int64_t n1 = n0 + nw;
+    const int nw1 = (nw > 0 && n1 < c.np) ? step_width(c, plan, n1) : 0;
+    // a 128-wide band is one tile row + one tile column: launch just those (32k early-exit workgroups cost 0.3 ms at np = 32768)
+    const bool direct1 = which == 1 && nw % RU_TM == 0 && nw > 0;
+    const bool direct3 = which == 3 && nw1 % RU_TM == 0 && nw1 > 0;
+    const unsigned grid = direct1 ? (unsigned)(c.np / RU_TM * (nw / RU_TM)) : (direct3 ? (unsigned)(c.np / RU_TM * (nw1 / RU_TM)) : (unsigned)c.ntiles);
+    const int band_tile = direct1 ? (int)(n0 / RU_TM) : (direct3 ? (int)(n1 / RU_TM) : -1);
+    hipLaunchKernelGGL(rank_update_kernel, dim3(grid), dim3(RU_THREADS), kRuLds, st, c.A, c.np, c.ldp, k0,
+                       kw, Ck, Bk, c.tiles, c.ntiles, which, n0, nw, band_tile, n1, nw1);
+}
+
+static int32_t factor_steps_serial(const FactorCtx &c, const FactorPlan &plan) {
+    for (int64_t k0 = 0; k0 < c.np; k0 += plan.kw_outer) {
+        step_chain(c, plan, k0, c.stepB(0), c.stepC(0), c.s);
+        step_update(c, plan, k0, c.stepB(0), c.stepC(0), 0, c.s);
+        LPVS_HIP(hipGetLastError());
     }
+    return LPVS_OK;
+}
+
+// both look-ahead depths start alike: the first chain on the side stream, behind the caller's stream
+static int32_t steps_first_chain(const FactorCtx &c, const FactorPlan &plan) {
+    LPVS_HIP(hipEventRecord(c.aux->rest, c.s));                 // A is ready on the main stream
+    LPVS_HIP(hipStreamWaitEvent(c.aux->side, c.aux->rest, 0));
+    step_chain(c, plan, 0, c.stepB(0), c.stepC(0), c.aux->side);
+    LPVS_HIP(hipEventRecord(c.aux->panel, c.aux->side));
+    return LPVS_OK;
+}
+
+static int32_t factor_steps_depth1(const FactorCtx &c, const FactorPlan &plan) {
+    hipStream_t s = c.s, side = c.aux->side;
+    SweepAux *aux = c.aux;
+    LPVS_TRY(steps_first_chain(c, plan));
     int cur = 0;
-    for (int64_t k0 = 0; k0 < np; k0 += kw_outer, cur ^= 1) {
-        double *Bk = panelbuf[cur], *Ck = Bk + KW * ldp;
-        const int64_t n0 = k0 + width(k0);
-        const bool next = n0 < np;
+    for (int64_t k0 = 0; k0 < c.np; k0 += plan.kw_outer, cur ^= 1) {
+        double *Bk = c.stepB(cur), *Ck = c.stepC(cur);
+        const int64_t n0 = k0 + step_width(c, plan, k0);
+        const bool next = n0 < c.np;
         LPVS_HIP(hipStreamWaitEvent(s, aux->panel, 0));     // panel k (captured before the side stream re-records the event)
         if (next) {
             LPVS_HIP(hipStreamWaitEvent(side, aux->rest, 0));   // bulk of U_{k-1}
-            update(k0, Bk, Ck, 1, side);
+            step_update(c, plan, k0, Bk, Ck, 1, side);
             LPVS_HIP(hipEventRecord(aux->band, side));
-            chain(n0, panelbuf[cur ^ 1], panelbuf[cur ^ 1] + KW * ldp, side);
+            step_chain(c, plan, n0, c.stepB(cur ^ 1), c.stepC(cur ^ 1), side);
             LPVS_HIP(hipEventRecord(aux->panel, side));
             // the bulk starts when the band is done: the one-workgroup pivot inverse (which needs most of a CU's
             // registers) is then dispatched onto an empty chip instead of starving behind the bulk's workgroups
             LPVS_HIP(hipStreamWaitEvent(s, aux->band, 0));
         }
-        update(k0, Bk, Ck, next ? 2 : 0, s);
+        step_update(c, plan, k0, Bk, Ck, next ? 2 : 0, s);
         LPVS_HIP(hipEventRecord(aux->rest, s));
         LPVS_HIP(hipGetLastError());
     }
     return LPVS_OK;
 }
 
+// Depth-2 look-ahead.  With depth one the main stream alternates  band_k | bulk_k  (the band of step k, which the next
+// pivot chain waits for, runs alone on the chip and two event hand-overs sit between consecutive bulks: 57 of 286 us
+// per step at np = 8192; profiles/r02_factor_timeline.txt).  Here the side stream owns everything the pivot chains need
+// and never blocks the bulk (the second-band launch costs the main stream 38 us, so the step shrinks to 278 us only):
+//   side:  band_k (tile row / column k+1, needs panel_k and second_{k-1})  ->  chain_{k+1}  ->  panel_{k+1}
+//   main:  bulk_k = { second band (tile row / column k+2) -> event second_k ;  everything else }   (needs panel_k)
+// band_k's tiles received the updates of steps < k as the "second band" of step k-1; the side stream may run a whole
+// step ahead, so the panels rotate through three buffers (chain_{k+1} writes while bulk_{k-1} may still read its own).
+static int32_t factor_steps_depth2(const FactorCtx &c, const FactorPlan &plan) {
+    hipStream_t s = c.s, side = c.aux->side;
+    SweepAux *aux = c.aux;
+    LPVS_TRY(steps_first_chain(c, plan));
+    int cur = 0;
+    for (int64_t k0 = 0; k0 < c.np; k0 += plan.kw_outer, cur = (cur + 1) % kStepPairs) {
+        double *Bk = c.stepB(cur), *Ck = c.stepC(cur);
+        const int64_t n0 = k0 + step_width(c, plan, k0);
+        const bool next = n0 < c.np;
+        LPVS_HIP(hipStreamWaitEvent(s, aux->panel, 0));     // panel k (captured before the side stream re-records the event)
+        if (next) {
+            if (k0 > 0) LPVS_HIP(hipStreamWaitEvent(side, aux->second, 0));   // second band of step k-1 = this step's band tiles
+            step_update(c, plan, k0, Bk, Ck, 1, side);
+            const int nxt = (cur + 1) % kStepPairs;
+            step_chain(c, plan, n0, c.stepB(nxt), c.stepC(nxt), side);
+            LPVS_HIP(hipEventRecord(aux->panel, side));
+            if (n0 + step_width(c, plan, n0) < c.np) step_update(c, plan, k0, Bk, Ck, 3, s);
+            LPVS_HIP(hipEventRecord(aux->second, s));
+            step_update(c, plan, k0, Bk, Ck, 4, s);
+        } else {
+            step_update(c, plan, k0, Bk, Ck, 0, s);
+        }
+        LPVS_HIP(hipGetLastError());
+    }
+    LPVS_HIP(hipEventRecord(aux->rest, side));              // the side stream has nothing pending when the caller goes on
+    LPVS_HIP(hipStreamWaitEvent(s, aux->rest, 0));
+    return LPVS_OK;
+}
+
+// ---- groups of up to four 128-wide steps: the trailing update takes the group's panels in ONE pass (rank_updatem_kernel) --------
+// Per group (pivot blocks kb .. kb + mg - 1; panel kb is ready when the group starts; the next group starts at block nb0):
+//   side:  for j = 1 .. mg-1:  band j += panels [.., j)  ->  chain kb+j        ->  [event panels]
+//          [wait: previous group's rest]  the NEXT group's bands += this group's panels (priority)  ->  chain nb0  (the next group's first panel)
+//   main:  [wait panels]  every tile outside the next group's bands += this group's panels                 ->  [event rest]
+// The side stream (high priority) thus owns everything the pivot chains wait for -- its priority launch shares the chip with the
+// main stream's pass instead of running ahead of it --, and the main stream is one deep pass per group.  Band / priority tiles are
+// disjoint from the rest launch's; the priority tiles were last written by the previous group's rest launch (hence the wait).
+// Panels live in 2 x kMaxGroup slots (slot = pivot block mod 8): chain nb0 and the next group's chains write the other half
+// while this group's launches still read theirs; a half is rewritten two groups later, behind the events above.
+// Deeper passes amortise the per-tile overhead further, but the side stream's share of the matrix work grows with the group (bands of
+// depth 128 .. 128 (mg - 1) and a priority launch of mg bands: 15 % of the flops at mg = 2, 30 % at mg = 4) and its workgroups
+// queue behind 170-us workgroups of the main pass: from mg = 3 the side stream is the critical path again (group_max: factor_plan.h).
+
+// what the plan's kernel choices come to, fixed for one factorisation
+struct GroupKernels {
+    decltype(&rank_updatem_kernel<8, 3>) ru_kernel;   // the deep pass and the 128 x 128 band launches: <8, 3> or <16, 2>
+    size_t ru_lds;
+    size_t pivot_pad;                                  // dynamic LDS the matrix-core pivot kernel asks for and never touches
+};
+
+static int32_t group_kernels(const FactorCtx &c, const FactorPlan &plan, GroupKernels &k) {
+    // 8-pivot LDS stages (32 KB per workgroup) and a register budget for three workgroups per CU
+    const bool bk8 = plan.ru_stage == 8;
+    k.ru_lds = bk8 ? kRuLds / 2 : kRuLds;
+    k.ru_kernel = bk8 ? rank_updatem_kernel<8, 3> : rank_updatem_kernel<16, 2>;
+    LPVS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k.ru_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.ru_lds));
+    // The one-workgroup pivot inverse asks for the rest of a CU's LDS (unused): it can then only be placed on a CU that holds no other
+    // workgroup -- one of those the deep passes' CU mask leaves out -- and nothing joins it there.  Without that mask (a runtime fact,
+    // not a choice of the plan) there is no such CU and nothing is asked for.
+    k.pivot_pad = (plan.pivot_alone && c.aux->bulk) ? (size_t)(160 * 1024 - 40 * 1024) : 0;
+    if (k.pivot_pad) LPVS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(pivot_inverse_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.pivot_pad));
+    return LPVS_OK;
+}
+
+static void group_chain(const FactorCtx &c, const FactorPlan &plan, const GroupKernels &k, int blk, hipStream_t st) {
+    const int64_t k0 = (int64_t)blk * 128;
+    if (plan.pivot == PivotKernel::mfma) hipLaunchKernelGGL(pivot_inverse_mfma_kernel, dim3(1), dim3(256), k.pivot_pad, st, c.A, c.np, k0, c.P, c.status_dev);
+    else hipLaunchKernelGGL(pivot_inverse_kernel<128>, dim3(1), dim3(192), 0, st, c.A, c.np, k0, c.P, c.status_dev);
+    if (plan.fused_chain) {
+        hipLaunchKernelGGL(panel_fused_kernel, dim3((unsigned)(c.ldp / 16)), dim3(256), 0, st, c.A, c.np, c.ldp, k0, (const double *)c.P, c.slotB(blk), c.slotC(blk));
+    } else {
+        hipLaunchKernelGGL(panel_gather_kernel, dim3((unsigned)(c.ldp / 64)), dim3(256), 0, st, c.A, c.np, c.ldp, k0, 128, c.slotB(blk));
+        hipLaunchKernelGGL(panel_gemm_kernel, dim3((unsigned)(c.ldp / 64)), dim3(256), 0, st, c.A, c.np, c.ldp, k0, 128, c.P, c.slotB(blk), c.slotC(blk));
+    }
+}
+
+static RuGroup group_of(const FactorCtx &c, int kb, int mg) {
+    RuGroup g{};
+    for (int i = 0; i < kMaxGroup; ++i) { g.Ck[i] = c.slotC(kb + (i < mg ? i : 0)); g.Bk[i] = c.slotB(kb + (i < mg ? i : 0)); }
+    g.kb = kb; g.mg = mg;
+    return g;
+}
+
+// the tiles of bands e0 .. e0 + nsl - 1
+static void group_bands(const FactorCtx &c, const FactorPlan &plan, const GroupKernels &k, hipStream_t st, const RuGroup &g, int e0, int nsl, int band) {
+    const int nr = (int)(c.np / RU_TM);
+    if (plan.band_tile == 64)
+        hipLaunchKernelGGL(rank_updateb_kernel<16>, dim3((unsigned)(4 * nr * nsl)), dim3(256), 2 * 16 * 128 * sizeof(double), st, c.A, c.np, c.ldp, g, e0, nsl, band);
+    else
+        hipLaunchKernelGGL(k.ru_kernel, dim3((unsigned)(nr * nsl)), dim3(RU_THREADS), k.ru_lds, st, c.A, c.np, c.ldp, g, c.tiles, c.ntiles, 1, e0, nsl, band, 0, 0);
+}
+
+static void group_rest(const FactorCtx &c, const GroupKernels &k, hipStream_t st, const RuGroup &g, int skip0, int nskip) {
+    hipLaunchKernelGGL(k.ru_kernel, dim3((unsigned)c.ntiles), dim3(RU_THREADS), k.ru_lds, st, c.A, c.np, c.ldp, g, c.tiles, c.ntiles, 0, 0, 0, -1, skip0, nskip);
+}
+
+static int32_t factor_groups(const FactorCtx &c, const FactorPlan &plan) {
+    GroupKernels k{};
+    LPVS_TRY(group_kernels(c, plan, k));
+    SweepAux *aux = c.aux;
+    hipStream_t s = c.s, side = aux->side;
+    hipStream_t mb = aux->bulk ? aux->bulk : s;             // the deep passes' stream (CU-masked: see SweepAux::ensure)
+    const int nblocks = (int)(c.np / 128), mgmax = plan.group_max;
+    LPVS_HIP(hipEventRecord(aux->rest, s));                 // A is ready on the caller's stream
+    LPVS_HIP(hipStreamWaitEvent(side, aux->rest, 0));
+    if (mb != s) LPVS_HIP(hipStreamWaitEvent(mb, aux->rest, 0));
+    group_chain(c, plan, k, 0, side);
+    bool rest_pending = false;                               // a rest launch of an earlier group is recorded in aux->second
+    for (int kb = 0; kb < nblocks;) {
+        const int mg = nblocks - kb < mgmax ? nblocks - kb : mgmax, nb0 = kb + mg;
+        const int mgn = nblocks - nb0 < mgmax ? nblocks - nb0 : mgmax;       // bands of the next group (0: this is the last)
+        const RuGroup g = group_of(c, kb, mg);
+        for (int j = 1; j < mg; ++j) {
+            group_bands(c, plan, k, side, g, kb + j, 1, j);      // band j += the group's earlier panels, then its chain
+            group_chain(c, plan, k, kb + j, side);
+        }
+        LPVS_HIP(hipEventRecord(aux->panel, side));         // the group's panels are complete
+        LPVS_HIP(hipStreamWaitEvent(mb, aux->panel, 0));
+        group_rest(c, k, mb, g, nb0, mgn);
+        if (mgn > 0) {
+            if (rest_pending) LPVS_HIP(hipStreamWaitEvent(side, aux->second, 0));   // the previous group's rest wrote the tiles of these bands
+            group_bands(c, plan, k, side, g, nb0, mgn, -1);      // priority: the next group's pivot bands
+            group_chain(c, plan, k, nb0, side);
+        }
+        LPVS_HIP(hipEventRecord(aux->second, mb));          // this group's rest
+        rest_pending = true;
+        LPVS_HIP(hipGetLastError());
+        kb = nb0;
+    }
+    if (mb != s) {
+        LPVS_HIP(hipEventRecord(aux->bulkdone, mb));
+        LPVS_HIP(hipStreamWaitEvent(s, aux->bulkdone, 0));
+    }
+    LPVS_HIP(hipEventRecord(aux->rest, side));              // neither helper stream has anything pending when the caller goes on
+    LPVS_HIP(hipStreamWaitEvent(s, aux->rest, 0));
+    return LPVS_OK;
+}
+
+// carves up the workspace, uploads the tile list and runs the plan's schedule
+static int32_t spd_inverse_two_level(double *A, int64_t np, double *work, int *status_dev, hipStream_t s, SweepAux *aux, const FactorPlan &plan) {
+    FactorCtx c{};
+    c.A = A; c.np = np; c.ldp = round_up(np, RU_TN);
+    c.panels = work; c.P = work + kPanelRows * c.ldp; c.inner = c.P + KW * KW;
+    c.tiles = reinterpret_cast<int2 *>(c.inner + sweep64_work_doubles(KW));
+    c.status_dev = status_dev; c.s = s; c.aux = aux;
+    const std::vector<int2> &ht = ru_tiles(np);   // persistent host copy: the async upload may outlive this call
+    c.ntiles = (int)ht.size();
+    LPVS_HIP(hipMemcpyAsync(c.tiles, ht.data(), sizeof(int2) * ht.size(), hipMemcpyHostToDevice, s));
+    LPVS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&rank_update_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRuLds));
+    if (plan.schedule != FactorSchedule::steps_serial) LPVS_TRY(aux->ensure());
+    switch (plan.schedule) {
+    case FactorSchedule::groups: return factor_groups(c, plan);
+    case FactorSchedule::steps_depth2: return factor_steps_depth2(c, plan);
+    case FactorSchedule::steps_depth1: return factor_steps_depth1(c, plan);
+    case FactorSchedule::steps_serial: break;
+    }
+    return factor_steps_serial(c, plan);
+}
+
 // nbatch independent matrices A + q*np*np; work holds nbatch * spd_inverse_work_bytes(np); status_dev nbatch ints
 static int32_t spd_inverse_impl(double *A, int64_t np, int nbatch, double *work, int *status_dev, hipStream_t s, SweepAux *aux) {
     if (np % 128 != 0) { set_error("spd_inverse: np=%lld not a multiple of 128", (long long)np); return LPVS_ESTATE; }
     LPVS_HIP(hipMemsetAsync(status_dev, 0, sizeof(int) * (size_t)nbatch, s));
-    const bool two_level_on = [] { const char *e = experiment_env("LPVS_FACTOR"); return !(e && std::string(e) == "sweep64"); }();
-    if (nbatch == 1 && np >= kTwoLevelMinNp && two_level_on) {
-        LPVS_TRY(spd_inverse_two_level(A, np, work, status_dev, s, aux));
+    // read per call, never cached: tests and the A/B tools switch the knobs between calls
+    const FactorPlan plan = factor_plan(np, nbatch, aux != nullptr, factor_knobs_from(experiment_env));
+    if (plan.level == FactorLevel::two) {
+        LPVS_TRY(spd_inverse_two_level(A, np, work, status_dev, s, aux, plan));
     } else {
         sweep64(A, np, nbatch, work, status_dev, s);
         LPVS_HIP(hipGetLastError());
