@@ -480,6 +480,42 @@ int mp_mode_for(const lpvs_problem *h) {
     return kMpMixed;   // (several right-hand sides: diagonal tiles always float-head; lpvs_admm_init)
 }
 
+// the tile-format bytes behind the 6-byte elements of nmat packed inverses (windows_plan.h: packed_layout)
+unsigned char *mp_tile_types(const DevBuf &Mp, int64_t np, size_t nmat) { return Mp.as<unsigned char>() + packed_layout(np, 6, nmat).elems_bytes; }
+
+// LPVS_NIB_PERIOD, LPVS_NIB_RAMP (experiments): refresh period of the stale nibble product (0: none, the 36-bit reads) and the ramp that
+// makes it denser while the right-hand side still moves fast -- after every launch up to 15, every 2nd up to 31, 4th up to 63, ..., 32nd
+// from 256 on (103 refreshes in 2000 iterations; u at cfg3 after 200 iterations 1.75e-10 from the exact iterate instead of 3.9e-10 --
+// 36-bit reads: 1.40e-10)
+struct NibKnobs { int period = 32, ramp = 8; };
+NibKnobs nib_knobs() {
+    NibKnobs k;
+    if (const char *e = experiment_env("LPVS_NIB_PERIOD")) k.period = atoi(e) > 0 ? atoi(e) : 0;
+    if (const char *e = experiment_env("LPVS_NIB_RAMP")) k.ramp = atoi(e) > 0 ? atoi(e) : 0;
+    return k;
+}
+
+// parameter checks of a sparse job: one copy for the handle entry points and the window engine
+int32_t check_prox(int kind, int64_t group_len) {
+    if (kind < LPVS_PROX_L1 || kind > LPVS_PROX_GROUP_L2) { set_error("unknown prox kind %d", kind); return LPVS_EUNSUPPORTED; }
+    if (kind == LPVS_PROX_GROUP_L2 && group_len <= 0) { set_error("group_len must be positive"); return LPVS_EARGUMENT; }
+    if (kind == LPVS_PROX_GROUP_L2 && group_len > 8192) { set_error("group_len > 8192 is not supported by the device prox"); return LPVS_EUNSUPPORTED; }
+    return LPVS_OK;
+}
+int32_t check_mu_and_sign(double mu, int linear_sign) {
+    if (!(mu >= 0 && mu <= 1)) { set_error("μ should be ≤ 1"); return LPVS_EASSERT; }  // src/lasso.jl:143
+    if (mu == 0) { set_error("mu = 0 makes the x-update singular"); return LPVS_ENUMERIC; }
+    if (linear_sign != 1 && linear_sign != -1) { set_error("linear_sign must be +1 or -1"); return LPVS_EARGUMENT; }
+    return LPVS_OK;
+}
+
+// count host doubles -> an output of the caller's, which may live on the host or on a device (NULL: not wanted)
+int32_t copy_out(double *dst, const double *src, size_t count) {
+    if (!dst) return LPVS_OK;
+    if (is_device_ptr(dst)) { LPVS_HIP(hipMemcpy(dst, src, sizeof(double) * count, hipMemcpyHostToDevice)); } else memcpy(dst, src, sizeof(double) * count);
+    return LPVS_OK;
+}
+
 AdmmParams make_params(const lpvs_problem *h) {
     const bool sym = h->np >= kSymmetricMinNp;
     AdmmParams p{h->M.as<double>(), h->np, h->n, h->bs.as<double>(), h->x.as<double>(), h->z.as<double>(), h->u.as<double>(),
@@ -487,13 +523,13 @@ AdmmParams make_params(const lpvs_problem *h) {
                  h->scratch.as<double>(), h->part.as<double>(), sym ? h->Mp.as<double>() : nullptr, (int)h->ns};
     p.mp_f32 = sym && h->Mp_mode == kMpF32 ? 1 : 0;
     p.mp_split = sym && (h->Mp_mode == kMpSplit || h->Mp_mode == kMpMixed) ? 1 : 0;
-    p.mp_types = sym && h->Mp_mode == kMpMixed ? h->Mp.as<unsigned char>() + 6 * symv_packed_doubles(h->np) : nullptr;
+    p.mp_types = sym && h->Mp_mode == kMpMixed ? mp_tile_types(h->Mp, h->np, 1) : nullptr;
     p.mp_fix32 = p.mp_types != nullptr && (h->Mp_fix_bits <= 32 || h->nib_period > 0) ? 1 : 0;
     p.nib_period = p.mp_types != nullptr ? h->nib_period : 0; p.nib_ramp = h->nib_ramp; p.xb_corr = h->xb_corr.as<double>(); p.nib_rhs = h->nib_rhs.as<double>(); p.nib_part = h->nib_part.as<double>(); p.nib_acc = h->nib_acc.as<long long>();
     p.xb = sym && h->offset_form ? h->xb.as<double>() : nullptr;
     p.fi = sym && h->offset_form && h->ns == 1 && (h->Mp_mode == kMpMixed || h->Mp_mode == kMpF32) && h->fi.p ? h->fi.as<double>() : nullptr;
     p.fi_R = h->fi_R; p.fi_xbmax = h->fi_xbmax;
-    p.fi_prefetch_all = sym && h->Mp_mode == kMpMixed && h->Mp_fixed_tiles == (int64_t)(symv_packed_doubles(h->np) / (128 * 128)) ? 1 : 0;
+    p.fi_prefetch_all = sym && h->Mp_mode == kMpMixed && h->Mp_fixed_tiles == (int64_t)packed_tiles(h->np) ? 1 : 0;
     p.opt_iteration = h->opt[LPVS_OPT_ITERATION]; p.opt_nt_loads = h->opt[LPVS_OPT_NT_LOADS];
     {   // single problems on the one-launch iteration: mirrored tile order on odd launches (LPVS_TILE_ORDER=forward: the same order every launch, for A/B runs; read per call)
         const char *e = experiment_env("LPVS_TILE_ORDER");
@@ -645,7 +681,7 @@ int32_t lpvs_fourier_regressor_f64(const double *t, int64_t N, const double *f, 
     if (zerofreq) *zerofreq = z;
     if (lpvs_device_count() == 0) { set_error("no HIP device visible (the gfx950 path has no CPU fallback)"); return LPVS_EDEVICE; }
     hipStream_t s = nullptr;
-    const int64_t nreg = z ? 2 * Nf - 1 : 2 * Nf;
+    const int64_t nreg = fourier_regressors(Nf, z != 0);
     DevArg dt, df; DevOut dA;
     LPVS_TRY(dt.set(t, N, s)); LPVS_TRY(df.set(f, Nf, s)); LPVS_TRY(dA.set(A_out, N * nreg));
     LPVS_TRY(launch_fourier_regressor_colmajor(dt.p, N, df.p, Nf, (int)z, dA.p, s));
@@ -1016,7 +1052,7 @@ int32_t lpvs_problem_create_fourier_f64(const double *y, const double *t, int64_
     LPVS_TRY(problem_begin(device, out, &h));
     struct Guard { lpvs_problem *h; ~Guard() { delete h; } } guard{h};
     hipStream_t s = h->stream;
-    h->kind = 0; h->N = N; h->Nf = Nf; h->zerofreq = zf; h->n = zf ? 2 * Nf - 1 : 2 * Nf;
+    h->kind = 0; h->N = N; h->Nf = Nf; h->zerofreq = zf; h->n = fourier_regressors(Nf, zf != 0);
     DevArg dt, df;
     LPVS_TRY(dt.set(t, N, s)); LPVS_TRY(df.set(f, Nf, s));
     // structured Gram when T(2pi)*f is an arithmetic progression (default_freqs and every grid of the reference's tests)
@@ -1192,9 +1228,7 @@ int32_t lpvs_problem_solve_ridge_f64(lpvs_problem *h, double ridge, double *x_ou
 
 int32_t lpvs_problem_set_prox(lpvs_problem *h, int32_t kind, double param, int64_t group_len) {
     if (!h) { set_error("NULL handle"); return LPVS_EARGUMENT; }
-    if (kind < LPVS_PROX_L1 || kind > LPVS_PROX_GROUP_L2) { set_error("unknown prox kind %d", kind); return LPVS_EUNSUPPORTED; }
-    if (kind == LPVS_PROX_GROUP_L2 && group_len <= 0) { set_error("group_len must be positive"); return LPVS_EARGUMENT; }
-    if (kind == LPVS_PROX_GROUP_L2 && group_len > 8192) { set_error("group_len > 8192 is not supported by the device prox"); return LPVS_EUNSUPPORTED; }
+    LPVS_TRY(check_prox(kind, group_len));
     h->prox_kind = kind; h->prox_param = param; h->group_len = group_len;
     h->drop_graph();   // kernel parameters are baked into the captured graph
     return LPVS_OK;
@@ -1202,9 +1236,7 @@ int32_t lpvs_problem_set_prox(lpvs_problem *h, int32_t kind, double param, int64
 
 int32_t lpvs_admm_init_f64(lpvs_problem *h, const double *x0, double mu, double tol, int32_t linear_sign) {
     if (!h) { set_error("NULL handle"); return LPVS_EARGUMENT; }
-    if (!(mu >= 0 && mu <= 1)) { set_error("μ should be ≤ 1"); return LPVS_EASSERT; }  // src/lasso.jl:143
-    if (mu == 0) { set_error("mu = 0 makes the x-update singular"); return LPVS_ENUMERIC; }
-    if (linear_sign != 1 && linear_sign != -1) { set_error("linear_sign must be +1 or -1"); return LPVS_EARGUMENT; }
+    LPVS_TRY(check_mu_and_sign(mu, linear_sign));
     LPVS_HIP(hipSetDevice(h->device));
     hipStream_t s = h->stream;
     h->drop_graph();
@@ -1245,12 +1277,8 @@ int32_t lpvs_admm_init_f64(lpvs_problem *h, const double *x0, double mu, double 
     const bool read32 = h->ns == 1 && !h->f32 && h->xcorr() && (st_asked == 0 || st_asked == LPVS_STORAGE_MIXED32);
     int fix_bits = 36;                               // (packed with all 36 bits: the nibble planes feed the stale nibble product)
     if (const char *e = experiment_env("LPVS_FIX_BITS")) fix_bits = atoi(e) >= 20 && atoi(e) <= 36 ? atoi(e) : fix_bits;
-    h->nib_period = read32 ? 32 : 0;                 // LPVS_NIB_PERIOD: refresh period of the stale nibble product (experiments; 0: no stale product, the 36-bit reads)
-    if (const char *e = read32 ? experiment_env("LPVS_NIB_PERIOD") : nullptr) h->nib_period = atoi(e) > 0 ? atoi(e) : 0;
-    // ... denser while the right-hand side still moves fast: after every launch up to 15, every 2nd up to 31, 4th up to 63, ..., 32nd from 256 on
-    // (103 refreshes in 2000 iterations; u at cfg3 after 200 iterations 1.75e-10 from the exact iterate instead of 3.9e-10 -- 36-bit reads: 1.40e-10)
-    h->nib_ramp = read32 ? 8 : 0;
-    if (const char *e = read32 ? experiment_env("LPVS_NIB_RAMP") : nullptr) h->nib_ramp = atoi(e) > 0 ? atoi(e) : 0;
+    const NibKnobs nib = read32 ? nib_knobs() : NibKnobs{0, 0};
+    h->nib_period = nib.period; h->nib_ramp = nib.ramp;
     h->Mp_read32 = read32;
     if (h->Mp_valid && h->Mp_mode == kMpMixed && h->Mp_fix_bits != fix_bits) h->Mp_valid = false;   // (the same M packed for the other choice)
     const int mode = mp_mode_for(h);
@@ -1259,18 +1287,18 @@ int32_t lpvs_admm_init_f64(lpvs_problem *h, const double *x0, double mu, double 
         h->Mp_demoted = false;
         bool just_demoted = false;   // set only by the demotion a few lines down: the handle's OLD (Mp_mode, Mp_valid) must not be mistaken for it
         const size_t elt = mode == kMpF32 ? 4 : (mode == kMpSplit || mode == kMpMixed ? 6 : 8);
-        const size_t ntiles = symv_packed_doubles(h->np) / (128 * 128);
-        const size_t need = elt * symv_packed_doubles(h->np) + (mode == kMpMixed ? ((ntiles + 255) / 256) * 256 + 256 : 0);   // + tile types + max|M|
+        const PackedLayout lay = packed_layout(h->np, elt, 1);
+        const size_t ntiles = lay.tiles, need = mode == kMpMixed ? lay.bytes : lay.elems_bytes;   // (mixed: + tile formats + max|M|)
         if (!h->Mp.p || h->Mp.bytes < need) LPVS_TRY(h->Mp.alloc(need));
-        h->Mp_stream_bytes = (double)elt * (double)symv_packed_doubles(h->np);
+        h->Mp_stream_bytes = (double)lay.elems_bytes;
         h->Mp_fixed_tiles = 0; h->Mp_fixed_diag = 0;
         if (mode == kMpF32) LPVS_TRY(launch_pack_tiles_f32(h->M.as<double>(), h->np, h->Mp.as<float>(), s));
         else if (mode == kMpSplit) LPVS_TRY(launch_pack_tiles_split(h->M.as<double>(), h->np, h->Mp.as<unsigned char>(), s));
         else if (mode == kMpMixed) {
-            unsigned char *types = h->Mp.as<unsigned char>() + 6 * symv_packed_doubles(h->np);
+            unsigned char *types = mp_tile_types(h->Mp, h->np, 1);
             // (single-signal handles: the packing pass also leaves the largest absolute row sum of M, which the one-launch iteration's quantum
             // bound needs -- one more pass over the matrix otherwise; the tile partials' buffer and the scratch vector are free here)
-            unsigned long long *amax = reinterpret_cast<unsigned long long *>(types + ((ntiles + 255) / 256) * 256);
+            unsigned long long *amax = reinterpret_cast<unsigned long long *>(h->Mp.as<unsigned char>() + lay.absmax_off);
             const bool want_R = h->ns == 1;
             LPVS_TRY(launch_pack_tiles_mixed(h->M.as<double>(), h->np, h->Mp.as<unsigned char>(), types, amax, s, /*diag_float=*/h->ns > 1,
                                              want_R ? h->part.as<double>() : nullptr, h->n, want_R ? h->scratch.as<double>() : nullptr, fix_bits));
@@ -1281,11 +1309,9 @@ int32_t lpvs_admm_init_f64(lpvs_problem *h, const double *x0, double mu, double 
             if (want_R) LPVS_HIP(hipMemcpyAsync(&rbits, amax + 1, sizeof(rbits), hipMemcpyDeviceToHost, s));
             LPVS_HIP(hipStreamSynchronize(s));
             if (want_R) memcpy(&h->Mp_rowsum, &rbits, sizeof(double));
-            size_t ndiag = 0;
-            for (unsigned char t : ht) { h->Mp_fixed_tiles += t != 0; ndiag += t == 2; }
-            h->Mp_fixed_diag = (int64_t)ndiag;
-            h->Mp_stream_bytes = (double)h->Mp_fixed_tiles * (double)kMixedFixedTileBytes + (double)ndiag * 1024.0 +
-                                 (double)(ntiles - (size_t)h->Mp_fixed_tiles) * (double)kMixedFloatTileBytes;
+            const TileCensus census = tile_census(ht.data(), ntiles);
+            h->Mp_fixed_tiles = (int64_t)census.fixed; h->Mp_fixed_diag = (int64_t)census.diag;
+            h->Mp_stream_bytes = census_stream_bytes(census, /*read32=*/false);
             const size_t nblk_ = (size_t)(h->np / 128);
             if (getenv("LPVS_TRACE")) fprintf(stderr, "[lpvs] mixed packing: %lld of %zu tiles fixed point (%zu diagonal), ns = %lld\n", (long long)h->Mp_fixed_tiles, ntiles, nblk_, (long long)h->ns);
             if (2 * (size_t)h->Mp_fixed_tiles < ntiles) {
@@ -1293,7 +1319,7 @@ int32_t lpvs_admm_init_f64(lpvs_problem *h, const double *x0, double mu, double 
                 // only lose against the plain 6-byte kernel -- store every tile in the float-head format
                 LPVS_TRY(launch_pack_tiles_split(h->M.as<double>(), h->np, h->Mp.as<unsigned char>(), s));
                 h->Mp_fixed_tiles = 0; h->Mp_fixed_diag = 0;
-                h->Mp_stream_bytes = 6.0 * (double)symv_packed_doubles(h->np);
+                h->Mp_stream_bytes = (double)lay.elems_bytes;
                 h->Mp_valid = true; h->Mp_mode = kMpSplit; h->Mp_demoted = true; just_demoted = true;
             }
         } else LPVS_TRY(launch_pack_tiles(h->M.as<double>(), h->np, h->Mp.as<double>(), s));
@@ -1336,7 +1362,7 @@ int32_t lpvs_admm_init_f64(lpvs_problem *h, const double *x0, double mu, double 
             if (!h->nib_rhs.p) LPVS_TRY(h->nib_rhs.alloc(v));
             if (!h->nib_acc.p) LPVS_TRY(h->nib_acc.alloc(v));
             LPVS_HIP(hipMemsetAsync(h->nib_acc.p, 0, v, s));
-            { const size_t nb = (size_t)(h->np / 128), nt = nb * (nb + 1) / 2; if (!h->nib_part.p) LPVS_TRY(h->nib_part.alloc(sizeof(double) * 2 * nt * 128)); }
+            if (!h->nib_part.p) LPVS_TRY(h->nib_part.alloc(sizeof(double) * 2 * packed_tiles(h->np) * 128));
             LPVS_HIP(hipMemcpyAsync(h->xb_corr.p, h->xb.p, v, hipMemcpyDeviceToDevice, s));
         } else h->nib_period = 0;
     } else { h->xcorr_base = 0; h->xcorr_every = 0; }
@@ -1601,17 +1627,13 @@ static int32_t pack_host(const lpvs_problem *h, const double *c, double *re_out,
     const int64_t Nf = h->Nf, nb = h->nb;
     const int64_t m = h->kind == 1 ? Nf * nb : Nf;
     std::vector<double> re((size_t)m), im((size_t)m);
-    if (h->kind == 0) {  // fourier2complex, src/utilities.jl:62-73
-        if (!h->zerofreq) for (int64_t i = 0; i < Nf; ++i) { re[i] = c[i]; im[i] = c[Nf + i]; }
-        else { re[0] = c[0]; im[0] = 0.0; for (int64_t i = 1; i < Nf; ++i) { re[i] = c[i]; im[i] = c[Nf + i - 1]; } }
-    } else if (h->kind == 1) {  // z[sortperm(inds)] -> complex, src/lasso.jl:67-68
+    if (h->kind == 0) fourier2complex(c, Nf, h->zerofreq != 0, re.data(), im.data());
+    else if (h->kind == 1) {  // z[sortperm(inds)] -> complex, src/lasso.jl:67-68
         for (int64_t f = 0; f < Nf; ++f)
             for (int64_t v = 0; v < nb; ++v) { re[f + v * Nf] = c[f * 2 * nb + v]; im[f + v * Nf] = c[f * 2 * nb + nb + v]; }
     } else { set_error("explicit-Gram problems have no parameter packing"); return LPVS_EUNSUPPORTED; }
-    const size_t bytes = sizeof(double) * (size_t)m;
-    if (re_out) { if (is_device_ptr(re_out)) { LPVS_HIP(hipMemcpy(re_out, re.data(), bytes, hipMemcpyHostToDevice)); } else memcpy(re_out, re.data(), bytes); }
-    if (im_out) { if (is_device_ptr(im_out)) { LPVS_HIP(hipMemcpy(im_out, im.data(), bytes, hipMemcpyHostToDevice)); } else memcpy(im_out, im.data(), bytes); }
-    return LPVS_OK;
+    LPVS_TRY(copy_out(re_out, re.data(), (size_t)m));
+    return copy_out(im_out, im.data(), (size_t)m);
 }
 
 int32_t lpvs_problem_get_params_f64(lpvs_problem *h, int32_t which, double *re_out, double *im_out) {
@@ -1662,7 +1684,7 @@ int32_t lpvs_ls_spectral_f64(const double *y, const double *t, int64_t N, const 
     if (N <= 0 || Nf <= 0) { set_error("N and Nf must be positive"); return LPVS_EARGUMENT; }
     int64_t zf = 0;
     LPVS_TRY(lpvs_check_freq_f64(f, Nf, &zf));
-    const int64_t nreg = zf ? 2 * Nf - 1 : 2 * Nf;
+    const int64_t nreg = fourier_regressors(Nf, zf != 0);
     lpvs_problem *h = nullptr;
     if (N >= nreg) {   // tall: the ordinary Gram problem
         LPVS_TRY(lpvs_problem_create_fourier_f64(y, t, N, f, Nf, nullptr, device, &h));
@@ -1705,11 +1727,9 @@ int32_t lpvs_ls_spectral_f64(const double *y, const double *t, int64_t N, const 
     LPVS_TRY(copy_from_device(x.data(), xo.p, sizeof(double) * (size_t)nreg, s));
     // pack with the Fourier layout (kind 0, Nf, zerofreq are set; n is the dual size, so pack by hand)
     std::vector<double> re((size_t)Nf), im((size_t)Nf);
-    if (!zf) for (int64_t i = 0; i < Nf; ++i) { re[i] = x[i]; im[i] = x[Nf + i]; }
-    else { re[0] = x[0]; im[0] = 0.0; for (int64_t i = 1; i < Nf; ++i) { re[i] = x[i]; im[i] = x[Nf + i - 1]; } }
-    const size_t bytes = sizeof(double) * (size_t)Nf;
-    if (re_out) { if (is_device_ptr(re_out)) { LPVS_HIP(hipMemcpy(re_out, re.data(), bytes, hipMemcpyHostToDevice)); } else memcpy(re_out, re.data(), bytes); }
-    if (im_out) { if (is_device_ptr(im_out)) { LPVS_HIP(hipMemcpy(im_out, im.data(), bytes, hipMemcpyHostToDevice)); } else memcpy(im_out, im.data(), bytes); }
+    fourier2complex(x.data(), Nf, zf != 0, re.data(), im.data());
+    LPVS_TRY(copy_out(re_out, re.data(), (size_t)Nf));
+    LPVS_TRY(copy_out(im_out, im.data(), (size_t)Nf));
     LPVS_HIP(hipStreamSynchronize(s));
     return LPVS_OK;
 }
@@ -1728,115 +1748,123 @@ namespace {
 thread_local double g_win_multi[2] = {0, 0};   // last several-device call of this thread: ranks of the RCCL communicator that gathered (0: no collective), devices driven
 thread_local double g_win_timing[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // [8] = bytes of packed inverses one timed mat-vec launch reads
 
-// sink(window index relative to win_lo, signal, re[Nf], im[Nf], iterations) is called in window order, signals innermost
-template <class Sink>
-int32_t windows_engine(const WinJob &a, Sink sink) {
+// the formats of `count` tiles, fetched from the device and counted (synchronises)
+int32_t fetch_tile_census(const unsigned char *types_dev, size_t count, hipStream_t s, TileCensus *census) {
+    std::vector<unsigned char> ht(count);
+    LPVS_HIP(hipMemcpyAsync(ht.data(), types_dev, count, hipMemcpyDeviceToHost, s));
+    LPVS_HIP(hipStreamSynchronize(s));
+    *census = tile_census(ht.data(), count);
+    return LPVS_OK;
+}
+
+// argument checks of a job; zf: whether the grid starts at the zero frequency
+int32_t check_window_job(const WinJob &a, int64_t *zf) {
     int64_t k = 0;
     LPVS_TRY(lpvs_window_count(a.L, a.n, a.noverlap, &k));
-    const int64_t n = a.n, Nf = a.Nf, ns = a.ns;
-    const int64_t noverlap = a.noverlap < 0 ? n >> 1 : a.noverlap;
-    const int64_t win_lo = a.win_lo, win_hi = a.win_hi;
     const bool sparse = a.estimator == LPVS_EST_SPARSE || a.estimator == LPVS_EST_SPARSE_INIT;
-    const bool init = a.estimator == LPVS_EST_SPARSE_INIT;       // x0 = fourier_solve(A, y, zerofreq, lam), src/lasso.jl:112
     if (!sparse && a.estimator != LPVS_EST_DENSE) { set_error("unknown estimator %d", a.estimator); return LPVS_EARGUMENT; }
-    if (ns < 1 || ns > 64) { set_error("number of signals %lld outside [1, 64]", (long long)ns); return LPVS_EARGUMENT; }
-    if (win_lo < 0 || win_hi > k || win_lo > win_hi) { set_error("window range [%lld,%lld) outside [0,%lld)", (long long)win_lo, (long long)win_hi, (long long)k); return LPVS_EARGUMENT; }
-    const double mu = a.mu, tol = a.tol;
+    if (a.ns < 1 || a.ns > 64) { set_error("number of signals %lld outside [1, 64]", (long long)a.ns); return LPVS_EARGUMENT; }
+    if (a.win_lo < 0 || a.win_hi > k || a.win_lo > a.win_hi) { set_error("window range [%lld,%lld) outside [0,%lld)", (long long)a.win_lo, (long long)a.win_hi, (long long)k); return LPVS_EARGUMENT; }
     if (sparse) {
-        if (!(mu >= 0 && mu <= 1)) { set_error("μ should be ≤ 1"); return LPVS_EASSERT; }
-        if (mu == 0) { set_error("mu = 0 makes the x-update singular"); return LPVS_ENUMERIC; }
-        if (a.prox_kind < LPVS_PROX_L1 || a.prox_kind > LPVS_PROX_GROUP_L2) { set_error("unknown prox kind %d", a.prox_kind); return LPVS_EUNSUPPORTED; }
-        if (a.prox_kind == LPVS_PROX_GROUP_L2 && a.group_len <= 0) { set_error("group_len must be positive"); return LPVS_EARGUMENT; }
-        if (a.prox_kind == LPVS_PROX_GROUP_L2 && a.group_len > 8192) { set_error("group_len > 8192 is not supported by the device prox"); return LPVS_EUNSUPPORTED; }
-        if (a.linear_sign != 1 && a.linear_sign != -1) { set_error("linear_sign must be +1 or -1"); return LPVS_EARGUMENT; }
+        LPVS_TRY(check_mu_and_sign(a.mu, a.linear_sign));
+        LPVS_TRY(check_prox(a.prox_kind, a.group_len));
     }
-    int64_t zf = 0;
-    LPVS_TRY(lpvs_check_freq_f64(a.freqs, Nf, &zf));
-    for (double &v : g_win_timing) v = 0;
-    g_win_multi[0] = g_win_multi[1] = 0;
-    const int64_t nwin = win_hi - win_lo;
-    if (nwin == 0) return LPVS_OK;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) { (void)hipGetLastError(); set_error("no HIP device visible (the gfx950 path has no CPU fallback)"); return LPVS_EDEVICE; }
-    if (a.device < 0 || a.device >= count) { set_error("device %d out of range", a.device); return LPVS_EDEVICE; }
-    LPVS_HIP(hipSetDevice(a.device));
-    StreamBundle *res = bundle_acquire(a.device);
-    if (!res) { set_error("stream / event creation failed"); return LPVS_EDEVICE; }
-    struct BundleGuard { StreamBundle *b; ~BundleGuard() { bundle_release(b); } } bg{res};
-    hipStream_t s = res->stream;
-    EventPair *ev = res->ev;
+    return lpvs_check_freq_f64(a.freqs, a.Nf, zf);
+}
 
-    const int64_t nreg = zf ? 2 * Nf - 1 : 2 * Nf, np = round_up(nreg, 128), ld = round_up(nreg, 256);
-    // sub-batch: the k-major regressor panels of one pass stay under a budget (default 48 GiB of the 288 GB)
-    size_t budget = (size_t)48 << 30;
-    if (const char *e = getenv("LPVS_BATCH_PANEL_GIB")) { const long g = atol(e); if (g > 0) budget = (size_t)g << 30; }
-    int64_t bw = (int64_t)(budget / (sizeof(double) * (size_t)round_up(n, 64) * (size_t)ld));
-    if (bw < 1) bw = 1;
-    if (bw > nwin) bw = nwin;
-    if (bw > 8192) bw = 8192;
-    const int64_t step = n - noverlap;
-    std::vector<DevArg> dys((size_t)ns);
-    DevArg dt, df;
-    for (int64_t q = 0; q < ns; ++q) LPVS_TRY(dys[(size_t)q].set(a.ys[q], a.L, s));
-    LPVS_TRY(dt.set(a.t, a.L, s)); LPVS_TRY(df.set(a.freqs, Nf, s));
-    // structured Gram (nudft.hip) when T(2pi)*freqs is an arithmetic progression: no regressor panels at all
-    ApSlots sl;
+// ---- the engine's context --------------------------------------------------------------------------------------------------------------
+// The job, its plans, the stream and every buffer of one call, with one member function per phase; run() and pass() are the order of the
+// phases.  sink(window index relative to win_lo, signal, re[Nf], im[Nf], iterations) is called in window order, signals innermost.
+// Members are destroyed in reverse order: the stream is drained (`drain`) before a buffer goes back to the process-wide cache, where
+// another handle's stream could pick it up, and the stream bundle goes back to its own cache last.
+struct WinEngine {
+    const WinJob &a; const WinSink &sink;
+    const int64_t n, Nf, ns, zf, nwin, step;
+    const bool sparse, init;                         // init: x0 = fourier_solve(A, y, zerofreq, lam), src/lasso.jl:112
+    struct BundleGuard { StreamBundle *b; ~BundleGuard() { bundle_release(b); } } bg;
+    const hipStream_t s; EventPair *const ev;
     int jopt[kOptCount];                             // the caller's options: captured by the entry point, or this thread's own
-    if (a.opt_captured) for (int i = 0; i < kOptCount; ++i) jopt[i] = a.opt[i];
-    else capture_default_options(jopt);
-    {
-        const int form_opt = option_in_effect(LPVS_OPT_GRAM_FORM, jopt[LPVS_OPT_GRAM_FORM]);
-        const std::string form = form_opt == LPVS_GRAM_AP ? "ap" : form_opt == LPVS_GRAM_KRS ? "krs" : form_opt == LPVS_GRAM_KR ? "kr" : "auto";
-        if (form == "auto" || form == "ap") {
+    // the plan
+    size_t budget = kPanelBudgetBytes;
+    ApSlots sl;                                      // structured Gram (nudft.hip): the slot tables; sl.ok says whether it is used
+    bool ap = false, wnufft = false, wnufft_rhs = false; int nfg = 0; int64_t wcols = 1;
+    GramPlan pl;                                     // dense form
+    WinPassPlan pp;
+    int64_t nreg = 0, np = 0, ld = 0, bw = 0; size_t vb = 0;   // (of pp: the names the phases use)
+    int storage_opt = 0; bool split_storage = false, want_mv = false;
+    // inputs and buffers
+    std::vector<DevArg> dys; DevArg dt, df;
+    DevBuf Wp; const double *Wdev = nullptr;
+    PhaseTrace tr;
+    DevBuf P, slab, M, Q, bvec, x, z, u, rhs, xb, status, work, istat, offs, scr, part, Mp, seg, npart, tab, tabb, fibuf, Q0, M0, b0, x0buf, ballscr, xbc, nibacc;
+    ApSlotsDev sd;
+    DevBuf wgrids, wscale_g, wscale_r, wepsr;
+    DrainOnExit drain;
+    std::vector<int64_t> hseg, hoff; std::vector<double> zh, re, im; std::vector<AdmmStatus> hst; std::vector<int> hist_;
+    // the pass under way: its first window (relative to win_lo), windows, problems, batch
+    int64_t w0 = 0; int nb_ = 0, nprob = 0;
+    AdmmBatch ab{};
+
+    WinEngine(const WinJob &job, const WinSink &sink_, int64_t zf_, StreamBundle *res)
+        : a(job), sink(sink_), n(job.n), Nf(job.Nf), ns(job.ns), zf(zf_), nwin(job.win_hi - job.win_lo),
+          step(job.n - (job.noverlap < 0 ? job.n >> 1 : job.noverlap)),
+          sparse(job.estimator == LPVS_EST_SPARSE || job.estimator == LPVS_EST_SPARSE_INIT), init(job.estimator == LPVS_EST_SPARSE_INIT),
+          bg{res}, s(res->stream), ev(res->ev), dys((size_t)job.ns), tr(res->stream), drain(res->stream) {}
+
+    int32_t run() {
+        for (int64_t q = 0; q < ns; ++q) LPVS_TRY(dys[(size_t)q].set(a.ys[q], a.L, s));
+        LPVS_TRY(dt.set(a.t, a.L, s)); LPVS_TRY(df.set(a.freqs, Nf, s));
+        LPVS_TRY(choose_gram_form());
+        LPVS_TRY(upload_window_function());
+        tr = PhaseTrace(s);
+        LPVS_TRY(upload_nufft_scales());
+        LPVS_TRY(allocate());
+        g_win_timing[3] = (double)nwin; g_win_timing[7] = ap ? (wnufft ? 2 : 1) : 0;   // Gram form: 0 dense, 1 structured (direct sums), 2 structured (NUFFT)
+        for (w0 = 0; w0 < nwin; w0 += bw) LPVS_TRY(pass());
+        return LPVS_OK;
+    }
+
+    // structured Gram when T(2pi)*freqs is an arithmetic progression: no regressor panels at all; then the pass plan, which depends on it
+    int32_t choose_gram_form() {
+        if (a.opt_captured) for (int i = 0; i < kOptCount; ++i) jopt[i] = a.opt[i];
+        else capture_default_options(jopt);
+        const int form = option_in_effect(LPVS_OPT_GRAM_FORM, jopt[LPVS_OPT_GRAM_FORM]);
+        if (form == 0 || form == LPVS_GRAM_AP) {
             std::vector<double> hw;
             LPVS_TRY(fetch_host(hw, a.freqs, Nf));
             for (auto &v : hw) v = 6.283185307179586 * v;
             double tlo, thi, tam = a.t_absmax;
             if (!(tam >= 0)) LPVS_TRY(device_minmax(dt.p, a.L, &tlo, &thi, &tam, s));
             sl = make_ap_slots(hw, tam);
-            if (form == "ap" && !sl.ok) { set_error("LPVS_GRAM_FORM=ap but 2*pi*freqs is not an arithmetic progression (max|eps|*max|t| = %.3g)", sl.emax * tam); return LPVS_EARGUMENT; }
+            if (form == LPVS_GRAM_AP && !sl.ok) { set_error("LPVS_GRAM_FORM=ap but 2*pi*freqs is not an arithmetic progression (max|eps|*max|t| = %.3g)", sl.emax * tam); return LPVS_EARGUMENT; }
         }
+        ap = sl.ok;
+        if (const char *e = getenv("LPVS_BATCH_PANEL_GIB")) { const long g = atol(e); if (g > 0) budget = (size_t)g << 30; }
+        pl = make_gram_plan(fourier_regressors(Nf, zf != 0), n, kNominalBatch);
+        pp = window_pass_plan(n, Nf, zf != 0, ns, nwin, sparse, init, ap, pl.ksplit * pl.rows_per_chunk, budget);
+        nreg = pp.nreg; np = pp.np; ld = pp.ld; bw = pp.windows; vb = pp.vb;
+        // slot sums by non-uniform FFT (nufft.hip) when one progression serves all slots; LPVS_NUDFT=direct keeps the direct sums
+        wnufft = ap && sl.merged && nufft_windows_applicable(n, sl.nsl) && option_in_effect(LPVS_OPT_SLOT_SUMS, jopt[LPVS_OPT_SLOT_SUMS]) != LPVS_SLOTS_DIRECT;
+        wnufft_rhs = wnufft && sl.s0 % 2 == 0 && sl.s0 / 2 + sl.nf8 <= sl.nsl;   // a + f D = mode s0/2 + f (residual delta/2 -> eps)
+        nfg = wnufft ? nufft_grid_size(sl.nsl) : 0;
+        wcols = wnufft_rhs ? 1 + ns : 1;
+        storage_opt = option_in_effect(LPVS_OPT_M_STORAGE, jopt[LPVS_OPT_M_STORAGE]);
+        split_storage = sparse && storage_opt != LPVS_STORAGE_F64;
+        want_mv = sparse && getenv("LPVS_WINDOW_MATVEC_TIMING") != nullptr;
+        return LPVS_OK;
     }
-    const bool ap = sl.ok;
-    const int nmat = (sparse ? 2 : 3) + (init ? 2 : 0);   // resident np x np matrices per window: M, packed M (sparse) / Q, M, work (dense) (+ A'A and its inverse for init)
-    if (ap) {   // windows per pass bounded by the matrices: 32 GiB
-        bw = (int64_t)(((size_t)32 << 30) / (sizeof(double) * (size_t)np * (size_t)np * (size_t)nmat));
-        if (bw < 1) bw = 1;
-        if (bw > nwin) bw = nwin;
-        if (bw > 8192) bw = 8192;
-    }
-    // the sample split of the dense form is chosen for a nominal batch of 64 windows, whatever the shard holds: the
-    // summation order of a window must not depend on how the windows are sharded
-    const GramPlan pl = make_gram_plan(nreg, n, 64);
-    const int64_t nrows = ap ? n : pl.ksplit * pl.rows_per_chunk;
-    const size_t panel_bytes = ap ? 0 : sizeof(double) * (size_t)nrows * (size_t)ld;
-    while (!ap && bw > 1 && panel_bytes * (size_t)bw > budget) --bw;
-    // structured form: every window is cut into segments of rpcw samples, one workgroup row per segment; the segment length
-    // is fixed: the summation order of a window must not depend on how many windows share the pass, so that window shards
-    // (ranks of a node) reproduce the whole run bit for bit
-    const int64_t rpcw = ap ? std::min<int64_t>(n, 4096) : 0;
-    const int spw = ap ? (int)ceil_div(n, rpcw) : 0;
-    DevBuf Wp;
-    const double *Wdev = nullptr;
-    if (a.W != nullptr) {
-        LPVS_TRY(Wp.alloc(sizeof(double) * (size_t)nrows));
+
+    int32_t upload_window_function() {
+        if (a.W == nullptr) return LPVS_OK;
+        LPVS_TRY(Wp.alloc(sizeof(double) * (size_t)pp.nrows));
         LPVS_HIP(hipMemsetAsync(Wp.p, 0, Wp.bytes, s));
         LPVS_TRY(copy_to_device(Wp.p, a.W, sizeof(double) * (size_t)n, s));
         Wdev = Wp.as<double>();
+        return LPVS_OK;
     }
-    PhaseTrace tr(s);
-    DevBuf P, slab, M, Q, bvec, x, z, u, rhs, xb, status, work, istat, offs, scr, part, Mp, seg, npart, tab, tabb, fibuf, Q0, M0, b0, x0buf, ballscr, xbc, nibacc;
-    ApSlotsDev sd;
-    DrainOnExit drain(s);
-    const int64_t nprob_max = bw * ns;
-    // slot sums by non-uniform FFT (nufft.hip) when one progression serves all slots; LPVS_NUDFT=direct keeps the direct sums
-    const bool wnufft = ap && sl.merged && nufft_windows_applicable(n, sl.nsl) &&
-                        option_in_effect(LPVS_OPT_SLOT_SUMS, jopt[LPVS_OPT_SLOT_SUMS]) != LPVS_SLOTS_DIRECT;
-    const bool wnufft_rhs = wnufft && sl.s0 % 2 == 0 && sl.s0 / 2 + sl.nf8 <= sl.nsl;   // a + f D = mode s0/2 + f (residual delta/2 -> eps)
-    const int nfg = wnufft ? nufft_grid_size(sl.nsl) : 0;
-    const int64_t wcols = wnufft_rhs ? 1 + ns : 1;
-    DevBuf wgrids, wscale_g, wscale_r, wepsr;
-    if (wnufft) {
+
+    int32_t upload_nufft_scales() {
+        if (!wnufft) return LPVS_OK;
         LPVS_TRY(wgrids.alloc(sizeof(double) * (size_t)bw * (size_t)wcols * 2 * (size_t)nfg));
         const std::vector<double> sg = nufft_window_scale(nfg, 0, (int)sl.nsl);
         LPVS_TRY(wscale_g.alloc(sizeof(double) * sg.size()));
@@ -1851,130 +1879,59 @@ int32_t windows_engine(const WinJob &a, Sink sink) {
             LPVS_TRY(copy_to_device(wepsr.p, er.data(), sizeof(double) * er.size(), s));
         }
         LPVS_HIP(hipStreamSynchronize(s));           // (the host vectors are locals)
+        return LPVS_OK;
     }
-    if (ap) {
-        LPVS_TRY(sd.upload(sl, s));
-        LPVS_TRY(seg.alloc(sizeof(int64_t) * 3 * (size_t)bw * (size_t)spw));
-        LPVS_TRY(npart.alloc(sizeof(double) * (size_t)bw * (size_t)spw * (size_t)sl.nsl * 4));
-        LPVS_TRY(tab.alloc(sizeof(double) * (size_t)bw * (size_t)sl.nsl * 4));
-        LPVS_TRY(tabb.alloc(sizeof(double) * (size_t)bw * (size_t)sl.nf8 * 4));
-    } else {
-        LPVS_TRY(P.alloc(panel_bytes * (size_t)bw));
-        LPVS_TRY(slab.alloc(pl.slab_bytes * (size_t)bw));
-    }
-    LPVS_TRY(M.alloc(sizeof(double) * (size_t)np * (size_t)np * (size_t)bw));
-    if (sparse) {
-        LPVS_TRY(part.alloc(sizeof(double) * symv_part_doubles(np, nprob_max)));
-        LPVS_TRY(Mp.alloc(sizeof(double) * symv_packed_doubles(np) * (size_t)bw));
-        LPVS_TRY(status.alloc(sizeof(AdmmStatus) * (size_t)nprob_max));
-    } else {
-        LPVS_TRY(Q.alloc(sizeof(double) * (size_t)np * (size_t)np * (size_t)bw));
-    }
-    const size_t vb = sizeof(double) * (size_t)np * (size_t)nprob_max;
-    LPVS_TRY(bvec.alloc(vb)); LPVS_TRY(x.alloc(vb)); LPVS_TRY(z.alloc(vb)); LPVS_TRY(u.alloc(vb)); LPVS_TRY(rhs.alloc(vb));
-    const int storage_opt = option_in_effect(LPVS_OPT_M_STORAGE, jopt[LPVS_OPT_M_STORAGE]);
-    const bool split_storage = sparse && storage_opt != LPVS_STORAGE_F64;
-    if (split_storage) LPVS_TRY(xb.alloc(vb));
-    LPVS_TRY(istat.alloc(sizeof(int) * (size_t)bw));
-    LPVS_TRY(work.alloc(spd_inverse_work_bytes(np) * (size_t)bw));
-    LPVS_TRY(offs.alloc(sizeof(int64_t) * (size_t)bw));
-    if (!ap) LPVS_TRY(scr.alloc(rhs_scratch_bytes(n, nreg) * (size_t)bw));
-    if (init) {
-        LPVS_TRY(Q0.alloc(sizeof(double) * (size_t)np * (size_t)np * (size_t)bw)); LPVS_TRY(M0.alloc(sizeof(double) * (size_t)np * (size_t)np * (size_t)bw));
-        LPVS_TRY(b0.alloc(vb)); LPVS_TRY(x0buf.alloc(vb));
-    }
-    if (sparse && a.prox_kind == LPVS_PROX_BALL_L0 && nreg > 8192) LPVS_TRY(ballscr.alloc(2 * vb));   // selection keys of vectors that do not fit the LDS image
 
-    tr.mark("alloc");
-    std::vector<int64_t> hseg((size_t)3 * (size_t)bw * (size_t)spw);
-    std::vector<double> zh((size_t)np * (size_t)nprob_max), re((size_t)Nf), im((size_t)Nf);
-    std::vector<int64_t> hoff((size_t)bw);
-    std::vector<AdmmStatus> hst((size_t)nprob_max);
-    std::vector<int> hist_((size_t)bw);
-    const bool want_mv = sparse && getenv("LPVS_WINDOW_MATVEC_TIMING") != nullptr;
-    g_win_timing[3] = (double)nwin; g_win_timing[7] = ap ? (wnufft ? 2 : 1) : 0;   // Gram form: 0 dense, 1 structured (direct sums), 2 structured (NUFFT)
+    // every buffer of a pass, once: a later pass has at most as many windows
+    int32_t allocate() {
+        const size_t mat = sizeof(double) * (size_t)np * (size_t)np * (size_t)bw;
+        const int64_t nprob_max = bw * ns;
+        if (ap) {
+            LPVS_TRY(sd.upload(sl, s));
+            LPVS_TRY(seg.alloc(sizeof(int64_t) * 3 * (size_t)bw * (size_t)pp.segs));
+            LPVS_TRY(npart.alloc(sizeof(double) * (size_t)bw * (size_t)pp.segs * (size_t)sl.nsl * 4));
+            LPVS_TRY(tab.alloc(sizeof(double) * (size_t)bw * (size_t)sl.nsl * 4));
+            LPVS_TRY(tabb.alloc(sizeof(double) * (size_t)bw * (size_t)sl.nf8 * 4));
+        } else {
+            LPVS_TRY(P.alloc(pp.panel_bytes * (size_t)bw));
+            LPVS_TRY(slab.alloc(pl.slab_bytes * (size_t)bw));
+        }
+        LPVS_TRY(M.alloc(mat));
+        if (sparse) {
+            LPVS_TRY(part.alloc(sizeof(double) * symv_part_doubles(np, nprob_max)));
+            LPVS_TRY(Mp.alloc(packed_layout(np, sizeof(double), (size_t)bw).elems_bytes));
+            LPVS_TRY(status.alloc(sizeof(AdmmStatus) * (size_t)nprob_max));
+        } else {
+            LPVS_TRY(Q.alloc(mat));
+        }
+        LPVS_TRY(bvec.alloc(vb)); LPVS_TRY(x.alloc(vb)); LPVS_TRY(z.alloc(vb)); LPVS_TRY(u.alloc(vb)); LPVS_TRY(rhs.alloc(vb));
+        if (split_storage) LPVS_TRY(xb.alloc(vb));
+        LPVS_TRY(istat.alloc(sizeof(int) * (size_t)bw));
+        LPVS_TRY(work.alloc(spd_inverse_work_bytes(np) * (size_t)bw));
+        LPVS_TRY(offs.alloc(sizeof(int64_t) * (size_t)bw));
+        if (!ap) LPVS_TRY(scr.alloc(rhs_scratch_bytes(n, nreg) * (size_t)bw));
+        if (init) {
+            LPVS_TRY(Q0.alloc(mat)); LPVS_TRY(M0.alloc(mat));
+            LPVS_TRY(b0.alloc(vb)); LPVS_TRY(x0buf.alloc(vb));
+        }
+        if (sparse && a.prox_kind == LPVS_PROX_BALL_L0 && nreg > 8192) LPVS_TRY(ballscr.alloc(2 * vb));   // selection keys of vectors that do not fit the LDS image
+        tr.mark("alloc");
+        hseg.resize((size_t)3 * (size_t)bw * (size_t)pp.segs);
+        zh.resize((size_t)np * (size_t)nprob_max); re.resize((size_t)Nf); im.resize((size_t)Nf);
+        hoff.resize((size_t)bw); hst.resize((size_t)nprob_max); hist_.resize((size_t)bw);
+        return LPVS_OK;
+    }
 
-    for (int64_t w0 = 0; w0 < nwin; w0 += bw) {
-        const int nb_ = (int)((nwin - w0 < bw) ? nwin - w0 : bw);
-        const int nprob = nb_ * (int)ns;
-        for (int q = 0; q < nb_; ++q) hoff[q] = (win_lo + w0 + q) * step;           // arraysplit offsets, src/windows.jl:33
+    // windows [w0, w0 + nb_) of the range
+    int32_t pass() {
+        nb_ = (int)((nwin - w0 < bw) ? nwin - w0 : bw);
+        nprob = nb_ * (int)ns;
+        for (int q = 0; q < nb_; ++q) hoff[q] = (a.win_lo + w0 + q) * step;           // arraysplit offsets, src/windows.jl:33
         LPVS_HIP(hipMemcpyAsync(offs.p, hoff.data(), sizeof(int64_t) * (size_t)nb_, hipMemcpyHostToDevice, s));
         double *G = sparse ? M.as<double>() : Q.as<double>();                      // where the window Grams are assembled
         LPVS_HIP(hipEventRecord(ev[0].a, s));
-        // Gram A' diag(Wd) A of every window of the pass -> Gdst ([nb_][np][np]) and right-hand sides A' diag(Wd) y_s -> bdst ([nprob][np])
-        auto build_gram = [&](const double *Wd, double *Gdst, double *bdst) -> int32_t {
-            if (ap) {
-                for (int q = 0; q < nb_; ++q)
-                    for (int c = 0; c < spw; ++c) {
-                        int64_t *e = hseg.data() + 3 * ((size_t)q * (size_t)spw + (size_t)c);
-                        e[0] = hoff[q] + (int64_t)c * rpcw;
-                        e[1] = std::min(hoff[q] + n, e[0] + rpcw);
-                        e[2] = hoff[q];
-                    }
-                LPVS_TRY(copy_to_device(seg.p, hseg.data(), sizeof(int64_t) * 3 * (size_t)nb_ * (size_t)spw, s));
-                LPVS_HIP(hipMemsetAsync(Gdst, 0, sizeof(double) * (size_t)np * (size_t)np * (size_t)nb_, s));
-                LPVS_HIP(hipMemsetAsync(bdst, 0, vb, s));
-                const int64_t gstride = wcols * 2 * (int64_t)nfg;      // doubles per window in wgrids: [column][plain, x-weighted][nfg]
-                if (wnufft) {   // column 0 = the window weights alone (Gram); with it, in the same pass over the samples, signal 0
-                    LPVS_TRY(launch_nufft_window_spread(dt.p, Wd, nullptr, wnufft_rhs ? dys[0].p : nullptr, wnufft_rhs, offs.as<int64_t>(), nb_, n, sl.step.hi[1],
-                                                        sl.step.lo[1], nfg, wgrids.as<double>(), wgrids.as<double>() + 2 * (int64_t)nfg, gstride, s));
-                    LPVS_TRY(launch_nufft_window_modes(wgrids.as<double>(), gstride, nb_, nfg, 0, (int)sl.nsl, wscale_g.as<double>(), tab.as<double>(), sl.nsl * 4, s));
-                } else {
-                    LPVS_TRY(launch_nudft_windows(dt.p, nullptr, Wd, sd.hi.as<double>(), sd.lo.as<double>(), (int)sl.nsl, sl.step, seg.as<int64_t>(), nb_, spw,
-                                                  npart.as<double>(), tab.as<double>(), s));
-                }
-                LPVS_TRY(launch_ap_assemble_fourier(tab.as<double>(), sd.eps.as<double>(), Nf, sl.s0, sl.delta, (int)zf, nreg, Gdst, np, nb_, sl.nsl * 4,
-                                                    np * np, s));                                       // Q = A'WA   src/lasso.jl:119
-                tr.mark("gram (structured)");
-                for (int64_t q = 0; q < ns; ++q) {   // q_s = A'W y_s for every signal sharing the window   :120
-                    if (wnufft_rhs) {
-                        if (q >= 1 && q % 2 == 1)        // signals 1, 2 | 3, 4 | ... two to a pass
-                            LPVS_TRY(launch_nufft_window_spread(dt.p, Wd, dys[(size_t)q].p, q + 1 < ns ? dys[(size_t)q + 1].p : nullptr, q + 1 < ns, offs.as<int64_t>(), nb_,
-                                                                n, sl.step.hi[1], sl.step.lo[1], nfg, wgrids.as<double>() + (1 + q) * 2 * (int64_t)nfg,
-                                                                wgrids.as<double>() + (2 + q) * 2 * (int64_t)nfg, gstride, s));
-                        LPVS_TRY(launch_nufft_window_modes(wgrids.as<double>() + (1 + q) * 2 * (int64_t)nfg, gstride, nb_, nfg, (int)(sl.s0 / 2), (int)sl.nf8,
-                                                           wscale_r.as<double>(), tabb.as<double>(), sl.nf8 * 4, s));
-                    } else {
-                        LPVS_TRY(launch_nudft_windows(dt.p, dys[(size_t)q].p, Wd, sd.rhi.as<double>(), sd.rlo.as<double>(), (int)sl.nf8, sl.step, seg.as<int64_t>(),
-                                                      nb_, spw, npart.as<double>(), tabb.as<double>(), s));
-                    }
-                    LPVS_TRY(launch_ap_rhs_fourier(tabb.as<double>(), wnufft_rhs ? wepsr.as<double>() : sd.eps.as<double>(), Nf, (int)zf, bdst + q * np, nb_,
-                                                   sl.nf8 * 4, ns * np, s));
-                }
-            } else {
-                LPVS_TRY(launch_window_panels(dt.p, offs.as<int64_t>(), nb_, n, nrows, df.p, Nf, (int)zf, P.as<double>(), ld, s));
-                tr.mark("panels");
-                LPVS_TRY(launch_gram_panel_batch(pl, nb_, P.as<double>(), nrows * ld, ld, Wd, slab.as<double>(), s));
-                tr.mark("gram");
-                LPVS_HIP(hipMemsetAsync(Gdst, 0, sizeof(double) * (size_t)np * (size_t)np * (size_t)nb_, s));
-                LPVS_HIP(hipMemsetAsync(bdst, 0, vb, s));
-                LPVS_TRY(launch_gram_reduce_batch(pl, nb_, slab.as<double>(), Gdst, np, s));                  // Q = A'WA   src/lasso.jl:119
-                for (int64_t q = 0; q < ns; ++q)
-                    LPVS_TRY(launch_rhs_panel_batch(nb_, P.as<double>(), nrows * ld, ld, nreg, Wd, dys[(size_t)q].p, offs.as<int64_t>(), n,
-                                                    bdst + q * np, ns * np, scr.as<double>(), scr.bytes, s));   // q = A'Wy   :120
-            }
-            return LPVS_OK;
-        };
         LPVS_TRY(build_gram(Wdev, G, bvec.as<double>()));
-        if (init) {
-            // x0 = fourier_solve(A, y, zerofreq, lam) = (A'A + lam^2 I) \ A'y per window and signal -- the UNWEIGHTED problem, whatever W is
-            // (src/lasso.jl:112 passes A and y, not Wd): with a window function its own Gram / right-hand sides, otherwise those just built
-            if (Wdev != nullptr) LPVS_TRY(build_gram(nullptr, Q0.as<double>(), b0.as<double>()));
-            else {
-                LPVS_HIP(hipMemcpyAsync(Q0.p, G, sizeof(double) * (size_t)np * (size_t)np * (size_t)nb_, hipMemcpyDeviceToDevice, s));
-                LPVS_HIP(hipMemcpyAsync(b0.p, bvec.p, sizeof(double) * (size_t)np * (size_t)nprob, hipMemcpyDeviceToDevice, s));
-            }
-            LPVS_HIP(hipMemcpyAsync(M0.p, Q0.p, sizeof(double) * (size_t)np * (size_t)np * (size_t)nb_, hipMemcpyDeviceToDevice, s));
-            LPVS_TRY(launch_add_diag_batch(M0.as<double>(), np, nreg, a.lam * a.lam, nb_, s));
-            LPVS_TRY(spd_inverse_inplace_batch(M0.as<double>(), np, nb_, work.as<double>(), istat.as<int>(), s));
-            LPVS_HIP(hipMemcpyAsync(hist_.data(), istat.p, sizeof(int) * (size_t)nb_, hipMemcpyDeviceToHost, s));
-            LPVS_HIP(hipStreamSynchronize(s));
-            for (int q = 0; q < nb_; ++q)
-                if (hist_[q] != 0) { set_error("window %lld: init = true needs (A'A + %.3g I) positive definite", (long long)(win_lo + w0 + q), a.lam * a.lam); return LPVS_ENUMERIC; }
-            LPVS_TRY(launch_batch_ridge_solve(Q0.as<double>(), M0.as<double>(), np, nreg, nprob, (int)ns, b0.as<double>(), a.lam * a.lam, 2, x0buf.as<double>(),
-                                              z.as<double>(), u.as<double>(), s));   // (z, u: scratch here; the ADMM init below rewrites them)
-            tr.mark("init (ridge)");
-        }
+        if (init) LPVS_TRY(ridge_start(G));
         LPVS_HIP(hipEventRecord(ev[0].b, s));
         if (sparse && a.linear_sign < 0) {  // Quadratic(Q, +q): the x-update's linear term is -q
             LPVS_HIP(hipMemcpyAsync(zh.data(), bvec.p, sizeof(double) * (size_t)np * (size_t)nprob, hipMemcpyDeviceToHost, s));
@@ -1984,152 +1941,272 @@ int32_t windows_engine(const WinJob &a, Sink sink) {
             LPVS_HIP(hipStreamSynchronize(s));
         }
         tr.mark("reduce+rhs");
+        LPVS_TRY(invert());
+        const double *sol = sparse ? z.as<double>() : x.as<double>();
+        if (sparse) {
+            LPVS_TRY(pack_inverses());
+            LPVS_TRY(choose_iteration());
+            LPVS_TRY(iterate());
+            if (want_mv && w0 + nb_ >= nwin) LPVS_TRY(time_matvec());
+            tr.mark("admm");
+        } else LPVS_TRY(dense_solves());
+        LPVS_HIP(hipMemcpyAsync(zh.data(), sol, sizeof(double) * (size_t)np * (size_t)nprob, hipMemcpyDeviceToHost, s));
+        LPVS_HIP(hipStreamSynchronize(s));
+        g_win_timing[0] += ev[0].ms(); g_win_timing[1] += ev[1].ms(); g_win_timing[2] += ev[2].ms(); g_win_timing[6] += 1;
+        if (sparse && (a.st_x || a.st_z || a.st_u)) LPVS_TRY(copy_state_out());
+        emit();
+        return LPVS_OK;
+    }
+
+    // Gram A' diag(Wd) A of every window of the pass -> Gdst ([nb_][np][np]) and right-hand sides A' diag(Wd) y_s -> bdst ([nprob][np])
+    int32_t build_gram(const double *Wd, double *Gdst, double *bdst) { return ap ? gram_structured(Wd, Gdst, bdst) : gram_dense(Wd, Gdst, bdst); }
+
+    int32_t gram_structured(const double *Wd, double *Gdst, double *bdst) {
+        const int spw = pp.segs;
+        for (int q = 0; q < nb_; ++q)
+            for (int c = 0; c < spw; ++c) {
+                int64_t *e = hseg.data() + 3 * ((size_t)q * (size_t)spw + (size_t)c);
+                e[0] = hoff[q] + (int64_t)c * pp.seg_len;
+                e[1] = std::min(hoff[q] + n, e[0] + pp.seg_len);
+                e[2] = hoff[q];
+            }
+        LPVS_TRY(copy_to_device(seg.p, hseg.data(), sizeof(int64_t) * 3 * (size_t)nb_ * (size_t)spw, s));
+        LPVS_HIP(hipMemsetAsync(Gdst, 0, sizeof(double) * (size_t)np * (size_t)np * (size_t)nb_, s));
+        LPVS_HIP(hipMemsetAsync(bdst, 0, vb, s));
+        const int64_t gstride = wcols * 2 * (int64_t)nfg;      // doubles per window in wgrids: [column][plain, x-weighted][nfg]
+        if (wnufft) {   // column 0 = the window weights alone (Gram); with it, in the same pass over the samples, signal 0
+            LPVS_TRY(launch_nufft_window_spread(dt.p, Wd, nullptr, wnufft_rhs ? dys[0].p : nullptr, wnufft_rhs, offs.as<int64_t>(), nb_, n, sl.step.hi[1],
+                                                sl.step.lo[1], nfg, wgrids.as<double>(), wgrids.as<double>() + 2 * (int64_t)nfg, gstride, s));
+            LPVS_TRY(launch_nufft_window_modes(wgrids.as<double>(), gstride, nb_, nfg, 0, (int)sl.nsl, wscale_g.as<double>(), tab.as<double>(), sl.nsl * 4, s));
+        } else {
+            LPVS_TRY(launch_nudft_windows(dt.p, nullptr, Wd, sd.hi.as<double>(), sd.lo.as<double>(), (int)sl.nsl, sl.step, seg.as<int64_t>(), nb_, spw,
+                                          npart.as<double>(), tab.as<double>(), s));
+        }
+        LPVS_TRY(launch_ap_assemble_fourier(tab.as<double>(), sd.eps.as<double>(), Nf, sl.s0, sl.delta, (int)zf, nreg, Gdst, np, nb_, sl.nsl * 4,
+                                            np * np, s));                                       // Q = A'WA   src/lasso.jl:119
+        tr.mark("gram (structured)");
+        for (int64_t q = 0; q < ns; ++q) {   // q_s = A'W y_s for every signal sharing the window   :120
+            if (wnufft_rhs) {
+                if (q >= 1 && q % 2 == 1)        // signals 1, 2 | 3, 4 | ... two to a pass
+                    LPVS_TRY(launch_nufft_window_spread(dt.p, Wd, dys[(size_t)q].p, q + 1 < ns ? dys[(size_t)q + 1].p : nullptr, q + 1 < ns, offs.as<int64_t>(), nb_,
+                                                        n, sl.step.hi[1], sl.step.lo[1], nfg, wgrids.as<double>() + (1 + q) * 2 * (int64_t)nfg,
+                                                        wgrids.as<double>() + (2 + q) * 2 * (int64_t)nfg, gstride, s));
+                LPVS_TRY(launch_nufft_window_modes(wgrids.as<double>() + (1 + q) * 2 * (int64_t)nfg, gstride, nb_, nfg, (int)(sl.s0 / 2), (int)sl.nf8,
+                                                   wscale_r.as<double>(), tabb.as<double>(), sl.nf8 * 4, s));
+            } else {
+                LPVS_TRY(launch_nudft_windows(dt.p, dys[(size_t)q].p, Wd, sd.rhi.as<double>(), sd.rlo.as<double>(), (int)sl.nf8, sl.step, seg.as<int64_t>(),
+                                              nb_, spw, npart.as<double>(), tabb.as<double>(), s));
+            }
+            LPVS_TRY(launch_ap_rhs_fourier(tabb.as<double>(), wnufft_rhs ? wepsr.as<double>() : sd.eps.as<double>(), Nf, (int)zf, bdst + q * np, nb_,
+                                           sl.nf8 * 4, ns * np, s));
+        }
+        return LPVS_OK;
+    }
+
+    int32_t gram_dense(const double *Wd, double *Gdst, double *bdst) {
+        const int64_t nrows = pp.nrows;
+        LPVS_TRY(launch_window_panels(dt.p, offs.as<int64_t>(), nb_, n, nrows, df.p, Nf, (int)zf, P.as<double>(), ld, s));
+        tr.mark("panels");
+        LPVS_TRY(launch_gram_panel_batch(pl, nb_, P.as<double>(), nrows * ld, ld, Wd, slab.as<double>(), s));
+        tr.mark("gram");
+        LPVS_HIP(hipMemsetAsync(Gdst, 0, sizeof(double) * (size_t)np * (size_t)np * (size_t)nb_, s));
+        LPVS_HIP(hipMemsetAsync(bdst, 0, vb, s));
+        LPVS_TRY(launch_gram_reduce_batch(pl, nb_, slab.as<double>(), Gdst, np, s));                  // Q = A'WA   src/lasso.jl:119
+        for (int64_t q = 0; q < ns; ++q)
+            LPVS_TRY(launch_rhs_panel_batch(nb_, P.as<double>(), nrows * ld, ld, nreg, Wd, dys[(size_t)q].p, offs.as<int64_t>(), n,
+                                            bdst + q * np, ns * np, scr.as<double>(), scr.bytes, s));   // q = A'Wy   :120
+        return LPVS_OK;
+    }
+
+    // x0 = fourier_solve(A, y, zerofreq, lam) = (A'A + lam^2 I) \ A'y per window and signal -- the UNWEIGHTED problem, whatever W is
+    // (src/lasso.jl:112 passes A and y, not Wd): with a window function its own Gram / right-hand sides, otherwise those just built
+    int32_t ridge_start(const double *G) {
+        const size_t mat = sizeof(double) * (size_t)np * (size_t)np * (size_t)nb_;
+        if (Wdev != nullptr) LPVS_TRY(build_gram(nullptr, Q0.as<double>(), b0.as<double>()));
+        else {
+            LPVS_HIP(hipMemcpyAsync(Q0.p, G, mat, hipMemcpyDeviceToDevice, s));
+            LPVS_HIP(hipMemcpyAsync(b0.p, bvec.p, sizeof(double) * (size_t)np * (size_t)nprob, hipMemcpyDeviceToDevice, s));
+        }
+        LPVS_HIP(hipMemcpyAsync(M0.p, Q0.p, mat, hipMemcpyDeviceToDevice, s));
+        LPVS_TRY(launch_add_diag_batch(M0.as<double>(), np, nreg, a.lam * a.lam, nb_, s));
+        LPVS_TRY(spd_inverse_inplace_batch(M0.as<double>(), np, nb_, work.as<double>(), istat.as<int>(), s));
+        LPVS_HIP(hipMemcpyAsync(hist_.data(), istat.p, sizeof(int) * (size_t)nb_, hipMemcpyDeviceToHost, s));
+        LPVS_HIP(hipStreamSynchronize(s));
+        for (int q = 0; q < nb_; ++q)
+            if (hist_[q] != 0) { set_error("window %lld: init = true needs (A'A + %.3g I) positive definite", (long long)(a.win_lo + w0 + q), a.lam * a.lam); return LPVS_ENUMERIC; }
+        LPVS_TRY(launch_batch_ridge_solve(Q0.as<double>(), M0.as<double>(), np, nreg, nprob, (int)ns, b0.as<double>(), a.lam * a.lam, 2, x0buf.as<double>(),
+                                          z.as<double>(), u.as<double>(), s));   // (z, u: scratch here; the ADMM init below rewrites them)
+        tr.mark("init (ridge)");
+        return LPVS_OK;
+    }
+
+    // M = (Q + I/mu)^-1 for the ADMM x-update; (A'WA + lam I)^-1 of src/lsfft.jl:77
+    int32_t invert() {
         LPVS_HIP(hipEventRecord(ev[1].a, s));
         if (!sparse) LPVS_HIP(hipMemcpyAsync(M.p, Q.p, sizeof(double) * (size_t)np * (size_t)np * (size_t)nb_, hipMemcpyDeviceToDevice, s));
-        const double shift = sparse ? 1.0 / mu : a.lam;       // (Q + I/mu) for the ADMM x-update; (A'WA + lam I) of src/lsfft.jl:77
+        const double shift = sparse ? 1.0 / a.mu : a.lam;
         LPVS_TRY(launch_add_diag_batch(M.as<double>(), np, nreg, shift, nb_, s));
         LPVS_TRY(spd_inverse_inplace_batch(M.as<double>(), np, nb_, work.as<double>(), istat.as<int>(), s));
         LPVS_HIP(hipMemcpyAsync(hist_.data(), istat.p, sizeof(int) * (size_t)nb_, hipMemcpyDeviceToHost, s));
         LPVS_HIP(hipStreamSynchronize(s));
         for (int q = 0; q < nb_; ++q)
-            if (hist_[q] != 0) { set_error("window %lld: (Q + %.3g I) is not positive definite", (long long)(win_lo + w0 + q), shift); return LPVS_ENUMERIC; }
+            if (hist_[q] != 0) { set_error("window %lld: (Q + %.3g I) is not positive definite", (long long)(a.win_lo + w0 + q), shift); return LPVS_ENUMERIC; }
         tr.mark("inverse");
-        const double *sol = nullptr;
-        if (sparse) {
-            AdmmBatch ab{M.as<double>(), np, nreg, nprob, bvec.as<double>(), x.as<double>(), z.as<double>(), u.as<double>(), rhs.as<double>(),
-                         mu, tol, a.prox_kind, a.prox_param, a.group_len, status.as<AdmmStatus>(), part.as<double>(), Mp.as<double>(), (int)ns};
-            ab.opt_iteration = jopt[LPVS_OPT_ITERATION]; ab.opt_nt_loads = jopt[LPVS_OPT_NT_LOADS];
-            ab.scratch = ballscr.p ? ballscr.as<double>() : nullptr;
-            ab.x0 = init ? x0buf.as<double>() : nullptr;
-            // 6-byte storage of the packed inverses + offset form of the x-update, as for the single problems (admm.hip); only
-            // where the tile-packed path runs at all (LPVS_M_STORAGE=f64: doubles)
-            const bool split = split_storage && admm_batch_uses_tiles(ab);
-            if (split) {
-                // mixed storage (36-bit fixed-point tiles where a window's inverse is small; the Fourier inverses are nearly diagonal):
-                // tile formats and the per-matrix max|M| live behind the 6-byte slots of the Mp buffer (sized for doubles)
-                const bool mixed = storage_opt != LPVS_STORAGE_SPLIT;
-                const size_t nt = symv_packed_doubles(np) / (128 * 128);
-                unsigned char *types = Mp.as<unsigned char>() + 6 * symv_packed_doubles(np) * (size_t)bw;
-                const size_t types_bytes = ((nt * (size_t)bw + 255) / 256) * 256;
-                if (mixed && ns == 1 && 6 * symv_packed_doubles(np) * (size_t)bw + types_bytes + 8 * (size_t)bw <= Mp.bytes) {
-                    LPVS_TRY(launch_pack_tiles_mixed_batch(M.as<double>(), np, nb_, Mp.as<unsigned char>(), types,
-                                                           reinterpret_cast<unsigned long long *>(types + types_bytes), s,
-                                                           /*diag_float=*/false, /*abs_part=*/nullptr, /*n_valid=*/nreg));
-                    ab.mp_types = types;
-                } else
-                LPVS_TRY(launch_pack_tiles_split_batch(M.as<double>(), np, nb_, Mp.as<unsigned char>(), s));
-                LPVS_TRY(launch_batch_matvec(M.as<double>(), np, nprob, (int)ns, bvec.as<double>(), xb.as<double>(), s));   // xb = M b, full precision
-                ab.xb = xb.as<double>(); ab.mp_split = 1;
-            } else {
-                LPVS_TRY(launch_pack_tiles_batch(M.as<double>(), np, nb_, Mp.as<double>(), s));
-            }
-            LPVS_HIP(hipEventRecord(ev[1].b, s));
-            LPVS_HIP(hipMemsetAsync(part.p, 0, part.bytes, s));   // tickets / block norms
-            // one launch per iteration (admm.hip): accumulators / records of the whole pass, whether every tile is fixed point
-            if (ab.mp_types != nullptr && ab.xb != nullptr && ns == 1) {
-                if (!fibuf.p) LPVS_TRY(fibuf.alloc(sizeof(double) * fi_doubles(np, bw)));
-                ab.fi = fibuf.as<double>();
-                if (fi_batch_applicable(ab)) {
-                    const size_t nt = symv_packed_doubles(np) / (128 * 128);
-                    std::vector<unsigned char> ht(nt * (size_t)nb_);
-                    LPVS_HIP(hipMemcpyAsync(ht.data(), ab.mp_types, ht.size(), hipMemcpyDeviceToHost, s));
-                    LPVS_HIP(hipStreamSynchronize(s));
-                    bool allfix = true;
-                    for (unsigned char t : ht) allfix = allfix && t != 0;
-                    ab.fi_prefetch_all = allfix ? 1 : 0;
-                } else ab.fi = nullptr;
-            }
-            // 32-bit reads of the fixed-point tiles + the stale nibble product (admm.hip) where the batch iterates in one launch: the
-            // default, and LPVS_STORAGE_MIXED32 by name; LPVS_STORAGE_MIXED reads all 36 bits.  (The refresh of a batch exists only inside the launch.)
-            if (ab.fi != nullptr && (storage_opt == 0 || storage_opt == LPVS_STORAGE_MIXED32) && !(experiment_env("LPVS_NIB_FUSED") && experiment_env("LPVS_NIB_FUSED")[0] == '0')) {
-                int period = 32, ramp = 8;
-                if (const char *e = experiment_env("LPVS_NIB_PERIOD")) period = atoi(e) > 0 ? atoi(e) : 0;
-                if (const char *e = experiment_env("LPVS_NIB_RAMP")) ramp = atoi(e) > 0 ? atoi(e) : 0;
-                if (period > 0) {
-                    if (!xbc.p) LPVS_TRY(xbc.alloc(vb));
-                    if (!nibacc.p) LPVS_TRY(nibacc.alloc(vb));
-                    LPVS_HIP(hipMemcpyAsync(xbc.p, xb.p, sizeof(double) * (size_t)np * (size_t)nprob, hipMemcpyDeviceToDevice, s));
-                    LPVS_HIP(hipMemsetAsync(nibacc.p, 0, sizeof(double) * (size_t)np * (size_t)nprob, s));
-                    ab.nib_period = period; ab.nib_ramp = ramp; ab.xb_corr = xbc.as<double>(); ab.nib_acc = nibacc.as<long long>();
-                }
-            }
-            LPVS_HIP(hipEventRecord(ev[2].a, s));
-            LPVS_TRY(launch_admm_batch_init(ab, s));
-            if (ab.fi) LPVS_TRY(launch_fi_batch_setup(ab, s));
-            for (int64_t done = 0; done < a.iters;) {   // chunks: stop early once every problem of the batch has converged
-                const int64_t chunk = a.iters - done < 256 ? a.iters - done : 256;
-                ab.fi_base = done;
-                LPVS_TRY(launch_admm_batch_iterations(ab, chunk, s));
-                done += chunk;
-                LPVS_HIP(hipMemcpyAsync(hst.data(), status.p, sizeof(AdmmStatus) * (size_t)nprob, hipMemcpyDeviceToHost, s));
-                LPVS_HIP(hipStreamSynchronize(s));
-                bool all = true;
-                for (int q = 0; q < nprob; ++q) all = all && hst[q].converged;
-                if (all) break;
-            }
-            if (a.iters <= 0) {
-                LPVS_HIP(hipMemcpyAsync(hst.data(), status.p, sizeof(AdmmStatus) * (size_t)nprob, hipMemcpyDeviceToHost, s));
-                LPVS_HIP(hipStreamSynchronize(s));
-            }
-            LPVS_HIP(hipEventRecord(ev[2].b, s));
-            g_win_timing[9] = ab.fi != nullptr ? (ab.nib_period > 0 ? 2 : 1) : 0;   // the pass ran one launch per iteration (2: reading 32 of the fixed-point tiles' 36 bits, stale nibble product)
-            if (want_mv && w0 + nb_ >= nwin) {
-                LPVS_TRY(launch_admm_batch_matvec_only(ab, 3, s));
-                LPVS_HIP(hipEventRecord(ev[3].a, s));
-                LPVS_TRY(launch_admm_batch_matvec_only(ab, 200, s));
-                LPVS_HIP(hipEventRecord(ev[3].b, s));
-                LPVS_HIP(hipStreamSynchronize(s));
-                g_win_timing[4] = ev[3].ms() * 1e3 / 200; g_win_timing[5] = nb_;
-                const size_t nt = symv_packed_doubles(np) / (128 * 128);
-                double bytes = (double)(ab.mp_split ? 6 : 8) * (double)symv_packed_doubles(np) * (double)nb_;
-                if (ab.mp_types) {
-                    std::vector<unsigned char> ht(nt * (size_t)nb_);
-                    LPVS_HIP(hipMemcpyAsync(ht.data(), ab.mp_types, ht.size(), hipMemcpyDeviceToHost, s));
-                    LPVS_HIP(hipStreamSynchronize(s));
-                    size_t nfix = 0, ndiag = 0;
-                    for (unsigned char t : ht) { nfix += t != 0; ndiag += t == 2; }
-                    bytes = (double)nfix * (double)(ab.nib_period > 0 ? kMixedFixed32TileBytes : kMixedFixedTileBytes) + (double)ndiag * 1024.0 + (double)(ht.size() - nfix) * (double)kMixedFloatTileBytes;   // (32-bit reads: no nibble planes)
-                }
-                g_win_timing[8] = bytes;
-            }
-            tr.mark("admm");
-            sol = z.as<double>();
+        return LPVS_OK;
+    }
+
+    // the pass's batch, and the packed copies of its inverses in the storage the options ask for
+    int32_t pack_inverses() {
+        ab = AdmmBatch{M.as<double>(), np, nreg, nprob, bvec.as<double>(), x.as<double>(), z.as<double>(), u.as<double>(), rhs.as<double>(),
+                       a.mu, a.tol, a.prox_kind, a.prox_param, a.group_len, status.as<AdmmStatus>(), part.as<double>(), Mp.as<double>(), (int)ns};
+        ab.opt_iteration = jopt[LPVS_OPT_ITERATION]; ab.opt_nt_loads = jopt[LPVS_OPT_NT_LOADS];
+        ab.scratch = ballscr.p ? ballscr.as<double>() : nullptr;
+        ab.x0 = init ? x0buf.as<double>() : nullptr;
+        // 6-byte storage of the packed inverses + offset form of the x-update, as for the single problems (admm.hip); only
+        // where the tile-packed path runs at all (LPVS_M_STORAGE=f64: doubles)
+        if (split_storage && admm_batch_uses_tiles(ab)) {
+            // mixed storage (36-bit fixed-point tiles where a window's inverse is small; the Fourier inverses are nearly diagonal):
+            // tile formats and the per-matrix max|M| live behind the 6-byte slots of the Mp buffer (sized for doubles)
+            const bool mixed = storage_opt != LPVS_STORAGE_SPLIT;
+            const PackedLayout lay = packed_layout(np, 6, (size_t)bw);
+            if (mixed && ns == 1 && lay.bytes <= Mp.bytes) {
+                unsigned char *types = mp_tile_types(Mp, np, (size_t)bw);
+                LPVS_TRY(launch_pack_tiles_mixed_batch(M.as<double>(), np, nb_, Mp.as<unsigned char>(), types,
+                                                       reinterpret_cast<unsigned long long *>(Mp.as<unsigned char>() + lay.absmax_off), s,
+                                                       /*diag_float=*/false, /*abs_part=*/nullptr, /*n_valid=*/nreg));
+                ab.mp_types = types;
+            } else
+            LPVS_TRY(launch_pack_tiles_split_batch(M.as<double>(), np, nb_, Mp.as<unsigned char>(), s));
+            LPVS_TRY(launch_batch_matvec(M.as<double>(), np, nprob, (int)ns, bvec.as<double>(), xb.as<double>(), s));   // xb = M b, full precision
+            ab.xb = xb.as<double>(); ab.mp_split = 1;
         } else {
-            LPVS_HIP(hipEventRecord(ev[1].b, s));
-            LPVS_HIP(hipEventRecord(ev[2].a, s));
-            // x = (A'WA + lam I)^-1 A'W y, refined twice against the window's own Gram (src/lsfft.jl:77)
-            LPVS_TRY(launch_batch_ridge_solve(Q.as<double>(), M.as<double>(), np, nreg, nprob, (int)ns, bvec.as<double>(), a.lam, 2, x.as<double>(),
-                                              z.as<double>(), u.as<double>(), s));
-            LPVS_HIP(hipEventRecord(ev[2].b, s));
-            for (int q = 0; q < nprob; ++q) hst[q] = AdmmStatus{0, 1, 0, 0.0};
-            tr.mark("ridge solves");
-            sol = x.as<double>();
+            LPVS_TRY(launch_pack_tiles_batch(M.as<double>(), np, nb_, Mp.as<double>(), s));
         }
-        LPVS_HIP(hipMemcpyAsync(zh.data(), sol, sizeof(double) * (size_t)np * (size_t)nprob, hipMemcpyDeviceToHost, s));
-        LPVS_HIP(hipStreamSynchronize(s));
-        g_win_timing[0] += ev[0].ms(); g_win_timing[1] += ev[1].ms(); g_win_timing[2] += ev[2].ms(); g_win_timing[6] += 1;
-        if (sparse && (a.st_x || a.st_z || a.st_u)) {   // the raw state of this pass's problems (lpvs_windows_estimate_state_f64)
-            std::vector<double> sh((size_t)np * (size_t)nprob);
-            const struct { const double *dev; double *out; } legs[3] = {{x.as<double>(), a.st_x}, {z.as<double>(), a.st_z}, {u.as<double>(), a.st_u}};
-            for (const auto &lg : legs) {
-                if (!lg.out) continue;
-                LPVS_HIP(hipMemcpyAsync(sh.data(), lg.dev, sizeof(double) * sh.size(), hipMemcpyDeviceToHost, s));
-                LPVS_HIP(hipStreamSynchronize(s));
-                for (int q = 0; q < nb_; ++q)
-                    for (int64_t sg = 0; sg < ns; ++sg)
-                        std::memcpy(lg.out + ((size_t)sg * (size_t)a.st_nwin + (size_t)(win_lo + w0 + q - a.st_base)) * (size_t)nreg,
-                                    sh.data() + ((size_t)q * (size_t)ns + (size_t)sg) * (size_t)np, sizeof(double) * (size_t)nreg);
+        LPVS_HIP(hipEventRecord(ev[1].b, s));
+        LPVS_HIP(hipMemsetAsync(part.p, 0, part.bytes, s));   // tickets / block norms
+        return LPVS_OK;
+    }
+
+    // one launch per iteration where the batch allows it, and there 32-bit reads of the fixed-point tiles
+    int32_t choose_iteration() {
+        // one launch per iteration (admm.hip): accumulators / records of the whole pass, whether every tile is fixed point
+        if (ab.mp_types != nullptr && ab.xb != nullptr && ns == 1) {
+            if (!fibuf.p) LPVS_TRY(fibuf.alloc(sizeof(double) * fi_doubles(np, bw)));
+            ab.fi = fibuf.as<double>();
+            if (fi_batch_applicable(ab)) {
+                TileCensus census;
+                LPVS_TRY(fetch_tile_census(ab.mp_types, packed_tiles(np) * (size_t)nb_, s, &census));
+                ab.fi_prefetch_all = census.fixed == census.total ? 1 : 0;
+            } else ab.fi = nullptr;
+        }
+        // 32-bit reads of the fixed-point tiles + the stale nibble product (admm.hip) where the batch iterates in one launch: the
+        // default, and LPVS_STORAGE_MIXED32 by name; LPVS_STORAGE_MIXED reads all 36 bits.  (The refresh of a batch exists only inside the launch.)
+        if (ab.fi != nullptr && (storage_opt == 0 || storage_opt == LPVS_STORAGE_MIXED32) && !(experiment_env("LPVS_NIB_FUSED") && experiment_env("LPVS_NIB_FUSED")[0] == '0')) {
+            const NibKnobs nib = nib_knobs();
+            if (nib.period > 0) {
+                if (!xbc.p) LPVS_TRY(xbc.alloc(vb));
+                if (!nibacc.p) LPVS_TRY(nibacc.alloc(vb));
+                LPVS_HIP(hipMemcpyAsync(xbc.p, xb.p, sizeof(double) * (size_t)np * (size_t)nprob, hipMemcpyDeviceToDevice, s));
+                LPVS_HIP(hipMemsetAsync(nibacc.p, 0, sizeof(double) * (size_t)np * (size_t)nprob, s));
+                ab.nib_period = nib.period; ab.nib_ramp = nib.ramp; ab.xb_corr = xbc.as<double>(); ab.nib_acc = nibacc.as<long long>();
             }
         }
+        return LPVS_OK;
+    }
+
+    int32_t iterate() {
+        LPVS_HIP(hipEventRecord(ev[2].a, s));
+        LPVS_TRY(launch_admm_batch_init(ab, s));
+        if (ab.fi) LPVS_TRY(launch_fi_batch_setup(ab, s));
+        for (int64_t done = 0; done < a.iters;) {   // chunks: stop early once every problem of the batch has converged
+            const int64_t chunk = a.iters - done < 256 ? a.iters - done : 256;
+            ab.fi_base = done;
+            LPVS_TRY(launch_admm_batch_iterations(ab, chunk, s));
+            done += chunk;
+            LPVS_HIP(hipMemcpyAsync(hst.data(), status.p, sizeof(AdmmStatus) * (size_t)nprob, hipMemcpyDeviceToHost, s));
+            LPVS_HIP(hipStreamSynchronize(s));
+            bool all = true;
+            for (int q = 0; q < nprob; ++q) all = all && hst[q].converged;
+            if (all) break;
+        }
+        if (a.iters <= 0) {
+            LPVS_HIP(hipMemcpyAsync(hst.data(), status.p, sizeof(AdmmStatus) * (size_t)nprob, hipMemcpyDeviceToHost, s));
+            LPVS_HIP(hipStreamSynchronize(s));
+        }
+        LPVS_HIP(hipEventRecord(ev[2].b, s));
+        g_win_timing[9] = ab.fi != nullptr ? (ab.nib_period > 0 ? 2 : 1) : 0;   // the pass ran one launch per iteration (2: reading 32 of the fixed-point tiles' 36 bits, stale nibble product)
+        return LPVS_OK;
+    }
+
+    // LPVS_WINDOW_MATVEC_TIMING: the batch mat-vec alone, and the bytes of packed inverse one launch of it reads (last pass)
+    int32_t time_matvec() {
+        LPVS_TRY(launch_admm_batch_matvec_only(ab, 3, s));
+        LPVS_HIP(hipEventRecord(ev[3].a, s));
+        LPVS_TRY(launch_admm_batch_matvec_only(ab, 200, s));
+        LPVS_HIP(hipEventRecord(ev[3].b, s));
+        LPVS_HIP(hipStreamSynchronize(s));
+        g_win_timing[4] = ev[3].ms() * 1e3 / 200; g_win_timing[5] = nb_;
+        double bytes = (double)packed_layout(np, ab.mp_split ? 6 : 8, (size_t)nb_).elems_bytes;
+        if (ab.mp_types) {
+            TileCensus census;
+            LPVS_TRY(fetch_tile_census(ab.mp_types, packed_tiles(np) * (size_t)nb_, s, &census));
+            bytes = census_stream_bytes(census, /*read32=*/ab.nib_period > 0);
+        }
+        g_win_timing[8] = bytes;
+        return LPVS_OK;
+    }
+
+    // x = (A'WA + lam I)^-1 A'W y, refined twice against the window's own Gram (src/lsfft.jl:77)
+    int32_t dense_solves() {
+        LPVS_HIP(hipEventRecord(ev[1].b, s));
+        LPVS_HIP(hipEventRecord(ev[2].a, s));
+        LPVS_TRY(launch_batch_ridge_solve(Q.as<double>(), M.as<double>(), np, nreg, nprob, (int)ns, bvec.as<double>(), a.lam, 2, x.as<double>(),
+                                          z.as<double>(), u.as<double>(), s));
+        LPVS_HIP(hipEventRecord(ev[2].b, s));
+        for (int q = 0; q < nprob; ++q) hst[q] = AdmmStatus{0, 1, 0, 0.0};
+        tr.mark("ridge solves");
+        return LPVS_OK;
+    }
+
+    // the raw state of this pass's problems (lpvs_windows_estimate_state_f64)
+    int32_t copy_state_out() {
+        std::vector<double> sh((size_t)np * (size_t)nprob);
+        const struct { const double *dev; double *out; } legs[3] = {{x.as<double>(), a.st_x}, {z.as<double>(), a.st_z}, {u.as<double>(), a.st_u}};
+        for (const auto &lg : legs) {
+            if (!lg.out) continue;
+            LPVS_HIP(hipMemcpyAsync(sh.data(), lg.dev, sizeof(double) * sh.size(), hipMemcpyDeviceToHost, s));
+            LPVS_HIP(hipStreamSynchronize(s));
+            for (int q = 0; q < nb_; ++q)
+                for (int64_t sg = 0; sg < ns; ++sg)
+                    std::memcpy(lg.out + ((size_t)sg * (size_t)a.st_nwin + (size_t)(a.win_lo + w0 + q - a.st_base)) * (size_t)nreg,
+                                sh.data() + ((size_t)q * (size_t)ns + (size_t)sg) * (size_t)np, sizeof(double) * (size_t)nreg);
+        }
+        return LPVS_OK;
+    }
+
+    void emit() {
         for (int q = 0; q < nb_; ++q)
             for (int64_t sg = 0; sg < ns; ++sg) {
-                const double *c = zh.data() + ((size_t)q * (size_t)ns + (size_t)sg) * (size_t)np;   // fourier2complex, src/utilities.jl:62-73
-                if (!zf) for (int64_t i = 0; i < Nf; ++i) { re[i] = c[i]; im[i] = c[Nf + i]; }
-                else { re[0] = c[0]; im[0] = 0.0; for (int64_t i = 1; i < Nf; ++i) { re[i] = c[i]; im[i] = c[Nf + i - 1]; } }
+                fourier2complex(zh.data() + ((size_t)q * (size_t)ns + (size_t)sg) * (size_t)np, Nf, zf != 0, re.data(), im.data());
                 sink(w0 + q, sg, re.data(), im.data(), (int64_t)hst[(size_t)q * (size_t)ns + (size_t)sg].iters);
             }
     }
-    return LPVS_OK;
+};
+
+int32_t windows_engine(const WinJob &a, const WinSink &sink) {
+    int64_t zf = 0;
+    LPVS_TRY(check_window_job(a, &zf));
+    for (double &v : g_win_timing) v = 0;
+    g_win_multi[0] = g_win_multi[1] = 0;
+    if (a.win_hi == a.win_lo) return LPVS_OK;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) { (void)hipGetLastError(); set_error("no HIP device visible (the gfx950 path has no CPU fallback)"); return LPVS_EDEVICE; }
+    if (a.device < 0 || a.device >= count) { set_error("device %d out of range", a.device); return LPVS_EDEVICE; }
+    LPVS_HIP(hipSetDevice(a.device));
+    StreamBundle *res = bundle_acquire(a.device);
+    if (!res) { set_error("stream / event creation failed"); return LPVS_EDEVICE; }
+    WinEngine engine(a, sink, zf, res);
+    return engine.run();
 }
 
 // ---- the engine over a window range, in chunks that stay in the Infinity Cache, two parts of a chunk in flight ------------------------
@@ -2141,62 +2218,61 @@ int32_t windows_engine(const WinJob &a, Sink sink) {
 // shards of an 8-GPU run: 128 windows) gain the same way: 44.3 -> 36.7 ms.  The per-window results do not depend on how a range is
 // cut (tests), and the sink sees them in window order -- buffered per part, replayed in order -- so every accumulation over windows
 // is bit-identical to the uncut call.  LPVS_OPT_WINDOW_CHUNK_MB (default 1.0625 x the Infinity Cache = 285 MB; uncut: one chunk),
-// LPVS_OPT_WINDOWS_IN_FLIGHT (default 2); the environment variables of the same names are the fallback.
-template <class Sink>
-int32_t windows_engine_chunked(const WinJob &a0, Sink sink) {
+// LPVS_OPT_WINDOWS_IN_FLIGHT (default 2); the environment variables of the same names are the fallback.  The cut itself: windows_plan.h.
+struct WinRec { int64_t w, sg, its; std::vector<double> re, im; };
+
+// windows [c0, c0 + cw) of the job's range on `parts` threads; the sink sees their results in window order; tms: the parts' phase times
+int32_t run_chunk_parts(const WinJob &a, int64_t c0, int64_t cw, int parts, const WinSink &sink, std::vector<std::array<double, 10>> &tms) {
+    std::vector<std::vector<WinRec>> recs((size_t)parts);
+    std::vector<int32_t> rcs((size_t)parts, LPVS_OK);
+    std::vector<std::string> errs((size_t)parts);
+    tms.assign((size_t)parts, {});
+    const int64_t Nf = a.Nf;
+    auto run = [&](int p) {
+        WinJob j = a;
+        const int64_t lo = c0 + WinChunkPlan::part_lo(cw, parts, p), hi = c0 + WinChunkPlan::part_hi(cw, parts, p);
+        j.win_lo = a.win_lo + lo; j.win_hi = a.win_lo + hi;
+        rcs[(size_t)p] = lpvs::windows_engine_run(j, [&](int64_t w, int64_t sg, const double *re, const double *im, int64_t its) {
+            recs[(size_t)p].push_back(WinRec{lo + w, sg, its, std::vector<double>(re, re + Nf), std::vector<double>(im, im + Nf)});
+        });
+        if (rcs[(size_t)p] != LPVS_OK) errs[(size_t)p] = lpvs_last_error();
+        lpvs::windows_last_timing(tms[(size_t)p].data());
+    };
+    if (parts == 1) run(0);
+    else {
+        std::vector<std::thread> th;
+        auto guarded = [&](int p) { run_guarded([&] { run(p); }, [&](int32_t rc) { rcs[(size_t)p] = rc; errs[(size_t)p] = lpvs_last_error(); }); };
+        for (int p = 1; p < parts; ++p) th.emplace_back(guarded, p);
+        guarded(0);
+        for (auto &q : th) q.join();
+    }
+    for (int p = 0; p < parts; ++p)
+        if (rcs[(size_t)p] != LPVS_OK) { set_error("%s", errs[(size_t)p].c_str()); return rcs[(size_t)p]; }
+    for (int p = 0; p < parts; ++p)
+        for (const WinRec &r : recs[(size_t)p]) sink(r.w, r.sg, r.re.data(), r.im.data(), r.its);   // window order: parts are contiguous ranges
+    return LPVS_OK;
+}
+
+int32_t windows_engine_chunked(const WinJob &a0, const WinSink &sink) {
     const int64_t nwin = a0.win_hi - a0.win_lo;
     const bool sparse = a0.estimator == LPVS_EST_SPARSE || a0.estimator == LPVS_EST_SPARSE_INIT;
     // (options: the job's captured copy of its caller's defaults when it runs on a worker thread, else this thread's; then the environment)
     const int o_chunk = option_in_effect(LPVS_OPT_WINDOW_CHUNK_MB, a0.opt_captured ? a0.opt[LPVS_OPT_WINDOW_CHUNK_MB] : 0);
     const int o_fly = option_in_effect(LPVS_OPT_WINDOWS_IN_FLIGHT, a0.opt_captured ? a0.opt[LPVS_OPT_WINDOWS_IN_FLIGHT] : 0);
-    const double chunk_mb = o_chunk == LPVS_WINDOW_UNCUT ? 0.0 : (o_chunk > 0 ? (double)o_chunk : 1.0625 * infinity_cache_bytes() * 1e-6);   // 285 MB for 256 MiB
-    const int in_flight = o_fly > 0 ? o_fly : 2;
     int64_t zf = 0;
-    if (!sparse || nwin < 16 || a0.iters < 64 || a0.freqs == nullptr || a0.Nf < 1 || lpvs_check_freq_f64(a0.freqs, a0.Nf, &zf) != LPVS_OK ||
-        (in_flight == 1 && chunk_mb <= 0))
+    if (!window_chunking_applies(nwin, a0.iters, sparse, o_chunk, o_fly) || a0.freqs == nullptr || a0.Nf < 1 ||
+        lpvs_check_freq_f64(a0.freqs, a0.Nf, &zf) != LPVS_OK)
         return windows_engine(a0, sink);              // (argument errors are reported by the engine itself)
-    const int64_t nreg = zf ? 2 * a0.Nf - 1 : 2 * a0.Nf, np = round_up(nreg, 128), nblk = np / 128;
-    const double win_bytes = (double)(nblk * (nblk + 1) / 2) * (double)kMixedFixedTileBytes * (double)a0.ns;
-    int64_t chunk = chunk_mb > 0 ? (int64_t)(chunk_mb * 1e6 / win_bytes) : nwin;
-    if (chunk < 16) chunk = 16;
-    if (chunk > nwin) chunk = nwin;
-    const int64_t nchunks = ceil_div(nwin, chunk);
-    chunk = ceil_div(nwin, nchunks);                  // even chunks
+    const WinChunkPlan cp = window_chunk_plan(nwin, a0.ns, round_up(fourier_regressors(a0.Nf, zf != 0), 128), a0.iters, sparse, o_chunk, o_fly, infinity_cache_bytes());
     WinJob a = a0;
     if (!a.opt_captured) { capture_default_options(a.opt); a.opt_captured = true; }   // (the parts run on other threads)
     a.f32_grid = a0.f32_grid || g_f32_admission;      // ... and so does the float-grid admission of the _f32 entry points (a thread-local switch)
-    struct Rec { int64_t w, sg, its; std::vector<double> re, im; };
     double tsum[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const int64_t Nf = a.Nf;
-    for (int64_t c0 = 0; c0 < nwin; c0 += chunk) {
-        const int64_t c1 = std::min(nwin, c0 + chunk), cw = c1 - c0;
-        const int parts = cw >= 16 * in_flight ? in_flight : 1;
-        std::vector<std::vector<Rec>> recs((size_t)parts);
-        std::vector<int32_t> rcs((size_t)parts, LPVS_OK);
-        std::vector<std::string> errs((size_t)parts);
-        std::vector<std::array<double, 10>> tms((size_t)parts);
-        auto run = [&](int p) {
-            WinJob j = a;
-            const int64_t lo = c0 + cw * p / parts, hi = c0 + cw * (p + 1) / parts;
-            j.win_lo = a.win_lo + lo; j.win_hi = a.win_lo + hi;
-            rcs[(size_t)p] = lpvs::windows_engine_run(j, [&](int64_t w, int64_t sg, const double *re, const double *im, int64_t its) {
-                recs[(size_t)p].push_back(Rec{lo + w, sg, its, std::vector<double>(re, re + Nf), std::vector<double>(im, im + Nf)});
-            });
-            if (rcs[(size_t)p] != LPVS_OK) errs[(size_t)p] = lpvs_last_error();
-            lpvs::windows_last_timing(tms[(size_t)p].data());
-        };
-        if (parts == 1) run(0);
-        else {
-            std::vector<std::thread> th;
-            auto guarded = [&](int p) { run_guarded([&] { run(p); }, [&](int32_t rc) { rcs[(size_t)p] = rc; errs[(size_t)p] = lpvs_last_error(); }); };
-            for (int p = 1; p < parts; ++p) th.emplace_back(guarded, p);
-            guarded(0);
-            for (auto &q : th) q.join();
-        }
-        for (int p = 0; p < parts; ++p)
-            if (rcs[(size_t)p] != LPVS_OK) { set_error("%s", errs[(size_t)p].c_str()); return rcs[(size_t)p]; }
-        for (int p = 0; p < parts; ++p)
-            for (const Rec &r : recs[(size_t)p]) sink(r.w, r.sg, r.re.data(), r.im.data(), r.its);   // window order: parts are contiguous ranges
+    std::vector<std::array<double, 10>> tms;
+    for (int64_t c0 = 0; c0 < nwin; c0 += cp.chunk) {
+        const int64_t cw = std::min(nwin, c0 + cp.chunk) - c0;
+        const int parts = cp.parts(cw);
+        LPVS_TRY(run_chunk_parts(a, c0, cw, parts, sink, tms));
         double tmax[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         for (int p = 0; p < parts; ++p)
             for (int i = 0; i < 10; ++i) {
@@ -2404,7 +2480,7 @@ int32_t lpvs_fourier_regressor_f32(const float *t, int64_t N, const float *f, in
     WideArg dt, df; LPVS_TRY(dt.set(t, N, nullptr)); LPVS_TRY(df.set(f, Nf, nullptr));
     int64_t zf = 0;
     LPVS_TRY(lpvs_check_freq_f64(df.p, Nf, &zf));
-    const int64_t nreg = zf ? 2 * Nf - 1 : 2 * Nf;
+    const int64_t nreg = fourier_regressors(Nf, zf != 0);
     DevBuf A; LPVS_TRY(A.alloc(sizeof(double) * (size_t)N * (size_t)nreg));
     LPVS_TRY(lpvs_fourier_regressor_f64(dt.p, N, df.p, Nf, A.as<double>(), zerofreq));
     return narrow_out(A_out, A.as<double>(), N * nreg, nullptr);

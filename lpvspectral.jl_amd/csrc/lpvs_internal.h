@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/lpvspectral.h"
+#include "windows_plan.h"
 
 namespace lpvs {
 
@@ -309,8 +310,7 @@ bool multi_signal_fixed_tiles_ok(int64_t np);               // the multi-signal 
 void release_panel_plans();                                 // admm_multi.hip: frees the cached device tables of the panel walk
 int32_t launch_pack_tiles_mixed_batch(const double *M, int64_t np, int nbatch, unsigned char *Mp, unsigned char *types, unsigned long long *absmax,
                                       hipStream_t s, bool diag_float = false, double *abs_part = nullptr, int64_t n_valid = 0, double *rows_scratch = nullptr, int fix_bits = 36);
-constexpr size_t kMixedFixedTileBytes = 128 * 128 * 4 + 128 * 128 / 2 + 128 * 4, kMixedFloatTileBytes = 128 * 128 * 6;
-constexpr size_t kMixedFixed32TileBytes = 128 * 128 * 4 + 128 * 4;   // read per 32-bit fixed-point tile: heads + steps (same slot layout, the nibble area is skipped)
+// (bytes read per tile of each format: kMixedFixedTileBytes, kMixedFixed32TileBytes, kMixedFloatTileBytes of windows_plan.h)
 // element conversions for the _f32 entry points (device buffers)
 int32_t launch_cvt_f32_f64(const float *src, double *dst, int64_t count, hipStream_t s);
 int32_t launch_cvt_f64_f32(const double *src, float *dst, int64_t count, hipStream_t s);

@@ -279,7 +279,7 @@ def test_chunked_engine_is_bit_identical_to_the_uncut_one(L, knobs, monkeypatch)
     and every accumulation over windows (S of ls_windowpsd, the csd sums) equal the uncut call bit for bit -- here with chunks of a few
     windows, ragged last chunks, two or three parts, the sparse estimator on one and on two signals."""
     rng = np.random.default_rng(12)
-    n, nwin, Nf = 1 << 10, 83, 96                              # (0.092 MB of packed inverse per window: chunks of 32 / 54 windows)
+    n, nwin, Nf = 1 << 10, 83, 96                              # (0.22 MB per window in the chunk plan: chunks of 14 / 21 windows, tests/test_windows_plan.py)
     t = np.arange(nwin * n, dtype=np.float64)
     f = np.arange(1, Nf + 1) / 250.0
     y = np.sin(2 * np.pi * f[20] * t) * (1 + 0.3 * np.sin(2 * np.pi * t / (7 * n))) + 0.3 * rng.standard_normal(nwin * n)
@@ -299,6 +299,47 @@ def test_chunked_engine_is_bit_identical_to_the_uncut_one(L, knobs, monkeypatch)
     assert np.array_equal(x1, x0) and np.array_equal(S1, S0) and np.array_equal(its1, its0)
     for a, b in zip(acc1, acc0):
         assert np.array_equal(np.asarray(a), np.asarray(b))
+
+
+def test_a_second_pass_is_bit_identical_to_one_pass(L, monkeypatch):
+    """The engine's loop over passes: 140 windows of the dense form (4096 samples, 100 frequencies: 8 MiB of panel per window) under a panel
+    budget of 1 GiB are a pass of at most 128 windows and a second one; coefficients, iteration counts and the raw state x, z, u equal those
+    of the same call under the default budget (one pass) bit for bit -- the dense estimator on one signal, the sparse one on two (uncut:
+    the chunker would halve the range below one pass)."""
+    from lpvspectral_jl_amd import _lib, api
+    rng = np.random.default_rng(33)
+    n, nwin, Nf = 4096, 140, 100
+    Lh = n + (nwin - 1) * 16
+    t = np.cumsum(0.5 + rng.random(Lh))
+    f = np.arange(1, Nf + 1) / (2.5 * Nf)
+    y = np.sin(2 * np.pi * f[17] * t) * (1 + 0.3 * np.sin(2 * np.pi * t / 900.0)) + 0.3 * rng.standard_normal(Lh)
+    v = 0.7 * np.cos(2 * np.pi * f[60] * t + 0.5) + 0.3 * rng.standard_normal(Lh)
+    dense = dict(estimator=_lib.EST_DENSE, lam=1e-3, prox=(_lib.PROX_L1, 0.0, 0), μ=0.05, tol=0.0, iters=0, sign=_lib.LINEAR_LEAST_SQUARES)
+    sparse = dict(estimator=_lib.EST_SPARSE, lam=0.0, prox=(_lib.PROX_L1, 0.3, 0), μ=0.05, tol=0.0, iters=100, sign=_lib.LINEAR_QUADRATIC_AS_WRITTEN)
+    monkeypatch.setenv("LPVS_GRAM_FORM", "kr")
+    monkeypatch.setenv("LPVS_WINDOW_CHUNK_MB", "0"); monkeypatch.setenv("LPVS_WINDOWS_IN_FLIGHT", "1")
+
+    def run():
+        out, passes = {}, []
+        out["dense x"], out["dense iterations"] = api.windows_estimate([y], t, f, n, n - 16, None, dense)
+        passes.append(api.windowpsd_last_timing())
+        out["sparse x"], out["sparse iterations"] = api.windows_estimate([y, v], t, f, n, n - 16, None, sparse)
+        passes.append(api.windowpsd_last_timing())
+        out["state x"], out["state z"], out["state u"], out["state iterations"] = api.windows_estimate_state([y, v], t, f, n, n - 16, None, sparse)
+        passes.append(api.windowpsd_last_timing())
+        assert all(tm["windows"] == nwin and tm["gram_form"] == "dense" for tm in passes), passes
+        return out, [tm["passes"] for tm in passes]
+
+    one, passes_one = run()
+    monkeypatch.setenv("LPVS_BATCH_PANEL_GIB", "1")
+    two, passes_two = run()
+    print(f"passes under the default budget {passes_one}, under 1 GiB {passes_two}")
+    assert passes_one == [1, 1, 1] and all(p >= 2 for p in passes_two), (passes_one, passes_two)
+    assert one["dense x"].shape == (1, nwin, Nf) and one["sparse x"].shape == (2, nwin, Nf) and one["state u"].shape == (2, nwin, 2 * Nf)
+    assert np.all(one["sparse iterations"] == 100) and np.count_nonzero(one["state u"]) > 0
+    for name in one:
+        differ = np.unique(np.nonzero(np.asarray(one[name]) != np.asarray(two[name]))[1])
+        assert differ.size == 0, f"{name}: windows that differ between one pass and two: {differ.tolist()}"
 
 
 def test_window_state_entry_point(L, oracle, monkeypatch):
