@@ -1414,11 +1414,7 @@ static AdmmParams batch_as_params(const AdmmBatch &p) {   // AdmmParams with ns 
     q.mp_fix32 = p.nib_period > 0 && p.nib_acc != nullptr && p.xb_corr != nullptr ? 1 : 0;
     return q;
 }
-bool fi_batch_applicable(const AdmmBatch &p) {
-    const AdmmParams q = batch_as_params(p);
-    return option_in_effect(LPVS_OPT_ITERATION, p.opt_iteration) != LPVS_ITERATION_TWO && p.fi != nullptr && p.nrhs <= 1 && p.mp_split && p.mp_types != nullptr && p.xb != nullptr && p.part != nullptr &&
-           p.Mp != nullptr && fused_ok(q) && p.np <= 8192 && (int64_t)p.nbatch * p.np * 8 < ((int64_t)1 << 40);
-}
+bool fi_batch_applicable(const AdmmBatch &p) { return batch_one_launch_applies(iter_facts(p)); }
 int32_t launch_fi_batch_setup(const AdmmBatch &p, hipStream_t s) { return launch_fi_setup(batch_as_params(p), 0, true, s); }
 
 int32_t launch_admm_batch_iterations(const AdmmBatch &p, int64_t iters, hipStream_t s) {
@@ -1505,8 +1501,9 @@ bool admm_batch_uses_tiles(const AdmmBatch &p) {
 }
 
 bool fused_ok(const AdmmParams &p) {
-    if (p.prox_kind == LPVS_PROX_L1 || p.prox_kind == LPVS_PROX_L0) return true;
-    return p.prox_kind == LPVS_PROX_GROUP_L2 && p.group_len <= TS && TS % p.group_len == 0 && p.n % p.group_len == 0;
+    IterFacts f;
+    f.n = p.n; f.prox_kind = p.prox_kind; f.group_len = p.group_len;
+    return prox_fusable(f);
 }
 
 static void launch_split(const unsigned char *Mp, const unsigned char *types, const double *rhs, int64_t np, unsigned ntiles, double *part1,

@@ -93,11 +93,7 @@ constexpr double kFiPackedRowSlack = 0x1p-24 + 0x1p-30;
 static_assert((1.0 + kFiPackedRowSlack) * (1.0 + kFiPackedRowSlack) * (1.0 + 0x1p-40) < 1.000001,
               "the quantum bound of admm_iter_mixed_kernel no longer covers the rounding of the packed inverse: raise its 1.000001");
 size_t fi_doubles(int64_t np, int64_t nprob) { return (size_t)((4 * np + 6 * (np / TS) + 4) * nprob + 2); }
-bool fi_applicable(const AdmmParams &p) {
-    const bool on = option_in_effect(LPVS_OPT_ITERATION, p.opt_iteration) != LPVS_ITERATION_TWO;   // (resolved per call: tests and tools switch it between handles)
-    return on && p.fi != nullptr && p.ns == 1 && (p.mp_types != nullptr || p.mp_f32) && p.xb != nullptr && p.part != nullptr && p.Mp != nullptr && fused_ok(p) &&
-           p.np <= 49152;                            // (six clamped loads per lane cover the block norms / maxima of 384 row blocks)
-}
+bool fi_applicable(const AdmmParams &p) { return one_launch_applies(iter_facts(p)); }   // (np <= kOneLaunchMaxNp: admm_plan.h)
 
 // R = max_i sum_j |M_ij| (one wave per row) -> consts[2 sg] as the bit pattern of a non-negative double (integer max: order-independent);
 // blockIdx.y = problem of a batch (matrices np x np apart)

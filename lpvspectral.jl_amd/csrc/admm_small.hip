@@ -28,7 +28,6 @@ namespace lpvs {
 // A chunk is: first launch (rhs from memory, no update), iters - 1 fused launches, a last update-only launch, and a fix-up that
 // brings x and u back to the handle's vectors when the final state sits in the alternate buffers.  Bit-reproducible (fixed orders).
 enum { SM_FIRST = 0, SM_MID = 1, SM_LAST = 2 };
-constexpr int kSmallMaxNp = 2048;                      // (LDS image of the right-hand side; np < kSymmetricMinNp anyway)
 template <int MODE, int NW /* waves = rows of M per workgroup */, int NPMAX /* np <= NPMAX: 1024 or kSmallMaxNp */>
 __global__ void __launch_bounds__(64 * NW)
 admm_small_iter_kernel(AdmmParams p, int j /* launch of the chunk: 0 = first */) {
@@ -170,12 +169,7 @@ admm_small_fixup_kernel(AdmmParams p, int iters) {
         p.u[o + e] = p.scratch[(int64_t)sg * 2 * p.np + p.np + e];
     }
 }
-bool small_iter_applicable(const AdmmParams &p) {
-    const bool on = option_in_effect(LPVS_OPT_ITERATION, p.opt_iteration) != LPVS_ITERATION_TWO;
-    if (!on || p.sm_ctl == nullptr || p.Mp != nullptr || p.scratch == nullptr || p.np > kSmallMaxNp || p.np < 128 || p.xb != nullptr) return false;
-    if (p.prox_kind == LPVS_PROX_L1 || p.prox_kind == LPVS_PROX_L0) return true;
-    return p.prox_kind == LPVS_PROX_GROUP_L2 && p.group_len >= 1 && p.group_len <= 256 && p.n % p.group_len == 0;
-}
+bool small_iter_applicable(const AdmmParams &p) { return small_one_launch_applies(iter_facts(p)); }
 template <int NW, int NPMAX>
 static void launch_small_launches(const AdmmParams &p, int64_t iters, hipStream_t s) {
     const dim3 grid((unsigned)(p.np / NW), (unsigned)p.ns), blk(64 * NW);

@@ -359,35 +359,19 @@ struct lpvs_problem {
     DevBuf G, b, M, x, z, u, rhs, bs, scratch, status, work, istat, part, Mp;
     bool M_valid = false; double M_shift = 0;
     bool Mp_valid = false;   // Mp is the packed copy of the CURRENT M (cleared whenever M is recomputed or G changes)
-    int64_t Mp_fixed_diag = 0;   // ... of which on the diagonal (type 2)
     DevBuf sm_ctl;               // control words of the one-launch iteration of small problems (AdmmParams::sm_ctl)
-    int Mp_mode = 0;         // storage of Mp: kMpF64 / kMpF32 / kMpSplit / kMpMixed (see make_params)
-    double Mp_stream_bytes = 0;   // bytes of Mp one mat-vec launch reads (mixed storage: depends on the tile formats chosen)
-    int64_t Mp_fixed_tiles = 0;
+    // what lpvs_admm_init decided (admm_plan.h) and what its packing left: the storage as stored (a demotion to split is in it), the
+    // formats of the mixed storage's tiles, the correction schedule
+    StoragePlan plan;
+    TileCensus Mp_census;         // mixed storage: fixed-point tiles, of which on the diagonal, all (else zeros)
     bool Mp_demoted = false;      // mixed storage was asked for, but fewer than half of the tiles qualified: stored as split
-    DevBuf xb; bool offset_form = false;   // xb = M * (signed b), computed at admm_init from the full-precision M (AdmmParams::xb)
-    // the x-update's systematic error removed (admm.hip, launch_xupdate_correction): xb0 = the refined offset vector, xb = xb0 - E (x_k - xb0)
-    // re-formed after the iterations k = 1, 2, 4, 8, ... (k_enq = iterations enqueued since lpvs_admm_init / lpvs_admm_set_state)
-    DevBuf xb_corr, nib_rhs, nib_part, nib_acc; int nib_period = 0, nib_ramp = 0; double n_nib = 0, nib_us = 0;   // refreshes enqueued by the timed runs; one refresh stand-alone (lpvs_admm_time_matvec)   // 32-bit reads with a stale nibble product (AdmmParams::nib_period): the offset vector without its nibble term, scratch
-    DevBuf xb0, corr; int xcorr_base = 0, xcorr_every = 0; long long k_enq = 0; bool xb_refined = false, xcorr_double = false, xcorr_early = false;
-    // the schedule: after the iterations base^j (xcorr_base >= 2), or after iteration 16 and every xcorr_every-th one; 0 0 = no correction
-    long long next_correction(long long k) const {
-        if (xcorr_every > 0 && xcorr_double) {   // 16 (xcorr_early: 1, 2, 4, 8, 16), then xcorr_every and its doublings: the iterates move ever more slowly
-            if (xcorr_early && k < 16) { long long q = 1; while (q <= k) q *= 2; return q; }
-            if (k < 16 && xcorr_every > 16) return 16;
-            long long q = xcorr_every;
-            while (q <= k) q *= 2;
-            return q;
-        }
-        if (xcorr_every > 0) { if (k < 16 && xcorr_every > 16) return 16; return (k / xcorr_every + 1) * (long long)xcorr_every; }
-        long long q = 1;
-        while (q <= k) q *= xcorr_base;
-        return q;
-    }
-    bool xcorr() const { return xcorr_base >= 2 || xcorr_every > 0; }
-    bool Mp_read32 = false; // the iteration reads the 32 leading bits of the fixed-point tiles only (storage mixed32 on a corrected handle)
-    int Mp_fix_bits = 36;   // significant bits of the fixed-point tiles of the packed copy (32: nibbles zero and not read)
-    double Mp_rowsum = 0;   // largest absolute row sum of M over its valid rows, left by the mixed packing pass (0: not known)
+    double Mp_rowsum = 0;         // largest absolute row sum of M over its valid rows, left by the mixed packing pass (0: not known)
+    DevBuf xb;                    // plan.offset_form: xb = M * (signed b), computed at admm_init from the full-precision M (AdmmParams::xb)
+    // 32-bit reads with a stale nibble product (plan.nib_period > 0; AdmmParams::nib_period): the offset vector without its nibble term, scratch
+    DevBuf xb_corr, nib_rhs, nib_part, nib_acc; double n_nib = 0, nib_us = 0;   // refreshes enqueued by the timed runs; one refresh stand-alone (lpvs_admm_time_matvec)
+    // the x-update's systematic error removed (admm_refine.hip, launch_xupdate_correction): xb0 = the refined offset vector, xb = xb0 - E (x_k - xb0)
+    // re-formed after the iterations of the schedule (k_enq = iterations enqueued since lpvs_admm_init / lpvs_admm_set_state)
+    DevBuf xb0, corr; XcorrSchedule xcorr; long long k_enq = 0; bool xb_refined = false;
     DevBuf fi; long long fi_sync = -1; double fi_R = 0, fi_xbmax = 0;      // one-launch iteration (AdmmParams::fi): its records are those of iteration fi_sync
     int prox_kind = LPVS_PROX_L1; double prox_param = 1.0; int64_t group_len = 0;
     double mu = 0.05, tol = 1e-5; int sign = 1; bool inited = false;
@@ -462,38 +446,8 @@ int32_t copy_state_in(lpvs_problem *h, void *dev, const double *src) {
     return LPVS_OK;
 }
 
-// storage of the tile-packed inverse streamed by the ADMM mat-vec of large problems
-enum { kMpNone = 0, kMpF64 = 1, kMpF32 = 2, kMpSplit = 3, kMpMixed = 4 };
-// LPVS_M_STORAGE = mixed (default) | split | f64: how a double-precision handle stores the tile-packed inverse its mat-vec streams.
-// split = float head + 16-bit tail (6 bytes, 40 significant bits, admm.hip); mixed = the same, except that
-// tiles whose entries are all small against max|M| (the off-diagonal tiles of the LPV / Fourier inverses) are 36-bit fixed point
-// (4.53 bytes per element); _f32 handles always stream floats.  Handles with several right-hand sides decode either format on
-// the way into the LDS image their matrix-core tile product reads (their diagonal tiles always stay 6-byte).
-int mp_mode_for(const lpvs_problem *h) {
-    if (h->np < kSymmetricMinNp) return kMpNone;
-    if (h->f32) return kMpF32;
-    const int st = option_in_effect(LPVS_OPT_M_STORAGE, h->opt[LPVS_OPT_M_STORAGE]);
-    if (st == LPVS_STORAGE_F64) return kMpF64;
-    if (h->ns > 1 && h->np > 49152) return kMpF64;   // the streaming multi-signal kernel addresses its partials with 31-bit byte offsets
-    if (st == LPVS_STORAGE_SPLIT) return kMpSplit;
-    if (h->ns > 1 && !multi_signal_fixed_tiles_ok(h->np)) return kMpSplit;
-    return kMpMixed;   // (several right-hand sides: diagonal tiles always float-head; lpvs_admm_init)
-}
-
 // the tile-format bytes behind the 6-byte elements of nmat packed inverses (windows_plan.h: packed_layout)
 unsigned char *mp_tile_types(const DevBuf &Mp, int64_t np, size_t nmat) { return Mp.as<unsigned char>() + packed_layout(np, 6, nmat).elems_bytes; }
-
-// LPVS_NIB_PERIOD, LPVS_NIB_RAMP (experiments): refresh period of the stale nibble product (0: none, the 36-bit reads) and the ramp that
-// makes it denser while the right-hand side still moves fast -- after every launch up to 15, every 2nd up to 31, 4th up to 63, ..., 32nd
-// from 256 on (103 refreshes in 2000 iterations; u at cfg3 after 200 iterations 1.75e-10 from the exact iterate instead of 3.9e-10 --
-// 36-bit reads: 1.40e-10)
-struct NibKnobs { int period = 32, ramp = 8; };
-NibKnobs nib_knobs() {
-    NibKnobs k;
-    if (const char *e = experiment_env("LPVS_NIB_PERIOD")) k.period = atoi(e) > 0 ? atoi(e) : 0;
-    if (const char *e = experiment_env("LPVS_NIB_RAMP")) k.ramp = atoi(e) > 0 ? atoi(e) : 0;
-    return k;
-}
 
 // parameter checks of a sparse job: one copy for the handle entry points and the window engine
 int32_t check_prox(int kind, int64_t group_len) {
@@ -516,20 +470,26 @@ int32_t copy_out(double *dst, const double *src, size_t count) {
     return LPVS_OK;
 }
 
+// bytes of Mp one mat-vec launch reads (mixed storage: depends on the tile formats chosen; fix32: without the nibble planes)
+double mp_stream_bytes(const lpvs_problem *h, bool fix32) {
+    return h->plan.mode == kMpMixed ? census_stream_bytes(h->Mp_census, fix32) : (double)packed_layout(h->np, h->plan.element_bytes, 1).elems_bytes;
+}
+
 AdmmParams make_params(const lpvs_problem *h) {
+    const StoragePlan &pl = h->plan;
     const bool sym = h->np >= kSymmetricMinNp;
     AdmmParams p{h->M.as<double>(), h->np, h->n, h->bs.as<double>(), h->x.as<double>(), h->z.as<double>(), h->u.as<double>(),
                  h->rhs.as<double>(), h->mu, h->tol, h->prox_kind, h->prox_param, h->group_len, h->status.as<AdmmStatus>(),
                  h->scratch.as<double>(), h->part.as<double>(), sym ? h->Mp.as<double>() : nullptr, (int)h->ns};
-    p.mp_f32 = sym && h->Mp_mode == kMpF32 ? 1 : 0;
-    p.mp_split = sym && (h->Mp_mode == kMpSplit || h->Mp_mode == kMpMixed) ? 1 : 0;
-    p.mp_types = sym && h->Mp_mode == kMpMixed ? mp_tile_types(h->Mp, h->np, 1) : nullptr;
-    p.mp_fix32 = p.mp_types != nullptr && (h->Mp_fix_bits <= 32 || h->nib_period > 0) ? 1 : 0;
-    p.nib_period = p.mp_types != nullptr ? h->nib_period : 0; p.nib_ramp = h->nib_ramp; p.xb_corr = h->xb_corr.as<double>(); p.nib_rhs = h->nib_rhs.as<double>(); p.nib_part = h->nib_part.as<double>(); p.nib_acc = h->nib_acc.as<long long>();
-    p.xb = sym && h->offset_form ? h->xb.as<double>() : nullptr;
-    p.fi = sym && h->offset_form && h->ns == 1 && (h->Mp_mode == kMpMixed || h->Mp_mode == kMpF32) && h->fi.p ? h->fi.as<double>() : nullptr;
+    p.mp_f32 = pl.mode == kMpF32 ? 1 : 0;
+    p.mp_split = pl.mode == kMpSplit || pl.mode == kMpMixed ? 1 : 0;
+    p.mp_types = pl.mode == kMpMixed ? mp_tile_types(h->Mp, h->np, 1) : nullptr;
+    p.mp_fix32 = p.mp_types != nullptr && (pl.fix_bits <= 32 || pl.nib_period > 0) ? 1 : 0;
+    p.nib_period = pl.nib_period; p.nib_ramp = pl.nib_ramp; p.xb_corr = h->xb_corr.as<double>(); p.nib_rhs = h->nib_rhs.as<double>(); p.nib_part = h->nib_part.as<double>(); p.nib_acc = h->nib_acc.as<long long>();
+    p.xb = pl.offset_form ? h->xb.as<double>() : nullptr;
+    p.fi = pl.owns_fi && h->fi.p ? h->fi.as<double>() : nullptr;
     p.fi_R = h->fi_R; p.fi_xbmax = h->fi_xbmax;
-    p.fi_prefetch_all = sym && h->Mp_mode == kMpMixed && h->Mp_fixed_tiles == (int64_t)packed_tiles(h->np) ? 1 : 0;
+    p.fi_prefetch_all = pl.mode == kMpMixed && h->Mp_census.fixed == h->Mp_census.total ? 1 : 0;
     p.opt_iteration = h->opt[LPVS_OPT_ITERATION]; p.opt_nt_loads = h->opt[LPVS_OPT_NT_LOADS];
     {   // single problems on the one-launch iteration: mirrored tile order on odd launches (LPVS_TILE_ORDER=forward: the same order every launch, for A/B runs; read per call)
         const char *e = experiment_env("LPVS_TILE_ORDER");
@@ -562,6 +522,223 @@ int32_t factorize(lpvs_problem *h, double shift) {
     }
     h->M_valid = true; h->M_shift = shift;
     return LPVS_OK;
+}
+
+// ---- the phases of lpvs_admm_init_f64 / lpvs_admm_set_state_f64 / lpvs_admm_run: what to do is admm_plan.h's, here it is allocated and launched ----
+
+// The correction schedule, then the storage of the packed inverse, which depends on it.  Knobs and options are read here, once per init.
+StoragePlan decide_plan(lpvs_problem *h) {
+    const int xc_opt = option_in_effect(LPVS_OPT_XUPDATE_CORRECTION, h->opt[LPVS_OPT_XUPDATE_CORRECTION]);   // explicit, thread default, or environment ("0" = off)
+    const bool corrected = h->np >= kSymmetricMinNp && xc_opt != LPVS_XCORR_OFF;
+    // (schedules: an experiment knob; "0" = off is the option's plain fallback, option_from_env)
+    h->xcorr = xcorr_schedule_from(corrected ? experiment_env("LPVS_XUPDATE_CORRECTION") : nullptr, xcorr_default_schedule(h->ns, corrected));
+    const int storage = option_in_effect(LPVS_OPT_M_STORAGE, h->opt[LPVS_OPT_M_STORAGE]);
+    return admm_storage_plan(h->np, h->ns, h->f32, storage, h->ns > 1 && multi_signal_fixed_tiles_ok(h->np), h->xcorr.on(), fix_bits_from(experiment_env),
+                             nib_knobs_from(experiment_env));
+}
+
+// mixed storage; fewer than half of the tiles fixed point: every tile again, in the float-head format (*stored: the demoted plan)
+int32_t pack_mixed(lpvs_problem *h, const StoragePlan &want, StoragePlan *stored) {
+    hipStream_t s = h->stream;
+    const PackedLayout lay = packed_layout(h->np, want.element_bytes, 1);
+    unsigned char *types = mp_tile_types(h->Mp, h->np, 1);
+    // (single-signal handles: the packing pass also leaves the largest absolute row sum of M, which the one-launch iteration's quantum
+    // bound needs -- one more pass over the matrix otherwise; the tile partials' buffer and the scratch vector are free here)
+    unsigned long long *amax = reinterpret_cast<unsigned long long *>(h->Mp.as<unsigned char>() + lay.absmax_off);
+    LPVS_TRY(launch_pack_tiles_mixed(h->M.as<double>(), h->np, h->Mp.as<unsigned char>(), types, amax, s, want.diag_float,
+                                     want.want_rowsum ? h->part.as<double>() : nullptr, h->n, want.want_rowsum ? h->scratch.as<double>() : nullptr, want.fix_bits));
+    std::vector<unsigned char> ht(lay.tiles);
+    unsigned long long rbits = 0;
+    LPVS_HIP(hipMemcpyAsync(ht.data(), types, lay.tiles, hipMemcpyDeviceToHost, s));
+    if (want.want_rowsum) LPVS_HIP(hipMemcpyAsync(&rbits, amax + 1, sizeof(rbits), hipMemcpyDeviceToHost, s));
+    LPVS_HIP(hipStreamSynchronize(s));
+    if (want.want_rowsum) memcpy(&h->Mp_rowsum, &rbits, sizeof(double));
+    h->Mp_census = tile_census(ht.data(), lay.tiles);
+    if (getenv("LPVS_TRACE")) fprintf(stderr, "[lpvs] mixed packing: %zu of %zu tiles fixed point (%zu diagonal), ns = %lld\n", h->Mp_census.fixed, lay.tiles, (size_t)(h->np / kTile), (long long)h->ns);
+    if (demote_to_split(h->Mp_census.fixed, lay.tiles)) {
+        LPVS_TRY(launch_pack_tiles_split(h->M.as<double>(), h->np, h->Mp.as<unsigned char>(), s));
+        h->Mp_census = TileCensus{};
+        h->Mp_demoted = true;
+        *stored = demoted_plan(want);
+    }
+    return LPVS_OK;
+}
+
+// tile-packed lower triangle for the half-traffic mat-vec, in the storage the plan asks for; the handle's plan becomes what was stored
+int32_t pack_inverse(lpvs_problem *h, const StoragePlan &want) {
+    hipStream_t s = h->stream;
+    h->Mp_demoted = false;
+    if (!h->Mp.p || h->Mp.bytes < want.bytes) LPVS_TRY(h->Mp.alloc(want.bytes));
+    h->Mp_census = TileCensus{};
+    StoragePlan stored = want;
+    if (want.mode == kMpF32) LPVS_TRY(launch_pack_tiles_f32(h->M.as<double>(), h->np, h->Mp.as<float>(), s));
+    else if (want.mode == kMpSplit) LPVS_TRY(launch_pack_tiles_split(h->M.as<double>(), h->np, h->Mp.as<unsigned char>(), s));
+    else if (want.mode == kMpMixed) LPVS_TRY(pack_mixed(h, want, &stored));
+    else LPVS_TRY(launch_pack_tiles(h->M.as<double>(), h->np, h->Mp.as<double>(), s));
+    h->plan = stored; h->Mp_valid = true;
+    return LPVS_OK;
+}
+
+// tickets / block norms zeroed, x = x0 (or 0), bs = the signed linear term
+int32_t start_state(lpvs_problem *h, const double *x0) {
+    hipStream_t s = h->stream;
+    LPVS_HIP(hipMemsetAsync(h->part.p, 0, h->part.bytes, s));
+    const size_t v = sizeof(double) * (size_t)h->np * (size_t)h->ns;
+    LPVS_HIP(hipMemsetAsync(h->x.p, 0, v, s));
+    if (x0) LPVS_TRY(copy_state_in(h, h->x.p, x0));
+    std::vector<double> hb((size_t)h->np * (size_t)h->ns, 0.0);
+    LPVS_HIP(hipMemcpyAsync(hb.data(), h->b.p, v, hipMemcpyDeviceToHost, s));
+    LPVS_HIP(hipStreamSynchronize(s));
+    if (h->sign < 0) for (auto &q : hb) q = -q;
+    return copy_to_device(h->bs.p, hb.data(), v, s);
+}
+
+// the offset vector xb and its companions: xb0 of a corrected handle, xb_corr and the nibble product's scratch of one that reads 32 bits
+int32_t offset_vectors(lpvs_problem *h) {
+    hipStream_t s = h->stream;
+    const size_t v = sizeof(double) * (size_t)h->np * (size_t)h->ns;
+    if (!h->xb.p) LPVS_TRY(h->xb.alloc(v));
+    // every signal's M b, refined once against the Gram the handle still holds, residual in twice the mantissa (admm_refine.hip).  Round 5 left
+    // that to the first correction for corrected handles ("sixteen iterations with an offset vector good to ~1e-12 do not show") -- they do
+    // show off the benchmark's input family: at cond(G + I/mu) = 2.8e5 (mu = 1, unnormalised basis) the sixteen x-updates with E b in them
+    // are integrated by the dual variable and stay there (decay 1 - 1/(mu g) per iteration): u 9.0e-9 from the exact iterates after 600
+    // iterations against 3.0e-10 with the offset vector refined here (profiles/r06_offfamily_probe_refine.txt).  One accurate product: 0.2 ms
+    // at n = 8192.  rhs and scratch are free until launch_admm_init writes the state.  LPVS_XB_REFINE = rounds (A/B measurements)
+    int steps = 1;
+    if (const char *e = experiment_env("LPVS_XB_REFINE")) steps = atoi(e) < 0 ? 0 : atoi(e);
+    h->xb_refined = steps > 0;
+    LPVS_TRY(launch_offset_vector_refined(h->G.as<double>(), h->M.as<double>(), h->np, h->n, (int)h->ns, h->bs.as<double>(), h->M_shift, steps,
+                                          h->xb.as<double>(), h->rhs.as<double>(), h->scratch.as<double>(), s));
+    if (h->xcorr.on()) {
+        if (!h->xb0.p) LPVS_TRY(h->xb0.alloc(v));
+        if (!h->corr.p) LPVS_TRY(h->corr.alloc(3 * v));
+        LPVS_HIP(hipMemcpyAsync(h->xb0.p, h->xb.p, v, hipMemcpyDeviceToDevice, s));
+    }
+    if (h->plan.nib_period > 0) {   // the offset vector without its nibble term: none yet (the first refresh is that of launch 0, committed before x_0 is formed)
+        if (!h->xb_corr.p) LPVS_TRY(h->xb_corr.alloc(v));
+        if (!h->nib_rhs.p) LPVS_TRY(h->nib_rhs.alloc(v));
+        if (!h->nib_acc.p) LPVS_TRY(h->nib_acc.alloc(v));
+        LPVS_HIP(hipMemsetAsync(h->nib_acc.p, 0, v, s));
+        if (!h->nib_part.p) LPVS_TRY(h->nib_part.alloc(sizeof(double) * 2 * packed_tiles(h->np) * 128));
+        LPVS_HIP(hipMemcpyAsync(h->xb_corr.p, h->xb.p, v, hipMemcpyDeviceToDevice, s));
+    }
+    return LPVS_OK;
+}
+
+// one-launch iteration: constants (largest row sum of M, max|xb|) and the records of iteration 0
+int32_t one_launch_constants(lpvs_problem *h, const AdmmParams &p) {
+    hipStream_t s = h->stream;
+    if (h->Mp_rowsum > 0 && h->plan.mode == kMpMixed) {
+        AdmmParams pr = p; pr.fi_R = h->Mp_rowsum;
+        LPVS_TRY(launch_fi_setup(pr, 0, true, s, h->Mp_rowsum));
+    } else LPVS_TRY(launch_fi_setup(p, 0, true, s));
+    double hc[2] = {0, 0};
+    LPVS_TRY(fi_read_consts(p, hc, s));              // (synchronises)
+    h->fi_R = hc[0]; h->fi_xbmax = hc[1] * (1.0 + 0x1p-20); h->fi_sync = 0;   // (max|xb| bounds the corrected offset vector too: it moves by ~1e-12 of it)
+    return LPVS_OK;
+}
+
+// set_state, a restart from iteration 0: the offset vector of a fresh lpvs_admm_init (no correction, no nibble term yet), not the one the
+// previous run's last scheduled iteration left behind
+int32_t restore_initial_offset(lpvs_problem *h) {
+    hipStream_t s = h->stream;
+    const size_t v = sizeof(double) * (size_t)h->np * (size_t)h->ns;
+    LPVS_HIP(hipMemcpyAsync(h->xb.p, h->xb0.p, v, hipMemcpyDeviceToDevice, s));
+    if (h->plan.nib_period > 0 && h->xb_corr.p) {
+        LPVS_HIP(hipMemcpyAsync(h->xb_corr.p, h->xb0.p, v, hipMemcpyDeviceToDevice, s));
+        LPVS_HIP(hipMemsetAsync(h->nib_acc.p, 0, v, s));
+    }
+    return LPVS_OK;
+}
+
+// the correction of the state in memory: xb re-formed; 32-bit reads: xb_corr = xb - N rhs (the refreshes re-add the nibble term of THEIR right-hand side)
+int32_t correct_offset(lpvs_problem *h, const AdmmParams &p) {
+    LPVS_TRY(launch_xupdate_correction(p, h->G.as<double>(), h->M_shift, h->xb_refined ? nullptr : h->bs.as<double>(), h->xb0.as<double>(), h->xb.as<double>(),
+                                       h->corr.as<double>(), h->stream));
+    if (p.nib_period > 0) LPVS_TRY(launch_nibble_refresh(p, false, nullptr, h->stream, /*split=*/true));
+    return LPVS_OK;
+}
+// ... as correction i of a lpvs_admm_run call, between the event pair xc_ev[2 i], xc_ev[2 i + 1] (read after the call's final synchronisation, then reused)
+int32_t timed_correction(lpvs_problem *h, const AdmmParams &p, size_t i) {
+    if (h->xc_ev.size() < 2 * (i + 1)) {
+        hipEvent_t ea = nullptr, eb = nullptr;
+        LPVS_HIP(hipEventCreate(&ea)); h->xc_ev.push_back(ea);
+        LPVS_HIP(hipEventCreate(&eb)); h->xc_ev.push_back(eb);
+    }
+    LPVS_HIP(hipEventRecord(h->xc_ev[2 * i], h->stream));
+    LPVS_TRY(correct_offset(h, p));
+    LPVS_HIP(hipEventRecord(h->xc_ev[2 * i + 1], h->stream));
+    return LPVS_OK;
+}
+
+// the device's status words of every signal (synchronises); have all signals converged?
+int32_t read_status(lpvs_problem *h, std::vector<AdmmStatus> &st, bool *all_converged) {
+    LPVS_HIP(hipMemcpyAsync(st.data(), h->status.p, sizeof(AdmmStatus) * st.size(), hipMemcpyDeviceToHost, h->stream));
+    LPVS_HIP(hipStreamSynchronize(h->stream));
+    *all_converged = true;
+    for (auto &q : st) *all_converged = *all_converged && q.converged;
+    return LPVS_OK;
+}
+
+// launch-bound regime (np < kSymmetricMinNp): a chunk of iterations captured once into a hipGraph, kept by the handle.
+// Iterations past convergence are no-ops (device flag), and exactly max_iters are enqueued.
+int32_t capture_graph(lpvs_problem *h, const AdmmParams &p, int64_t chunk) {
+    hipStream_t s = h->stream;
+    hipGraph_t g = nullptr;
+    LPVS_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    const int32_t rc = launch_admm_iterations(p, chunk, s);
+    const hipError_t e = hipStreamEndCapture(s, &g);
+    if (rc != LPVS_OK || e != hipSuccess || g == nullptr) {
+        (void)hipGetLastError();
+        if (g) (void)hipGraphDestroy(g);
+        set_error("hipGraph capture of the ADMM chunk failed");
+        return LPVS_EDEVICE;
+    }
+    const hipError_t ei = hipGraphInstantiate(&h->admm_graph, g, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(g);
+    if (ei != hipSuccess) { (void)hipGetLastError(); h->admm_graph = nullptr; set_error("hipGraphInstantiate failed"); return LPVS_EDEVICE; }
+    h->admm_graph_iters = chunk;
+    return LPVS_OK;
+}
+
+// max_iters iterations between the event pair ev[0]: graph replays first (admm_plan.h: graph_replays), then sub-chunks that end at the
+// next scheduled correction (next_run_step).  *nxc: corrections enqueued; st: scratch for the status read after a correction.
+int32_t enqueue_run(lpvs_problem *h, AdmmParams &p, IterationKind kind, int64_t max_iters, std::vector<AdmmStatus> &st, size_t *nxc) {
+    hipStream_t s = h->stream;
+    if (kind == IterationKind::one_launch && h->fi_sync != p.fi_base) LPVS_TRY(launch_fi_setup(p, p.fi_base, false, s));   // state set from outside, or the last chunk took the other path
+    LPVS_HIP(hipEventRecord(h->ev[0].a, s));
+    int64_t todo = max_iters;
+    const int64_t chunk = graph_chunk_iters(kind);
+    if (h->admm_graph && h->admm_graph_iters != chunk) h->drop_graph();
+    const int64_t replays = graph_replays(h->np, todo, chunk, h->np < kSymmetricMinNp && getenv("LPVS_NO_GRAPH") == nullptr);
+    if (replays > 0 && !h->admm_graph) LPVS_TRY(capture_graph(h, p, chunk));
+    for (int64_t i = 0; i < replays; ++i) { LPVS_HIP(hipGraphLaunch(h->admm_graph, s)); todo -= chunk; }
+    while (todo > 0) {
+        const RunStep r = next_run_step(h->xcorr, h->k_enq, todo);
+        LPVS_TRY(launch_admm_iterations(p, r.step, s));
+        h->n_nib += (double)nib_refreshes_between(p.fi_base, p.fi_base + r.step, p.nib_period, p.nib_ramp);
+        todo -= r.step; h->k_enq += r.step;
+        if (!r.correct_after) continue;
+        LPVS_TRY(timed_correction(h, p, (*nxc)++));
+        if (todo > 0 && !(h->tol > 0)) p.fi_base += r.step;   // (no stopping test can fire: the device committed exactly `step` more)
+        else if (todo > 0) {   // the next sub-chunk starts from the iteration count the device committed (a stopping test may have fired)
+            bool all = false;
+            LPVS_TRY(read_status(h, st, &all));
+            if (all) break;
+            p.fi_base = st[0].iters;
+        }
+    }
+    LPVS_HIP(hipEventRecord(h->ev[0].b, s));
+    return LPVS_OK;
+}
+
+// the timings of a run that enqueued iterations: the corrections' event pairs, the run's, the iterations it committed
+void fold_timings(lpvs_problem *h, size_t nxc, long long iters_before, long long iters_after) {
+    for (size_t i = 0; i < nxc; ++i) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, h->xc_ev[2 * i], h->xc_ev[2 * i + 1]) == hipSuccess) { h->t_xcorr += ms; h->n_xcorr += 1; } else (void)hipGetLastError();
+    }
+    h->t_admm += h->ev[0].ms(); h->admm_iters_timed += (double)(iters_after - iters_before);
 }
 
 }  // namespace
@@ -1238,149 +1415,21 @@ int32_t lpvs_admm_init_f64(lpvs_problem *h, const double *x0, double mu, double 
     if (!h) { set_error("NULL handle"); return LPVS_EARGUMENT; }
     LPVS_TRY(check_mu_and_sign(mu, linear_sign));
     LPVS_HIP(hipSetDevice(h->device));
-    hipStream_t s = h->stream;
     h->drop_graph();
     LPVS_TRY(factorize(h, 1.0 / mu));            // no-op when M is cached for this shift; clears Mp_valid otherwise
-    // ---- the x-update correction (admm.hip, launch_xupdate_correction): decided first, the packing below depends on it.
-    // Default: every handle of n >= 2048, after the iterations 16, 512, 1024, 2048, ... (three corrections in 2000 iterations).
-    // Round 6: handles with several right-hand sides too -- at cfg5's judged size (n = 32768, 8 channels) the uncorrected run drifts 4.1e-10
-    // in x, z (1.4e-10 in u) from the corrected one after 2000 iterations (profiles/r06_cfg5_xcorr_fullsize.txt), the same constant forcing
-    // E w as at cfg3; a correction there is an accurate product over the 8.6-GB f64 Gram for all channels in one pass: 8.6 ms, three of them
-    // 1.9 % of a 2000-iteration run.  LPVS_XCORR_OFF switches it off per handle.
-    // LPVS_XUPDATE_CORRECTION (A/B measurements): "0" none; "B" after B^j; "eN" after 16 and every N-th; "dN" after 16, N, 2N, 4N, ...
-    const bool offset_form_wanted = h->np >= kSymmetricMinNp;
-    const int xc_opt = option_in_effect(LPVS_OPT_XUPDATE_CORRECTION, h->opt[LPVS_OPT_XUPDATE_CORRECTION]);   // explicit, thread default, or environment ("0" = off)
-    const bool xc_on = offset_form_wanted && xc_opt != LPVS_XCORR_OFF;
-    // Schedule (round 6): after 16, then 128 and its doublings for one right-hand side (five corrections in 2000 iterations: +0.4 ms at cfg3) --
-    // the off-family sweep (tests/test_gpu_offfamily.py, profiles/r06_offfamily_probe*.txt) has cases at cond(G + I/mu) ~ 2e4 where 16, 512, ...
-    // leaves x, z 8e-10 from the exact iterates after 600 iterations and this schedule 1.5e-10; 512 and its doublings for several right-hand sides
-    // (a correction there is a pass over the whole f64 Gram for all channels: 8.6 ms at cfg5; measured 2.6e-10 from the CPU reference iterates at n = 8192: tests/test_gpu_configs.py).
-    h->xcorr_base = 0; h->xcorr_every = xc_on ? (h->ns == 1 ? 128 : 512) : 0; h->xcorr_double = true;
-    const char *xc_env = xc_on ? experiment_env("LPVS_XUPDATE_CORRECTION") : nullptr;   // (schedules: an experiment knob; "0" = off is the option's plain fallback, option_from_env)
-    if (xc_env != nullptr && xc_env[0] == '0' && xc_env[1] == 0) xc_env = nullptr;   // ("0" only says off, and only as the option's last fallback)
-    if (const char *e = xc_env) {                                                    // schedule experiments: "B", "eN", "dN", "qN"
-        const bool sched = (e[0] == 'e' || e[0] == 'd' || e[0] == 'q') && atoi(e + 1) > 0;
-        const bool base = e[0] >= '0' && e[0] <= '9' && atoi(e) >= 2;
-        if (sched) {
-            h->xcorr_double = e[0] == 'd' || e[0] == 'q'; h->xcorr_early = e[0] == 'q';   // "qN": after 1, 2, 4, 8, 16, N, 2N, 4N, ...
-            h->xcorr_base = 0; h->xcorr_every = atoi(e + 1);
-        } else if (base) { h->xcorr_every = 0; h->xcorr_base = atoi(e); }
-        // anything else ("1", "on", "true", ...) only says ON: the default schedule set above stays (it used to fall through
-        // to base = 0, i.e. silently OFF, and took the 32-bit reads with it)
-    }
-    // Corrected single-signal handles READ 32 bits of the 36 their fixed-point tiles hold (4 B per element instead of 4.5) and carry the
-    // product of the 4-bit planes with a right-hand side up to nib_period iterations old in the offset vector (admm.hip, "the stale nibble
-    // product"): x, z and u all stay where the 36-bit reads leave them (u within 5.0e-10 of the exact iterates at cfg3; plain truncation to
-    // 32 bits: 2e-9 .. 7e-9 -- the dual variable integrates it; profiles/r05_cfg3_stale_nibble_product.txt, r05_cfg3_fixbits.txt).
-    // The default, and LPVS_STORAGE_MIXED32 by name; LPVS_STORAGE_MIXED asks for the 36-bit reads.
-    const int st_asked = option_in_effect(LPVS_OPT_M_STORAGE, h->opt[LPVS_OPT_M_STORAGE]);
-    const bool read32 = h->ns == 1 && !h->f32 && h->xcorr() && (st_asked == 0 || st_asked == LPVS_STORAGE_MIXED32);
-    int fix_bits = 36;                               // (packed with all 36 bits: the nibble planes feed the stale nibble product)
-    if (const char *e = experiment_env("LPVS_FIX_BITS")) fix_bits = atoi(e) >= 20 && atoi(e) <= 36 ? atoi(e) : fix_bits;
-    const NibKnobs nib = read32 ? nib_knobs() : NibKnobs{0, 0};
-    h->nib_period = nib.period; h->nib_ramp = nib.ramp;
-    h->Mp_read32 = read32;
-    if (h->Mp_valid && h->Mp_mode == kMpMixed && h->Mp_fix_bits != fix_bits) h->Mp_valid = false;   // (the same M packed for the other choice)
-    const int mode = mp_mode_for(h);
-    const bool demoted = mode == kMpMixed && h->Mp_mode == kMpSplit && h->Mp_demoted;   // mixed was tried for this M and found no small tiles
-    if (h->np >= kSymmetricMinNp && (!h->Mp_valid || (h->Mp_mode != mode && !demoted))) {   // tile-packed lower triangle for the half-traffic mat-vec
-        h->Mp_demoted = false;
-        bool just_demoted = false;   // set only by the demotion a few lines down: the handle's OLD (Mp_mode, Mp_valid) must not be mistaken for it
-        const size_t elt = mode == kMpF32 ? 4 : (mode == kMpSplit || mode == kMpMixed ? 6 : 8);
-        const PackedLayout lay = packed_layout(h->np, elt, 1);
-        const size_t ntiles = lay.tiles, need = mode == kMpMixed ? lay.bytes : lay.elems_bytes;   // (mixed: + tile formats + max|M|)
-        if (!h->Mp.p || h->Mp.bytes < need) LPVS_TRY(h->Mp.alloc(need));
-        h->Mp_stream_bytes = (double)lay.elems_bytes;
-        h->Mp_fixed_tiles = 0; h->Mp_fixed_diag = 0;
-        if (mode == kMpF32) LPVS_TRY(launch_pack_tiles_f32(h->M.as<double>(), h->np, h->Mp.as<float>(), s));
-        else if (mode == kMpSplit) LPVS_TRY(launch_pack_tiles_split(h->M.as<double>(), h->np, h->Mp.as<unsigned char>(), s));
-        else if (mode == kMpMixed) {
-            unsigned char *types = mp_tile_types(h->Mp, h->np, 1);
-            // (single-signal handles: the packing pass also leaves the largest absolute row sum of M, which the one-launch iteration's quantum
-            // bound needs -- one more pass over the matrix otherwise; the tile partials' buffer and the scratch vector are free here)
-            unsigned long long *amax = reinterpret_cast<unsigned long long *>(h->Mp.as<unsigned char>() + lay.absmax_off);
-            const bool want_R = h->ns == 1;
-            LPVS_TRY(launch_pack_tiles_mixed(h->M.as<double>(), h->np, h->Mp.as<unsigned char>(), types, amax, s, /*diag_float=*/h->ns > 1,
-                                             want_R ? h->part.as<double>() : nullptr, h->n, want_R ? h->scratch.as<double>() : nullptr, fix_bits));
-            h->Mp_fix_bits = fix_bits;
-            std::vector<unsigned char> ht(ntiles);
-            unsigned long long rbits = 0;
-            LPVS_HIP(hipMemcpyAsync(ht.data(), types, ntiles, hipMemcpyDeviceToHost, s));
-            if (want_R) LPVS_HIP(hipMemcpyAsync(&rbits, amax + 1, sizeof(rbits), hipMemcpyDeviceToHost, s));
-            LPVS_HIP(hipStreamSynchronize(s));
-            if (want_R) memcpy(&h->Mp_rowsum, &rbits, sizeof(double));
-            const TileCensus census = tile_census(ht.data(), ntiles);
-            h->Mp_fixed_tiles = (int64_t)census.fixed; h->Mp_fixed_diag = (int64_t)census.diag;
-            h->Mp_stream_bytes = census_stream_bytes(census, /*read32=*/false);
-            const size_t nblk_ = (size_t)(h->np / 128);
-            if (getenv("LPVS_TRACE")) fprintf(stderr, "[lpvs] mixed packing: %lld of %zu tiles fixed point (%zu diagonal), ns = %lld\n", (long long)h->Mp_fixed_tiles, ntiles, nblk_, (long long)h->ns);
-            if (2 * (size_t)h->Mp_fixed_tiles < ntiles) {
-                // not a diagonally dominant inverse: the mixed kernel (three workgroups per CU, float-head tiles in two halves) would
-                // only lose against the plain 6-byte kernel -- store every tile in the float-head format
-                LPVS_TRY(launch_pack_tiles_split(h->M.as<double>(), h->np, h->Mp.as<unsigned char>(), s));
-                h->Mp_fixed_tiles = 0; h->Mp_fixed_diag = 0;
-                h->Mp_stream_bytes = (double)lay.elems_bytes;
-                h->Mp_valid = true; h->Mp_mode = kMpSplit; h->Mp_demoted = true; just_demoted = true;
-            }
-        } else LPVS_TRY(launch_pack_tiles(h->M.as<double>(), h->np, h->Mp.as<double>(), s));
-        if (!just_demoted) { h->Mp_valid = true; h->Mp_mode = mode; }
-    }
-    LPVS_HIP(hipMemsetAsync(h->part.p, 0, h->part.bytes, s));   // zero the ticket / block norms
+    const StoragePlan want = decide_plan(h);
+    if (want.mode != kMpNone && must_repack(h->Mp_valid, h->plan.mode, h->plan.fix_bits, h->Mp_demoted, want.mode, want.fix_bits)) LPVS_TRY(pack_inverse(h, want));
+    else h->plan = h->Mp_demoted && want.mode == kMpMixed ? demoted_plan(want) : want;   // (mixed was tried for this M and found no small tiles)
     h->mu = mu; h->tol = tol; h->sign = linear_sign;
-    const size_t v = sizeof(double) * (size_t)h->np * (size_t)h->ns;
-    LPVS_HIP(hipMemsetAsync(h->x.p, 0, v, s));
-    if (x0) LPVS_TRY(copy_state_in(h, h->x.p, x0));
-    // signed linear term
-    std::vector<double> hb((size_t)h->np * (size_t)h->ns, 0.0);
-    LPVS_HIP(hipMemcpyAsync(hb.data(), h->b.p, v, hipMemcpyDeviceToHost, s));
-    LPVS_HIP(hipStreamSynchronize(s));
-    if (linear_sign < 0) for (auto &q : hb) q = -q;
-    LPVS_TRY(copy_to_device(h->bs.p, hb.data(), v, s));
-    // reduced-precision copies of M (split, f32) are only ever applied to (z-u)/mu: x = xb + M~ (z-u)/mu, xb = M b in full precision
-    // (round 5: the 8-byte storage too -- the offset vector is refined against a double-double residual, which the in-loop product M (b + v) cannot be)
-    h->offset_form = h->np >= kSymmetricMinNp;
-    if (h->offset_form) {
-        if (!h->xb.p) LPVS_TRY(h->xb.alloc(v));
-        // every signal's M b, refined once against the Gram the handle still holds, residual in twice the mantissa (admm.hip).  Round 5 left
-        // that to the first correction for corrected handles ("sixteen iterations with an offset vector good to ~1e-12 do not show") -- they do
-        // show off the benchmark's input family: at cond(G + I/mu) = 2.8e5 (mu = 1, unnormalised basis) the sixteen x-updates with E b in them
-        // are integrated by the dual variable and stay there (decay 1 - 1/(mu g) per iteration): u 9.0e-9 from the exact iterates after 600
-        // iterations against 3.0e-10 with the offset vector refined here (profiles/r06_offfamily_probe_refine.txt).  One accurate product: 0.2 ms
-        // at n = 8192.  rhs and scratch are free until launch_admm_init below writes the state.  LPVS_XB_REFINE = rounds (A/B measurements)
-        int steps = 1;
-        if (const char *e = experiment_env("LPVS_XB_REFINE")) steps = atoi(e) < 0 ? 0 : atoi(e);
-        h->xb_refined = steps > 0;
-        LPVS_TRY(launch_offset_vector_refined(h->G.as<double>(), h->M.as<double>(), h->np, h->n, (int)h->ns, h->bs.as<double>(), h->M_shift, steps,
-                                              h->xb.as<double>(), h->rhs.as<double>(), h->scratch.as<double>(), s));
-        if (h->xcorr()) {
-            if (!h->xb0.p) LPVS_TRY(h->xb0.alloc(v));
-            if (!h->corr.p) LPVS_TRY(h->corr.alloc(3 * v));
-            LPVS_HIP(hipMemcpyAsync(h->xb0.p, h->xb.p, v, hipMemcpyDeviceToDevice, s));
-        }
-        if (h->nib_period > 0 && h->Mp_mode == kMpMixed) {   // the offset vector without its nibble term: none yet (the first refresh is that of launch 0, committed before x_0 is formed)
-            if (!h->xb_corr.p) LPVS_TRY(h->xb_corr.alloc(v));
-            if (!h->nib_rhs.p) LPVS_TRY(h->nib_rhs.alloc(v));
-            if (!h->nib_acc.p) LPVS_TRY(h->nib_acc.alloc(v));
-            LPVS_HIP(hipMemsetAsync(h->nib_acc.p, 0, v, s));
-            if (!h->nib_part.p) LPVS_TRY(h->nib_part.alloc(sizeof(double) * 2 * packed_tiles(h->np) * 128));
-            LPVS_HIP(hipMemcpyAsync(h->xb_corr.p, h->xb.p, v, hipMemcpyDeviceToDevice, s));
-        } else h->nib_period = 0;
-    } else { h->xcorr_base = 0; h->xcorr_every = 0; }
+    LPVS_TRY(start_state(h, x0));
+    if (h->plan.offset_form) LPVS_TRY(offset_vectors(h));
     h->k_enq = 0;
-    if (h->offset_form && h->ns == 1 && (h->Mp_mode == kMpMixed || h->Mp_mode == kMpF32) && !h->fi.p) LPVS_TRY(h->fi.alloc(sizeof(double) * fi_doubles(h->np)));
+    if (h->plan.owns_fi && !h->fi.p) LPVS_TRY(h->fi.alloc(sizeof(double) * fi_doubles(h->np)));
     const AdmmParams p = make_params(h);
-    LPVS_TRY(launch_admm_init(p, s));
+    LPVS_TRY(launch_admm_init(p, h->stream));
     h->fi_sync = -1;
-    if (p.fi) {   // constants (largest row sum of M, max|xb|) and the records of iteration 0
-        if (h->Mp_rowsum > 0 && h->Mp_mode == kMpMixed) {
-            AdmmParams pr = p; pr.fi_R = h->Mp_rowsum;
-            LPVS_TRY(launch_fi_setup(pr, 0, true, s, h->Mp_rowsum));
-        } else LPVS_TRY(launch_fi_setup(p, 0, true, s));
-        double hc[2] = {0, 0};
-        LPVS_TRY(fi_read_consts(p, hc, s));              // (synchronises)
-        h->fi_R = hc[0]; h->fi_xbmax = hc[1] * (1.0 + 0x1p-20); h->fi_sync = 0;   // (max|xb| bounds the corrected offset vector too: it moves by ~1e-12 of it)
-    }
-    LPVS_HIP(hipStreamSynchronize(s));
+    if (p.fi) LPVS_TRY(one_launch_constants(h, p));
+    LPVS_HIP(hipStreamSynchronize(h->stream));
     h->inited = true;
     return LPVS_OK;
 }
@@ -1390,28 +1439,17 @@ int32_t lpvs_admm_set_state_f64(lpvs_problem *h, const double *x, const double *
     if (!h->inited) { set_error("lpvs_admm_set_state before lpvs_admm_init"); return LPVS_ESTATE; }
     if (iters_done < 0) { set_error("iters_done must be >= 0"); return LPVS_EARGUMENT; }
     LPVS_HIP(hipSetDevice(h->device));
-    hipStream_t s = h->stream;
     LPVS_TRY(copy_state_in(h, h->x.p, x));
     LPVS_TRY(copy_state_in(h, h->z.p, z));
     LPVS_TRY(copy_state_in(h, h->u.p, u));
     const AdmmParams p = make_params(h);
-    LPVS_TRY(launch_admm_restate(p, iters_done, s));
+    LPVS_TRY(launch_admm_restate(p, iters_done, h->stream));
     h->fi_sync = -1;                                  // (the next run rebuilds the one-launch iteration's records from the new state)
     h->k_enq = iters_done;
-    if (h->xcorr() && iters_done == 0) {              // a restart from iteration 0: the offset vector of a fresh lpvs_admm_init (no correction, no nibble term yet),
-        const size_t v = sizeof(double) * (size_t)h->np * (size_t)h->ns;   // not the one the previous run's last scheduled iteration left behind
-        LPVS_HIP(hipMemcpyAsync(h->xb.p, h->xb0.p, v, hipMemcpyDeviceToDevice, s));
-        if (h->nib_period > 0 && h->xb_corr.p) {
-            LPVS_HIP(hipMemcpyAsync(h->xb_corr.p, h->xb0.p, v, hipMemcpyDeviceToDevice, s));
-            LPVS_HIP(hipMemsetAsync(h->nib_acc.p, 0, v, s));
-        }
-    }
-    if (h->xcorr() && iters_done > 0)                 // re-entry: the correction of the state handed in (an uninterrupted run holds the one of its last scheduled iteration: same to second order)
-    {
-        LPVS_TRY(launch_xupdate_correction(make_params(h), h->G.as<double>(), h->M_shift, h->xb_refined ? nullptr : h->bs.as<double>(), h->xb0.as<double>(), h->xb.as<double>(), h->corr.as<double>(), s));
-        if (h->nib_period > 0) LPVS_TRY(launch_nibble_refresh(make_params(h), false, nullptr, s, /*split=*/true));
-    }
-    LPVS_HIP(hipStreamSynchronize(s));
+    if (h->xcorr.on() && iters_done == 0) LPVS_TRY(restore_initial_offset(h));
+    // re-entry: the correction of the state handed in (an uninterrupted run holds the one of its last scheduled iteration: same to second order)
+    if (h->xcorr.on() && iters_done > 0) LPVS_TRY(correct_offset(h, p));
+    LPVS_HIP(hipStreamSynchronize(h->stream));
     return LPVS_OK;
 }
 
@@ -1419,96 +1457,24 @@ int32_t lpvs_admm_run(lpvs_problem *h, int64_t max_iters, int64_t *iters_done, d
     if (!h) { set_error("NULL handle"); return LPVS_EARGUMENT; }
     if (!h->inited) { set_error("lpvs_admm_run before lpvs_admm_init"); return LPVS_ESTATE; }
     LPVS_HIP(hipSetDevice(h->device));
-    hipStream_t s = h->stream;
     AdmmParams p = make_params(h);
-    const size_t ns = (size_t)h->ns;
-    std::vector<AdmmStatus> st0(ns), st(ns);
-    LPVS_HIP(hipMemcpyAsync(st0.data(), h->status.p, sizeof(AdmmStatus) * ns, hipMemcpyDeviceToHost, s));
-    LPVS_HIP(hipStreamSynchronize(s));
-    bool all0 = true;
-    for (auto &q : st0) all0 = all0 && q.converged;
+    std::vector<AdmmStatus> st0((size_t)h->ns), st((size_t)h->ns);
+    bool all0 = false, all = false;
+    LPVS_TRY(read_status(h, st0, &all0));
     p.fi_base = st0[0].iters;
-    size_t nxc_done = 0;
-    if (max_iters > 0 && !all0) {
-        if (fi_applicable(p) && h->fi_sync != p.fi_base) LPVS_TRY(launch_fi_setup(p, p.fi_base, false, s));   // state set from outside, or the last chunk took the other path
-        LPVS_HIP(hipEventRecord(h->ev[0].a, s));
-        int64_t todo = max_iters;
-        // (the one-launch iteration of small problems pays two extra launches per chunk: longer chunks)
-        const int64_t kGraphIters = small_iter_applicable(p) ? 250 : 50;
-        if (h->admm_graph && h->admm_graph_iters != kGraphIters) h->drop_graph();
-        if (h->np < kSymmetricMinNp && todo >= 2 * kGraphIters && getenv("LPVS_NO_GRAPH") == nullptr) {
-            // two launches of a few microseconds per iteration: host launch cost dominates, so replay a captured
-            // chunk.  Iterations past convergence are no-ops (device flag), and exactly max_iters are enqueued.
-            if (!h->admm_graph) {
-                hipGraph_t g = nullptr;
-                LPVS_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-                const int32_t rc = launch_admm_iterations(p, kGraphIters, s);
-                const hipError_t e = hipStreamEndCapture(s, &g);
-                if (rc != LPVS_OK || e != hipSuccess || g == nullptr) {
-                    (void)hipGetLastError();
-                    if (g) (void)hipGraphDestroy(g);
-                    set_error("hipGraph capture of the ADMM chunk failed");
-                    return LPVS_EDEVICE;
-                }
-                const hipError_t ei = hipGraphInstantiate(&h->admm_graph, g, nullptr, nullptr, 0);
-                (void)hipGraphDestroy(g);
-                if (ei != hipSuccess) { (void)hipGetLastError(); h->admm_graph = nullptr; set_error("hipGraphInstantiate failed"); return LPVS_EDEVICE; }
-                h->admm_graph_iters = kGraphIters;
-            }
-            while (todo >= h->admm_graph_iters) { LPVS_HIP(hipGraphLaunch(h->admm_graph, s)); todo -= h->admm_graph_iters; }
-        }
-        size_t nxc = 0;                              // corrections of this call (event pairs xc_ev[2 i], xc_ev[2 i + 1])
-        while (todo > 0) {
-            // the correction schedule cuts the run at the iterations base^j, whatever chunks the caller asks for: the iterates do not depend on the chunking
-            int64_t step = todo;
-            long long next_corr = 0;
-            if (h->xcorr()) {
-                next_corr = h->next_correction(h->k_enq);
-                if (next_corr - h->k_enq < step) step = next_corr - h->k_enq;
-            }
-            LPVS_TRY(launch_admm_iterations(p, step, s));
-            if (p.nib_period > 0) for (long long g = p.fi_base; g < p.fi_base + step; ++g) h->n_nib += nib_refresh_due(g, p.nib_period, p.nib_ramp);
-            todo -= step; h->k_enq += step;
-            if (h->xcorr() && h->k_enq == next_corr) {
-                if (h->xc_ev.size() < 2 * (nxc + 1)) {
-                    hipEvent_t ea = nullptr, eb = nullptr;
-                    LPVS_HIP(hipEventCreate(&ea)); h->xc_ev.push_back(ea);
-                    LPVS_HIP(hipEventCreate(&eb)); h->xc_ev.push_back(eb);
-                }
-                LPVS_HIP(hipEventRecord(h->xc_ev[2 * nxc], s));
-                LPVS_TRY(launch_xupdate_correction(p, h->G.as<double>(), h->M_shift, h->xb_refined ? nullptr : h->bs.as<double>(), h->xb0.as<double>(), h->xb.as<double>(), h->corr.as<double>(), s));
-                if (p.nib_period > 0) LPVS_TRY(launch_nibble_refresh(p, false, nullptr, s, /*split=*/true));   // xb_corr = xb - N rhs: the refreshes re-add the nibble term of THEIR right-hand side
-                LPVS_HIP(hipEventRecord(h->xc_ev[2 * nxc + 1], s));
-                ++nxc;
-                if (todo > 0 && !(h->tol > 0)) p.fi_base += step;   // (no stopping test can fire: the device committed exactly `step` more)
-                else if (todo > 0) {   // the next sub-chunk starts from the iteration count the device committed (a stopping test may have fired)
-                    LPVS_HIP(hipMemcpyAsync(st.data(), h->status.p, sizeof(AdmmStatus) * ns, hipMemcpyDeviceToHost, s));
-                    LPVS_HIP(hipStreamSynchronize(s));
-                    bool alls = true;
-                    for (auto &q : st) alls = alls && q.converged;
-                    if (alls) break;
-                    p.fi_base = st[0].iters;
-                }
-            }
-        }
-        LPVS_HIP(hipEventRecord(h->ev[0].b, s));
-        nxc_done = nxc;
-    }
-    LPVS_HIP(hipMemcpyAsync(st.data(), h->status.p, sizeof(AdmmStatus) * ns, hipMemcpyDeviceToHost, s));
-    LPVS_HIP(hipStreamSynchronize(s));
-    for (size_t i = 0; i < nxc_done; ++i) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, h->xc_ev[2 * i], h->xc_ev[2 * i + 1]) == hipSuccess) { h->t_xcorr += ms; h->n_xcorr += 1; } else (void)hipGetLastError();
-    }
-    long long it_max = 0, it0_max = 0; double nxz_max = 0; bool all = true;
-    for (size_t q = 0; q < ns; ++q) {
+    const bool runs = max_iters > 0 && !all0;
+    const IterationKind kind = iteration_kind(iter_facts(p));   // (the iteration option is read per call)
+    size_t nxc = 0;                                  // corrections of this call
+    if (runs) LPVS_TRY(enqueue_run(h, p, kind, max_iters, st, &nxc));
+    LPVS_TRY(read_status(h, st, &all));
+    long long it_max = 0, it0_max = 0; double nxz_max = 0;
+    for (size_t q = 0; q < st.size(); ++q) {
         if (st[q].iters > it_max) it_max = st[q].iters;
         if (st0[q].iters > it0_max) it0_max = st0[q].iters;
         if (st[q].nxz > nxz_max) nxz_max = st[q].nxz;
-        all = all && st[q].converged;
     }
-    if (max_iters > 0 && !all0) { h->t_admm += h->ev[0].ms(); h->admm_iters_timed += (double)(it_max - it0_max); }
-    if (max_iters > 0 && !all0) h->fi_sync = fi_applicable(p) ? (long long)st[0].iters : -1;   // (the other path leaves no records behind)
+    if (runs) fold_timings(h, nxc, it0_max, it_max);
+    if (runs) h->fi_sync = kind == IterationKind::one_launch ? (long long)st[0].iters : -1;   // (the other path leaves no records behind)
     if (iters_done) *iters_done = it_max;     // ns > 1: the slowest signal; per-signal values via lpvs_admm_status
     if (nxz) *nxz = nxz_max;
     if (converged) *converged = all ? 1 : 0;
@@ -1521,9 +1487,10 @@ int32_t lpvs_admm_run(lpvs_problem *h, int64_t max_iters, int64_t *iters_done, d
 int32_t lpvs_admm_matvec_kind(lpvs_problem *h, int32_t *kind) {
     if (!h || !kind) { set_error("NULL argument"); return LPVS_EARGUMENT; }
     if (!h->inited) { set_error("lpvs_admm_matvec_kind before lpvs_admm_init"); return LPVS_ESTATE; }
-    *kind = h->np >= kSymmetricMinNp ? h->Mp_mode : kMpNone;
-    if (fi_applicable(make_params(h)) || small_iter_applicable(make_params(h))) *kind |= 16;   // one launch per iteration (with the prox currently set)
-    if (make_params(h).mp_fix32) *kind |= 32;                                                  // 32-bit fixed-point tiles
+    const AdmmParams p = make_params(h);
+    *kind = h->plan.mode;
+    if (iteration_kind(iter_facts(p)) != IterationKind::two_launch) *kind |= 16;   // one launch per iteration (with the prox currently set)
+    if (p.mp_fix32) *kind |= 32;                                                   // 32-bit fixed-point tiles
     return LPVS_OK;
 }
 
@@ -1553,7 +1520,7 @@ int32_t lpvs_admm_time_matvec(lpvs_problem *h, int32_t reps, double *us_per_laun
         LPVS_HIP(hipStreamSynchronize(s));
         h->nib_us = h->ev[1].ms() * 1e3 / reps;
     }
-    if (bytes_per_launch) *bytes_per_launch = sym ? h->Mp_stream_bytes - (make_params(h).mp_fix32 ? 8192.0 * (double)h->Mp_fixed_tiles : 0.0) : 8.0 * (double)h->np * (double)h->np;   // (32-bit reads: no nibble plane)
+    if (bytes_per_launch) *bytes_per_launch = sym ? mp_stream_bytes(h, p.mp_fix32 != 0) : 8.0 * (double)h->np * (double)h->np;
     return LPVS_OK;
 }
 
@@ -1578,11 +1545,11 @@ int32_t lpvs_admm_status(lpvs_problem *h, int64_t signal, int64_t *iters_done, d
 }
 
 // the offset vector(s): xb, and -- handles that run the stale nibble product -- xb_corr behind it (both are state between two refreshes)
-static bool offset_has_nibble_part(const lpvs_problem *h) { return h->nib_period > 0 && h->xb_corr.p != nullptr; }
+static bool offset_has_nibble_part(const lpvs_problem *h) { return h->plan.nib_period > 0 && h->xb_corr.p != nullptr; }
 int32_t lpvs_admm_offset_len(lpvs_problem *h, int64_t *len) {
     if (!h || !len) { set_error("NULL argument"); return LPVS_EARGUMENT; }
     if (!h->inited) { set_error("lpvs_admm_offset_len before lpvs_admm_init"); return LPVS_ESTATE; }
-    *len = !h->offset_form || !h->xb.p ? 0 : (int64_t)h->ns * h->n * (offset_has_nibble_part(h) ? 2 : 1);
+    *len = !h->plan.offset_form || !h->xb.p ? 0 : (int64_t)h->ns * h->n * (offset_has_nibble_part(h) ? 2 : 1);
     return LPVS_OK;
 }
 static int32_t offset_len_matches(const lpvs_problem *h, int64_t len) {
@@ -1596,7 +1563,7 @@ static int32_t offset_len_matches(const lpvs_problem *h, int64_t len) {
 }
 int32_t lpvs_admm_get_offset_f64(lpvs_problem *h, double *xb_out, int64_t len) {
     if (!h || !xb_out) { set_error("NULL argument"); return LPVS_EARGUMENT; }
-    if (!h->inited || !h->offset_form || !h->xb.p) { set_error("this handle has no offset vector (n < 2048, or lpvs_admm_init has not run)"); return LPVS_ESTATE; }
+    if (!h->inited || !h->plan.offset_form || !h->xb.p) { set_error("this handle has no offset vector (n < 2048, or lpvs_admm_init has not run)"); return LPVS_ESTATE; }
     LPVS_TRY(offset_len_matches(h, len));
     LPVS_HIP(hipSetDevice(h->device));
     LPVS_TRY(copy_state_out(h, h->xb.p, xb_out));
@@ -1605,7 +1572,7 @@ int32_t lpvs_admm_get_offset_f64(lpvs_problem *h, double *xb_out, int64_t len) {
 }
 int32_t lpvs_admm_set_offset_f64(lpvs_problem *h, const double *xb, int64_t len) {
     if (!h || !xb) { set_error("NULL argument"); return LPVS_EARGUMENT; }
-    if (!h->inited || !h->offset_form || !h->xb.p) { set_error("this handle has no offset vector (n < 2048, or lpvs_admm_init has not run)"); return LPVS_ESTATE; }
+    if (!h->inited || !h->plan.offset_form || !h->xb.p) { set_error("this handle has no offset vector (n < 2048, or lpvs_admm_init has not run)"); return LPVS_ESTATE; }
     LPVS_TRY(offset_len_matches(h, len));           // (no length, no way to tell a 36-bit handle's n-vector from a 32-bit handle's 2n: a host out-of-bounds read)
     LPVS_HIP(hipSetDevice(h->device));
     LPVS_TRY(copy_state_in(h, h->xb.p, xb));
@@ -2101,8 +2068,8 @@ struct WinEngine {
         }
         // 32-bit reads of the fixed-point tiles + the stale nibble product (admm.hip) where the batch iterates in one launch: the
         // default, and LPVS_STORAGE_MIXED32 by name; LPVS_STORAGE_MIXED reads all 36 bits.  (The refresh of a batch exists only inside the launch.)
-        if (ab.fi != nullptr && (storage_opt == 0 || storage_opt == LPVS_STORAGE_MIXED32) && !(experiment_env("LPVS_NIB_FUSED") && experiment_env("LPVS_NIB_FUSED")[0] == '0')) {
-            const NibKnobs nib = nib_knobs();
+        if (storage_reads_32_bits(ns, /*f32=*/false, /*corrected=*/ab.fi != nullptr, storage_opt) && !(experiment_env("LPVS_NIB_FUSED") && experiment_env("LPVS_NIB_FUSED")[0] == '0')) {
+            const NibKnobs nib = nib_knobs_from(experiment_env);
             if (nib.period > 0) {
                 if (!xbc.p) LPVS_TRY(xbc.alloc(vb));
                 if (!nibacc.p) LPVS_TRY(nibacc.alloc(vb));

@@ -10,6 +10,7 @@
 
 #include "../../include/lpvspectral.h"
 #include "windows_plan.h"
+#include "admm_plan.h"
 
 namespace lpvs {
 
@@ -278,17 +279,7 @@ bool small_iter_applicable(const AdmmParams &p);
 // xb (written) = xb_corr + N rhs, N = the nibble planes of the packed copy's fixed-point tiles; rhs = p.rhs (from_state = false) or (z - u_src) / mu
 // (split: xb_corr (written) = xb - N rhs instead: after a correction re-formed xb for the right-hand side in memory)
 int32_t launch_nibble_refresh(const AdmmParams &p, bool from_state, const double *u_src, hipStream_t s, bool split = false);
-// is the stale nibble product refreshed after launch g?  An absolute function of g: the iterates do not depend on the chunking.
-inline bool nib_refresh_due(long long g, int period, int ramp) {
-    if (period <= 0) return false;
-    if (ramp <= 0) return g == 1 || g % period == 0;
-    long long p2 = 1;
-    while (2 * p2 <= g) p2 *= 2;                      // 2^floor(log2 g)   (g = 0: 1)
-    long long step = p2 / ramp;
-    if (step < 1) step = 1;
-    if (step > period) step = period;
-    return g % step == 0;
-}
+// (is it refreshed after launch g: nib_refresh_due of admm_plan.h)
 // the one-launch iteration multiplies the nibble planes inside the launches after which a refresh is due (otherwise: launch_nibble_refresh's three kernels)
 bool nib_fused_applies(const AdmmParams &p);
 // one step of iterative refinement for the right-hand side the next x-update multiplies (p.rhs), its residual in twice-the-mantissa
@@ -314,7 +305,6 @@ int32_t launch_pack_tiles_mixed_batch(const double *M, int64_t np, int nbatch, u
 // element conversions for the _f32 entry points (device buffers)
 int32_t launch_cvt_f32_f64(const float *src, double *dst, int64_t count, hipStream_t s);
 int32_t launch_cvt_f64_f32(const double *src, float *dst, int64_t count, hipStream_t s);
-constexpr int64_t kSymmetricMinNp = 2048;  // below this the iteration is launch-latency bound: plain mat-vec
 // batch of nbatch independent problems of one shape: arrays are [nbatch][np]; matrices [nbatch / nrhs][np][np]
 struct AdmmBatch {
     const double *M;
@@ -348,6 +338,26 @@ struct AdmmBatch {
     long long *nib_acc = nullptr;              // [nbatch][np], zero between refreshes
 };
 bool fi_batch_applicable(const AdmmBatch &p);
+// what the predicates of admm_plan.h read of a handle's / a batch's parameters (the iteration option is resolved per call: tests and
+// tools switch it between handles); small_iter_applicable, fi_applicable, fi_batch_applicable and fused_ok are these plus the pure rule
+inline IterFacts iter_facts(const AdmmParams &p) {
+    IterFacts f;
+    f.np = p.np; f.n = p.n; f.ns = p.ns; f.prox_kind = p.prox_kind; f.group_len = p.group_len;
+    f.option_two = option_in_effect(LPVS_OPT_ITERATION, p.opt_iteration) == LPVS_ITERATION_TWO;
+    f.packed = p.Mp != nullptr; f.partials = p.part != nullptr; f.offset = p.xb != nullptr; f.tile_formats = p.mp_types != nullptr;
+    f.split_copy = p.mp_split != 0; f.f32_copy = p.mp_f32 != 0;
+    f.fi = p.fi != nullptr; f.small_ctl = p.sm_ctl != nullptr; f.scratch = p.scratch != nullptr;
+    return f;
+}
+inline IterFacts iter_facts(const AdmmBatch &p) {
+    IterFacts f;
+    f.np = p.np; f.n = p.n; f.ns = p.nbatch; f.prox_kind = p.prox_kind; f.group_len = p.group_len;
+    f.option_two = option_in_effect(LPVS_OPT_ITERATION, p.opt_iteration) == LPVS_ITERATION_TWO;
+    f.packed = p.Mp != nullptr; f.partials = p.part != nullptr; f.offset = p.xb != nullptr; f.tile_formats = p.mp_types != nullptr;
+    f.split_copy = p.mp_split != 0; f.fi = p.fi != nullptr; f.scratch = p.scratch != nullptr;
+    f.nrhs = p.nrhs; f.nbatch = p.nbatch;
+    return f;
+}
 int32_t launch_fi_batch_setup(const AdmmBatch &p, hipStream_t s);   // constants and the records of iteration 0 (after launch_admm_batch_init)
 bool admm_batch_uses_tiles(const AdmmBatch &p);   // will launch_admm_batch_iterations take the tile-packed path for this batch?
 int32_t launch_batch_matvec(const double *A, int64_t np, int nprob, int nrhs, const double *v, double *out, hipStream_t s);   // out_q = A[q / nrhs] v_q
