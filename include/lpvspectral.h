@@ -196,6 +196,11 @@ int32_t lpvs_problem_create_dense_f64(const double *A, const double *y, int64_t 
                                       const double *W, int32_t device, lpvs_problem **out);
 int32_t lpvs_problem_create_gram_f64(const double *G, const double *b, int64_t n, int32_t device,
                                      lpvs_problem **out);
+/* path:    a new handle with ns right-hand sides from a single-signal handle of ANY constructor above (LPVS_EARGUMENT if src has
+ *          several signals, or unless 1 <= ns <= 64): src's kind, sizes, zerofreq, parameter packing, _f32 flag and options; its Gram
+ *          is a device-to-device copy of src's and each of its ns right-hand sides is src's b.  src stays valid and independent (it
+ *          may be destroyed first).  With lpvs_problem_set_prox_per_signal: ns penalties solved in one pass over one inverse. */
+int32_t lpvs_problem_create_path(lpvs_problem *src, int64_t ns, lpvs_problem **out);
 int32_t lpvs_problem_destroy(lpvs_problem *h);
 
 int32_t lpvs_problem_size(const lpvs_problem *h, int64_t *n);
@@ -231,6 +236,17 @@ int32_t lpvs_ls_spectral_f64(const double *y, const double *t, int64_t N, const 
  * returns to the caller so that printing, cb(x,z) and Ctrl-C stay on the host thread
  * (src/lasso.jl:158-163, :59-63).  *iters_done counts iterations since init. */
 int32_t lpvs_problem_set_prox(lpvs_problem *h, int32_t kind, double param, int64_t group_len);
+/* one prox parameter per signal slot of a handle with several right-hand sides (extension: a regularisation path, or one penalty per
+ * channel): params[q] is the lambda -- or the r of LPVS_PROX_BALL_L0 -- of signal q; kind and group_len are shared.  count must be the
+ * handle's number of signals (LPVS_EARGUMENT otherwise, as for a negative or non-finite parameter); params may live on the host or on a
+ * device and is copied.  Checks and invalidates what lpvs_problem_set_prox does; a later lpvs_problem_set_prox returns the handle to
+ * one parameter for all.  Nothing but the prox reads the parameter: Gram, inverse, packing, offset vector and correction schedule are
+ * shared, every signal keeps its own iteration count and stopping test, and signal q's iterates are those of a handle whose
+ * lpvs_problem_set_prox was given params[q]. */
+int32_t lpvs_problem_set_prox_per_signal(lpvs_problem *h, int32_t kind, const double *params, int64_t count, int64_t group_len);
+/* the parameter every signal's prox will read (count = the handle's number of signals): the scalar repeated when no per-signal values
+ * are installed.  out may live on the host or on a device. */
+int32_t lpvs_problem_get_prox_params(lpvs_problem *h, double *out, int64_t count);
 int32_t lpvs_admm_init_f64(lpvs_problem *h, const double *x0, double mu, double tol,
                            int32_t linear_sign);
 int32_t lpvs_admm_run(lpvs_problem *h, int64_t max_iters, int64_t *iters_done, double *nxz,

@@ -217,6 +217,25 @@ function gram_problem(Q::AbstractMatrix, q; device=0)     # ADMM(x, Quadratic(Q,
     Problem(h[], 0)
 end
 
+# ---- regularisation path (extension): ns penalties on one shared inverse -----------------------
+# a handle with ns signal slots from a single-signal problem of any constructor: a copy of its Gram, ns copies of its right-hand side
+function path_problem(src::Problem, ns::Integer)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(@ccall LIB.lpvs_problem_create_path(src.h::Ptr{Cvoid}, Int64(ns)::Int64, h::Ref{Ptr{Cvoid}})::Int32)
+    Problem(h[], src.m, Int(ns))
+end
+# pars[q] is the λ (or the r of IndBallL0) of signal slot q; kind and glen as in proxparams
+function set_prox_per_signal!(p::Problem, kind::Integer, pars, glen::Integer=0)
+    pv = dense(Float64, pars)
+    GC.@preserve pv check(@ccall LIB.lpvs_problem_set_prox_per_signal(p.h::Ptr{Cvoid}, Int32(kind)::Int32, pv::Ptr{Float64},
+        Int64(length(pv))::Int64, Int64(glen)::Int64)::Int32)
+end
+function prox_params(p::Problem)                           # what every slot's prox will read (the scalar repeated if one prox is set)
+    out = zeros(p.ns)
+    GC.@preserve out check(@ccall LIB.lpvs_problem_get_prox_params(p.h::Ptr{Cvoid}, out::Ptr{Float64}, Int64(p.ns)::Int64)::Int32)
+    out
+end
+
 function params(p::Problem, which=0)
     re, im_ = zeros(p.m * p.ns), zeros(p.m * p.ns)
     GC.@preserve re im_ check(@ccall LIB.lpvs_problem_get_params_f64(p.h::Ptr{Cvoid}, Int32(which)::Int32, re::Ptr{Float64}, im_::Ptr{Float64})::Int32)

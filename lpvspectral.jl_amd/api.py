@@ -235,7 +235,8 @@ def _pop_options(kwargs):
 class Problem:
     """Owner of one ``lpvs_problem`` handle (regressor + Gram resident on one MI355X)."""
 
-    ns = 1   # signals sharing the regressor (lpv_multi)
+    ns = 1   # signals sharing the regressor (lpv_multi, path)
+    weighted = False   # fourier(..., W): the estimator runs it as the reference's as-written Quadratic (linear term of the other sign)
     f32 = False   # created from float32 inputs: float I/O, single-precision copy of M in the ADMM mat-vec
 
     def __init__(self, handle, kind):
@@ -263,7 +264,7 @@ class Problem:
         fn = lib().lpvs_problem_create_fourier_f32 if f32 else lib().lpvs_problem_create_fourier_f64
         check(fn(py, pt, N, pf, Nf, pw, int(device), C.byref(h)))
         p = cls(h, "fourier")
-        p.Nf, p.f32 = Nf, f32
+        p.Nf, p.f32, p.weighted = Nf, f32, W is not None
         return p
 
     @classmethod
@@ -363,6 +364,20 @@ class Problem:
         check(lib().lpvs_problem_create_gram_f64(pg, pb, n, int(device), C.byref(h)))
         return cls(h, "gram")
 
+    @classmethod
+    def path(cls, src, ns):
+        """A handle with ``ns`` signal slots from a single-signal problem of any constructor (extension): a device copy of ``src``'s Gram
+        and ``ns`` copies of its right-hand side.  With a list of prox objects in :meth:`set_prox` the slots are ``ns`` penalties solved in
+        one pass over one inverse.  ``src`` stays valid and independent."""
+        h = C.c_void_p()
+        check(lib().lpvs_problem_create_path(src._h, int(ns), C.byref(h)))
+        p = cls(h, src.kind)
+        for name in ("Nf", "nb"):
+            if hasattr(src, name):
+                setattr(p, name, getattr(src, name))
+        p.ns, p.f32, p.weighted = int(ns), src.f32, src.weighted
+        return p
+
     # housekeeping ---------------------------------------------------------------------------
     def close(self):
         if getattr(self, "_h", None):
@@ -439,11 +454,30 @@ class Problem:
         return x
 
     def set_prox(self, proxg):
+        """One prox object for every signal, or a list / tuple of ``ns`` objects of one kind (and one group length): one per signal slot."""
+        if isinstance(proxg, (list, tuple)):
+            if not proxg or not all(hasattr(g, "device_params") for g in proxg):
+                raise NotImplementedError("every entry of a per-signal proxg list must be a prox object with a device kernel")
+            trip = [g.device_params(self.n) for g in proxg]
+            if len({(k, gl) for k, _, gl in trip}) != 1:
+                raise ValueError("the prox objects of a per-signal list must be of one kind and one group length")
+            return self.set_prox_params(trip[0][0], [p for _, p, _ in trip], trip[0][2])
         if not hasattr(proxg, "device_params"):
             raise NotImplementedError(f"proxg of type {type(proxg).__name__} has no device kernel "
                                       "(supported: NormL1, NormL0, IndBallL0, SlicedSeparableSum(NormL2))")
         kind, param, glen = proxg.device_params(self.n)
         check(lib().lpvs_problem_set_prox(self._h, kind, float(param), int(glen)))
+
+    def set_prox_params(self, kind, params, group_len=0):
+        """``lpvs_problem_set_prox_per_signal``: prox ``kind`` (``_lib.PROX_*``) with ``params[q]`` for signal slot ``q`` (``ns`` values)."""
+        pv = np.ascontiguousarray(np.asarray(params, dtype=np.float64).ravel())
+        check(lib().lpvs_problem_set_prox_per_signal(self._h, int(kind), out_ptr(pv), int(pv.size), int(group_len)))
+
+    def get_prox_params(self):
+        """The parameter the prox of every signal slot will read (``ns`` values; the scalar repeated when one object is set)."""
+        out = np.zeros(self.ns)
+        check(lib().lpvs_problem_get_prox_params(self._h, out_ptr(out), int(out.size)))
+        return out
 
     def admm_init(self, x0=None, μ=0.05, tol=1e-5, linear_sign=_lib.LINEAR_LEAST_SQUARES):
         k0, p0, n0 = (as_f32 if self.f32 else as_f64)(x0)
@@ -730,6 +764,87 @@ def ls_sparse_spectral_lpv(y, X, V, w, Nv, λ=1, coulomb=False, normalize=True, 
             log.info("Aborting")
             params = prob.params(1)                                  # z = copy(x)
     return SpectralExt(y, X, V, w, Nv, λ, coulomb, normalize, params, None)
+
+
+# --------------------------------------------------------------------------- regularisation paths (extension)
+def lambda_max(prob, proxg_kind, group_len=0):
+    """The smallest penalty whose solution is all-zero, from the handle's right-hand side ``b = A'y``: the KKT conditions of
+    ``½‖Ax−y‖² + λ g(x)`` at ``x = 0`` are ``‖b‖∞ ≤ λ`` for ``NormL1`` and ``max_g ‖b_g‖₂ ≤ λ`` for the grouped lasso (contiguous groups of
+    ``group_len``).  ``proxg_kind``: a prox class, object or ``_lib.PROX_*`` id.  ``NormL0`` / ``IndBallL0`` have no such value, and the
+    weighted Fourier problem runs as the reference's as-written ``Quadratic``, whose linear term has the other sign: ``ValueError``.
+    A handle with several signals gives one value per signal."""
+    kind = getattr(proxg_kind, "kind", proxg_kind)
+    if kind not in (_lib.PROX_L1, _lib.PROX_GROUP_L2):
+        raise ValueError("lambda_max is defined for NormL1 and the grouped lasso only (NormL0 / IndBallL0 have no penalty that gives x = 0)")
+    if getattr(prob, "weighted", False):
+        raise ValueError("lambda_max: the weighted problem is the as-written Quadratic (linear term of the other sign), not ½‖Ax−y‖²")
+    B = np.abs(np.asarray(prob.get_rhs(), dtype=np.float64).reshape(prob.n, -1, order="F"))
+    if kind == _lib.PROX_GROUP_L2:
+        gl = int(group_len or getattr(proxg_kind, "group_len", 0))
+        if gl <= 0:
+            raise ValueError("lambda_max of the grouped lasso needs group_len > 0")
+        ng = prob.n // gl
+        out = np.sqrt((B[:ng * gl] ** 2).reshape(ng, gl, -1).sum(axis=1)).max(axis=0)
+    else:
+        out = B.max(axis=0)
+    return float(out[0]) if out.size == 1 else out
+
+
+def lambda_grid(lmax, count, ratio=1e-3):
+    """``count`` penalties, geometric from ``lmax`` down to ``ratio·lmax`` (both end points exact; ``count = 1``: ``[lmax]``)."""
+    count = int(count)
+    if count < 1 or not (lmax > 0) or not (0 < ratio <= 1):
+        raise ValueError("lambda_grid needs count >= 1, lmax > 0 and 0 < ratio <= 1")
+    if count == 1:
+        return np.array([float(lmax)])
+    return float(lmax) * float(ratio) ** (np.arange(count) / (count - 1.0))
+
+
+def _path_proxgs(src, λs, nλ, proxg, make, kind, group_len):
+    """The prox objects of a path and the value each stands for: ``proxg`` (a list, e.g. ``[IndBallL0(4), IndBallL0(8)]``) as given, else
+    ``make(λ)`` over ``λs`` (``None``: ``lambda_grid(lambda_max(src, ...), nλ)``)."""
+    if proxg is not None:
+        gs = list(proxg)
+        return gs, np.array([float(g.device_params(src.n)[1]) for g in gs])
+    if λs is None:
+        λs = lambda_grid(lambda_max(src, kind, group_len), nλ)
+    λs = np.asarray(λs, dtype=np.float64).ravel()
+    return [make(l) for l in λs], λs
+
+
+def ls_sparse_spectral_path(y, t, f=None, W=None, λs=None, nλ=8, proxg_kind=NormL1, **kwargs):
+    """:func:`ls_sparse_spectral` for a whole regularisation path (extension) -> ``(params[Nf, nλ], f, λs)``: column ``q`` is the estimate
+    with ``proxg_kind(λs[q])``.  One Gram, one factorisation and one pass over the inverse per iteration serve every penalty; each column
+    stops at its own ``‖x−z‖₂ < tol``.  ``λs=None``: ``lambda_grid(lambda_max(...), nλ)``; ``proxg=[IndBallL0(4), IndBallL0(8), …]``
+    gives an ``r``-path (``λs`` returned: the ``r``); ``group_len=`` with ``proxg_kind=SlicedSeparableSum``."""
+    f = default_freqs(t) if f is None else f
+    device, proxg, gl = kwargs.pop("device", 0), kwargs.pop("proxg", None), int(kwargs.pop("group_len", 0))
+    with default_options(**_pop_options(kwargs)):
+        with Problem.fourier(y, t, f, W, device=device) as src:
+            make = (lambda l: SlicedSeparableSum.frequency_groups(l, src.n // gl, gl)) if proxg_kind is SlicedSeparableSum else proxg_kind
+            gs, vals = _path_proxgs(src, λs, nλ, proxg, make, proxg_kind, gl)
+            prob = Problem.path(src, len(gs))
+        with prob:
+            sign = _lib.LINEAR_LEAST_SQUARES if W is None else _lib.LINEAR_QUADRATIC_AS_WRITTEN
+            _admm_on_problem(prob, None, gs, sign, **kwargs)
+            params = prob.params(0).reshape(prob.Nf, -1, order="F")
+    return params, _host(f), vals
+
+
+def ls_sparse_spectral_lpv_path(y, X, V, w, Nv, λs=None, nλ=8, proxg=None, normalize=True, **kwargs):
+    """:func:`ls_sparse_spectral_lpv` for a whole regularisation path (extension) -> a list of :class:`SpectralExt`, one per penalty of
+    the frequency-grouped lasso, each with its own ``λ``.  Rules as :func:`ls_sparse_spectral_path`."""
+    w = _host_vec(w) if not _lib.is_device_array(w) else w
+    Nf, Nv = len(w), int(Nv)
+    device = kwargs.pop("device", 0)
+    with default_options(**_pop_options(kwargs)):
+        with Problem.lpv(y, X, V, w, Nv, normalize, False, device=device) as src:
+            gs, vals = _path_proxgs(src, λs, nλ, proxg, lambda l: SlicedSeparableSum.frequency_groups(l, Nf, 2 * Nv), SlicedSeparableSum, 2 * Nv)
+            prob = Problem.path(src, len(gs))
+        with prob:
+            _admm_on_problem(prob, None, gs, _lib.LINEAR_LEAST_SQUARES, **kwargs)
+            P = prob.params(0).reshape(Nf * Nv, -1, order="F")
+    return [SpectralExt(y, X, V, w, Nv, float(vals[q]), False, normalize, P[:, q].copy(), None) for q in range(len(gs))]
 
 
 def lpv_ranges(X, V):

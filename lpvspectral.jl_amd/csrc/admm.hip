@@ -379,8 +379,9 @@ admm_prox_kernel(AdmmParams p) {
     };
 
     const int kind = p.prox_kind;
-    double thr_l1 = mu * p.prox_param, thr_l0 = sqrt(2.0 * mu * p.prox_param);
-    unsigned long long ball_thr = 0; long long ball_keep_eq = 0, ball_eq_count = 0, ball_r = (long long)p.prox_param;
+    const double param = prox_param_of(p, sg);
+    double thr_l1 = mu * param, thr_l0 = sqrt(2.0 * mu * param);
+    unsigned long long ball_thr = 0; long long ball_keep_eq = 0, ball_eq_count = 0, ball_r = (long long)param;
     double *vbuf = n <= PASS ? sq : p.scratch + 2 * so;   // v = x + u is scanned 8 times: keep it in LDS when it fits
     unsigned int *key32 = reinterpret_cast<unsigned int *>(lds2);
     unsigned int thr32 = 0;
@@ -399,7 +400,7 @@ admm_prox_kernel(AdmmParams p) {
 
     if (kind == LPVS_PROX_GROUP_L2) {
         const int64_t gl = p.group_len, ng = n / gl;
-        const double lm = p.prox_param * mu;
+        const double lm = param * mu;
         const int64_t gpp = PASS / gl;                         // whole groups per pass
         for (int64_t g0 = 0; g0 < ng; g0 += gpp) {
             const int64_t gcount = (ng - g0 < gpp) ? ng - g0 : gpp;
@@ -1121,7 +1122,7 @@ admm_fused_update_kernel(AdmmParams p, const double *__restrict__ part1_all, con
     const double ui = ok ? p.u[gi] : 0.0, bi = ok ? (offset_form ? p.xb[gi] : p.b[gi]) : 0.0;   // in flight together with the partials
     double xi = gather_x4(part1, part2, nblk, I, sh);
     if (offset_form) xi += bi;                                   // (bi holds xb here)
-    const double zi = block_prox(p, xi + ui, row, i, sq, gs);
+    const double zi = block_prox(p, sg, xi + ui, row, i, sq, gs);
     const double d2 = row ? row_update(p, gi, xi, ui, bi, zi, ok, offset_form) : 0.0;
     // block sum of d2: the two row waves reduce by shuffles (fixed pattern -> reproducible)
     const double wsum = wave_sum(d2);
@@ -1243,7 +1244,7 @@ admm_fused_update2_kernel(AdmmParams p, const double *__restrict__ part1_all, co
         xi = gq == 0 ? ((sacc + sh[i]) + sh[TS + i]) + sh[2 * TS + i] : 0.0;
     }
     if (offset_form) xi += bi;                                       // (bi holds xb here)
-    const double zi = block_prox(p, xi + ui, row, i, sq, gs);
+    const double zi = block_prox(p, sg, xi + ui, row, i, sq, gs);
     const double d2 = row ? row_update(p, gi, xi, ui, bi, zi, ok, offset_form) : 0.0;
     const double wsum = wave_sum(d2);
     __syncthreads();
@@ -1286,7 +1287,7 @@ admm_window_update_kernel(AdmmParams p, const double *__restrict__ part1_all, co
     for (int e = 1; e < 8; ++e) xi += a[e];                    // fixed order: tile column 0, 1, ...
     const bool offset_form = p.xb != nullptr;                  // x = xb + M~ (z-u)/mu (reduced-precision copy of M, see the split kernel)
     if (offset_form) xi += ok ? p.xb[gi] : 0.0;
-    const double zi = block_prox(p, xi + ui, true, i, sq + I * TS, gs + I * TS);   // (every thread holds a row; its row block's slices)
+    const double zi = block_prox(p, sg, xi + ui, true, i, sq + I * TS, gs + I * TS);   // (every thread holds a row; its row block's slices)
     const double w = wave_sum(row_update(p, gi, xi, ui, bi, zi, ok, offset_form));
     if ((threadIdx.x & 63) == 0) wsum_s[threadIdx.x >> 6] = w;
     __syncthreads();
@@ -1353,9 +1354,10 @@ admm_batch_prox_kernel(AdmmBatch p) {
         R[i] = t.rhs;
         ss = fma(t.d, t.d, ss);
     };
+    const double param = prox_param_of(p, q);
     if (p.prox_kind == LPVS_PROX_GROUP_L2) {
         const int64_t gl = p.group_len, ng = n / gl;
-        const double lm = p.prox_param * mu;
+        const double lm = param * mu;
         for (int64_t g = threadIdx.x; g < ng; g += 256) {
             double s2 = 0;
             for (int64_t k = 0; k < gl; ++k) { const double v = X[g * gl + k] + U[g * gl + k]; s2 += v * v; }
@@ -1368,7 +1370,7 @@ admm_batch_prox_kernel(AdmmBatch p) {
         }
         for (int64_t i = ng * gl + threadIdx.x; i < n; i += 256) finish(i, X[i], U[i], Z[i]);
     } else {
-        const double gl1 = mu * p.prox_param, th0 = sqrt(2.0 * mu * p.prox_param);
+        const double gl1 = mu * param, th0 = sqrt(2.0 * mu * param);
         for (int64_t i = threadIdx.x; i < n; i += 256) {
             const double xi = X[i], ui = U[i], v = xi + ui;
             const double zi = p.prox_kind == LPVS_PROX_L1 ? prox_l1(v, gl1) : prox_l0(v, th0);
@@ -1659,6 +1661,7 @@ int32_t launch_admm_iterations(const AdmmParams &p, int64_t iters, hipStream_t s
                 // small problems: the light 256-thread kernel (no 128 KiB LDS image) has the shorter latency
                 AdmmBatch q{p.M, p.np, p.n, p.ns, p.b, p.x, p.z, p.u, p.rhs, p.mu, p.tol, p.prox_kind, p.prox_param, p.group_len,
                             p.status, nullptr, nullptr, 1};
+                q.prox_params = p.prox_params;
                 hipLaunchKernelGGL(admm_batch_prox_kernel, dim3((unsigned)p.ns), dim3(256), 0, s, q);
             } else {
                 hipLaunchKernelGGL(admm_prox_kernel, dim3((unsigned)p.ns), dim3(1024), 0, s, p);

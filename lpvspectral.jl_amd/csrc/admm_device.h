@@ -305,19 +305,25 @@ __device__ __forceinline__ DualStep dual_step(double xi, double ui, double zi, d
     return {d, un, ok ? (offset_form ? (zi - un) / mu : bi + (zi - un) / mu) : 0.0};
 }
 
-// the prox of one 128-row block held one element per thread (`row`: this thread holds element i of the block; sq / gs: TS doubles of
+// the prox parameter of signal slot sg: the handle's per-signal array when one is installed, else the scalar.  Uniform over a workgroup
+// (sg comes from the block index): one scalar load.
+template <class P>
+__device__ __forceinline__ double prox_param_of(const P &p, int sg) { return p.prox_params ? p.prox_params[sg] : p.prox_param; }
+
+// the prox of one 128-row block of signal sg held one element per thread (`row`: this thread holds element i of the block; sq / gs: TS doubles of
 // LDS each).  Element-wise for L1 / L0; for groups (128 % group_len == 0) the squares go through LDS and one lane per group sums them
 // sequentially, as norm() on the slice.  Every thread of the workgroup calls it (two barriers in the group branch).
-__device__ __forceinline__ double block_prox(const AdmmParams &p, double v, bool row, int i, double *sq, double *gs) {
-    if (p.prox_kind == LPVS_PROX_L1) return prox_l1(v, p.mu * p.prox_param);
-    if (p.prox_kind == LPVS_PROX_L0) return prox_l0(v, sqrt(2.0 * p.mu * p.prox_param));
+__device__ __forceinline__ double block_prox(const AdmmParams &p, int sg, double v, bool row, int i, double *sq, double *gs) {
+    const double param = prox_param_of(p, sg);
+    if (p.prox_kind == LPVS_PROX_L1) return prox_l1(v, p.mu * param);
+    if (p.prox_kind == LPVS_PROX_L0) return prox_l0(v, sqrt(2.0 * p.mu * param));
     const int gl = (int)p.group_len;
     if (row) sq[i] = v * v;
     __syncthreads();
     if (row & (i < TS / gl)) {                              // one lane per group (a single branch)
         double s2 = 0;
         for (int q = 0; q < gl; ++q) s2 += sq[i * gl + q];
-        gs[i] = group_scale(s2, p.prox_param * p.mu);
+        gs[i] = group_scale(s2, param * p.mu);
     }
     __syncthreads();
     return row ? gs[i / gl] * v : 0.0;

@@ -82,6 +82,7 @@ admm_small_iter_kernel(AdmmParams p, int j /* launch of the chunk: 0 = first */)
         if (was_conv) { if (blockIdx.x == 0 && threadIdx.x == 0) ctl[j & 1] = 1; return; }
         // ---- update of iteration (base + j): z = prox(x + u), u += x - z, rhs = b + (z - u)/mu, ||x - z||     src/lasso.jl:153-157
         double zv[EPT], vv[EPT];
+        const double param = prox_param_of(p, sg);
 #pragma unroll
         for (int k = 0; k < EPT; ++k) { const int i = threadIdx.x + NT * k; vv[k] = i < n ? xv[k] + uv[k] : 0.0; }
         if (p.prox_kind == LPVS_PROX_GROUP_L2) {
@@ -94,10 +95,10 @@ admm_small_iter_kernel(AdmmParams p, int j /* launch of the chunk: 0 = first */)
                 const int i = threadIdx.x + NT * k;
                 double s2 = 0;
                 if (i < n) { const double *grp = sv + (i / gl) * gl; for (int q = 0; q < gl; ++q) s2 += grp[q]; }   // the same sequential order as norm() on the slice
-                zv[k] = i < n ? group_scale(s2, p.prox_param * p.mu) * vv[k] : 0.0;
+                zv[k] = i < n ? group_scale(s2, param * p.mu) * vv[k] : 0.0;
             }
         } else {
-            const double gl1 = p.mu * p.prox_param, th0 = sqrt(2.0 * p.mu * p.prox_param);
+            const double gl1 = p.mu * param, th0 = sqrt(2.0 * p.mu * param);
 #pragma unroll
             for (int k = 0; k < EPT; ++k) {
                 const double v = vv[k];

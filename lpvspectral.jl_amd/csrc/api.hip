@@ -374,6 +374,7 @@ struct lpvs_problem {
     DevBuf xb0, corr; XcorrSchedule xcorr; long long k_enq = 0; bool xb_refined = false;
     DevBuf fi; long long fi_sync = -1; double fi_R = 0, fi_xbmax = 0;      // one-launch iteration (AdmmParams::fi): its records are those of iteration fi_sync
     int prox_kind = LPVS_PROX_L1; double prox_param = 1.0; int64_t group_len = 0;
+    DevBuf prox_params; bool prox_per_signal = false;   // lpvs_problem_set_prox_per_signal: ns parameters, one per signal slot (AdmmParams::prox_params)
     double mu = 0.05, tol = 1e-5; int sign = 1; bool inited = false;
     // timing (ms) -- see lpvs_problem_get_timing
     double t_basis = 0, t_gram = 0, t_reduce = 0, t_factor = 0, t_admm = 0, gram_launches = 0, gram_flops = 0, admm_iters_timed = 0, gram_form = 0;
@@ -496,6 +497,7 @@ AdmmParams make_params(const lpvs_problem *h) {
         p.tile_order = p.fi != nullptr && !(e && std::string(e) == "forward") ? 1 : 0;
     }
     p.sm_ctl = !sym && h->sm_ctl.p ? h->sm_ctl.as<int>() : nullptr;
+    p.prox_params = h->prox_per_signal && h->ns > 1 ? h->prox_params.as<double>() : nullptr;   // (ns == 1: prox_param holds the one value; the one-launch iteration reads only that)
     return p;
 }
 
@@ -1407,7 +1409,60 @@ int32_t lpvs_problem_set_prox(lpvs_problem *h, int32_t kind, double param, int64
     if (!h) { set_error("NULL handle"); return LPVS_EARGUMENT; }
     LPVS_TRY(check_prox(kind, group_len));
     h->prox_kind = kind; h->prox_param = param; h->group_len = group_len;
+    h->prox_per_signal = false;
     h->drop_graph();   // kernel parameters are baked into the captured graph
+    return LPVS_OK;
+}
+
+int32_t lpvs_problem_set_prox_per_signal(lpvs_problem *h, int32_t kind, const double *params, int64_t count, int64_t group_len) {
+    if (!h || !params) { set_error("NULL argument"); return LPVS_EARGUMENT; }
+    LPVS_TRY(check_prox(kind, group_len));
+    if (count != h->ns) { set_error("%lld prox parameters for a handle of %lld signals", (long long)count, (long long)h->ns); return LPVS_EARGUMENT; }
+    LPVS_HIP(hipSetDevice(h->device));
+    std::vector<double> hp;
+    LPVS_TRY(fetch_host(hp, params, count));
+    for (int64_t q = 0; q < count; ++q)
+        if (!(hp[(size_t)q] >= 0) || !std::isfinite(hp[(size_t)q])) { set_error("prox parameter %lld is negative or not finite", (long long)q); return LPVS_EARGUMENT; }
+    if (!h->prox_params.p) LPVS_TRY(h->prox_params.alloc(sizeof(double) * (size_t)h->ns));
+    LPVS_TRY(copy_to_device(h->prox_params.p, hp.data(), sizeof(double) * (size_t)count, h->stream));   // (behind every launch enqueued so far)
+    h->prox_kind = kind; h->prox_param = hp[0]; h->group_len = group_len;
+    h->prox_per_signal = true;
+    h->drop_graph();   // the captured graph holds the pointer argument (null for a scalar prox)
+    return LPVS_OK;
+}
+
+int32_t lpvs_problem_get_prox_params(lpvs_problem *h, double *out, int64_t count) {
+    if (!h || !out) { set_error("NULL argument"); return LPVS_EARGUMENT; }
+    if (count != h->ns) { set_error("room for %lld prox parameters, the handle has %lld signals", (long long)count, (long long)h->ns); return LPVS_EARGUMENT; }
+    LPVS_HIP(hipSetDevice(h->device));
+    std::vector<double> hp((size_t)count, h->prox_param);
+    if (make_params(h).prox_params) LPVS_TRY(copy_from_device(hp.data(), h->prox_params.p, sizeof(double) * (size_t)count, h->stream));
+    return copy_out(out, hp.data(), (size_t)count);
+}
+
+int32_t lpvs_problem_create_path(lpvs_problem *src, int64_t ns, lpvs_problem **out) {
+    if (!src) { set_error("NULL handle"); return LPVS_EARGUMENT; }
+    if (src->ns != 1) { set_error("lpvs_problem_create_path needs a single-signal source (it has %lld signals)", (long long)src->ns); return LPVS_EARGUMENT; }
+    if (ns < 1 || ns > 64) { set_error("ns = %lld outside [1, 64]", (long long)ns); return LPVS_EARGUMENT; }
+    lpvs_problem *h = nullptr;
+    LPVS_TRY(problem_begin(src->device, out, &h));
+    struct Guard { lpvs_problem *h; ~Guard() { delete h; } } guard{h};
+    hipStream_t s = h->stream;
+    h->kind = src->kind; h->N = src->N; h->Nf = src->Nf; h->nb = src->nb; h->zerofreq = src->zerofreq; h->n = src->n; h->np = src->np; h->ns = ns;
+    h->f32 = src->f32;
+    for (int i = 0; i < kOptCount; ++i) h->opt[i] = src->opt[i];
+    h->prox_kind = src->prox_kind; h->prox_param = src->prox_param; h->group_len = src->group_len;
+    const size_t gbytes = sizeof(double) * (size_t)h->np * (size_t)h->np, vbytes = sizeof(double) * (size_t)h->np;
+    LPVS_TRY(h->G.alloc(gbytes));
+    LPVS_TRY(h->b.alloc(vbytes * (size_t)ns));
+    LPVS_TRY(alloc_state(h));
+    LPVS_HIP(hipStreamSynchronize(src->stream));     // (whatever the source's stream still writes into its Gram)
+    LPVS_HIP(hipMemcpyAsync(h->G.p, src->G.p, gbytes, hipMemcpyDeviceToDevice, s));
+    for (int64_t q = 0; q < ns; ++q)                 // every right-hand side is the source's
+        LPVS_HIP(hipMemcpyAsync(h->b.as<double>() + q * h->np, src->b.p, vbytes, hipMemcpyDeviceToDevice, s));
+    LPVS_HIP(hipStreamSynchronize(s));
+    guard.h = nullptr;
+    *out = h;
     return LPVS_OK;
 }
 

@@ -252,11 +252,16 @@ struct AdmmParams {
     // nib_period.  nib_period = 0: off.  xb_corr: the offset vector without any nibble term; nib_rhs: np doubles of scratch.
     int nib_period = 0;
     int nib_ramp = 0;   // > 0: the first refreshes are denser -- the period is min(nib_period, max(1, 2^floor(log2 g) / nib_ramp)) (the right-hand side moves fastest in the first iterations)
+    int mp_fix32 = 0;  // the fixed-point tiles keep 32 significant bits: their nibbles are zero and are not read (handles whose x-update is corrected: the storage error's systematic part leaves the iteration with the inverse's)
     const double *xb_corr = nullptr;
     double *nib_rhs = nullptr;
     long long *nib_acc = nullptr;   // np integers, zero between refreshes: the one-launch iteration's sums of the nibble planes' product (admm_iter_mixed_kernel<..., NIBR>)
     double *nib_part = nullptr;   // the nibble product's own per-tile partials (2 ntiles TS doubles: the two-launch iteration's are in flight in `part` when a refresh runs)
-    int mp_fix32 = 0;  // the fixed-point tiles keep 32 significant bits: their nibbles are zero and are not read (handles whose x-update is corrected: the storage error's systematic part leaves the iteration with the inverse's)
+    // one prox parameter per signal slot (lpvs_problem_set_prox_per_signal): ns doubles in device memory, read through prox_param_of
+    // (admm_device.h) by every update a handle with ns > 1 can reach; nullptr = prox_param for all (window batches and one-launch handles:
+    // always).  It sits where mp_fix32 and its padding sat (mp_fix32 now fills the gap behind nib_ramp): the struct is a kernel argument,
+    // and neither its size nor the offset of any other member has changed.
+    const double *prox_params = nullptr;
     const unsigned char *mp_types = nullptr;   // mixed storage: per-tile format, 1 = 36-bit fixed point (admm.hip); several right-hand sides: diagonal tiles always 0
     // offset form of the x-update (single-problem tile-packed path): x = xb + M (z-u)/mu with xb = M b computed once from
     // the full-precision inverse; the per-iteration product then never multiplies the large constant vector b by the
@@ -321,7 +326,7 @@ struct AdmmBatch {
     const double *Mp;     // [nbatch / nrhs] tile-packed lower triangles (or nullptr: plain mat-vec)
     int nrhs = 1;         // problems per matrix: problem q uses matrix q / nrhs (signals sharing a window's Gram)
     const double *xb = nullptr;   // offset form: x = xb + M~ (z-u)/mu, xb = M b per problem ([nbatch][np]); nullptr: classic
-    int mp_split = 0;     // Mp holds 6-byte elements (float head + 16-bit tail)
+    const double *prox_params = nullptr;   // [nbatch] per-problem prox parameters (AdmmParams::prox_params; in mp_split's old place, as there); nullptr = prox_param for all
     const unsigned char *mp_types = nullptr;   // mixed storage: [matrix][tile] formats (1 = 36-bit fixed point), see admm.hip
     // one-launch iteration for the whole batch (admm.hip; nrhs == 1, mixed storage, offset form, fusable prox): fi_doubles(np, nbatch)
     // doubles of accumulators / records, iterations committed before the chunk about to be launched, "every tile is fixed point"
@@ -329,6 +334,7 @@ struct AdmmBatch {
     long long fi_base = 0;
     int fi_prefetch_all = 0;
     int opt_iteration = 0, opt_nt_loads = 0;   // LPVS_OPT_ITERATION / LPVS_OPT_NT_LOADS of the call (0: thread default / environment)
+    int mp_split = 0;                          // Mp holds 6-byte elements (float head + 16-bit tail)
     double *scratch = nullptr;                 // IndBallL0 with n > 8192: 2 * np doubles per problem (selection keys), else unused
     const double *x0 = nullptr;                // init = true: the starting point of every problem ([nbatch][np]); nullptr: zeros
     // 32-bit reads of the fixed-point tiles with the stale nibble product (AdmmParams: nib_period, nib_ramp, xb_corr, nib_acc), one-launch batches only:
