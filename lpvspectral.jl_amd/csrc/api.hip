@@ -1029,8 +1029,7 @@ static int32_t create_lpv_impl(const double *y, int64_t ns, const double *X, con
     LPVS_TRY(dy.set(y, N * ns, s)); LPVS_TRY(dX.set(X, N, s)); LPVS_TRY(dV.set(V, N, s)); LPVS_TRY(dw.set(w, Nf, s));
     LPVS_TRY(h->G.alloc(sizeof(double) * (size_t)h->np * (size_t)h->np));
     LPVS_TRY(h->b.alloc(sizeof(double) * (size_t)h->np * (size_t)ns));
-    LPVS_HIP(hipMemsetAsync(h->G.p, 0, h->G.bytes, s));
-    LPVS_HIP(hipMemsetAsync(h->b.p, 0, h->b.bytes, s));
+    LPVS_HIP(hipMemsetAsync(h->b.p, 0, h->b.bytes, s));   // (G: below, once the Gram form is known)
     LPVS_TRY(alloc_state(h));
 
     // ---- Gram form.  LPVS_GRAM_FORM = auto (default) | ap | krs | kr
@@ -1051,6 +1050,17 @@ static int32_t create_lpv_impl(const double *y, int64_t ns, const double *X, con
         sl = make_ap_slots(hw, xam);
         use_ap = sl.ok;
         if (form == "ap" && !use_ap) { set_error("LPVS_GRAM_FORM=ap but w is not an arithmetic progression (max|eps|*max|x| = %.3g)", sl.emax * xam); return LPVS_EARGUMENT; }
+    }
+    // The structured assembly writes every element of the n x n block: only the pad strips (rows and columns n .. np) need zeros.
+    // The dense forms accumulate into / leave parts of G: they get the whole of it zeroed.
+    if (use_ap) {
+        const int64_t n = h->n, np = h->np;
+        if (np > n) {
+            LPVS_HIP(hipMemsetAsync(h->G.as<double>() + n * np, 0, sizeof(double) * (size_t)(np - n) * (size_t)np, s));
+            LPVS_HIP(hipMemset2DAsync(h->G.as<double>() + n, sizeof(double) * (size_t)np, 0, sizeof(double) * (size_t)(np - n), (size_t)n, s));
+        }
+    } else {
+        LPVS_HIP(hipMemsetAsync(h->G.p, 0, h->G.bytes, s));
     }
     if (use_ap) {
         const int64_t nf8 = sl.nf8, nsl = sl.nsl, P = nb * (nb + 1) / 2;

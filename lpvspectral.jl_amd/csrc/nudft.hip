@@ -304,12 +304,8 @@ ap_rhs_fourier_kernel(const double *__restrict__ tab_all, const double *__restri
 
 // G[a][b] = G[b][a], a >= b, from the slot tables tab[slot][q][4]; slots 0..Nf-1 are the differences m = f-f',
 // slots s0..s0+2Nf-2 the sums s = f+f' (s0 = Nf rounded up to a multiple of 8).
-__global__ void __launch_bounds__(256)
-ap_assemble_kernel(const double *__restrict__ tab, const double *__restrict__ eps, int Nf, int s0, double delta, int nb, int P, int64_t n,
-                   double *__restrict__ G, int64_t ldg) {
-    const int64_t ga = blockIdx.y;
-    const int64_t gb = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (gb > ga || ga >= n) return;
+__device__ __forceinline__ double ap_gram_value(const double *__restrict__ tab, const double *__restrict__ eps, int s0, double delta, int nb, int P,
+                                                int64_t ga, int64_t gb) {
     const int g2 = 2 * nb;
     const int fa = (int)(ga / g2), ra = (int)(ga - (int64_t)fa * g2), ca = ra >= nb, ja0 = ra - ca * nb;
     const int fb = (int)(gb / g2), rbm = (int)(gb - (int64_t)fb * g2), cb = rbm >= nb, jb0 = rbm - cb * nb;
@@ -327,8 +323,38 @@ ap_assemble_kernel(const double *__restrict__ tab, const double *__restrict__ ep
     else if (ca && cb) v = 0.5 * (cm - cp);                 // -sin * -sin
     else if (!ca && cb) v = -0.5 * (sp - sm);               //  cos(w_f x) * -sin(w_f' x)
     else v = -0.5 * (sp + sm);                              // -sin(w_f x) *  cos(w_f' x)
-    G[ga * ldg + gb] = v;
-    G[gb * ldg + ga] = v;
+    return v;
+}
+// Workgroup = one 32 x 32 tile of G on or below the diagonal (blockIdx.y = tile row >= blockIdx.x = tile column).  Every value a >= b
+// is computed once and stored along its row; the mirror image goes out from a padded LDS copy of the tile, again along rows: both
+// stores are 256-byte runs (the mirrored store used to put a wave's 64 lanes ldg * 8 bytes apart).  A diagonal tile writes its lower
+// triangle from registers and its strict upper triangle from LDS: every element of G[0..n)[0..n) is written exactly once.
+constexpr int AP_TILE = 32;
+__global__ void __launch_bounds__(256)
+ap_assemble_kernel(const double *__restrict__ tab, const double *__restrict__ eps, int Nf, int s0, double delta, int nb, int P, int64_t n,
+                   double *__restrict__ G, int64_t ldg) {
+    (void)Nf;
+    if (blockIdx.x > blockIdx.y) return;
+    __shared__ double tile[AP_TILE][AP_TILE + 1];
+    const int tx = threadIdx.x & (AP_TILE - 1), ty = threadIdx.x / AP_TILE;   // 32 x 8 threads, four rows each
+    const int64_t row0 = (int64_t)blockIdx.y * AP_TILE, col0 = (int64_t)blockIdx.x * AP_TILE;
+#pragma unroll
+    for (int u = 0; u < AP_TILE / 8; ++u) {
+        const int r = ty + 8 * u;
+        const int64_t ga = row0 + r, gb = col0 + tx;
+        if (ga < n && gb <= ga) {
+            const double v = ap_gram_value(tab, eps, s0, delta, nb, P, ga, gb);
+            tile[r][tx] = v;
+            G[ga * ldg + gb] = v;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < AP_TILE / 8; ++u) {
+        const int r = ty + 8 * u;
+        const int64_t R = col0 + r, C = row0 + tx;           // mirror element (R, C) = value (C, R), strictly above the diagonal
+        if (C < n && R < C) G[R * ldg + C] = tile[tx][r];
+    }
 }
 
 // b[f*2nb + j] = sum y K_j cos(w_f x),  b[f*2nb + nb + j] = -sum y K_j sin(w_f x)   from tab[f][j][4] at the
@@ -422,7 +448,7 @@ int32_t launch_ap_rhs_fourier(const double *tab, const double *eps, int64_t Nf, 
 int32_t launch_ap_assemble(const double *tab, const double *eps, int64_t Nf, int64_t s0, double delta, int64_t nb, int64_t n, double *G,
                            int64_t ldg, hipStream_t s) {
     const int P = (int)(nb * (nb + 1) / 2);
-    dim3 grid((unsigned)ceil_div(n, 256), (unsigned)n);
+    dim3 grid((unsigned)ceil_div(n, AP_TILE), (unsigned)ceil_div(n, AP_TILE));
     hipLaunchKernelGGL(ap_assemble_kernel, grid, dim3(256), 0, s, tab, eps, (int)Nf, (int)s0, delta, (int)nb, P, n, G, ldg);
     LPVS_HIP(hipGetLastError());
     return LPVS_OK;

@@ -15,8 +15,10 @@
 // Work at cfg3 (N = 2^20, 1032 slots, 72 weight vectors): 1.2e9 fixed-point accumulations + 3e8 complex MACs instead of 1.6e11 FMAs.
 //
 // DETERMINISM.  Spreading is a scatter; floating-point atomics would make the result depend on the order the hardware
-// happens to serve them in.  The grid is therefore accumulated in 64-bit FIXED POINT (LDS ds_add_u64, then integer sums
-// over the sample chunks): integer addition is associative, so the result does not depend on any order.  A weight vector's
+// happens to serve them in.  The grid is therefore accumulated in 64-bit FIXED POINT (integer sums per sample chunk, then integer sums
+// over the chunks): integer addition is associative, so the result does not depend on any order -- nor on WHO adds: the default
+// spreading is a gather (samples sorted by cell, one thread per cell, sums in registers: nufft_gather_kernel), the LDS-atomic scatter
+// (nufft_spread_kernel, LPVS_NUFFT_SPREAD=scatter) gives the same bits and is kept as its control.  A weight vector's
 // quantum is q = N max|c| 2^-62 (no overflow for any input); an addend is rounded to it once, by the FMA that also adds the
 // 1.5 * 2^52 "magic" constant whose mantissa then holds the integer: error <= q/2 = max|c| 2^-43 per addend, ~3e-16 (max|c| /
 // mean|c|) of sum|c| in a coefficient -- below the kernel's own error.
@@ -24,8 +26,10 @@
 // Phase: theta_n is formed as in nudft.hip -- D in double-double, the product D x_n with an FMA-exact low part, reduced by 2 pi
 // in double-double -- so it is the phase of the REAL progression step.
 #include "lpvs_internal.h"
+#include "nufft_bins.h"
 
 #include <cmath>
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <vector>
@@ -33,12 +37,12 @@
 namespace lpvs {
 namespace {
 
-constexpr int NU_W = 16;                             // kernel width (grid points)
+constexpr int NU_W = kNuWidth;                       // kernel width (grid points)
 constexpr double NU_BETA = 2.30 * NU_W;
-// grids per spreading workgroup: GPW x nf x 8 B of LDS -- 4 for nf <= 4096, 2 for nf = 8192 (the cfg5 slot count)
-static int nu_gpw(int nf) { return nf <= 4096 ? 4 : 2; }
+// grids per scatter workgroup: GPW x nf x 8 B of LDS -- 4 for nf <= 4096, 2 for nf = 8192 (the cfg5 slot count)
+static int nu_gpw(int nf) { return nu_scatter_gpw(nf); }
 constexpr double NU_MAGIC = 6755399441055744.0;      // 1.5 * 2^52
-constexpr int NU_CHUNK = 32768;                      // samples per spreading workgroup
+constexpr int NU_CHUNK = kNuChunk;                   // samples per chunk partial
 
 // sample -> first grid cell of its support and the 16 kernel values
 __global__ void __launch_bounds__(256)
@@ -133,6 +137,121 @@ nufft_spread_kernel(const double *__restrict__ x, const double *__restrict__ y, 
     __syncthreads();
     long long *out = partial + ((int64_t)ch * ngroups + gg) * GPW * nf;
     for (int e = threadIdx.x; e < GPW * nf; e += 256) out[e] = G[e];
+}
+
+// ---- gather-form spreading (the default; nufft_bins.h holds its index arithmetic) ----------------------------------------------------
+// The grid is an INTEGER sum of the addends bits(fma(cw, tap, 1.5 * 2^52)) - bits(1.5 * 2^52): any kernel that adds every (sample, tap,
+// grid) addend exactly once gives the same 64-bit grid.  Instead of scattering a sample's 16 addends with LDS atomics, the samples of
+// every run of kNuBinChunk are sorted by cell0 once per coordinate set, and a thread that owns cell c sums, in registers, over the
+// samples of the bins c - 15 .. c: no atomics, no LDS grid, nothing to zero.
+
+// one workgroup per sorted run: histogram over the nf cells, exclusive scan -> bin_start[run][nf + 1], permutation by bin (the order
+// inside a bin is whatever the LDS atomics make it: the sums are integers, so it does not matter)
+__global__ void __launch_bounds__(256)
+nufft_bin_kernel(const int *__restrict__ cell0, int64_t N, int nf, int *__restrict__ bin_start, int *__restrict__ perm) {
+    extern __shared__ __attribute__((aligned(16))) int cnt[];              // [nf] counts, then cursors
+    __shared__ int part[256];
+    const int64_t base = (int64_t)blockIdx.x * kNuBinChunk;
+    const int count = (int)(N - base < kNuBinChunk ? N - base : kNuBinChunk);
+    for (int e = threadIdx.x; e < nf; e += 256) cnt[e] = 0;
+    __syncthreads();
+    for (int i = threadIdx.x; i < count; i += 256) atomicAdd(&cnt[cell0[base + i]], 1);
+    __syncthreads();
+    const int per = nf / 256, e0 = threadIdx.x * per;                      // consecutive cells of this thread
+    int sum = 0;
+    for (int e = 0; e < per; ++e) sum += cnt[e0 + e];
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {                                    // inclusive scan of the 256 thread sums
+        const int v = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    int run = part[threadIdx.x] - sum;
+    int *bs = bin_start + (int64_t)blockIdx.x * (nf + 1);
+    for (int e = 0; e < per; ++e) { const int c = cnt[e0 + e]; cnt[e0 + e] = run; bs[e0 + e] = run; run += c; }
+    if (threadIdx.x == 255) bs[nf] = run;                                  // == count
+    __syncthreads();
+    for (int i = threadIdx.x; i < count; i += 256) perm[base + atomicAdd(&cnt[cell0[base + i]], 1)] = i;
+}
+
+// Workgroup (chunk, block of 256 cells, group of 8 grids = 4 weight columns), thread = cell.  Per sorted run of the chunk: the block's
+// positions (nu_cell_ranges of the block) are staged kNuStage at a time -- cell0, sample and the weights in quanta, formed as the
+// scatter kernel forms them -- and every thread walks the part of ITS positions that lies in the stage.  The raw FMA bit patterns are
+// summed and bits(1.5 * 2^52) is taken off once per addend at the end (sums modulo 2^64, as the grid's are); the walk is unrolled by
+// four with the tail padded by kernel value 0, whose addend is exactly 0.
+__global__ void __launch_bounds__(256)
+nufft_gather_kernel(const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ Wt, int64_t ldw, int nq, int64_t N, int nf,
+                    const int *__restrict__ cell0, const double *__restrict__ taps, const int *__restrict__ perm, const int *__restrict__ bin_start,
+                    const double *__restrict__ invq, long long *__restrict__ partial, NuGatherPlan plan) {
+    constexpr int G = kNuGatherGrids, NC = G / 2, T = kNuStage;
+    __shared__ double s_cw[G][T];
+    __shared__ int2 s_cs[T];                                               // {cell0, run-local sample}
+    const NuGatherBlock blk = nu_gather_block(plan, blockIdx.x);
+    if (!blk.valid) return;
+    const int c = blk.cellblock * kNuCellBlock + threadIdx.x;
+    const int q0 = blk.group * NC;
+    double iq[G];
+#pragma unroll
+    for (int j = 0; j < NC; ++j) { iq[2 * j] = q0 + j < nq ? invq[2 * (q0 + j)] : 0.0; iq[2 * j + 1] = q0 + j < nq ? invq[2 * (q0 + j) + 1] : 0.0; }
+    unsigned long long acc[G];
+#pragma unroll
+    for (int gi = 0; gi < G; ++gi) acc[gi] = 0;
+    unsigned long long naddends = 0;
+    constexpr int RUNS = kNuChunk / kNuBinChunk;
+    for (int sub = 0; sub < RUNS; ++sub) {
+        const int64_t run = (int64_t)blk.chunk * RUNS + sub, base = run * kNuBinChunk;
+        if (base >= N) break;
+        const int *bs = bin_start + run * (nf + 1);
+        const NuRanges mine = nu_cell_ranges(bs, nf, c, 1), block = nu_cell_ranges(bs, nf, blk.cellblock * kNuCellBlock, kNuCellBlock);
+        for (int seg = 0; seg < 2; ++seg)
+            for (int t0 = block.r[seg].lo; t0 < block.r[seg].hi; t0 += T) {
+                const int t1 = t0 + T < block.r[seg].hi ? t0 + T : block.r[seg].hi;
+                __syncthreads();                                           // the previous stage has been walked
+                for (int p = t0 + threadIdx.x; p < t1; p += 256) {
+                    const int ls = perm[base + p];
+                    const int64_t n = base + ls;
+                    const double xv = x[n], yv = y ? y[n] : 1.0;
+                    s_cs[p - t0] = make_int2(cell0[n], ls);
+#pragma unroll
+                    for (int j = 0; j < NC; ++j) {
+                        const double wv = q0 + j < nq ? Wt[n * ldw + q0 + j] * yv : 0.0;
+                        s_cw[2 * j][p - t0] = wv * iq[2 * j];
+                        s_cw[2 * j + 1][p - t0] = (xv * wv) * iq[2 * j + 1];
+                    }
+                }
+                __syncthreads();
+#pragma unroll
+                for (int r = 0; r < 2; ++r) {
+                    const int lo = mine.r[r].lo > t0 ? mine.r[r].lo : t0, hi = mine.r[r].hi < t1 ? mine.r[r].hi : t1;
+                    for (int p = lo; p < hi; p += 4) {
+                        int idx[4];
+                        double tv[4];
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) {
+                            idx[u] = (p + u < hi ? p + u : hi - 1) - t0;
+                            const int2 cs = s_cs[idx[u]];
+                            tv[u] = taps[(base + cs.y) * NU_W + nu_tap_index(c, cs.x, nf)];
+                        }
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) {
+                            const double t = p + u < hi ? tv[u] : 0.0;
+#pragma unroll
+                            for (int gi = 0; gi < G; ++gi)
+                                acc[gi] += (unsigned long long)__double_as_longlong(fma(s_cw[gi][idx[u]], t, NU_MAGIC));
+                        }
+                        naddends += 4;
+                    }
+                }
+            }
+    }
+    const unsigned long long off = naddends * (unsigned long long)__double_as_longlong(NU_MAGIC);
+#pragma unroll
+    for (int gi = 0; gi < G; ++gi) {
+        const int gamma = blk.group * G + gi;
+        if (gamma < 2 * nq) partial[((int64_t)blk.chunk * plan.padded_grids + gamma) * nf + c] = (long long)(acc[gi] - off);
+    }
 }
 
 // integer sum of the chunk partials -> grid[gamma][g] as doubles (gamma = 2 q + twin)
@@ -328,18 +447,7 @@ bool nufft_applicable(int64_t N, int64_t nslots, int64_t nq) {
     const int nf = nufft_grid_size(nslots);
     return nf <= 8192 && N >= 4096 && nq >= 1 && nq <= 256;   // (at least two grids of nf 64-bit cells have to fit the LDS)
 }
-size_t nufft_work_bytes(int64_t N, int64_t nslots, int64_t nq) {
-    const int nf = nufft_grid_size(nslots), gpw = nu_gpw(nf);
-    const int64_t ngroups = (nq + gpw / 2 - 1) / (gpw / 2), nchunks = (N + NU_CHUNK - 1) / NU_CHUNK;
-    size_t b = 0;
-    b += sizeof(double) * (size_t)N * NU_W;                                   // taps
-    b += ((sizeof(int) * (size_t)N + 255) / 256) * 256;                       // cell0
-    b += sizeof(long long) * (size_t)nchunks * (size_t)ngroups * (size_t)gpw * (size_t)nf;   // chunk partial grids
-    b += sizeof(double) * (size_t)(2 * nq) * (size_t)(nslots + 1);            // scale table + 1 / quantum
-    b += sizeof(double) * (size_t)(2 * nq) * (size_t)nf;                      // reduced grids
-    b += sizeof(unsigned long long) * (size_t)nq + 256;                       // column maxima
-    return b;
-}
+size_t nufft_work_bytes(int64_t N, int64_t nslots, int64_t nq) { return nu_work_layout(N, nufft_grid_size(nslots), nslots, nq).total; }
 
 // tab[nslots][nq][4] = sum_n y_n Wt[n][q] {cos, sin, x cos, x sin}((mode0 + j) D x_n),  D = D_hi + D_lo;  xam = max |x|; y may be
 // nullptr (= 1).  nf = fine grid size (>= nufft_grid_size(mode0 + nslots)); reuse_coords: the sample coordinates at the head of
@@ -348,17 +456,26 @@ int32_t launch_nufft_tab(const double *x, const double *y, int64_t N, double xam
                          int mode0, int nslots, int nf, bool reuse_coords, void *work, double *tab, hipStream_t s) {
     const int gpw = nu_gpw(nf);
     const int ngroups = (nq + gpw / 2 - 1) / (gpw / 2), nchunks = (int)((N + NU_CHUNK - 1) / NU_CHUNK);
+    // LPVS_NUFFT_SPREAD=scatter (experiment knob): the LDS-atomic scatter kernel, the bit-for-bit control of the gather form
+    const bool scatter = [] { const char *e = experiment_env("LPVS_NUFFT_SPREAD"); return e && strcmp(e, "scatter") == 0; }();
+    const NuWork lay = nu_work_layout(N, nf, nslots, nq);
     unsigned char *wp = static_cast<unsigned char *>(work);
-    double *taps = reinterpret_cast<double *>(wp); wp += sizeof(double) * (size_t)N * NU_W;
-    int *cell0 = reinterpret_cast<int *>(wp); wp += ((sizeof(int) * (size_t)N + 255) / 256) * 256;
-    long long *partial = reinterpret_cast<long long *>(wp); wp += sizeof(long long) * (size_t)nchunks * (size_t)ngroups * (size_t)gpw * (size_t)nf;
-    double *scale = reinterpret_cast<double *>(wp); wp += sizeof(double) * (size_t)(2 * nq) * (size_t)nslots;
-    double *invq = reinterpret_cast<double *>(wp); wp += sizeof(double) * (size_t)(2 * nq);
-    double *grid = reinterpret_cast<double *>(wp); wp += sizeof(double) * (size_t)(2 * nq) * (size_t)nf;
-    unsigned long long *colmax = reinterpret_cast<unsigned long long *>(wp);
+    double *taps = reinterpret_cast<double *>(wp + lay.taps);
+    int *cell0 = reinterpret_cast<int *>(wp + lay.cell0);
+    int *perm = reinterpret_cast<int *>(wp + lay.perm);
+    int *bin_start = reinterpret_cast<int *>(wp + lay.bin_start);
+    long long *partial = reinterpret_cast<long long *>(wp + lay.partial);
+    double *scale = reinterpret_cast<double *>(wp + lay.scale);
+    double *invq = reinterpret_cast<double *>(wp + lay.invq);
+    double *grid = reinterpret_cast<double *>(wp + lay.grid);
+    unsigned long long *colmax = reinterpret_cast<unsigned long long *>(wp + lay.colmax);
 
     LPVS_HIP(hipMemsetAsync(colmax, 0, sizeof(unsigned long long) * (size_t)nq, s));
-    if (!reuse_coords) hipLaunchKernelGGL(nufft_coord_kernel, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, s, x, N, D_hi, D_lo, nf, cell0, taps);
+    if (!reuse_coords) {
+        hipLaunchKernelGGL(nufft_coord_kernel, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, s, x, N, D_hi, D_lo, nf, cell0, taps);
+        if (!scatter)
+            hipLaunchKernelGGL(nufft_bin_kernel, dim3((unsigned)ceil_div(N, kNuBinChunk)), dim3(256), sizeof(int) * (size_t)nf, s, cell0, N, nf, bin_start, perm);
+    }
     if (nq > 256) { set_error("nufft: more than 256 weight vectors"); return LPVS_EUNSUPPORTED; }
     hipLaunchKernelGGL(nufft_colmax_kernel, dim3(1024), dim3(256), 0, s, Wt, y, ldw, nq, N, colmax);
     LPVS_HIP(hipGetLastError());
@@ -368,8 +485,9 @@ int32_t launch_nufft_tab(const double *x, const double *y, int64_t N, double xam
     LPVS_HIP(hipStreamSynchronize(s));
     for (int q = 0; q < nq; ++q)                     // non-finite weights (or abscissae): no fixed-point grid can hold them
         if (!std::isfinite(__builtin_bit_cast(double, hm[(size_t)q])) || !std::isfinite(xam)) return kNufftNonFinite;
-    std::vector<double> hscale((size_t)(2 * nq) * (size_t)nslots), hinvq((size_t)(2 * nq));
-    const std::vector<long double> phat = nufft_phihat(nf, mode0 + nslots);
+    // 1 / quantum first: it is all the spreading reads.  The per-mode scale table (2 nq x nslots long-double quotients, ~0.4 ms of host
+    // work at cfg3) is formed below, AFTER the spreading has been launched, and is on the device before nufft_modes_kernel needs it.
+    std::vector<double> hquantum((size_t)(2 * nq)), hinvq((size_t)(2 * nq));
     for (int q = 0; q < nq; ++q) {
         const double cmax = __builtin_bit_cast(double, hm[(size_t)q]);
         for (int twin = 0; twin < 2; ++twin) {
@@ -377,14 +495,17 @@ int32_t launch_nufft_tab(const double *x, const double *y, int64_t N, double xam
             int e = 0;
             (void)std::frexp(bound > 0 ? bound : 1.0, &e);                     // bound < 2^e
             const double quantum = std::ldexp(1.0, e - 62);                    // power of two: the scalings are exact
+            hquantum[(size_t)(2 * q + twin)] = quantum;
             hinvq[(size_t)(2 * q + twin)] = bound > 0 ? 1.0 / quantum : 0.0;
-            for (int j = 0; j < nslots; ++j) hscale[(size_t)(2 * q + twin) * (size_t)nslots + (size_t)j] = (double)((long double)quantum / phat[(size_t)(mode0 + j)]);
         }
     }
-    LPVS_TRY(copy_to_device(scale, hscale.data(), sizeof(double) * hscale.size(), s));
     LPVS_TRY(copy_to_device(invq, hinvq.data(), sizeof(double) * hinvq.size(), s));
     const size_t lds_spread = sizeof(long long) * (size_t)gpw * (size_t)nf;
-    if (gpw == 4) {
+    if (!scatter) {
+        const NuGatherPlan plan = nu_gather_plan(N, nf, nq);
+        hipLaunchKernelGGL(nufft_gather_kernel, dim3((unsigned)plan.nblocks), dim3(256), 0, s, x, y, Wt, ldw, nq, N, nf, cell0, taps, perm, bin_start, invq,
+                           partial, plan);
+    } else if (gpw == 4) {
         LPVS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&nufft_spread_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_spread));
         hipLaunchKernelGGL(nufft_spread_kernel<4>, dim3((unsigned)(8 * ngroups * ceil_div(nchunks, 8))), dim3(256), lds_spread, s, x, y, Wt, ldw, nq, N, nf, cell0,
                            taps, invq, partial, ngroups, nchunks);
@@ -394,6 +515,14 @@ int32_t launch_nufft_tab(const double *x, const double *y, int64_t N, double xam
                            taps, invq, partial, ngroups, nchunks);
     }
     hipLaunchKernelGGL(nufft_reduce_kernel, dim3((unsigned)ceil_div(nf, 256), (unsigned)(2 * nq)), dim3(256), 0, s, partial, ngroups, nchunks, nf, gpw, grid);
+    LPVS_HIP(hipGetLastError());
+    {   // (the device spreads meanwhile)
+        std::vector<double> hscale((size_t)(2 * nq) * (size_t)nslots);
+        const std::vector<long double> phat = nufft_phihat(nf, mode0 + nslots);
+        for (int g = 0; g < 2 * nq; ++g)
+            for (int j = 0; j < nslots; ++j) hscale[(size_t)g * (size_t)nslots + (size_t)j] = (double)((long double)hquantum[(size_t)g] / phat[(size_t)(mode0 + j)]);
+        LPVS_TRY(copy_to_device(scale, hscale.data(), sizeof(double) * hscale.size(), s));
+    }
     if (nf <= 4096) {
         const size_t lds_modes = sizeof(double) * 3 * (size_t)nf;
         LPVS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&nufft_modes_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_modes));
