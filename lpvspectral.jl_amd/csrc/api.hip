@@ -261,35 +261,12 @@ struct DevOut {
     }
 };
 
-static int64_t check_freq_host(const double *f, int64_t Nf) {  // src/lsfft.jl:20-24
-    for (int64_t i = 0; i < Nf; ++i)
-        if (f[i] == 0.0) return i == 0 ? 1 : -1;
-    return 0;
-}
 static int32_t fetch_host(std::vector<double> &h, const double *src, int64_t count) {
     h.resize((size_t)count);
     if (count == 0) return LPVS_OK;
     if (is_device_ptr(src)) { LPVS_HIP(hipMemcpy(h.data(), src, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost)); }
     else memcpy(h.data(), src, sizeof(double) * (size_t)count);
     return LPVS_OK;
-}
-
-// basis centres (src/utilities.jl:24-32); twice-precision range reproduced with long double
-static void basis_centers(double lo, double hi, double amax, int64_t Nv, int coulomb, std::vector<double> &vc, double *gamma) {
-    if (!coulomb) {
-        vc.resize((size_t)Nv);
-        for (int64_t j = 0; j < Nv; ++j)
-            vc[j] = Nv > 1 ? (double)((long double)lo + (long double)j * ((long double)hi - (long double)lo) / (long double)(Nv - 1)) : lo;
-        *gamma = (double)Nv / std::fabs(vc[0] - vc[Nv - 1]);
-    } else {
-        vc.resize((size_t)(2 * Nv));
-        for (int64_t j = 0; j < Nv; ++j) {
-            const double c = (double)((long double)(j + 1) * (long double)amax / (long double)(Nv + 1));
-            vc[Nv + j] = c;
-            vc[Nv - 1 - j] = -c;
-        }
-        *gamma = (double)(2 * Nv) / std::fabs(vc[0] - vc[2 * Nv - 1]);
-    }
 }
 
 struct EventPair {
@@ -432,6 +409,68 @@ int32_t alloc_state(lpvs_problem *h) {
     LPVS_HIP(hipMemsetAsync(h->status.p, 0, sizeof(AdmmStatus) * (size_t)h->ns, h->stream));
     return LPVS_OK;
 }
+
+// ---- what the problem constructors share ---------------------------------------------------------------------------------------------
+// a handle under construction: deleted unless release() hands it to the caller
+struct HandleGuard {
+    lpvs_problem *h;
+    ~HandleGuard() { delete h; }
+    int32_t release(lpvs_problem **out) { *out = h; h = nullptr; return LPVS_OK; }
+};
+
+// The opening (h->n is set): the padded size, G and ns right-hand sides with their zeros, the ADMM state.
+// The structured LPV assembly writes every element of the n x n block: only the pad strips (rows and columns n .. np) need zeros.
+// The dense forms accumulate into / leave parts of G, and so does the Fourier assembly: they get the whole of it zeroed.
+enum class ZeroGram { all, pad_strips };
+int32_t open_problem(lpvs_problem *h, int64_t ns, ZeroGram zero) {
+    hipStream_t s = h->stream;
+    h->np = round_up(h->n, 128); h->ns = ns;
+    const int64_t n = h->n, np = h->np;
+    LPVS_TRY(h->G.alloc(sizeof(double) * (size_t)np * (size_t)np));
+    LPVS_TRY(h->b.alloc(sizeof(double) * (size_t)np * (size_t)ns));
+    if (zero == ZeroGram::all) LPVS_HIP(hipMemsetAsync(h->G.p, 0, h->G.bytes, s));
+    else if (np > n) {
+        LPVS_HIP(hipMemsetAsync(h->G.as<double>() + n * np, 0, sizeof(double) * (size_t)(np - n) * (size_t)np, s));
+        LPVS_HIP(hipMemset2DAsync(h->G.as<double>() + n, sizeof(double) * (size_t)np, 0, sizeof(double) * (size_t)(np - n), (size_t)n, s));
+    }
+    LPVS_HIP(hipMemsetAsync(h->b.p, 0, h->b.bytes, s));
+    return alloc_state(h);
+}
+
+// The close: the stream's work is awaited and the three event pairs are folded into the timing record.  issued: flops the form issues;
+// ksplit: sample chunks of a dense form (structured: 0).
+int32_t close_problem(lpvs_problem *h, GramForm form, double issued, int64_t ksplit) {
+    LPVS_HIP(hipStreamSynchronize(h->stream));
+    h->t_basis = h->ev[0].ms(); h->t_gram = h->ev[1].ms(); h->t_reduce = h->ev[2].ms();
+    h->gram_launches = issued; h->gram_flops = gram_flops(h->N, h->n);
+    h->gram_form = (double)(int)form; h->gram_ksplit = (int)ksplit;
+    return LPVS_OK;
+}
+
+// Float-rounded frequency grids are admitted to the structured Gram (gram_form_plan.h: make_ap_slots, f32_grid) while an Admit is alive
+// on the thread: the _f32 entry points hold one across the _f64 entry point they call, a window job's worker thread takes the job's.
+thread_local bool g_f32_admission = false;
+struct Admit {
+    bool prev;
+    explicit Admit(bool on = true) : prev(g_f32_admission) { if (on) g_f32_admission = true; }
+    ~Admit() { g_f32_admission = prev; }
+};
+
+// device copies of the slot tables
+struct ApSlotsDev {
+    DevBuf hi, lo, rhi, rlo, eps;
+    int32_t upload(const ApSlots &sl, hipStream_t s) {
+        LPVS_TRY(hi.alloc(sizeof(double) * (size_t)sl.nsl)); LPVS_TRY(lo.alloc(sizeof(double) * (size_t)sl.nsl));
+        LPVS_TRY(rhi.alloc(sizeof(double) * (size_t)sl.nf8)); LPVS_TRY(rlo.alloc(sizeof(double) * (size_t)sl.nf8));
+        LPVS_TRY(eps.alloc(sizeof(double) * sl.eps.size()));
+        LPVS_TRY(copy_to_device(hi.p, sl.om_hi.data(), sizeof(double) * (size_t)sl.nsl, s));
+        LPVS_TRY(copy_to_device(lo.p, sl.om_lo.data(), sizeof(double) * (size_t)sl.nsl, s));
+        LPVS_TRY(copy_to_device(rhi.p, sl.omr_hi.data(), sizeof(double) * (size_t)sl.nf8, s));
+        LPVS_TRY(copy_to_device(rlo.p, sl.omr_lo.data(), sizeof(double) * (size_t)sl.nf8, s));
+        LPVS_TRY(copy_to_device(eps.p, sl.eps.data(), sizeof(double) * sl.eps.size(), s));
+        return LPVS_OK;
+    }
+};
 
 // device [ns][np] (first n of every row valid)  <->  caller's n x ns column-major array
 int32_t copy_state_out(lpvs_problem *h, const void *dev, double *dst) {
@@ -745,54 +784,95 @@ void fold_timings(lpvs_problem *h, size_t nxc, long long iters_before, long long
 
 }  // namespace
 
-// Common tail of the panel-form constructors: P is the k-major regressor panel [Npad][ld].
-// fill(P) must enqueue the kernel(s) that write rows [0,N) of the panel on the handle's stream.
-template <class Fill>
-static int32_t create_panel_problem(lpvs_problem *h, const double *y, const double *W, int64_t N, Fill fill) {
-    hipStream_t s = h->stream;
-    h->np = round_up(h->n, 128);
-    const GramPlan pl = make_gram_plan(h->n, N);
-    const int64_t Npad = pl.ksplit * pl.rows_per_chunk;
-    const int64_t ld = round_up(h->n, 256);
-    DevArg dy;
-    LPVS_TRY(dy.set(y, N, s));
-    LPVS_TRY(h->G.alloc(sizeof(double) * (size_t)h->np * (size_t)h->np));
-    LPVS_TRY(h->b.alloc(sizeof(double) * (size_t)h->np));
-    LPVS_HIP(hipMemsetAsync(h->G.p, 0, h->G.bytes, s));
-    LPVS_HIP(hipMemsetAsync(h->b.p, 0, h->b.bytes, s));
-    LPVS_TRY(alloc_state(h));
+// ---- the panel-form constructors (Fourier on an arbitrary grid, dense A) ---------------------------------------------------------------
+// P is the k-major regressor panel [Npad][ld].  The buffers live in create_panel_problem's scope, which owns the drain.
+struct PanelBufs { DevBuf P, Wp, slab, scr; const double *Wdev = nullptr; int64_t ld = 0; };
 
-    DevBuf P, Wp, slab, scr;
-    DrainOnExit drain(s);
-    LPVS_TRY(P.alloc(sizeof(double) * (size_t)Npad * (size_t)ld));
-    if (Npad > N) LPVS_HIP(hipMemsetAsync(P.as<double>() + N * ld, 0, sizeof(double) * (size_t)(Npad - N) * (size_t)ld, s));
-    const double *Wdev = nullptr;
+// the panel with its zero pad rows and the padded weights; fill(P, ld) enqueues the kernel(s) that write rows [0,N) on the handle's stream
+template <class Fill>
+static int32_t panel_tables(lpvs_problem *h, const GramPlan &pl, const double *W, int64_t N, PanelBufs &t, Fill fill) {
+    hipStream_t s = h->stream;
+    const int64_t Npad = pl.ksplit * pl.rows_per_chunk, ld = t.ld = round_up(h->n, 256);
+    LPVS_TRY(t.P.alloc(sizeof(double) * (size_t)Npad * (size_t)ld));
+    if (Npad > N) LPVS_HIP(hipMemsetAsync(t.P.as<double>() + N * ld, 0, sizeof(double) * (size_t)(Npad - N) * (size_t)ld, s));
     if (W != nullptr) {  // padded copy: pad rows carry weight 0
-        LPVS_TRY(Wp.alloc(sizeof(double) * (size_t)Npad));
-        LPVS_HIP(hipMemsetAsync(Wp.p, 0, Wp.bytes, s));
-        LPVS_TRY(copy_to_device(Wp.p, W, sizeof(double) * (size_t)N, s));
-        Wdev = Wp.as<double>();
+        LPVS_TRY(t.Wp.alloc(sizeof(double) * (size_t)Npad));
+        LPVS_HIP(hipMemsetAsync(t.Wp.p, 0, t.Wp.bytes, s));
+        LPVS_TRY(copy_to_device(t.Wp.p, W, sizeof(double) * (size_t)N, s));
+        t.Wdev = t.Wp.as<double>();
     }
     LPVS_HIP(hipEventRecord(h->ev[0].a, s));
-    LPVS_TRY(fill(P.as<double>(), ld));
+    LPVS_TRY(fill(t.P.as<double>(), ld));
     LPVS_HIP(hipEventRecord(h->ev[0].b, s));
-    LPVS_TRY(slab.alloc(pl.slab_bytes));
-    LPVS_TRY(scr.alloc(rhs_scratch_bytes(N, h->n)));
-    LPVS_HIP(hipEventRecord(h->ev[1].a, s));
-    LPVS_TRY(launch_gram_panel(pl, P.as<double>(), ld, Wdev, slab.as<double>(), s, &h->gram_stage));
-    LPVS_HIP(hipEventRecord(h->ev[1].b, s));
-    LPVS_HIP(hipEventRecord(h->ev[2].a, s));
-    LPVS_TRY(launch_gram_reduce(pl, slab.as<double>(), h->G.as<double>(), h->np, s));
-    LPVS_TRY(launch_rhs_panel(P.as<double>(), ld, h->n, Wdev, dy.p, N, h->b.as<double>(), scr.as<double>(), scr.bytes, s));
-    LPVS_HIP(hipEventRecord(h->ev[2].b, s));
-    LPVS_HIP(hipStreamSynchronize(s));
-    h->t_basis = h->ev[0].ms(); h->t_gram = h->ev[1].ms(); h->t_reduce = h->ev[2].ms();
-    h->gram_launches = (double)pl.tiles * 128.0 * 256.0 * 2.0 * (double)(pl.ksplit * pl.rows_per_chunk);   // flops the MFMA core issues
-    h->gram_form = 3; h->gram_ksplit = (int)pl.ksplit;
-    h->gram_flops = (double)N * (double)h->n * (double)(h->n + 1);
     return LPVS_OK;
 }
 
+// Common tail of the panel-form constructors: tables, Gram, reduction with the right-hand side.
+template <class Fill>
+static int32_t create_panel_problem(lpvs_problem *h, const double *y, const double *W, int64_t N, Fill fill) {
+    hipStream_t s = h->stream;
+    const GramPlan pl = make_gram_plan(h->n, N);
+    DevArg dy;
+    LPVS_TRY(dy.set(y, N, s));
+    LPVS_TRY(open_problem(h, 1, ZeroGram::all));
+    PanelBufs t;
+    DrainOnExit drain(s);
+    LPVS_TRY(panel_tables(h, pl, W, N, t, fill));
+    LPVS_TRY(t.slab.alloc(pl.slab_bytes));
+    LPVS_TRY(t.scr.alloc(rhs_scratch_bytes(N, h->n)));
+    LPVS_HIP(hipEventRecord(h->ev[1].a, s));
+    LPVS_TRY(launch_gram_panel(pl, t.P.as<double>(), t.ld, t.Wdev, t.slab.as<double>(), s, &h->gram_stage));
+    LPVS_HIP(hipEventRecord(h->ev[1].b, s));
+    LPVS_HIP(hipEventRecord(h->ev[2].a, s));
+    LPVS_TRY(launch_gram_reduce(pl, t.slab.as<double>(), h->G.as<double>(), h->np, s));
+    LPVS_TRY(launch_rhs_panel(t.P.as<double>(), t.ld, h->n, t.Wdev, dy.p, N, h->b.as<double>(), t.scr.as<double>(), t.scr.bytes, s));
+    LPVS_HIP(hipEventRecord(h->ev[2].b, s));
+    return close_problem(h, GramForm::panel, dense_issued_flops(pl), pl.ksplit);
+}
+
+// Slot tables of a Fourier grid f over time stamps t_dev[0, N): the angular frequencies are rounded as the regressor kernel does
+// (src/lsfft.jl:33).  *tam: max|t| where the caller knows it, else (not >= 0) it is reduced on the device and left there.
+static int32_t fourier_slots(const double *f, int64_t Nf, const double *t_dev, int64_t N, double *tam, hipStream_t s, ApSlots &sl) {
+    std::vector<double> hw;
+    LPVS_TRY(fetch_host(hw, f, Nf));
+    for (auto &v : hw) v = 6.283185307179586 * v;
+    double tlo, thi;
+    if (!(*tam >= 0)) LPVS_TRY(device_minmax(t_dev, N, &tlo, &thi, tam, s));
+    sl = make_ap_slots(hw, *tam, g_f32_admission);
+    return LPVS_OK;
+}
+
+// ---- the structured Fourier constructor: 2 pi f is an arithmetic progression (default_freqs and every grid of the reference's tests) ----
+// A' diag(W) A and A' (W .* y), src/lasso.jl:119-120.  Owns its temporaries and the drain.
+static int32_t create_fourier_structured(lpvs_problem *h, const double *y, const double *t_dev, const double *W, const ApSlots &sl) {
+    hipStream_t s = h->stream;
+    const int64_t N = h->N, Nf = h->Nf; const int zf = (int)h->zerofreq;
+    DevArg dy, dW;
+    LPVS_TRY(dy.set(y, N, s));
+    if (W) LPVS_TRY(dW.set(W, N, s));
+    const double *Wd = W ? dW.p : nullptr;
+    LPVS_TRY(open_problem(h, 1, ZeroGram::all));
+    ApSlotsDev sd; DevBuf part, tab, tabb;
+    DrainOnExit drain(s);
+    LPVS_HIP(hipEventRecord(h->ev[0].a, s));
+    LPVS_TRY(sd.upload(sl, s));
+    LPVS_HIP(hipEventRecord(h->ev[0].b, s));
+    // (BOTH launches below share `part`: the right-hand side's has a third of the slots but -- fewer slot groups, so smaller chunks --
+    // up to four times the chunks.  Sized for the Gram launch alone it overflowed for N / rows-per-chunk in [171, 256), e.g.
+    // N = 118727 or 204800: found as a GPU fault in test_fourier_gram_additivity_cfg2 when the minimum chunk went from 512 to 64.)
+    LPVS_TRY(part.alloc(std::max(nudft_partial_bytes(N, sl.nsl, 1), nudft_partial_bytes(N, sl.nf8, 1))));
+    LPVS_TRY(tab.alloc(sizeof(double) * (size_t)sl.nsl * 4));
+    LPVS_TRY(tabb.alloc(sizeof(double) * (size_t)sl.nf8 * 4));
+    LPVS_HIP(hipEventRecord(h->ev[1].a, s));
+    LPVS_TRY(launch_nudft(t_dev, nullptr, N, Wd, 1, 1, sd.hi.as<double>(), sd.lo.as<double>(), (int)sl.nsl, sl.step, part.as<double>(), tab.as<double>(), s));
+    LPVS_TRY(launch_ap_assemble_fourier(tab.as<double>(), sd.eps.as<double>(), Nf, sl.s0, sl.delta, zf, h->n, h->G.as<double>(), h->np, 1, 0, 0, s));
+    LPVS_HIP(hipEventRecord(h->ev[1].b, s));
+    LPVS_HIP(hipEventRecord(h->ev[2].a, s));
+    LPVS_TRY(launch_nudft(t_dev, dy.p, N, Wd, 1, 1, sd.rhi.as<double>(), sd.rlo.as<double>(), (int)sl.nf8, sl.step, part.as<double>(), tabb.as<double>(), s));
+    LPVS_TRY(launch_ap_rhs_fourier(tabb.as<double>(), sd.eps.as<double>(), Nf, zf, h->b.as<double>(), 1, 0, 0, s));
+    LPVS_HIP(hipEventRecord(h->ev[2].b, s));
+    return close_problem(h, GramForm::ap, structured_issued_flops(N, sl.nsl, 1), 0);
+}
 extern "C" {
 
 int32_t lpvs_version(void) { return LPVS_VERSION; }
@@ -928,91 +1008,210 @@ int32_t lpvs_lpv_regressor_f64(const double *X, const double *V, int64_t N, cons
     return dP.finish(s);
 }
 
-// Slot tables of the structured Gram (nudft.hip) for frequencies w_f = a + f*D + eps_f: exact progressions in
-// double-double, each family padded to a multiple of 8:
-//   [0, nf8): m*D (differences), [nf8, nf8+s8): 2a + s*D (sums); the right-hand side uses a + f*D, f < nf8.
-// MERGED layout: when 2a is (up to rounding) an integer multiple j0 < Nf of D -- default_freqs (a = 0), the README grid
-// w = D*(1..Nf) (a = D) -- the sum frequencies (j0 + s) D are multiples of D like the differences, so ONE progression
-// j*D, j = 0 .. j0+2Nf-2 serves both families: 2Nf-1+j0 slots instead of 3Nf-1 (a third less work); the sum of (f, f') is
-// slot s0 + f + f' with s0 = j0, and the rounding residual delta = 2a - j0*D joins the first-order correction.
-struct ApSlots {
-    bool ok = false;
-    double emax = 0;
-    int64_t nf8 = 0, s8 = 0, nsl = 0;
-    bool merged = false;   // one progression j*D serves differences and sums (see above)
-    int64_t s0 = 0;        // slot of the sum frequency 2a (split layout: nf8; merged: j0)
-    double delta = 0;      // merged layout: 2a - j0*D
-    std::vector<double> eps, om_hi, om_lo, omr_hi, omr_lo;
-    ApStep step{};
-};
-// Single-precision callers (_f32 entry points): the frequency grid is a progression rounded to FLOATS, so its residuals are up
-// to 2^-24 |w| and |eps| max|x| reaches 0.2 rad at the cfg3 size -- far beyond the double-precision admission bound.  But a
-// Float32 run of the reference evaluates fl32(w x) itself, a phase error of up to 2^-24 |w x|: snapping w to the exact
-// progression its floats were rounded from stays inside that error.  While an _f32 constructor runs, residuals up to
-// 2^-23 max|w| (one float ulp) are admitted and dropped.
-static thread_local bool g_f32_admission = false;
-
-static ApSlots make_ap_slots(const std::vector<double> &hw, double xam) {
+// ---- the LPV constructor: choose the form (gram_form_plan.h), then the structured or the dense sequence ---------------------------------
+// the arguments as the phases see them, their device copies, and what the form decision left
+struct LpvJob {
+    lpvs_problem *h = nullptr;
+    int64_t ns = 0, N = 0, Nf = 0, Nv = 0, nb = 0; int normalize = 0, coulomb = 0;
+    const double *ranges = nullptr;   // (optional) {min V, max V, max|V|, max|X|} over ALL rows of the signal when (y, X, V) is only a row shard of it
+    DevArg dy, dX, dV, dw;
+    double xam = 0;                   // max|X| (over all rows of the signal)
     ApSlots sl;
-    const int64_t Nf = (int64_t)hw.size();
-    const long double a0 = hw[0], D = Nf > 1 ? ((long double)hw[Nf - 1] - (long double)hw[0]) / (long double)(Nf - 1) : 0.0L;
-    sl.eps.resize((size_t)Nf);
-    for (int64_t f = 0; f < Nf; ++f) {
-        sl.eps[f] = (double)((long double)hw[f] - (a0 + (long double)f * D));
-        sl.emax = std::fmax(sl.emax, std::fabs(sl.eps[f]));
+    GramForm form = GramForm::kr;
+};
+
+static int32_t lpv_choose_form(LpvJob &J, const double *w) {
+    lpvs_problem *h = J.h;
+    GramFormFacts ff; ff.family = GramFamily::lpv;
+    ff.option = option_in_effect(LPVS_OPT_GRAM_FORM, h->opt[LPVS_OPT_GRAM_FORM]);
+    ff.slots_direct = option_in_effect(LPVS_OPT_SLOT_SUMS, h->opt[LPVS_OPT_SLOT_SUMS]) == LPVS_SLOTS_DIRECT;   // LPVS_NUDFT=direct keeps the direct evaluation of nudft.hip
+    if (gram_option_wants_slots(ff.option)) {
+        std::vector<double> hw;
+        LPVS_TRY(fetch_host(hw, w, J.Nf));
+        double xlo, xhi;
+        if (J.ranges) J.xam = J.ranges[3];
+        else LPVS_TRY(device_minmax(J.dX.p, J.N, &xlo, &xhi, &J.xam, h->stream));
+        J.sl = make_ap_slots(hw, J.xam, g_f32_admission);
     }
-    double wam = 0;
-    for (double v : hw) wam = std::fmax(wam, std::fabs(v));
-    sl.ok = std::isfinite(sl.emax) && std::isfinite(xam) && sl.emax * xam <= 1e-7;   // second-order term (eps x)^2/2 <= 5e-15
-    if (!sl.ok && g_f32_admission && std::isfinite(sl.emax) && std::isfinite(xam) && sl.emax <= 0x1p-23 * wam) {
-        // large residual phases: snapped grid, NO first-order term -- G is then exactly the Gram of the regressor at the snapped
-        // frequencies (positive semidefinite by construction), which a first-order expansion with |eps x| ~ 0.2 would not guarantee
-        sl.ok = true;
-        if (sl.emax * xam > 3e-3) for (auto &e : sl.eps) e = 0.0;   // small residual phases keep the first-order term (error (eps x)^2/2 <= 5e-6)
-    }
-    if (!sl.ok) return sl;
-    sl.nf8 = round_up(Nf, 8); sl.s8 = round_up(2 * Nf - 1, 8); sl.nsl = sl.nf8 + sl.s8;
-    auto split = [](long double v, double &hi, double &lo) { hi = (double)v; lo = (double)(v - (long double)hi); };
-    sl.omr_hi.resize((size_t)sl.nf8); sl.omr_lo.resize((size_t)sl.nf8);
-    sl.s0 = sl.nf8;
-    bool merged = false;
-    if (Nf > 1 && D != 0.0L) {
-        const long double j0r = 2.0L * a0 / D;
-        const long long j0 = llroundl(j0r);
-        const long double delta = 2.0L * a0 - (long double)j0 * D;
-        if (j0 >= 0 && j0 < Nf && std::fabs((double)delta) * xam <= 1e-7) {
-            merged = true; sl.merged = true;
-            sl.s0 = j0; sl.delta = (double)delta;
-            sl.nsl = round_up(j0 + 2 * Nf - 1, 8);
-            sl.s8 = sl.nsl;
-        }
-    }
-    sl.om_hi.resize((size_t)sl.nsl); sl.om_lo.resize((size_t)sl.nsl);
-    if (merged) {
-        for (int64_t j = 0; j < sl.nsl; ++j) split((long double)j * D, sl.om_hi[j], sl.om_lo[j]);
-    } else {
-        for (int64_t m = 0; m < sl.nf8; ++m) split((long double)m * D, sl.om_hi[m], sl.om_lo[m]);
-        for (int64_t q = 0; q < sl.s8; ++q) split(2.0L * a0 + (long double)q * D, sl.om_hi[sl.nf8 + q], sl.om_lo[sl.nf8 + q]);
-    }
-    for (int64_t f = 0; f < sl.nf8; ++f) split(a0 + (long double)f * D, sl.omr_hi[f], sl.omr_lo[f]);
-    for (int b = 0; b < 8; ++b) split((long double)b * D, sl.step.hi[b], sl.step.lo[b]);
-    return sl;
+    ff.slots_ok = J.sl.ok; ff.merged = J.sl.merged;
+    ff.N = J.N; ff.nsl = J.sl.nsl; ff.nb = J.nb; ff.nq = J.nb * (J.nb + 1) / 2;
+    J.form = choose_gram_form(ff);
+    if (J.form != GramForm::refused) return LPVS_OK;
+    set_error("LPVS_GRAM_FORM=ap but w is not an arithmetic progression (max|eps|*max|x| = %.3g)", J.sl.emax * J.xam);
+    return LPVS_EARGUMENT;
 }
-// device copies of the slot tables
-struct ApSlotsDev {
-    DevBuf hi, lo, rhi, rlo, eps;
-    int32_t upload(const ApSlots &sl, hipStream_t s) {
-        LPVS_TRY(hi.alloc(sizeof(double) * (size_t)sl.nsl)); LPVS_TRY(lo.alloc(sizeof(double) * (size_t)sl.nsl));
-        LPVS_TRY(rhi.alloc(sizeof(double) * (size_t)sl.nf8)); LPVS_TRY(rlo.alloc(sizeof(double) * (size_t)sl.nf8));
-        LPVS_TRY(eps.alloc(sizeof(double) * sl.eps.size()));
-        LPVS_TRY(copy_to_device(hi.p, sl.om_hi.data(), sizeof(double) * (size_t)sl.nsl, s));
-        LPVS_TRY(copy_to_device(lo.p, sl.om_lo.data(), sizeof(double) * (size_t)sl.nsl, s));
-        LPVS_TRY(copy_to_device(rhi.p, sl.omr_hi.data(), sizeof(double) * (size_t)sl.nf8, s));
-        LPVS_TRY(copy_to_device(rlo.p, sl.omr_lo.data(), sizeof(double) * (size_t)sl.nf8, s));
-        LPVS_TRY(copy_to_device(eps.p, sl.eps.data(), sizeof(double) * sl.eps.size(), s));
+
+// Buffers of the structured sequence.  They live in lpv_structured's scope, which owns the drain; the phases receive them.
+struct ApBufs {
+    DevBuf K, KK, dvc, part, tab, tabb, nwork, epsr;
+    ApSlotsDev sd;
+    int64_t ldk = 0, P = 0; int nfg = 0;
+    bool nufft = false;               // the slot sums went through the non-uniform FFT (false after its non-finite fallback)
+};
+
+// activation table, its pair products, the slot tables
+static int32_t ap_tables(LpvJob &J, ApBufs &t) {
+    lpvs_problem *h = J.h; hipStream_t s = h->stream;
+    const int64_t N = J.N, nb = J.nb;
+    double lo, hi, am, gamma; std::vector<double> vc;
+    LPVS_HIP(hipEventRecord(h->ev[0].a, s));
+    if (J.ranges) { lo = J.ranges[0]; hi = J.ranges[1]; am = J.ranges[2]; }
+    else LPVS_TRY(device_minmax(J.dV.p, N, &lo, &hi, &am, s));
+    basis_centers(lo, hi, am, J.Nv, J.coulomb, vc, &gamma);
+    t.ldk = nb + 1; t.P = nb * (nb + 1) / 2;
+    LPVS_TRY(t.dvc.alloc(sizeof(double) * vc.size()));
+    LPVS_TRY(copy_to_device(t.dvc.p, vc.data(), sizeof(double) * vc.size(), s));
+    LPVS_TRY(t.K.alloc(sizeof(double) * (size_t)N * (size_t)t.ldk));
+    LPVS_TRY(t.KK.alloc(sizeof(double) * (size_t)N * (size_t)t.P));
+    LPVS_TRY(launch_basis_table(J.dV.p, N, t.dvc.as<double>(), nb, gamma, J.normalize, J.coulomb, t.K.as<double>(), t.ldk, s));
+    LPVS_TRY(launch_pair_table(t.K.as<double>(), t.ldk, nb, N, t.KK.as<double>(), s));
+    LPVS_TRY(t.sd.upload(J.sl, s));
+    LPVS_HIP(hipEventRecord(h->ev[0].b, s));
+    return LPVS_OK;
+}
+
+// slot sums (merged slot layout: Fourier coefficients at the multiples of ONE step -> non-uniform FFT, nufft.hip), then the assembly
+static int32_t ap_gram(LpvJob &J, ApBufs &t) {
+    lpvs_problem *h = J.h; hipStream_t s = h->stream;
+    const ApSlots &sl = J.sl;
+    const int64_t N = J.N, nsl = sl.nsl, P = t.P;
+    // (both families of launches share `part`: sized for the larger of the two)
+    LPVS_TRY(t.part.alloc(std::max(nudft_partial_bytes(N, nsl, P), nudft_partial_bytes(N, sl.nf8, J.nb))));
+    LPVS_TRY(t.tab.alloc(sizeof(double) * (size_t)nsl * (size_t)P * 4));
+    LPVS_TRY(t.tabb.alloc(sizeof(double) * (size_t)sl.nf8 * (size_t)J.nb * 4));
+    LPVS_HIP(hipEventRecord(h->ev[1].a, s));
+    t.nufft = J.form == GramForm::ap_nufft;
+    t.nfg = nufft_grid_size(nsl);
+    if (t.nufft) {
+        LPVS_TRY(t.nwork.alloc(nufft_work_bytes(N, nsl, P)));
+        const int32_t rc = launch_nufft_tab(J.dX.p, nullptr, N, J.xam, t.KK.as<double>(), P, (int)P, sl.step.hi[1], sl.step.lo[1], 0, (int)nsl, t.nfg, false,
+                                            t.nwork.p, t.tab.as<double>(), s);
+        if (rc == kNufftNonFinite) t.nufft = false;    // NaN / Inf in the inputs: the direct sums propagate them as the reference does
+        else if (rc != LPVS_OK) return rc;
+    }
+    if (!t.nufft) {
+        J.form = GramForm::ap;
+        LPVS_TRY(launch_nudft(J.dX.p, nullptr, N, t.KK.as<double>(), P, (int)P, t.sd.hi.as<double>(), t.sd.lo.as<double>(), (int)nsl, sl.step, t.part.as<double>(),
+                              t.tab.as<double>(), s));
+    }
+    LPVS_TRY(launch_ap_assemble(t.tab.as<double>(), t.sd.eps.as<double>(), J.Nf, sl.s0, sl.delta, J.nb, h->n, h->G.as<double>(), h->np, s));
+    LPVS_HIP(hipEventRecord(h->ev[1].b, s));
+    return LPVS_OK;
+}
+
+// b_q = Phi' y_q: Nf slots a + f*D, weights y K_j, first-order eps correction; on the Gram's grid where they ride it (rhs_on_grid)
+static int32_t ap_rhs(LpvJob &J, ApBufs &t) {
+    lpvs_problem *h = J.h; hipStream_t s = h->stream;
+    const ApSlots &sl = J.sl;
+    const int64_t N = J.N, nb = J.nb, nf8 = sl.nf8;
+    LPVS_HIP(hipEventRecord(h->ev[2].a, s));
+    const bool nufft_rhs = t.nufft && rhs_on_grid(sl);
+    if (nufft_rhs) {
+        const std::vector<double> er = rhs_residuals(sl);
+        LPVS_TRY(t.epsr.alloc(sizeof(double) * er.size()));
+        LPVS_TRY(copy_to_device(t.epsr.p, er.data(), sizeof(double) * er.size(), s));
+        LPVS_HIP(hipStreamSynchronize(s));       // (er is a local)
+    }
+    for (int64_t q = 0; q < J.ns; ++q) {
+        bool by_nufft = nufft_rhs;
+        if (by_nufft) {
+            const int32_t rc = launch_nufft_tab(J.dX.p, J.dy.p + q * N, N, J.xam, t.K.as<double>(), t.ldk, (int)nb, sl.step.hi[1], sl.step.lo[1], (int)(sl.s0 / 2),
+                                                (int)nf8, t.nfg, true, t.nwork.p, t.tabb.as<double>(), s);
+            if (rc == kNufftNonFinite) by_nufft = false;   // a NaN / Inf in this signal
+            else if (rc != LPVS_OK) return rc;
+        }
+        if (!by_nufft)
+            LPVS_TRY(launch_nudft(J.dX.p, J.dy.p + q * N, N, t.K.as<double>(), t.ldk, (int)nb, t.sd.rhi.as<double>(), t.sd.rlo.as<double>(), (int)nf8, sl.step,
+                                  t.part.as<double>(), t.tabb.as<double>(), s));
+        LPVS_TRY(launch_ap_rhs(t.tabb.as<double>(), by_nufft ? t.epsr.as<double>() : t.sd.eps.as<double>(), J.Nf, nb, h->b.as<double>() + q * h->np, s));
+    }
+    LPVS_HIP(hipEventRecord(h->ev[2].b, s));
+    return LPVS_OK;
+}
+
+// structured: tables, Gram, right-hand sides.  Owns the temporaries and the drain (all temporaries before the drain guard: released
+// only after the stream is idle).
+static int32_t lpv_structured(LpvJob &J) {
+    LPVS_TRY(open_problem(J.h, J.ns, ZeroGram::pad_strips));
+    ApBufs t;
+    DrainOnExit drain(J.h->stream);
+    LPVS_TRY(ap_tables(J, t));
+    LPVS_TRY(ap_gram(J, t));
+    LPVS_TRY(ap_rhs(J, t));
+    return close_problem(J.h, J.form, structured_issued_flops(J.N, J.sl.nsl, t.P), 0);
+}
+
+// Buffers of the dense sequence; they live in lpv_dense's scope, which owns the drain.
+struct KrBufs { DevBuf T, K, KK, G3, slab, scr; int64_t ldk = 0; };
+// b_q = Phi' y_q is HBM-bound (it streams the trig table) while the Gram is MFMA-bound and leaves registers free for small
+// workgroups: it runs on a side stream underneath the Gram kernel.  Destroyed before the drain: the side stream is idle first.
+struct SideStream {
+    hipStream_t s = nullptr; hipEvent_t ready = nullptr, done = nullptr;
+    int32_t open() {
+        LPVS_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        LPVS_HIP(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
+        LPVS_HIP(hipEventCreateWithFlags(&done, hipEventDisableTiming));
         return LPVS_OK;
     }
+    ~SideStream() {
+        if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
+        if (ready) (void)hipEventDestroy(ready);
+        if (done) (void)hipEventDestroy(done);
+    }
 };
+
+// trig and activation tables (Npad rows), the pair products of the symmetric-pair form, the work buffers
+static int32_t kr_tables(LpvJob &J, const GramPlan &pl, KrBufs &t) {
+    lpvs_problem *h = J.h; hipStream_t s = h->stream;
+    const int64_t Npad = pl.ksplit * pl.rows_per_chunk;
+    const bool krs = J.form == GramForm::krs;
+    LPVS_HIP(hipEventRecord(h->ev[0].a, s));
+    LPVS_TRY(build_lpv_tables(J.dX.p, J.dV.p, J.N, Npad, J.dw.p, J.Nf, J.Nv, J.normalize, J.coulomb, t.T, t.K, &t.ldk, s, J.ranges));
+    if (krs) {
+        LPVS_TRY(t.KK.alloc(sizeof(double) * (size_t)Npad * (size_t)pl.pairs));
+        LPVS_TRY(launch_pair_table(t.K.as<double>(), t.ldk, J.nb, Npad, t.KK.as<double>(), s));
+    }
+    LPVS_HIP(hipEventRecord(h->ev[0].b, s));
+    LPVS_TRY(t.slab.alloc(pl.slab_bytes));
+    LPVS_TRY(t.scr.alloc(rhs_scratch_bytes(J.N, h->n)));
+    if (krs) LPVS_TRY(t.G3.alloc(sizeof(double) * (size_t)pl.np2 * (size_t)(pl.np2 * pl.pairs)));
+    return LPVS_OK;
+}
+
+// the Gram kernel with the right-hand sides on the side stream underneath it, then the reduction, which waits for them
+static int32_t kr_gram_rhs_reduce(LpvJob &J, const GramPlan &pl, KrBufs &t, SideStream &side) {
+    lpvs_problem *h = J.h; hipStream_t s = h->stream;
+    const bool krs = J.form == GramForm::krs;
+    const double2 *T = t.T.as<double2>(); const double *K = t.K.as<double>();
+    LPVS_HIP(hipEventRecord(side.ready, s));                 // tables are complete at this point of the main stream
+    LPVS_HIP(hipStreamWaitEvent(side.s, side.ready, 0));
+    LPVS_HIP(hipEventRecord(h->ev[1].a, s));
+    if (krs) LPVS_TRY(launch_gram_krs(pl, T, J.Nf, t.KK.as<double>(), J.nb, t.slab.as<double>(), s, &h->gram_stage));
+    else LPVS_TRY(launch_gram_kr(pl, T, J.Nf, K, t.ldk, J.nb, t.slab.as<double>(), s, &h->gram_stage));
+    LPVS_HIP(hipEventRecord(h->ev[1].b, s));
+    for (int64_t q = 0; q < J.ns; ++q)   // b_q = Phi' y_q for every signal sharing the regressor
+        LPVS_TRY(launch_rhs_kr(T, J.Nf, K, t.ldk, J.nb, J.dy.p + q * J.N, J.N, h->b.as<double>() + q * h->np, t.scr.as<double>(), t.scr.bytes, side.s));
+    LPVS_HIP(hipEventRecord(side.done, side.s));
+    LPVS_HIP(hipEventRecord(h->ev[2].a, s));
+    if (krs) LPVS_TRY(launch_gram_reduce_krs(pl, t.slab.as<double>(), J.nb, t.G3.as<double>(), h->G.as<double>(), h->np, s));
+    else LPVS_TRY(launch_gram_reduce(pl, t.slab.as<double>(), h->G.as<double>(), h->np, s));
+    LPVS_HIP(hipStreamWaitEvent(s, side.done, 0));
+    LPVS_HIP(hipEventRecord(h->ev[2].b, s));
+    return LPVS_OK;
+}
+
+// dense: tables, Gram with the side-stream right-hand sides, reduce.  Owns the temporaries and the drain.
+static int32_t lpv_dense(LpvJob &J) {
+    LPVS_TRY(open_problem(J.h, J.ns, ZeroGram::all));
+    const GramPlan pl = J.form == GramForm::krs ? make_gram_plan_pairs(J.Nf, J.nb, J.N) : make_gram_plan(J.h->n, J.N);
+    KrBufs t;
+    DrainOnExit drain(J.h->stream);
+    LPVS_TRY(kr_tables(J, pl, t));
+    SideStream side;
+    LPVS_TRY(side.open());
+    LPVS_TRY(kr_gram_rhs_reduce(J, pl, t, side));
+    return close_problem(J.h, J.form, dense_issued_flops(pl), pl.ksplit);
+}
 
 // ranges (optional) = {min V, max V, max|V|, max|X|} over ALL rows of the signal when (y, X, V) is only a row shard of it
 static int32_t create_lpv_impl(const double *y, int64_t ns, const double *X, const double *V, int64_t N, const double *w, int64_t Nf,
@@ -1021,169 +1220,15 @@ static int32_t create_lpv_impl(const double *y, int64_t ns, const double *X, con
     if (N <= 0 || Nf <= 0 || Nv <= 0 || ns <= 0) { set_error("N, Nf, Nv and the number of signals must be positive"); return LPVS_EARGUMENT; }
     lpvs_problem *h = nullptr;
     LPVS_TRY(problem_begin(device, out, &h));
-    struct Guard { lpvs_problem *h; ~Guard() { delete h; } } guard{h};
+    HandleGuard guard{h};
     hipStream_t s = h->stream;
-    const int64_t nb = coulomb ? 2 * Nv : Nv;
-    h->kind = 1; h->N = N; h->Nf = Nf; h->nb = nb; h->n = 2 * Nf * nb; h->np = round_up(h->n, 128); h->ns = ns;
-    DevArg dy, dX, dV, dw;
-    LPVS_TRY(dy.set(y, N * ns, s)); LPVS_TRY(dX.set(X, N, s)); LPVS_TRY(dV.set(V, N, s)); LPVS_TRY(dw.set(w, Nf, s));
-    LPVS_TRY(h->G.alloc(sizeof(double) * (size_t)h->np * (size_t)h->np));
-    LPVS_TRY(h->b.alloc(sizeof(double) * (size_t)h->np * (size_t)ns));
-    LPVS_HIP(hipMemsetAsync(h->b.p, 0, h->b.bytes, s));   // (G: below, once the Gram form is known)
-    LPVS_TRY(alloc_state(h));
-
-    // ---- Gram form.  LPVS_GRAM_FORM = auto (default) | ap | krs | kr
-    //   ap : w is an arithmetic progression up to rounding -> 3Nf-1 non-uniform Fourier sums per activation pair
-    //        (nudft.hip); admitted when max|eps_f| * max|x| <= 1e-7 (second-order term <= 5e-15)
-    //   krs / kr : dense MFMA contraction for arbitrary w (gram.hip)
-    const int form_opt = option_in_effect(LPVS_OPT_GRAM_FORM, h->opt[LPVS_OPT_GRAM_FORM]);
-    const std::string form = form_opt == LPVS_GRAM_AP ? "ap" : form_opt == LPVS_GRAM_KRS ? "krs" : form_opt == LPVS_GRAM_KR ? "kr" : "auto";
-    bool use_ap = false;
-    ApSlots sl;
-    double xam = 0;                                  // max|X| (over all rows of the signal)
-    if (form == "auto" || form == "ap") {
-        std::vector<double> hw;
-        LPVS_TRY(fetch_host(hw, w, Nf));
-        double xlo, xhi;
-        if (ranges) xam = ranges[3];
-        else LPVS_TRY(device_minmax(dX.p, N, &xlo, &xhi, &xam, s));
-        sl = make_ap_slots(hw, xam);
-        use_ap = sl.ok;
-        if (form == "ap" && !use_ap) { set_error("LPVS_GRAM_FORM=ap but w is not an arithmetic progression (max|eps|*max|x| = %.3g)", sl.emax * xam); return LPVS_EARGUMENT; }
-    }
-    // The structured assembly writes every element of the n x n block: only the pad strips (rows and columns n .. np) need zeros.
-    // The dense forms accumulate into / leave parts of G: they get the whole of it zeroed.
-    if (use_ap) {
-        const int64_t n = h->n, np = h->np;
-        if (np > n) {
-            LPVS_HIP(hipMemsetAsync(h->G.as<double>() + n * np, 0, sizeof(double) * (size_t)(np - n) * (size_t)np, s));
-            LPVS_HIP(hipMemset2DAsync(h->G.as<double>() + n, sizeof(double) * (size_t)np, 0, sizeof(double) * (size_t)(np - n), (size_t)n, s));
-        }
-    } else {
-        LPVS_HIP(hipMemsetAsync(h->G.p, 0, h->G.bytes, s));
-    }
-    if (use_ap) {
-        const int64_t nf8 = sl.nf8, nsl = sl.nsl, P = nb * (nb + 1) / 2;
-        const ApStep &step = sl.step;
-        double lo, hi, am, gamma; std::vector<double> vc;
-        DevBuf K, KK, dvc, part, tab, tabb, nwork, epsr;   // (all temporaries before the drain guard: released only after the stream is idle)
-        ApSlotsDev sd;
-        DrainOnExit drain(s);
-        LPVS_HIP(hipEventRecord(h->ev[0].a, s));
-        if (ranges) { lo = ranges[0]; hi = ranges[1]; am = ranges[2]; }
-        else LPVS_TRY(device_minmax(dV.p, N, &lo, &hi, &am, s));
-        basis_centers(lo, hi, am, Nv, coulomb, vc, &gamma);
-        const int64_t ldk = nb + 1;
-        LPVS_TRY(dvc.alloc(sizeof(double) * vc.size()));
-        LPVS_TRY(copy_to_device(dvc.p, vc.data(), sizeof(double) * vc.size(), s));
-        LPVS_TRY(K.alloc(sizeof(double) * (size_t)N * (size_t)ldk));
-        LPVS_TRY(KK.alloc(sizeof(double) * (size_t)N * (size_t)P));
-        LPVS_TRY(launch_basis_table(dV.p, N, dvc.as<double>(), nb, gamma, normalize, coulomb, K.as<double>(), ldk, s));
-        LPVS_TRY(launch_pair_table(K.as<double>(), ldk, nb, N, KK.as<double>(), s));
-        LPVS_TRY(sd.upload(sl, s));
-        LPVS_HIP(hipEventRecord(h->ev[0].b, s));
-        LPVS_TRY(part.alloc(std::max(nudft_partial_bytes(N, nsl, P), nudft_partial_bytes(N, nf8, nb))));
-        LPVS_TRY(tab.alloc(sizeof(double) * (size_t)nsl * (size_t)P * 4));
-        LPVS_TRY(tabb.alloc(sizeof(double) * (size_t)nf8 * (size_t)nb * 4));
-        LPVS_HIP(hipEventRecord(h->ev[1].a, s));
-        // merged slot layout: the slot sums are Fourier coefficients at the multiples of ONE step -> non-uniform FFT (nufft.hip);
-        // LPVS_NUDFT=direct keeps the direct evaluation of nudft.hip
-        const bool nufft_on = option_in_effect(LPVS_OPT_SLOT_SUMS, h->opt[LPVS_OPT_SLOT_SUMS]) != LPVS_SLOTS_DIRECT;
-        bool nufft = nufft_on && sl.merged && nufft_applicable(N, nsl, P);
-        const int nfg = nufft_grid_size(nsl);
-        const double xam_ = xam;
-        if (nufft) {
-            LPVS_TRY(nwork.alloc(nufft_work_bytes(N, nsl, P)));
-            const int32_t rc = launch_nufft_tab(dX.p, nullptr, N, xam_, KK.as<double>(), P, (int)P, step.hi[1], step.lo[1], 0, (int)nsl, nfg, false, nwork.p,
-                                                tab.as<double>(), s);
-            if (rc == kNufftNonFinite) nufft = false;    // NaN / Inf in the inputs: the direct sums propagate them as the reference does
-            else if (rc != LPVS_OK) return rc;
-        }
-        if (nufft) {
-            h->gram_form = 5;
-        } else {
-            h->gram_form = 4;
-            LPVS_TRY(launch_nudft(dX.p, nullptr, N, KK.as<double>(), P, (int)P, sd.hi.as<double>(), sd.lo.as<double>(), (int)nsl, step, part.as<double>(), tab.as<double>(), s));
-        }
-        LPVS_TRY(launch_ap_assemble(tab.as<double>(), sd.eps.as<double>(), Nf, sl.s0, sl.delta, nb, h->n, h->G.as<double>(), h->np, s));
-        LPVS_HIP(hipEventRecord(h->ev[1].b, s));
-        LPVS_HIP(hipEventRecord(h->ev[2].a, s));
-        // right-hand sides: the slots a + f*D are the modes s0/2 + f of the same step when s0 is even -> same grid, same coordinates
-        const bool nufft_rhs = nufft && sl.s0 % 2 == 0 && (int)(sl.s0 / 2 + nf8) <= (int)nsl;
-        // mode (s0/2 + f) D is a + f D - delta/2: the residual joins the first-order term (epsr)
-        if (nufft_rhs) {
-            std::vector<double> er(sl.eps.size());
-            for (size_t f = 0; f < er.size(); ++f) er[f] = sl.eps[f] + 0.5 * sl.delta;
-            LPVS_TRY(epsr.alloc(sizeof(double) * er.size()));
-            LPVS_TRY(copy_to_device(epsr.p, er.data(), sizeof(double) * er.size(), s));
-            LPVS_HIP(hipStreamSynchronize(s));       // (er is a local)
-        }
-        for (int64_t q = 0; q < ns; ++q) {   // b_q = Phi' y_q: Nf slots a + f*D, weights y K_j, first-order eps correction
-            bool by_nufft = nufft_rhs;
-            if (by_nufft) {
-                const int32_t rc = launch_nufft_tab(dX.p, dy.p + q * N, N, xam_, K.as<double>(), ldk, (int)nb, step.hi[1], step.lo[1], (int)(sl.s0 / 2), (int)nf8, nfg,
-                                                    true, nwork.p, tabb.as<double>(), s);
-                if (rc == kNufftNonFinite) by_nufft = false;   // a NaN / Inf in this signal
-                else if (rc != LPVS_OK) return rc;
-            }
-            if (!by_nufft)
-                LPVS_TRY(launch_nudft(dX.p, dy.p + q * N, N, K.as<double>(), ldk, (int)nb, sd.rhi.as<double>(), sd.rlo.as<double>(), (int)nf8, step, part.as<double>(), tabb.as<double>(), s));
-            LPVS_TRY(launch_ap_rhs(tabb.as<double>(), by_nufft ? epsr.as<double>() : sd.eps.as<double>(), Nf, nb, h->b.as<double>() + q * h->np, s));
-        }
-        LPVS_HIP(hipEventRecord(h->ev[2].b, s));
-        LPVS_HIP(hipStreamSynchronize(s));
-        h->t_basis = h->ev[0].ms(); h->t_gram = h->ev[1].ms(); h->t_reduce = h->ev[2].ms();
-        h->gram_launches = 8.0 * (double)N * (double)nsl * (double)P;   // flops the structured form issues (4 fma per sample, slot, pair)
-        h->gram_flops = (double)N * (double)h->n * (double)(h->n + 1);
-        guard.h = nullptr;
-        *out = h;
-        return LPVS_OK;
-    }
-
-    const bool krs = form != "kr" && gram_krs_fits(nb);   // symmetric-pair form unless the pair table does not fit LDS
-    const GramPlan pl = krs ? make_gram_plan_pairs(Nf, nb, N) : make_gram_plan(h->n, N);
-    const int64_t Npad = pl.ksplit * pl.rows_per_chunk;
-
-    DevBuf T, K, KK, G3, slab, scr; int64_t ldk;
-    DrainOnExit drain(s);
-    LPVS_HIP(hipEventRecord(h->ev[0].a, s));
-    LPVS_TRY(build_lpv_tables(dX.p, dV.p, N, Npad, dw.p, Nf, Nv, normalize, coulomb, T, K, &ldk, s, ranges));
-    if (krs) {
-        LPVS_TRY(KK.alloc(sizeof(double) * (size_t)Npad * (size_t)pl.pairs));
-        LPVS_TRY(launch_pair_table(K.as<double>(), ldk, nb, Npad, KK.as<double>(), s));
-    }
-    LPVS_HIP(hipEventRecord(h->ev[0].b, s));
-    LPVS_TRY(slab.alloc(pl.slab_bytes));
-    LPVS_TRY(scr.alloc(rhs_scratch_bytes(N, h->n)));
-    if (krs) LPVS_TRY(G3.alloc(sizeof(double) * (size_t)pl.np2 * (size_t)(pl.np2 * pl.pairs)));
-    // b_q = Phi' y_q is HBM-bound (it streams the trig table) while the Gram is MFMA-bound and leaves registers
-    // free for small workgroups: run it on a side stream underneath the Gram kernel.
-    struct Side { hipStream_t s = nullptr; hipEvent_t ready = nullptr, done = nullptr;
-                  ~Side() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } if (ready) (void)hipEventDestroy(ready); if (done) (void)hipEventDestroy(done); } } side;
-    LPVS_HIP(hipStreamCreateWithFlags(&side.s, hipStreamNonBlocking));
-    LPVS_HIP(hipEventCreateWithFlags(&side.ready, hipEventDisableTiming));
-    LPVS_HIP(hipEventCreateWithFlags(&side.done, hipEventDisableTiming));
-    LPVS_HIP(hipEventRecord(side.ready, s));                 // tables are complete at this point of the main stream
-    LPVS_HIP(hipStreamWaitEvent(side.s, side.ready, 0));
-    LPVS_HIP(hipEventRecord(h->ev[1].a, s));
-    if (krs) LPVS_TRY(launch_gram_krs(pl, T.as<double2>(), Nf, KK.as<double>(), nb, slab.as<double>(), s, &h->gram_stage));
-    else LPVS_TRY(launch_gram_kr(pl, T.as<double2>(), Nf, K.as<double>(), ldk, nb, slab.as<double>(), s, &h->gram_stage));
-    LPVS_HIP(hipEventRecord(h->ev[1].b, s));
-    for (int64_t q = 0; q < ns; ++q)   // b_q = Phi' y_q for every signal sharing the regressor
-        LPVS_TRY(launch_rhs_kr(T.as<double2>(), Nf, K.as<double>(), ldk, nb, dy.p + q * N, N, h->b.as<double>() + q * h->np, scr.as<double>(), scr.bytes, side.s));
-    LPVS_HIP(hipEventRecord(side.done, side.s));
-    LPVS_HIP(hipEventRecord(h->ev[2].a, s));
-    if (krs) LPVS_TRY(launch_gram_reduce_krs(pl, slab.as<double>(), nb, G3.as<double>(), h->G.as<double>(), h->np, s));
-    else LPVS_TRY(launch_gram_reduce(pl, slab.as<double>(), h->G.as<double>(), h->np, s));
-    LPVS_HIP(hipStreamWaitEvent(s, side.done, 0));
-    LPVS_HIP(hipEventRecord(h->ev[2].b, s));
-    LPVS_HIP(hipStreamSynchronize(s));
-    h->t_basis = h->ev[0].ms(); h->t_gram = h->ev[1].ms(); h->t_reduce = h->ev[2].ms();
-    h->gram_launches = (double)pl.tiles * 128.0 * 256.0 * 2.0 * (double)(pl.ksplit * pl.rows_per_chunk); h->gram_flops = (double)N * (double)h->n * (double)(h->n + 1);
-    h->gram_form = krs ? 2 : 1; h->gram_ksplit = (int)pl.ksplit;
-    guard.h = nullptr;
-    *out = h;
-    return LPVS_OK;
+    LpvJob J;
+    J.h = h; J.ns = ns; J.N = N; J.Nf = Nf; J.Nv = Nv; J.nb = coulomb ? 2 * Nv : Nv; J.normalize = normalize; J.coulomb = coulomb; J.ranges = ranges;
+    h->kind = 1; h->N = N; h->Nf = Nf; h->nb = J.nb; h->n = 2 * Nf * J.nb;
+    LPVS_TRY(J.dy.set(y, N * ns, s)); LPVS_TRY(J.dX.set(X, N, s)); LPVS_TRY(J.dV.set(V, N, s)); LPVS_TRY(J.dw.set(w, Nf, s));
+    LPVS_TRY(lpv_choose_form(J, w));
+    LPVS_TRY(is_structured(J.form) ? lpv_structured(J) : lpv_dense(J));
+    return guard.release(out);
 }
 
 int32_t lpvs_problem_create_lpv_f64(const double *y, const double *X, const double *V, int64_t N, const double *w, int64_t Nf,
@@ -1239,68 +1284,26 @@ int32_t lpvs_problem_create_fourier_f64(const double *y, const double *t, int64_
     LPVS_TRY(lpvs_check_freq_f64(f, Nf, &zf));
     lpvs_problem *h = nullptr;
     LPVS_TRY(problem_begin(device, out, &h));
-    struct Guard { lpvs_problem *h; ~Guard() { delete h; } } guard{h};
+    HandleGuard guard{h};
     hipStream_t s = h->stream;
     h->kind = 0; h->N = N; h->Nf = Nf; h->zerofreq = zf; h->n = fourier_regressors(Nf, zf != 0);
     DevArg dt, df;
     LPVS_TRY(dt.set(t, N, s)); LPVS_TRY(df.set(f, Nf, s));
-    // structured Gram when T(2pi)*f is an arithmetic progression (default_freqs and every grid of the reference's tests)
-    const int form_opt = option_in_effect(LPVS_OPT_GRAM_FORM, h->opt[LPVS_OPT_GRAM_FORM]);
-    const std::string form = form_opt == LPVS_GRAM_AP ? "ap" : form_opt == LPVS_GRAM_KRS ? "krs" : form_opt == LPVS_GRAM_KR ? "kr" : "auto";
-    if (form == "auto" || form == "ap") {
-        std::vector<double> hw;
-        LPVS_TRY(fetch_host(hw, f, Nf));
-        for (auto &v : hw) v = 6.283185307179586 * v;          // rounded as the regressor kernel does (src/lsfft.jl:33)
-        double tlo, thi, tam;
-        LPVS_TRY(device_minmax(dt.p, N, &tlo, &thi, &tam, s));
-        const ApSlots sl = make_ap_slots(hw, tam);
-        if (form == "ap" && !sl.ok) { set_error("LPVS_GRAM_FORM=ap but 2*pi*f is not an arithmetic progression (max|eps|*max|t| = %.3g)", sl.emax * tam); return LPVS_EARGUMENT; }
-        if (sl.ok) {
-            h->np = round_up(h->n, 128);
-            DevArg dy, dW;
-            LPVS_TRY(dy.set(y, N, s));
-            if (W) LPVS_TRY(dW.set(W, N, s));
-            LPVS_TRY(h->G.alloc(sizeof(double) * (size_t)h->np * (size_t)h->np));
-            LPVS_TRY(h->b.alloc(sizeof(double) * (size_t)h->np));
-            LPVS_HIP(hipMemsetAsync(h->G.p, 0, h->G.bytes, s));
-            LPVS_HIP(hipMemsetAsync(h->b.p, 0, h->b.bytes, s));
-            LPVS_TRY(alloc_state(h));
-            ApSlotsDev sd; DevBuf part, tab, tabb;
-            DrainOnExit drain(s);
-            LPVS_HIP(hipEventRecord(h->ev[0].a, s));
-            LPVS_TRY(sd.upload(sl, s));
-            LPVS_HIP(hipEventRecord(h->ev[0].b, s));
-            // (BOTH launches below share `part`: the right-hand side's has a third of the slots but -- fewer slot groups, so smaller chunks --
-            // up to four times the chunks.  Sized for the Gram launch alone it overflowed for N / rows-per-chunk in [171, 256), e.g.
-            // N = 118727 or 204800: found as a GPU fault in test_fourier_gram_additivity_cfg2 when the minimum chunk went from 512 to 64.)
-            LPVS_TRY(part.alloc(std::max(nudft_partial_bytes(N, sl.nsl, 1), nudft_partial_bytes(N, sl.nf8, 1))));
-            LPVS_TRY(tab.alloc(sizeof(double) * (size_t)sl.nsl * 4));
-            LPVS_TRY(tabb.alloc(sizeof(double) * (size_t)sl.nf8 * 4));
-            const double *Wd = W ? dW.p : nullptr;               // A' diag(W) A and A' (W .* y), src/lasso.jl:119-120
-            LPVS_HIP(hipEventRecord(h->ev[1].a, s));
-            LPVS_TRY(launch_nudft(dt.p, nullptr, N, Wd, 1, 1, sd.hi.as<double>(), sd.lo.as<double>(), (int)sl.nsl, sl.step, part.as<double>(), tab.as<double>(), s));
-            LPVS_TRY(launch_ap_assemble_fourier(tab.as<double>(), sd.eps.as<double>(), Nf, sl.s0, sl.delta, (int)zf, h->n, h->G.as<double>(), h->np, 1, 0, 0, s));
-            LPVS_HIP(hipEventRecord(h->ev[1].b, s));
-            LPVS_HIP(hipEventRecord(h->ev[2].a, s));
-            LPVS_TRY(launch_nudft(dt.p, dy.p, N, Wd, 1, 1, sd.rhi.as<double>(), sd.rlo.as<double>(), (int)sl.nf8, sl.step, part.as<double>(), tabb.as<double>(), s));
-            LPVS_TRY(launch_ap_rhs_fourier(tabb.as<double>(), sd.eps.as<double>(), Nf, (int)zf, h->b.as<double>(), 1, 0, 0, s));
-            LPVS_HIP(hipEventRecord(h->ev[2].b, s));
-            LPVS_HIP(hipStreamSynchronize(s));
-            h->t_basis = h->ev[0].ms(); h->t_gram = h->ev[1].ms(); h->t_reduce = h->ev[2].ms();
-            h->gram_launches = 8.0 * (double)N * (double)sl.nsl;
-            h->gram_flops = (double)N * (double)h->n * (double)(h->n + 1);
-            h->gram_form = 4;
-            guard.h = nullptr;
-            *out = h;
-            return LPVS_OK;
-        }
+    GramFormFacts ff; ff.family = GramFamily::fourier;
+    ff.option = option_in_effect(LPVS_OPT_GRAM_FORM, h->opt[LPVS_OPT_GRAM_FORM]);
+    ApSlots sl; double tam = -1;
+    if (gram_option_wants_slots(ff.option)) LPVS_TRY(fourier_slots(f, Nf, dt.p, N, &tam, s, sl));
+    ff.slots_ok = sl.ok; ff.merged = sl.merged;
+    const GramForm form = choose_gram_form(ff);
+    if (form == GramForm::refused) { set_error("LPVS_GRAM_FORM=ap but 2*pi*f is not an arithmetic progression (max|eps|*max|t| = %.3g)", sl.emax * tam); return LPVS_EARGUMENT; }
+    if (is_structured(form)) {
+        LPVS_TRY(create_fourier_structured(h, y, dt.p, W, sl));
+        return guard.release(out);
     }
     LPVS_TRY(create_panel_problem(h, y, W, N, [&](double *P, int64_t ld) {
         return launch_fourier_panel(dt.p, N, df.p, Nf, (int)zf, P, ld, s);
     }));
-    guard.h = nullptr;
-    *out = h;
-    return LPVS_OK;
+    return guard.release(out);
 }
 
 int32_t lpvs_problem_create_dense_f64(const double *A, const double *y, int64_t m, int64_t n, const double *W, int32_t device,
@@ -1308,7 +1311,7 @@ int32_t lpvs_problem_create_dense_f64(const double *A, const double *y, int64_t 
     if (m <= 0 || n <= 0) { set_error("m and n must be positive"); return LPVS_EARGUMENT; }
     lpvs_problem *h = nullptr;
     LPVS_TRY(problem_begin(device, out, &h));
-    struct Guard { lpvs_problem *h; ~Guard() { delete h; } } guard{h};
+    HandleGuard guard{h};
     hipStream_t s = h->stream;
     h->kind = 2; h->N = m; h->n = n;
     DevArg dA;
@@ -1316,30 +1319,22 @@ int32_t lpvs_problem_create_dense_f64(const double *A, const double *y, int64_t 
     LPVS_TRY(create_panel_problem(h, y, W, m, [&](double *P, int64_t ld) {
         return launch_transpose_to_panel(dA.p, m, n, P, ld, s);
     }));
-    guard.h = nullptr;
-    *out = h;
-    return LPVS_OK;
+    return guard.release(out);
 }
 
 int32_t lpvs_problem_create_gram_f64(const double *G, const double *b, int64_t n, int32_t device, lpvs_problem **out) {
     if (n <= 0) { set_error("n must be positive"); return LPVS_EARGUMENT; }
     lpvs_problem *h = nullptr;
     LPVS_TRY(problem_begin(device, out, &h));
-    struct Guard { lpvs_problem *h; ~Guard() { delete h; } } guard{h};
+    HandleGuard guard{h};
     hipStream_t s = h->stream;
-    h->kind = 2; h->n = n; h->np = round_up(n, 128);
-    LPVS_TRY(h->G.alloc(sizeof(double) * (size_t)h->np * (size_t)h->np));
-    LPVS_TRY(h->b.alloc(sizeof(double) * (size_t)h->np));
-    LPVS_HIP(hipMemsetAsync(h->G.p, 0, h->G.bytes, s));
-    LPVS_HIP(hipMemsetAsync(h->b.p, 0, h->b.bytes, s));
-    LPVS_TRY(alloc_state(h));
+    h->kind = 2; h->n = n;
+    LPVS_TRY(open_problem(h, 1, ZeroGram::all));
     LPVS_HIP(hipMemcpy2DAsync(h->G.p, sizeof(double) * (size_t)h->np, G, sizeof(double) * (size_t)n, sizeof(double) * (size_t)n, (size_t)n,
                               is_device_ptr(G) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
     LPVS_HIP(hipStreamSynchronize(s));
     LPVS_TRY(copy_to_device(h->b.p, b, sizeof(double) * (size_t)n, s));
-    guard.h = nullptr;
-    *out = h;
-    return LPVS_OK;
+    return guard.release(out);
 }
 
 int32_t lpvs_problem_destroy(lpvs_problem *h) {
@@ -1456,7 +1451,7 @@ int32_t lpvs_problem_create_path(lpvs_problem *src, int64_t ns, lpvs_problem **o
     if (ns < 1 || ns > 64) { set_error("ns = %lld outside [1, 64]", (long long)ns); return LPVS_EARGUMENT; }
     lpvs_problem *h = nullptr;
     LPVS_TRY(problem_begin(src->device, out, &h));
-    struct Guard { lpvs_problem *h; ~Guard() { delete h; } } guard{h};
+    HandleGuard guard{h};
     hipStream_t s = h->stream;
     h->kind = src->kind; h->N = src->N; h->Nf = src->Nf; h->nb = src->nb; h->zerofreq = src->zerofreq; h->n = src->n; h->np = src->np; h->ns = ns;
     h->f32 = src->f32;
@@ -1471,9 +1466,7 @@ int32_t lpvs_problem_create_path(lpvs_problem *src, int64_t ns, lpvs_problem **o
     for (int64_t q = 0; q < ns; ++q)                 // every right-hand side is the source's
         LPVS_HIP(hipMemcpyAsync(h->b.as<double>() + q * h->np, src->b.p, vbytes, hipMemcpyDeviceToDevice, s));
     LPVS_HIP(hipStreamSynchronize(s));
-    guard.h = nullptr;
-    *out = h;
-    return LPVS_OK;
+    return guard.release(out);
 }
 
 int32_t lpvs_admm_init_f64(lpvs_problem *h, const double *x0, double mu, double tol, int32_t linear_sign) {
@@ -1729,18 +1722,14 @@ int32_t lpvs_ls_spectral_f64(const double *y, const double *t, int64_t N, const 
     // fat: Gram over the regressor columns, G2 = A A' (N x N), alpha = (G2 + lam^2 I)^-1 y, x = A' alpha
     lpvs_problem *dummy = nullptr;
     LPVS_TRY(problem_begin(device, &dummy, &h));
-    struct Guard { lpvs_problem *h; ~Guard() { delete h; } } guard{h};
+    HandleGuard guard{h};
     hipStream_t s = h->stream;
-    h->kind = 0; h->N = nreg; h->Nf = Nf; h->zerofreq = zf; h->n = N; h->np = round_up(N, 128);
+    h->kind = 0; h->N = nreg; h->Nf = Nf; h->zerofreq = zf; h->n = N;
     const GramPlan pl = make_gram_plan(N, nreg);
     const int64_t rows = pl.ksplit * pl.rows_per_chunk, ldn = round_up(N, 256);
     DevArg dy, dt, df;
     LPVS_TRY(dy.set(y, N, s)); LPVS_TRY(dt.set(t, N, s)); LPVS_TRY(df.set(f, Nf, s));
-    LPVS_TRY(h->G.alloc(sizeof(double) * (size_t)h->np * (size_t)h->np));
-    LPVS_TRY(h->b.alloc(sizeof(double) * (size_t)h->np));
-    LPVS_HIP(hipMemsetAsync(h->G.p, 0, h->G.bytes, s));
-    LPVS_HIP(hipMemsetAsync(h->b.p, 0, h->b.bytes, s));
-    LPVS_TRY(alloc_state(h));
+    LPVS_TRY(open_problem(h, 1, ZeroGram::all));
     LPVS_HIP(hipMemcpyAsync(h->b.p, dy.p, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, s));   // right-hand side = y
     DevBuf D, slab, xo;
     DrainOnExit drain(s);
@@ -1860,24 +1849,21 @@ struct WinEngine {
     int32_t choose_gram_form() {
         if (a.opt_captured) for (int i = 0; i < kOptCount; ++i) jopt[i] = a.opt[i];
         else capture_default_options(jopt);
-        const int form = option_in_effect(LPVS_OPT_GRAM_FORM, jopt[LPVS_OPT_GRAM_FORM]);
-        if (form == 0 || form == LPVS_GRAM_AP) {
-            std::vector<double> hw;
-            LPVS_TRY(fetch_host(hw, a.freqs, Nf));
-            for (auto &v : hw) v = 6.283185307179586 * v;
-            double tlo, thi, tam = a.t_absmax;
-            if (!(tam >= 0)) LPVS_TRY(device_minmax(dt.p, a.L, &tlo, &thi, &tam, s));
-            sl = make_ap_slots(hw, tam);
-            if (form == LPVS_GRAM_AP && !sl.ok) { set_error("LPVS_GRAM_FORM=ap but 2*pi*freqs is not an arithmetic progression (max|eps|*max|t| = %.3g)", sl.emax * tam); return LPVS_EARGUMENT; }
-        }
-        ap = sl.ok;
+        GramFormFacts ff; ff.family = GramFamily::windows;
+        ff.option = option_in_effect(LPVS_OPT_GRAM_FORM, jopt[LPVS_OPT_GRAM_FORM]);
+        ff.slots_direct = option_in_effect(LPVS_OPT_SLOT_SUMS, jopt[LPVS_OPT_SLOT_SUMS]) == LPVS_SLOTS_DIRECT;   // LPVS_NUDFT=direct keeps the direct sums
+        double tam = a.t_absmax;
+        if (gram_option_wants_slots(ff.option)) LPVS_TRY(fourier_slots(a.freqs, Nf, dt.p, a.L, &tam, s, sl));
+        ff.slots_ok = sl.ok; ff.merged = sl.merged; ff.N = n; ff.nsl = sl.nsl;
+        const GramForm form = lpvs::choose_gram_form(ff);
+        if (form == GramForm::refused) { set_error("LPVS_GRAM_FORM=ap but 2*pi*freqs is not an arithmetic progression (max|eps|*max|t| = %.3g)", sl.emax * tam); return LPVS_EARGUMENT; }
+        ap = is_structured(form);
         if (const char *e = getenv("LPVS_BATCH_PANEL_GIB")) { const long g = atol(e); if (g > 0) budget = (size_t)g << 30; }
         pl = make_gram_plan(fourier_regressors(Nf, zf != 0), n, kNominalBatch);
         pp = window_pass_plan(n, Nf, zf != 0, ns, nwin, sparse, init, ap, pl.ksplit * pl.rows_per_chunk, budget);
         nreg = pp.nreg; np = pp.np; ld = pp.ld; bw = pp.windows; vb = pp.vb;
-        // slot sums by non-uniform FFT (nufft.hip) when one progression serves all slots; LPVS_NUDFT=direct keeps the direct sums
-        wnufft = ap && sl.merged && nufft_windows_applicable(n, sl.nsl) && option_in_effect(LPVS_OPT_SLOT_SUMS, jopt[LPVS_OPT_SLOT_SUMS]) != LPVS_SLOTS_DIRECT;
-        wnufft_rhs = wnufft && sl.s0 % 2 == 0 && sl.s0 / 2 + sl.nf8 <= sl.nsl;   // a + f D = mode s0/2 + f (residual delta/2 -> eps)
+        wnufft = form == GramForm::ap_nufft;         // slot sums by non-uniform FFT (nufft.hip): one progression serves all slots
+        wnufft_rhs = wnufft && rhs_on_grid(sl);      // a + f D = mode s0/2 + f (residual delta/2 -> eps)
         nfg = wnufft ? nufft_grid_size(sl.nsl) : 0;
         wcols = wnufft_rhs ? 1 + ns : 1;
         storage_opt = option_in_effect(LPVS_OPT_M_STORAGE, jopt[LPVS_OPT_M_STORAGE]);
@@ -1903,8 +1889,7 @@ struct WinEngine {
         LPVS_TRY(copy_to_device(wscale_g.p, sg.data(), sizeof(double) * sg.size(), s));
         if (wnufft_rhs) {
             const std::vector<double> sr = nufft_window_scale(nfg, (int)(sl.s0 / 2), (int)sl.nf8);
-            std::vector<double> er(sl.eps.size());
-            for (size_t f = 0; f < er.size(); ++f) er[f] = sl.eps[f] + 0.5 * sl.delta;
+            const std::vector<double> er = rhs_residuals(sl);
             LPVS_TRY(wscale_r.alloc(sizeof(double) * sr.size()));
             LPVS_TRY(wepsr.alloc(sizeof(double) * er.size()));
             LPVS_TRY(copy_to_device(wscale_r.p, sr.data(), sizeof(double) * sr.size(), s));
@@ -2334,7 +2319,7 @@ struct HostOut {
 namespace lpvs {
 int32_t windows_engine_run(const WinJob &job, const WinSink &sink, bool chunked) {
     // (worker threads of multi.hip: the float-grid admission is a thread-local switch)
-    struct Admit { bool prev; explicit Admit(bool on) : prev(g_f32_admission) { if (on) g_f32_admission = true; } ~Admit() { g_f32_admission = prev; } } admit(job.f32_grid);
+    Admit admit(job.f32_grid);
     return chunked ? windows_engine_chunked(job, sink) : windows_engine(job, sink);
 }
 void windows_last_timing(double *out10) { for (int i = 0; i < 10; ++i) out10[i] = g_win_timing[i]; }
@@ -2536,7 +2521,7 @@ int32_t lpvs_problem_create_fourier_f32(const float *y, const float *t, int64_t 
     LPVS_HIP(hipSetDevice(device));
     WideArg dy, dt, df, dW;
     LPVS_TRY(dy.set(y, N, nullptr)); LPVS_TRY(dt.set(t, N, nullptr)); LPVS_TRY(df.set(f, Nf, nullptr)); LPVS_TRY(dW.set(W, N, nullptr));
-    struct Admit { Admit() { g_f32_admission = true; } ~Admit() { g_f32_admission = false; } } admit;
+    Admit admit;
     LPVS_TRY(lpvs_problem_create_fourier_f64(dy.p, dt.p, N, df.p, Nf, dW.p, device, out));
     (*out)->f32 = true;
     return LPVS_OK;
@@ -2549,7 +2534,7 @@ int32_t lpvs_problem_create_lpv_f32(const float *y, const float *X, const float 
     LPVS_HIP(hipSetDevice(device));
     WideArg dy, dX, dV, dw;
     LPVS_TRY(dy.set(y, N, nullptr)); LPVS_TRY(dX.set(X, N, nullptr)); LPVS_TRY(dV.set(V, N, nullptr)); LPVS_TRY(dw.set(w, Nf, nullptr));
-    struct Admit { Admit() { g_f32_admission = true; } ~Admit() { g_f32_admission = false; } } admit;
+    Admit admit;
     LPVS_TRY(lpvs_problem_create_lpv_f64(dy.p, dX.p, dV.p, N, dw.p, Nf, Nv, normalize, coulomb, device, out));
     (*out)->f32 = true;
     return LPVS_OK;
@@ -2562,7 +2547,7 @@ int32_t lpvs_problem_create_lpv_multi_f32(const float *Y, int64_t ns, const floa
     LPVS_HIP(hipSetDevice(device));
     WideArg dY, dX, dV, dw;
     LPVS_TRY(dY.set(Y, N * ns, nullptr)); LPVS_TRY(dX.set(X, N, nullptr)); LPVS_TRY(dV.set(V, N, nullptr)); LPVS_TRY(dw.set(w, Nf, nullptr));
-    struct Admit { Admit() { g_f32_admission = true; } ~Admit() { g_f32_admission = false; } } admit;
+    Admit admit;
     LPVS_TRY(lpvs_problem_create_lpv_multi_f64(dY.p, ns, dX.p, dV.p, N, dw.p, Nf, Nv, normalize, coulomb, device, out));
     (*out)->f32 = true;   // float I/O through the _f32 accessors; several right-hand sides keep the double matrix stream (matrix cores)
     return LPVS_OK;
@@ -2582,7 +2567,7 @@ int32_t lpvs_windows_estimate_f32(const float *Y, int64_t ns, const float *t, in
     const int64_t nwin = win_hi > win_lo ? win_hi - win_lo : 0;
     const int64_t cnt = ns * nwin * Nf;
     DevBuf o; LPVS_TRY(o.alloc(sizeof(double) * (size_t)(cnt > 0 ? cnt : 1) * 2));
-    struct Admit { Admit() { g_f32_admission = true; } ~Admit() { g_f32_admission = false; } } admit;
+    Admit admit;
     LPVS_TRY(lpvs_windows_estimate_f64(dY.p, ns, dt.p, L, n, noverlap, dW.p, df.p, Nf, estimator, lam, prox_kind, prox_param, group_len, mu, tol,
                                        iters, linear_sign, win_lo, win_hi, device, o.as<double>(), o.as<double>() + cnt, iters_out));
     LPVS_TRY(narrow_out(x_re, o.as<double>(), cnt, nullptr));
@@ -2603,7 +2588,7 @@ int32_t lpvs_windowcsd_f32(const float *y, const float *u, const float *t, int64
     const int64_t nwin = win_hi > win_lo ? win_hi - win_lo : 0, cnt = 2 * nwin * Nf;
     DevBuf o; LPVS_TRY(o.alloc(sizeof(double) * (size_t)((cnt > 0 ? cnt : 1) * 2 + 4 * Nf)));
     double *xr = o.as<double>(), *xi = xr + cnt, *acc = xi + cnt;          // acc: Syu_re, Syu_im, Syy, Suu
-    struct Admit { Admit() { g_f32_admission = true; } ~Admit() { g_f32_admission = false; } } admit;
+    Admit admit;
     LPVS_TRY(lpvs_windowcsd_f64(dy.p, du.p, dt.p, L, n, noverlap, dW.p, df.p, Nf, estimator, lam, prox_kind, prox_param, group_len, mu, tol, iters,
                                 linear_sign, win_lo, win_hi, device, acc, acc + Nf, acc + 2 * Nf, acc + 3 * Nf, x_re ? xr : nullptr,
                                 x_im ? xi : nullptr, iters_out));
@@ -2623,7 +2608,7 @@ int32_t lpvs_problem_create_lpv_rows_f32(const float *Y, int64_t ns, const float
     WideArg dY, dX, dV, dw;
     LPVS_TRY(dY.set(Y, N_local * ns, nullptr)); LPVS_TRY(dX.set(X, N_local, nullptr)); LPVS_TRY(dV.set(V, N_local, nullptr));
     LPVS_TRY(dw.set(w, Nf, nullptr));
-    struct Admit { Admit() { g_f32_admission = true; } ~Admit() { g_f32_admission = false; } } admit;
+    Admit admit;
     LPVS_TRY(lpvs_problem_create_lpv_rows_f64(dY.p, ns, dX.p, dV.p, N_local, dw.p, Nf, Nv, normalize, coulomb, ranges4, device, out));
     (*out)->f32 = true;
     return LPVS_OK;

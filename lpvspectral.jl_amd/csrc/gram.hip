@@ -33,9 +33,11 @@ namespace {
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
-constexpr int TM = 128;     // tile extent along a (rows of G)
-constexpr int TN = 256;     // tile extent along b (cols of G)
-constexpr int BK_ALIGN = 64;  // sample chunks are multiples of this (every stage depth divides it)
+constexpr int TM = kGramTileRows;     // tile extent along a (rows of G)
+constexpr int TN = kGramTileCols;     // tile extent along b (cols of G)
+// the tile lists of gram_form_plan.h go to the device as they are
+static_assert(sizeof(GramTile) == sizeof(int2) && alignof(GramTile) <= alignof(int2) && offsetof(GramTile, i) == offsetof(int2, x) &&
+              offsetof(GramTile, j) == offsetof(int2, y), "GramTile must match int2");
 constexpr int NTHREADS = 512;  // 8 waves: 2 (a) x 4 (b), 64x64 outputs each
 
 struct GramArgs {
@@ -471,64 +473,7 @@ rhs_reduce_kernel(const double *__restrict__ part, int nparts, int64_t ncol, dou
     b[col] = s;
 }
 
-struct TileList {
-    std::vector<int2> host;
-};
-TileList make_tiles(int64_t n) {
-    TileList tl;
-    const int64_t nti = ceil_div(n, TM);
-    for (int64_t ti = 0; ti < nti; ++ti)
-        for (int64_t tj = 0; tj <= ti / 2; ++tj) tl.host.push_back(make_int2((int)ti, (int)tj));
-    return tl;
-}
-
-// KRS tiles: rows p in [0,2Nf), columns q = p'*P + pair; tile needed when its first column's p' <= its last row
-TileList make_tiles_pairs(int64_t np2, int64_t P) {
-    TileList tl;
-    const int64_t nti = ceil_div(np2, TM), ntj = ceil_div(np2 * P, TN);
-    for (int64_t ti = 0; ti < nti; ++ti) {
-        const int64_t plast = (ti * TM + TM - 1 < np2 - 1) ? ti * TM + TM - 1 : np2 - 1;
-        for (int64_t tj = 0; tj < ntj; ++tj)
-            if ((tj * TN) / P <= plast) tl.host.push_back(make_int2((int)ti, (int)tj));
-    }
-    return tl;
-}
-
-static void choose_split(GramPlan &pl, int64_t N, int64_t nbatch = 1) {
-    // split the samples so that (tiles x chunks [x problems of a batch]) fills the 256 CUs in whole rounds
-    const int64_t nstage = ceil_div(N, BK_ALIGN);
-    const int64_t max_split = nstage / 8 > 0 ? nstage / 8 : 1;  // >= 512 samples per chunk
-    int64_t want = ceil_div(256 * 16, pl.tiles * nbatch);
-    if (want > max_split) want = max_split;
-    int64_t best = 1; double best_eff = -1;
-    for (int64_t ks = want / 2 > 0 ? want / 2 : 1; ks <= want * 2 && ks <= max_split; ++ks) {
-        const int64_t items = pl.tiles * ks * nbatch;
-        const double eff = (double)items / (double)(ceil_div(items, 256) * 256);
-        if (eff > best_eff + 1e-9) { best_eff = eff; best = ks; }
-    }
-    pl.ksplit = best;
-    pl.rows_per_chunk = round_up(ceil_div(N, pl.ksplit), BK_ALIGN);
-    pl.slab_bytes = sizeof(double) * (size_t)pl.tiles * (size_t)pl.ksplit * TM * TN;
-}
-
 }  // namespace
-
-GramPlan make_gram_plan_pairs(int64_t Nf, int64_t nb, int64_t N) {
-    GramPlan pl;
-    pl.n = 2 * Nf * nb; pl.N = N; pl.pairs = nb * (nb + 1) / 2; pl.np2 = 2 * Nf;
-    pl.tiles = (int64_t)make_tiles_pairs(pl.np2, pl.pairs).host.size();
-    choose_split(pl, N);
-    return pl;
-}
-
-GramPlan make_gram_plan(int64_t n, int64_t N, int64_t nbatch) {
-    GramPlan pl;
-    pl.n = n; pl.N = N;
-    pl.tiles = (int64_t)make_tiles(n).host.size();
-    choose_split(pl, N, nbatch < 1 ? 1 : nbatch);
-    return pl;
-}
-
 
 // Device copy of the tile list, cached per (n, pairs) on the calling thread.
 static int32_t get_tiles(int64_t n, int64_t pairs, hipStream_t s, const int2 **out, int *count) {
@@ -539,36 +484,16 @@ static int32_t get_tiles(int64_t n, int64_t pairs, hipStream_t s, const int2 **o
     int dev = 0;
     LPVS_HIP(hipGetDevice(&dev));
     if (cached_n != n || cached_pairs != pairs || cached_dev != dev) {
-        TileList tl = pairs > 0 ? make_tiles_pairs(n, pairs) : make_tiles(n);
+        const std::vector<GramTile> tl = pairs > 0 ? make_tiles_pairs(n, pairs) : make_tiles(n);
         cached.release();
-        LPVS_TRY(cached.alloc(sizeof(int2) * tl.host.size()));
-        LPVS_HIP(hipMemcpyAsync(cached.p, tl.host.data(), sizeof(int2) * tl.host.size(), hipMemcpyHostToDevice, s));
+        LPVS_TRY(cached.alloc(sizeof(int2) * tl.size()));
+        LPVS_HIP(hipMemcpyAsync(cached.p, tl.data(), sizeof(int2) * tl.size(), hipMemcpyHostToDevice, s));
         LPVS_HIP(hipStreamSynchronize(s));
-        cached_n = n; cached_pairs = pairs; cached_count = (int)tl.host.size(); cached_dev = dev;
+        cached_n = n; cached_pairs = pairs; cached_count = (int)tl.size(); cached_dev = dev;
     }
     *out = cached.as<int2>();
     *count = cached_count;
     return LPVS_OK;
-}
-
-static size_t gram_lds_bytes(int mode, int BK, int64_t nb, int64_t ldk) {
-    int img, aux;
-    if (mode == 0) {
-        const int g2 = (int)(2 * nb);
-        const int nfI = (TM + g2 - 2) / g2 + 1, nfJ = (TN + g2 - 2) / g2 + 1;  // upper bounds
-        img = BK * (nfI + nfJ) * 2;
-        aux = (int)(BK * ldk);
-    } else if (mode == 2) {
-        const int P = (int)(nb * (nb + 1) / 2);
-        const int nfI = TM / 2 + 1, nfJ = ((TN + P - 2) / P + 1) / 2 + 2;     // upper bounds
-        img = BK * (nfI + nfJ) * 2;
-        aux = (int)(BK * ldk);
-    } else {
-        img = BK * (TM + TN);
-        aux = BK;
-    }
-    const int img_pad = (img + 127) & ~127, aux_pad = (aux + 127) & ~127;
-    return sizeof(double) * 2 * (size_t)(img_pad + aux_pad);
 }
 
 template <int MODE, int BK>
@@ -580,8 +505,6 @@ static int32_t launch_gram_t(const GramArgs &a, unsigned grid, size_t lds, hipSt
     return LPVS_OK;
 }
 
-constexpr size_t kLdsBudget = 160 * 1024;
-
 int32_t launch_gram_kr(const GramPlan &pl, const double2 *T, int64_t Nf, const double *K, int64_t ldk,
                        int64_t nb, double *slab, hipStream_t s, int *stage) {
     GramArgs a{};
@@ -589,10 +512,14 @@ int32_t launch_gram_kr(const GramPlan &pl, const double2 *T, int64_t Nf, const d
     LPVS_TRY(get_tiles(pl.n, 0, s, &a.tiles, &a.ntiles));
     a.slab = slab; a.T = T; a.K = K; a.Nf = (int)Nf; a.nb = (int)nb; a.ldk = (int)ldk;
     const unsigned grid = (unsigned)(pl.tiles * pl.ksplit);
-    // deepest stage whose two LDS images fit (few basis functions -> many frequencies per tile)
-    if (gram_lds_bytes(0, 32, nb, ldk) <= kLdsBudget) { if (stage) *stage = 32; return launch_gram_t<0, 32>(a, grid, gram_lds_bytes(0, 32, nb, ldk), s); }
-    if (gram_lds_bytes(0, 16, nb, ldk) <= kLdsBudget) { if (stage) *stage = 16; return launch_gram_t<0, 16>(a, grid, gram_lds_bytes(0, 16, nb, ldk), s); }
-    if (gram_lds_bytes(0, 8, nb, ldk) <= kLdsBudget) { if (stage) *stage = 8; return launch_gram_t<0, 8>(a, grid, gram_lds_bytes(0, 8, nb, ldk), s); }
+    const int bk = gram_stage_for(kGramModeKr, nb, ldk);
+    const size_t lds = gram_lds_bytes(kGramModeKr, bk, nb, ldk);
+    if (stage && bk) *stage = bk;
+    switch (bk) {
+    case 32: return launch_gram_t<0, 32>(a, grid, lds, s);
+    case 16: return launch_gram_t<0, 16>(a, grid, lds, s);
+    case 8: return launch_gram_t<0, 8>(a, grid, lds, s);
+    }
     set_error("gram_kr: LDS image exceeds 160 KiB even at 8 samples per stage (nb=%lld)", (long long)nb);
     return LPVS_EUNSUPPORTED;
 }
@@ -605,15 +532,15 @@ int32_t launch_gram_krs(const GramPlan &pl, const double2 *T, int64_t Nf, const 
     a.slab = slab; a.T = T; a.K = KK; a.Nf = (int)Nf; a.nb = (int)nb; a.ldk = (int)pl.pairs; a.npair = (int)pl.pairs;
     a.nq = pl.np2 * pl.pairs;
     const unsigned grid = (unsigned)(pl.tiles * pl.ksplit);
-    if (gram_lds_bytes(2, 32, nb, pl.pairs) <= kLdsBudget) { if (stage) *stage = 32; return launch_gram_t<2, 32>(a, grid, gram_lds_bytes(2, 32, nb, pl.pairs), s); }
-    if (gram_lds_bytes(2, 16, nb, pl.pairs) <= kLdsBudget) { if (stage) *stage = 16; return launch_gram_t<2, 16>(a, grid, gram_lds_bytes(2, 16, nb, pl.pairs), s); }
+    const int bk = gram_stage_for(kGramModeKrs, nb, pl.pairs);
+    const size_t lds = gram_lds_bytes(kGramModeKrs, bk, nb, pl.pairs);
+    if (stage && bk) *stage = bk;
+    switch (bk) {
+    case 32: return launch_gram_t<2, 32>(a, grid, lds, s);
+    case 16: return launch_gram_t<2, 16>(a, grid, lds, s);
+    }
     set_error("gram_krs: LDS image exceeds 160 KiB (nb=%lld)", (long long)nb);
     return LPVS_EUNSUPPORTED;
-}
-
-bool gram_krs_fits(int64_t nb) {
-    const int64_t P = nb * (nb + 1) / 2;
-    return nb >= 2 && gram_lds_bytes(2, 16, nb, P) <= kLdsBudget;
 }
 
 int32_t launch_pair_table(const double *K, int64_t ldk, int64_t nb, int64_t Npad, double *KK, hipStream_t s) {
@@ -643,8 +570,8 @@ int32_t launch_gram_panel(const GramPlan &pl, const double *P, int64_t ld, const
     a.n = pl.n; a.rows_per_chunk = pl.rows_per_chunk; a.ksplit = (int)pl.ksplit;
     LPVS_TRY(get_tiles(pl.n, 0, s, &a.tiles, &a.ntiles));
     a.slab = slab; a.P = P; a.W = W; a.ld = ld;
-    if (stage) *stage = 16;
-    return launch_gram_t<1, 16>(a, (unsigned)(pl.tiles * pl.ksplit), gram_lds_bytes(1, 16, 0, 0), s);  // 2 x 48 KiB
+    if (stage) *stage = kGramPanelStage;
+    return launch_gram_t<1, kGramPanelStage>(a, (unsigned)(pl.tiles * pl.ksplit), gram_lds_bytes(kGramModePanel, kGramPanelStage, 0, 0), s);  // 2 x 48 KiB
 }
 
 // batch of nbatch independent panel problems of identical shape (windows of ls_windowpsd)
@@ -654,7 +581,7 @@ int32_t launch_gram_panel_batch(const GramPlan &pl, int nbatch, const double *P,
     a.n = pl.n; a.rows_per_chunk = pl.rows_per_chunk; a.ksplit = (int)pl.ksplit;
     LPVS_TRY(get_tiles(pl.n, 0, s, &a.tiles, &a.ntiles));
     a.slab = slab; a.P = P; a.W = W; a.ld = ld; a.nbatch = nbatch; a.batch_stride_P = batch_stride_P;
-    return launch_gram_t<1, 16>(a, (unsigned)(pl.tiles * pl.ksplit * nbatch), gram_lds_bytes(1, 16, 0, 0), s);
+    return launch_gram_t<1, kGramPanelStage>(a, (unsigned)(pl.tiles * pl.ksplit * nbatch), gram_lds_bytes(kGramModePanel, kGramPanelStage, 0, 0), s);
 }
 
 int32_t launch_gram_reduce_batch(const GramPlan &pl, int nbatch, const double *slab, double *G, int64_t ldg, hipStream_t s) {

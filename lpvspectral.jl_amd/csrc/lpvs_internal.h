@@ -11,6 +11,7 @@
 #include "../../include/lpvspectral.h"
 #include "windows_plan.h"
 #include "admm_plan.h"
+#include "gram_form_plan.h"
 
 namespace lpvs {
 
@@ -75,9 +76,6 @@ static inline void run_guarded(F &&f, OnFail &&on_fail) {
     catch (...) { set_error("worker thread of the library: unknown exception"); on_fail(LPVS_EDEVICE); }
 }
 
-static inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
-static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
 // ---- device buffers ---------------------------------------------------------------------
 // RAII device allocation; copy_in accepts a host or a device source pointer.
 struct DevBuf {
@@ -128,19 +126,7 @@ int32_t launch_transpose_to_panel(const double *A, int64_t m, int64_t n, double 
                                   hipStream_t s);
 
 // ---- Gram (gram.hip) --------------------------------------------------------------------
-struct GramPlan {
-    int64_t n = 0;       // unknowns (valid columns)
-    int64_t N = 0;       // samples
-    int64_t tiles = 0;   // lower-triangle 128x256 tiles
-    int64_t ksplit = 0;  // sample chunks
-    int64_t rows_per_chunk = 0;
-    size_t slab_bytes = 0;
-    int64_t pairs = 0;   // KRS: nb(nb+1)/2, else 0
-    int64_t np2 = 0;     // KRS: row space 2Nf
-};
-GramPlan make_gram_plan(int64_t n, int64_t N, int64_t nbatch = 1);   // nbatch: problems solved together
-GramPlan make_gram_plan_pairs(int64_t Nf, int64_t nb, int64_t N);
-bool gram_krs_fits(int64_t nb);   // does the symmetric-pair form fit LDS for this many basis functions?
+// (GramPlan, make_gram_plan, make_gram_plan_pairs, gram_krs_fits, gram_stage_for: gram_form_plan.h)
 // symmetric-pair form of the LPV Gram (see gram.hip): KK = pair products of the activation table
 int32_t launch_pair_table(const double *K, int64_t ldk, int64_t nb, int64_t Npad, double *KK, hipStream_t s);
 // (stage, where not NULL: the samples per stage of the gram_kernel instance that was launched)
@@ -172,7 +158,7 @@ int32_t launch_rhs_panel_batch(int nbatch, const double *P, int64_t strideP, int
                                size_t scratch_bytes, hipStream_t s);
 
 // ---- structured Gram for arithmetic-progression frequency grids (nudft.hip) ----------------------------------
-struct ApStep { double hi[8], lo[8]; };   // b*D in double-double, b = 0..7 (in-group offsets of the slot progressions)
+// (ApStep, ApSlots: gram_form_plan.h)
 size_t nudft_partial_bytes(int64_t N, int64_t nslots, int64_t nq);
 int64_t nudft_rows_per_chunk(int64_t N, int64_t nslots);
 int32_t launch_nudft(const double *x, const double *y, int64_t N, const double *Wt, int64_t ldw, int nq, const double *om_hi,
@@ -182,13 +168,11 @@ int32_t launch_nudft_windows(const double *x, const double *y, const double *Wt,
                              const ApStep &step, const int64_t *seg_dev, int nwin, int segs_per_window, double *partial, double *tab,
                              hipStream_t s);
 // the same slot sums by a type-1 non-uniform FFT when the slot frequencies are j * D (nufft.hip); work: nufft_work_bytes
-int nufft_grid_size(int64_t nslots);
-bool nufft_applicable(int64_t N, int64_t nslots, int64_t nq);
+// (nufft_grid_size, nufft_applicable, nufft_windows_applicable: gram_form_plan.h)
 size_t nufft_work_bytes(int64_t N, int64_t nslots, int64_t nq);
 int32_t launch_nufft_tab(const double *x, const double *y, int64_t N, double xam, const double *Wt, int64_t ldw, int nq, double D_hi, double D_lo,
                          int mode0, int nslots, int nf, bool reuse_coords, void *work, double *tab, hipStream_t s);
 constexpr int32_t kNufftNonFinite = -1000;       // launch_nufft_tab: a weight vector holds NaN / Inf -- take the direct sums (not an error)
-bool nufft_windows_applicable(int64_t n, int64_t nslots);
 std::vector<double> nufft_window_scale(int nf, int mode0, int nslots);
 int32_t launch_nufft_window_spread(const double *x, const double *W, const double *yA, const double *yB, bool hasB, const int64_t *offs_dev, int nwin,
                                    int64_t n, double D_hi, double D_lo, int nf, double *gridA, double *gridB, int64_t grid_bstride, hipStream_t s);

@@ -437,16 +437,7 @@ static std::vector<long double> nufft_phihat(int nf, int nmodes) {
     return it->second;
 }
 
-// fine grid for nslots modes: the smallest power of two >= 3.9 nslots (oversampling ~2 of the two-sided mode range)
-int nufft_grid_size(int64_t nslots) {
-    int nf = 256;
-    while ((double)nf < 3.9 * (double)nslots) nf *= 2;
-    return nf;
-}
-bool nufft_applicable(int64_t N, int64_t nslots, int64_t nq) {
-    const int nf = nufft_grid_size(nslots);
-    return nf <= 8192 && N >= 4096 && nq >= 1 && nq <= 256;   // (at least two grids of nf 64-bit cells have to fit the LDS)
-}
+// (the fine grid's size and the limits of this path: gram_form_plan.h)
 size_t nufft_work_bytes(int64_t N, int64_t nslots, int64_t nq) { return nu_work_layout(N, nufft_grid_size(nslots), nslots, nq).total; }
 
 // tab[nslots][nq][4] = sum_n y_n Wt[n][q] {cos, sin, x cos, x sin}((mode0 + j) D x_n),  D = D_hi + D_lo;  xam = max |x|; y may be
@@ -476,7 +467,7 @@ int32_t launch_nufft_tab(const double *x, const double *y, int64_t N, double xam
         if (!scatter)
             hipLaunchKernelGGL(nufft_bin_kernel, dim3((unsigned)ceil_div(N, kNuBinChunk)), dim3(256), sizeof(int) * (size_t)nf, s, cell0, N, nf, bin_start, perm);
     }
-    if (nq > 256) { set_error("nufft: more than 256 weight vectors"); return LPVS_EUNSUPPORTED; }
+    if (nq > kNufftMaxWeights) { set_error("nufft: more than 256 weight vectors"); return LPVS_EUNSUPPORTED; }
     hipLaunchKernelGGL(nufft_colmax_kernel, dim3(1024), dim3(256), 0, s, Wt, y, ldw, nq, N, colmax);
     LPVS_HIP(hipGetLastError());
     // quanta and the per-mode scale on the host (nq maxima come back: one small synchronising copy)
@@ -540,9 +531,6 @@ int32_t launch_nufft_tab(const double *x, const double *y, int64_t N, double xam
 
 
 // ---- batched windows
-bool nufft_windows_applicable(int64_t n, int64_t nslots) {
-    return n >= 2048 && nslots >= 64 && nufft_grid_size(nslots) <= 4096;   // (four grids of nf 64-bit cells in LDS)
-}
 // 1 / phihat(mode0 + j), j < nslots: the per-mode scale shared by every window (their quanta are folded into the grids)
 std::vector<double> nufft_window_scale(int nf, int mode0, int nslots) {
     const std::vector<long double> phat = nufft_phihat(nf, mode0 + nslots);
