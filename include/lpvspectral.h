@@ -180,6 +180,29 @@ int32_t lpvs_problem_create_lpv_multi_f64(const double *Y, int64_t ns, const dou
  *   ranges4 = {min V, max V, max|V|, max|X|}   (lpvs_lpv_ranges_f64 gives a shard's own; combine with min/max)
  * max|X| only steers the choice of Gram form, which must be the same on every shard. */
 int32_t lpvs_lpv_ranges_f64(const double *X, const double *V, int64_t N, double *out4);
+
+/* ---- model evaluation (extension: the reference has no predict): the fitted model at M samples without the regressor,
+ *   yhat_m[c] = s sum_f sum_j K_j(v_m) Re( p[f + j Nf, c] exp(i phi_fm) )
+ * Fourier: s = 1/sqrt(2 Nf), one K = 1, phi = (2 pi f_f) t_m, p = what lpvs_ls_spectral_f64 returns -- the result is the regressor of
+ * lpvs_fourier_regressor_f64 times the coefficients.  LPV: s = 1, phi = w_f x_m, p in the reference's order j Nf + f
+ * (lpvs_problem_get_params_f64), K the activations with centres built from ranges3 = {min V, max V, max|V|} of the TRAINING record
+ * (lpvs_lpv_ranges_f64), so that new samples meet the fitted basis -- the regressor of lpvs_lpv_regressor_f64 (permuted = 0) times
+ * [re p; im p].  nc coefficient columns (a regularisation path) are evaluated in one call, each to the bits of its own call.
+ * path: 0 auto, 1 direct sums (any grid), 2 type-2 non-uniform FFT (grids that are an arithmetic progression up to rounding, within
+ * the fine-grid limit: LPVS_EARGUMENT otherwise).  y may be NULL: out = yhat, else out = y - yhat; out is M x nc column-major.
+ * sums (host, 2 nc doubles, may be NULL): sum and sum of squares of every output column, in a fixed order (two calls, same bits).
+ * t / X / V / y / out: host or device memory; coefficients, f / w and ranges3: host memory.
+ * lpvs_eval_last_timing (the calling thread's last call): [0] path taken, [1] fine grid size (0: direct), [2] the first-order twin
+ * grids ran, ms of [3] staging and the reduction of max|x|, [4] the fine grids, [5] the interpolation or the direct sums, [6] the
+ * sums, [7] the copy-out, [8] total, [9] slabs of partial sums per column. */
+int32_t lpvs_fourier_eval_f64(const double *p_re, const double *p_im, int64_t nc, const double *f, int64_t Nf,
+                              const double *t, const double *y, int64_t M, int32_t path, int32_t device,
+                              double *out, double *sums);
+int32_t lpvs_lpv_eval_f64(const double *p_re, const double *p_im, int64_t nc, const double *w, int64_t Nf, int64_t Nv,
+                          int32_t normalize, int32_t coulomb, const double *ranges3,
+                          const double *X, const double *V, const double *y, int64_t M, int32_t path, int32_t device,
+                          double *out, double *sums);
+int32_t lpvs_eval_last_timing(double *out, int32_t n);
 int32_t lpvs_problem_create_lpv_rows_f64(const double *Y, int64_t ns, const double *X, const double *V,
                                          int64_t N_local, const double *w, int64_t Nf, int64_t Nv,
                                          int32_t normalize, int32_t coulomb, const double *ranges4,

@@ -20,7 +20,7 @@ export ls_spectral, tls_spectral, ls_sparse_spectral, ls_sparse_spectral_lpv, ls
        ls_cohere, ls_windowpsd_lpv, get_fourier_regressor, check_freq, default_freqs, Windows2, Windows3, mapwindows,
        SpectralExt, psd, reshape_params, ADMM, rect, hanning, autocov, autocor, isequidistant,
        melspectrogram, mfcc, mel, spectrogram, Spectrogram, MelSpectrogram, MFCC, freq, rand_cn, schedfunc,
-       Periodogram, welch_pgram, periodogram, compress, heatmap
+       Periodogram, welch_pgram, periodogram, compress, heatmap, predict, residual, fva
 
 const LIB = get(ENV, "LPVSPECTRAL_LIB", joinpath(@__DIR__, "..", "lpvspectral.jl_amd", "liblpvspectral.so"))
 
@@ -494,6 +494,63 @@ function ls_spectral_lpv(Y::AbstractVector, X::AbstractVector, V::AbstractVector
     fva = 1 - var_e / var(Yv)                             # :255
     fva < 0.9 && @warn("Fraction of variance explained = $(fva)")                    # :256
     SpectralExt(Y, X, V, w, Nv, λ, coulomb, normalize, prm, Σ)
+end
+
+# ---- model evaluation (extension: the reference has no predict): the regressor times the coefficients without the regressor ------
+# path = :auto | :direct (any frequency grid) | :nufft (a type-2 non-uniform FFT; grids that are an arithmetic progression up to rounding)
+const EVAL_PATHS = Dict(:auto => Int32(0), :direct => Int32(1), :nufft => Int32(2))
+_columns(x) = (P = reshape(ComplexF64.(x), size(x, 1), :); (Matrix{Float64}(real.(P)), Matrix{Float64}(imag.(P)), size(P, 2)))
+_shaped(x, out) = x isa AbstractVector ? vec(out) : out
+# -> (ŷ or y − ŷ as M × nc, [Σ Σ²] of every output column as nc × 2); the basis is the FITTED one: centres from the ranges of se.V
+function _eval_lpv(se::SpectralExt, X, V, y, path::Symbol, device)
+    wv, Xv, Vv, Vt = dense(Float64, se.w), dense(Float64, X), dense(Float64, V), dense(Float64, se.V)
+    Nf, M = length(wv), length(Xv)
+    @assert length(Vv) == M "X and V has to be the same length"
+    pre, pim, nc = _columns(se.x)
+    ranges = Float64[minimum(Vt), maximum(Vt), maximum(abs, Vt)]
+    out, sums = zeros(M, nc), zeros(2, nc)
+    if y === nothing
+        GC.@preserve pre pim wv ranges Xv Vv out sums check(@ccall LIB.lpvs_lpv_eval_f64(pre::Ptr{Float64}, pim::Ptr{Float64}, Int64(nc)::Int64, wv::Ptr{Float64}, Int64(Nf)::Int64, Int64(se.Nv)::Int64, Int32(se.normalize)::Int32, Int32(se.coulomb)::Int32, ranges::Ptr{Float64}, Xv::Ptr{Float64}, Vv::Ptr{Float64}, C_NULL::Ptr{Float64}, Int64(M)::Int64, EVAL_PATHS[path]::Int32, Int32(device)::Int32, out::Ptr{Float64}, sums::Ptr{Float64})::Int32)
+    else
+        yv = dense(Float64, y)
+        @assert length(yv) == M "y has to be as long as the sampling points"
+        GC.@preserve pre pim wv ranges Xv Vv yv out sums check(@ccall LIB.lpvs_lpv_eval_f64(pre::Ptr{Float64}, pim::Ptr{Float64}, Int64(nc)::Int64, wv::Ptr{Float64}, Int64(Nf)::Int64, Int64(se.Nv)::Int64, Int32(se.normalize)::Int32, Int32(se.coulomb)::Int32, ranges::Ptr{Float64}, Xv::Ptr{Float64}, Vv::Ptr{Float64}, yv::Ptr{Float64}, Int64(M)::Int64, EVAL_PATHS[path]::Int32, Int32(device)::Int32, out::Ptr{Float64}, sums::Ptr{Float64})::Int32)
+    end
+    out, permutedims(sums)
+end
+function _eval_fourier(x, f, t, y, path::Symbol, device)
+    fv, tv = dense(Float64, f), dense(Float64, t)
+    Nf, M = length(fv), length(tv)
+    pre, pim, nc = _columns(x)
+    @assert size(pre, 1) == Nf "one complex coefficient per frequency (what ls_spectral returns)"
+    out, sums = zeros(M, nc), zeros(2, nc)
+    if y === nothing
+        GC.@preserve pre pim fv tv out sums check(@ccall LIB.lpvs_fourier_eval_f64(pre::Ptr{Float64}, pim::Ptr{Float64}, Int64(nc)::Int64, fv::Ptr{Float64}, Int64(Nf)::Int64, tv::Ptr{Float64}, C_NULL::Ptr{Float64}, Int64(M)::Int64, EVAL_PATHS[path]::Int32, Int32(device)::Int32, out::Ptr{Float64}, sums::Ptr{Float64})::Int32)
+    else
+        yv = dense(Float64, y)
+        @assert length(yv) == M "y has to be as long as the sampling points"
+        GC.@preserve pre pim fv tv yv out sums check(@ccall LIB.lpvs_fourier_eval_f64(pre::Ptr{Float64}, pim::Ptr{Float64}, Int64(nc)::Int64, fv::Ptr{Float64}, Int64(Nf)::Int64, tv::Ptr{Float64}, yv::Ptr{Float64}, Int64(M)::Int64, EVAL_PATHS[path]::Int32, Int32(device)::Int32, out::Ptr{Float64}, sums::Ptr{Float64})::Int32)
+    end
+    out, permutedims(sums)
+end
+_fva(sums, M, y) = 1 .- ((sums[:, 2] .- sums[:, 1] .^ 2 ./ M) ./ (M - 1)) ./ var(dense(Float64, y))   # src/lsfft.jl:255, var(e) from the device's sums
+_scalar(x, v) = x isa AbstractVector ? v[1] : v
+
+"""    predict(se::SpectralExt, X=se.X, V=se.V; path=:auto)   and   predict(x, f, t; path=:auto)
+The fitted model at the samples: `lpv_regressor(X, V, …, permuted=false) * [real(x); imag(x)]` resp. `get_fourier_regressor(t, f)[1] * x`
+without the regressor; a matrix of coefficient columns (a regularisation path) gives one output column each."""
+predict(se::SpectralExt, X=se.X, V=se.V; path::Symbol=:auto, device=0) = _shaped(se.x, _eval_lpv(se, X, V, nothing, path, device)[1])
+predict(x::AbstractVecOrMat, f::AbstractVector, t::AbstractVector; path::Symbol=:auto, device=0) = _shaped(x, _eval_fourier(x, f, t, nothing, path, device)[1])
+"    residual(se) = se.Y − predict(se)   and   residual(x, f, t, y) = y − predict(x, f, t), formed on the device"
+residual(se::SpectralExt; path::Symbol=:auto, device=0) = _shaped(se.x, _eval_lpv(se, se.X, se.V, se.Y, path, device)[1])
+residual(x::AbstractVecOrMat, f::AbstractVector, t::AbstractVector, y::AbstractVector; path::Symbol=:auto, device=0) = _shaped(x, _eval_fourier(x, f, t, y, path, device)[1])
+"    fva(se)   and   fva(x, f, t, y): fraction of variance explained, 1 − var(e)/var(y) (src/lsfft.jl:255), one value per coefficient column"
+fva(se::SpectralExt; path::Symbol=:auto, device=0) = _scalar(se.x, _fva(_eval_lpv(se, se.X, se.V, se.Y, path, device)[2], length(se.Y), se.Y))
+fva(x::AbstractVecOrMat, f::AbstractVector, t::AbstractVector, y::AbstractVector; path::Symbol=:auto, device=0) = _scalar(x, _fva(_eval_fourier(x, f, t, y, path, device)[2], length(y), y))
+function eval_last_timing()
+    tm = zeros(10)
+    GC.@preserve tm check(@ccall LIB.lpvs_eval_last_timing(tm::Ptr{Float64}, Int32(10)::Int32)::Int32)
+    (path=Int(tm[1]), nf=Int(tm[2]), twin=tm[3] != 0, stage_ms=tm[4], grid_ms=tm[5], eval_ms=tm[6], sums_ms=tm[7], copy_ms=tm[8], total_ms=tm[9], slabs=Int(tm[10]))
 end
 
 # ---- windows: src/windows.jl (offsets from the C-ABI, views into the arrays) ---------------------

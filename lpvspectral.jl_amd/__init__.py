@@ -16,7 +16,7 @@ from .api import (MFCC, MelSpectrogram, Spectrogram, dct_matrix, fft_frequencies
                   cn_V2ΓC, cn_Vxx, cn_Vyy, cn_Vxy, cn_Vyx, cn_fVxx, cn_fVyy, cn_fVxy, cn_fVyx, cn_Vs, cn_fV, cn_V,  # noqa: E402
                   ADMM, Problem, autocor, autocov, autofun_last_timing, isequidistant, SpectralExt, basis_activation_func, check_freq, default_freqs,  # noqa: E402
                   fourier2complex, get_fourier_regressor, lpv_regressor, ls_sparse_spectral,
-                  ls_cohere, lambda_max, lambda_grid, ls_sparse_spectral_path, ls_sparse_spectral_lpv_path, ls_sparse_spectral_lpv, ls_sparse_spectral_lpv_multi, ls_sparse_spectral_lpv_rowsharded, lpv_ranges, lpv_batch_multi, lpv_signals_multi, ls_spectral, ls_spectral_lpv, tls_spectral, ls_windowcsd, ls_windowpsd, ls_windowpsd_lpv, psd,
+                  ls_cohere, lambda_max, lambda_grid, ls_sparse_spectral_path, ls_sparse_spectral_lpv_path, ls_sparse_spectral_lpv, ls_sparse_spectral_lpv_multi, ls_sparse_spectral_lpv_rowsharded, lpv_ranges, predict, residual, fva, eval_last_timing, lpv_batch_multi, lpv_signals_multi, ls_spectral, ls_spectral_lpv, tls_spectral, ls_windowcsd, ls_windowpsd, ls_windowpsd_lpv, psd,
                   reshape_params, set_default_option, get_default_option, default_options, windowpsd_sparse_batched, windowpsd_last_timing, windows_estimate, windows_estimate_multi, windowcsd_batched)
 from .prox import IndBallL0, LeastSquares, NormL0, NormL1, NormL2, Quadratic, SlicedSeparableSum  # noqa: E402
 from . import sharding  # noqa: E402
@@ -30,7 +30,7 @@ __all__ = [
     "nextfastfft", "Spectrogram", "MelSpectrogram", "MFCC", "freq", "time", "stft_last_timing",
     "Periodogram", "welch_pgram", "periodogram", "compress", "compress_thresholds", "heatmap", "compress_last_timing",
     "ADMM", "Problem", "SpectralExt", "basis_activation_func", "check_freq", "default_freqs", "fourier2complex",
-    "get_fourier_regressor", "lpv_regressor", "ls_sparse_spectral", "ls_sparse_spectral_lpv", "ls_sparse_spectral_lpv_multi", "ls_sparse_spectral_lpv_rowsharded", "lpv_ranges", "lpv_batch_multi", "lpv_signals_multi", "ls_spectral",
+    "get_fourier_regressor", "lpv_regressor", "ls_sparse_spectral", "ls_sparse_spectral_lpv", "ls_sparse_spectral_lpv_multi", "ls_sparse_spectral_lpv_rowsharded", "lpv_ranges", "predict", "residual", "fva", "eval_last_timing", "lpv_batch_multi", "lpv_signals_multi", "ls_spectral",
     "lambda_max", "lambda_grid", "ls_sparse_spectral_path", "ls_sparse_spectral_lpv_path", "ls_spectral_lpv", "tls_spectral", "ls_windowcsd", "ls_cohere", "ls_windowpsd", "ls_windowpsd_lpv", "psd", "reshape_params", "IndBallL0", "LeastSquares",
     "NormL0", "NormL1", "NormL2", "Quadratic", "SlicedSeparableSum", "Windows2", "Windows3", "hanning",
     "mapwindows", "merge", "rect", "set_default_option", "get_default_option", "default_options", "windowpsd_sparse_batched", "windowpsd_last_timing", "windows_estimate", "windows_estimate_multi", "windowcsd_batched", "DeviceError", "DomainError", "NumericError",

@@ -857,6 +857,131 @@ def lpv_ranges(X, V):
     return out
 
 
+# --------------------------------------------------------------------------- model evaluation (extension)
+_EVAL_PATHS = {"auto": 0, "direct": 1, "nufft": 2}
+
+
+def _f64_arg(a):
+    """float32 inputs are widened (device tensors on the device, everything else on the host)."""
+    if a is not None and _lib.is_device_array(a) and is_f32(a):
+        return a.double()
+    return a
+
+
+def _coef_columns(x, n):
+    """Coefficients as an (n, nc) complex column-major matrix and whether the caller gave a single vector."""
+    P = np.asarray(_host_c(x) if np.iscomplexobj(np.asarray(x)) else _host(x))
+    single = P.ndim == 1
+    P = P.reshape(P.shape[0], -1)
+    if P.shape[0] != n:
+        raise ValueError(f"{P.shape[0]} coefficients per column, the model has {n}")
+    return np.asfortranarray(P.astype(np.complex128)), single
+
+
+def _evaluate(se, a, b, y, path, device, out, want_sums):
+    """Shared by predict / residual / fva -> (output, sums or None, M).  ``se``: a :class:`SpectralExt` (``a``, ``b`` = X, V or None)
+    or Fourier coefficients (``a``, ``b`` = f, t)."""
+    if path not in _EVAL_PATHS:
+        raise ValueError(f"path: unknown value {path!r} (known: {sorted(_EVAL_PATHS)})")
+    lpv = isinstance(se, SpectralExt)
+    if lpv:
+        w = np.ascontiguousarray(_host_vec(se.w).astype(np.float64))
+        Nf, Nv = len(w), int(se.Nv)
+        nb = 2 * Nv if se.coulomb else Nv
+        P, single = _coef_columns(se.x, Nf * nb)
+        X = _f64_arg(se.X if a is None else a)
+        V = _f64_arg(se.V if b is None else b)
+        ranges = np.ascontiguousarray(lpv_ranges(_f64_arg(se.X), _f64_arg(se.V))[:3])   # of the TRAINING record: the fitted basis
+        kx, px, M = as_f64(X)
+        kv, pv, Mv = as_f64(V)
+        assert M == Mv, "X and V has to be the same length"
+    else:
+        if a is None or b is None:
+            raise TypeError("predict(x, f, t): the frequencies and the sampling points are needed")
+        f = np.ascontiguousarray(_host_vec(a).astype(np.float64))
+        Nf = len(f)
+        xa = np.asarray(se if not hasattr(se, "detach") else se.detach().cpu().numpy())
+        if not np.iscomplexobj(xa) and xa.shape[0] != Nf:                # the real vector [cos; sin] the regressor multiplies
+            zf = check_freq(f)
+            cols = xa.reshape(xa.shape[0], -1)
+            xa = np.stack([fourier2complex(cols[:, q], zf) for q in range(cols.shape[1])], axis=1).reshape((Nf,) + xa.shape[1:])
+        P, single = _coef_columns(xa, Nf)
+        kx, px, M = as_f64(_f64_arg(b))
+    nc = P.shape[1]
+    pre, pim = np.asfortranarray(P.real), np.asfortranarray(P.imag)
+    ky, py, My = as_f64(_f64_arg(y))
+    if y is not None:
+        assert My == M, "y has to be as long as the sampling points"
+    if out is None:
+        res = np.zeros(M if single else (M, nc), order="F")
+        po = out_ptr(res)
+    else:
+        ko, po, no = as_f64(out)
+        if no != M * nc:
+            raise ValueError(f"out has {no} elements, {M} x {nc} are written (column-major)")
+        res = out
+    sums = np.zeros(2 * nc) if want_sums else None
+    ps = out_ptr(sums) if want_sums else None
+    if lpv:
+        check(lib().lpvs_lpv_eval_f64(out_ptr(pre), out_ptr(pim), nc, out_ptr(w), Nf, Nv, int(bool(se.normalize)), int(bool(se.coulomb)), out_ptr(ranges),
+                                      px, pv, py, M, _EVAL_PATHS[path], int(device), po, ps))
+    else:
+        check(lib().lpvs_fourier_eval_f64(out_ptr(pre), out_ptr(pim), nc, out_ptr(f), Nf, px, py, M, _EVAL_PATHS[path], int(device), po, ps))
+    return res, (sums.reshape(nc, 2) if want_sums else None), M, single
+
+
+def predict(se, X=None, V=None, path="auto", device=0, out=None):
+    """The fitted model at samples (extension; the reference has no predict), without materialising the regressor.
+
+    ``predict(se, X=None, V=None)``: an LPV estimate (:class:`SpectralExt`) at its own samples or at new ``X``, ``V`` -- the basis is the
+    FITTED one (centres from the ranges of ``se.V``), not a basis of the new ``V``; equals ``lpv_regressor(X, V, w, Nv, normalize,
+    coulomb, permuted=False) @ [re x; im x]`` on the training record.  ``predict(x, f, t)``: a Fourier estimate (what ``ls_spectral``
+    returns, or the real coefficient vector) at sampling points ``t``; equals ``get_fourier_regressor(t, f)[0] @ x``.
+    Coefficients may be one vector or an (n, nc) matrix (a regularisation path): the result is (M,) or (M, nc), each column to the bits
+    of its own call.  ``path``: ``"auto"``, ``"direct"`` (any frequency grid) or ``"nufft"`` (a type-2 non-uniform FFT for grids that
+    are an arithmetic progression up to rounding; ValueError otherwise).  ``out``: a float64 array / device tensor of M·nc elements
+    that is filled column-major and returned instead of a new numpy array."""
+    return _evaluate(se, X, V, None, path, device, out, False)[0]
+
+
+def residual(se, f=None, t=None, y=None, path="auto", device=0, out=None, return_sums=False):
+    """``residual(se)`` = ``se.Y - predict(se)`` and ``residual(x, f, t, y)`` = ``y - predict(x, f, t)``, formed on the device (one
+    column per coefficient column).  ``return_sums``: also the device's ``[Σe, Σe²]`` per column, an (nc, 2) array -- added in a fixed
+    order, so two calls give the same bits."""
+    if isinstance(se, SpectralExt):
+        if f is not None or t is not None or y is not None:
+            raise TypeError("residual(se) is taken at the fitted samples")
+        y, f, t = se.Y, None, None
+    elif y is None:
+        raise TypeError("residual(x, f, t, y): the signal is needed")
+    e, sums, _, _ = _evaluate(se, f, t, y, path, device, out, bool(return_sums))
+    return (e, sums) if return_sums else e
+
+
+def fva(se, f=None, t=None, y=None, path="auto", device=0):
+    """Fraction of variance explained, ``1 - var(e) / var(y)`` with the corrected variances (src/lsfft.jl:255), for ``fva(se)`` or
+    ``fva(x, f, t, y)``; one value per coefficient column for a path.  ``var(e)`` comes from the device's sums of ``e`` and ``e²``."""
+    if isinstance(se, SpectralExt):
+        if f is not None or t is not None or y is not None:
+            raise TypeError("fva(se) is taken at the fitted samples")
+        y, f, t = se.Y, None, None
+    elif y is None:
+        raise TypeError("fva(x, f, t, y): the signal is needed")
+    _, sums, M, single = _evaluate(se, f, t, y, path, device, None, True)
+    var_e = (sums[:, 1] - sums[:, 0] * sums[:, 0] / M) / (M - 1)
+    r = 1.0 - var_e / float(np.var(_host(_f64_arg(y)), ddof=1))
+    return float(r[0]) if single else r
+
+
+def eval_last_timing():
+    """Timing of the calling thread's last predict / residual / fva: the path taken, the fine grid, whether the first-order twin grids
+    ran, milliseconds per phase and the slabs of partial sums."""
+    t = np.zeros(10)
+    check(lib().lpvs_eval_last_timing(out_ptr(t), 10))
+    return {"path": {1: "direct", 2: "nufft"}.get(int(t[0]), "none"), "nf": int(t[1]), "twin": bool(t[2]), "stage_ms": float(t[3]), "grid_ms": float(t[4]),
+            "eval_ms": float(t[5]), "sums_ms": float(t[6]), "copy_ms": float(t[7]), "total_ms": float(t[8]), "slabs": int(t[9])}
+
+
 def ls_sparse_spectral_lpv_rowsharded(y, X, V, w, Nv, λ=1, normalize=True, device=0, proxg=None, dist=None, **kwargs):
     """One signal whose SAMPLE ROWS are sharded over the ranks of ``dist`` (``torch.distributed``, initialised;
     backend nccl = RCCL over xGMI): every rank passes its rows ``(y, X, V)``.  SURVEY.md §8(e)(2): each rank forms the

@@ -1254,6 +1254,148 @@ int32_t lpvs_lpv_ranges_f64(const double *X, const double *V, int64_t N, double 
     return LPVS_OK;
 }
 
+// ---- model evaluation: predict / residual (eval.hip; the decisions: eval_plan.h) --------------------------------------------------------
+// what lpvs_eval_last_timing reports of the calling thread's last call: [0] path taken (1 direct, 2 type-2 NUFFT), [1] fine grid nf (0:
+// direct), [2] the first-order twin grids ran, ms of [3] staging the samples and reducing max|x| (the admission's input; the cell and the
+// kernel values of a sample are computed inside the interpolation), [4] the fine grids, [5] the interpolation or the direct sums,
+// [6] the sums, [7] the copy-out, [8] total, [9] slabs of partial sums per column
+static thread_local double g_eval_timing[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+struct EvalEvents {
+    hipEvent_t e[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    ~EvalEvents() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
+};
+// hw: the angular frequencies whose products with X are the phases (Fourier: fl(2 pi f)); nb basis functions with centres vc (empty: K = 1)
+static int32_t eval_impl(const double *p_re, const double *p_im, int64_t nc, const std::vector<double> &hw, int64_t nb, const std::vector<double> &vc,
+                         double gamma, int normalize, int coulomb, double scale, const double *X, const double *V, const double *y, int64_t M,
+                         int32_t path, int32_t device, double *out, double *sums) {
+    const int64_t Nf = (int64_t)hw.size();
+    if (lpvs_device_count() == 0) { set_error("no HIP device visible (the gfx950 path has no CPU fallback)"); return LPVS_EDEVICE; }
+    LPVS_HIP(hipSetDevice(device));
+    hipStream_t s = nullptr;
+    EvalEvents ev;
+    for (auto &e : ev.e) LPVS_HIP(hipEventCreate(&e));
+    DevArg dX, dV, dy; DevOut dout;
+    DevBuf dvc, dw, dP, dtw, dgrid, dpart, dsums;
+    DrainOnExit drain(s);
+    LPVS_HIP(hipEventRecord(ev.e[0], s));
+    LPVS_TRY(dX.set(X, M, s));
+    if (V) LPVS_TRY(dV.set(V, M, s));
+    if (y) LPVS_TRY(dy.set(y, M, s));
+    LPVS_TRY(dout.set(out, M * nc));
+    EvalGrid eg;
+    if (path != kEvalPathDirect) {                   // the direct path does not look at the grid
+        double xlo, xhi, xam;
+        LPVS_TRY(device_minmax(dX.p, M, &xlo, &xhi, &xam, s));
+        eg = eval_admit(hw, xam);
+    }
+    const int taken = eval_choose_path(path, eg.ok, M);
+    if (taken == kEvalPathRefused) {
+        if (path != kEvalPathNufft) set_error("path must be 0 (auto), 1 (direct) or 2 (NUFFT), got %d", path);
+        else if (!eg.progression) set_error("path = NUFFT but the frequency grid is not an arithmetic progression up to rounding (max|eps| = %.3g)", eg.emax);
+        else set_error("path = NUFFT but %lld frequencies need a fine grid beyond %d points", (long long)Nf, kNufftMaxGrid);
+        return LPVS_EARGUMENT;
+    }
+    EvalBasis B;
+    B.nb = (int)nb; B.gamma = gamma; B.normalize = normalize; B.coulomb = coulomb;
+    if (!vc.empty()) {
+        LPVS_TRY(dvc.alloc(sizeof(double) * vc.size()));
+        LPVS_TRY(copy_to_device(dvc.p, vc.data(), sizeof(double) * vc.size(), s));
+        B.vc = dvc.as<double>();
+    }
+    const int64_t nslab = eval_sum_slabs(M), ncoef = nc * nb * Nf;
+    double *part = nullptr;
+    if (sums) {
+        LPVS_TRY(dpart.alloc(sizeof(double) * (size_t)(2 * nc * nslab)));
+        LPVS_TRY(dsums.alloc(sizeof(double) * (size_t)(2 * nc)));
+        part = dpart.as<double>();
+    }
+    LPVS_HIP(hipEventRecord(ev.e[1], s));
+    LPVS_HIP(hipEventRecord(ev.e[2], s));
+    if (taken == kEvalPathDirect) {
+        std::vector<double> hP((size_t)(2 * ncoef));
+        for (int64_t i = 0; i < ncoef; ++i) { hP[(size_t)(2 * i)] = p_re[i]; hP[(size_t)(2 * i + 1)] = p_im[i]; }
+        LPVS_TRY(dP.alloc(sizeof(double) * hP.size()));
+        LPVS_TRY(copy_to_device(dP.p, hP.data(), sizeof(double) * hP.size(), s));
+        LPVS_TRY(dw.alloc(sizeof(double) * (size_t)Nf));
+        LPVS_TRY(copy_to_device(dw.p, hw.data(), sizeof(double) * (size_t)Nf, s));
+        LPVS_TRY(launch_eval_direct(dX.p, dV.p, dy.p, M, dw.as<double>(), Nf, dP.as<double>(), nc, B, scale, dout.p, part, s));
+    } else {
+        // step 1 on the host: q_f = p_f / phihat(f), and the twins' i eps_f p_f / phihat(f)
+        const std::vector<double> iphat = nufft_window_scale(eg.nf, 0, (int)Nf);
+        const int64_t ntw = eg.twin ? 2 : 1, ngrids = nc * nb * ntw;
+        std::vector<double> hQ((size_t)(2 * ngrids * Nf));
+        for (int64_t g = 0; g < nc * nb; ++g)
+            for (int64_t f = 0; f < Nf; ++f) {
+                const double qr = p_re[g * Nf + f] * iphat[(size_t)f], qi = p_im[g * Nf + f] * iphat[(size_t)f];
+                double *q = &hQ[(size_t)(2 * ((g * ntw) * Nf + f))];
+                q[0] = qr; q[1] = qi;
+                if (eg.twin) { q[2 * Nf] = -eg.eps[(size_t)f] * qi; q[2 * Nf + 1] = eg.eps[(size_t)f] * qr; }
+            }
+        LPVS_TRY(dP.alloc(sizeof(double) * hQ.size()));
+        LPVS_TRY(copy_to_device(dP.p, hQ.data(), sizeof(double) * hQ.size(), s));
+        LPVS_TRY(dtw.alloc(sizeof(double) * 2 * (size_t)eg.nf));
+        LPVS_TRY(dgrid.alloc(sizeof(double) * 2 * (size_t)(ngrids * eg.nf)));
+        LPVS_TRY(launch_eval_grids(dP.as<double>(), ngrids, Nf, eg.nf, dtw.as<double>(), dgrid.as<double>(), s));
+        LPVS_HIP(hipEventRecord(ev.e[2], s));
+        LPVS_TRY(launch_eval_interp(dX.p, dV.p, dy.p, M, eg.a, eg.D_hi, eg.D_lo, eg.nf, dgrid.as<double>(), eg.twin, nc, B, scale, dout.p, part, s));
+    }
+    LPVS_HIP(hipEventRecord(ev.e[3], s));
+    if (sums) LPVS_TRY(launch_eval_sums(part, M, nc, dsums.as<double>(), s));
+    LPVS_HIP(hipEventRecord(ev.e[4], s));
+    if (sums) LPVS_TRY(copy_from_device(sums, dsums.p, sizeof(double) * (size_t)(2 * nc), s));
+    LPVS_TRY(dout.finish(s));
+    LPVS_HIP(hipEventRecord(ev.e[5], s));
+    LPVS_HIP(hipStreamSynchronize(s));
+    float ms[5] = {0, 0, 0, 0, 0};
+    for (int i = 0; i < 5; ++i) LPVS_HIP(hipEventElapsedTime(&ms[i], ev.e[i], ev.e[i + 1]));
+    float total = 0;
+    LPVS_HIP(hipEventElapsedTime(&total, ev.e[0], ev.e[5]));
+    const bool nu = taken == kEvalPathNufft;
+    g_eval_timing[0] = taken; g_eval_timing[1] = nu ? eg.nf : 0; g_eval_timing[2] = nu && eg.twin ? 1 : 0;
+    g_eval_timing[3] = ms[0]; g_eval_timing[4] = ms[1]; g_eval_timing[5] = ms[2]; g_eval_timing[6] = ms[3]; g_eval_timing[7] = ms[4];
+    g_eval_timing[8] = total; g_eval_timing[9] = (double)nslab;
+    return LPVS_OK;
+}
+static int32_t eval_check(const double *p_re, const double *p_im, int64_t nc, const double *w, int64_t Nf, const double *X, int64_t M, int32_t path,
+                          const double *out) {
+    if (!p_re || !p_im || !w || !X || !out) { set_error("NULL argument"); return LPVS_EARGUMENT; }
+    if (M <= 0 || Nf <= 0 || nc <= 0 || nc > 65535) { set_error("need M > 0, Nf > 0 and 1 <= nc <= 65535 (M = %lld, Nf = %lld, nc = %lld)", (long long)M, (long long)Nf, (long long)nc); return LPVS_EARGUMENT; }
+    if (Nf > ((int64_t)1 << 24)) { set_error("%lld frequencies are too many", (long long)Nf); return LPVS_EUNSUPPORTED; }
+    if (path < kEvalPathAuto || path > kEvalPathNufft) { set_error("path must be 0 (auto), 1 (direct) or 2 (NUFFT), got %d", path); return LPVS_EARGUMENT; }
+    return LPVS_OK;
+}
+
+int32_t lpvs_fourier_eval_f64(const double *p_re, const double *p_im, int64_t nc, const double *f, int64_t Nf, const double *t, const double *y, int64_t M,
+                              int32_t path, int32_t device, double *out, double *sums) {
+    try {
+        LPVS_TRY(eval_check(p_re, p_im, nc, f, Nf, t, M, path, out));
+        std::vector<double> hw(f, f + Nf);
+        for (auto &v : hw) v = 6.283185307179586 * v;                      // T(2pi) f, rounded as the regressor kernel rounds it (src/lsfft.jl:33)
+        return eval_impl(p_re, p_im, nc, hw, 1, std::vector<double>(), 0.0, 0, 0, 1.0 / std::sqrt((double)(2 * Nf)), t, nullptr, y, M, path, device, out, sums);
+    } catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
+}
+
+int32_t lpvs_lpv_eval_f64(const double *p_re, const double *p_im, int64_t nc, const double *w, int64_t Nf, int64_t Nv, int32_t normalize, int32_t coulomb,
+                          const double *ranges3, const double *X, const double *V, const double *y, int64_t M, int32_t path, int32_t device, double *out,
+                          double *sums) {
+    try {
+        LPVS_TRY(eval_check(p_re, p_im, nc, w, Nf, X, M, path, out));
+        if (!V || !ranges3) { set_error("NULL argument"); return LPVS_EARGUMENT; }
+        if (Nv <= 0 || Nv > 4096) { set_error("need 1 <= Nv <= 4096 (Nv = %lld)", (long long)Nv); return LPVS_EARGUMENT; }
+        if (!(ranges3[0] <= ranges3[1]) || !(ranges3[2] >= 0)) { set_error("ranges3 = {min V, max V, max|V|} of the training record is inconsistent"); return LPVS_EARGUMENT; }
+        std::vector<double> vc; double gamma = 0;
+        basis_centers(ranges3[0], ranges3[1], ranges3[2], Nv, coulomb, vc, &gamma);
+        return eval_impl(p_re, p_im, nc, std::vector<double>(w, w + Nf), coulomb ? 2 * Nv : Nv, vc, gamma, normalize ? 1 : 0, coulomb ? 1 : 0, 1.0, X, V, y, M, path,
+                         device, out, sums);
+    } catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
+}
+
+int32_t lpvs_eval_last_timing(double *out, int32_t n) {
+    if (!out || n < 0) { set_error("NULL argument"); return LPVS_EARGUMENT; }
+    for (int32_t k = 0; k < n && k < 10; ++k) out[k] = g_eval_timing[k];
+    return LPVS_OK;
+}
+
 int32_t lpvs_problem_create_lpv_rows_f64(const double *Y, int64_t ns, const double *X, const double *V, int64_t N_local, const double *w,
                                          int64_t Nf, int64_t Nv, int32_t normalize, int32_t coulomb, const double *ranges4,
                                          int32_t device, lpvs_problem **out) {

@@ -6,6 +6,7 @@
 // These kernels are HBM-write bound (one sincos / exp per 16 / 8 output bytes); all stores are
 // coalesced along the fastest-varying output index.
 #include "lpvs_internal.h"
+#include "basis_device.h"
 
 #include <cstdlib>
 #include <string>
@@ -125,8 +126,6 @@ trig_table_kernel(const double *__restrict__ X, int64_t N, const double *__restr
 }
 
 // ---- a3: activation table K[n][ldk] -------------------------------------------------------
-__device__ inline double sgn(double x) { return (double)((x > 0) - (x < 0)); }
-
 __global__ void __launch_bounds__(256)
 basis_table_kernel(const double *__restrict__ V, int64_t N, const double *__restrict__ vc, int64_t nb,
                    double gamma, int normalize, int coulomb, double *__restrict__ K, int64_t ldk) {
@@ -136,9 +135,7 @@ basis_table_kernel(const double *__restrict__ V, int64_t N, const double *__rest
     double *row = K + n * ldk;
     double sum = 0;
     for (int64_t j = 0; j < nb; ++j) {
-        const double d = v - vc[j];
-        double k = exp(-gamma * (d * d));
-        if (coulomb) k = k * (sgn(v) == sgn(vc[j]) ? 1.0 : 0.0);  // src/lsfft.jl:202
+        const double k = basis_activation(v, vc[j], gamma, coulomb);   // basis_device.h
         row[j] = k;
         sum = j == 0 ? k : sum + k;  // sequential, as Base.sum on a short vector
     }

@@ -12,6 +12,7 @@
 #include "windows_plan.h"
 #include "admm_plan.h"
 #include "gram_form_plan.h"
+#include "eval_plan.h"
 
 namespace lpvs {
 
@@ -186,6 +187,23 @@ int32_t launch_ap_rhs_fourier(const double *tab, const double *eps, int64_t Nf, 
 int32_t launch_ap_assemble(const double *tab, const double *eps, int64_t Nf, int64_t s0, double delta, int64_t nb, int64_t n, double *G,
                            int64_t ldg, hipStream_t s);
 int32_t launch_ap_rhs(const double *tab, const double *eps, int64_t Nf, int64_t nb, double *b, hipStream_t s);
+
+// ---- model evaluation (eval.hip; the decisions: eval_plan.h) ---------------------------------------------------------------------------
+// the basis of a call: vc = nb centres in device memory (nullptr: the Fourier family's single K = 1, nb = 1)
+struct EvalBasis {
+    const double *vc = nullptr;
+    int nb = 1;
+    double gamma = 0;
+    int normalize = 0, coulomb = 0;
+};
+// out[c M + m] = s yhat_m[c] (y == nullptr) or y_m - s yhat_m[c]; part (or nullptr): 2 nc rows of eval_sum_slabs(M) partial sums.
+// P_dev[(c nb + j) Nf + f] = (re, im) of p[f + j Nf, c]; w_dev: the angular frequencies whose ROUNDED products with x are the phases
+int32_t launch_eval_direct(const double *x, const double *v, const double *y, int64_t M, const double *w_dev, int64_t Nf, const double *P_dev, int64_t nc,
+                           const EvalBasis &B, double scale, double *out, double *part, hipStream_t s);
+int32_t launch_eval_grids(const double *Q_dev, int64_t ngrids, int64_t Nf, int nf, double *tw_dev, double *grids_dev, hipStream_t s);
+int32_t launch_eval_interp(const double *x, const double *v, const double *y, int64_t M, double a, double D_hi, double D_lo, int nf, const double *grids_dev,
+                           bool twin, int64_t nc, const EvalBasis &B, double scale, double *out, double *part, hipStream_t s);
+int32_t launch_eval_sums(const double *part, int64_t M, int64_t nc, double *sums_dev, hipStream_t s);
 
 // ---- dense symmetric inverse (linalg.hip) ------------------------------------------------
 // In-place inverse of the SPD matrix A (np x np, np % 64 == 0, full symmetric storage) by

@@ -27,6 +27,7 @@
 // in double-double -- so it is the phase of the REAL progression step.
 #include "lpvs_internal.h"
 #include "nufft_bins.h"
+#include "nufft_coord.h"
 
 #include <cmath>
 #include <cstring>
@@ -38,7 +39,6 @@ namespace lpvs {
 namespace {
 
 constexpr int NU_W = kNuWidth;                       // kernel width (grid points)
-constexpr double NU_BETA = 2.30 * NU_W;
 // grids per scatter workgroup: GPW x nf x 8 B of LDS -- 4 for nf <= 4096, 2 for nf = 8192 (the cfg5 slot count)
 static int nu_gpw(int nf) { return nu_scatter_gpw(nf); }
 constexpr double NU_MAGIC = 6755399441055744.0;      // 1.5 * 2^52
@@ -49,22 +49,11 @@ __global__ void __launch_bounds__(256)
 nufft_coord_kernel(const double *__restrict__ x, int64_t N, double D_hi, double D_lo, int nf, int *__restrict__ cell0, double *__restrict__ taps) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
-    constexpr double I2PI_HI = 0.15915494309189535, I2PI_LO = -9.8393384885635288e-18;   // 1 / (2 pi) in double-double
-    const double xv = x[i];
-    const double th = D_hi * xv, tl = fma(D_hi, xv, -th) + D_lo * xv;                     // D x (double-double)
-    const double uh = th * I2PI_HI, ul = fma(th, I2PI_HI, -uh) + (th * I2PI_LO + tl * I2PI_HI);   // turns
-    double r = (uh - rint(uh)) + ul;
-    r -= floor(r);                                   // [0, 1)
-    double p = r * (double)nf;
-    if (p >= (double)nf) p -= (double)nf;
-    const int g0 = (int)ceil(p - 0.5 * NU_W);        // grid points g0 .. g0 + 15 lie within |g - p| <= 8
+    int g0;                                          // (nufft_coord.h: the phase in double-double, the position, the kernel values)
+    const double p = nu_grid_pos(nu_phase_turns(D_hi, D_lo, x[i]), nf, &g0);
     cell0[i] = (g0 + nf) & (nf - 1);
 #pragma unroll
-    for (int k = 0; k < NU_W; ++k) {
-        const double z = ((double)(g0 + k) - p) * (2.0 / NU_W);
-        const double s = 1.0 - z * z;
-        taps[i * NU_W + k] = s > 0.0 ? exp(NU_BETA * (sqrt(s) - 1.0)) : exp(-NU_BETA);
-    }
+    for (int k = 0; k < NU_W; ++k) taps[i * NU_W + k] = nu_tap(g0, k, p);
 }
 
 // max |Wt[n][q]| per column, one coalesced pass (order-independent: integer max on the bit patterns of non-negative doubles)
@@ -358,24 +347,16 @@ nufft_window_kernel(const double *__restrict__ x, const double *__restrict__ W, 
         quantum[g] = finite ? ldexp(1.0, e - 62) : __longlong_as_double(0x7ff8000000000000ll);   // power of two: the scalings are exact
         iq[g] = bound > 0.0 && finite ? 1.0 / ldexp(1.0, e - 62) : 0.0;
     }
-    constexpr double I2PI_HI = 0.15915494309189535, I2PI_LO = -9.8393384885635288e-18;   // 1 / (2 pi) in double-double
     const long long magic_bits = __double_as_longlong(NU_MAGIC);
     for (int64_t i = threadIdx.x; i < n; i += 256) {
         const double xv = x[r0 + i], wv = W ? W[i] : 1.0;
         const double cA = yA ? wv * yA[r0 + i] : wv, cB = hasB ? wv * yB[r0 + i] : 0.0;
         const double cw[4] = {cA * iq[0], (xv * cA) * iq[1], cB * iq[2], (xv * cB) * iq[3]};
-        const double th = D_hi * xv, tl = fma(D_hi, xv, -th) + D_lo * xv;                     // D x (double-double), as nufft_coord_kernel
-        const double uh = th * I2PI_HI, ul = fma(th, I2PI_HI, -uh) + (th * I2PI_LO + tl * I2PI_HI);
-        double r = (uh - rint(uh)) + ul;
-        r -= floor(r);
-        double p = r * (double)nf;
-        if (p >= (double)nf) p -= (double)nf;
-        const int g0 = (int)ceil(p - 0.5 * NU_W);
+        int g0;                                      // as nufft_coord_kernel
+        const double p = nu_grid_pos(nu_phase_turns(D_hi, D_lo, xv), nf, &g0);
 #pragma unroll 4
         for (int k = 0; k < NU_W; ++k) {
-            const double z = ((double)(g0 + k) - p) * (2.0 / NU_W);
-            const double sq = 1.0 - z * z;
-            const double tv = sq > 0.0 ? exp(NU_BETA * (sqrt(sq) - 1.0)) : exp(-NU_BETA);
+            const double tv = nu_tap(g0, k, p);
             const int cell = (g0 + k + nf) & (nf - 1);
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
@@ -428,7 +409,7 @@ static std::vector<long double> nufft_phihat(int nf, int nmodes) {
             long double acc = 0;
             for (const auto &nw : gl) {
                 const long double z = nw.first, t = z * half;
-                acc += nw.second * half * expl((long double)NU_BETA * (sqrtl(1 - z * z) - 1)) * cosl(2 * pi * (long double)j * t / (long double)nf);
+                acc += nw.second * half * expl((long double)kNuBeta * (sqrtl(1 - z * z) - 1)) * cosl(2 * pi * (long double)j * t / (long double)nf);
             }
             v[(size_t)j] = acc;
         }
