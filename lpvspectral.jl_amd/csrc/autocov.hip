@@ -342,33 +342,6 @@ __global__ void __launch_bounds__(kBlock) radix_scatter_kernel(const K *kin, con
 // ---- thread-local phase times of the last call -----------------------------------------------------------------------------------------
 thread_local double g_timing[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
-struct StreamHolder {
-    hipStream_t s = nullptr;
-    ~StreamHolder() { if (s) (void)hipStreamDestroy(s); }
-};
-struct Events {
-    hipEvent_t e[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
-};
-
-// a read-only argument made resident on the current device (aliased when it already is)
-template <class T> struct Staged {
-    DevBuf own;
-    const T *p = nullptr;
-    int32_t set(const T *src, int64_t count, int dev, hipStream_t s) {
-        const int owner = device_of_ptr(src);
-        if (owner == dev) { p = src; return LPVS_OK; }
-        LPVS_TRY(own.alloc(sizeof(T) * (size_t)count));
-        if (owner >= 0) {
-            LPVS_HIP(hipMemcpyPeerAsync(own.p, dev, src, owner, sizeof(T) * (size_t)count, s));
-            LPVS_HIP(hipStreamSynchronize(s));
-        } else
-            LPVS_TRY(copy_to_device(own.p, src, sizeof(T) * (size_t)count, s));
-        p = own.as<T>();
-        return LPVS_OK;
-    }
-};
-
 template <class T> int32_t isequidistant_host(const T *t, int64_t N) {
     const T d = t[1] - t[0];
     if (!(d > (T)0)) return 0;
@@ -424,7 +397,7 @@ int32_t autofun_impl(int32_t kind, const T *t, const T *y, const int64_t *seg_of
     StreamHolder sh;
     LPVS_HIP(hipStreamCreateWithFlags(&sh.s, hipStreamNonBlocking));
     const hipStream_t s = sh.s;
-    Events ev;
+    Events<6> ev;
     for (auto &x : ev.e) LPVS_HIP(hipEventCreate(&x));
     Staged<T> dt, dy;
     DevBuf doff, dst, dc, dcnt, dbits, hist, k0, v0, k1, v1;

@@ -40,33 +40,6 @@ int32_t need_device() {
     return LPVS_OK;
 }
 
-struct StreamHolder {
-    hipStream_t s = nullptr;
-    ~StreamHolder() { if (s) (void)hipStreamDestroy(s); }
-};
-struct Events {
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
-};
-
-// a read-only argument made resident on the current device (aliased when it already is)
-struct Staged {
-    DevBuf own;
-    const double *p = nullptr;
-    int32_t set(const double *src, size_t count, int dev, hipStream_t s) {
-        const int owner = device_of_ptr(src);
-        if (owner == dev) { p = src; return LPVS_OK; }
-        LPVS_TRY(own.alloc(sizeof(double) * count));
-        if (owner >= 0) {
-            LPVS_HIP(hipMemcpyPeerAsync(own.p, dev, src, owner, sizeof(double) * count, s));
-            LPVS_HIP(hipStreamSynchronize(s));
-        } else
-            LPVS_TRY(copy_to_device(own.p, src, sizeof(double) * count, s));
-        p = own.as<double>();
-        return LPVS_OK;
-    }
-};
-
 // ---- 1. Cholesky ----------------------------------------------------------------------------------------------------------------------
 // W (np x np, column-major, np % 128 == 0): upper triangle of V, identity on the padding, zero elsewhere
 __global__ void __launch_bounds__(256) pad_upper_kernel(const double *V, int64_t n2, double *W, int64_t np) {
@@ -415,8 +388,8 @@ thread_local double g_timing[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
 // Z (device, s x n2, ld s) = m' .+ R U
 int32_t sample_device(const Cn &cn, int64_t s, uint64_t seed, const double *R, double *Z, hipStream_t st) {
-    Staged dR;
-    if (R) LPVS_TRY(dR.set(R, (size_t)s * (size_t)cn.n2, cn.device, st));
+    Staged<double> dR;
+    if (R) LPVS_TRY(dR.set(R, s * cn.n2, cn.device, st));
     DrainOnExit drain(st);
     const dim3 grid((unsigned)ceil_div(s, kSR), (unsigned)ceil_div(cn.n2, kSC));
     cn_sample_kernel<<<grid, 256, 0, st>>>(cn.U.as<double>(), cn.np, cn.n2, cn.m.as<double>(), R ? dR.p : nullptr, s, seed, s, Z, s);
@@ -440,10 +413,10 @@ int32_t cholesky_impl(const double *V, int64_t n2, int32_t device, double *U_out
     LPVS_HIP(hipSetDevice(device));
     StreamHolder sh;
     LPVS_HIP(hipStreamCreateWithFlags(&sh.s, hipStreamNonBlocking));
-    Staged dV;
+    Staged<double> dV;
     DevBuf W, Uc;
     DrainOnExit drain(sh.s);
-    LPVS_TRY(dV.set(V, (size_t)n2 * (size_t)n2, device, sh.s));
+    LPVS_TRY(dV.set(V, n2 * n2, device, sh.s));
     int64_t np = 0;
     LPVS_TRY(factor_device(dV.p, n2, W, &np, sh.s));
     LPVS_TRY(Uc.alloc(sizeof(double) * (size_t)n2 * (size_t)n2));
@@ -479,10 +452,10 @@ int32_t cov_impl(const double *A, int64_t rows, int64_t cols, int32_t device, do
     LPVS_HIP(hipSetDevice(device));
     StreamHolder sh;
     LPVS_HIP(hipStreamCreateWithFlags(&sh.s, hipStreamNonBlocking));
-    Staged dA;
+    Staged<double> dA;
     DevBuf part, dmean;
     DrainOnExit drain(sh.s);
-    LPVS_TRY(dA.set(A, (size_t)rows * (size_t)cols, device, sh.s));
+    LPVS_TRY(dA.set(A, rows * cols, device, sh.s));
     const int64_t pairs = cols * (cols + 1) / 2;
     LPVS_TRY(part.alloc(sizeof(double) * (size_t)pairs * kCovBlocks));
     LPVS_TRY(dmean.alloc(sizeof(double) * (size_t)cols));
@@ -516,13 +489,13 @@ int32_t cn_create_impl(const double *m_re, const double *m_im, const double *V, 
     LPVS_HIP(hipSetDevice(device));
     StreamHolder sh;
     LPVS_HIP(hipStreamCreateWithFlags(&sh.s, hipStreamNonBlocking));
-    Events ev;
+    Events<4> ev;
     for (auto &x : ev.e) LPVS_HIP(hipEventCreate(&x));
     std::unique_ptr<Cn> cn(new Cn);
     cn->device = device; cn->n = n; cn->n2 = 2 * n;
-    Staged dV;
+    Staged<double> dV;
     DrainOnExit drain(sh.s);
-    LPVS_TRY(dV.set(V, (size_t)cn->n2 * (size_t)cn->n2, device, sh.s));
+    LPVS_TRY(dV.set(V, cn->n2 * cn->n2, device, sh.s));
     LPVS_HIP(hipEventRecord(ev.e[0], sh.s));
     LPVS_TRY(factor_device(dV.p, cn->n2, cn->U, &cn->np, sh.s));
     zero_lower_kernel<<<(unsigned)ceil_div(cn->np * cn->np, 256), 256, 0, sh.s>>>(cn->U.as<double>(), cn->np);
@@ -550,7 +523,7 @@ int32_t cn_rand_impl(int64_t id, int64_t s, int64_t seed, const double *R, doubl
     LPVS_HIP(hipSetDevice(cn->device));
     StreamHolder sh;
     LPVS_HIP(hipStreamCreateWithFlags(&sh.s, hipStreamNonBlocking));
-    Events ev;
+    Events<4> ev;
     for (auto &x : ev.e) LPVS_HIP(hipEventCreate(&x));
     DevBuf Z;
     DrainOnExit drain(sh.s);
@@ -580,14 +553,14 @@ int32_t cn_bands_impl(int64_t id, int64_t Nf, int64_t nb, const double *Phi_g, i
     LPVS_HIP(hipSetDevice(cn->device));
     StreamHolder sh;
     LPVS_HIP(hipStreamCreateWithFlags(&sh.s, hipStreamNonBlocking));
-    Events ev;
+    Events<4> ev;
     for (auto &x : ev.e) LPVS_HIP(hipEventCreate(&x));
     DevBuf Z, out;
-    Staged dPhi;
+    Staged<double> dPhi;
     DrainOnExit drain(sh.s);
     LPVS_TRY(Z.alloc(sizeof(double) * (size_t)nMC * (size_t)cn->n2));
     LPVS_TRY(out.alloc(sizeof(double) * 6 * (size_t)Nf * (size_t)G));
-    LPVS_TRY(dPhi.set(Phi_g, (size_t)G * (size_t)nb, cn->device, sh.s));
+    LPVS_TRY(dPhi.set(Phi_g, G * nb, cn->device, sh.s));
     LPVS_HIP(hipEventRecord(ev.e[0], sh.s));
     LPVS_TRY(sample_device(*cn, nMC, (uint64_t)seed, R, Z.as<double>(), sh.s));
     LPVS_HIP(hipEventRecord(ev.e[1], sh.s));

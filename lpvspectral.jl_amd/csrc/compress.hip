@@ -151,15 +151,6 @@ template <class T> __global__ void log_values_kernel(double *v, int n) {
     if ((int)threadIdx.x < n) v[threadIdx.x] = value_of((T)v[threadIdx.x], 1);
 }
 
-struct StreamHolder {
-    hipStream_t s = nullptr;
-    ~StreamHolder() { if (s) (void)hipStreamDestroy(s); }
-};
-struct Events {
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
-};
-
 // Julia's quantile (alpha = beta = 1) of m sorted values: the 0-based ranks of its two neighbours and the weight
 struct Quant { int64_t j0 = 0, j1 = 0; double g = 0; };
 Quant quantile_ranks(int64_t m, double p) {
@@ -189,7 +180,7 @@ int32_t compress_impl(const T *x, int64_t rows, int64_t cols, int64_t ld, int32_
     StreamHolder sh;
     LPVS_HIP(hipStreamCreateWithFlags(&sh.s, hipStreamNonBlocking));
     const hipStream_t s = sh.s;
-    Events ev;
+    Events<4> ev;
     for (auto &e : ev.e) LPVS_HIP(hipEventCreate(&e));
     DevBuf dx, dout, dstate;
     DrainOnExit drain(s);

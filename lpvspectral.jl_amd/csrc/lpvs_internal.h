@@ -67,6 +67,15 @@ struct DrainOnExit {
     explicit DrainOnExit(hipStream_t s_) : s(s_) {}
     ~DrainOnExit() { (void)hipStreamSynchronize(s); }
 };
+// a call's own stream and its timing events, destroyed when the scope is left
+struct StreamHolder {
+    hipStream_t s = nullptr;
+    ~StreamHolder() { if (s) (void)hipStreamDestroy(s); }
+};
+template <int N> struct Events {
+    hipEvent_t e[N] = {};
+    ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
+};
 
 // Body of a worker std::thread: an exception leaving it would end the process (std::terminate) -- it becomes a status instead.
 template <class F, class OnFail>
@@ -97,6 +106,24 @@ int device_of_ptr(const void *p);   // owning device, -1 for host memory
 // dst device <- src (host or device); dst (host or device) <- src device
 int32_t copy_to_device(void *dst_dev, const void *src, size_t bytes, hipStream_t s);
 int32_t copy_from_device(void *dst, const void *src_dev, size_t bytes, hipStream_t s);
+// a read-only argument made resident on device `dev` (aliased when it already is, or when there is nothing to stage)
+template <class T> struct Staged {
+    DevBuf own;
+    const T *p = nullptr;
+    int32_t set(const T *src, int64_t count, int dev, hipStream_t s) {
+        if (!src || count == 0) { p = src; return LPVS_OK; }
+        const int owner = device_of_ptr(src);
+        if (owner == dev) { p = src; return LPVS_OK; }
+        LPVS_TRY(own.alloc(sizeof(T) * (size_t)count));
+        if (owner >= 0) {
+            LPVS_HIP(hipMemcpyPeerAsync(own.p, dev, src, owner, sizeof(T) * (size_t)count, s));
+            LPVS_HIP(hipStreamSynchronize(s));
+        } else
+            LPVS_TRY(copy_to_device(own.p, src, sizeof(T) * (size_t)count, s));
+        p = own.as<T>();
+        return LPVS_OK;
+    }
+};
 
 // ---- basis tables (basis.hip) -----------------------------------------------------------
 // Fourier regressor, column-major N x Nreg (reference layout)          src/lsfft.jl:26-49

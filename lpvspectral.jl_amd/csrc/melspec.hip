@@ -19,9 +19,11 @@
 // launch whose workgroups loop over their batches with the sums in LDS was measured at 3x the time: the FFT already fills the register
 // file, and the loop's live state spills.)  On the four-step paths a chunk's spectra already sit in global scratch: the split, the power
 // and the sum over slabs of kWelchChunkFrames frames are one kernel, a thread per bin.
-// A second kernel adds the slabs in a fixed pairwise tree and a third divides by the frame count.  The longest chain of dependent
-// additions behind one bin is D = F - 1 + ceil(log2 S), F the most frames behind one slab (<= kWelchChain), S the slabs.
+// A second kernel adds the slabs in a fixed pairwise tree and a third divides by the frame count.
+// Which path a call takes, its frame pairs per workgroup, its chunks, its slabs with their sum chain and the memory it needs are decided
+// in stft_plan.h (StftPlan: pure host arithmetic, tested without a device); stft_impl below runs one function per phase of that plan.
 #include "lpvs_internal.h"
+#include "stft_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -31,18 +33,9 @@
 namespace lpvs {
 namespace {
 
-constexpr int kFftMax = 8192;        // complex points per workgroup (16 B each: 128 KiB of LDS)
-constexpr int kThreads = 512;           // 8 waves: up to 256 VGPRs each, no spills in the radix-7 stage
-constexpr int kMaxStages = 16;
-constexpr int kMaxPairs = 512;       // frame pairs per workgroup (small nfft)
-constexpr int kSplitPer = 10;        // split items per thread: pairs x bins of a workgroup <= kSplitPer * kThreads (host-checked)
-constexpr int64_t kMaxLen = 1ll << 26;
+// (kFftMax, kThreads, kMaxStages, kMaxPairs, kSplitPer, kMaxLen, the scratch budget and the frame average's constants: stft_plan.h)
 constexpr int64_t kRootB = 8192;     // two-table roots: r = hi * kRootB + lo
 constexpr int kEpiThreads = 256;
-constexpr size_t kScratchBudget = (size_t)1 << 30;   // bytes of four-step scratch per chunk of frame pairs
-constexpr int64_t kWelchChain = 1024;        // most frames one workgroup adds sequentially into its slab (LDS paths)
-constexpr int64_t kWelchSlabs = 1024;        // slabs launched when the frames allow it (more when kWelchChain asks for it)
-constexpr int64_t kWelchChunkFrames = 256;   // frames per slab on the four-step paths
 
 enum : int { IN_SIGNAL = 0, IN_GLOBAL = 1 };
 enum : int { POST_NONE = 0, POST_TWIDDLE = 1, POST_BLUE_MUL = 2, POST_BLUESTEIN_LDS = 3 };
@@ -51,24 +44,7 @@ enum : int { OUT_GLOBAL = 0, OUT_EPI = 1 };
 __host__ __device__ inline double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 __host__ __device__ inline double2 conjd(double2 a) { return make_double2(a.x, -a.y); }
 
-// ---- host: 7-smooth lengths, factorisation, roots -----------------------------------------------------------------------------------
-bool is_smooth(int64_t n) {
-    if (n < 1) return false;
-    for (int64_t p : {2, 3, 5, 7}) while (n % p == 0) n /= p;
-    return n == 1;
-}
-int64_t next_smooth(int64_t n) {
-    int64_t m = n < 1 ? 1 : n;
-    while (!is_smooth(m)) ++m;
-    return m;
-}
-struct Radices { int n = 0; int r[kMaxStages]; };
-Radices factor(int64_t N) {
-    Radices f;
-    for (int p : {8, 4, 2, 3, 5, 7})
-        while (N % p == 0) { f.r[f.n++] = p; N /= p; }
-    return f;
-}
+// ---- host: roots (7-smooth lengths and their factorisation: stft_plan.h) -------------------------------------------------------------
 // exp(-2 pi i t / M) within about 1 ulp: quadrant and octant taken in integers, the rest in long double on [0, pi/4]
 double2 host_root(int64_t t, int64_t M) {
     t %= M;
@@ -647,55 +623,13 @@ __global__ void bluestein_b_kernel(RootTab chirp, int64_t n, int64_t m, double2 
 constexpr int kTimingSlots = 11;
 thread_local double g_timing[kTimingSlots] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
-struct StreamHolder {
-    hipStream_t s = nullptr;
-    ~StreamHolder() { if (s) (void)hipStreamDestroy(s); }
-};
-struct Events {
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
-};
-template <class T> struct Staged {
-    DevBuf own;
-    const T *p = nullptr;
-    int32_t set(const T *src, int64_t count, int dev, hipStream_t s) {
-        if (!src || count == 0) { p = src; return LPVS_OK; }
-        const int owner = device_of_ptr(src);
-        if (owner == dev) { p = src; return LPVS_OK; }
-        LPVS_TRY(own.alloc(sizeof(T) * (size_t)count));
-        if (owner >= 0) {
-            LPVS_HIP(hipMemcpyPeerAsync(own.p, dev, src, owner, sizeof(T) * (size_t)count, s));
-            LPVS_HIP(hipStreamSynchronize(s));
-        } else
-            LPVS_TRY(copy_to_device(own.p, src, sizeof(T) * (size_t)count, s));
-        p = own.as<T>();
-        return LPVS_OK;
-    }
-};
-
-// a length <= 2^26 the engine runs: <= 8192 in LDS, else n1 * n2 with both factors <= 8192 and the most balanced such split
-struct Plan {
-    int64_t len = 0, n1 = 0, n2 = 0;
-    bool fits() const { return len > 0; }
-};
-Plan plan_length(int64_t N) {
-    Plan p;
-    if (!is_smooth(N) || N > kMaxLen) return p;
-    if (N <= kFftMax) { p.len = N; p.n1 = N; p.n2 = 1; return p; }
-    int64_t best = 0;
-    for (int64_t d = 2; d <= kFftMax; ++d)
-        if (N % d == 0 && N / d <= kFftMax && (best == 0 || std::llabs(d * d - N) < std::llabs(best * best - N))) best = d;
-    if (best) { p.len = N; p.n1 = best; p.n2 = N / best; }
-    return p;
-}
-
 // one FFT length on the device: LDS twiddles of its factors and, for the four-step, the twiddle table of n1 n2
 struct LengthTables {
-    Plan pl;
+    FftSplit pl;
     HostTwiddles t1, t2;
     HostRootTab t4;
     Radices r1, r2;
-    int32_t make(const Plan &p, hipStream_t s) {
+    int32_t make(const FftSplit &p, hipStream_t s) {
         pl = p;
         r1 = factor(p.n1);
         LPVS_TRY(t1.make(p.n1, s));
@@ -731,14 +665,14 @@ template <class T> int32_t four_step(FftJob<T> J, const LengthTables &L, int64_t
     const int64_t n1 = L.pl.n1, n2 = L.pl.n2;
     // pass 1: columns j2 (n2 of them), length n1, times omega^(j2 k1) -> tmp[p][k1][j2]
     FftJob<T> A = J;
-    set_fft(A, (int)n1, L.r1, L.t1.buf.as<double2>(), (int)std::max<int64_t>(1, kFftMax / n1), npair * n2, n2);
+    set_fft(A, (int)n1, L.r1, L.t1.buf.as<double2>(), fft_batch(n1), npair * n2, n2);
     if (A.in_mode == IN_GLOBAL) { A.in_cs = 1; A.in_es = n2; }
     A.post = POST_TWIDDLE; A.tw4 = L.t4.tab;
     A.out_mode = OUT_GLOBAL; A.gout = tmp; A.out_ps = ps; A.out_cs = 1; A.out_es = n2;
     LPVS_TRY(launch_fft(A, s));
     // pass 2: rows k1 (n1 of them), length n2 -> out[p][k1 + n1 k2]
     FftJob<T> Bj;
-    set_fft(Bj, (int)n2, L.r2, L.t2.buf.as<double2>(), (int)std::max<int64_t>(1, kFftMax / n2), npair * n1, n1);
+    set_fft(Bj, (int)n2, L.r2, L.t2.buf.as<double2>(), fft_batch(n2), npair * n1, n1);
     Bj.in_mode = IN_GLOBAL; Bj.gin = tmp; Bj.in_ps = ps; Bj.in_cs = n2; Bj.in_es = 1;
     if (bhat) { Bj.post = POST_BLUE_MUL; Bj.bhat = bhat; Bj.bhat_cs = 1; Bj.bhat_es = n1; }
     Bj.out_mode = OUT_GLOBAL; Bj.gout = out; Bj.out_ps = ps; Bj.out_cs = 1; Bj.out_es = n1;
@@ -797,273 +731,293 @@ struct EpiTables {   // W compacted band by band (each band's weights of its bin
     }
 };
 
+// ---- one STFT call, phase by phase (every number that is decided: StftPlan) -----------------------------------------------------
+// the arguments, before any device is needed (LPVS_STFT_WELCH is lpvs_welch's only: out holds the mean over the frames)
 template <class T>
-int32_t stft_impl(int32_t kind, const T *s_in, int64_t L, int64_t n, int64_t noverlap, int64_t nfft, double fs, const T *window, const float *W,
-                  int64_t nmels, const float *D, int64_t nmfcc, int32_t device, T *out, int64_t capacity, int64_t *nframes, int twosided = 0) {
-    // ---- arguments (before any device is needed)
-    const bool welch = kind == LPVS_STFT_WELCH;   // lpvs_welch only: out holds the mean over the frames, nbins values (nfft two-sided)
-    if (kind != LPVS_STFT_POWER && kind != LPVS_STFT_MEL && kind != LPVS_STFT_MFCC && !welch) { set_error("kind must be LPVS_STFT_POWER, _MEL or _MFCC, got %d", kind); return LPVS_EARGUMENT; }
+int32_t check_stft_arguments(int32_t kind, const T *s_in, int64_t L, int64_t n, int64_t noverlap, int64_t nfft, const float *W, int64_t nmels,
+                             const float *D, int64_t nmfcc, const int64_t *nframes) {
+    if (kind != LPVS_STFT_POWER && kind != LPVS_STFT_MEL && kind != LPVS_STFT_MFCC && kind != LPVS_STFT_WELCH) { set_error("kind must be LPVS_STFT_POWER, _MEL or _MFCC, got %d", kind); return LPVS_EARGUMENT; }
     if (!nframes || (!s_in && L > 0)) { set_error("NULL argument"); return LPVS_EARGUMENT; }
     if (L < 0 || n < 1) { set_error("need L >= 0 and n >= 1 (L = %lld, n = %lld)", (long long)L, (long long)n); return LPVS_EARGUMENT; }
     if (noverlap < 0 || noverlap >= n) { set_error("noverlap must satisfy 0 <= noverlap < n (noverlap = %lld, n = %lld)", (long long)noverlap, (long long)n); return LPVS_EDOMAIN; }
     if (nfft < n) { set_error("nfft must be >= n (nfft = %lld, n = %lld)", (long long)nfft, (long long)n); return LPVS_EARGUMENT; }
     if (nfft > kMaxLen) { set_error("nfft = %lld exceeds the supported 2^26", (long long)nfft); return LPVS_EUNSUPPORTED; }
-    const int64_t nbins = nfft / 2 + 1;
     if ((kind == LPVS_STFT_MEL || kind == LPVS_STFT_MFCC) && (!W || nmels < 1)) { set_error("the mel and MFCC kinds need W and nmels >= 1"); return LPVS_EARGUMENT; }
     if (kind == LPVS_STFT_MFCC && (!D || nmfcc < 1)) { set_error("the MFCC kind needs D and nmfcc >= 1"); return LPVS_EARGUMENT; }
     if (kind == LPVS_STFT_MFCC && nmels + nmfcc > 16384) { set_error("nmels + nmfcc = %lld exceeds 16384", (long long)(nmels + nmfcc)); return LPVS_EUNSUPPORTED; }
-    const int64_t hop = n - noverlap;
-    const int64_t k = L >= n ? (L - n) / hop + 1 : 0;
-    const int64_t rows = welch ? (twosided ? nfft : nbins) : (kind == LPVS_STFT_POWER ? nbins : (kind == LPVS_STFT_MEL ? nmels : nmfcc));
-    const int64_t nout = welch ? rows : k * rows;   // output values
-    *nframes = k;
-    if (welch && k == 0) { set_error("welch_pgram: the signal (L = %lld) is shorter than one frame (n = %lld): the mean over no frame is undefined", (long long)L, (long long)n); return LPVS_EDOMAIN; }
-    // Bluestein length: the smallest 7-smooth m >= 2 nfft - 1 the engine runs
-    const bool blue = !is_smooth(nfft);
-    Plan pl = plan_length(nfft);
-    int64_t m = 0;
-    if (blue) {
-        m = next_smooth(2 * nfft - 1);
-        while (m <= kMaxLen && !plan_length(m).fits()) m = next_smooth(m + 1);
-        if (m > kMaxLen) { set_error("nfft = %lld is not 7-smooth and its Bluestein length exceeds 2^26", (long long)nfft); return LPVS_EUNSUPPORTED; }
-        pl = plan_length(m);
-    } else if (!pl.fits()) {
-        set_error("nfft = %lld has no split into two factors <= 8192", (long long)nfft);
-        return LPVS_EUNSUPPORTED;
+    return LPVS_OK;
+}
+// what the plan refuses, as a status and a message
+int32_t refusal_status(const StftPlan &P) {
+    switch (P.refusal) {
+        case kStftOk: return LPVS_OK;
+        case kStftNfftTooLong: set_error("nfft = %lld exceeds the supported 2^26", (long long)P.nfft); return LPVS_EUNSUPPORTED;
+        case kStftNoSplit: set_error("nfft = %lld has no split into two factors <= 8192", (long long)P.nfft); return LPVS_EUNSUPPORTED;
+        case kStftBluesteinTooLong: set_error("nfft = %lld is not 7-smooth and its Bluestein length exceeds 2^26", (long long)P.nfft); return LPVS_EUNSUPPORTED;
+        case kStftTooManySlabs: set_error("welch_pgram: %lld frames need more than 2^30 slabs", (long long)P.frames); return LPVS_EUNSUPPORTED;
+        case kStftWelchNoPair: break;
     }
+    set_error("internal: the frame average of nfft = %lld has no room for a frame pair in LDS", (long long)P.nfft);
+    return LPVS_EASSERT;
+}
+
+// the device buffers of a call, in stft_impl BEFORE its DrainOnExit (they return to the pool once the stream is idle); the tables after it
+template <class T> struct StftBuffers {
+    Staged<T> ds, dw;
+    DevBuf dout, tmp, zbuf, pwbuf, bvec, btmp, bhat, fbad, fexp, wslab;
+    T *dst = nullptr;   // the output on the device: the caller's array, or dout
+};
+struct StftTables {
+    EpiTables et;
+    LengthTables lt;
+    HostRootTab chirp;
+};
+// how the split undoes Bluestein after the four-step inverse: conj / m and the chirp (spectra through the LDS inverse need neither)
+struct Unchirp {
+    int blue = 0;
+    RootTab chirp;
+    int64_t m = 0;
+};
+
+// r / fs = sum(win.^2) (n without a window); hwin: the window on the host
+template <class T> int32_t window_norm(const T *window, int64_t n, hipStream_t s, std::vector<T> &hwin, double *norm2) {
+    *norm2 = (double)n;
+    if (!window) return LPVS_OK;
+    hwin.resize((size_t)n);
+    if (device_of_ptr(window) >= 0) LPVS_TRY(copy_from_device(hwin.data(), window, sizeof(T) * (size_t)n, s));
+    else std::memcpy(hwin.data(), window, sizeof(T) * (size_t)n);
+    *norm2 = 0.0;
+    for (int64_t i = 0; i < n; ++i) *norm2 = *norm2 + (double)hwin[(size_t)i] * (double)hwin[(size_t)i];
+    return LPVS_OK;
+}
+
+// the slabs must be countable and the outputs plus the minimum scratch must fit, or LPVS_ENOMEM
+int32_t admit(const StftPlan &P, size_t elt, bool dev_out, bool dev_signal, int device) {
+    LPVS_TRY(refusal_status(P));
+    size_t fr = 0, tot = 0;
+    LPVS_HIP(hipMemGetInfo(&fr, &tot));
+    const size_t avail = fr + pool_cached_bytes(device), need = stft_device_bytes(P, elt, dev_out, dev_signal);
+    if (need > avail) {
+        set_error("spectrogram: %lld frames of nfft %lld need %.2f GB of device memory, %.2f GB are free", (long long)P.frames, (long long)P.nfft,
+                  need / 1e9, avail / 1e9);
+        return LPVS_ENOMEM;
+    }
+    return LPVS_OK;
+}
+
+// the signal, the window and the output on the device, the slabs, the epilogue's and the lengths' tables
+template <class T>
+int32_t stage_inputs(const StftPlan &P, const T *s_in, const std::vector<T> &hwin, const float *W, const float *D, int device, T *out, bool dev_out,
+                     hipStream_t s, StftBuffers<T> &b, StftTables &t) {
+    LPVS_TRY(b.ds.set(s_in, P.L, device, s));
+    if (!hwin.empty()) {
+        LPVS_TRY(b.dw.own.alloc(sizeof(T) * (size_t)P.n));
+        LPVS_TRY(copy_to_device(b.dw.own.p, hwin.data(), sizeof(T) * (size_t)P.n, s));
+        b.dw.p = b.dw.own.template as<T>();
+    }
+    b.dst = out;
+    if (!dev_out) { LPVS_TRY(b.dout.alloc(P.out_bytes(sizeof(T)))); b.dst = b.dout.template as<T>(); }
+    if (P.welch) LPVS_TRY(b.wslab.alloc(P.slab_bytes()));
+    if (P.kind == LPVS_STFT_MEL || P.kind == LPVS_STFT_MFCC)
+        LPVS_TRY(t.et.make(W, P.nmels, P.nbins, P.kind == LPVS_STFT_MFCC ? D : nullptr, P.nmfcc, device, s));
+    LPVS_TRY(t.lt.make(P.split, s));
+    if (P.blue) LPVS_TRY(t.chirp.make(2 * P.nfft, s));
+    return LPVS_OK;
+}
+
+// the four-step's sequences (and the LDS fallback's split) do not see whole frames: flag the frames and take their max-abs exponents first
+template <class T> int32_t flag_frames(const StftPlan &P, FftJob<T> &J, StftBuffers<T> &b, hipStream_t s) {
+    LPVS_TRY(b.fbad.alloc(P.flag_bytes()));
+    LPVS_TRY(b.fexp.alloc(P.flag_bytes()));
+    frame_bad_kernel<T><<<frame_blocks(P.frames), kEpiThreads, 0, s>>>(b.ds.p, b.dw.p, P.n, P.hop, b.fbad.template as<int32_t>(), b.fexp.template as<int32_t>(), P.frames);
+    LPVS_HIP(hipGetLastError());
+    J.fbad = b.fbad.template as<int32_t>(); J.fexp = b.fexp.template as<int32_t>();
+    return LPVS_OK;
+}
+
+// Bluestein: bhat = FFT_m(b), b_j = conj(chirp_|j|) for |j| < nfft (indices mod m)
+template <class T> int32_t bluestein_bhat(const StftPlan &P, const StftTables &t, StftBuffers<T> &b, hipStream_t s) {
+    const int64_t m = P.m;
+    LPVS_TRY(b.bvec.alloc(P.bluestein_bytes()));
+    LPVS_TRY(b.bhat.alloc(P.bluestein_bytes()));
+    bluestein_b_kernel<<<(unsigned)std::min<int64_t>(ceil_div(m, 256), 65536), 256, 0, s>>>(t.chirp.tab, P.nfft, m, b.bvec.template as<double2>());
+    LPVS_HIP(hipGetLastError());
+    FftJob<T> Bj;
+    Bj.in_mode = IN_GLOBAL; Bj.gin = b.bvec.template as<double2>(); Bj.in_ps = m; Bj.in_es = 1;
+    if (P.lds) {
+        set_fft(Bj, (int)m, t.lt.r1, t.lt.t1.buf.template as<double2>(), 1, 1, 1);
+        Bj.out_mode = OUT_GLOBAL; Bj.gout = b.bhat.template as<double2>(); Bj.out_ps = m; Bj.out_es = 1;
+        return launch_fft(Bj, s);
+    }
+    LPVS_TRY(b.btmp.alloc(P.bluestein_bytes()));
+    return four_step(Bj, t.lt, 1, b.btmp.template as<double2>(), b.bhat.template as<double2>(), m, s, nullptr);
+}
+
+// np frame pairs' spectra in zbuf, the first of them frame f0's -> power rows of the output, the slabs from *wbase on, or power columns
+// and the epilogue
+template <class T>
+int32_t spectra_to_output(const StftPlan &P, const Epi<T> &E, const StftBuffers<T> &b, const Unchirp &u, int64_t f0, int64_t np, int64_t *wbase, hipStream_t s) {
+    const double2 *Z = b.zbuf.template as<double2>();
+    const int32_t *fbad = b.fbad.template as<int32_t>(), *fexp = b.fexp.template as<int32_t>();
+    const int64_t flen = P.split.len, nfr = std::min<int64_t>(2 * np, P.frames - f0);
+    if (P.welch) {
+        const int64_t ns = welch_chunk_slabs(nfr);
+        welch_split_sum_kernel<<<dim3((unsigned)ceil_div(P.nbins, kEpiThreads), (unsigned)ns), kEpiThreads, 0, s>>>(
+            Z, flen, P.nfft, P.nbins, E.m1, E.m2, u.blue, u.chirp, u.m, f0, P.frames, fbad, fexp, np, kWelchChunkPairs,
+            b.wslab.template as<double>() + *wbase * P.nbins);
+        LPVS_HIP(hipGetLastError());
+        *wbase += ns;
+    } else if (P.power_columns()) {
+        split_power_kernel<double><<<frame_blocks(np), kEpiThreads, 0, s>>>(Z, flen, P.nfft, P.nbins, E.m1, E.m2, u.blue, u.chirp, u.m, f0, P.frames, fbad,
+                                                                            fexp, b.pwbuf.template as<double>(), f0, np);
+        LPVS_HIP(hipGetLastError());
+        const size_t shb = P.kind == LPVS_STFT_MFCC ? sizeof(double) * (size_t)(P.nmels + P.nmfcc) : 0;
+        epilogue_kernel<double, T><<<frame_blocks(nfr), kEpiThreads, shb, s>>>(b.pwbuf.template as<double>(), f0, E, f0, nfr);
+        LPVS_HIP(hipGetLastError());
+    } else {
+        split_power_kernel<T><<<frame_blocks(np), kEpiThreads, 0, s>>>(Z, flen, P.nfft, P.nbins, E.m1, E.m2, u.blue, u.chirp, u.m, f0, P.frames, fbad, fexp,
+                                                                       b.dst, 0, np);
+        LPVS_HIP(hipGetLastError());
+    }
+    return LPVS_OK;
+}
+
+// the LDS paths: everything in one launch; the frame average batch after batch into its slabs; or the fallback
+template <class T>
+int32_t run_lds(const StftPlan &P, FftJob<T> J, const Epi<T> &E, const StftTables &t, StftBuffers<T> &b, hipStream_t s) {
+    const int64_t flen = P.split.len;
+    set_fft(J, (int)flen, t.lt.r1, t.lt.t1.buf.template as<double2>(), 1, P.pairs, 1);
+    if (P.blue) { J.post = POST_BLUESTEIN_LDS; J.bhat = b.bhat.template as<double2>(); J.bhat_cs = 0; J.bhat_es = 1; J.blue_m = P.m; }
+    if (!P.fallback) {
+        J.B = (int)P.pairs_per_workgroup; J.out_mode = OUT_EPI; J.epi = E;
+        if (!P.welch) return launch_fft(J, s);
+        for (int64_t b0 = 0; b0 < P.batches; b0 += P.slabs) {   // the same P.slabs workgroups a launch, each into its own slab
+            J.blk0 = b0;
+            stft_welch_kernel<T><<<(unsigned)std::min<int64_t>(P.slabs, P.batches - b0), kThreads, 0, s>>>(J);
+            LPVS_HIP(hipGetLastError());
+        }
+        return LPVS_OK;
+    }
+    // the epilogue's LDS regions do not fit next to a frame pair: spectra (already through the Bluestein inverse) to global, then as a chunk
+    LPVS_TRY(flag_frames(P, J, b, s));
+    LPVS_TRY(b.pwbuf.alloc(P.fallback_power_bytes()));
+    J.B = P.fallback_batch;
+    J.out_mode = OUT_GLOBAL;
+    LPVS_TRY(b.zbuf.alloc(P.fallback_spectra_bytes()));
+    J.gout = b.zbuf.template as<double2>(); J.out_ps = flen; J.out_cs = 0; J.out_es = 1;
+    LPVS_TRY(launch_fft(J, s));
+    Unchirp none;
+    none.m = 1;
+    return spectra_to_output(P, E, b, none, 0, P.pairs, nullptr, s);
+}
+
+// the four-step paths: chunks of P.chunk_pairs frame pairs through global scratch
+template <class T>
+int32_t run_four_step(const StftPlan &P, FftJob<T> J, const Epi<T> &E, const StftTables &t, StftBuffers<T> &b, hipStream_t s) {
+    const int64_t flen = P.split.len, cp = P.chunk_pairs;
+    LPVS_TRY(flag_frames(P, J, b, s));
+    LPVS_TRY(b.tmp.alloc((size_t)cp * P.pair_spectrum_bytes()));
+    LPVS_TRY(b.zbuf.alloc((size_t)cp * P.pair_spectrum_bytes()));
+    if (P.power_columns()) LPVS_TRY(b.pwbuf.alloc((size_t)cp * P.pair_power_bytes()));
+    double2 *tmp = b.tmp.template as<double2>(), *Z = b.zbuf.template as<double2>();
+    Unchirp u;
+    u.blue = P.blue; u.chirp = t.chirp.tab; u.m = P.m;
+    int64_t wbase = 0;   // slabs written by the chunks so far
+    for (int64_t p0 = 0; p0 < P.pairs; p0 += cp) {
+        const int64_t np = std::min<int64_t>(cp, P.pairs - p0);
+        FftJob<T> A = J;
+        A.frame0 = 2 * p0;
+        if (P.blue) {
+            // forward FFT_m of the chirped frames (times bhat, conjugated, after pass 2) into Z, then the inverse (a forward FFT of
+            // the conjugate) back into Z; the split applies conj / m and the chirp
+            LPVS_TRY(four_step(A, t.lt, np, tmp, Z, flen, s, b.bhat.template as<double2>()));
+            FftJob<T> I;
+            I.in_mode = IN_GLOBAL; I.gin = Z; I.in_ps = flen;
+            LPVS_TRY(four_step(I, t.lt, np, tmp, Z, flen, s, nullptr));
+        } else
+            LPVS_TRY(four_step(A, t.lt, np, tmp, Z, flen, s, nullptr));
+        LPVS_TRY(spectra_to_output(P, E, b, u, 2 * p0, np, &wbase, s));
+    }
+    return LPVS_OK;
+}
+
+// the slabs in a fixed pairwise tree (two levels a launch), then the mean
+template <class T> int32_t welch_reduce(const StftPlan &P, const StftBuffers<T> &b, hipStream_t s) {
+    double *slab = b.wslab.template as<double>();
+    for (int64_t st = 1; st < P.slabs; st *= 4) {
+        const int64_t groups = ceil_div(P.slabs, 4 * st);
+        welch_tree_kernel<<<(unsigned)ceil_div(groups * P.nbins, kEpiThreads), kEpiThreads, 0, s>>>(slab, P.slabs, P.nbins, st, groups);
+        LPVS_HIP(hipGetLastError());
+    }
+    welch_finish_kernel<T><<<(unsigned)ceil_div(P.nbins, kEpiThreads), kEpiThreads, 0, s>>>(slab, P.nbins, P.nfft, (double)P.frames, P.twosided, b.dst);
+    LPVS_HIP(hipGetLastError());
+    return LPVS_OK;
+}
+
+// [0] device work: Bluestein kernel, frame flags, FFTs, epilogue, [1] copy-out, [2] total (setup + [0] + [1]), [3] frames,
+// [4] path (1 LDS, 2 four-step, 3 Bluestein in LDS, 4 Bluestein four-step), [5] FFT length, [6] frame pairs per workgroup (LDS
+// paths; 0 on the LDS fallback through global power columns), [7] rows, [8] setup: host tables, band ranges and uploads,
+// [9] LPVS_STFT_WELCH: the longest chain of dependent additions behind one bin (StftPlan::sum_chain), [10] its slabs S (0 otherwise)
+int32_t report_timing(const StftPlan &P, const Events<4> &ev) {
+    float ms[3] = {0, 0, 0};
+    for (int i = 0; i < 3; ++i) LPVS_HIP(hipEventElapsedTime(&ms[i], ev.e[i], ev.e[i + 1]));
+    g_timing[0] = ms[1]; g_timing[1] = ms[2]; g_timing[2] = (double)ms[0] + ms[1] + ms[2]; g_timing[3] = (double)P.frames; g_timing[4] = P.path;
+    g_timing[5] = (double)P.split.len; g_timing[6] = P.lds ? (double)P.pairs_per_workgroup : 1.0; g_timing[7] = (double)P.rows; g_timing[8] = ms[0];
+    g_timing[9] = (double)P.sum_chain; g_timing[10] = (double)P.slabs;
+    return LPVS_OK;
+}
+
+template <class T>
+int32_t stft_impl(int32_t kind, const T *s_in, int64_t L, int64_t n, int64_t noverlap, int64_t nfft, double fs, const T *window, const float *W,
+                  int64_t nmels, const float *D, int64_t nmfcc, int32_t device, T *out, int64_t capacity, int64_t *nframes, int twosided = 0) {
+    LPVS_TRY(check_stft_arguments(kind, s_in, L, n, noverlap, nfft, W, nmels, D, nmfcc, nframes));
+    const StftPlan P = stft_plan(kind, L, n, noverlap, nfft, nmels, nmfcc, twosided != 0);
+    *nframes = P.frames;
+    if (P.welch && P.frames == 0) { set_error("welch_pgram: the signal (L = %lld) is shorter than one frame (n = %lld): the mean over no frame is undefined", (long long)L, (long long)n); return LPVS_EDOMAIN; }
+    if (P.refusal != kStftTooManySlabs) LPVS_TRY(refusal_status(P));   // (the slabs are refused where the memory is: admit)
     LPVS_TRY(need_device());
     if (!out) return LPVS_OK;   // count only
-    if (capacity < nout) { set_error("capacity %lld < %lld outputs (%lld rows x %lld frames)", (long long)capacity, (long long)nout, (long long)rows, (long long)(welch ? 1 : k)); return LPVS_EARGUMENT; }
-    if (k == 0) return LPVS_OK;
+    if (capacity < P.nout) { set_error("capacity %lld < %lld outputs (%lld rows x %lld frames)", (long long)capacity, (long long)P.nout, (long long)P.rows, (long long)(P.welch ? 1 : P.frames)); return LPVS_EARGUMENT; }
+    if (P.frames == 0) return LPVS_OK;
     LPVS_HIP(hipSetDevice(device));
 
     StreamHolder sh;
     LPVS_HIP(hipStreamCreateWithFlags(&sh.s, hipStreamNonBlocking));
     const hipStream_t s = sh.s;
-    Events ev;
+    Events<4> ev;
     for (auto &x : ev.e) LPVS_HIP(hipEventCreate(&x));
-    // ---- window: r = fs * sum(win.^2) (n without a window)
     std::vector<T> hwin;
-    double norm2 = (double)n;
-    if (window) {
-        hwin.resize((size_t)n);
-        if (device_of_ptr(window) >= 0) LPVS_TRY(copy_from_device(hwin.data(), window, sizeof(T) * (size_t)n, s));
-        else std::memcpy(hwin.data(), window, sizeof(T) * (size_t)n);
-        norm2 = 0.0;
-        for (int64_t i = 0; i < n; ++i) norm2 = norm2 + (double)hwin[(size_t)i] * (double)hwin[(size_t)i];
-    }
+    double norm2 = 0;
+    LPVS_TRY(window_norm(window, n, s, hwin, &norm2));
     const double r = fs * norm2;
-
-    // ---- memory: outputs plus the minimum scratch must fit, or LPVS_ENOMEM
     const bool dev_out = device_of_ptr(out) == device;
-    const int64_t npair_all = (k + 1) / 2;
-    const int64_t flen = pl.len;                             // FFT length: nfft, or m for Bluestein
-    const bool lds = flen <= kFftMax;
-    const size_t per_pair = lds ? 0 : 2 * sizeof(double2) * (size_t)flen;   // tmp + Z
-    const size_t power_per_pair = (kind == LPVS_STFT_POWER || welch) ? 0 : 2 * sizeof(double) * (size_t)nbins;
-    // LDS paths: frame pairs per workgroup -- the FFT buffer, the power / mel / DCT regions of the epilogue (doubles) and the split's
-    // registers must fit; 0 means the epilogue's regions do not fit next to one pair (the fallback through global power columns)
-    int64_t lds_b = 0;
-    if (lds) {
-        const int64_t per_pair_dbl = kind == LPVS_STFT_POWER ? 0 : 2 * (nbins + nmels + (kind == LPVS_STFT_MFCC ? nmfcc : 0));
-        lds_b = kFftMax / flen;
-        if (per_pair_dbl > 0) lds_b = std::min<int64_t>(lds_b, (2 * kFftMax) / per_pair_dbl);
-        lds_b = std::min<int64_t>(std::min<int64_t>(lds_b, kMaxPairs), npair_all);
-        while (lds_b > 1 && lds_b * nbins > (int64_t)kSplitPer * kThreads) --lds_b;
-        lds_b = std::max<int64_t>(lds_b, 0);
-    }
-    const bool fallback = lds && lds_b < 1;
-    // frame averaging: S slabs of nbins partial sums, at most F frames behind one slab (the header comment has the rule)
-    int64_t wS = 0, wF = 0, wcp = 0;
-    if (welch && lds) {
-        const int64_t nbatch = ceil_div(npair_all, lds_b), bpw = std::max<int64_t>(1, kWelchChain / (2 * lds_b));
-        wS = std::max<int64_t>(std::min<int64_t>(nbatch, kWelchSlabs), ceil_div(nbatch, bpw));
-        wF = ceil_div(nbatch, wS) * 2 * lds_b - ((nbatch - 1) % wS == 0 ? 2 * lds_b * nbatch - k : 0);
-    } else if (welch) {
-        wcp = std::max<int64_t>(1, std::min<int64_t>(npair_all, (int64_t)(kScratchBudget / per_pair)));
-        for (int64_t p0 = 0; p0 < npair_all; p0 += wcp) {
-            const int64_t nfr = std::min<int64_t>(2 * std::min<int64_t>(wcp, npair_all - p0), k - 2 * p0);
-            wS += ceil_div(nfr, kWelchChunkFrames);
-            wF = std::max<int64_t>(wF, std::min<int64_t>(nfr, kWelchChunkFrames));
-        }
-    }
-    if (wS > ((int64_t)1 << 30)) { set_error("welch_pgram: %lld frames need more than 2^30 slabs", (long long)k); return LPVS_EUNSUPPORTED; }
-    int64_t wdepth = 0;
-    while (((int64_t)1 << wdepth) < wS) ++wdepth;
-    {
-        size_t fr = 0, tot = 0;
-        LPVS_HIP(hipMemGetInfo(&fr, &tot));
-        const size_t avail = fr + pool_cached_bytes(device);
-        const size_t need = (dev_out ? 0 : sizeof(T) * (size_t)nout) + sizeof(double) * (size_t)(wS * nbins) + (device_of_ptr(s_in) == device ? 0 : sizeof(T) * (size_t)L) +
-                            per_pair + power_per_pair + (blue ? sizeof(double2) * (size_t)m * 3 : 0) +
-                            (lds && !fallback ? 0 : 2 * sizeof(int32_t) * (size_t)k) +                    // frame flags, exponents
-                            (fallback ? sizeof(double) * (size_t)(k * nbins) + sizeof(double2) * (size_t)(npair_all * flen) : 0);
-        if (need > avail) {
-            set_error("spectrogram: %lld frames of nfft %lld need %.2f GB of device memory, %.2f GB are free", (long long)k, (long long)nfft,
-                      need / 1e9, avail / 1e9);
-            return LPVS_ENOMEM;
-        }
-    }
+    LPVS_TRY(admit(P, sizeof(T), dev_out, device_of_ptr(s_in) == device, device));
+
     LPVS_HIP(hipEventRecord(ev.e[0], s));   // setup: host tables, band ranges, uploads (the stream is idle until e[1])
-    Staged<T> ds, dw;
-    DevBuf dout, tmp, zbuf, pwbuf, bvec, btmp, bhat, fbad, fexp, wslab;
+    StftBuffers<T> b;
     DrainOnExit drain(s);
-    LPVS_TRY(ds.set(s_in, L, device, s));
-    if (window) {
-        LPVS_TRY(dw.own.alloc(sizeof(T) * (size_t)n));
-        LPVS_TRY(copy_to_device(dw.own.p, hwin.data(), sizeof(T) * (size_t)n, s));
-        dw.p = dw.own.template as<T>();
-    }
-    T *dst = out;
-    if (!dev_out) { LPVS_TRY(dout.alloc(sizeof(T) * (size_t)nout)); dst = dout.as<T>(); }
-    if (welch) LPVS_TRY(wslab.alloc(sizeof(double) * (size_t)(wS * nbins)));
-    EpiTables et;
-    if (kind == LPVS_STFT_MEL || kind == LPVS_STFT_MFCC) LPVS_TRY(et.make(W, nmels, nbins, kind == LPVS_STFT_MFCC ? D : nullptr, nmfcc, device, s));
-    LengthTables lt;
-    LPVS_TRY(lt.make(pl, s));
-    HostRootTab chirp;
-    if (blue) LPVS_TRY(chirp.make(2 * nfft, s));
-
+    StftTables t;
+    LPVS_TRY(stage_inputs(P, s_in, hwin, W, D, device, out, dev_out, s, b, t));
     Epi<T> E;
-    E.kind = kind; E.nfft = nfft; E.nbins = nbins; E.m1 = 1.0 / r; E.m2 = 2.0 / r;
-    E.W = et.w.as<float>(); E.blo = et.lo.as<int64_t>(); E.bhi = et.hi.as<int64_t>(); E.woff = et.off.as<int64_t>(); E.nmels = (int)nmels;
-    E.D = et.d.as<float>(); E.nmfcc = (int)nmfcc; E.out = dst; E.nframes = k; E.wslab = wslab.as<double>();
-
+    E.kind = kind; E.nfft = nfft; E.nbins = P.nbins; E.m1 = 1.0 / r; E.m2 = 2.0 / r;
+    E.W = t.et.w.as<float>(); E.blo = t.et.lo.as<int64_t>(); E.bhi = t.et.hi.as<int64_t>(); E.woff = t.et.off.as<int64_t>(); E.nmels = (int)nmels;
+    E.D = t.et.d.as<float>(); E.nmfcc = (int)nmfcc; E.out = b.dst; E.nframes = P.frames; E.wslab = b.wslab.template as<double>();
     FftJob<T> J;
-    J.in_mode = IN_SIGNAL; J.s = ds.p; J.win = dw.p; J.n = n; J.hop = hop; J.nframes = k;
-    if (blue) { J.chirp_in = 1; J.blue_n = nfft; J.chirp = chirp.tab; }
-    // the four-step's sequences (and the LDS fallback's split) do not see whole frames: flag the frames and take their max-abs exponents first
-    auto flag_frames = [&]() -> int32_t {
-        LPVS_TRY(fbad.alloc(sizeof(int32_t) * (size_t)k));
-        LPVS_TRY(fexp.alloc(sizeof(int32_t) * (size_t)k));
-        frame_bad_kernel<T><<<frame_blocks(k), kEpiThreads, 0, s>>>(ds.p, dw.p, n, hop, fbad.as<int32_t>(), fexp.as<int32_t>(), k);
-        LPVS_HIP(hipGetLastError());
-        J.fbad = fbad.as<int32_t>(); J.fexp = fexp.as<int32_t>();
-        return LPVS_OK;
-    };
+    J.in_mode = IN_SIGNAL; J.s = b.ds.p; J.win = b.dw.p; J.n = n; J.hop = P.hop; J.nframes = P.frames;
+    if (P.blue) { J.chirp_in = 1; J.blue_n = nfft; J.chirp = t.chirp.tab; }
 
+    // Kernels lie in the code object in the order they are first named.  The flag pass is named here, ahead of the FFT kernels, where it
+    // has always lain: with it behind them the same kernels ran the Bluestein four-step path 0.04 ms slower (profiles/stft_plan_ab.txt).
+    (void)&flag_frames<T>;
     LPVS_HIP(hipEventRecord(ev.e[1], s));   // device work from here on
-    // Bluestein: bhat = FFT_m(b), b_j = conj(chirp_|j|) for |j| < nfft (indices mod m)
-    if (blue) {
-        LPVS_TRY(bvec.alloc(sizeof(double2) * (size_t)m));
-        LPVS_TRY(bhat.alloc(sizeof(double2) * (size_t)m));
-        bluestein_b_kernel<<<(unsigned)std::min<int64_t>(ceil_div(m, 256), 65536), 256, 0, s>>>(chirp.tab, nfft, m, bvec.as<double2>());
-        LPVS_HIP(hipGetLastError());
-        FftJob<T> Bj;
-        Bj.in_mode = IN_GLOBAL; Bj.gin = bvec.as<double2>(); Bj.in_ps = m; Bj.in_es = 1;
-        if (lds) {
-            set_fft(Bj, (int)m, lt.r1, lt.t1.buf.as<double2>(), 1, 1, 1);
-            Bj.out_mode = OUT_GLOBAL; Bj.gout = bhat.as<double2>(); Bj.out_ps = m; Bj.out_es = 1;
-            LPVS_TRY(launch_fft(Bj, s));
-        } else {
-            LPVS_TRY(btmp.alloc(sizeof(double2) * (size_t)m));
-            LPVS_TRY(four_step(Bj, lt, 1, btmp.as<double2>(), bhat.as<double2>(), m, s, nullptr));
-        }
-    }
-
-    int path = 1, B = 1;
-    if (lds) {
-        const int64_t b = lds_b;
-        path = blue ? 3 : 1;
-        set_fft(J, (int)flen, lt.r1, lt.t1.buf.as<double2>(), 1, npair_all, 1);
-        if (blue) { J.post = POST_BLUESTEIN_LDS; J.bhat = bhat.as<double2>(); J.bhat_cs = 0; J.bhat_es = 1; J.blue_m = m; }
-        if (welch) {    // wS workgroups a launch, batch after batch into their slabs
-            J.B = (int)b; J.out_mode = OUT_EPI; J.epi = E;
-            const int64_t nbatch = ceil_div(npair_all, b);
-            for (int64_t b0 = 0; b0 < nbatch; b0 += wS) {
-                J.blk0 = b0;
-                stft_welch_kernel<T><<<(unsigned)std::min<int64_t>(wS, nbatch - b0), kThreads, 0, s>>>(J);
-                LPVS_HIP(hipGetLastError());
-            }
-            B = (int)b;
-        } else if (b >= 1) {   // everything in one launch
-            J.B = (int)b; J.out_mode = OUT_EPI; J.epi = E;
-            LPVS_TRY(launch_fft(J, s));
-            B = (int)b;
-        } else {        // the epilogue's LDS regions do not fit next to a frame pair: power columns to global, then the epilogue
-            LPVS_TRY(flag_frames());
-            LPVS_TRY(pwbuf.alloc(sizeof(double) * (size_t)(k * nbins)));
-            J.B = (int)std::max<int64_t>(1, std::min<int64_t>(kFftMax / flen, kMaxPairs));
-            J.out_mode = OUT_GLOBAL;
-            LPVS_TRY(zbuf.alloc(sizeof(double2) * (size_t)(npair_all * flen)));
-            J.gout = zbuf.as<double2>(); J.out_ps = flen; J.out_cs = 0; J.out_es = 1;
-            LPVS_TRY(launch_fft(J, s));
-            B = 0;
-            // Z (already through the Bluestein inverse when blue) -> power
-            split_power_kernel<double><<<frame_blocks(npair_all), kEpiThreads, 0, s>>>(zbuf.as<double2>(), flen, nfft, nbins, E.m1, E.m2, 0, RootTab{},
-                                                                                      1, 0, k, J.fbad, J.fexp, pwbuf.as<double>(), 0, npair_all);
-            LPVS_HIP(hipGetLastError());
-            const size_t shb = kind == LPVS_STFT_MFCC ? sizeof(double) * (size_t)(nmels + nmfcc) : 0;
-            epilogue_kernel<double, T><<<frame_blocks(k), kEpiThreads, shb, s>>>(pwbuf.as<double>(), 0, E, 0, k);
-            LPVS_HIP(hipGetLastError());
-        }
-    } else {
-        path = blue ? 4 : 2;
-        LPVS_TRY(flag_frames());
-        // chunks of frame pairs: tmp + Z of a chunk within the scratch budget (at least one pair)
-        const int64_t cp = std::max<int64_t>(1, std::min<int64_t>(npair_all, (int64_t)(kScratchBudget / per_pair)));
-        int64_t wbase = 0;   // slabs written by the chunks so far
-        LPVS_TRY(tmp.alloc(sizeof(double2) * (size_t)(cp * flen)));
-        LPVS_TRY(zbuf.alloc(sizeof(double2) * (size_t)(cp * flen)));
-        if (kind != LPVS_STFT_POWER && !welch) LPVS_TRY(pwbuf.alloc(sizeof(double) * (size_t)(2 * cp * nbins)));
-        for (int64_t p0 = 0; p0 < npair_all; p0 += cp) {
-            const int64_t np = std::min<int64_t>(cp, npair_all - p0), f0 = 2 * p0;
-            FftJob<T> A = J;
-            A.frame0 = f0;
-            if (blue) {
-                // forward FFT_m of the chirped frames (times bhat, conjugated, after pass 2) into Z, then the inverse (a forward FFT of
-                // the conjugate) back into Z; the split applies conj / m and the chirp
-                LPVS_TRY(four_step(A, lt, np, tmp.as<double2>(), zbuf.as<double2>(), flen, s, bhat.as<double2>()));
-                FftJob<T> I;
-                I.in_mode = IN_GLOBAL; I.gin = zbuf.as<double2>(); I.in_ps = flen;
-                LPVS_TRY(four_step(I, lt, np, tmp.as<double2>(), zbuf.as<double2>(), flen, s, nullptr));
-            } else
-                LPVS_TRY(four_step(A, lt, np, tmp.as<double2>(), zbuf.as<double2>(), flen, s, nullptr));
-            if (welch) {
-                const int64_t ns = ceil_div(np, kWelchChunkFrames / 2);
-                welch_split_sum_kernel<<<dim3((unsigned)ceil_div(nbins, kEpiThreads), (unsigned)ns), kEpiThreads, 0, s>>>(
-                    zbuf.as<double2>(), flen, nfft, nbins, E.m1, E.m2, blue, chirp.tab, m, f0, k, fbad.as<int32_t>(), fexp.as<int32_t>(), np,
-                    kWelchChunkFrames / 2, wslab.as<double>() + wbase * nbins);
-                LPVS_HIP(hipGetLastError());
-                wbase += ns;
-            } else if (kind == LPVS_STFT_POWER) {
-                split_power_kernel<T><<<frame_blocks(np), kEpiThreads, 0, s>>>(zbuf.as<double2>(), flen, nfft, nbins, E.m1, E.m2, blue, chirp.tab, m,
-                                                                               f0, k, fbad.as<int32_t>(), fexp.as<int32_t>(), dst, 0, np);
-                LPVS_HIP(hipGetLastError());
-            } else {
-                split_power_kernel<double><<<frame_blocks(np), kEpiThreads, 0, s>>>(zbuf.as<double2>(), flen, nfft, nbins, E.m1, E.m2, blue,
-                                                                                    chirp.tab, m, f0, k, fbad.as<int32_t>(), fexp.as<int32_t>(), pwbuf.as<double>(), f0, np);
-                LPVS_HIP(hipGetLastError());
-                const int64_t nfr = std::min<int64_t>(2 * np, k - f0);
-                const size_t shb = kind == LPVS_STFT_MFCC ? sizeof(double) * (size_t)(nmels + nmfcc) : 0;
-                epilogue_kernel<double, T><<<frame_blocks(nfr), kEpiThreads, shb, s>>>(pwbuf.as<double>(), f0, E, f0, nfr);
-                LPVS_HIP(hipGetLastError());
-            }
-        }
-    }
-    if (welch) {   // the slabs in a fixed pairwise tree (two levels a launch), then the mean
-        for (int64_t st = 1; st < wS; st *= 4) {
-            const int64_t groups = ceil_div(wS, 4 * st);
-            welch_tree_kernel<<<(unsigned)ceil_div(groups * nbins, kEpiThreads), kEpiThreads, 0, s>>>(wslab.as<double>(), wS, nbins, st, groups);
-            LPVS_HIP(hipGetLastError());
-        }
-        welch_finish_kernel<T><<<(unsigned)ceil_div(nbins, kEpiThreads), kEpiThreads, 0, s>>>(wslab.as<double>(), nbins, nfft, (double)k, twosided, dst);
-        LPVS_HIP(hipGetLastError());
-    }
+    if (P.blue) LPVS_TRY(bluestein_bhat(P, t, b, s));
+    LPVS_TRY(P.lds ? run_lds(P, J, E, t, b, s) : run_four_step(P, J, E, t, b, s));
+    if (P.welch) LPVS_TRY(welch_reduce(P, b, s));
     LPVS_HIP(hipEventRecord(ev.e[2], s));
-    if (!dev_out) LPVS_HIP(hipMemcpyAsync(out, dst, sizeof(T) * (size_t)nout, hipMemcpyDefault, s));
+    if (!dev_out) LPVS_HIP(hipMemcpyAsync(out, b.dst, P.out_bytes(sizeof(T)), hipMemcpyDefault, s));
     LPVS_HIP(hipEventRecord(ev.e[3], s));
     LPVS_HIP(hipStreamSynchronize(s));
-    float ms[3] = {0, 0, 0};
-    for (int i = 0; i < 3; ++i) LPVS_HIP(hipEventElapsedTime(&ms[i], ev.e[i], ev.e[i + 1]));
-    // [0] device work: Bluestein kernel, frame flags, FFTs, epilogue, [1] copy-out, [2] total (setup + [0] + [1]), [3] frames,
-    // [4] path (1 LDS, 2 four-step, 3 Bluestein in LDS, 4 Bluestein four-step), [5] FFT length, [6] frame pairs per workgroup (LDS
-    // paths; 0 on the LDS fallback through global power columns), [7] rows, [8] setup: host tables, band ranges and uploads
-    g_timing[0] = ms[1]; g_timing[1] = ms[2]; g_timing[2] = (double)ms[0] + ms[1] + ms[2]; g_timing[3] = (double)k; g_timing[4] = path;
-    g_timing[5] = (double)flen; g_timing[6] = B; g_timing[7] = (double)rows; g_timing[8] = ms[0];
-    // [9] LPVS_STFT_WELCH: the longest chain of dependent additions behind one bin, D = F - 1 + ceil(log2 S); [10] its slabs S (0 otherwise)
-    g_timing[9] = welch ? (double)(wF - 1 + wdepth) : 0.0; g_timing[10] = (double)wS;
-    return LPVS_OK;
+    return report_timing(P, ev);
 }
 
 template <class T>
