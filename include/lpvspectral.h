@@ -665,6 +665,38 @@ int32_t lpvs_cn_bands_f64(int64_t cn, int64_t Nf, int64_t nb, const double *Phi_
                           int32_t phase, double *Fl, double *Fu, double *Fm, double *Pl, double *Pu, double *Pm);
 int32_t lpvs_cn_last_timing(double *out, int32_t n);
 
+/* ---- g4  generalised Lomb-Scargle periodogram of non-uniformly sampled signals (extension: the reference has none; the floating-mean
+ * form of Zechmeister & Kuerster, A&A 496 (2009), without the time shift tau).
+ * y: N x ns column-major (ns signals sharing the times t), W: N non-negative weights or NULL (ones), normalised to w = W / sum W;
+ * f: Nf frequencies in cycles per unit of t.  The phase of (f_k, t_n) is phi = 2 pi (f_k t_n) with the EXACT product reduced to one
+ * cycle before any trigonometry.  Per frequency  C = sum w cos, S = sum w sin, C2 = sum w cos 2phi, S2 = sum w sin 2phi;  per signal
+ * Y = sum w y, YY = sum w y^2, YC = sum w y cos, YS = sum w y sin  (center_data: y is replaced by y - Y first; the weighted mean is
+ * formed on the device in a fixed order).  CC = (1 + C2)/2, SS = (1 - C2)/2, CS = S2/2;  fit_mean: YY -= Y^2, YC -= Y C, YS -= Y S,
+ * CC -= C^2, SS -= S^2, CS -= C S.  D = CC SS - CS^2,  p = (SS YC^2 + CC YS^2 - 2 CS YC YS) / D.
+ *   power (Nf x ns column-major): LPVS_LOMB_STANDARD p / YY in [0, 1]; LPVS_LOMB_PSD p N / 2 (unit weights: the classical
+ *     unnormalised periodogram).  A constant signal has standard power 0: with u = (N + 16) 2^-53 and R = sum w y^2 of the signal as
+ *     given, p / YY is replaced by 0 when YY <= (center_data: u^2 R) + (fit_mean: 3 u YY before the fit_mean term) -- the rounding
+ *     residue that centring and the subtraction of Y^2 leave of a constant signal.
+ *   coef (3 x Nf x ns: planes a, b, c, each Nf x ns column-major; may be NULL): y ~ c + a cos phi + b sin phi,
+ *     a = (SS YC - CS YS) / D, b = (CC YS - CS YC) / D, c = (the mean center_data removed) + (fit_mean: Y - a C - b S).
+ *   sums (HOST, (4 + 2 ns) Nf + 3 ns doubles, may be NULL): the rows C, S, C2, S2, YC_0, YS_0, YC_1, ... of Nf values, then Y_c, YY_c
+ *     per signal (of the centred signal, before the fit_mean terms), then the ns weighted means that center_data removed (as the
+ *     device formed them; computed also when they are not removed).
+ * Degenerate frequencies -- D <= 2^-40 (CC + SS)^2 with CC + SS taken before the fit_mean terms (f = 0, the Nyquist alias of a uniform
+ * record) -- give power and coefficients 0 and are counted.  A non-finite t, y, W or f, a negative weight or sum W = 0 -> LPVS_EARGUMENT.
+ * path: 0 auto, 1 direct sums (any grid), 2 non-uniform FFTs in blocks of modes (grids that are an arithmetic progression up to
+ * rounding; LPVS_EARGUMENT otherwise).  Both paths add in a fixed order: two calls give the same bits, and a signal's column does not
+ * depend on the other signals of the call.  t, y, W, power, coef: host or device memory; f, sums: host.
+ * lpvs_lombscargle_last_timing (the calling thread's last call), out[0..11]: path taken, blocks of family 1 (C, S, YC, YS) and of
+ * family 2 (C2, S2), fine grid (0: direct), degenerate frequencies, slabs of the direct sums, ms of the scan and the moments, the sums,
+ * the epilogue, the copy-out, total, whether the first-order term of the frequency residuals ran. */
+#define LPVS_LOMB_STANDARD 0
+#define LPVS_LOMB_PSD 1
+int32_t lpvs_lombscargle_f64(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const double *f, int64_t Nf,
+                             int32_t fit_mean, int32_t center_data, int32_t normalization, int32_t path, int32_t device,
+                             double *power, double *coef, double *sums);
+int32_t lpvs_lombscargle_last_timing(double *out, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif

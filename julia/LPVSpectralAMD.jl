@@ -20,7 +20,7 @@ export ls_spectral, tls_spectral, ls_sparse_spectral, ls_sparse_spectral_lpv, ls
        ls_cohere, ls_windowpsd_lpv, get_fourier_regressor, check_freq, default_freqs, Windows2, Windows3, mapwindows,
        SpectralExt, psd, reshape_params, ADMM, rect, hanning, autocov, autocor, isequidistant,
        melspectrogram, mfcc, mel, spectrogram, Spectrogram, MelSpectrogram, MFCC, freq, rand_cn, schedfunc,
-       Periodogram, welch_pgram, periodogram, compress, heatmap, predict, residual, fva
+       Periodogram, welch_pgram, periodogram, compress, heatmap, predict, residual, fva, lombscargle, lombscargle_last_timing
 
 const LIB = get(ENV, "LPVSPECTRAL_LIB", joinpath(@__DIR__, "..", "lpvspectral.jl_amd", "liblpvspectral.so"))
 
@@ -1068,6 +1068,37 @@ end
 function periodogram(s::AbstractVector{<:Real}; onesided::Bool = true, nfft::Int = _nextfastfft(length(s)), fs::Real = 1, window = nothing,
                      device::Integer = 0)                                                                 # DSP.periodogram (real s)
     _welch(s, length(s), 0, nfft, fs, window, onesided; device=device)
+end
+
+# ---- generalised Lomb-Scargle periodogram (extension: the non-uniform twin of periodogram; include/lpvspectral.h g4) ----------------
+const LOMB_NORMALIZATIONS = Dict(:standard => Int32(0), :psd => Int32(1))
+"""    lombscargle(y, t, f=default_freqs(t); W=nothing, fit_mean=true, center_data=true, normalization=:standard, path=:auto, coef=false)
+Every frequency fitted on its own, `y ≈ c + a cos 2πft + b sin 2πft` in weighted least squares; `y` a vector or an N × ns matrix of
+signals sharing `t`.  Returns `(power = Nf or Nf × ns, freq = f)` and, with `coef=true`, also `(a, b, c)`."""
+function lombscargle(y::AbstractVecOrMat{<:Real}, t::AbstractVector{<:Real}, f::AbstractVector{<:Real}=default_freqs(t); W=nothing, fit_mean::Bool=true,
+                     center_data::Bool=true, normalization::Symbol=:standard, path::Symbol=:auto, device::Integer=0, coef::Bool=false)
+    tv, fv = Vector{Float64}(t), Vector{Float64}(f)
+    N, Nf, ns = length(tv), length(fv), size(y, 2)
+    @assert size(y, 1) == N "y has to be as long as the sampling points"
+    yv = Matrix{Float64}(reshape(y, N, ns))
+    Wv = W === nothing ? Float64[] : Vector{Float64}(W)
+    @assert W === nothing || length(Wv) == N "W has to be as long as the sampling points"
+    Wp = W === nothing ? Ptr{Float64}(C_NULL) : pointer(Wv)
+    power = zeros(Nf, ns)
+    cfv = coef ? zeros(Nf, ns, 3) : Float64[]
+    cfp = coef ? pointer(cfv) : Ptr{Float64}(C_NULL)
+    GC.@preserve yv tv Wv fv power cfv check(@ccall LIB.lpvs_lombscargle_f64(yv::Ptr{Float64}, Int64(ns)::Int64, tv::Ptr{Float64}, Int64(N)::Int64, Wp::Ptr{Float64},
+        fv::Ptr{Float64}, Int64(Nf)::Int64, Int32(fit_mean)::Int32, Int32(center_data)::Int32, LOMB_NORMALIZATIONS[normalization]::Int32, EVAL_PATHS[path]::Int32,
+        Int32(device)::Int32, power::Ptr{Float64}, cfp::Ptr{Float64}, C_NULL::Ptr{Float64})::Int32)
+    shaped(A) = y isa AbstractVector ? vec(A) : A
+    P = (power = shaped(power), freq = fv)
+    coef ? (P, (shaped(cfv[:, :, 1]), shaped(cfv[:, :, 2]), shaped(cfv[:, :, 3]))) : P
+end
+function lombscargle_last_timing()
+    tm = zeros(12)
+    GC.@preserve tm check(@ccall LIB.lpvs_lombscargle_last_timing(tm::Ptr{Float64}, Int32(12)::Int32)::Int32)
+    (path=Int(tm[1]), blocks=(Int(tm[2]), Int(tm[3])), nf=Int(tm[4]), degenerate=Int(tm[5]), slabs=Int(tm[6]), moments_ms=tm[7], sums_ms=tm[8], epilogue_ms=tm[9],
+     copy_ms=tm[10], total_ms=tm[11], twin=tm[12] != 0)
 end
 
 _quantile_pair(q::Number) = (q = q < 0.5 ? q : 1 - q; (Float64(q), Float64(1 - q)))                      # src/plotting.jl:39-44

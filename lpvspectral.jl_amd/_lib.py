@@ -186,6 +186,8 @@ SIGNATURES = {
     "lpvs_fourier_eval_f64": (_I32, [_P, _P, _I64, _P, _I64, _P, _P, _I64, _I32, _I32, _P, _P]),
     "lpvs_lpv_eval_f64": (_I32, [_P, _P, _I64, _P, _I64, _I64, _I32, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _P, _P]),
     "lpvs_eval_last_timing": (_I32, [_P, _I32]),
+    "lpvs_lombscargle_f64": (_I32, [_P, _I64, _P, _I64, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    "lpvs_lombscargle_last_timing": (_I32, [_P, _I32]),
 }
 
 _lib = None

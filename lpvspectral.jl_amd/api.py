@@ -2058,6 +2058,78 @@ def heatmap(S, compression=(0.005, 1), device=0):
     return S.time, axis, z
 
 
+_LOMB_NORMALIZATIONS = {"standard": 0, "psd": 1}
+
+
+def _lomb_signals(y):
+    """Signals as what the library reads -- N x ns column-major -- and (N, ns, whether the caller gave one vector)."""
+    y = _f64_arg(y)
+    if _lib.is_device_array(y):
+        single = y.dim() == 1
+        N, ns = int(y.shape[0]), 1 if single else int(y.shape[1])
+        return (y if single else y.t().contiguous()), N, ns, single      # (ns, N) row-major = N x ns column-major
+    ya = _host(y)
+    single = ya.ndim == 1
+    ya = ya.reshape(ya.shape[0], -1)
+    return np.asfortranarray(ya), ya.shape[0], ya.shape[1], single
+
+
+def lombscargle(y, t, f=None, W=None, fit_mean=True, center_data=True, normalization="standard", path="auto", device=0, coef=False, return_sums=False):
+    """Generalised Lomb-Scargle periodogram of non-uniformly sampled signals (extension; the floating-mean form of Zechmeister &
+    Kürster 2009): every frequency is fitted on its own, ``y ≈ c + a cos 2πft + b sin 2πft`` in weighted least squares.
+
+    ``y``: (N,) or (N, ns) signals sharing the times ``t``; ``f``: frequencies in cycles per unit of ``t`` (``None``:
+    ``default_freqs(t)``); ``W``: non-negative weights (``None``: ones), normalised to sum 1.  ``fit_mean``: the constant is fitted
+    along with the sinusoid at every frequency; ``center_data``: the weighted mean is removed first.  ``normalization``:
+    ``"standard"`` (``p / YY`` in [0, 1]) or ``"psd"`` (``p N / 2``: with unit weights the classical unnormalised periodogram, what
+    ``scipy.signal.lombscargle`` returns).  ``path``: ``"auto"``, ``"direct"`` (any frequency grid) or ``"nufft"`` (non-uniform FFTs in
+    blocks of modes, for grids that are an arithmetic progression up to rounding; ValueError otherwise).  Phases are those of the exact
+    products ``f t``.  Frequencies where the fit is degenerate (``f = 0``, the Nyquist alias of a uniform record) give 0.
+
+    Returns a :class:`Periodogram` (``power``: (Nf,) or (Nf, ns)); with ``coef=True`` also ``(a, b, c)``, with ``return_sums=True``
+    also the raw sums as a dict (with ``"mean"``: the weighted means as the device formed them).  A constant signal has standard power 0
+    (a ``YY`` within rounding of 0 counts as 0).  Float32 inputs are widened; a non-finite input, a negative weight or a zero weight sum raise
+    ValueError."""
+    if path not in _EVAL_PATHS:
+        raise ValueError(f"path: unknown value {path!r} (known: {sorted(_EVAL_PATHS)})")
+    if normalization not in _LOMB_NORMALIZATIONS:
+        raise ValueError(f"normalization: unknown value {normalization!r} (known: {sorted(_LOMB_NORMALIZATIONS)})")
+    fa = np.ascontiguousarray(np.ravel(_host(default_freqs(t) if f is None else f)).astype(np.float64))
+    Nf = len(fa)
+    ys, N, ns, single = _lomb_signals(y)
+    ky, py, ny = as_f64(ys)
+    kt, pt, nt = as_f64(_f64_arg(t))
+    if nt != N:
+        raise ValueError(f"y has {N} samples, t has {nt}")
+    kw, pw, nw = as_f64(_f64_arg(W))
+    if W is not None and nw != N:
+        raise ValueError(f"y has {N} samples, W has {nw}")
+    power = np.zeros((Nf, ns), order="F")
+    co = np.zeros((3, ns, Nf)) if coef else None                           # [plane][signal][frequency] = planes of Nf x ns column-major
+    sums = np.zeros((4 + 2 * ns) * Nf + 3 * ns) if return_sums else None
+    check(lib().lpvs_lombscargle_f64(py, ns, pt, N, pw, out_ptr(fa), Nf, int(bool(fit_mean)), int(bool(center_data)), _LOMB_NORMALIZATIONS[normalization],
+                                     _EVAL_PATHS[path], int(device), out_ptr(power), out_ptr(co) if coef else None, out_ptr(sums) if return_sums else None))
+    res = [Periodogram(power[:, 0].copy() if single else power, fa)]
+    if coef:
+        res.append(tuple((co[i, 0].copy() if single else np.asfortranarray(co[i].T)) for i in range(3)))
+    if return_sums:
+        nr = (4 + 2 * ns) * Nf
+        rows, mom, mean = sums[:nr].reshape(4 + 2 * ns, Nf), sums[nr:nr + 2 * ns].reshape(ns, 2), sums[nr + 2 * ns:]
+        res.append({"C": rows[0], "S": rows[1], "C2": rows[2], "S2": rows[3], "YC": rows[4::2], "YS": rows[5::2], "Y": mom[:, 0], "YY": mom[:, 1],
+                    "mean": mean})
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+def lombscargle_last_timing():
+    """Plan and timing of the calling thread's last :func:`lombscargle`: the path taken, the blocks per family and the fine grid of the
+    transforms, the degenerate frequencies, the slabs of the direct sums, milliseconds per phase."""
+    o = np.zeros(12)
+    check(lib().lpvs_lombscargle_last_timing(out_ptr(o), 12))
+    return {"path": {1: "direct", 2: "nufft"}.get(int(o[0]), "none"), "blocks": (int(o[1]), int(o[2])), "nf": int(o[3]), "degenerate": int(o[4]),
+            "slabs": int(o[5]), "moments_ms": float(o[6]), "sums_ms": float(o[7]), "epilogue_ms": float(o[8]), "copy_ms": float(o[9]),
+            "total_ms": float(o[10]), "twin": bool(o[11])}
+
+
 def compress_last_timing():
     """Plan and HIP-event times (ms) of this thread's last compress / heatmap call."""
     o = np.zeros(5)

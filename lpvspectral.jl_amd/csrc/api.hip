@@ -1396,6 +1396,154 @@ int32_t lpvs_eval_last_timing(double *out, int32_t n) {
     return LPVS_OK;
 }
 
+// ---- Lomb-Scargle periodogram (lomb.hip; the decisions: lomb_plan.h) --------------------------------------------------------------------
+// what lpvs_lombscargle_last_timing reports of the calling thread's last call: [0] path taken (1 direct, 2 transforms), [1], [2] blocks of
+// family 1 / family 2 (0: direct), [3] fine grid (0: direct), [4] degenerate frequencies, [5] slabs of the direct sums (0: transforms),
+// ms of [6] staging, the scan and the moments, [7] the sums, [8] the epilogue, [9] the copy-out, [10] total, [11] the first-order term ran
+static thread_local double g_lomb_timing[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+static int32_t lomb_impl(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const std::vector<double> &hf, bool fit_mean, bool center,
+                         bool psd, int32_t path, int32_t device, double *power, double *coef, double *sums_out) {
+    const int64_t Nf = (int64_t)hf.size(), nrow = 4 + 2 * ns;
+    if (lpvs_device_count() == 0) { set_error("no HIP device visible (the gfx950 path has no CPU fallback)"); return LPVS_EDEVICE; }
+    LPVS_HIP(hipSetDevice(device));
+    hipStream_t s = nullptr;
+    Events<5> ev;
+    for (auto &e : ev.e) LPVS_HIP(hipEventCreate(&e));
+    DevArg dt, dy, dW; DevOut dpower, dcoef;
+    DevBuf dw, dwy, dsmall, dpart, dsums, dfreq, dslab, dWt, dwork, dtab, deps;
+    DrainOnExit drain(s);
+    LPVS_HIP(hipEventRecord(ev.e[0], s));
+    LPVS_TRY(dt.set(t, N, s));
+    LPVS_TRY(dy.set(y, N * ns, s));
+    if (W) LPVS_TRY(dW.set(W, N, s));
+    LPVS_TRY(dpower.set(power, Nf * ns));
+    if (coef) LPVS_TRY(dcoef.set(coef, 3 * Nf * ns));
+    // small device record: [0] sum W, [1 .. ns] the weighted means, then Y_c, YY_c per signal (2 ns) and sum w y_c^2 of the signals as
+    // given (ns), then two ints (flags, degenerate count)
+    const size_t nsmall = (size_t)(1 + 4 * ns);
+    LPVS_TRY(dsmall.alloc(sizeof(double) * (nsmall + 1)));
+    double *sumW_dev = dsmall.as<double>(), *mean_dev = sumW_dev + 1, *mom_dev = mean_dev + ns;
+    int *flags_dev = reinterpret_cast<int *>(sumW_dev + nsmall), *ndeg_dev = flags_dev + 1;
+    const int64_t nsum = lomb_sum_slabs(N);
+    LPVS_TRY(dpart.alloc(sizeof(double) * (size_t)(3 * ns * nsum)));
+    LPVS_TRY(launch_lomb_scan(dt.p, dy.p, dW.p, N, ns, flags_dev, dpart.as<double>(), sumW_dev, s));
+    double sumW = 0; int flags = 0;
+    LPVS_TRY(copy_from_device(&sumW, sumW_dev, sizeof(double), s));
+    LPVS_TRY(copy_from_device(&flags, flags_dev, sizeof(int), s));
+    if (flags & 1) { set_error("lombscargle: t, y or W holds a value that is not finite"); return LPVS_EARGUMENT; }
+    if (flags & 2) { set_error("lombscargle: a weight is negative"); return LPVS_EARGUMENT; }
+    if (!(sumW > 0.0) || !std::isfinite(sumW)) { set_error("lombscargle: the weights sum to %g", sumW); return LPVS_EARGUMENT; }
+    LPVS_TRY(dw.alloc(sizeof(double) * (size_t)N));
+    LPVS_TRY(dwy.alloc(sizeof(double) * (size_t)(N * ns)));
+    LPVS_TRY(launch_lomb_moments(dy.p, dW.p, N, ns, sumW, center, dw.as<double>(), dwy.as<double>(), mean_dev, mom_dev, dpart.as<double>(), s));
+    // the path
+    LombGrid lg;
+    double tam = 0;
+    if (lomb_needs_admission(path, N, Nf)) {         // not when the call goes direct whatever the grid is
+        double tlo, thi;
+        LPVS_TRY(device_minmax(dt.p, N, &tlo, &thi, &tam, s));
+        lg = lomb_admit(hf, tam);
+    }
+    const int taken = lomb_choose_path(path, lg.ok, N, Nf);
+    if (taken == kLombPathRefused) {
+        if (path != kLombPathNufft) set_error("path must be 0 (auto), 1 (direct) or 2 (NUFFT), got %d", path);
+        else set_error("path = NUFFT but the frequency grid is not an arithmetic progression up to rounding (max|eps| = %.3g)", lg.emax);
+        return LPVS_EARGUMENT;
+    }
+    LPVS_TRY(dsums.alloc(sizeof(double) * (size_t)(nrow * Nf)));
+    LPVS_HIP(hipEventRecord(ev.e[1], s));
+    int64_t nblocks = 0, nslab = 0; int nf1 = 0; bool twin = false;
+    if (taken == kLombPathDirect) {
+        const LombTiling tl = lomb_tiling(N, Nf, ns);
+        nslab = tl.nslab;
+        LPVS_TRY(dfreq.alloc(sizeof(double) * (size_t)Nf));
+        LPVS_TRY(copy_to_device(dfreq.p, hf.data(), sizeof(double) * (size_t)Nf, s));
+        LPVS_TRY(dslab.alloc(sizeof(double) * (size_t)(tl.nslab * nrow * Nf)));
+        LPVS_TRY(launch_lomb_direct(dt.p, dw.as<double>(), dwy.as<double>(), N, ns, dfreq.as<double>(), Nf, tl, dslab.as<double>(), dsums.as<double>(), s));
+    } else {
+        const char *knob = experiment_env("LPVS_LOMB_BLOCK");
+        const int L = lomb_block_len(knob ? atoll(knob) : 0);
+        const std::vector<LombBlock> blocks = lomb_blocks(hf, L);
+        const std::vector<double> heps = lomb_block_residuals(hf, lg, L);
+        for (double e : heps) twin = twin || e != 0.0;
+        nblocks = (int64_t)blocks.size();
+        const int nf = lomb_fine_grid(Nf, L), Lmax = (int)(Nf < L ? Nf : L);
+        nf1 = nf;
+        const int gmax = (int)(ns < kLombGroupSignals ? ns : kLombGroupSignals), nqmax = lomb_weight_vectors(1, gmax, true);
+        LPVS_TRY(deps.alloc(sizeof(double) * (size_t)Nf));
+        LPVS_TRY(copy_to_device(deps.p, heps.data(), sizeof(double) * (size_t)Nf, s));
+        LPVS_TRY(dWt.alloc(sizeof(double) * (size_t)N * (size_t)nqmax));
+        LPVS_TRY(dtab.alloc(sizeof(double) * 4 * (size_t)Lmax * (size_t)nqmax));
+        LPVS_TRY(dwork.alloc(nufft_work_bytes(N, Lmax, nqmax)));           // (its fine grid is nf: that of the longest block)
+        // family 1: step D, the weights w and w y_c of a group of signals; family 2: step 2D, w alone.  One set of sample coordinates per family.
+        for (int family = 1; family <= 2; ++family) {
+            const double w_hi = family == 1 ? lg.w1_hi : lg.w2_hi, w_lo = family == 1 ? lg.w1_lo : lg.w2_lo, fscale = family == 1 ? 1.0 : 2.0;
+            bool have_coords = false;
+            const int64_t ngroups = family == 1 ? lomb_signal_groups(ns) : 1;
+            for (int64_t grp = 0; grp < ngroups; ++grp) {
+                const int c0 = (int)(grp * kLombGroupSignals);
+                const int g = family == 1 ? (int)(ns - c0 < kLombGroupSignals ? ns - c0 : kLombGroupSignals) : 0;
+                for (const LombBlock &b : blocks) {
+                    const int nq = lomb_weight_vectors(family, g, b.prephase), nre = 1 + g;
+                    LPVS_TRY(launch_lomb_prephase(dt.p, dw.as<double>(), dwy.as<double>(), N, c0, g, fscale * b.base, b.prephase, dWt.as<double>(), s));
+                    const int32_t rc = launch_nufft_tab(dt.p, nullptr, N, tam, dWt.as<double>(), nq, nq, w_hi, w_lo, 0, b.count, nf, have_coords, dwork.p,
+                                                        dtab.as<double>(), s);
+                    if (rc == kNufftNonFinite) { set_error("lombscargle: a weight vector of the transform is not finite"); return LPVS_ENUMERIC; }
+                    LPVS_TRY(rc);
+                    have_coords = true;
+                    LPVS_TRY(launch_lomb_combine(dtab.as<double>(), nq, nre, b.prephase, b.count, b.k0, Nf, deps.as<double>(), fscale, family == 1 ? -1 : 2, c0,
+                                                 dsums.as<double>(), s));
+                }
+            }
+        }
+    }
+    LPVS_HIP(hipEventRecord(ev.e[2], s));
+    LPVS_TRY(launch_lomb_epilogue(dsums.as<double>(), Nf, ns, mom_dev, mean_dev, fit_mean, center, psd, N, dpower.p, coef ? dcoef.p : nullptr, ndeg_dev, s));
+    LPVS_HIP(hipEventRecord(ev.e[3], s));
+    int ndeg = 0;
+    LPVS_TRY(copy_from_device(&ndeg, ndeg_dev, sizeof(int), s));
+    if (sums_out) {
+        LPVS_TRY(copy_from_device(sums_out, dsums.p, sizeof(double) * (size_t)(nrow * Nf), s));
+        LPVS_TRY(copy_from_device(sums_out + nrow * Nf, mom_dev, sizeof(double) * (size_t)(2 * ns), s));
+        LPVS_TRY(copy_from_device(sums_out + nrow * Nf + 2 * ns, mean_dev, sizeof(double) * (size_t)ns, s));
+    }
+    LPVS_TRY(dpower.finish(s));
+    if (coef) LPVS_TRY(dcoef.finish(s));
+    LPVS_HIP(hipEventRecord(ev.e[4], s));
+    LPVS_HIP(hipStreamSynchronize(s));
+    float ms[4] = {0, 0, 0, 0}, total = 0;
+    for (int i = 0; i < 4; ++i) LPVS_HIP(hipEventElapsedTime(&ms[i], ev.e[i], ev.e[i + 1]));
+    LPVS_HIP(hipEventElapsedTime(&total, ev.e[0], ev.e[4]));
+    const bool nu = taken == kLombPathNufft;
+    g_lomb_timing[0] = taken; g_lomb_timing[1] = (double)nblocks; g_lomb_timing[2] = (double)nblocks; g_lomb_timing[3] = nu ? nf1 : 0;
+    g_lomb_timing[4] = ndeg; g_lomb_timing[5] = (double)nslab;
+    g_lomb_timing[6] = ms[0]; g_lomb_timing[7] = ms[1]; g_lomb_timing[8] = ms[2]; g_lomb_timing[9] = ms[3]; g_lomb_timing[10] = total;
+    g_lomb_timing[11] = nu && twin ? 1 : 0;
+    return LPVS_OK;
+}
+
+int32_t lpvs_lombscargle_f64(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const double *f, int64_t Nf, int32_t fit_mean,
+                             int32_t center_data, int32_t normalization, int32_t path, int32_t device, double *power, double *coef, double *sums) {
+    try {
+        if (!y || !t || !f || !power) { set_error("NULL argument"); return LPVS_EARGUMENT; }
+        if (N <= 0 || Nf <= 0 || ns <= 0 || ns > 65535) { set_error("need N > 0, Nf > 0 and 1 <= ns <= 65535 (N = %lld, Nf = %lld, ns = %lld)", (long long)N, (long long)Nf, (long long)ns); return LPVS_EARGUMENT; }
+        if (Nf > ((int64_t)1 << 24)) { set_error("%lld frequencies are too many", (long long)Nf); return LPVS_EUNSUPPORTED; }
+        if (path < kLombPathAuto || path > kLombPathNufft) { set_error("path must be 0 (auto), 1 (direct) or 2 (NUFFT), got %d", path); return LPVS_EARGUMENT; }
+        if (normalization != LPVS_LOMB_STANDARD && normalization != LPVS_LOMB_PSD) { set_error("normalization must be 0 (standard) or 1 (psd), got %d", normalization); return LPVS_EARGUMENT; }
+        if (is_device_ptr(f) || (sums && is_device_ptr(sums))) { set_error("lombscargle: f and sums are host memory"); return LPVS_EARGUMENT; }
+        std::vector<double> hf(f, f + Nf);
+        for (double v : hf)
+            if (!std::isfinite(v)) { set_error("lombscargle: a frequency is not finite"); return LPVS_EARGUMENT; }
+        return lomb_impl(y, ns, t, N, W, hf, fit_mean != 0, center_data != 0, normalization == LPVS_LOMB_PSD, path, device, power, coef, sums);
+    } catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
+}
+
+int32_t lpvs_lombscargle_last_timing(double *out, int32_t n) {
+    if (!out || n < 0) { set_error("NULL argument"); return LPVS_EARGUMENT; }
+    for (int32_t k = 0; k < n && k < 12; ++k) out[k] = g_lomb_timing[k];
+    return LPVS_OK;
+}
+
 int32_t lpvs_problem_create_lpv_rows_f64(const double *Y, int64_t ns, const double *X, const double *V, int64_t N_local, const double *w,
                                          int64_t Nf, int64_t Nv, int32_t normalize, int32_t coulomb, const double *ranges4,
                                          int32_t device, lpvs_problem **out) {

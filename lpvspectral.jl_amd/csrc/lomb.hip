@@ -1,0 +1,341 @@
+// lomb.hip -- the generalised Lomb-Scargle periodogram of non-uniformly sampled signals (lombscargle; hand-written HIP, gfx950).
+//
+// Per frequency f_k and signal c, with normalised weights w = W / sum W and phases phi = 2 pi f_k t_n:
+//   C = sum w cos, S = sum w sin, C2 = sum w cos 2phi, S2 = sum w sin 2phi, YC = sum w y cos, YS = sum w y sin     (4 + 2 ns non-uniform Fourier sums)
+// and the 2x2 / 3x3 least-squares fit of y ~ c + a cos + b sin in closed form (lomb_epilogue_kernel; include/lpvspectral.h has the formulas).
+//
+// PHASES.  The phase of (f, t) is that of the EXACT product f t: p = fl(f t), e = fma(f, t, -p) (error-free), and the turns
+// (p - rint(p)) + e go to sincospi -- nothing grows with |f t|.
+//
+// DIRECT PATH (any grid): lomb_direct_kernel.  A workgroup = 64 frequencies x 4 sample lanes (lomb_plan.h: lomb_tiling) walks one slab of
+// samples, staged through LDS 256 at a time; one sincospi per (sample, frequency), the double angle from c^2 - s^2 and 2 s c; 4 + 2 ts
+// accumulators in registers.  The four lanes are added as (0 + 1) + (2 + 3), the slabs by a pairwise tree (lomb_slab_sum_kernel): a fixed
+// order, so two calls give the same bits, and a signal's sums do not depend on which other signals ride along.
+//
+// TRANSFORM PATH (progressions, cut into blocks by lomb_plan.h): lomb_prephase_kernel forms a block's weight vectors
+// w e^{i 2 pi base t}, w y_c e^{i 2 pi base t} (real and imaginary parts as separate real vectors), nufft.hip's spreading and mode
+// extraction (launch_nufft_tab, as it is) transform them, and lomb_combine_kernel puts real and imaginary transforms back together,
+// adds the first-order term of the frequency residuals from the t-weighted twins, and files the block's sums.
+//
+// MOMENTS: sum W, the weighted means and YY by slabs of 256 samples and a fixed tree (lomb_scan / lomb_mean / lomb_center kernels).
+#include "lpvs_internal.h"
+#include "lomb_plan.h"
+
+namespace lpvs {
+namespace {
+
+constexpr int LB_TF = kLombFreqTile, LB_LANES = kLombSampleLanes, LB_STAGE = kLombStage;
+static_assert(LB_TF * LB_LANES == 256 && LB_STAGE == 256 && kLombSumBlock == 256, "the kernels are written for 256 threads");
+
+// sum over the workgroup's 256 threads in a pairwise tree (every thread calls it)
+__device__ inline double lomb_block_sum(double v, double *red) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + s];
+        __syncthreads();
+    }
+    const double r = red[0];
+    __syncthreads();
+    return r;
+}
+
+// cos, sin of 2 pi f t from the exact product
+__device__ inline void lomb_sincos(double f, double t, double *sn, double *cs) {
+    const double p = f * t, e = fma(f, t, -p);
+    const double r = (p - rint(p)) + e;               // turns in [-1/2, 1/2] (+ e); p - rint(p) is exact
+    sincospi(2.0 * r, sn, cs);
+}
+
+// ---- moments ---------------------------------------------------------------------------------------------------------------------------
+// flags: bit 0 a non-finite t, y or W, bit 1 a negative weight (integer OR: order-free); part[workgroup] = sum of W over its 256 samples
+__global__ void __launch_bounds__(256)
+lomb_scan_kernel(const double *__restrict__ t, const double *__restrict__ y, const double *__restrict__ W, int64_t N, int ns, int *__restrict__ flags,
+                 double *__restrict__ part) {
+    __shared__ double red[256];
+    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    double wv = 0.0;
+    int bad = 0;
+    if (n < N) {
+        const double inf = 1.0 / 0.0;
+        wv = W ? W[n] : 1.0;
+        if (!(fabs(t[n]) < inf) || !(fabs(wv) < inf)) bad |= 1;
+        for (int c = 0; c < ns; ++c)
+            if (!(fabs(y[(int64_t)c * N + n]) < inf)) bad |= 1;
+        if (wv < 0.0) bad |= 2;
+    }
+    if (bad) atomicOr(flags, bad);
+    const double s = lomb_block_sum(bad ? 0.0 : wv, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+// out[row] = sum of part[row][0 .. nslab): thread t the slabs t, t + 256, ... ascending, then the tree
+__global__ void __launch_bounds__(256) lomb_tree_kernel(const double *__restrict__ part, int64_t nslab, double *__restrict__ out) {
+    __shared__ double red[256];
+    const double *p = part + (int64_t)blockIdx.x * nslab;
+    double s = 0.0;
+    for (int64_t i = threadIdx.x; i < nslab; i += 256) s = s + p[i];
+    const double r = lomb_block_sum(s, red);
+    if (threadIdx.x == 0) out[blockIdx.x] = r;
+}
+// w = W / sum W (signal 0's workgroups write it); part[c][workgroup] = sum of w y_c
+__global__ void __launch_bounds__(256)
+lomb_mean_kernel(const double *__restrict__ y, const double *__restrict__ W, int64_t N, double sumW, double *__restrict__ w, double *__restrict__ part,
+                 int64_t nslab) {
+    __shared__ double red[256];
+    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int c = blockIdx.y;
+    double v = 0.0;
+    if (n < N) {
+        const double wv = (W ? W[n] : 1.0) / sumW;
+        if (c == 0) w[n] = wv;
+        v = wv * y[(int64_t)c * N + n];
+    }
+    const double s = lomb_block_sum(v, red);
+    if (threadIdx.x == 0) part[(int64_t)c * nslab + blockIdx.x] = s;
+}
+// wy[c][n] = w (y_c - m_c), m_c = the weighted mean (center) or 0; part[2 c + {0, 1}][workgroup] = sum w yc, sum w yc^2 and
+// part[2 ns + c][workgroup] = sum w y_c^2 of the signal as given (the scale of the constant-signal rule)
+__global__ void __launch_bounds__(256)
+lomb_center_kernel(const double *__restrict__ y, const double *__restrict__ w, int64_t N, const double *__restrict__ mean, int center,
+                   double *__restrict__ wy, double *__restrict__ part, int64_t nslab) {
+    __shared__ double red[256];
+    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int c = blockIdx.y;
+    const double m = center ? mean[c] : 0.0;
+    double v1 = 0.0, v2 = 0.0, v3 = 0.0;
+    if (n < N) {
+        const double yr = y[(int64_t)c * N + n], yc = yr - m;
+        v1 = w[n] * yc;
+        v2 = v1 * yc;
+        v3 = (w[n] * yr) * yr;
+        wy[(int64_t)c * N + n] = v1;
+    }
+    const double s1 = lomb_block_sum(v1, red), s2 = lomb_block_sum(v2, red), s3 = lomb_block_sum(v3, red);
+    if (threadIdx.x == 0) {
+        part[(int64_t)(2 * c) * nslab + blockIdx.x] = s1;
+        part[(int64_t)(2 * c + 1) * nslab + blockIdx.x] = s2;
+        part[(int64_t)(2 * gridDim.y + c) * nslab + blockIdx.x] = s3;
+    }
+}
+
+// ---- direct path: workgroup (tile of 64 frequencies, slab of samples, block of TS signals) ---------------------------------------------
+// part[(slab nrow + row) Nf + k], nrow = 4 + 2 ns: rows C, S, C2, S2 (written by signal block 0), then YC_c, YS_c
+template <int TS>
+__global__ void __launch_bounds__(256)
+lomb_direct_kernel(const double *__restrict__ t, const double *__restrict__ w, const double *__restrict__ wy, int64_t N, int ns, const double *__restrict__ f,
+                   int64_t Nf, int64_t slab_samples, double *__restrict__ part) {
+    constexpr int NA = 4 + 2 * TS;
+    __shared__ double st[LB_STAGE], sw[LB_STAGE], swy[TS][LB_STAGE];
+    __shared__ double red[NA][LB_LANES][LB_TF];
+    const int fl = threadIdx.x % LB_TF, lane = threadIdx.x / LB_TF;
+    const int64_t k = (int64_t)blockIdx.x * LB_TF + fl;
+    const int c0 = blockIdx.z * TS;
+    const double fv = k < Nf ? f[k] : 0.0;
+    const int64_t n0 = (int64_t)blockIdx.y * slab_samples, n1 = n0 + slab_samples < N ? n0 + slab_samples : N;
+    double acc[NA];
+#pragma unroll
+    for (int a = 0; a < NA; ++a) acc[a] = 0.0;
+    for (int64_t base = n0; base < n1; base += LB_STAGE) {
+        const int cnt = (int)(n1 - base < LB_STAGE ? n1 - base : LB_STAGE);
+        __syncthreads();                                                   // the previous stage has been walked
+        if ((int)threadIdx.x < cnt) {
+            const int64_t n = base + threadIdx.x;
+            st[threadIdx.x] = t[n];
+            sw[threadIdx.x] = w[n];
+#pragma unroll
+            for (int c = 0; c < TS; ++c) swy[c][threadIdx.x] = c0 + c < ns ? wy[(int64_t)(c0 + c) * N + n] : 0.0;
+        }
+        __syncthreads();
+        for (int i = lane; i < cnt; i += LB_LANES) {
+            double sn, cs;
+            lomb_sincos(fv, st[i], &sn, &cs);
+            const double wv = sw[i];
+            const double c2 = fma(cs, cs, -(sn * sn)), s2 = 2.0 * (sn * cs);
+            acc[0] = fma(wv, cs, acc[0]);
+            acc[1] = fma(wv, sn, acc[1]);
+            acc[2] = fma(wv, c2, acc[2]);
+            acc[3] = fma(wv, s2, acc[3]);
+#pragma unroll
+            for (int c = 0; c < TS; ++c) {
+                const double v = swy[c][i];
+                acc[4 + 2 * c] = fma(v, cs, acc[4 + 2 * c]);
+                acc[5 + 2 * c] = fma(v, sn, acc[5 + 2 * c]);
+            }
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < NA; ++a) red[a][lane][fl] = acc[a];
+    __syncthreads();
+    if (lane != 0 || k >= Nf) return;
+    const int nrow = 4 + 2 * ns;
+    double *o = part + (int64_t)blockIdx.y * nrow * Nf + k;
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+        const double v = (red[a][0][fl] + red[a][1][fl]) + (red[a][2][fl] + red[a][3][fl]);
+        if (a < 4) { if (blockIdx.z == 0) o[(int64_t)a * Nf] = v; }
+        else if (c0 + (a - 4) / 2 < ns) o[(int64_t)(4 + 2 * c0 + (a - 4)) * Nf] = v;
+    }
+}
+
+// sums[e] = pairwise tree over the slabs of part[slab][e], e < nrow Nf: slabs 2i and 2i + 1 first, then pairs of pairs, ... (a binary
+// counter of partial sums), what is left over added from the smallest piece up
+__global__ void __launch_bounds__(256) lomb_slab_sum_kernel(const double *__restrict__ part, int64_t nslab, int64_t count, double *__restrict__ sums) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= count) return;
+    double stack[12];                                                      // nslab <= kLombMaxSlabs = 2^10
+    for (int64_t i = 0; i < nslab; ++i) {
+        double v = part[i * count + e];
+        int b = 0;
+        for (; (i >> b) & 1; ++b) v = stack[b] + v;
+        stack[b] = v;
+    }
+    double r = 0.0;
+    bool have = false;
+    for (int b = 0; b < 12; ++b)
+        if ((nslab >> b) & 1) { r = have ? stack[b] + r : stack[b]; have = true; }
+    sums[e] = r;
+}
+
+// ---- transform path ------------------------------------------------------------------------------------------------------------------------
+// Wt[n][nq]: columns q < nre = 1 + g: {w, w y_c0, ...} cos(2 pi base t); with prephase, columns nre + q the same times sin
+__global__ void __launch_bounds__(256)
+lomb_prephase_kernel(const double *__restrict__ t, const double *__restrict__ w, const double *__restrict__ wy, int64_t N, int c0, int g, double base,
+                     int prephase, double *__restrict__ Wt) {
+    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    double sn = 0.0, cs = 1.0;
+    if (prephase) lomb_sincos(base, t[n], &sn, &cs);
+    const int nre = 1 + g, nq = prephase ? 2 * nre : nre;
+    double *o = Wt + n * nq;
+    for (int q = 0; q < nre; ++q) {
+        const double v = q == 0 ? w[n] : wy[(int64_t)(c0 + q - 1) * N + n];
+        o[q] = prephase ? v * cs : v;
+        if (prephase) o[nre + q] = v * sn;
+    }
+}
+// tab[(j nq + q) 4 + {cos, sin, t cos, t sin}] of a block -> sums[row][k0 + j]: Z = (A - B') + i (B + A') for the weight (re) + i (im) with
+// transforms A + i B and A' + i B'; first-order term Z += i 2 pi e Zt, e = escale eps[k0 + j].  row0 < 0: column q goes to the rows of
+// signal c0 + q - 1 (q = 0: rows 0, 1, C and S); row0 >= 0: the single column goes to rows row0, row0 + 1 (C2, S2).
+__global__ void __launch_bounds__(256)
+lomb_combine_kernel(const double *__restrict__ tab, int nq, int nre, int prephase, int count, int64_t k0, int64_t Nf, const double *__restrict__ eps, double escale,
+                    int row0, int c0, double *__restrict__ sums) {
+    const int j = blockIdx.x * 256 + threadIdx.x, q = blockIdx.y;
+    if (j >= count) return;
+    const double *a = tab + ((int64_t)j * nq + q) * 4;
+    double zr = a[0], zi = a[1], tr = a[2], ti = a[3];
+    if (prephase) {
+        const double *b = tab + ((int64_t)j * nq + nre + q) * 4;
+        zr = zr - b[1]; zi = zi + b[0];
+        tr = tr - b[3]; ti = ti + b[2];
+    }
+    const double e = escale * eps[k0 + j];
+    if (e != 0.0) {
+        const double h = 6.283185307179586 * e;
+        zr = fma(-h, ti, zr);
+        zi = fma(h, tr, zi);
+    }
+    const int row = row0 >= 0 ? row0 : (q == 0 ? 0 : 4 + 2 * (c0 + q - 1));
+    sums[(int64_t)row * Nf + k0 + j] = zr;
+    sums[(int64_t)(row + 1) * Nf + k0 + j] = zi;
+}
+
+// ---- epilogue: one thread per (frequency, signal) --------------------------------------------------------------------------------------
+// mom[2 c + {0, 1}] = Y_c, YY_c of the (centred) signal, mom[2 ns + c] = sum w y_c^2 of the signal as given; mean[c]: its weighted mean.
+// CONSTANT SIGNALS.  The standard power is 0 when YY is within rounding of 0 (lomb_yy_noise of lomb_plan.h), not only when it is exactly 0:
+// a constant signal with unequal weights leaves a YY that is a rounding residue, and p / YY would be a quotient of two noise terms.
+__global__ void __launch_bounds__(256)
+lomb_epilogue_kernel(const double *__restrict__ sums, int64_t Nf, int ns, const double *__restrict__ mom, const double *__restrict__ mean, int fit_mean,
+                     int center, int psd, double Nsamples, double *__restrict__ power, double *__restrict__ coef, int *__restrict__ ndegenerate) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int c = blockIdx.y;
+    if (k >= Nf) return;
+    const double C = sums[k], S = sums[Nf + k], C2 = sums[2 * Nf + k], S2 = sums[3 * Nf + k];
+    double YC = sums[(int64_t)(4 + 2 * c) * Nf + k], YS = sums[(int64_t)(5 + 2 * c) * Nf + k];
+    const double Y = mom[2 * c];
+    double YY = mom[2 * c + 1];
+    const double yy_noise = lomb_yy_noise(Nsamples, center != 0, fit_mean != 0, mom[2 * ns + c], YY);
+    double CC = 0.5 * (1.0 + C2), SS = 0.5 * (1.0 - C2), CS = 0.5 * S2;
+    const double scale = CC + SS;
+    if (fit_mean) {
+        YY = fma(-Y, Y, YY); YC = fma(-Y, C, YC); YS = fma(-Y, S, YS);
+        CC = fma(-C, C, CC); SS = fma(-S, S, SS); CS = fma(-C, S, CS);
+    }
+    const double D = fma(CC, SS, -(CS * CS));
+    const double removed = center ? mean[c] : 0.0;
+    double pw = 0.0, ca = 0.0, cb = 0.0, cc = removed + (fit_mean ? Y : 0.0);
+    if (!(D > kLombDegenerate * (scale * scale))) {
+        if (c == 0) atomicAdd(ndegenerate, 1);
+        cc = 0.0;
+    } else {
+        const double p = (fma(SS * YC, YC, (CC * YS) * YS) - 2.0 * ((CS * YC) * YS)) / D;
+        ca = fma(SS, YC, -(CS * YS)) / D;
+        cb = fma(CC, YS, -(CS * YC)) / D;
+        if (fit_mean) cc = removed + ((Y - ca * C) - cb * S);
+        pw = psd ? p * (0.5 * Nsamples) : (YY > yy_noise ? p / YY : 0.0);
+    }
+    power[(int64_t)c * Nf + k] = pw;
+    if (coef) {
+        const int64_t plane = Nf * ns;
+        coef[(int64_t)c * Nf + k] = ca;
+        coef[plane + (int64_t)c * Nf + k] = cb;
+        coef[2 * plane + (int64_t)c * Nf + k] = cc;
+    }
+}
+
+}  // namespace
+
+// flags_dev: one int, zeroed here; sumW_dev: one double; part: lomb_sum_slabs(N) doubles
+int32_t launch_lomb_scan(const double *t, const double *y, const double *W, int64_t N, int64_t ns, int *flags_dev, double *part, double *sumW_dev, hipStream_t s) {
+    const int64_t nslab = lomb_sum_slabs(N);
+    LPVS_HIP(hipMemsetAsync(flags_dev, 0, sizeof(int), s));
+    hipLaunchKernelGGL(lomb_scan_kernel, dim3((unsigned)nslab), dim3(256), 0, s, t, y, W, N, (int)ns, flags_dev, part);
+    hipLaunchKernelGGL(lomb_tree_kernel, dim3(1), dim3(256), 0, s, part, nslab, sumW_dev);
+    LPVS_HIP(hipGetLastError());
+    return LPVS_OK;
+}
+// w[N], wy[ns][N], mean_dev[ns], mom_dev[3 ns] = {Y_c, YY_c} per signal, then sum w y_c^2 of the signals as given; part: 3 ns lomb_sum_slabs(N) doubles
+int32_t launch_lomb_moments(const double *y, const double *W, int64_t N, int64_t ns, double sumW, bool center, double *w, double *wy, double *mean_dev,
+                            double *mom_dev, double *part, hipStream_t s) {
+    const int64_t nslab = lomb_sum_slabs(N);
+    hipLaunchKernelGGL(lomb_mean_kernel, dim3((unsigned)nslab, (unsigned)ns), dim3(256), 0, s, y, W, N, sumW, w, part, nslab);
+    hipLaunchKernelGGL(lomb_tree_kernel, dim3((unsigned)ns), dim3(256), 0, s, part, nslab, mean_dev);
+    hipLaunchKernelGGL(lomb_center_kernel, dim3((unsigned)nslab, (unsigned)ns), dim3(256), 0, s, y, w, N, mean_dev, center ? 1 : 0, wy, part, nslab);
+    hipLaunchKernelGGL(lomb_tree_kernel, dim3((unsigned)(3 * ns)), dim3(256), 0, s, part, nslab, mom_dev);
+    LPVS_HIP(hipGetLastError());
+    return LPVS_OK;
+}
+// sums[(4 + 2 ns)][Nf] by direct summation; part: nslab (4 + 2 ns) Nf doubles
+int32_t launch_lomb_direct(const double *t, const double *w, const double *wy, int64_t N, int64_t ns, const double *f_dev, int64_t Nf, const LombTiling &tl,
+                           double *part, double *sums, hipStream_t s) {
+    const dim3 grid((unsigned)tl.ftiles, (unsigned)tl.nslab, (unsigned)tl.sblocks);
+    if (tl.ts == 1) hipLaunchKernelGGL(lomb_direct_kernel<1>, grid, dim3(256), 0, s, t, w, wy, N, (int)ns, f_dev, Nf, tl.slab_samples, part);
+    else hipLaunchKernelGGL(lomb_direct_kernel<4>, grid, dim3(256), 0, s, t, w, wy, N, (int)ns, f_dev, Nf, tl.slab_samples, part);
+    const int64_t count = (4 + 2 * ns) * Nf;
+    hipLaunchKernelGGL(lomb_slab_sum_kernel, dim3((unsigned)ceil_div(count, 256)), dim3(256), 0, s, part, tl.nslab, count, sums);
+    LPVS_HIP(hipGetLastError());
+    return LPVS_OK;
+}
+// Wt[N][nq], nq = lomb_weight_vectors(.., g, prephase): the weights of signals c0 .. c0 + g - 1 (g = 0: w alone) times e^{i 2 pi base t}
+int32_t launch_lomb_prephase(const double *t, const double *w, const double *wy, int64_t N, int c0, int g, double base, bool prephase, double *Wt, hipStream_t s) {
+    hipLaunchKernelGGL(lomb_prephase_kernel, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, s, t, w, wy, N, c0, g, base, prephase ? 1 : 0, Wt);
+    LPVS_HIP(hipGetLastError());
+    return LPVS_OK;
+}
+int32_t launch_lomb_combine(const double *tab, int nq, int nre, bool prephase, int count, int64_t k0, int64_t Nf, const double *eps_dev, double escale, int row0,
+                            int c0, double *sums, hipStream_t s) {
+    hipLaunchKernelGGL(lomb_combine_kernel, dim3((unsigned)ceil_div(count, 256), (unsigned)nre), dim3(256), 0, s, tab, nq, nre, prephase ? 1 : 0, count, k0, Nf,
+                       eps_dev, escale, row0, c0, sums);
+    LPVS_HIP(hipGetLastError());
+    return LPVS_OK;
+}
+// power[ns][Nf] (column-major Nf x ns), coef[3][ns][Nf] or nullptr; ndeg_dev: one int, zeroed here
+int32_t launch_lomb_epilogue(const double *sums, int64_t Nf, int64_t ns, const double *mom_dev, const double *mean_dev, bool fit_mean, bool center, bool psd,
+                             int64_t N, double *power, double *coef, int *ndeg_dev, hipStream_t s) {
+    LPVS_HIP(hipMemsetAsync(ndeg_dev, 0, sizeof(int), s));
+    hipLaunchKernelGGL(lomb_epilogue_kernel, dim3((unsigned)ceil_div(Nf, 256), (unsigned)ns), dim3(256), 0, s, sums, Nf, (int)ns, mom_dev, mean_dev,
+                       fit_mean ? 1 : 0, center ? 1 : 0, psd ? 1 : 0, (double)N, power, coef, ndeg_dev);
+    LPVS_HIP(hipGetLastError());
+    return LPVS_OK;
+}
+
+}  // namespace lpvs

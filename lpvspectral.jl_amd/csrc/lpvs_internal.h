@@ -13,6 +13,7 @@
 #include "admm_plan.h"
 #include "gram_form_plan.h"
 #include "eval_plan.h"
+#include "lomb_plan.h"
 
 namespace lpvs {
 
@@ -231,6 +232,19 @@ int32_t launch_eval_grids(const double *Q_dev, int64_t ngrids, int64_t Nf, int n
 int32_t launch_eval_interp(const double *x, const double *v, const double *y, int64_t M, double a, double D_hi, double D_lo, int nf, const double *grids_dev,
                            bool twin, int64_t nc, const EvalBasis &B, double scale, double *out, double *part, hipStream_t s);
 int32_t launch_eval_sums(const double *part, int64_t M, int64_t nc, double *sums_dev, hipStream_t s);
+
+// ---- Lomb-Scargle periodogram (lomb.hip; the decisions: lomb_plan.h) ------------------------------------------------------------------------
+// y, wy: [ns][N] (N x ns column-major); sums: [(4 + 2 ns)][Nf] rows C, S, C2, S2, YC_c, YS_c; power: Nf x ns column-major; coef: [3][ns][Nf]
+int32_t launch_lomb_scan(const double *t, const double *y, const double *W, int64_t N, int64_t ns, int *flags_dev, double *part, double *sumW_dev, hipStream_t s);
+int32_t launch_lomb_moments(const double *y, const double *W, int64_t N, int64_t ns, double sumW, bool center, double *w, double *wy, double *mean_dev,
+                            double *mom_dev, double *part, hipStream_t s);
+int32_t launch_lomb_direct(const double *t, const double *w, const double *wy, int64_t N, int64_t ns, const double *f_dev, int64_t Nf, const LombTiling &tl,
+                           double *part, double *sums, hipStream_t s);
+int32_t launch_lomb_prephase(const double *t, const double *w, const double *wy, int64_t N, int c0, int g, double base, bool prephase, double *Wt, hipStream_t s);
+int32_t launch_lomb_combine(const double *tab, int nq, int nre, bool prephase, int count, int64_t k0, int64_t Nf, const double *eps_dev, double escale, int row0,
+                            int c0, double *sums, hipStream_t s);
+int32_t launch_lomb_epilogue(const double *sums, int64_t Nf, int64_t ns, const double *mom_dev, const double *mean_dev, bool fit_mean, bool center, bool psd,
+                             int64_t N, double *power, double *coef, int *ndeg_dev, hipStream_t s);
 
 // ---- dense symmetric inverse (linalg.hip) ------------------------------------------------
 // In-place inverse of the SPD matrix A (np x np, np % 64 == 0, full symmetric storage) by
