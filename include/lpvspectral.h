@@ -697,6 +697,44 @@ int32_t lpvs_lombscargle_f64(const double *y, int64_t ns, const double *t, int64
                              double *power, double *coef, double *sums);
 int32_t lpvs_lombscargle_last_timing(double *out, int32_t n);
 
+/* ---- g5  windowed Lomb-Scargle: the non-uniform twins of spectrogram and welch_pgram (extension).
+ * y, t, W, f as in g4.  Window w < nwin is the contiguous index range [starts[w], starts[w] + counts[w]) of the record with the time
+ * interval [lo[w], hi[w]] (starts, counts, lo, hi: HOST arrays).  Ranges may overlap, leave gaps, differ in length and come in any
+ * order; counts[w] = 0 is allowed; a range outside [0, N], hi[w] < lo[w] or a non-finite lo / hi -> LPVS_EARGUMENT.
+ * Window w is the g4 estimate of its own samples with the weights W_n g_w(t_n), the taper g_w evaluated from TIME, not from the index:
+ *   LPVS_TAPER_RECT g = 1;  LPVS_TAPER_HANN g = sin^2(pi u), u = (t_n - lo_w) / (hi_w - lo_w), g = 0 for u outside [0, 1], g = 1 if
+ *   hi_w == lo_w.  On a uniform record with lo = t[start], hi = t[start + count - 1] the Hann taper is DSP.hanning(count).
+ * Everything else is g4 with N := counts[w]: the weights normalised by sum W g, the weighted mean formed on the device in a fixed order
+ * and removed BEFORE the Fourier sums (center_data), the six sums per frequency and the moments per signal, the fit_mean terms, the
+ * degenerate rule, the constant-signal rule with u = (counts[w] + 16) 2^-53, standard and psd (p counts[w] / 2) normalisation, phases
+ * from the exact products f t.  An EMPTY window -- counts[w] = 0 or sum W g = 0, e.g. a Hann window whose only samples lie on its
+ * edges -- is no error: its column of power and coefficients is 0, and it is counted and reported.
+ *   power: average == 0: Nf x nwin x ns column-major (frequency fastest, then window, then signal); average == 1: Nf x ns, the mean of
+ *     the window columns over the windows that are not empty, added in a fixed pairwise tree in the order of the list (0 if all are empty).
+ *   coef (may be NULL; refused with average == 1): three planes a, b, c, each of the shape of the un-averaged power.
+ *   empty_out (HOST, nwin int32, may be NULL): 1 for an empty window, else 0.
+ * Errors as in g4: a non-finite t, y, W (anywhere in the record) or f, or a negative weight -> LPVS_EARGUMENT.  More than 2^24 windows,
+ * Nf beyond 2^24, a window of more than 2^20 samples or a call whose work list exceeds a launch -> LPVS_EUNSUPPORTED.
+ * Only direct sums: the transforms of g4 pay from 2^18 samples per transform on, and windows are far shorter.  A window's samples are
+ * cut into slabs of a constant length, so every sum behind a window's column is added in an order that depends on that window alone:
+ * two calls give the same bits, and a column does not depend on the other windows of the call, their order, or the other signals.
+ * t, y, W, power, coef: host or device memory.
+ * lpvs_lombscargle_windows_last_timing (the calling thread's last call), out[0..9]: windows, empty windows, work items (window slabs),
+ * slab length, degenerate (window, frequency) pairs, ms of the scan and the moments, the sums, the epilogue (and the average), the
+ * copy-out, total.
+ * lpvs_time_windows_f64: the index ranges of the time intervals [lo[w], hi[w]] in a non-decreasing t (checked on the device;
+ * LPVS_EARGUMENT otherwise, and for a non-finite t, lo or hi): starts_out[w] = #{t_n < lo_w}, counts_out[w] = #{t_n <= hi_w} - starts_out[w]
+ * (0 when hi_w < lo_w), one device binary search per edge.  t: host or device memory; lo, hi, starts_out, counts_out: HOST. */
+#define LPVS_TAPER_RECT 0
+#define LPVS_TAPER_HANN 1
+int32_t lpvs_lombscargle_windows_f64(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const double *f, int64_t Nf,
+                                     const int64_t *starts, const int64_t *counts, const double *lo, const double *hi, int64_t nwin,
+                                     int32_t taper, int32_t fit_mean, int32_t center_data, int32_t normalization, int32_t average,
+                                     int32_t device, double *power, double *coef, int32_t *empty_out);
+int32_t lpvs_lombscargle_windows_last_timing(double *out, int32_t n);
+int32_t lpvs_time_windows_f64(const double *t, int64_t N, const double *lo, const double *hi, int64_t nwin, int32_t device,
+                              int64_t *starts_out, int64_t *counts_out);
+
 #ifdef __cplusplus
 }
 #endif

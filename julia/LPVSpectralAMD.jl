@@ -20,7 +20,8 @@ export ls_spectral, tls_spectral, ls_sparse_spectral, ls_sparse_spectral_lpv, ls
        ls_cohere, ls_windowpsd_lpv, get_fourier_regressor, check_freq, default_freqs, Windows2, Windows3, mapwindows,
        SpectralExt, psd, reshape_params, ADMM, rect, hanning, autocov, autocor, isequidistant,
        melspectrogram, mfcc, mel, spectrogram, Spectrogram, MelSpectrogram, MFCC, freq, rand_cn, schedfunc,
-       Periodogram, welch_pgram, periodogram, compress, heatmap, predict, residual, fva, lombscargle, lombscargle_last_timing
+       Periodogram, welch_pgram, periodogram, compress, heatmap, predict, residual, fva, lombscargle, lombscargle_last_timing,
+       lombscargle_spectrogram, lombscargle_welch, lombscargle_windows_last_timing, time_windows
 
 const LIB = get(ENV, "LPVSPECTRAL_LIB", joinpath(@__DIR__, "..", "lpvspectral.jl_amd", "liblpvspectral.so"))
 
@@ -1099,6 +1100,88 @@ function lombscargle_last_timing()
     GC.@preserve tm check(@ccall LIB.lpvs_lombscargle_last_timing(tm::Ptr{Float64}, Int32(12)::Int32)::Int32)
     (path=Int(tm[1]), blocks=(Int(tm[2]), Int(tm[3])), nf=Int(tm[4]), degenerate=Int(tm[5]), slabs=Int(tm[6]), moments_ms=tm[7], sums_ms=tm[8], epilogue_ms=tm[9],
      copy_ms=tm[10], total_ms=tm[11], twin=tm[12] != 0)
+end
+
+# ---- windowed Lomb-Scargle (extension: the non-uniform twins of spectrogram and welch_pgram; include/lpvspectral.h g5) -----------------
+const LOMB_TAPERS = Dict(:rect => Int32(0), :hanning => Int32(1))
+"""    time_windows(t, lo, hi) -> (starts, counts)
+0-based index ranges of the time intervals `[lo[w], hi[w]]` in a non-decreasing `t`: one binary search per edge on the device."""
+function time_windows(t::AbstractVector{<:Real}, lo::AbstractVector{<:Real}, hi::AbstractVector{<:Real}; device::Integer=0)
+    tv, lov, hiv = Vector{Float64}(t), Vector{Float64}(lo), Vector{Float64}(hi)
+    @assert length(lov) == length(hiv) "lo and hi have to be the same length"
+    starts, counts = zeros(Int64, length(lov)), zeros(Int64, length(lov))
+    GC.@preserve tv lov hiv starts counts check(@ccall LIB.lpvs_time_windows_f64(tv::Ptr{Float64}, Int64(length(tv))::Int64, lov::Ptr{Float64}, hiv::Ptr{Float64},
+        Int64(length(lov))::Int64, Int32(device)::Int32, starts::Ptr{Int64}, counts::Ptr{Int64})::Int32)
+    starts, counts
+end
+# (starts 0-based, counts, lo, hi) of the one window form that was given
+function _lomb_window_list(t::Vector{Float64}, n, noverlap, width, hop, windows, device)
+    forms = (n !== nothing || noverlap !== nothing) + (width !== nothing || hop !== nothing) + (windows !== nothing)
+    forms > 1 && throw(ArgumentError("give the windows in one form: n (noverlap), width (hop) or windows=(starts, counts, lo, hi)"))
+    if windows !== nothing
+        return Vector{Int64}(windows[1]), Vector{Int64}(windows[2]), Vector{Float64}(windows[3]), Vector{Float64}(windows[4])
+    elseif width !== nothing || hop !== nothing
+        width === nothing && throw(ArgumentError("hop needs width"))
+        h = hop === nothing ? width / 2 : hop
+        lo = Float64[]
+        while t[1] + length(lo) * h <= t[end]
+            push!(lo, t[1] + length(lo) * h)
+        end
+        hi = lo .+ Float64(width)
+        starts, counts = time_windows(t, lo, hi; device=device)
+        return starts, counts, lo, hi
+    end
+    nn = n === nothing ? length(t) >> 3 : Int(n)
+    nov = noverlap === nothing ? nn >> 1 : Int(noverlap)
+    starts = Vector{Int64}(_offsets(length(t), nn, nov))                      # (0-based, as the library counts)
+    starts, fill(Int64(nn), length(starts)), t[starts .+ 1], t[starts .+ nn]
+end
+function _lomb_windows(y, t, f, n, noverlap, width, hop, windows, window, W, fit_mean, center_data, normalization, coef, average, device)
+    tv, fv = Vector{Float64}(t), Vector{Float64}(f)
+    N, Nf, ns = length(tv), length(fv), size(y, 2)
+    @assert size(y, 1) == N "y has to be as long as the sampling points"
+    taper = window === hanning ? LOMB_TAPERS[:hanning] : window === rect ? LOMB_TAPERS[:rect] : throw(ArgumentError("window: hanning or rect"))
+    yv = Matrix{Float64}(reshape(y, N, ns))
+    Wv = W === nothing ? Float64[] : Vector{Float64}(W)
+    @assert W === nothing || length(Wv) == N "W has to be as long as the sampling points"
+    Wp = W === nothing ? Ptr{Float64}(C_NULL) : pointer(Wv)
+    starts, counts, lov, hiv = _lomb_window_list(tv, n, noverlap, width, hop, windows, device)
+    nwin = length(starts)
+    power = average ? zeros(Nf, ns) : zeros(Nf, nwin, ns)
+    cfv = coef ? zeros(Nf, nwin, ns, 3) : Float64[]
+    cfp = coef ? pointer(cfv) : Ptr{Float64}(C_NULL)
+    empty = zeros(Int32, nwin)
+    GC.@preserve yv tv Wv fv starts counts lov hiv power cfv empty check(@ccall LIB.lpvs_lombscargle_windows_f64(yv::Ptr{Float64}, Int64(ns)::Int64, tv::Ptr{Float64},
+        Int64(N)::Int64, Wp::Ptr{Float64}, fv::Ptr{Float64}, Int64(Nf)::Int64, starts::Ptr{Int64}, counts::Ptr{Int64}, lov::Ptr{Float64}, hiv::Ptr{Float64},
+        Int64(nwin)::Int64, taper::Int32, Int32(fit_mean)::Int32, Int32(center_data)::Int32, LOMB_NORMALIZATIONS[normalization]::Int32, Int32(average)::Int32,
+        Int32(device)::Int32, power::Ptr{Float64}, cfp::Ptr{Float64}, empty::Ptr{Int32})::Int32)
+    one = y isa AbstractVector
+    average && return (power = one ? vec(power) : power, freq = fv)
+    shaped(A) = one ? A[:, :, 1] : A
+    S = (power = shaped(power), freq = fv, time = (lov .+ hiv) ./ 2, counts = counts, empty = empty .!= 0)
+    coef ? (S, (shaped(cfv[:, :, :, 1]), shaped(cfv[:, :, :, 2]), shaped(cfv[:, :, :, 3]))) : S
+end
+"""    lombscargle_spectrogram(y, t, f=default_freqs(t); n, noverlap, width, hop, windows, window=hanning, W, fit_mean, center_data, normalization, coef)
+The `lombscargle` estimate of every window of the record in one batched call; the windows in ONE of the forms `n` (`noverlap`), `width`
+(`hop`) or `windows=(starts, counts, lo, hi)` (0-based starts).  The taper is evaluated from the sample times.  Returns
+`(power = Nf × nwin (× ns), freq, time, counts, empty)` and, with `coef=true`, also `(a, b, c)`."""
+function lombscargle_spectrogram(y::AbstractVecOrMat{<:Real}, t::AbstractVector{<:Real}, f::AbstractVector{<:Real}=default_freqs(t); n=nothing, noverlap=nothing,
+                                 width=nothing, hop=nothing, windows=nothing, window=hanning, W=nothing, fit_mean::Bool=true, center_data::Bool=true,
+                                 normalization::Symbol=:standard, coef::Bool=false, device::Integer=0)
+    _lomb_windows(y, t, f, n, noverlap, width, hop, windows, window, W, fit_mean, center_data, normalization, coef, false, device)
+end
+"""    lombscargle_welch(y, t, f=default_freqs(t); ...) -> (power, freq)
+The mean of the columns of `lombscargle_spectrogram` over the windows that are not empty, added on the device in a fixed order."""
+function lombscargle_welch(y::AbstractVecOrMat{<:Real}, t::AbstractVector{<:Real}, f::AbstractVector{<:Real}=default_freqs(t); n=nothing, noverlap=nothing,
+                           width=nothing, hop=nothing, windows=nothing, window=hanning, W=nothing, fit_mean::Bool=true, center_data::Bool=true,
+                           normalization::Symbol=:standard, device::Integer=0)
+    _lomb_windows(y, t, f, n, noverlap, width, hop, windows, window, W, fit_mean, center_data, normalization, false, true, device)
+end
+function lombscargle_windows_last_timing()
+    tm = zeros(10)
+    GC.@preserve tm check(@ccall LIB.lpvs_lombscargle_windows_last_timing(tm::Ptr{Float64}, Int32(10)::Int32)::Int32)
+    (windows=Int(tm[1]), empty=Int(tm[2]), items=Int(tm[3]), slab=Int(tm[4]), degenerate=Int(tm[5]), moments_ms=tm[6], sums_ms=tm[7], epilogue_ms=tm[8],
+     copy_ms=tm[9], total_ms=tm[10])
 end
 
 _quantile_pair(q::Number) = (q = q < 0.5 ? q : 1 - q; (Float64(q), Float64(1 - q)))                      # src/plotting.jl:39-44

@@ -188,6 +188,9 @@ SIGNATURES = {
     "lpvs_eval_last_timing": (_I32, [_P, _I32]),
     "lpvs_lombscargle_f64": (_I32, [_P, _I64, _P, _I64, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P, _P]),
     "lpvs_lombscargle_last_timing": (_I32, [_P, _I32]),
+    "lpvs_lombscargle_windows_f64": (_I32, [_P, _I64, _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    "lpvs_lombscargle_windows_last_timing": (_I32, [_P, _I32]),
+    "lpvs_time_windows_f64": (_I32, [_P, _I64, _P, _P, _I64, _I32, _P, _P]),
 }
 
 _lib = None

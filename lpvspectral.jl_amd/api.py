@@ -2130,6 +2130,141 @@ def lombscargle_last_timing():
             "total_ms": float(o[10]), "twin": bool(o[11])}
 
 
+def time_windows(t, lo, hi, device=0):
+    """The index ranges of the time intervals ``[lo[w], hi[w]]`` in a non-decreasing ``t`` (host array or device tensor): ``(starts,
+    counts)`` with ``starts[w] = #{t < lo[w]}`` and ``counts[w] = #{t <= hi[w]} - starts[w]`` -- ``np.searchsorted`` left and right --
+    by one binary search per edge on the device.  A ``t`` that decreases somewhere, or a non-finite value, raises ValueError."""
+    la, ha = (np.ascontiguousarray(np.ravel(_host(v)).astype(np.float64)) for v in (lo, hi))
+    if len(la) != len(ha):
+        raise ValueError(f"lo has {len(la)} values, hi has {len(ha)}")
+    kt, pt, N = as_f64(_f64_arg(t))
+    starts, counts = np.zeros(len(la), dtype=np.int64), np.zeros(len(la), dtype=np.int64)
+    check(lib().lpvs_time_windows_f64(pt, N, out_ptr(la), out_ptr(ha), len(la), int(device), out_ptr(starts), out_ptr(counts)))
+    del kt
+    return starts, counts
+
+
+_LOMB_TAPERS = {"rect": 0, "hanning": 1}
+
+
+def _lomb_window_list(t, N, n, noverlap, width, hop, windows, device):
+    """(starts, counts, lo, hi) of the one window form that was given."""
+    forms = [n is not None or noverlap is not None, width is not None or hop is not None, windows is not None]
+    if sum(forms) > 1:
+        raise ValueError("give the windows in one form: n (noverlap), width (hop) or windows=(starts, counts, lo, hi)")
+    if windows is not None:
+        if len(windows) != 4:
+            raise ValueError("windows: (starts, counts, lo, hi) is needed")
+        starts, counts = (np.ascontiguousarray(np.ravel(np.asarray(v)).astype(np.int64)) for v in windows[:2])
+        lo, hi = (np.ascontiguousarray(np.ravel(_host(v)).astype(np.float64)) for v in windows[2:])
+        if not len(starts) == len(counts) == len(lo) == len(hi):
+            raise ValueError("windows: starts, counts, lo and hi differ in length")
+        return starts, counts, lo, hi
+    if forms[1]:
+        if width is None:
+            raise ValueError("hop needs width")
+        width = float(width)
+        hop = width / 2 if hop is None else float(hop)
+        if not (width > 0 and hop > 0 and np.isfinite(width) and np.isfinite(hop)):
+            raise ValueError(f"width and hop must be positive and finite (width = {width}, hop = {hop})")
+        ends = _host(t[[0, -1]] if _is_torch(t) else np.asarray(t)[[0, -1]])
+        first, last = np.float64(ends[0]), np.float64(ends[1])
+        nwin = int(np.floor((last - first) / hop)) + 1
+        lo = first + np.arange(nwin + 1, dtype=np.float64) * np.float64(hop)      # (one more, then cut: the quotient above is rounded)
+        lo = lo[lo <= last]
+        hi = lo + np.float64(width)
+        starts, counts = time_windows(t, lo, hi, device)
+        return starts, counts, lo, hi
+    n = N >> 3 if n is None else int(n)
+    noverlap = n >> 1 if noverlap is None else int(noverlap)
+    if n < 1 or N < n:
+        raise _lib.DomainError(f"the record ({N} samples) holds no window of n = {n} samples")
+    if noverlap < 0 or noverlap >= n:
+        raise _lib.DomainError(f"noverlap must satisfy 0 <= noverlap < n (noverlap = {noverlap}, n = {n})")
+    from .windows import _offsets
+    starts = np.ascontiguousarray(_offsets(N, n, noverlap), dtype=np.int64)
+    th = np.ravel(_host(t))
+    return starts, np.full(len(starts), n, dtype=np.int64), th[starts].copy(), th[starts + n - 1].copy()
+
+
+def _lomb_windows(y, t, f, n, noverlap, width, hop, windows, window, W, fit_mean, center_data, normalization, coef, average, device):
+    if normalization not in _LOMB_NORMALIZATIONS:
+        raise ValueError(f"normalization: unknown value {normalization!r} (known: {sorted(_LOMB_NORMALIZATIONS)})")
+    if window is hanning:
+        taper = _LOMB_TAPERS["hanning"]
+    elif window is rect:
+        taper = _LOMB_TAPERS["rect"]
+    else:
+        raise ValueError("window: hanning or rect (the taper is evaluated from the sample times, not from a vector of n values)")
+    if coef and average:
+        raise ValueError("coef: the coefficients of an average over windows are not defined")
+    fa = np.ascontiguousarray(np.ravel(_host(default_freqs(t) if f is None else f)).astype(np.float64))
+    Nf = len(fa)
+    ys, N, ns, single = _lomb_signals(y)
+    ky, py, ny = as_f64(ys)
+    kt, pt, nt = as_f64(_f64_arg(t))
+    if nt != N:
+        raise ValueError(f"y has {N} samples, t has {nt}")
+    kw, pw, nw = as_f64(_f64_arg(W))
+    if W is not None and nw != N:
+        raise ValueError(f"y has {N} samples, W has {nw}")
+    starts, counts, lo, hi = _lomb_window_list(t, N, n, noverlap, width, hop, windows, device)
+    nwin = len(starts)
+    if nwin == 0:
+        raise ValueError("no window")
+    power = np.zeros((ns, Nf) if average else (ns, nwin, Nf))               # [signal][window][frequency]: frequency fastest
+    co = np.zeros((3, ns, nwin, Nf)) if coef else None
+    empty = np.zeros(nwin, dtype=np.int32)
+    check(lib().lpvs_lombscargle_windows_f64(py, ns, pt, N, pw, out_ptr(fa), Nf, out_ptr(starts), out_ptr(counts), out_ptr(lo), out_ptr(hi), nwin, taper,
+                                             int(bool(fit_mean)), int(bool(center_data)), _LOMB_NORMALIZATIONS[normalization], int(bool(average)), int(device),
+                                             out_ptr(power), out_ptr(co) if coef else None, out_ptr(empty)))
+    del ky, kt, kw
+
+    def shaped(a):                                                             # (ns, nwin, Nf) -> (Nf, nwin) or (Nf, nwin, ns)
+        return np.ascontiguousarray(a[0].T) if single else np.ascontiguousarray(np.transpose(a, (2, 1, 0)))
+    if average:
+        return Periodogram(power[0].copy() if single else np.asfortranarray(power.T), fa)
+    S = Spectrogram(shaped(power), fa, (lo + hi) / 2)
+    S.counts, S.empty = counts, empty.astype(bool)
+    return (S, tuple(shaped(co[i]) for i in range(3))) if coef else S
+
+
+def lombscargle_spectrogram(y, t, f=None, n=None, noverlap=None, width=None, hop=None, windows=None, window=hanning, W=None, fit_mean=True,
+                            center_data=True, normalization="standard", coef=False, device=0):
+    """The non-uniform twin of :func:`spectrogram`: the :func:`lombscargle` estimate of every window of the record, all windows, all
+    frequencies and all signals in one batched call (direct sums; csrc/lomb.hip).
+
+    The windows are given in ONE of three forms (two together raise ValueError): ``n`` (``noverlap``): windows of n samples, the
+    arithmetic of :class:`Windows2` (defaults ``n = len(y) >> 3``, ``noverlap = n >> 1``), with the time interval from the first to the
+    last sample of the window (``t`` need not be sorted); ``width`` (``hop``, default ``width / 2``): windows of equal duration
+    ``[t[0] + w hop, t[0] + w hop + width]`` as long as they begin in the record, their samples found by :func:`time_windows` (``t``
+    sorted); ``windows=(starts, counts, lo, hi)``: explicit index ranges and time intervals -- they may overlap, leave gaps, differ in
+    length, come in any order and be empty.  ``window``: ``hanning`` or ``rect``; the taper is evaluated from the sample TIMES,
+    ``sin²(π (t - lo) / (hi - lo))``, and multiplies the weights ``W``.  Everything else as in :func:`lombscargle`, per window.
+
+    Returns a :class:`Spectrogram`: ``power`` (Nf, nwin) or (Nf, nwin, ns), ``freq = f``, ``time = (lo + hi) / 2``, and the added
+    attributes ``counts`` (samples per window) and ``empty`` (windows without samples or with weights that sum to 0: their columns are
+    0).  With ``coef=True`` also ``(a, b, c)`` of the same shape.  A column has the same bits whether its window is computed alone or
+    among others."""
+    return _lomb_windows(y, t, f, n, noverlap, width, hop, windows, window, W, fit_mean, center_data, normalization, coef, False, device)
+
+
+def lombscargle_welch(y, t, f=None, n=None, noverlap=None, width=None, hop=None, windows=None, window=hanning, W=None, fit_mean=True,
+                      center_data=True, normalization="standard", device=0):
+    """The non-uniform twin of :func:`welch_pgram`: the mean of the columns of :func:`lombscargle_spectrogram` over the windows that are
+    not empty, added on the device in a fixed pairwise tree (0 if every window is empty).  Returns a :class:`Periodogram` (``power``:
+    (Nf,) or (Nf, ns))."""
+    return _lomb_windows(y, t, f, n, noverlap, width, hop, windows, window, W, fit_mean, center_data, normalization, False, True, device)
+
+
+def lombscargle_windows_last_timing():
+    """Plan and timing of the calling thread's last :func:`lombscargle_spectrogram` / :func:`lombscargle_welch`."""
+    o = np.zeros(10)
+    check(lib().lpvs_lombscargle_windows_last_timing(out_ptr(o), 10))
+    return {"windows": int(o[0]), "empty": int(o[1]), "items": int(o[2]), "slab": int(o[3]), "degenerate": int(o[4]), "moments_ms": float(o[5]),
+            "sums_ms": float(o[6]), "epilogue_ms": float(o[7]), "copy_ms": float(o[8]), "total_ms": float(o[9])}
+
+
 def compress_last_timing():
     """Plan and HIP-event times (ms) of this thread's last compress / heatmap call."""
     o = np.zeros(5)

@@ -1544,6 +1544,179 @@ int32_t lpvs_lombscargle_last_timing(double *out, int32_t n) {
     return LPVS_OK;
 }
 
+// ---- windowed Lomb-Scargle (lomb.hip; the work list: lomb_plan.h lomb_window_plan) ----------------------------------------------------------
+// what lpvs_lombscargle_windows_last_timing reports: [0] windows, [1] empty windows, [2] work items, [3] slab length, [4] degenerate
+// (window, frequency) pairs, ms of [5] staging, the scan and the moments, [6] the sums, [7] the epilogue and the average, [8] the copy-out, [9] total
+static thread_local double g_lomb_windows_timing[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+static int32_t lomb_windows_impl(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const std::vector<double> &hf,
+                                 const std::vector<int64_t> &starts, const std::vector<int64_t> &counts, const double *lo, const double *hi, int taper,
+                                 bool fit_mean, bool center, bool psd, bool average, int32_t device, double *power, double *coef, int32_t *empty_out) {
+    const int64_t Nf = (int64_t)hf.size(), nrow = 4 + 2 * ns, nwin = (int64_t)counts.size();
+    const LombWindowPlan plan = lomb_window_plan(counts);
+    if (!plan.ok) { set_error("%s", plan.why.c_str()); return LPVS_EUNSUPPORTED; }
+    const int64_t nitems = (int64_t)plan.items.size();
+    if (!lomb_windows_fit(nitems, nwin, Nf, ns)) {
+        set_error("lombscargle: %lld window slabs, %lld frequencies and %lld signals are more than one call takes", (long long)nitems, (long long)Nf, (long long)ns);
+        return LPVS_EUNSUPPORTED;
+    }
+    const LombTiling tl = lomb_windows_tiling(Nf, ns);
+    if (lpvs_device_count() == 0) { set_error("no HIP device visible (the gfx950 path has no CPU fallback)"); return LPVS_EDEVICE; }
+    LPVS_HIP(hipSetDevice(device));
+    hipStream_t s = nullptr;
+    Events<5> ev;
+    for (auto &e : ev.e) LPVS_HIP(hipEventCreate(&e));
+    DevArg dt, dy, dW; DevOut dpower, dcoef;
+    DevBuf dsmall, dscan, ditems, dwin, dlohi, dmom, dpart, dsums, dfreq, dcols, dempty;
+    DrainOnExit drain(s);
+    LPVS_HIP(hipEventRecord(ev.e[0], s));
+    LPVS_TRY(dt.set(t, N, s));
+    LPVS_TRY(dy.set(y, N * ns, s));
+    if (W) LPVS_TRY(dW.set(W, N, s));
+    const int64_t ncols = Nf * nwin * ns;
+    LPVS_TRY(dpower.set(power, average ? Nf * ns : ncols));
+    if (coef) LPVS_TRY(dcoef.set(coef, 3 * ncols));
+    // the record is held to g4's rules as a whole: a non-finite t, y or W, a negative weight (the scan's sum of W is not used)
+    LPVS_TRY(dsmall.alloc(sizeof(double) * 3));
+    double *sumW_dev = dsmall.as<double>();
+    unsigned long long *ndeg_dev = reinterpret_cast<unsigned long long *>(sumW_dev + 1);
+    int *flags_dev = reinterpret_cast<int *>(sumW_dev + 2);
+    LPVS_TRY(dscan.alloc(sizeof(double) * (size_t)lomb_sum_slabs(N)));
+    LPVS_TRY(launch_lomb_scan(dt.p, dy.p, dW.p, N, ns, flags_dev, dscan.as<double>(), sumW_dev, s));
+    // the work list and the windows: [starts | counts | offset] (int64), nslab (int32) behind them; [lo | hi]
+    LPVS_TRY(ditems.alloc(sizeof(LombWindowItem) * (size_t)nitems));
+    LPVS_TRY(copy_to_device(ditems.p, plan.items.data(), sizeof(LombWindowItem) * (size_t)nitems, s));
+    LPVS_TRY(dwin.alloc(sizeof(int64_t) * (size_t)(3 * nwin) + sizeof(int32_t) * (size_t)nwin));
+    int64_t *starts_dev = dwin.as<int64_t>(), *counts_dev = starts_dev + nwin, *offset_dev = counts_dev + nwin;
+    int32_t *nslab_dev = reinterpret_cast<int32_t *>(offset_dev + nwin);
+    LPVS_TRY(copy_to_device(starts_dev, starts.data(), sizeof(int64_t) * (size_t)nwin, s));
+    LPVS_TRY(copy_to_device(counts_dev, counts.data(), sizeof(int64_t) * (size_t)nwin, s));
+    LPVS_TRY(copy_to_device(offset_dev, plan.offset.data(), sizeof(int64_t) * (size_t)nwin, s));
+    LPVS_TRY(copy_to_device(nslab_dev, plan.nslab.data(), sizeof(int32_t) * (size_t)nwin, s));
+    LPVS_TRY(dlohi.alloc(sizeof(double) * (size_t)(2 * nwin)));
+    LPVS_TRY(copy_to_device(dlohi.p, lo, sizeof(double) * (size_t)nwin, s));
+    LPVS_TRY(copy_to_device(dlohi.as<double>() + nwin, hi, sizeof(double) * (size_t)nwin, s));
+    LombWindows A;
+    A.t = dt.p; A.y = dy.p; A.W = dW.p; A.N = N; A.nwin = nwin; A.nitems = nitems; A.ns = (int)ns; A.taper = taper;
+    A.items = ditems.as<LombWindowItem>(); A.starts = starts_dev; A.counts = counts_dev; A.offset = offset_dev; A.nslab = nslab_dev;
+    A.lo = dlohi.as<double>(); A.hi = A.lo + nwin;
+    // per window: [0] sum W g, [1 .. ns] the weighted means, then Y_c, YY_c per signal and sum w y_c^2 of the signals as given
+    LPVS_TRY(dmom.alloc(sizeof(double) * (size_t)(nwin * (1 + 4 * ns))));
+    double *swg_dev = dmom.as<double>(), *mean_dev = swg_dev + nwin, *mom_dev = mean_dev + nwin * ns;
+    LPVS_TRY(dpart.alloc(sizeof(double) * (size_t)(nitems * nrow * Nf > 3 * ns * nitems ? nitems * nrow * Nf : 3 * ns * nitems)));
+    LPVS_TRY(launch_lomb_windows_moments(A, center, swg_dev, mean_dev, mom_dev, dpart.as<double>(), s));
+    LPVS_TRY(dsums.alloc(sizeof(double) * (size_t)(nwin * nrow * Nf)));
+    LPVS_TRY(dfreq.alloc(sizeof(double) * (size_t)Nf));
+    LPVS_TRY(copy_to_device(dfreq.p, hf.data(), sizeof(double) * (size_t)Nf, s));
+    LPVS_HIP(hipEventRecord(ev.e[1], s));
+    LPVS_TRY(launch_lomb_windows_direct(A, dfreq.as<double>(), Nf, tl, swg_dev, center ? mean_dev : nullptr, dpart.as<double>(), dsums.as<double>(), s));
+    LPVS_HIP(hipEventRecord(ev.e[2], s));
+    LPVS_TRY(dempty.alloc(sizeof(int32_t) * (size_t)nwin));
+    double *cols = dpower.p;
+    if (average) { LPVS_TRY(dcols.alloc(sizeof(double) * (size_t)ncols)); cols = dcols.as<double>(); }
+    LPVS_TRY(launch_lomb_windows_epilogue(A, dsums.as<double>(), Nf, swg_dev, mom_dev, mean_dev, fit_mean, center, psd, cols, coef ? dcoef.p : nullptr,
+                                          dempty.as<int32_t>(), flags_dev, ndeg_dev, s));
+    if (average) LPVS_TRY(launch_lomb_windows_average(cols, Nf, nwin, ns, dempty.as<int32_t>(), dpower.p, s));
+    LPVS_HIP(hipEventRecord(ev.e[3], s));
+    int flags = 0; unsigned long long ndeg = 0;
+    LPVS_TRY(copy_from_device(&flags, flags_dev, sizeof(int), s));
+    if (flags & 1) { set_error("lombscargle: t, y or W holds a value that is not finite"); return LPVS_EARGUMENT; }
+    if (flags & 2) { set_error("lombscargle: a weight is negative"); return LPVS_EARGUMENT; }
+    if (flags & 4) { set_error("lombscargle: the weights of a window do not sum to a finite value"); return LPVS_EARGUMENT; }
+    LPVS_TRY(copy_from_device(&ndeg, ndeg_dev, sizeof(ndeg), s));
+    std::vector<int32_t> hempty((size_t)nwin);
+    LPVS_TRY(copy_from_device(hempty.data(), dempty.p, sizeof(int32_t) * (size_t)nwin, s));
+    int64_t nempty = 0;
+    for (int64_t w = 0; w < nwin; ++w) { nempty += hempty[(size_t)w]; if (empty_out) empty_out[w] = hempty[(size_t)w]; }
+    LPVS_TRY(dpower.finish(s));
+    if (coef) LPVS_TRY(dcoef.finish(s));
+    LPVS_HIP(hipEventRecord(ev.e[4], s));
+    LPVS_HIP(hipStreamSynchronize(s));
+    float ms[4] = {0, 0, 0, 0}, total = 0;
+    for (int i = 0; i < 4; ++i) LPVS_HIP(hipEventElapsedTime(&ms[i], ev.e[i], ev.e[i + 1]));
+    LPVS_HIP(hipEventElapsedTime(&total, ev.e[0], ev.e[4]));
+    double *g = g_lomb_windows_timing;
+    g[0] = (double)nwin; g[1] = (double)nempty; g[2] = (double)nitems; g[3] = (double)plan.slab_samples; g[4] = (double)ndeg;
+    g[5] = ms[0]; g[6] = ms[1]; g[7] = ms[2]; g[8] = ms[3]; g[9] = total;
+    return LPVS_OK;
+}
+
+int32_t lpvs_lombscargle_windows_f64(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const double *f, int64_t Nf, const int64_t *starts,
+                                     const int64_t *counts, const double *lo, const double *hi, int64_t nwin, int32_t taper, int32_t fit_mean, int32_t center_data,
+                                     int32_t normalization, int32_t average, int32_t device, double *power, double *coef, int32_t *empty_out) {
+    try {
+        if (!y || !t || !f || !power || !starts || !counts || !lo || !hi) { set_error("NULL argument"); return LPVS_EARGUMENT; }
+        if (N <= 0 || Nf <= 0 || ns <= 0 || ns > 65535 || nwin <= 0) {
+            set_error("need N > 0, Nf > 0, nwin > 0 and 1 <= ns <= 65535 (N = %lld, Nf = %lld, nwin = %lld, ns = %lld)", (long long)N, (long long)Nf, (long long)nwin, (long long)ns);
+            return LPVS_EARGUMENT;
+        }
+        if (Nf > ((int64_t)1 << 24)) { set_error("%lld frequencies are too many", (long long)Nf); return LPVS_EUNSUPPORTED; }
+        if (nwin > kLombMaxWindows) { set_error("lombscargle: %lld windows are more than 2^24", (long long)nwin); return LPVS_EUNSUPPORTED; }
+        if (taper != LPVS_TAPER_RECT && taper != LPVS_TAPER_HANN) { set_error("taper must be 0 (rect) or 1 (hann), got %d", taper); return LPVS_EARGUMENT; }
+        if (normalization != LPVS_LOMB_STANDARD && normalization != LPVS_LOMB_PSD) { set_error("normalization must be 0 (standard) or 1 (psd), got %d", normalization); return LPVS_EARGUMENT; }
+        if (average && coef) { set_error("lombscargle: the coefficients of an average over windows are not defined (coef with average)"); return LPVS_EARGUMENT; }
+        if (is_device_ptr(f) || is_device_ptr(starts) || is_device_ptr(counts) || is_device_ptr(lo) || is_device_ptr(hi) || (empty_out && is_device_ptr(empty_out))) {
+            set_error("lombscargle: f, starts, counts, lo, hi and empty_out are host memory"); return LPVS_EARGUMENT;
+        }
+        std::vector<double> hf(f, f + Nf);
+        for (double v : hf)
+            if (!std::isfinite(v)) { set_error("lombscargle: a frequency is not finite"); return LPVS_EARGUMENT; }
+        std::vector<int64_t> hs(starts, starts + nwin), hc(counts, counts + nwin);
+        for (int64_t w = 0; w < nwin; ++w) {
+            if (hs[(size_t)w] < 0 || hc[(size_t)w] < 0 || hs[(size_t)w] > N || hc[(size_t)w] > N - hs[(size_t)w]) {
+                set_error("lombscargle: window %lld covers the samples [%lld, %lld + %lld), outside [0, %lld]", (long long)w, (long long)hs[(size_t)w],
+                          (long long)hs[(size_t)w], (long long)hc[(size_t)w], (long long)N);
+                return LPVS_EARGUMENT;
+            }
+            if (!std::isfinite(lo[w]) || !std::isfinite(hi[w])) { set_error("lombscargle: the time interval of window %lld is not finite", (long long)w); return LPVS_EARGUMENT; }
+            if (hi[w] < lo[w]) { set_error("lombscargle: the time interval of window %lld ends before it begins", (long long)w); return LPVS_EARGUMENT; }
+        }
+        return lomb_windows_impl(y, ns, t, N, W, hf, hs, hc, lo, hi, taper, fit_mean != 0, center_data != 0, normalization == LPVS_LOMB_PSD, average != 0, device,
+                                 power, coef, empty_out);
+    } catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
+}
+
+int32_t lpvs_lombscargle_windows_last_timing(double *out, int32_t n) {
+    if (!out || n < 0) { set_error("NULL argument"); return LPVS_EARGUMENT; }
+    for (int32_t k = 0; k < n && k < 10; ++k) out[k] = g_lomb_windows_timing[k];
+    return LPVS_OK;
+}
+
+int32_t lpvs_time_windows_f64(const double *t, int64_t N, const double *lo, const double *hi, int64_t nwin, int32_t device, int64_t *starts_out,
+                              int64_t *counts_out) {
+    try {
+        if (!t || !lo || !hi || !starts_out || !counts_out) { set_error("NULL argument"); return LPVS_EARGUMENT; }
+        if (N <= 0 || nwin <= 0 || nwin > kLombMaxWindows) { set_error("time_windows: need N > 0 and 1 <= nwin <= 2^24 (N = %lld, nwin = %lld)", (long long)N, (long long)nwin); return LPVS_EARGUMENT; }
+        if (is_device_ptr(lo) || is_device_ptr(hi) || is_device_ptr(starts_out) || is_device_ptr(counts_out)) {
+            set_error("time_windows: lo, hi, starts_out and counts_out are host memory"); return LPVS_EARGUMENT;
+        }
+        for (int64_t w = 0; w < nwin; ++w)
+            if (!std::isfinite(lo[w]) || !std::isfinite(hi[w])) { set_error("time_windows: the time interval of window %lld is not finite", (long long)w); return LPVS_EARGUMENT; }
+        if (lpvs_device_count() == 0) { set_error("no HIP device visible (the gfx950 path has no CPU fallback)"); return LPVS_EDEVICE; }
+        LPVS_HIP(hipSetDevice(device));
+        hipStream_t s = nullptr;
+        DevArg dt; DevBuf dlohi, dedges, dflags;
+        DrainOnExit drain(s);
+        LPVS_TRY(dt.set(t, N, s));
+        LPVS_TRY(dlohi.alloc(sizeof(double) * (size_t)(2 * nwin)));
+        LPVS_TRY(copy_to_device(dlohi.p, lo, sizeof(double) * (size_t)nwin, s));
+        LPVS_TRY(copy_to_device(dlohi.as<double>() + nwin, hi, sizeof(double) * (size_t)nwin, s));
+        LPVS_TRY(dedges.alloc(sizeof(int64_t) * (size_t)(2 * nwin)));
+        LPVS_TRY(dflags.alloc(sizeof(int)));
+        LPVS_TRY(launch_lomb_time_windows(dt.p, N, dlohi.as<double>(), dlohi.as<double>() + nwin, nwin, dflags.as<int>(), dedges.as<int64_t>(), s));
+        int flags = 0;
+        LPVS_TRY(copy_from_device(&flags, dflags.p, sizeof(int), s));
+        if (flags & 1) { set_error("time_windows: t holds a value that is not finite"); return LPVS_EARGUMENT; }
+        if (flags & 8) { set_error("time_windows: t is not sorted (it decreases somewhere)"); return LPVS_EARGUMENT; }
+        std::vector<int64_t> edges((size_t)(2 * nwin));
+        LPVS_TRY(copy_from_device(edges.data(), dedges.p, sizeof(int64_t) * edges.size(), s));
+        for (int64_t w = 0; w < nwin; ++w) {
+            const int64_t a = edges[(size_t)(2 * w)], b = edges[(size_t)(2 * w + 1)];
+            starts_out[w] = a; counts_out[w] = b > a ? b - a : 0;
+        }
+        return LPVS_OK;
+    } catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
+}
+
 int32_t lpvs_problem_create_lpv_rows_f64(const double *Y, int64_t ns, const double *X, const double *V, int64_t N_local, const double *w,
                                          int64_t Nf, int64_t Nv, int32_t normalize, int32_t coulomb, const double *ranges4,
                                          int32_t device, lpvs_problem **out) {

@@ -18,6 +18,12 @@
 // adds the first-order term of the frequency residuals from the t-weighted twins, and files the block's sums.
 //
 // MOMENTS: sum W, the weighted means and YY by slabs of 256 samples and a fixed tree (lomb_scan / lomb_mean / lomb_center kernels).
+//
+// WINDOWS (lombscargle_spectrogram / lombscargle_welch; include/lpvspectral.h g5): every window is the estimate above of its own samples
+// with the weights W g, g a taper evaluated from time.  The lomb_windows_* kernels walk the work list of lomb_plan.h (one item per slab
+// of a window; the slab is a constant, so a window's sums are added in an order that depends on that window alone): three moment passes,
+// the segmented direct kernel (the inner loop of lomb_direct_kernel), a pairwise tree per window, the epilogue per (frequency, window,
+// signal) and the average over the windows that are not empty.  lomb_time_windows_kernel: the index range of a time interval.
 #include "lpvs_internal.h"
 #include "lomb_plan.h"
 
@@ -118,6 +124,30 @@ lomb_center_kernel(const double *__restrict__ y, const double *__restrict__ w, i
     }
 }
 
+// the inner loop of the direct kernels (lomb_direct_kernel and the segmented lomb_windows_direct_kernel): sample lane `lane` walks the
+// staged samples lane, lane + 4, ... of one frequency: one sincospi per sample, the double angle from c^2 - s^2 and 2 s c
+template <int TS>
+__device__ inline void lomb_walk_stage(double fv, const double *st, const double *sw, const double (*swy)[LB_STAGE], int cnt, int lane, double *acc) {
+    for (int i = lane; i < cnt; i += LB_LANES) {
+        double sn, cs;
+        lomb_sincos(fv, st[i], &sn, &cs);
+        const double wv = sw[i];
+        const double c2 = fma(cs, cs, -(sn * sn)), s2 = 2.0 * (sn * cs);
+        acc[0] = fma(wv, cs, acc[0]);
+        acc[1] = fma(wv, sn, acc[1]);
+        acc[2] = fma(wv, c2, acc[2]);
+        acc[3] = fma(wv, s2, acc[3]);
+#pragma unroll
+        for (int c = 0; c < TS; ++c) {
+            const double v = swy[c][i];
+            acc[4 + 2 * c] = fma(v, cs, acc[4 + 2 * c]);
+            acc[5 + 2 * c] = fma(v, sn, acc[5 + 2 * c]);
+        }
+    }
+}
+// the four sample lanes of one accumulator, added as (0 + 1) + (2 + 3)
+__device__ inline double lomb_lane_sum(const double (*red)[LB_TF], int fl) { return (red[0][fl] + red[1][fl]) + (red[2][fl] + red[3][fl]); }
+
 // ---- direct path: workgroup (tile of 64 frequencies, slab of samples, block of TS signals) ---------------------------------------------
 // part[(slab nrow + row) Nf + k], nrow = 4 + 2 ns: rows C, S, C2, S2 (written by signal block 0), then YC_c, YS_c
 template <int TS>
@@ -146,22 +176,7 @@ lomb_direct_kernel(const double *__restrict__ t, const double *__restrict__ w, c
             for (int c = 0; c < TS; ++c) swy[c][threadIdx.x] = c0 + c < ns ? wy[(int64_t)(c0 + c) * N + n] : 0.0;
         }
         __syncthreads();
-        for (int i = lane; i < cnt; i += LB_LANES) {
-            double sn, cs;
-            lomb_sincos(fv, st[i], &sn, &cs);
-            const double wv = sw[i];
-            const double c2 = fma(cs, cs, -(sn * sn)), s2 = 2.0 * (sn * cs);
-            acc[0] = fma(wv, cs, acc[0]);
-            acc[1] = fma(wv, sn, acc[1]);
-            acc[2] = fma(wv, c2, acc[2]);
-            acc[3] = fma(wv, s2, acc[3]);
-#pragma unroll
-            for (int c = 0; c < TS; ++c) {
-                const double v = swy[c][i];
-                acc[4 + 2 * c] = fma(v, cs, acc[4 + 2 * c]);
-                acc[5 + 2 * c] = fma(v, sn, acc[5 + 2 * c]);
-            }
-        }
+        lomb_walk_stage<TS>(fv, st, sw, swy, cnt, lane, acc);
     }
 #pragma unroll
     for (int a = 0; a < NA; ++a) red[a][lane][fl] = acc[a];
@@ -171,7 +186,7 @@ lomb_direct_kernel(const double *__restrict__ t, const double *__restrict__ w, c
     double *o = part + (int64_t)blockIdx.y * nrow * Nf + k;
 #pragma unroll
     for (int a = 0; a < NA; ++a) {
-        const double v = (red[a][0][fl] + red[a][1][fl]) + (red[a][2][fl] + red[a][3][fl]);
+        const double v = lomb_lane_sum(red[a], fl);
         if (a < 4) { if (blockIdx.z == 0) o[(int64_t)a * Nf] = v; }
         else if (c0 + (a - 4) / 2 < ns) o[(int64_t)(4 + 2 * c0 + (a - 4)) * Nf] = v;
     }
@@ -179,12 +194,10 @@ lomb_direct_kernel(const double *__restrict__ t, const double *__restrict__ w, c
 
 // sums[e] = pairwise tree over the slabs of part[slab][e], e < nrow Nf: slabs 2i and 2i + 1 first, then pairs of pairs, ... (a binary
 // counter of partial sums), what is left over added from the smallest piece up
-__global__ void __launch_bounds__(256) lomb_slab_sum_kernel(const double *__restrict__ part, int64_t nslab, int64_t count, double *__restrict__ sums) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= count) return;
-    double stack[12];                                                      // nslab <= kLombMaxSlabs = 2^10
-    for (int64_t i = 0; i < nslab; ++i) {
-        double v = part[i * count + e];
+__device__ inline double lomb_pairwise(const double *__restrict__ p, int64_t stride, int64_t n) {
+    double stack[12];                                                      // n <= kLombMaxSlabs = 2^10
+    for (int64_t i = 0; i < n; ++i) {
+        double v = p[i * stride];
         int b = 0;
         for (; (i >> b) & 1; ++b) v = stack[b] + v;
         stack[b] = v;
@@ -192,8 +205,13 @@ __global__ void __launch_bounds__(256) lomb_slab_sum_kernel(const double *__rest
     double r = 0.0;
     bool have = false;
     for (int b = 0; b < 12; ++b)
-        if ((nslab >> b) & 1) { r = have ? stack[b] + r : stack[b]; have = true; }
-    sums[e] = r;
+        if ((n >> b) & 1) { r = have ? stack[b] + r : stack[b]; have = true; }
+    return r;
+}
+__global__ void __launch_bounds__(256) lomb_slab_sum_kernel(const double *__restrict__ part, int64_t nslab, int64_t count, double *__restrict__ sums) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= count) return;
+    sums[e] = lomb_pairwise(part + e, count, nslab);
 }
 
 // ---- transform path ------------------------------------------------------------------------------------------------------------------------
@@ -243,17 +261,11 @@ lomb_combine_kernel(const double *__restrict__ tab, int nq, int nre, int prephas
 // mom[2 c + {0, 1}] = Y_c, YY_c of the (centred) signal, mom[2 ns + c] = sum w y_c^2 of the signal as given; mean[c]: its weighted mean.
 // CONSTANT SIGNALS.  The standard power is 0 when YY is within rounding of 0 (lomb_yy_noise of lomb_plan.h), not only when it is exactly 0:
 // a constant signal with unequal weights leaves a YY that is a rounding residue, and p / YY would be a quotient of two noise terms.
-__global__ void __launch_bounds__(256)
-lomb_epilogue_kernel(const double *__restrict__ sums, int64_t Nf, int ns, const double *__restrict__ mom, const double *__restrict__ mean, int fit_mean,
-                     int center, int psd, double Nsamples, double *__restrict__ power, double *__restrict__ coef, int *__restrict__ ndegenerate) {
-    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int c = blockIdx.y;
-    if (k >= Nf) return;
-    const double C = sums[k], S = sums[Nf + k], C2 = sums[2 * Nf + k], S2 = sums[3 * Nf + k];
-    double YC = sums[(int64_t)(4 + 2 * c) * Nf + k], YS = sums[(int64_t)(5 + 2 * c) * Nf + k];
-    const double Y = mom[2 * c];
-    double YY = mom[2 * c + 1];
-    const double yy_noise = lomb_yy_noise(Nsamples, center != 0, fit_mean != 0, mom[2 * ns + c], YY);
+struct LombFit { double pw, a, b, c; bool degenerate; };
+// the fit of one (frequency, signal) from its sums: R = sum w y^2 of the signal as given, removed = the mean that centring took out
+__device__ inline LombFit lomb_fit(double C, double S, double C2, double S2, double YC, double YS, double Y, double YY, double R, double removed, int fit_mean,
+                                   int center, int psd, double Nsamples) {
+    const double yy_noise = lomb_yy_noise(Nsamples, center != 0, fit_mean != 0, R, YY);
     double CC = 0.5 * (1.0 + C2), SS = 0.5 * (1.0 - C2), CS = 0.5 * S2;
     const double scale = CC + SS;
     if (fit_mean) {
@@ -261,25 +273,243 @@ lomb_epilogue_kernel(const double *__restrict__ sums, int64_t Nf, int ns, const 
         CC = fma(-C, C, CC); SS = fma(-S, S, SS); CS = fma(-C, S, CS);
     }
     const double D = fma(CC, SS, -(CS * CS));
-    const double removed = center ? mean[c] : 0.0;
-    double pw = 0.0, ca = 0.0, cb = 0.0, cc = removed + (fit_mean ? Y : 0.0);
+    LombFit r = {0.0, 0.0, 0.0, removed + (fit_mean ? Y : 0.0), false};
     if (!(D > kLombDegenerate * (scale * scale))) {
-        if (c == 0) atomicAdd(ndegenerate, 1);
-        cc = 0.0;
+        r.degenerate = true;
+        r.c = 0.0;
     } else {
         const double p = (fma(SS * YC, YC, (CC * YS) * YS) - 2.0 * ((CS * YC) * YS)) / D;
-        ca = fma(SS, YC, -(CS * YS)) / D;
-        cb = fma(CC, YS, -(CS * YC)) / D;
-        if (fit_mean) cc = removed + ((Y - ca * C) - cb * S);
-        pw = psd ? p * (0.5 * Nsamples) : (YY > yy_noise ? p / YY : 0.0);
+        r.a = fma(SS, YC, -(CS * YS)) / D;
+        r.b = fma(CC, YS, -(CS * YC)) / D;
+        if (fit_mean) r.c = removed + ((Y - r.a * C) - r.b * S);
+        r.pw = psd ? p * (0.5 * Nsamples) : (YY > yy_noise ? p / YY : 0.0);
     }
-    power[(int64_t)c * Nf + k] = pw;
+    return r;
+}
+__global__ void __launch_bounds__(256)
+lomb_epilogue_kernel(const double *__restrict__ sums, int64_t Nf, int ns, const double *__restrict__ mom, const double *__restrict__ mean, int fit_mean,
+                     int center, int psd, double Nsamples, double *__restrict__ power, double *__restrict__ coef, int *__restrict__ ndegenerate) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int c = blockIdx.y;
+    if (k >= Nf) return;
+    const LombFit r = lomb_fit(sums[k], sums[Nf + k], sums[2 * Nf + k], sums[3 * Nf + k], sums[(int64_t)(4 + 2 * c) * Nf + k], sums[(int64_t)(5 + 2 * c) * Nf + k],
+                               mom[2 * c], mom[2 * c + 1], mom[2 * ns + c], center ? mean[c] : 0.0, fit_mean, center, psd, Nsamples);
+    if (r.degenerate && c == 0) atomicAdd(ndegenerate, 1);
+    power[(int64_t)c * Nf + k] = r.pw;
     if (coef) {
         const int64_t plane = Nf * ns;
-        coef[(int64_t)c * Nf + k] = ca;
-        coef[plane + (int64_t)c * Nf + k] = cb;
-        coef[2 * plane + (int64_t)c * Nf + k] = cc;
+        coef[(int64_t)c * Nf + k] = r.a;
+        coef[plane + (int64_t)c * Nf + k] = r.b;
+        coef[2 * plane + (int64_t)c * Nf + k] = r.c;
     }
+}
+
+// ---- windows: segmented kernels over the work list of lomb_plan.h (item = one slab of one window) -----------------------------------------
+// The taper of the window [lo, hi] at time t: 1 (rect), or sin^2(pi u), u = (t - lo) / (hi - lo), 0 outside [0, 1] and 1 when hi == lo
+// (hann).  The rounding of the quotient q = fl(d / L) is taken back to first order -- r = fma(-q, L, d) is its exact remainder, and
+// sin pi (q + r / L) = sin pi q + pi cos pi q (r / L) -- so that what is left is the error of sincospi and of the square.
+// It is evaluated where it is consumed, once per (window, sample) and pass; no array of sum(counts) tapers is kept.
+__device__ inline double lomb_taper(int kind, double t, double lo, double hi) {
+    if (kind == LPVS_TAPER_RECT) return 1.0;
+    const double L = hi - lo;
+    if (!(L > 0.0)) return 1.0;
+    const double d = t - lo, q = d / L;
+    if (!(q >= 0.0 && q <= 1.0)) return 0.0;
+    const double r = fma(-q, L, d) / L;
+    double sn, cs;
+    sincospi(q, &sn, &cs);
+    const double sv = fma(3.141592653589793 * cs, r, sn);
+    return sv * sv;
+}
+// W g of sample n (an index into the record) of window w
+__device__ inline double lomb_window_weight(const LombWindows &A, int w, int64_t n) {
+    return (A.W ? A.W[n] : 1.0) * lomb_taper(A.taper, A.t[n], A.lo[w], A.hi[w]);
+}
+// the samples [n0, n1) of the record that item `item` covers
+__device__ inline int lomb_item_range(const LombWindows &A, int64_t item, int64_t *n0, int64_t *n1) {
+    const LombWindowItem it = A.items[item];
+    const int64_t s0 = A.starts[it.window];
+    *n0 = s0 + it.first; *n1 = s0 + it.last + 1;
+    return it.window;
+}
+// The moments' kernels: one workgroup per item (and signal); it adds the item's blocks of 256 samples -- each by the tree over the
+// threads -- in ascending order.  pass 0: part[item] = sum W g;  pass 1: part[item ns + c] = sum w y_c, w = W g / swg;
+// pass 2: part[item 3 ns + {2 c, 2 c + 1, 2 ns + c}] = sum w yc, sum w yc^2, sum w y^2 (yc = y - the window's mean, or y)
+template <int PASS>
+__global__ void __launch_bounds__(256)
+lomb_windows_moments_kernel(const LombWindows A, const double *__restrict__ swg, const double *__restrict__ mean, int center, double *__restrict__ part) {
+    __shared__ double red[256];
+    int64_t n0, n1;
+    const int w = lomb_item_range(A, blockIdx.x, &n0, &n1);
+    const int c = blockIdx.y;
+    const double sw = PASS > 0 ? swg[w] : 1.0;
+    const double m = PASS == 2 && center ? mean[(int64_t)w * A.ns + c] : 0.0;
+    double a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    for (int64_t base = n0; base < n1; base += 256) {
+        const int64_t n = base + threadIdx.x;
+        double v1 = 0.0, v2 = 0.0, v3 = 0.0;
+        if (n < n1) {
+            const double wg = lomb_window_weight(A, w, n);
+            if (PASS == 0) v1 = wg;
+            else {
+                const double wv = sw > 0.0 ? wg / sw : 0.0, yr = A.y[(int64_t)c * A.N + n];
+                if (PASS == 1) v1 = wv * yr;
+                else {
+                    const double yc = yr - m;
+                    v1 = wv * yc;
+                    v2 = v1 * yc;
+                    v3 = (wv * yr) * yr;
+                }
+            }
+        }
+        const double s1 = lomb_block_sum(v1, red);
+        a1 = base == n0 ? s1 : a1 + s1;
+        if (PASS == 2) {
+            const double s2 = lomb_block_sum(v2, red), s3 = lomb_block_sum(v3, red);
+            a2 = base == n0 ? s2 : a2 + s2;
+            a3 = base == n0 ? s3 : a3 + s3;
+        }
+    }
+    if (threadIdx.x != 0) return;
+    const int64_t item = blockIdx.x;
+    if (PASS == 0) part[item] = a1;
+    else if (PASS == 1) part[item * A.ns + c] = a1;
+    else {
+        double *o = part + item * 3 * A.ns;
+        o[2 * c] = a1; o[2 * c + 1] = a2; o[2 * A.ns + c] = a3;
+    }
+}
+// out[w rows + r] = the pairwise tree over the items of window w of part[item rows + r] (an empty window: 0); a thread per element
+__global__ void __launch_bounds__(256)
+lomb_windows_tree_kernel(const double *__restrict__ part, int64_t rows, const int64_t *__restrict__ offset, const int32_t *__restrict__ nslab, int64_t total,
+                         double *__restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    const int64_t w = e / rows, r = e - w * rows;
+    out[e] = lomb_pairwise(part + offset[w] * rows + r, rows, nslab[w]);
+}
+// The segmented direct kernel: workgroup = (item, tile of 64 frequencies) x block of TS signals, laid out as lomb_direct_kernel: 64 x 4
+// threads, 256 samples staged through LDS at a time -- here with the weight W g / swg and the centred w (y - mean) formed while staging --
+// the same accumulators and the same (0 + 1) + (2 + 3).  part[(item nrow + row) Nf + k]
+template <int TS>
+__global__ void __launch_bounds__(256)
+lomb_windows_direct_kernel(const LombWindows A, const double *__restrict__ f, int64_t Nf, int64_t ftiles, const double *__restrict__ swg,
+                           const double *__restrict__ mean, double *__restrict__ part) {
+    constexpr int NA = 4 + 2 * TS;
+    __shared__ double st[LB_STAGE], sw[LB_STAGE], swy[TS][LB_STAGE];
+    __shared__ double red[NA][LB_LANES][LB_TF];
+    const int fl = threadIdx.x % LB_TF, lane = threadIdx.x / LB_TF;
+    const int64_t item = (int64_t)blockIdx.x / ftiles, tile = (int64_t)blockIdx.x - item * ftiles;
+    const int64_t k = tile * LB_TF + fl;
+    const int c0 = blockIdx.y * TS, ns = A.ns;
+    const double fv = k < Nf ? f[k] : 0.0;
+    int64_t n0, n1;
+    const int w = lomb_item_range(A, item, &n0, &n1);
+    const double sumwg = swg[w];
+    double m[TS];
+#pragma unroll
+    for (int c = 0; c < TS; ++c) m[c] = mean && c0 + c < ns ? mean[(int64_t)w * ns + c0 + c] : 0.0;
+    double acc[NA];
+#pragma unroll
+    for (int a = 0; a < NA; ++a) acc[a] = 0.0;
+    for (int64_t base = n0; base < n1; base += LB_STAGE) {
+        const int cnt = (int)(n1 - base < LB_STAGE ? n1 - base : LB_STAGE);
+        __syncthreads();                                                   // the previous stage has been walked
+        if ((int)threadIdx.x < cnt) {
+            const int64_t n = base + threadIdx.x;
+            const double wg = lomb_window_weight(A, w, n), wv = sumwg > 0.0 ? wg / sumwg : 0.0;
+            st[threadIdx.x] = A.t[n];
+            sw[threadIdx.x] = wv;
+#pragma unroll
+            for (int c = 0; c < TS; ++c) swy[c][threadIdx.x] = c0 + c < ns ? wv * (A.y[(int64_t)(c0 + c) * A.N + n] - m[c]) : 0.0;
+        }
+        __syncthreads();
+        lomb_walk_stage<TS>(fv, st, sw, swy, cnt, lane, acc);
+    }
+#pragma unroll
+    for (int a = 0; a < NA; ++a) red[a][lane][fl] = acc[a];
+    __syncthreads();
+    if (lane != 0 || k >= Nf) return;
+    const int nrow = 4 + 2 * ns;
+    double *o = part + item * nrow * Nf + k;
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+        const double v = lomb_lane_sum(red[a], fl);
+        if (a < 4) { if (blockIdx.y == 0) o[(int64_t)a * Nf] = v; }
+        else if (c0 + (a - 4) / 2 < ns) o[(int64_t)(4 + 2 * c0 + (a - 4)) * Nf] = v;
+    }
+}
+// one thread per (frequency, window, signal): power[(c nwin + w) Nf + k], the planes of coef likewise.  An empty window (no samples, or
+// weights that sum to 0) gives zeros and is reported in empty[w]; it counts no degenerate pairs.
+__global__ void __launch_bounds__(256)
+lomb_windows_epilogue_kernel(const LombWindows A, const double *__restrict__ sums, int64_t Nf, const double *__restrict__ swg, const double *__restrict__ mom,
+                             const double *__restrict__ mean, int fit_mean, int center, int psd, double *__restrict__ power, double *__restrict__ coef,
+                             int32_t *__restrict__ empty, int *__restrict__ flags, unsigned long long *__restrict__ ndegenerate) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x, total = Nf * A.nwin * A.ns;
+    if (e >= total) return;
+    const int64_t k = e % Nf, w = (e / Nf) % A.nwin;
+    const int c = (int)(e / (Nf * A.nwin)), ns = A.ns;
+    const double sw = swg[w];
+    const bool live = sw > 0.0;
+    if (k == 0 && c == 0) {
+        empty[w] = live ? 0 : 1;
+        if (!(fabs(sw) < 1.0 / 0.0)) atomicOr(flags, 4);
+    }
+    LombFit r = {0.0, 0.0, 0.0, 0.0, false};
+    if (live) {
+        const double *s = sums + w * (4 + 2 * ns) * Nf + k, *mo = mom + w * 3 * ns;
+        r = lomb_fit(s[0], s[Nf], s[2 * Nf], s[3 * Nf], s[(int64_t)(4 + 2 * c) * Nf], s[(int64_t)(5 + 2 * c) * Nf], mo[2 * c], mo[2 * c + 1], mo[2 * ns + c],
+                     center ? mean[w * ns + c] : 0.0, fit_mean, center, psd, (double)A.counts[w]);
+        if (r.degenerate && c == 0) atomicAdd(ndegenerate, 1ull);
+    }
+    power[e] = r.pw;
+    if (coef) { coef[e] = r.a; coef[total + e] = r.b; coef[2 * total + e] = r.c; }
+}
+// out[c Nf + k] = the mean over the windows that are not empty of cols[(c nwin + w) Nf + k]: the pairwise tree of lomb_pairwise over
+// those windows in the order of the list (a binary counter of partial sums), divided by their number; 0 if there is none
+__global__ void __launch_bounds__(256)
+lomb_windows_average_kernel(const double *__restrict__ cols, int64_t Nf, int64_t nwin, int64_t ns, const int32_t *__restrict__ empty, double *__restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= Nf * ns) return;
+    const int64_t k = e % Nf, c = e / Nf;
+    double stack[26];                                                      // nwin <= kLombMaxWindows = 2^24
+    int64_t j = 0;
+    for (int64_t w = 0; w < nwin; ++w) {
+        if (empty[w]) continue;
+        double v = cols[(c * nwin + w) * Nf + k];
+        int b = 0;
+        for (; (j >> b) & 1; ++b) v = stack[b] + v;
+        stack[b] = v;
+        ++j;
+    }
+    double r = 0.0;
+    bool have = false;
+    for (int b = 0; b < 26; ++b)
+        if ((j >> b) & 1) { r = have ? stack[b] + r : stack[b]; have = true; }
+    out[e] = j > 0 ? r / (double)j : 0.0;
+}
+// time windows: is t finite and non-decreasing (flags), and one binary search per edge: edges[2 w] = #{t < lo_w}, edges[2 w + 1] = #{t <= hi_w}
+__global__ void __launch_bounds__(256) lomb_sorted_kernel(const double *__restrict__ t, int64_t N, int *__restrict__ flags) {
+    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    int bad = 0;
+    if (!(fabs(t[n]) < 1.0 / 0.0)) bad |= 1;
+    if (n + 1 < N && t[n] > t[n + 1]) bad |= 8;
+    if (bad) atomicOr(flags, bad);
+}
+__global__ void __launch_bounds__(256)
+lomb_time_windows_kernel(const double *__restrict__ t, int64_t N, const double *__restrict__ lo, const double *__restrict__ hi, int64_t nwin, int64_t *__restrict__ edges) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= 2 * nwin) return;
+    const bool upper = e & 1;
+    const double v = upper ? hi[e >> 1] : lo[e >> 1];
+    int64_t a = 0, b = N;                                                  // the answer lies in [a, b]
+    while (a < b) {
+        const int64_t mid = a + (b - a) / 2;
+        const double tv = t[mid];
+        if (upper ? tv <= v : tv < v) a = mid + 1; else b = mid;
+    }
+    edges[e] = a;
 }
 
 }  // namespace
@@ -334,6 +564,55 @@ int32_t launch_lomb_epilogue(const double *sums, int64_t Nf, int64_t ns, const d
     LPVS_HIP(hipMemsetAsync(ndeg_dev, 0, sizeof(int), s));
     hipLaunchKernelGGL(lomb_epilogue_kernel, dim3((unsigned)ceil_div(Nf, 256), (unsigned)ns), dim3(256), 0, s, sums, Nf, (int)ns, mom_dev, mean_dev,
                        fit_mean ? 1 : 0, center ? 1 : 0, psd ? 1 : 0, (double)N, power, coef, ndeg_dev);
+    LPVS_HIP(hipGetLastError());
+    return LPVS_OK;
+}
+
+// ---- windows -------------------------------------------------------------------------------------------------------------------------------
+static void launch_lomb_windows_tree(const LombWindows &A, const double *part, int64_t rows, double *out, hipStream_t s) {
+    const int64_t total = A.nwin * rows;
+    hipLaunchKernelGGL(lomb_windows_tree_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, part, rows, A.offset, A.nslab, total, out);
+}
+int32_t launch_lomb_windows_moments(const LombWindows &A, bool center, double *swg, double *mean, double *mom, double *part, hipStream_t s) {
+    const dim3 one((unsigned)A.nitems), per((unsigned)A.nitems, (unsigned)A.ns);
+    const double *none = nullptr;
+    if (A.nitems > 0) hipLaunchKernelGGL(lomb_windows_moments_kernel<0>, one, dim3(256), 0, s, A, none, none, 0, part);
+    launch_lomb_windows_tree(A, part, 1, swg, s);
+    if (A.nitems > 0) hipLaunchKernelGGL(lomb_windows_moments_kernel<1>, per, dim3(256), 0, s, A, (const double *)swg, none, 0, part);
+    launch_lomb_windows_tree(A, part, A.ns, mean, s);
+    if (A.nitems > 0) hipLaunchKernelGGL(lomb_windows_moments_kernel<2>, per, dim3(256), 0, s, A, (const double *)swg, (const double *)mean, center ? 1 : 0, part);
+    launch_lomb_windows_tree(A, part, 3 * (int64_t)A.ns, mom, s);
+    LPVS_HIP(hipGetLastError());
+    return LPVS_OK;
+}
+int32_t launch_lomb_windows_direct(const LombWindows &A, const double *f_dev, int64_t Nf, const LombTiling &tl, const double *swg, const double *mean_or_null,
+                                   double *part, double *sums, hipStream_t s) {
+    const dim3 grid((unsigned)(A.nitems * tl.ftiles), (unsigned)tl.sblocks);
+    if (A.nitems > 0) {
+        if (tl.ts == 1) hipLaunchKernelGGL(lomb_windows_direct_kernel<1>, grid, dim3(256), 0, s, A, f_dev, Nf, tl.ftiles, swg, mean_or_null, part);
+        else hipLaunchKernelGGL(lomb_windows_direct_kernel<4>, grid, dim3(256), 0, s, A, f_dev, Nf, tl.ftiles, swg, mean_or_null, part);
+    }
+    launch_lomb_windows_tree(A, part, (4 + 2 * (int64_t)A.ns) * Nf, sums, s);
+    LPVS_HIP(hipGetLastError());
+    return LPVS_OK;
+}
+int32_t launch_lomb_windows_epilogue(const LombWindows &A, const double *sums, int64_t Nf, const double *swg, const double *mom, const double *mean, bool fit_mean,
+                                     bool center, bool psd, double *power, double *coef, int32_t *empty, int *flags_dev, unsigned long long *ndeg_dev, hipStream_t s) {
+    LPVS_HIP(hipMemsetAsync(ndeg_dev, 0, sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(lomb_windows_epilogue_kernel, dim3((unsigned)ceil_div(Nf * A.nwin * A.ns, 256)), dim3(256), 0, s, A, sums, Nf, swg, mom, mean,
+                       fit_mean ? 1 : 0, center ? 1 : 0, psd ? 1 : 0, power, coef, empty, flags_dev, ndeg_dev);
+    LPVS_HIP(hipGetLastError());
+    return LPVS_OK;
+}
+int32_t launch_lomb_windows_average(const double *cols, int64_t Nf, int64_t nwin, int64_t ns, const int32_t *empty, double *out, hipStream_t s) {
+    hipLaunchKernelGGL(lomb_windows_average_kernel, dim3((unsigned)ceil_div(Nf * ns, 256)), dim3(256), 0, s, cols, Nf, nwin, ns, empty, out);
+    LPVS_HIP(hipGetLastError());
+    return LPVS_OK;
+}
+int32_t launch_lomb_time_windows(const double *t, int64_t N, const double *lo, const double *hi, int64_t nwin, int *flags_dev, int64_t *edges, hipStream_t s) {
+    LPVS_HIP(hipMemsetAsync(flags_dev, 0, sizeof(int), s));
+    hipLaunchKernelGGL(lomb_sorted_kernel, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, s, t, N, flags_dev);
+    hipLaunchKernelGGL(lomb_time_windows_kernel, dim3((unsigned)ceil_div(2 * nwin, 256)), dim3(256), 0, s, t, N, lo, hi, nwin, edges);
     LPVS_HIP(hipGetLastError());
     return LPVS_OK;
 }

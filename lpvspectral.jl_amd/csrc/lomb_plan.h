@@ -6,6 +6,8 @@
 // No HIP dependency: the host-side test (tests/test_lomb_plan.py) compiles it as it is.
 #pragma once
 
+#include <string>
+
 #include "gram_form_plan.h"
 
 namespace lpvs {
@@ -181,5 +183,76 @@ inline double lomb_yy_noise(double N, bool center, bool fit_mean, double R, doub
 // D <= kLombDegenerate (CC + SS)^2, with CC + SS taken BEFORE the floating-mean terms are subtracted (it is 1 there; after the
 // subtraction it is itself rounding noise at f = 0, where the rule has to bite)
 constexpr double kLombDegenerate = 0x1p-40;
+
+// ---- windows (lombscargle_spectrogram / lombscargle_welch: include/lpvspectral.h g5) --------------------------------------
+// Every window is a g4 estimate of its own samples; one call runs them all through segmented kernels.  Only the direct path: the
+// transforms pay from kLombNufftMinSamples = 2^18 samples per transform on, and windows are far shorter.
+// The samples of a window are cut into slabs of kLombWindowSlab -- a CONSTANT (a multiple of kLombStage, at least kLombMinSlab), not a
+// function of the call as lomb_tiling's slab is: a window's slabs, and with them the order of every addition behind its column, depend on
+// its own count alone, so the column has the same bits whether the window is computed alone, among others or in another place of the list.
+// The work list holds one item per (window, slab); empty windows leave none.  The moments' kernels take one item per workgroup (its
+// blocks of kLombSumBlock samples in ascending order), the direct kernel one item, one tile of frequencies and one block of signals;
+// a window's items are then added in the pairwise tree of lomb_slab_sum_kernel.
+constexpr int64_t kLombWindowSlab = 1024, kLombMaxWindows = (int64_t)1 << 24;
+static_assert(kLombWindowSlab % kLombStage == 0 && kLombWindowSlab >= kLombMinSlab && kLombWindowSlab % kLombSumBlock == 0, "the slab of a window");
+struct LombWindowItem {
+    int32_t window = 0, slab = 0;       // the window, and the index of this slab within it
+    int64_t first = 0, last = 0;        // its samples first .. last (inclusive), counted from the window's first sample
+};
+struct LombWindowPlan {
+    bool ok = false;
+    std::string why;                    // (refused: the reason)
+    int64_t slab_samples = kLombWindowSlab;
+    std::vector<LombWindowItem> items;
+    std::vector<int32_t> nslab;         // per window: its slabs (0: an empty window)
+    std::vector<int64_t> offset;        // per window: the index of its first item; one more entry: the number of items
+};
+inline LombWindowPlan lomb_window_plan(const std::vector<int64_t> &counts) {
+    LombWindowPlan p;
+    if ((int64_t)counts.size() > kLombMaxWindows) {
+        p.why = "lombscargle: " + std::to_string(counts.size()) + " windows are more than 2^24";
+        return p;
+    }
+    p.nslab.reserve(counts.size()); p.offset.reserve(counts.size() + 1);
+    for (size_t w = 0; w < counts.size(); ++w) {
+        const int64_t n = counts[w];
+        if (n < 0) { p.why = "lombscargle: window " + std::to_string(w) + " has a negative count"; return p; }
+        const int64_t ns = ceil_div(n, kLombWindowSlab);
+        if (ns > kLombMaxSlabs) {
+            p.why = "lombscargle: window " + std::to_string(w) + " holds " + std::to_string(n) + " samples, more than the " +
+                    std::to_string(kLombMaxSlabs * kLombWindowSlab) + " a window may hold (" + std::to_string(kLombMaxSlabs) + " slabs of " +
+                    std::to_string(kLombWindowSlab) + ")";
+            return p;
+        }
+        p.offset.push_back((int64_t)p.items.size());
+        p.nslab.push_back((int32_t)ns);
+        for (int64_t s = 0; s < ns; ++s) {
+            LombWindowItem it;
+            it.window = (int32_t)w; it.slab = (int32_t)s;
+            it.first = s * kLombWindowSlab;
+            it.last = (it.first + kLombWindowSlab < n ? it.first + kLombWindowSlab : n) - 1;
+            p.items.push_back(it);
+        }
+    }
+    p.offset.push_back((int64_t)p.items.size());
+    p.ok = true;
+    return p;
+}
+// the direct kernel's tiles of frequencies and blocks of signals (as lomb_tiling's; the slab is the constant)
+inline LombTiling lomb_windows_tiling(int64_t Nf, int64_t ns) {
+    LombTiling t;
+    t.ts = ns <= 1 ? 1 : 4;
+    t.sblocks = (int)ceil_div(ns, t.ts);
+    t.acc = 4 + 2 * t.ts;
+    t.ftiles = ceil_div(Nf, kLombFreqTile);
+    t.slab_samples = kLombWindowSlab;
+    return t;
+}
+// one-dimensional grids: (items x tiles) workgroups of the direct kernel, a thread per element of the trees and of the epilogue
+constexpr int64_t kLombMaxGrid = ((int64_t)1 << 31) - 1;
+inline bool lomb_windows_fit(int64_t nitems, int64_t nwin, int64_t Nf, int64_t ns) {
+    const double most = (double)kLombMaxGrid, rows = (double)(4 + 2 * ns) * (double)Nf;   // (products of up to 2^65: compared as doubles)
+    return (double)nitems * (double)ceil_div(Nf, kLombFreqTile) <= most && (double)nwin * rows <= 255.0 * most && (double)nitems * rows <= 255.0 * most;
+}
 
 }  // namespace lpvs

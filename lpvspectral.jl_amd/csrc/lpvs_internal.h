@@ -245,6 +245,28 @@ int32_t launch_lomb_combine(const double *tab, int nq, int nre, bool prephase, i
                             int c0, double *sums, hipStream_t s);
 int32_t launch_lomb_epilogue(const double *sums, int64_t Nf, int64_t ns, const double *mom_dev, const double *mean_dev, bool fit_mean, bool center, bool psd,
                              int64_t N, double *power, double *coef, int *ndeg_dev, hipStream_t s);
+// windows (lpvs_lombscargle_windows_f64; the work list: lomb_plan.h lomb_window_plan).  All pointers are device memory.
+struct LombWindows {
+    const double *t = nullptr, *y = nullptr, *W = nullptr;       // the record: t[N], y[ns][N], W[N] or nullptr
+    int64_t N = 0, nwin = 0, nitems = 0;
+    int ns = 0, taper = 0;
+    const LombWindowItem *items = nullptr;                       // [nitems]
+    const int64_t *starts = nullptr, *counts = nullptr, *offset = nullptr;   // [nwin]: first sample, samples, first item
+    const int32_t *nslab = nullptr;                              // [nwin]
+    const double *lo = nullptr, *hi = nullptr;                   // [nwin]: the time interval of the taper
+};
+// swg[nwin] = sum W g, mean[nwin][ns], mom[nwin][3 ns] = {Y_c, YY_c} per signal, then sum w y_c^2 of the signals as given; part: 3 ns nitems doubles
+int32_t launch_lomb_windows_moments(const LombWindows &A, bool center, double *swg, double *mean, double *mom, double *part, hipStream_t s);
+// sums[nwin][4 + 2 ns][Nf]; part: nitems (4 + 2 ns) Nf doubles
+int32_t launch_lomb_windows_direct(const LombWindows &A, const double *f_dev, int64_t Nf, const LombTiling &tl, const double *swg, const double *mean_or_null,
+                                   double *part, double *sums, hipStream_t s);
+// power[ns][nwin][Nf], coef[3][ns][nwin][Nf] or nullptr, empty[nwin]; flags_dev |= 4: a window's weights do not sum to a finite value; ndeg_dev: zeroed here
+int32_t launch_lomb_windows_epilogue(const LombWindows &A, const double *sums, int64_t Nf, const double *swg, const double *mom, const double *mean, bool fit_mean,
+                                     bool center, bool psd, double *power, double *coef, int32_t *empty, int *flags_dev, unsigned long long *ndeg_dev, hipStream_t s);
+// out[ns][Nf] = the mean of the columns cols[ns][nwin][Nf] of the windows that are not empty (0 if all are)
+int32_t launch_lomb_windows_average(const double *cols, int64_t Nf, int64_t nwin, int64_t ns, const int32_t *empty, double *out, hipStream_t s);
+// flags_dev (zeroed here) |= 1: a non-finite t, |= 8: t decreases somewhere; edges[2 w] = #{t < lo_w}, edges[2 w + 1] = #{t <= hi_w}
+int32_t launch_lomb_time_windows(const double *t, int64_t N, const double *lo, const double *hi, int64_t nwin, int *flags_dev, int64_t *edges, hipStream_t s);
 
 // ---- dense symmetric inverse (linalg.hip) ------------------------------------------------
 // In-place inverse of the SPD matrix A (np x np, np % 64 == 0, full symmetric storage) by

@@ -1,0 +1,368 @@
+"""lombscargle_spectrogram / lombscargle_welch / time_windows on the GPU against tests/_lomb_ref.lomb_ref applied to every window's slice.
+
+REFERENCE.  Window w is lomb_ref(y[slice], t[slice], f, W = W[slice] g_w) with the taper g_w = sin^2(pi (t - lo) / (hi - lo)) evaluated in
+long double from the same doubles lo, hi, t (0 outside [0, 1]; 1 for rect).  lomb_ref takes its weights as doubles, so the product W g is
+rounded to double once: a relative error of u = 2^-53 per weight on the reference's side, accounted below.  The slice is centred with the
+reference's own mean (no per-window means are reported by the device).
+
+INPUTS follow tests/test_gpu_lomb.py: t in multiples of 2^-10 (below 2^14), f in multiples of 2^-6 (at most 3, or 24 on the uniform
+record whose t are multiples of 2^-6): every product f t is exact in double.  lo and hi are multiples of 2^-10 too, so t - lo and hi - lo
+are exact and the only rounding in the taper's argument is that of the quotient, which the device takes back to first order
+(csrc/lomb.hip: lomb_taper).  The samples are sparse -- 6000 over 12000 units -- so that a window of 37 samples still spans many periods of
+the lowest frequency (1/4): the reference's D >= 0.01 wherever it is not degenerate, for every compared window (asserted).
+
+BOUNDS (u = 2^-53, n = the window's samples).  The direct sums, moments and the epilogue are held to the bounds of tests/test_gpu_lomb.py
+with N := n -- (n + 16) u sum|terms| plus the trigonometry allowance, passed through the epilogue to first order by the reference's D
+(its helpers are imported as they are).  Two allowances are added, both derived here and none fitted to what the device gives:
+
+  taper.  The device's g~ = s~^2 with s~ = sinpi(q) + pi cospi(q) r (r: the exact remainder of the quotient): sincospi is good to 1 ulp,
+      |ds| <= 2^-53 for |s| <= 1, so |d(s^2)| <= 2 |s| |ds| + u s^2 <= 2.5 u, and the first-order correction leaves O(u^2) of the
+      quotient's rounding: within the |g~ - g| <= 4 u per sample that the allowance uses.  The reference's rounding of W g to double
+      adds u W g <= u W.  With T = 4 u + u, Sg = sum W g and kappa = sum W / Sg (about 2 for Hann), the normalised weight
+      w_n = W_n g_n / Sg moves by |dw_n| <= T W_n / Sg + w_n T sum W / Sg, hence
+          C, S, C2, S2 (|cos| <= 1):  sum|dw_n| <= 2 T kappa
+          Y, YC, YS:                  sum|dw_n| |yc_n| <= T (sum W |yc| / Sg + kappa sum w |yc|)
+          YY:                         T (sum W yc^2 / Sg + kappa sum w yc^2)
+          the weighted mean:          T (sum W |y| / Sg + kappa sum w |y|).
+      The rect taper is exactly 1 on both sides: T = 0.
+  mean.  The device's weighted mean is off by at most dm = (n + 16) u sum w|y| + (the taper term above).  It was removed before the
+      sums, so the device's centred signal is yc - dm' with |dm'| <= dm, and
+          YC -> YC - dm' C,  YS -> YS - dm' S,  Y -> Y - dm',  YY -> YY - 2 dm' Y + dm'^2,  removed -> removed + dm'.
+      With fit_mean the epilogue works with YC - Y C, YS - Y S, YY - Y^2 and c = removed + Y - a C - b S, and every one of them is
+      UNCHANGED by dm' in exact arithmetic (YC - dm' C - (Y - dm') C = YC - Y C, and so on): the fitted constant absorbs whatever mean was
+      removed, and no allowance is due -- which is why the bounds of the large-offset case do not grow with the offset, although
+      sum w|y| does.  (A code that formed YC - Y C from UNcentred sums would carry (n + 16) u sum w |y| |cos| = 1e-7 there, against
+      bounds of 1e-12.)  Without fit_mean the model has no constant and dm' is real:
+          dYC += dm sum w|cos|,  dYS += dm sum w|sin|,  dY += dm,  dYY += 2 dm sum w|yc| + dm^2,  dc += dm.
+
+WINDOWS of 1 - 3 samples are not compared (their D is far below 0.01 where it is not 0): all their values are finite, and their standard
+power lies in [-b, 1 + b] wherever the reference's D >= 0.01, with b the same first-order bound.
+
+WELCH.  The mean over the m windows that are not empty is a sum of m terms in a pairwise tree and one division:
+|mean - ref| <= (nwin + 16) u sum|columns| / m."""
+import functools
+
+import numpy as np
+import pytest
+
+from _lomb_ref import LD, lomb_ref
+from test_gpu_lomb import U, _epilogue_bounds, _ratio, _sum_bounds
+
+pytestmark = pytest.mark.gpu
+N, NF, NS, SLAB = 6000, 70, 5, 1024
+PI = np.arccos(LD(-1))
+
+
+# ---- inputs ------------------------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _record(offset=0.0):
+    rng = np.random.default_rng(6000)
+    t = np.sort(rng.integers(0, 12000 * 1024, N)) / 1024.0
+    y = np.cos(2 * np.pi * 1.25 * t[:, None] + np.arange(NS)[None, :]) * (1.0 + np.arange(NS))[None, :] + 0.5 * rng.standard_normal((N, NS)) + 0.75 + offset
+    W = rng.uniform(0.5, 2.0, N)
+    for a in (t, y, W):
+        a.setflags(write=False)
+    return t, y, W
+
+
+@functools.lru_cache(maxsize=None)
+def _freqs(uniform=False):
+    rng = np.random.default_rng(70)
+    j = rng.choice(np.arange(32, 1537) if uniform else np.arange(16, 193), NF, replace=False)   # [1/2, 24] or [1/4, 3] in steps of 2^-6
+    f = np.sort(j) / 64.0
+    f.setflags(write=False)
+    return f
+
+
+@functools.lru_cache(maxsize=None)
+def _windows():
+    """Case 1: overlapping, out of order, one ending at N; the window of two samples has its samples ON the edges of its interval (empty
+    under the Hann taper), the others' intervals reach 1/2 before their first and 1/4 beyond their last sample."""
+    t = _record()[0]
+    starts = np.array([123, 5990, 1500, 100, 2900, 2000, 3000, 5743, 0], dtype=np.int64)
+    counts = np.array([3 * SLAB + 5, 2, SLAB, 0, 255, SLAB + 1, 37, 257, 256], dtype=np.int64)
+    assert sorted(counts) == [0, 2, 37, 255, 256, 257, SLAB, SLAB + 1, 3 * SLAB + 5] and np.all(starts + counts <= N) and starts[7] + counts[7] == N
+    last = starts + np.maximum(counts, 1) - 1
+    lo, hi = t[starts] - 0.5, t[last] + 0.25
+    lo[1], hi[1] = t[starts[1]], t[last[1]]
+    return starts, counts, lo, hi
+
+
+# ---- reference and bounds ----------------------------------------------------------------------------------------------------------------
+def _taper(kind, t, lo, hi):
+    """Long double; kind "rect" or "hanning".  sin(pi u) = sin(pi (1 - u)) is taken at the smaller of u and 1 - u, so that the edge u = 1
+    gives the 0 it is and not the square of the long-double pi's own rounding."""
+    if kind == "rect" or hi == lo:
+        return np.ones(len(t), dtype=LD)
+    u = (t.astype(LD) - LD(lo)) / (LD(hi) - LD(lo))
+    return np.where((u >= 0) & (u <= 1), np.sin(PI * np.minimum(u, 1 - u)) ** 2, LD(0))
+
+
+def _window_ref(y, t, W, f, start, count, lo, hi, kind, fit_mean, center, normalization):
+    """(reference, bounds of power / a / b / c) of one window, all NS signals; None for an empty window."""
+    sl = slice(int(start), int(start + count))
+    ys, ts, Ws = y[sl], t[sl], (np.ones(count) if W is None else W[sl]).astype(LD)
+    g = _taper(kind, ts, lo, hi)
+    Wg = (Ws * g).astype(np.float64)                                          # (lomb_ref reads doubles: one rounding, u W g)
+    if count == 0 or not Wg.sum() > 0:
+        return None
+    r = lomb_ref(ys, ts, f, W=Wg, fit_mean=fit_mean, center_data=center, normalization=normalization)
+    b = _sum_bounds(r, ts, ys, Wg, False)
+    n = int(count)
+    T = 0.0 if kind == "rect" else 5 * U
+    Sg = (Ws * g).sum()
+    kappa = Ws.sum() / Sg
+    w = Ws * g / Sg
+    yl = ys.astype(LD)
+    yc = yl - r["removed"][None, :]
+    swy, swyy = (w[:, None] * np.abs(yc)).sum(axis=0), (w[:, None] * yc * yc).sum(axis=0)
+    for k in ("C", "S", "C2", "S2"):
+        b[k] = b[k] + 2 * T * kappa
+    tY = T * ((Ws[:, None] * np.abs(yc)).sum(axis=0) / Sg + kappa * swy)
+    for k in ("YC", "YS"):
+        b[k] = b[k] + tY[:, None]
+    b["Y"] = b["Y"] + tY
+    b["YY"] = b["YY"] + T * ((Ws[:, None] * yc * yc).sum(axis=0) / Sg + kappa * swyy)
+    if center and not fit_mean:
+        dm = (n + 16) * U * r["abs_mean"] + T * ((Ws[:, None] * np.abs(yl)).sum(axis=0) / Sg + kappa * r["abs_mean"])
+        b["YC"] = b["YC"] + dm[:, None] * r["abs_C"][None, :]
+        b["YS"] = b["YS"] + dm[:, None] * r["abs_S"][None, :]
+        b["Y"] = b["Y"] + dm
+        b["YY"] = b["YY"] + 2 * dm * swy + dm * dm
+        b["removed"] = b["removed"] + dm
+    return r, _epilogue_bounds(r, b, fit_mean, normalization == "psd", n)
+
+
+@functools.lru_cache(maxsize=None)
+def _case1_refs(kind, fit_mean, center, normalization, offset=0.0):
+    t, y, W = _record(offset)
+    return [_window_ref(y, t, W, _freqs(), s, c, a, b, kind, fit_mean, center, normalization) for s, c, a, b in zip(*_windows())]
+
+
+def _compare(got, refs, counts, ns, standard):
+    """got: dict of (Nf, nwin, ns) arrays; refs: per window None or (reference, bounds) of NS >= ns signals."""
+    worst = {k: 0.0 for k in got}
+    for w, rb in enumerate(refs):
+        cols = {k: np.asarray(v).reshape(NF, len(refs), ns)[:, w, :] for k, v in got.items()}
+        if rb is None:
+            assert all(np.all(c == 0.0) for c in cols.values()), f"window {w}: an empty window gives exact zeros"
+            continue
+        r, be = rb
+        deg = r["degenerate"]
+        assert all(np.all(np.isfinite(c)) for c in cols.values()), w
+        if counts[w] < 8:
+            ok = r["D"] >= 0.01
+            if standard:
+                bnd = be["power"][ok][:, :ns].astype(np.float64)
+                assert np.all(cols["power"][ok] >= -bnd) and np.all(cols["power"][ok] <= 1.0 + bnd), w
+            continue
+        assert np.all(r["D"][~deg] >= 0.01) and np.all(r["D"][deg] <= 2.0 ** -45), f"window {w}: the inputs are to stay clear of the degenerate threshold"
+        for k, c in cols.items():
+            assert np.all(c[deg] == 0.0), (k, w)
+            err, bnd = np.abs(c.astype(LD) - r[k][:, :ns])[~deg], be[k][~deg][:, :ns]
+            worst[k] = max(worst[k], _ratio(err, bnd))
+            assert np.all(err <= bnd), (k, w, _ratio(err, bnd))
+    print("worst error / bound:", worst)
+
+
+def _run(L, ns, kind, fit_mean, center, normalization, offset=0.0):
+    t, y, W = _record(offset)
+    starts, counts, lo, hi = _windows()
+    S, (a, b, c) = L.lombscargle_spectrogram(y[:, :ns] if ns > 1 else y[:, 0], t, _freqs(), windows=(starts, counts, lo, hi),
+                                             window=L.hanning if kind == "hanning" else L.rect, W=W, fit_mean=fit_mean, center_data=center,
+                                             normalization=normalization, coef=True)
+    assert S.power.shape == ((NF, 9) if ns == 1 else (NF, 9, ns)) and a.shape == S.power.shape and np.array_equal(S.freq, _freqs())
+    assert np.array_equal(S.time, (lo + hi) / 2) and np.array_equal(S.counts, counts)
+    refs = _case1_refs(kind, fit_mean, center, normalization, offset)
+    assert np.array_equal(S.empty, [rb is None for rb in refs])
+    tm = L.lombscargle_windows_last_timing()
+    assert (tm["windows"], tm["empty"], tm["slab"]) == (9, int(S.empty.sum()), SLAB)
+    assert tm["items"] == sum(-(-int(n) // SLAB) for n in counts) == 12
+    _compare({"power": S.power, "a": a, "b": b, "c": c}, refs, counts, ns, normalization == "standard")
+    return S
+
+
+# ---- 1  explicit windows -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("ns,kind,fit_mean,center,normalization", [
+    (5, "hanning", True, True, "standard"),
+    (1, "hanning", True, True, "standard"),
+    (3, "hanning", True, False, "psd"),
+    (1, "hanning", False, True, "standard"),
+    (5, "hanning", False, False, "psd"),
+    (3, "rect", True, True, "psd"),
+    (1, "rect", False, True, "standard"),
+])
+def test_explicit_windows_power_and_coefficients(L, ns, kind, fit_mean, center, normalization):
+    """Counts 0, 2, 37, 255, 256, 257, S, S + 1, 3 S + 5: around the block of 256 and the slab; 70 frequencies are two tiles, 3 and 5
+    signals one and two blocks of four.  Under the Hann taper the window of two samples (both on its edges) is empty."""
+    S = _run(L, ns, kind, fit_mean, center, normalization)
+    assert list(np.flatnonzero(S.empty)) == ([1, 3] if kind == "hanning" else [3])
+
+
+# ---- 2  large offset ---------------------------------------------------------------------------------------------------------------------
+def test_large_offset_is_removed_before_the_sums(L):
+    """y + 10^6, centred, fit_mean: the bounds are those of the centred terms (the docstring: no allowance for the mean is due with
+    fit_mean) -- sums of the uncentred signal would miss them by five orders."""
+    _run(L, 3, "hanning", True, True, "standard", offset=1e6)
+    small, big = _case1_refs("hanning", True, True, "standard"), _case1_refs("hanning", True, True, "standard", 1e6)
+    for s, b in zip(small, big):
+        if s is not None:
+            ok = ~s[0]["degenerate"]
+            assert np.all(b[1]["power"][ok] <= 1.001 * s[1]["power"][ok]), "the bounds are not to grow with the offset"
+
+
+# ---- 3  independence and reproducibility -------------------------------------------------------------------------------------------------
+def test_columns_do_not_depend_on_the_call(L):
+    t, y, W = _record()
+    f = _freqs()
+    wins = _windows()
+
+    def call(ysig, w):
+        S, co = L.lombscargle_spectrogram(ysig, t, f, windows=w, W=W, coef=True)
+        return [np.asarray(x) for x in (S.power, *co)]
+    full = call(y, wins)
+    for x, z in zip(full, call(y, wins)):
+        assert np.array_equal(x, z), "two calls give the same bits"
+    for w in range(9):
+        for x, z in zip(full, call(y, tuple(v[w:w + 1] for v in wins))):
+            assert z.shape == (NF, 1, NS) and np.array_equal(x[:, w], z[:, 0]), f"window {w} alone"
+    for x, z in zip(full, call(y, tuple(v[::-1].copy() for v in wins))):
+        assert np.array_equal(x, z[:, ::-1]), "the list reversed"
+    for x, z in zip(full, call(y[:, 0], wins)):
+        assert z.shape == (NF, 9) and np.array_equal(x[:, :, 0], z), "the first signal alone"
+
+
+# ---- 4  sample-count form on a uniform record ----------------------------------------------------------------------------------------------
+def test_sample_count_windows_on_a_uniform_record_are_hanning_weighted_fits(L):
+    """t = k / 64, n = 500, noverlap = 250, lo and hi the window's first and last time: the taper from time IS DSP.hanning(500)."""
+    _, y, _ = _record()
+    t, f = np.arange(N) / 64.0, _freqs(True)
+    Wn = L.Windows2(y[:, 0], t, 500, 250)
+    S, (a, b, c) = L.lombscargle_spectrogram(y[:, :3], t, f, n=500, noverlap=250, window=L.hanning, coef=True)
+    assert len(Wn) == 23 and S.power.shape == (NF, 23, 3) and np.array_equal(S.counts, np.full(23, 500)) and not S.empty.any()
+    assert np.array_equal(S.time, (t[Wn.offsets] + t[Wn.offsets + 499]) / 2)
+    h = L.hanning(500)
+    Th = float(np.max(np.abs(h.astype(LD) - _taper("hanning", t[:500], t[0], t[499]))))   # the reference's own weights against sin^2: 4 u here
+    assert Th <= 8 * U
+    refs = []
+    for o in Wn.offsets:
+        sl = slice(int(o), int(o) + 500)
+        r = lomb_ref(y[sl, :3], t[sl], f, W=h)
+        bs = _sum_bounds(r, t[sl], y[sl, :3], h, False)
+        # DSP.hanning in double (the reference's weights, Th from sin^2) against the device's taper from time (4 u from sin^2):
+        # T = 4 u + Th in the docstring's taper terms, with W = 1
+        T, Sg, hl, yc = 4 * U + Th, h.astype(LD).sum(), h.astype(LD), y[sl, :3].astype(LD) - r["removed"][None, :]
+        kappa, w = 500 / Sg, hl / Sg
+        for k in ("C", "S", "C2", "S2"):
+            bs[k] = bs[k] + 2 * T * kappa
+        tY = T * (np.abs(yc).sum(axis=0) / Sg + kappa * (w[:, None] * np.abs(yc)).sum(axis=0))
+        bs["YC"], bs["YS"], bs["Y"] = bs["YC"] + tY[:, None], bs["YS"] + tY[:, None], bs["Y"] + tY
+        bs["YY"] = bs["YY"] + T * ((yc * yc).sum(axis=0) / Sg + kappa * (w[:, None] * yc * yc).sum(axis=0))
+        refs.append((r, _epilogue_bounds(r, bs, True, False, 500)))
+    _compare({"power": S.power, "a": a, "b": b, "c": c}, refs, S.counts, 3, True)
+    P = L.lombscargle_spectrogram(y[:, 0], t, f)                               # the defaults: n = N >> 3, noverlap = n >> 1
+    assert P.power.shape == (NF, len(L.Windows2(y[:, 0], t)))
+
+
+# ---- 5  time_windows ---------------------------------------------------------------------------------------------------------------------
+def test_time_windows_are_searchsorted(L):
+    import torch
+    t = np.sort(np.random.default_rng(5).integers(0, 400, 1000)) / 4.0          # many ties
+    lo = np.array([-3.0, t[0], t[17], t[500], 50.125, t[-1], t[-1] + 1, 20.0, t[300]])
+    hi = np.array([-1.0, t[0], t[400], t[500], 50.125, t[-1] + 5, t[-1] + 2, t[-1], t[300] + 0.125])
+    want_s = np.searchsorted(t, lo, "left")
+    want_c = np.searchsorted(t, hi, "right") - want_s
+    for tt in (t, torch.tensor(t, device="cuda")):
+        s, c = L.time_windows(tt, lo, hi)
+        assert s.dtype == np.int64 and np.array_equal(s, want_s) and np.array_equal(c, want_c)
+    assert want_c[0] == 0 and want_c[4] == 0 and want_c[6] == 0 and want_s[6] == 1000 and want_c[3] >= 1
+    bad = t.copy(); bad[[10, 700]] = bad[[700, 10]]
+    with pytest.raises(ValueError, match="sorted"):
+        L.time_windows(bad, lo, hi)
+    with pytest.raises(ValueError, match="finite"):
+        L.time_windows(t, np.array([np.nan]), np.array([1.0]))
+
+
+def test_width_and_hop_give_the_windows_numpy_computes(L):
+    t, y, W = _record()
+    f = _freqs()
+    width, hop = 1500.0, 625.0
+    lo = []
+    while t[0] + len(lo) * hop <= t[-1]:
+        lo.append(t[0] + len(lo) * hop)
+    lo = np.array(lo); hi = lo + width
+    S = L.lombscargle_spectrogram(y[:, 0], t, f, width=width, hop=hop, W=W)
+    starts = np.searchsorted(t, lo, "left")
+    counts = np.searchsorted(t, hi, "right") - starts
+    assert S.power.shape == (NF, len(lo)) and np.array_equal(S.counts, counts) and np.array_equal(S.time, (lo + hi) / 2)
+    E = L.lombscargle_spectrogram(y[:, 0], t, f, windows=(starts, counts, lo, hi), W=W)
+    assert np.array_equal(S.power, E.power) and np.array_equal(S.empty, E.empty)
+    D = L.lombscargle_spectrogram(y[:, 0], t, f, width=width)                  # hop = width / 2
+    assert D.power.shape[1] == int(np.floor((t[-1] - t[0]) / 750.0)) + 1
+
+
+# ---- 6  lombscargle_welch ----------------------------------------------------------------------------------------------------------------
+def test_welch_is_the_mean_over_the_windows_that_are_not_empty(L):
+    t, y, W = _record()
+    f, wins = _freqs(), _windows()
+    S = L.lombscargle_spectrogram(y[:, :3], t, f, windows=wins, W=W, normalization="psd")
+    P = L.lombscargle_welch(y[:, :3], t, f, windows=wins, W=W, normalization="psd")
+    assert P.power.shape == (NF, 3) and np.array_equal(P.freq, f) and list(np.flatnonzero(S.empty)) == [1, 3]
+    cols = S.power[:, ~S.empty, :].astype(LD)
+    m = cols.shape[1]
+    err, bnd = np.abs(P.power.astype(LD) - cols.sum(axis=1) / m), (9 + 16) * U * np.abs(cols).sum(axis=1) / m
+    print("welch: worst error / bound:", _ratio(err, bnd))
+    assert m == 7 and np.all(err <= bnd)
+    assert np.array_equal(P.power, L.lombscargle_welch(y[:, :3], t, f, windows=wins, W=W, normalization="psd").power)
+    P1 = L.lombscargle_welch(y[:, 0], t, f, windows=wins, W=W, normalization="psd")
+    assert P1.power.shape == (NF,) and np.array_equal(P1.power, P.power[:, 0])
+    none = (np.array([5, 9, 6000]), np.zeros(3, dtype=np.int64), np.zeros(3), np.ones(3))
+    Z = L.lombscargle_welch(y[:, 0], t, f, windows=none)
+    assert np.all(Z.power == 0.0) and L.lombscargle_windows_last_timing()["empty"] == 3
+    assert L.lombscargle_spectrogram(y[:, 0], t, f, windows=none).empty.all()
+
+
+# ---- 7  errors ---------------------------------------------------------------------------------------------------------------------------
+def test_bad_inputs_raise_value_errors(L):
+    from lpvspectral_jl_amd._lib import check, lib, out_ptr
+    t, y, W = _record()
+    f, y0 = _freqs(), y[:, 0]
+    one = lambda s, c, a=0.0, b=1.0: (np.array([s]), np.array([c]), np.array([a]), np.array([b]))   # noqa: E731
+    with pytest.raises(ValueError, match="outside"):
+        L.lombscargle_spectrogram(y0, t, f, windows=one(5990, 11))
+    with pytest.raises(ValueError, match="outside"):
+        L.lombscargle_spectrogram(y0, t, f, windows=one(-1, 5))
+    with pytest.raises(ValueError, match="finite"):
+        L.lombscargle_spectrogram(y0, t, f, windows=one(0, 50, np.nan, 1.0))
+    Wn = W.copy(); Wn[5] = -0.25
+    with pytest.raises(ValueError, match="negative"):
+        L.lombscargle_spectrogram(y0, t, f, windows=one(0, 50), W=Wn)
+    yn = y0.copy(); yn[4000] = np.inf
+    with pytest.raises(ValueError, match="not finite"):
+        L.lombscargle_welch(yn, t, f, windows=one(0, 50))
+    with pytest.raises(ValueError, match="one form"):
+        L.lombscargle_spectrogram(y0, t, f, n=500, width=10.0)
+    with pytest.raises(ValueError, match="one form"):
+        L.lombscargle_welch(y0, t, f, hop=10.0, windows=one(0, 50))
+    with pytest.raises(ValueError, match="window"):
+        L.lombscargle_spectrogram(y0, t, f, n=500, window=np.hamming)
+    with pytest.raises(ValueError):
+        L.lombscargle_spectrogram(y0, t, f, n=500, normalization="density")
+    # coef together with average: refused by the library itself
+    s, c, a, b = one(0, 50)
+    power, co = np.zeros(NF), np.zeros(3 * NF)
+    yc, tc = np.ascontiguousarray(y0), np.ascontiguousarray(t)
+    with pytest.raises(ValueError, match="coef"):
+        check(lib().lpvs_lombscargle_windows_f64(out_ptr(yc), 1, out_ptr(tc), N, None, out_ptr(np.ascontiguousarray(f)), NF, out_ptr(s), out_ptr(c), out_ptr(a),
+                                                 out_ptr(b), 1, 1, 1, 1, 0, 1, 0, out_ptr(power), out_ptr(co), None))
+
+
+# ---- 8  surface --------------------------------------------------------------------------------------------------------------------------
+def test_heatmap_takes_the_spectrogram(L):
+    """heatmap skips the first frequency row, as for every Spectrogram (src/plotting.jl:15-36)."""
+    t, y, W = _record()
+    S = L.lombscargle_spectrogram(y[:, 0], t, _freqs(), width=1500.0, hop=625.0)
+    assert isinstance(S, L.Spectrogram) and not S.empty.any()
+    tt, ff, z = L.heatmap(S)
+    assert np.array_equal(tt, S.time) and np.array_equal(ff, S.freq[1:]) and z.shape == (NF - 1, S.power.shape[1]) and np.all(np.isfinite(z))
+    assert isinstance(L.lombscargle_welch(y[:, 0], t, _freqs(), width=1500.0), L.Periodogram)
