@@ -735,6 +735,36 @@ int32_t lpvs_lombscargle_windows_last_timing(double *out, int32_t n);
 int32_t lpvs_time_windows_f64(const double *t, int64_t N, const double *lo, const double *hi, int64_t nwin, int32_t device,
                               int64_t *starts_out, int64_t *counts_out);
 
+/* ---- g6  the bootstrap of the Lomb-Scargle periodogram: the maxima of the periodograms of B resamples of one record (extension; what
+ * false-alarm probabilities and levels are read from without assuming Gaussian errors).
+ * y: ONE signal of N samples; t, W, f and the flags as in g4.  Resample b >= 0 is y*_b[i] = y[pi_b(i)], t and W staying with the epochs
+ * (under the null hypothesis the values are exchangeable and the weights belong to the times; astropy draws (y, dy) PAIRS instead, which
+ * would make C, S, C2, S2 differ per resample: not done here).  The call computes the resamples row0 .. row0 + B - 1.
+ * THE STREAM.  Philox4x32-10 keyed as lpvs_randn_f64 keys it: key = the 64-bit seed, counter = (b, pair p = i >> 1), words w0 .. w3;
+ * sample 2p takes u = (w0 << 32) | w1, sample 2p + 1 takes u = (w2 << 32) | w3, and pi = (u N) >> 64, the high half of the 128-bit
+ * product: pi < N always, the bias is below N 2^-64, and a resample depends on (seed, b) only.
+ * Resample b's column of power IS the g4 estimate (same flags) of y[pi_b], t, W, f: the weights normalised by sum W, the weighted mean
+ * formed on the device in a fixed order and removed before the Fourier sums, the fit_mean terms, the degenerate rule, the constant-signal
+ * rule with N and the resample's own R and YY, phases from the exact products f t, both normalisations.
+ *   max_out (B, host or device): the largest power of the resample's column.
+ *   argmax_out (HOST, B int64, may be NULL): its frequency index; ties go to the lowest index.
+ *   mean_out (HOST, B, may be NULL): the weighted mean of each resample as the device formed it (computed also when it is not removed).
+ *   power_out (Nf x B column-major, host or device, may be NULL): the columns themselves, for small problems and tests; with NULL no
+ *     B x Nf array exists anywhere, and no B x N array of resamples ever does.
+ * FIXED ORDER.  Every sum is added in an order that depends on N and Nf only -- not on B, on row0, on how the call is cut into chunks, or
+ * on whether power_out was asked for: two calls give the same bits, and resample b has the same bits alone (B = 1, row0 = b) and among
+ * others.  Bit-equality with lpvs_lombscargle_f64 on the gathered signal is NOT promised (the additions come in another order).
+ * Errors: a non-finite t, y, W or f, a negative weight, sum W = 0, B < 1, row0 < 0, N < 1, Nf < 1 -> LPVS_EARGUMENT; N >= 2^31,
+ * Nf > 2^24, row0 + B > 2^40 or more resamples than one call takes (2^31 - 1) -> LPVS_EUNSUPPORTED.
+ * lpvs_lombscargle_bootstrap_last_timing (the calling thread's last call), out[0..11]: resamples, chunks, resamples per thread (TS), slab
+ * length, slabs, degenerate frequencies (counted once: they are those of the record), ms of the scan and the shared sums C, S, C2, S2,
+ * of the resamples' moments, of the bootstrap sums, of the epilogue and the maxima, of the copy-out, total. */
+int32_t lpvs_lombscargle_bootstrap_f64(const double *y, const double *t, int64_t N, const double *W, const double *f, int64_t Nf,
+                                       int64_t B, int64_t seed, int64_t row0, int32_t fit_mean, int32_t center_data,
+                                       int32_t normalization, int32_t device, double *max_out, int64_t *argmax_out, double *mean_out,
+                                       double *power_out);
+int32_t lpvs_lombscargle_bootstrap_last_timing(double *out, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,7 +21,8 @@ export ls_spectral, tls_spectral, ls_sparse_spectral, ls_sparse_spectral_lpv, ls
        SpectralExt, psd, reshape_params, ADMM, rect, hanning, autocov, autocor, isequidistant,
        melspectrogram, mfcc, mel, spectrogram, Spectrogram, MelSpectrogram, MFCC, freq, rand_cn, schedfunc,
        Periodogram, welch_pgram, periodogram, compress, heatmap, predict, residual, fva, lombscargle, lombscargle_last_timing,
-       lombscargle_spectrogram, lombscargle_welch, lombscargle_windows_last_timing, time_windows
+       lombscargle_spectrogram, lombscargle_welch, lombscargle_windows_last_timing, time_windows, lombscargle_bootstrap,
+       lombscargle_bootstrap_last_timing
 
 const LIB = get(ENV, "LPVSPECTRAL_LIB", joinpath(@__DIR__, "..", "lpvspectral.jl_amd", "liblpvspectral.so"))
 
@@ -1182,6 +1183,36 @@ function lombscargle_windows_last_timing()
     GC.@preserve tm check(@ccall LIB.lpvs_lombscargle_windows_last_timing(tm::Ptr{Float64}, Int32(10)::Int32)::Int32)
     (windows=Int(tm[1]), empty=Int(tm[2]), items=Int(tm[3]), slab=Int(tm[4]), degenerate=Int(tm[5]), moments_ms=tm[6], sums_ms=tm[7], epilogue_ms=tm[8],
      copy_ms=tm[9], total_ms=tm[10])
+end
+
+# ---- the bootstrap of the Lomb-Scargle periodogram (extension; include/lpvspectral.h g6) -------------------------------------------------
+"""    lombscargle_bootstrap(y, t, f=default_freqs(t); W=nothing, B=1000, seed=0, row0=0, fit_mean=true, center_data=true, normalization=:standard, power=false)
+The maxima of the `lombscargle` periodograms of the resamples `row0 .. row0 + B - 1` of ONE record (`t` and `W` stay with the epochs), formed
+on the device.  Returns `(maxima, argmax, means)` -- `argmax` 1-based -- and, with `power=true`, also the columns `Nf × B`."""
+function lombscargle_bootstrap(y::AbstractVector{<:Real}, t::AbstractVector{<:Real}, f::AbstractVector{<:Real}=default_freqs(t); W=nothing, B::Integer=1000,
+                               seed::Integer=0, row0::Integer=0, fit_mean::Bool=true, center_data::Bool=true, normalization::Symbol=:standard,
+                               device::Integer=0, power::Bool=false)
+    yv, tv, fv = Vector{Float64}(y), Vector{Float64}(t), Vector{Float64}(f)
+    N, Nf = length(tv), length(fv)
+    @assert length(yv) == N "y has to be as long as the sampling points"
+    Wv = W === nothing ? Float64[] : Vector{Float64}(W)
+    @assert W === nothing || length(Wv) == N "W has to be as long as the sampling points"
+    Wp = W === nothing ? Ptr{Float64}(C_NULL) : pointer(Wv)
+    nb = max(Int(B), 1)
+    maxima, argmax, means = zeros(nb), zeros(Int64, nb), zeros(nb)
+    pwv = power ? zeros(Nf, nb) : Float64[]
+    pwp = power ? pointer(pwv) : Ptr{Float64}(C_NULL)
+    GC.@preserve yv tv Wv fv maxima argmax means pwv check(@ccall LIB.lpvs_lombscargle_bootstrap_f64(yv::Ptr{Float64}, tv::Ptr{Float64}, Int64(N)::Int64,
+        Wp::Ptr{Float64}, fv::Ptr{Float64}, Int64(Nf)::Int64, Int64(B)::Int64, Int64(seed)::Int64, Int64(row0)::Int64, Int32(fit_mean)::Int32,
+        Int32(center_data)::Int32, LOMB_NORMALIZATIONS[normalization]::Int32, Int32(device)::Int32, maxima::Ptr{Float64}, argmax::Ptr{Int64},
+        means::Ptr{Float64}, pwp::Ptr{Float64})::Int32)
+    power ? (maxima, argmax .+ 1, means, pwv) : (maxima, argmax .+ 1, means)
+end
+function lombscargle_bootstrap_last_timing()
+    tm = zeros(12)
+    GC.@preserve tm check(@ccall LIB.lpvs_lombscargle_bootstrap_last_timing(tm::Ptr{Float64}, Int32(12)::Int32)::Int32)
+    (resamples=Int(tm[1]), chunks=Int(tm[2]), ts=Int(tm[3]), slab=Int(tm[4]), slabs=Int(tm[5]), degenerate=Int(tm[6]), shared_ms=tm[7], moments_ms=tm[8],
+     sums_ms=tm[9], epilogue_ms=tm[10], copy_ms=tm[11], total_ms=tm[12])
 end
 
 _quantile_pair(q::Number) = (q = q < 0.5 ? q : 1 - q; (Float64(q), Float64(1 - q)))                      # src/plotting.jl:39-44

@@ -2265,6 +2265,214 @@ def lombscargle_windows_last_timing():
             "sums_ms": float(o[6]), "epilogue_ms": float(o[7]), "copy_ms": float(o[8]), "total_ms": float(o[9])}
 
 
+# ---- false-alarm probabilities of the Lomb-Scargle periodogram: the device bootstrap and the closed forms (include/lpvspectral.h g6) ------
+_M32 = np.uint64(0xFFFFFFFF)
+
+
+def _philox4x32_10(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 on arrays of uint64 that hold 32-bit words (csrc/philox.h)."""
+    s32 = np.uint64(32)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ k0, p1 & _M32, (p0 >> s32) ^ c3 ^ k1, p0 & _M32
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & _M32, (k1 + np.uint64(0xBB67AE85)) & _M32
+    return c0, c1, c2, c3
+
+
+def _mulhi64(u, n):
+    """High 64 bits of the product of the uint64 arrays u and the integer n < 2^64 (32-bit limbs in uint64 arithmetic)."""
+    s32 = np.uint64(32)
+    nl, nh = np.uint64(n & 0xFFFFFFFF), np.uint64(n >> 32)
+    ul, uh = u & _M32, u >> s32
+    t1 = uh * nl + ((ul * nl) >> s32)
+    t2 = ul * nh + (t1 & _M32)
+    return uh * nh + (t1 >> s32) + (t2 >> s32)
+
+
+def bootstrap_indices(N, B, seed=0, row0=0, samples=None):
+    """The resampling indices of :func:`lombscargle_bootstrap` on the host: ``int64[B, N]``, row ``b`` holding ``π_{row0+b}(i)``, so that
+    resample ``row0 + b`` of a record ``y`` is ``y[indices[b]]``.
+
+    The stream: Philox4x32-10 as :func:`randn` keys it -- key = the 64-bit ``seed``, counter = (resample, pair ``i >> 1``), words
+    ``w0..w3``; sample ``2p`` takes ``u = (w0 << 32) | w1``, sample ``2p+1`` takes ``u = (w2 << 32) | w3``; ``π = (u N) >> 64``.  Every
+    index lies in ``[0, N)``; a resample depends on ``(seed, row0 + b)`` only.  ``samples``: only these sample positions ``i`` (columns),
+    for records too long to list."""
+    N, B, row0 = int(N), int(B), int(row0)
+    if N < 1 or B < 1 or row0 < 0 or N >= 1 << 63:
+        raise ValueError(f"bootstrap_indices: need N > 0, B > 0 and row0 >= 0 (N = {N}, B = {B}, row0 = {row0})")
+    i = np.arange(N, dtype=np.uint64) if samples is None else np.ravel(np.asarray(samples)).astype(np.uint64)
+    if len(i) and int(i.max()) >= N:
+        raise ValueError("bootstrap_indices: samples reach beyond N")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    b = (np.arange(B, dtype=np.uint64) + np.uint64(row0))[:, None]
+    p = (i >> np.uint64(1))[None, :]
+    b, p = np.broadcast_arrays(b, p)
+    w0, w1, w2, w3 = _philox4x32_10(b & _M32, b >> np.uint64(32), p & _M32, p >> np.uint64(32), np.uint64(seed & 0xFFFFFFFF), np.uint64(seed >> 32))
+    odd = (i & np.uint64(1)).astype(bool)[None, :]
+    u = np.where(odd, (w2 << np.uint64(32)) | w3, (w0 << np.uint64(32)) | w1)
+    return _mulhi64(u, N).astype(np.int64)
+
+
+def lombscargle_bootstrap(y, t, f=None, W=None, B=1000, seed=0, row0=0, fit_mean=True, center_data=True, normalization="standard", device=0,
+                          return_argmax=False, return_means=False, return_power=False):
+    """The maxima of the :func:`lombscargle` periodograms of ``B`` resamples of one record, on the device (extension; csrc/lomb_boot.hip):
+    what :func:`false_alarm_probability` and :func:`false_alarm_level` with ``method="bootstrap"`` are read from.
+
+    Resample ``b`` is ``y[π_b]`` (:func:`bootstrap_indices`, resamples ``row0 .. row0 + B - 1`` of ``seed``); ``t`` and ``W`` stay with
+    the epochs (astropy resamples ``(y, dy)`` pairs instead).  Each resample's periodogram is the :func:`lombscargle` estimate with the
+    same flags; only its maximum leaves the device: neither the resamples nor the ``B × Nf`` powers are ever stored.  Two calls give the
+    same bits, and a resample's result does not depend on ``B``, ``row0`` or the other resamples.
+
+    Returns the maxima ``(B,)``; with ``return_argmax`` / ``return_means`` / ``return_power`` a tuple that adds the frequency index of
+    each maximum (ties: the lowest), the weighted mean of each resample as the device formed it, and the columns ``(Nf, B)``."""
+    if normalization not in _LOMB_NORMALIZATIONS:
+        raise ValueError(f"normalization: unknown value {normalization!r} (known: {sorted(_LOMB_NORMALIZATIONS)})")
+    fa = np.ascontiguousarray(np.ravel(_host(default_freqs(t) if f is None else f)).astype(np.float64))
+    Nf, B = len(fa), int(B)
+    ya = _f64_arg(y)
+    if (ya.dim() if _lib.is_device_array(ya) else np.ndim(ya)) != 1:
+        raise ValueError("lombscargle_bootstrap: y is one signal (a vector)")
+    ky, py, N = as_f64(ya)
+    kt, pt, nt = as_f64(_f64_arg(t))
+    if nt != N:
+        raise ValueError(f"y has {N} samples, t has {nt}")
+    kw, pw, nw = as_f64(_f64_arg(W))
+    if W is not None and nw != N:
+        raise ValueError(f"y has {N} samples, W has {nw}")
+    nb = max(B, 1)
+    maxima, argmax, means = np.zeros(nb), np.zeros(nb, dtype=np.int64), np.zeros(nb)
+    power = np.zeros((Nf, nb), order="F") if return_power else None
+    check(lib().lpvs_lombscargle_bootstrap_f64(py, pt, N, pw, out_ptr(fa), Nf, B, int(seed), int(row0), int(bool(fit_mean)), int(bool(center_data)),
+                                               _LOMB_NORMALIZATIONS[normalization], int(device), out_ptr(maxima), out_ptr(argmax), out_ptr(means),
+                                               out_ptr(power) if return_power else None))
+    del ky, kt, kw
+    res = [maxima] + ([argmax] if return_argmax else []) + ([means] if return_means else []) + ([power] if return_power else [])
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+def lombscargle_bootstrap_last_timing():
+    """Plan and timing of the calling thread's last :func:`lombscargle_bootstrap`."""
+    o = np.zeros(12)
+    check(lib().lpvs_lombscargle_bootstrap_last_timing(out_ptr(o), 12))
+    return {"resamples": int(o[0]), "chunks": int(o[1]), "ts": int(o[2]), "slab": int(o[3]), "slabs": int(o[4]), "degenerate": int(o[5]),
+            "shared_ms": float(o[6]), "moments_ms": float(o[7]), "sums_ms": float(o[8]), "epilogue_ms": float(o[9]), "copy_ms": float(o[10]),
+            "total_ms": float(o[11])}
+
+
+_FAP_METHODS = ("naive", "davies", "baluev", "bootstrap")
+_LDF = np.longdouble
+
+
+def _fap_setup(y, t, f, W, fit_mean, center_data, normalization, method):
+    """(N_H, N_K, f_max T, gamma(N_H) f_max sqrt(4 pi Var_w t)) of the analytic methods, as long doubles."""
+    import math
+    if normalization != "standard":
+        raise ValueError(f"method {method!r} is defined for normalization='standard' only (the null distribution of 'psd' needs the noise variance); "
+                         "use method='bootstrap'")
+    th = np.ravel(_host(t)).astype(np.float64)
+    N = len(th)
+    fa = np.ravel(_host(default_freqs(t) if f is None else f)).astype(np.float64)
+    NH = N - (1 if (fit_mean or center_data) else 0)
+    NK = NH - 2
+    if NK < 2:
+        raise ValueError(f"false alarm: {N} samples are too few")
+    fmax = _LDF(fa.max())
+    tl = th.astype(_LDF)
+    w = np.ones(N, dtype=_LDF) if W is None else np.ravel(_host(W)).astype(np.float64).astype(_LDF)
+    w = w / w.sum()
+    var = (w * tl * tl).sum() - (w * tl).sum() ** 2
+    gam = np.sqrt(_LDF(2) / NH) * np.exp(_LDF(math.lgamma(NH / 2) - math.lgamma((NH - 1) / 2)))
+    pi = np.arccos(_LDF(-1))
+    return NH, NK, fmax * (tl.max() - tl.min()), gam * fmax * np.sqrt(4 * pi * var)
+
+
+def _fap_analytic(z, method, NH, NK, neff, tau0):
+    """The false-alarm probability of the peak heights z (long doubles) by one of the closed forms."""
+    one = _LDF(1)
+    lz = np.log1p(-z)                                                         # log(1 - z)
+    single = np.exp(_LDF(NK) / 2 * lz)
+    if method == "naive":
+        return -np.expm1(neff * np.log1p(-single))
+    tau = tau0 * np.exp(_LDF(NK - 1) / 2 * lz) * np.sqrt(_LDF(NH) * z / 2)
+    if method == "davies":
+        return single + tau
+    return -np.expm1(np.log1p(-single) - tau)                                 # baluev: 1 - (1 - single) exp(-tau)
+
+
+def _bootstrap_maxima(y, t, f, W, fit_mean, center_data, normalization, B, seed, maxima, device):
+    if maxima is not None:
+        M = np.ravel(np.asarray(maxima, dtype=np.float64))
+        if len(M) < 1:
+            raise ValueError("maxima: empty")
+        return M
+    return lombscargle_bootstrap(y, t, f, W=W, B=B, seed=seed, fit_mean=fit_mean, center_data=center_data, normalization=normalization, device=device)
+
+
+def false_alarm_probability(power, y, t, f=None, W=None, method="baluev", fit_mean=True, center_data=True, normalization="standard", B=1000, seed=0,
+                            maxima=None, device=0):
+    """The probability that noise alone gives a highest periodogram peak of at least ``power`` (a scalar or an array; the result has its
+    shape) for the record ``y, t, W`` and the grid ``f`` of :func:`lombscargle`.
+
+    ``method``: ``"naive"``, ``"davies"``, ``"baluev"`` -- closed forms for ``normalization="standard"`` (ValueError for ``"psd"``), with
+    ``N_H = N - d_H`` (``d_H = 1`` if ``fit_mean or center_data``), ``N_K = N_H - 2``, ``single = (1 - z)^(N_K/2)``, ``T = max t - min t``,
+    ``τ = γ(N_H) f_max √(4π Var_w t) (1 - z)^((N_K-1)/2) √(N_H z / 2)``, ``γ(n) = √(2/n) exp(lgamma(n/2) - lgamma((n-1)/2))``:
+    ``naive = 1 - (1 - single)^(f_max T)``, ``davies = single + τ``, ``baluev = 1 - (1 - single) e^{-τ}`` -- or ``"bootstrap"``: the
+    distribution-free estimate ``#{M_b ≥ z} / B`` from the maxima ``M_b`` of ``B`` resampled periodograms (:func:`lombscargle_bootstrap`,
+    with ``seed`` and the estimator's flags, either normalisation); ``maxima``: the maxima of an earlier call, to reuse them."""
+    if method not in _FAP_METHODS:
+        raise ValueError(f"method: unknown value {method!r} (known: {list(_FAP_METHODS)})")
+    z = np.asarray(power, dtype=np.float64)
+    if method == "bootstrap":
+        M = np.sort(_bootstrap_maxima(y, t, f, W, fit_mean, center_data, normalization, B, seed, maxima, device))
+        res = (len(M) - np.searchsorted(M, z, side="left")) / len(M)           # #{M >= z} / B
+    else:
+        NH, NK, neff, tau0 = _fap_setup(y, t, f, W, fit_mean, center_data, normalization, method)
+        res = np.asarray(_fap_analytic(z.astype(_LDF), method, NH, NK, neff, tau0), dtype=np.float64)
+    return float(res) if np.ndim(power) == 0 else res
+
+
+def false_alarm_level(probability, y, t, f=None, W=None, method="baluev", fit_mean=True, center_data=True, normalization="standard", B=1000, seed=0,
+                      maxima=None, device=0):
+    """The peak height whose :func:`false_alarm_probability` is ``probability`` (a scalar or an array), by the same ``method``.
+
+    ``"naive"`` is inverted in closed form; ``"davies"`` and ``"baluev"`` by bisection on ``[1/N_K, 1)``, where both decrease (``τ`` peaks
+    at ``z = 1/N_K``), until the bracket no longer shrinks -- a probability above the value at ``1/N_K`` raises ValueError;
+    ``"bootstrap"``: the order statistic ``M_(k)``, the k-th smallest maximum with ``k = clamp(ceil((1 - p) B), 1, B)``, no interpolation."""
+    import math
+    if method not in _FAP_METHODS:
+        raise ValueError(f"method: unknown value {method!r} (known: {list(_FAP_METHODS)})")
+    p = np.asarray(probability, dtype=np.float64)
+    if np.any(~(p > 0)) or np.any(~(p <= 1)):
+        raise ValueError("probability: values in (0, 1] are needed")
+    flat = np.ravel(p)
+    if method == "bootstrap":
+        M = np.sort(_bootstrap_maxima(y, t, f, W, fit_mean, center_data, normalization, B, seed, maxima, device))
+        nb = len(M)
+        out = np.array([M[min(max(math.ceil((1.0 - float(q)) * nb), 1), nb) - 1] for q in flat])
+    else:
+        NH, NK, neff, tau0 = _fap_setup(y, t, f, W, fit_mean, center_data, normalization, method)
+        out = np.zeros(len(flat))
+        for i, q in enumerate(flat):
+            ql = _LDF(q)
+            if method == "naive":
+                single = -np.expm1(np.log1p(-ql) / neff) if q < 1 else _LDF(1)
+                out[i] = float(-np.expm1(np.log(single) * 2 / _LDF(NK)))
+                continue
+            lo, hi = _LDF(1) / NK, _LDF(1)
+            if _fap_analytic(lo, method, NH, NK, neff, tau0) < ql:
+                raise ValueError(f"probability {q} is above the {method} value at z = 1/N_K, beyond which the bound does not decrease")
+            while True:                                                        # fap(lo) >= q > fap(hi)
+                mid = lo + (hi - lo) / 2
+                if not (lo < mid < hi):
+                    break
+                if _fap_analytic(mid, method, NH, NK, neff, tau0) >= ql:
+                    lo = mid
+                else:
+                    hi = mid
+            out[i] = float(lo)
+    return float(out[0]) if np.ndim(probability) == 0 else out.reshape(p.shape)
+
+
 def compress_last_timing():
     """Plan and HIP-event times (ms) of this thread's last compress / heatmap call."""
     o = np.zeros(5)

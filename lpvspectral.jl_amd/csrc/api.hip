@@ -1717,6 +1717,132 @@ int32_t lpvs_time_windows_f64(const double *t, int64_t N, const double *lo, cons
     } catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
 }
 
+// ---- the bootstrap of the Lomb-Scargle periodogram (lomb_boot.hip; the decisions: lomb_boot_plan.h) ------------------------------------------
+// what lpvs_lombscargle_bootstrap_last_timing reports of the calling thread's last call: [0] resamples, [1] chunks, [2] resamples per thread
+// (TS), [3] slab length, [4] slabs, [5] degenerate frequencies, ms of [6] staging, the scan and the shared sums of the record, [7] the
+// moments of the resamples, [8] the bootstrap sums, [9] the epilogue and the maxima, [10] the copy-out, [11] total
+static thread_local double g_lomb_boot_timing[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+static int32_t lomb_boot_impl(const double *y, const double *t, int64_t N, const double *W, const std::vector<double> &hf, int64_t B, int64_t seed, int64_t row0,
+                              bool fit_mean, bool center, bool psd, int32_t device, const LombBootPlan &plan, double *max_out, int64_t *argmax_out, double *mean_out,
+                              double *power_out) {
+    const int64_t Nf = (int64_t)hf.size();
+    if (lpvs_device_count() == 0) { set_error("no HIP device visible (the gfx950 path has no CPU fallback)"); return LPVS_EDEVICE; }
+    LPVS_HIP(hipSetDevice(device));
+    hipStream_t s = nullptr;
+    Events<5> ev;
+    for (auto &e : ev.e) LPVS_HIP(hipEventCreate(&e));
+    struct ChunkEvents {                                                     // a chunk: before its sums, between sums and epilogue, after the epilogue
+        hipEvent_t a = nullptr, b = nullptr, c = nullptr;
+        ~ChunkEvents() { for (hipEvent_t x : {a, b, c}) if (x) (void)hipEventDestroy(x); }
+    };
+    std::vector<ChunkEvents> cev((size_t)plan.nchunks);
+    DevArg dt, dy, dW; DevOut dmax, dpower;
+    DevBuf dw, dwy, dsmall, dscan, dshared, dfreq, dslab, dmom, dargmax, dpart, dsums;
+    DrainOnExit drain(s);
+    LPVS_HIP(hipEventRecord(ev.e[0], s));
+    LPVS_TRY(dt.set(t, N, s));
+    LPVS_TRY(dy.set(y, N, s));
+    if (W) LPVS_TRY(dW.set(W, N, s));
+    LPVS_TRY(dmax.set(max_out, B));
+    if (power_out) LPVS_TRY(dpower.set(power_out, Nf * B));
+    // the observed record, as g4 takes it: the scan (sum W, the refusals), the normalised weights, and C, S, C2, S2 by the direct path's
+    // kernels with one signal (small record: [0] sum W, [1] mean, [2 .. 4] moments, then two ints: flags, degenerate count)
+    LPVS_TRY(dsmall.alloc(sizeof(double) * 6));
+    double *sumW_dev = dsmall.as<double>(), *mean1_dev = sumW_dev + 1, *mom1_dev = mean1_dev + 1;
+    int *flags_dev = reinterpret_cast<int *>(sumW_dev + 5), *ndeg_dev = flags_dev + 1;
+    LPVS_TRY(dscan.alloc(sizeof(double) * (size_t)(3 * lomb_sum_slabs(N))));
+    LPVS_TRY(launch_lomb_scan(dt.p, dy.p, dW.p, N, 1, flags_dev, dscan.as<double>(), sumW_dev, s));
+    double sumW = 0; int flags = 0;
+    LPVS_TRY(copy_from_device(&sumW, sumW_dev, sizeof(double), s));
+    LPVS_TRY(copy_from_device(&flags, flags_dev, sizeof(int), s));
+    if (flags & 1) { set_error("lombscargle: t, y or W holds a value that is not finite"); return LPVS_EARGUMENT; }
+    if (flags & 2) { set_error("lombscargle: a weight is negative"); return LPVS_EARGUMENT; }
+    if (!(sumW > 0.0) || !std::isfinite(sumW)) { set_error("lombscargle: the weights sum to %g", sumW); return LPVS_EARGUMENT; }
+    LPVS_TRY(dw.alloc(sizeof(double) * (size_t)N));
+    LPVS_TRY(dwy.alloc(sizeof(double) * (size_t)N));
+    LPVS_TRY(launch_lomb_moments(dy.p, dW.p, N, 1, sumW, center, dw.as<double>(), dwy.as<double>(), mean1_dev, mom1_dev, dscan.as<double>(), s));
+    const LombTiling tl = lomb_tiling(N, Nf, 1);
+    LPVS_TRY(dfreq.alloc(sizeof(double) * (size_t)Nf));
+    LPVS_TRY(copy_to_device(dfreq.p, hf.data(), sizeof(double) * (size_t)Nf, s));
+    LPVS_TRY(dslab.alloc(sizeof(double) * (size_t)(tl.nslab * 6 * Nf)));
+    LPVS_TRY(dshared.alloc(sizeof(double) * (size_t)(6 * Nf)));              // rows C, S, C2, S2 (and the record's own YC, YS, not used)
+    LPVS_TRY(launch_lomb_direct(dt.p, dw.as<double>(), dwy.as<double>(), N, 1, dfreq.as<double>(), Nf, tl, dslab.as<double>(), dshared.as<double>(), s));
+    dslab.release();
+    LPVS_HIP(hipEventRecord(ev.e[1], s));
+    // the resamples' moments: mean[B], then {Y, YY, R, -} per resample
+    LPVS_TRY(dmom.alloc(sizeof(double) * (size_t)(5 * B)));
+    double *mean_dev = dmom.as<double>(), *mom_dev = mean_dev + B;
+    LPVS_TRY(dargmax.alloc(sizeof(int64_t) * (size_t)B));
+    LPVS_TRY(launch_lomb_boot_moments(dy.p, dw.as<double>(), N, seed, row0, B, center, mean_dev, mom_dev, s));
+    LPVS_HIP(hipEventRecord(ev.e[2], s));
+    LPVS_HIP(hipMemsetAsync(ndeg_dev, 0, sizeof(int), s));
+    LPVS_TRY(dpart.alloc(sizeof(double) * (size_t)plan.part_doubles));
+    LPVS_TRY(dsums.alloc(sizeof(double) * (size_t)(2 * plan.chunk * Nf)));
+    for (int64_t c = 0; c < plan.nchunks; ++c) {
+        const int64_t r0 = c * plan.chunk, count = c + 1 < plan.nchunks ? plan.chunk : plan.last_chunk;
+        ChunkEvents &ce = cev[(size_t)c];
+        LPVS_HIP(hipEventCreate(&ce.a)); LPVS_HIP(hipEventCreate(&ce.b)); LPVS_HIP(hipEventCreate(&ce.c));
+        LPVS_HIP(hipEventRecord(ce.a, s));
+        LPVS_TRY(launch_lomb_boot_sums(dt.p, dw.as<double>(), dy.p, N, seed, row0, r0, count, center ? mean_dev : nullptr, dfreq.as<double>(), Nf, plan,
+                                       dpart.as<double>(), dsums.as<double>(), s));
+        LPVS_HIP(hipEventRecord(ce.b, s));
+        LPVS_TRY(launch_lomb_boot_epilogue(dshared.as<double>(), dsums.as<double>(), Nf, r0, count, mean_dev, mom_dev, fit_mean, center, psd, N,
+                                           power_out ? dpower.p : nullptr, dmax.p, dargmax.as<int64_t>(), c == 0, ndeg_dev, s));
+        LPVS_HIP(hipEventRecord(ce.c, s));
+    }
+    LPVS_HIP(hipEventRecord(ev.e[3], s));
+    int ndeg = 0;
+    LPVS_TRY(copy_from_device(&ndeg, ndeg_dev, sizeof(int), s));
+    if (argmax_out) LPVS_TRY(copy_from_device(argmax_out, dargmax.p, sizeof(int64_t) * (size_t)B, s));
+    if (mean_out) LPVS_TRY(copy_from_device(mean_out, mean_dev, sizeof(double) * (size_t)B, s));
+    LPVS_TRY(dmax.finish(s));
+    if (power_out) LPVS_TRY(dpower.finish(s));
+    LPVS_HIP(hipEventRecord(ev.e[4], s));
+    LPVS_HIP(hipStreamSynchronize(s));
+    float shared_ms = 0, mom_ms = 0, copy_ms = 0, total = 0;
+    LPVS_HIP(hipEventElapsedTime(&shared_ms, ev.e[0], ev.e[1]));
+    LPVS_HIP(hipEventElapsedTime(&mom_ms, ev.e[1], ev.e[2]));
+    LPVS_HIP(hipEventElapsedTime(&copy_ms, ev.e[3], ev.e[4]));
+    LPVS_HIP(hipEventElapsedTime(&total, ev.e[0], ev.e[4]));
+    double sums_ms = 0, epi_ms = 0;
+    for (int64_t c = 0; c < plan.nchunks; ++c) {
+        float x = 0, z = 0;
+        LPVS_HIP(hipEventElapsedTime(&x, cev[(size_t)c].a, cev[(size_t)c].b));
+        LPVS_HIP(hipEventElapsedTime(&z, cev[(size_t)c].b, cev[(size_t)c].c));
+        sums_ms += x; epi_ms += z;
+    }
+    double *g = g_lomb_boot_timing;
+    g[0] = (double)B; g[1] = (double)plan.nchunks; g[2] = plan.ts; g[3] = (double)plan.slab_samples; g[4] = (double)plan.nslab; g[5] = ndeg;
+    g[6] = shared_ms; g[7] = mom_ms; g[8] = sums_ms; g[9] = epi_ms; g[10] = copy_ms; g[11] = total;
+    return LPVS_OK;
+}
+
+int32_t lpvs_lombscargle_bootstrap_f64(const double *y, const double *t, int64_t N, const double *W, const double *f, int64_t Nf, int64_t B, int64_t seed, int64_t row0,
+                                       int32_t fit_mean, int32_t center_data, int32_t normalization, int32_t device, double *max_out, int64_t *argmax_out,
+                                       double *mean_out, double *power_out) {
+    try {
+        if (!y || !t || !f || !max_out) { set_error("NULL argument"); return LPVS_EARGUMENT; }
+        const char *ts_knob = experiment_env("LPVS_LOMB_BOOT_TS"), *mb_knob = experiment_env("LPVS_LOMB_BOOT_MB");
+        const LombBootPlan plan = lomb_boot_plan(N, Nf, B, row0, ts_knob ? atoll(ts_knob) : 0, mb_knob ? atof(mb_knob) : 0.0);
+        if (plan.status != kLombBootOk) { set_error("%s", plan.why.c_str()); return plan.status == kLombBootArgument ? LPVS_EARGUMENT : LPVS_EUNSUPPORTED; }
+        if (normalization != LPVS_LOMB_STANDARD && normalization != LPVS_LOMB_PSD) { set_error("normalization must be 0 (standard) or 1 (psd), got %d", normalization); return LPVS_EARGUMENT; }
+        if (is_device_ptr(f) || (argmax_out && is_device_ptr(argmax_out)) || (mean_out && is_device_ptr(mean_out))) {
+            set_error("lombscargle_bootstrap: f, argmax_out and mean_out are host memory"); return LPVS_EARGUMENT;
+        }
+        std::vector<double> hf(f, f + Nf);
+        for (double v : hf)
+            if (!std::isfinite(v)) { set_error("lombscargle: a frequency is not finite"); return LPVS_EARGUMENT; }
+        return lomb_boot_impl(y, t, N, W, hf, B, seed, row0, fit_mean != 0, center_data != 0, normalization == LPVS_LOMB_PSD, device, plan, max_out, argmax_out,
+                              mean_out, power_out);
+    } catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
+}
+
+int32_t lpvs_lombscargle_bootstrap_last_timing(double *out, int32_t n) {
+    if (!out || n < 0) { set_error("NULL argument"); return LPVS_EARGUMENT; }
+    for (int32_t k = 0; k < n && k < 12; ++k) out[k] = g_lomb_boot_timing[k];
+    return LPVS_OK;
+}
+
 int32_t lpvs_problem_create_lpv_rows_f64(const double *Y, int64_t ns, const double *X, const double *V, int64_t N_local, const double *w,
                                          int64_t Nf, int64_t Nv, int32_t normalize, int32_t coulomb, const double *ranges4,
                                          int32_t device, lpvs_problem **out) {

@@ -14,6 +14,7 @@
 //                     angle(d)) as sortable keys in LDS, a bitonic sort, two order statistics and the fixed-order mean.
 //   5. covariance     cov of a tall matrix with few columns (the sample-matrix constructors): two fixed-order block reductions.
 #include "lpvs_internal.h"
+#include "philox.h"
 
 #include <cmath>
 #include <cstring>
@@ -175,16 +176,7 @@ int32_t factor_device(const double *V, int64_t n2, DevBuf &W, int64_t *np_out, h
 }
 
 // ---- 2. normals -------------------------------------------------------------------------------------------------------------------------
-struct U4 { uint32_t w[4]; };
-__host__ __device__ inline U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return U4{{c0, c1, c2, c3}};
-}
+// (philox4x32_10: philox.h, shared with the resampling indices of lomb_boot.hip)
 // the two normals of (row, column pair): columns 2 pair and 2 pair + 1
 __device__ inline void normal_pair(uint64_t seed, uint64_t row, uint64_t pair, double *z0, double *z1) {
     const U4 u = philox4x32_10((uint32_t)row, (uint32_t)(row >> 32), (uint32_t)pair, (uint32_t)(pair >> 32), (uint32_t)seed, (uint32_t)(seed >> 32));

@@ -26,33 +26,12 @@
 // signal) and the average over the windows that are not empty.  lomb_time_windows_kernel: the index range of a time interval.
 #include "lpvs_internal.h"
 #include "lomb_plan.h"
+#include "lomb_device.h"
 
 namespace lpvs {
 namespace {
 
-constexpr int LB_TF = kLombFreqTile, LB_LANES = kLombSampleLanes, LB_STAGE = kLombStage;
-static_assert(LB_TF * LB_LANES == 256 && LB_STAGE == 256 && kLombSumBlock == 256, "the kernels are written for 256 threads");
-
-// sum over the workgroup's 256 threads in a pairwise tree (every thread calls it)
-__device__ inline double lomb_block_sum(double v, double *red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
-// cos, sin of 2 pi f t from the exact product
-__device__ inline void lomb_sincos(double f, double t, double *sn, double *cs) {
-    const double p = f * t, e = fma(f, t, -p);
-    const double r = (p - rint(p)) + e;               // turns in [-1/2, 1/2] (+ e); p - rint(p) is exact
-    sincospi(2.0 * r, sn, cs);
-}
-
+// (lomb_block_sum, lomb_sincos, lomb_lane_sum, lomb_pairwise and lomb_fit: lomb_device.h, shared with lomb_boot.hip)
 // ---- moments ---------------------------------------------------------------------------------------------------------------------------
 // flags: bit 0 a non-finite t, y or W, bit 1 a negative weight (integer OR: order-free); part[workgroup] = sum of W over its 256 samples
 __global__ void __launch_bounds__(256)
@@ -145,9 +124,6 @@ __device__ inline void lomb_walk_stage(double fv, const double *st, const double
         }
     }
 }
-// the four sample lanes of one accumulator, added as (0 + 1) + (2 + 3)
-__device__ inline double lomb_lane_sum(const double (*red)[LB_TF], int fl) { return (red[0][fl] + red[1][fl]) + (red[2][fl] + red[3][fl]); }
-
 // ---- direct path: workgroup (tile of 64 frequencies, slab of samples, block of TS signals) ---------------------------------------------
 // part[(slab nrow + row) Nf + k], nrow = 4 + 2 ns: rows C, S, C2, S2 (written by signal block 0), then YC_c, YS_c
 template <int TS>
@@ -192,22 +168,7 @@ lomb_direct_kernel(const double *__restrict__ t, const double *__restrict__ w, c
     }
 }
 
-// sums[e] = pairwise tree over the slabs of part[slab][e], e < nrow Nf: slabs 2i and 2i + 1 first, then pairs of pairs, ... (a binary
-// counter of partial sums), what is left over added from the smallest piece up
-__device__ inline double lomb_pairwise(const double *__restrict__ p, int64_t stride, int64_t n) {
-    double stack[12];                                                      // n <= kLombMaxSlabs = 2^10
-    for (int64_t i = 0; i < n; ++i) {
-        double v = p[i * stride];
-        int b = 0;
-        for (; (i >> b) & 1; ++b) v = stack[b] + v;
-        stack[b] = v;
-    }
-    double r = 0.0;
-    bool have = false;
-    for (int b = 0; b < 12; ++b)
-        if ((n >> b) & 1) { r = have ? stack[b] + r : stack[b]; have = true; }
-    return r;
-}
+// sums[e] = lomb_pairwise over the slabs of part[slab][e], e < nrow Nf
 __global__ void __launch_bounds__(256) lomb_slab_sum_kernel(const double *__restrict__ part, int64_t nslab, int64_t count, double *__restrict__ sums) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= count) return;
@@ -259,33 +220,6 @@ lomb_combine_kernel(const double *__restrict__ tab, int nq, int nre, int prephas
 
 // ---- epilogue: one thread per (frequency, signal) --------------------------------------------------------------------------------------
 // mom[2 c + {0, 1}] = Y_c, YY_c of the (centred) signal, mom[2 ns + c] = sum w y_c^2 of the signal as given; mean[c]: its weighted mean.
-// CONSTANT SIGNALS.  The standard power is 0 when YY is within rounding of 0 (lomb_yy_noise of lomb_plan.h), not only when it is exactly 0:
-// a constant signal with unequal weights leaves a YY that is a rounding residue, and p / YY would be a quotient of two noise terms.
-struct LombFit { double pw, a, b, c; bool degenerate; };
-// the fit of one (frequency, signal) from its sums: R = sum w y^2 of the signal as given, removed = the mean that centring took out
-__device__ inline LombFit lomb_fit(double C, double S, double C2, double S2, double YC, double YS, double Y, double YY, double R, double removed, int fit_mean,
-                                   int center, int psd, double Nsamples) {
-    const double yy_noise = lomb_yy_noise(Nsamples, center != 0, fit_mean != 0, R, YY);
-    double CC = 0.5 * (1.0 + C2), SS = 0.5 * (1.0 - C2), CS = 0.5 * S2;
-    const double scale = CC + SS;
-    if (fit_mean) {
-        YY = fma(-Y, Y, YY); YC = fma(-Y, C, YC); YS = fma(-Y, S, YS);
-        CC = fma(-C, C, CC); SS = fma(-S, S, SS); CS = fma(-C, S, CS);
-    }
-    const double D = fma(CC, SS, -(CS * CS));
-    LombFit r = {0.0, 0.0, 0.0, removed + (fit_mean ? Y : 0.0), false};
-    if (!(D > kLombDegenerate * (scale * scale))) {
-        r.degenerate = true;
-        r.c = 0.0;
-    } else {
-        const double p = (fma(SS * YC, YC, (CC * YS) * YS) - 2.0 * ((CS * YC) * YS)) / D;
-        r.a = fma(SS, YC, -(CS * YS)) / D;
-        r.b = fma(CC, YS, -(CS * YC)) / D;
-        if (fit_mean) r.c = removed + ((Y - r.a * C) - r.b * S);
-        r.pw = psd ? p * (0.5 * Nsamples) : (YY > yy_noise ? p / YY : 0.0);
-    }
-    return r;
-}
 __global__ void __launch_bounds__(256)
 lomb_epilogue_kernel(const double *__restrict__ sums, int64_t Nf, int ns, const double *__restrict__ mom, const double *__restrict__ mean, int fit_mean,
                      int center, int psd, double Nsamples, double *__restrict__ power, double *__restrict__ coef, int *__restrict__ ndegenerate) {

@@ -14,6 +14,7 @@
 #include "gram_form_plan.h"
 #include "eval_plan.h"
 #include "lomb_plan.h"
+#include "lomb_boot_plan.h"
 
 namespace lpvs {
 
@@ -267,6 +268,18 @@ int32_t launch_lomb_windows_epilogue(const LombWindows &A, const double *sums, i
 int32_t launch_lomb_windows_average(const double *cols, int64_t Nf, int64_t nwin, int64_t ns, const int32_t *empty, double *out, hipStream_t s);
 // flags_dev (zeroed here) |= 1: a non-finite t, |= 8: t decreases somewhere; edges[2 w] = #{t < lo_w}, edges[2 w + 1] = #{t <= hi_w}
 int32_t launch_lomb_time_windows(const double *t, int64_t N, const double *lo, const double *hi, int64_t nwin, int *flags_dev, int64_t *edges, hipStream_t s);
+
+// bootstrap (lpvs_lombscargle_bootstrap_f64; lomb_boot.hip; the decisions: lomb_boot_plan.h).  All pointers are device memory; resamples are counted from row0.
+// mean[B], mom[4 B] = {Y, YY of the resample less what centring removes, R = sum w y*^2, unused}; w: the normalised weights of the record
+int32_t launch_lomb_boot_moments(const double *y, const double *w, int64_t N, int64_t seed, int64_t row0, int64_t B, bool center, double *mean, double *mom,
+                                 hipStream_t s);
+// sums[2 count][Nf] = YC, YS of the resamples r0 .. r0 + count - 1; part: plan.nslab * 2 count * Nf doubles
+int32_t launch_lomb_boot_sums(const double *t, const double *w, const double *y, int64_t N, int64_t seed, int64_t row0, int64_t r0, int64_t count,
+                              const double *mean_or_null, const double *f_dev, int64_t Nf, const LombBootPlan &plan, double *part, double *sums, hipStream_t s);
+// shared[4][Nf] = C, S, C2, S2 of the record; power_or_null: Nf x B; maxv[B], maxi[B]; ndeg_dev += the degenerate frequencies when count_deg
+int32_t launch_lomb_boot_epilogue(const double *shared, const double *sums, int64_t Nf, int64_t r0, int64_t count, const double *mean, const double *mom,
+                                  bool fit_mean, bool center, bool psd, int64_t N, double *power_or_null, double *maxv, int64_t *maxi, bool count_deg, int *ndeg_dev,
+                                  hipStream_t s);
 
 // ---- dense symmetric inverse (linalg.hip) ------------------------------------------------
 // In-place inverse of the SPD matrix A (np x np, np % 64 == 0, full symmetric storage) by
