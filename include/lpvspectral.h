@@ -765,6 +765,42 @@ int32_t lpvs_lombscargle_bootstrap_f64(const double *y, const double *t, int64_t
                                        double *power_out);
 int32_t lpvs_lombscargle_bootstrap_last_timing(double *out, int32_t n);
 
+/* ---- g7  Lomb-Scargle with several harmonics per frequency (extension; astropy's nterms, Palmer's fast chi^2): at every frequency
+ *   y ~ c + sum_{h = 1 .. K} a_h cos(h phi) + b_h sin(h phi),  K = nterms in 1 .. 6,
+ * in weighted least squares.  y, t, W, f, the phases phi = 2 pi (f t) of the exact products, center_data and the moments as in g4.
+ * SUMS.  With w = W / sum W and y_c the (optionally centred) signal:
+ *   C_m = sum w cos m phi, S_m = sum w sin m phi (m = 1 .. 2K; C_0 = 1, S_0 = 0);  YC_h = sum w y_c cos h phi, YS_h = sum w y_c sin h phi
+ *   (h = 1 .. K);  Y = sum w y_c, YY = sum w y_c^2.  One sincospi per (sample, frequency); the harmonics follow by complex rotation.
+ * NORMAL EQUATIONS.  Unknowns in the order (a_1, b_1, a_2, b_2, ...), n = 2K.  For the harmonics h and j:
+ *   A[cos h, cos j] = (C_|h-j| + C_{h+j}) / 2,  A[sin h, sin j] = (C_|h-j| - C_{h+j}) / 2,  A[cos h, sin j] = (S_{h+j} + sgn(j - h) S_|j-h|) / 2,
+ *   g = (C_1, S_1, C_2, S_2, ...),  b = (YC_1, YS_1, ...).  fit_mean eliminates the constant: A -= g g^T, b -= Y g, YY -= Y^2.
+ *   For K = 1 these are g4's formulas.
+ * FIT.  A = L D L^T in that order without pivoting (pivots d_j);  theta = A^-1 b,  p = b^T theta;
+ *   power_out (Nf x ns column-major): LPVS_LOMB_STANDARD p / YY, and 0 under g4's constant-signal rule (the same threshold on YY);
+ *     LPVS_LOMB_PSD p N / 2.
+ *   coef_out (may be NULL): 2K + 1 planes of Nf x ns column-major: plane 2 (h - 1) = a_h, plane 2 (h - 1) + 1 = b_h, plane 2K = c,
+ *     c = (the mean center_data removed) + (fit_mean: Y - g^T theta).
+ *   sums_out (HOST, (4K + 2K ns) Nf + 3 ns doubles, may be NULL): rows of Nf values: row 2 (m - 1) = C_m, row 2 (m - 1) + 1 = S_m; for
+ *     signal c and harmonic h rows 4K + 2K c + 2 (h - 1) + {0, 1} = YC_h, YS_h; then Y_c, YY_c per signal (of the centred signal, before
+ *     the fit_mean term), then the ns weighted means as the device formed them.  With K = 1 both layouts are g4's.
+ * DEGENERATE FREQUENCIES.  A frequency is degenerate when some pivot fails d_j > 2^-40 (the entries of A are on the scale of unit total
+ * weight, as g4's rule assumes): power and all coefficients are 0 there, and it is counted once.  There is no separate rule for
+ * N < 2K + 1: such a record is degenerate at every frequency through its pivots.  (For K = 1 the pivots are CC and D / CC where g4 tests
+ * D against (CC + SS)^2: the same frequencies away from the threshold, not the same rule.)
+ * Errors: nterms outside 1 .. 6 and every argument error of g4 -> LPVS_EARGUMENT; Nf beyond 2^24 or more rows of sums than one launch
+ * takes -> LPVS_EUNSUPPORTED.
+ * ONLY DIRECT SUMS.  Every harmonic m of a progression of frequencies is a progression itself and could take the non-uniform FFTs of
+ * g4 -- 2K families of transforms instead of two; that is not built, and there is no path argument.  The windowed estimators (g5) and
+ * the bootstrap (g6) stay single-term.
+ * Every sum is added in a fixed order that depends on N and Nf alone: two calls give the same bits, and a signal's column does not
+ * depend on the other signals of the call.  t, y, W, power_out, coef_out: host or device memory; f, sums_out: host.
+ * lpvs_lombscargle_terms_last_timing (the calling thread's last call), out[0..9]: nterms, signals per thread of the sums kernel, slabs,
+ * degenerate frequencies, ms of the scan and the moments, the sums, the epilogue, the copy-out, total, accumulators per thread. */
+int32_t lpvs_lombscargle_terms_f64(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const double *f, int64_t Nf,
+                                   int32_t nterms, int32_t fit_mean, int32_t center_data, int32_t normalization, int32_t device,
+                                   double *power_out, double *coef_out, double *sums_out);
+int32_t lpvs_lombscargle_terms_last_timing(double *out, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,7 @@ export ls_spectral, tls_spectral, ls_sparse_spectral, ls_sparse_spectral_lpv, ls
        ls_cohere, ls_windowpsd_lpv, get_fourier_regressor, check_freq, default_freqs, Windows2, Windows3, mapwindows,
        SpectralExt, psd, reshape_params, ADMM, rect, hanning, autocov, autocor, isequidistant,
        melspectrogram, mfcc, mel, spectrogram, Spectrogram, MelSpectrogram, MFCC, freq, rand_cn, schedfunc,
-       Periodogram, welch_pgram, periodogram, compress, heatmap, predict, residual, fva, lombscargle, lombscargle_last_timing,
+       Periodogram, welch_pgram, periodogram, compress, heatmap, predict, residual, fva, lombscargle, lombscargle_last_timing, lombscargle_terms_last_timing,
        lombscargle_spectrogram, lombscargle_welch, lombscargle_windows_last_timing, time_windows, lombscargle_bootstrap,
        lombscargle_bootstrap_last_timing
 
@@ -1074,11 +1074,13 @@ end
 
 # ---- generalised Lomb-Scargle periodogram (extension: the non-uniform twin of periodogram; include/lpvspectral.h g4) ----------------
 const LOMB_NORMALIZATIONS = Dict(:standard => Int32(0), :psd => Int32(1))
-"""    lombscargle(y, t, f=default_freqs(t); W=nothing, fit_mean=true, center_data=true, normalization=:standard, path=:auto, coef=false)
+"""    lombscargle(y, t, f=default_freqs(t); W=nothing, fit_mean=true, center_data=true, normalization=:standard, path=:auto, coef=false, nterms=1)
 Every frequency fitted on its own, `y ≈ c + a cos 2πft + b sin 2πft` in weighted least squares; `y` a vector or an N × ns matrix of
-signals sharing `t`.  Returns `(power = Nf or Nf × ns, freq = f)` and, with `coef=true`, also `(a, b, c)`."""
+signals sharing `t`.  Returns `(power = Nf or Nf × ns, freq = f)` and, with `coef=true`, also `(a, b, c)`.
+`nterms = K` in 2:6 fits K harmonics per frequency, `y ≈ c + Σ_h a_h cos 2πhft + b_h sin 2πhft` (include/lpvspectral.h g7; direct sums
+only: `path=:nufft` is an ArgumentError); `a`, `b` are then Nf × K (one signal) or Nf × ns × K, `c` as before."""
 function lombscargle(y::AbstractVecOrMat{<:Real}, t::AbstractVector{<:Real}, f::AbstractVector{<:Real}=default_freqs(t); W=nothing, fit_mean::Bool=true,
-                     center_data::Bool=true, normalization::Symbol=:standard, path::Symbol=:auto, device::Integer=0, coef::Bool=false)
+                     center_data::Bool=true, normalization::Symbol=:standard, path::Symbol=:auto, device::Integer=0, coef::Bool=false, nterms::Integer=1)
     tv, fv = Vector{Float64}(t), Vector{Float64}(f)
     N, Nf, ns = length(tv), length(fv), size(y, 2)
     @assert size(y, 1) == N "y has to be as long as the sampling points"
@@ -1087,6 +1089,20 @@ function lombscargle(y::AbstractVecOrMat{<:Real}, t::AbstractVector{<:Real}, f::
     @assert W === nothing || length(Wv) == N "W has to be as long as the sampling points"
     Wp = W === nothing ? Ptr{Float64}(C_NULL) : pointer(Wv)
     power = zeros(Nf, ns)
+    1 <= nterms <= 6 || throw(ArgumentError("nterms must be in 1:6, got $nterms"))
+    if nterms > 1
+        haskey(EVAL_PATHS, path) || throw(ArgumentError("path: unknown value $path"))
+        path == :nufft && throw(ArgumentError("path=:nufft: the transforms are not implemented for several terms (nterms = $nterms)"))
+        K = Int(nterms)
+        ctv = coef ? zeros(Nf, ns, 2K + 1) : Float64[]                       # planes a_1, b_1, a_2, ..., then c
+        ctp = coef ? pointer(ctv) : Ptr{Float64}(C_NULL)
+        GC.@preserve yv tv Wv fv power ctv check(@ccall LIB.lpvs_lombscargle_terms_f64(yv::Ptr{Float64}, Int64(ns)::Int64, tv::Ptr{Float64}, Int64(N)::Int64,
+            Wp::Ptr{Float64}, fv::Ptr{Float64}, Int64(Nf)::Int64, Int32(K)::Int32, Int32(fit_mean)::Int32, Int32(center_data)::Int32,
+            LOMB_NORMALIZATIONS[normalization]::Int32, Int32(device)::Int32, power::Ptr{Float64}, ctp::Ptr{Float64}, C_NULL::Ptr{Float64})::Int32)
+        shapedk(A) = y isa AbstractVector ? reshape(A, Nf, :) : A
+        Pk = (power = y isa AbstractVector ? vec(power) : power, freq = fv)
+        return coef ? (Pk, (shapedk(ctv[:, :, 1:2:2K]), shapedk(ctv[:, :, 2:2:2K]), y isa AbstractVector ? vec(ctv[:, :, 2K + 1]) : ctv[:, :, 2K + 1])) : Pk
+    end
     cfv = coef ? zeros(Nf, ns, 3) : Float64[]
     cfp = coef ? pointer(cfv) : Ptr{Float64}(C_NULL)
     GC.@preserve yv tv Wv fv power cfv check(@ccall LIB.lpvs_lombscargle_f64(yv::Ptr{Float64}, Int64(ns)::Int64, tv::Ptr{Float64}, Int64(N)::Int64, Wp::Ptr{Float64},
@@ -1095,6 +1111,12 @@ function lombscargle(y::AbstractVecOrMat{<:Real}, t::AbstractVector{<:Real}, f::
     shaped(A) = y isa AbstractVector ? vec(A) : A
     P = (power = shaped(power), freq = fv)
     coef ? (P, (shaped(cfv[:, :, 1]), shaped(cfv[:, :, 2]), shaped(cfv[:, :, 3]))) : P
+end
+function lombscargle_terms_last_timing()
+    tm = zeros(10)
+    GC.@preserve tm check(@ccall LIB.lpvs_lombscargle_terms_last_timing(tm::Ptr{Float64}, Int32(10)::Int32)::Int32)
+    (nterms=Int(tm[1]), ts=Int(tm[2]), slabs=Int(tm[3]), degenerate=Int(tm[4]), moments_ms=tm[5], sums_ms=tm[6], epilogue_ms=tm[7], copy_ms=tm[8], total_ms=tm[9],
+     accumulators=Int(tm[10]))
 end
 function lombscargle_last_timing()
     tm = zeros(12)

@@ -12,7 +12,7 @@ _load()  # fail loudly at import time if the HIP extension is missing
 from .api import (MFCC, MelSpectrogram, Spectrogram, dct_matrix, fft_frequencies, freq, hz_to_mel, mel, mel_frequencies, mel_to_hz,  # noqa: E402
                   melspectrogram, mfcc, nextfastfft, spectrogram, stft_last_timing, time,
                   Periodogram, welch_pgram, periodogram, compress, compress_thresholds, heatmap, compress_last_timing,
-                  lombscargle, lombscargle_last_timing, lombscargle_spectrogram, lombscargle_welch, lombscargle_windows_last_timing, time_windows,
+                  lombscargle, lombscargle_last_timing, lombscargle_terms_last_timing, lombscargle_spectrogram, lombscargle_welch, lombscargle_windows_last_timing, time_windows,
                   bootstrap_indices, lombscargle_bootstrap, lombscargle_bootstrap_last_timing, false_alarm_probability, false_alarm_level,
                   ComplexNormal, SchedFunc, schedfunc, rand, randn, cholesky_upper, cn_last_timing, pdf, affine_transform, detrend, detrend_, Σ,  # noqa: E402
                   cn_V2ΓC, cn_Vxx, cn_Vyy, cn_Vxy, cn_Vyx, cn_fVxx, cn_fVyy, cn_fVxy, cn_fVyx, cn_Vs, cn_fV, cn_V,  # noqa: E402
@@ -31,7 +31,7 @@ __all__ = [
     "spectrogram", "melspectrogram", "mfcc", "mel", "hz_to_mel", "mel_to_hz", "mel_frequencies", "fft_frequencies", "dct_matrix",
     "nextfastfft", "Spectrogram", "MelSpectrogram", "MFCC", "freq", "time", "stft_last_timing",
     "Periodogram", "welch_pgram", "periodogram", "compress", "compress_thresholds", "heatmap", "compress_last_timing",
-    "lombscargle", "lombscargle_last_timing", "lombscargle_spectrogram", "lombscargle_welch", "lombscargle_windows_last_timing", "time_windows",
+    "lombscargle", "lombscargle_last_timing", "lombscargle_terms_last_timing", "lombscargle_spectrogram", "lombscargle_welch", "lombscargle_windows_last_timing", "time_windows",
     "bootstrap_indices", "lombscargle_bootstrap", "lombscargle_bootstrap_last_timing", "false_alarm_probability", "false_alarm_level",
     "ADMM", "Problem", "SpectralExt", "basis_activation_func", "check_freq", "default_freqs", "fourier2complex",
     "get_fourier_regressor", "lpv_regressor", "ls_sparse_spectral", "ls_sparse_spectral_lpv", "ls_sparse_spectral_lpv_multi", "ls_sparse_spectral_lpv_rowsharded", "lpv_ranges", "predict", "residual", "fva", "eval_last_timing", "lpv_batch_multi", "lpv_signals_multi", "ls_spectral",

@@ -2074,7 +2074,7 @@ def _lomb_signals(y):
     return np.asfortranarray(ya), ya.shape[0], ya.shape[1], single
 
 
-def lombscargle(y, t, f=None, W=None, fit_mean=True, center_data=True, normalization="standard", path="auto", device=0, coef=False, return_sums=False):
+def lombscargle(y, t, f=None, W=None, fit_mean=True, center_data=True, normalization="standard", path="auto", device=0, coef=False, return_sums=False, nterms=1):
     """Generalised Lomb-Scargle periodogram of non-uniformly sampled signals (extension; the floating-mean form of Zechmeister &
     Kürster 2009): every frequency is fitted on its own, ``y ≈ c + a cos 2πft + b sin 2πft`` in weighted least squares.
 
@@ -2089,11 +2089,27 @@ def lombscargle(y, t, f=None, W=None, fit_mean=True, center_data=True, normaliza
     Returns a :class:`Periodogram` (``power``: (Nf,) or (Nf, ns)); with ``coef=True`` also ``(a, b, c)``, with ``return_sums=True``
     also the raw sums as a dict (with ``"mean"``: the weighted means as the device formed them).  A constant signal has standard power 0
     (a ``YY`` within rounding of 0 counts as 0).  Float32 inputs are widened; a non-finite input, a negative weight or a zero weight sum raise
-    ValueError."""
+    ValueError.
+
+    ``nterms=K`` in 2 .. 6 fits ``K`` harmonics per frequency, ``y ≈ c + Σ_h a_h cos 2πhft + b_h sin 2πhft`` (astropy's ``nterms``; for
+    signals that are periodic but not sinusoidal): one ``sincospi`` per (sample, frequency) and complex rotations for the harmonics, the
+    ``2K × 2K`` normal equations factored per frequency on the device (csrc/lomb_terms.hip; include/lpvspectral.h g7).  Only direct sums:
+    ``path="nufft"`` raises ValueError (the transforms are not implemented for several terms), ``"auto"`` and ``"direct"`` run the
+    direct sums.  ``coef=True`` then gives ``(a, b, c)`` with ``a``, ``b`` of shape (K, Nf[, ns]) and ``c`` of shape (Nf[, ns]);
+    ``return_sums=True`` a dict with ``"C"``, ``"S"``: (2K, Nf) (harmonics 1 .. 2K), ``"YC"``, ``"YS"``: (ns, K, Nf), and ``"Y"``,
+    ``"YY"``, ``"mean"``.  A frequency where a pivot of the factorisation is not above 2^-40 is degenerate and gives 0
+    (:func:`lombscargle_terms_last_timing` counts them).  ``false_alarm_probability`` / ``false_alarm_level``, the windowed estimators
+    and :func:`lombscargle_bootstrap` stay single-term."""
     if path not in _EVAL_PATHS:
         raise ValueError(f"path: unknown value {path!r} (known: {sorted(_EVAL_PATHS)})")
     if normalization not in _LOMB_NORMALIZATIONS:
         raise ValueError(f"normalization: unknown value {normalization!r} (known: {sorted(_LOMB_NORMALIZATIONS)})")
+    if int(nterms) != nterms or not 1 <= int(nterms) <= 6:
+        raise ValueError(f"nterms must be an integer in 1 .. 6, got {nterms!r}")
+    if int(nterms) > 1:
+        if path == "nufft":
+            raise ValueError(f'path="nufft": the transforms are not implemented for several terms (nterms = {int(nterms)}); use "auto" or "direct"')
+        return _lombscargle_terms(y, t, f, W, fit_mean, center_data, normalization, device, coef, return_sums, int(nterms))
     fa = np.ascontiguousarray(np.ravel(_host(default_freqs(t) if f is None else f)).astype(np.float64))
     Nf = len(fa)
     ys, N, ns, single = _lomb_signals(y)
@@ -2118,6 +2134,47 @@ def lombscargle(y, t, f=None, W=None, fit_mean=True, center_data=True, normaliza
         res.append({"C": rows[0], "S": rows[1], "C2": rows[2], "S2": rows[3], "YC": rows[4::2], "YS": rows[5::2], "Y": mom[:, 0], "YY": mom[:, 1],
                     "mean": mean})
     return res[0] if len(res) == 1 else tuple(res)
+
+
+def _lombscargle_terms(y, t, f, W, fit_mean, center_data, normalization, device, coef, return_sums, nterms):
+    """:func:`lombscargle` with ``nterms`` harmonics through ``lpvs_lombscargle_terms_f64`` (``nterms=1`` is admitted here, for tests: the
+    public function keeps its own entry for one term)."""
+    K = int(nterms)
+    fa = np.ascontiguousarray(np.ravel(_host(default_freqs(t) if f is None else f)).astype(np.float64))
+    Nf = len(fa)
+    ys, N, ns, single = _lomb_signals(y)
+    ky, py, ny = as_f64(ys)
+    kt, pt, nt = as_f64(_f64_arg(t))
+    if nt != N:
+        raise ValueError(f"y has {N} samples, t has {nt}")
+    kw, pw, nw = as_f64(_f64_arg(W))
+    if W is not None and nw != N:
+        raise ValueError(f"y has {N} samples, W has {nw}")
+    nrow = max(4 * K + 2 * K * ns, 0)
+    power = np.zeros((Nf, ns), order="F")
+    co = np.zeros((max(2 * K + 1, 1), ns, Nf)) if coef else None           # [plane][signal][frequency] = planes of Nf x ns column-major
+    sums = np.zeros(nrow * Nf + 3 * ns) if return_sums else None
+    check(lib().lpvs_lombscargle_terms_f64(py, ns, pt, N, pw, out_ptr(fa), Nf, K, int(bool(fit_mean)), int(bool(center_data)), _LOMB_NORMALIZATIONS[normalization],
+                                           int(device), out_ptr(power), out_ptr(co) if coef else None, out_ptr(sums) if return_sums else None))
+    res = [Periodogram(power[:, 0].copy() if single else power, fa)]
+    if coef:
+        shaped = (lambda x: x[..., 0, :].copy()) if single else (lambda x: np.ascontiguousarray(np.swapaxes(x, -1, -2)))
+        res.append((shaped(co[0:2 * K:2]), shaped(co[1:2 * K:2]), shaped(co[2 * K])))
+    if return_sums:
+        nr = nrow * Nf
+        rows, mom, mean = sums[:nr].reshape(nrow, Nf), sums[nr:nr + 2 * ns].reshape(ns, 2), sums[nr + 2 * ns:]
+        ycs = rows[4 * K:].reshape(ns, K, 2, Nf)
+        res.append({"C": rows[0:4 * K:2], "S": rows[1:4 * K:2], "YC": ycs[:, :, 0], "YS": ycs[:, :, 1], "Y": mom[:, 0], "YY": mom[:, 1], "mean": mean})
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+def lombscargle_terms_last_timing():
+    """Plan and timing of the calling thread's last :func:`lombscargle` with ``nterms > 1``: the terms, the signals and the accumulators
+    per thread of the sums kernel, the slabs, the degenerate frequencies, milliseconds per phase."""
+    o = np.zeros(10)
+    check(lib().lpvs_lombscargle_terms_last_timing(out_ptr(o), 10))
+    return {"nterms": int(o[0]), "ts": int(o[1]), "slabs": int(o[2]), "degenerate": int(o[3]), "moments_ms": float(o[4]), "sums_ms": float(o[5]),
+            "epilogue_ms": float(o[6]), "copy_ms": float(o[7]), "total_ms": float(o[8]), "accumulators": int(o[9])}
 
 
 def lombscargle_last_timing():

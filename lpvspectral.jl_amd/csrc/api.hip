@@ -1544,6 +1544,97 @@ int32_t lpvs_lombscargle_last_timing(double *out, int32_t n) {
     return LPVS_OK;
 }
 
+// ---- Lomb-Scargle with several harmonics per frequency (lomb_terms.hip; the decisions: lomb_terms_plan.h) ----------------------------------
+// what lpvs_lombscargle_terms_last_timing reports of the calling thread's last call: [0] nterms, [1] signals per thread, [2] slabs,
+// [3] degenerate frequencies, ms of [4] staging, the scan and the moments, [5] the sums, [6] the epilogue, [7] the copy-out, [8] total,
+// [9] accumulators per thread
+static thread_local double g_lomb_terms_timing[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+static int32_t lomb_terms_impl(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const std::vector<double> &hf, const LombTermsPlan &plan,
+                               bool fit_mean, bool center, bool psd, int32_t device, double *power, double *coef, double *sums_out) {
+    const int64_t Nf = (int64_t)hf.size(), nrow = plan.rows;
+    const int K = plan.K;
+    if (lpvs_device_count() == 0) { set_error("no HIP device visible (the gfx950 path has no CPU fallback)"); return LPVS_EDEVICE; }
+    LPVS_HIP(hipSetDevice(device));
+    hipStream_t s = nullptr;
+    Events<5> ev;
+    for (auto &e : ev.e) LPVS_HIP(hipEventCreate(&e));
+    DevArg dt, dy, dW; DevOut dpower, dcoef;
+    DevBuf dw, dwy, dsmall, dpart, dsums, dfreq, dslab;
+    DrainOnExit drain(s);
+    LPVS_HIP(hipEventRecord(ev.e[0], s));
+    LPVS_TRY(dt.set(t, N, s));
+    LPVS_TRY(dy.set(y, N * ns, s));
+    if (W) LPVS_TRY(dW.set(W, N, s));
+    LPVS_TRY(dpower.set(power, Nf * ns));
+    if (coef) LPVS_TRY(dcoef.set(coef, (2 * K + 1) * Nf * ns));
+    // small device record, as lomb_impl's: [0] sum W, [1 .. ns] the weighted means, then Y_c, YY_c per signal (2 ns) and sum w y_c^2 of the
+    // signals as given (ns), then two ints (flags, degenerate count)
+    const size_t nsmall = (size_t)(1 + 4 * ns);
+    LPVS_TRY(dsmall.alloc(sizeof(double) * (nsmall + 1)));
+    double *sumW_dev = dsmall.as<double>(), *mean_dev = sumW_dev + 1, *mom_dev = mean_dev + ns;
+    int *flags_dev = reinterpret_cast<int *>(sumW_dev + nsmall), *ndeg_dev = flags_dev + 1;
+    const int64_t nsum = lomb_sum_slabs(N);
+    LPVS_TRY(dpart.alloc(sizeof(double) * (size_t)(3 * ns * nsum)));
+    LPVS_TRY(launch_lomb_scan(dt.p, dy.p, dW.p, N, ns, flags_dev, dpart.as<double>(), sumW_dev, s));
+    double sumW = 0; int flags = 0;
+    LPVS_TRY(copy_from_device(&sumW, sumW_dev, sizeof(double), s));
+    LPVS_TRY(copy_from_device(&flags, flags_dev, sizeof(int), s));
+    if (flags & 1) { set_error("lombscargle: t, y or W holds a value that is not finite"); return LPVS_EARGUMENT; }
+    if (flags & 2) { set_error("lombscargle: a weight is negative"); return LPVS_EARGUMENT; }
+    if (!(sumW > 0.0) || !std::isfinite(sumW)) { set_error("lombscargle: the weights sum to %g", sumW); return LPVS_EARGUMENT; }
+    LPVS_TRY(dw.alloc(sizeof(double) * (size_t)N));
+    LPVS_TRY(dwy.alloc(sizeof(double) * (size_t)(N * ns)));
+    LPVS_TRY(launch_lomb_moments(dy.p, dW.p, N, ns, sumW, center, dw.as<double>(), dwy.as<double>(), mean_dev, mom_dev, dpart.as<double>(), s));
+    LPVS_TRY(dsums.alloc(sizeof(double) * (size_t)(nrow * Nf)));
+    LPVS_TRY(dfreq.alloc(sizeof(double) * (size_t)Nf));
+    LPVS_TRY(copy_to_device(dfreq.p, hf.data(), sizeof(double) * (size_t)Nf, s));
+    LPVS_TRY(dslab.alloc(sizeof(double) * (size_t)plan.part_doubles));
+    LPVS_HIP(hipEventRecord(ev.e[1], s));
+    LPVS_TRY(launch_lomb_terms_sums(dt.p, dw.as<double>(), dwy.as<double>(), N, ns, dfreq.as<double>(), Nf, plan, dslab.as<double>(), dsums.as<double>(), s));
+    LPVS_HIP(hipEventRecord(ev.e[2], s));
+    LPVS_TRY(launch_lomb_terms_epilogue(K, dsums.as<double>(), Nf, ns, mom_dev, mean_dev, fit_mean, center, psd, N, dpower.p, coef ? dcoef.p : nullptr, ndeg_dev, s));
+    LPVS_HIP(hipEventRecord(ev.e[3], s));
+    int ndeg = 0;
+    LPVS_TRY(copy_from_device(&ndeg, ndeg_dev, sizeof(int), s));
+    if (sums_out) {
+        LPVS_TRY(copy_from_device(sums_out, dsums.p, sizeof(double) * (size_t)(nrow * Nf), s));
+        LPVS_TRY(copy_from_device(sums_out + nrow * Nf, mom_dev, sizeof(double) * (size_t)(2 * ns), s));
+        LPVS_TRY(copy_from_device(sums_out + nrow * Nf + 2 * ns, mean_dev, sizeof(double) * (size_t)ns, s));
+    }
+    LPVS_TRY(dpower.finish(s));
+    if (coef) LPVS_TRY(dcoef.finish(s));
+    LPVS_HIP(hipEventRecord(ev.e[4], s));
+    LPVS_HIP(hipStreamSynchronize(s));
+    float ms[4] = {0, 0, 0, 0}, total = 0;
+    for (int i = 0; i < 4; ++i) LPVS_HIP(hipEventElapsedTime(&ms[i], ev.e[i], ev.e[i + 1]));
+    LPVS_HIP(hipEventElapsedTime(&total, ev.e[0], ev.e[4]));
+    double *g = g_lomb_terms_timing;
+    g[0] = K; g[1] = plan.ts; g[2] = (double)plan.nslab; g[3] = ndeg; g[4] = ms[0]; g[5] = ms[1]; g[6] = ms[2]; g[7] = ms[3]; g[8] = total; g[9] = plan.acc;
+    return LPVS_OK;
+}
+
+int32_t lpvs_lombscargle_terms_f64(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const double *f, int64_t Nf, int32_t nterms,
+                                   int32_t fit_mean, int32_t center_data, int32_t normalization, int32_t device, double *power_out, double *coef_out,
+                                   double *sums_out) {
+    try {
+        if (!y || !t || !f || !power_out) { set_error("NULL argument"); return LPVS_EARGUMENT; }
+        const LombTermsPlan plan = lomb_terms_plan(N, Nf, ns, nterms);
+        if (plan.status != kLombTermsOk) { set_error("%s", plan.why.c_str()); return plan.status == kLombTermsArgument ? LPVS_EARGUMENT : LPVS_EUNSUPPORTED; }
+        if (normalization != LPVS_LOMB_STANDARD && normalization != LPVS_LOMB_PSD) { set_error("normalization must be 0 (standard) or 1 (psd), got %d", normalization); return LPVS_EARGUMENT; }
+        if (is_device_ptr(f) || (sums_out && is_device_ptr(sums_out))) { set_error("lombscargle: f and sums are host memory"); return LPVS_EARGUMENT; }
+        std::vector<double> hf(f, f + Nf);
+        for (double v : hf)
+            if (!std::isfinite(v)) { set_error("lombscargle: a frequency is not finite"); return LPVS_EARGUMENT; }
+        return lomb_terms_impl(y, ns, t, N, W, hf, plan, fit_mean != 0, center_data != 0, normalization == LPVS_LOMB_PSD, device, power_out, coef_out, sums_out);
+    } catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
+}
+
+int32_t lpvs_lombscargle_terms_last_timing(double *out, int32_t n) {
+    if (!out || n < 0) { set_error("NULL argument"); return LPVS_EARGUMENT; }
+    for (int32_t k = 0; k < n && k < 10; ++k) out[k] = g_lomb_terms_timing[k];
+    return LPVS_OK;
+}
+
 // ---- windowed Lomb-Scargle (lomb.hip; the work list: lomb_plan.h lomb_window_plan) ----------------------------------------------------------
 // what lpvs_lombscargle_windows_last_timing reports: [0] windows, [1] empty windows, [2] work items, [3] slab length, [4] degenerate
 // (window, frequency) pairs, ms of [5] staging, the scan and the moments, [6] the sums, [7] the epilogue and the average, [8] the copy-out, [9] total

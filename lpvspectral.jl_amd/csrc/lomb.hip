@@ -479,6 +479,12 @@ int32_t launch_lomb_direct(const double *t, const double *w, const double *wy, i
     LPVS_HIP(hipGetLastError());
     return LPVS_OK;
 }
+// sums[e] = the pairwise tree over the slabs of part[slab][e], e < count (lomb_terms.hip adds its slabs with the same kernel)
+int32_t launch_lomb_slab_sum(const double *part, int64_t nslab, int64_t count, double *sums, hipStream_t s) {
+    hipLaunchKernelGGL(lomb_slab_sum_kernel, dim3((unsigned)ceil_div(count, 256)), dim3(256), 0, s, part, nslab, count, sums);
+    LPVS_HIP(hipGetLastError());
+    return LPVS_OK;
+}
 // Wt[N][nq], nq = lomb_weight_vectors(.., g, prephase): the weights of signals c0 .. c0 + g - 1 (g = 0: w alone) times e^{i 2 pi base t}
 int32_t launch_lomb_prephase(const double *t, const double *w, const double *wy, int64_t N, int c0, int g, double base, bool prephase, double *Wt, hipStream_t s) {
     hipLaunchKernelGGL(lomb_prephase_kernel, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, s, t, w, wy, N, c0, g, base, prephase ? 1 : 0, Wt);

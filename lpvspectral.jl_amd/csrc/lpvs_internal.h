@@ -15,6 +15,7 @@
 #include "eval_plan.h"
 #include "lomb_plan.h"
 #include "lomb_boot_plan.h"
+#include "lomb_terms_plan.h"
 
 namespace lpvs {
 
@@ -241,6 +242,7 @@ int32_t launch_lomb_moments(const double *y, const double *W, int64_t N, int64_t
                             double *mom_dev, double *part, hipStream_t s);
 int32_t launch_lomb_direct(const double *t, const double *w, const double *wy, int64_t N, int64_t ns, const double *f_dev, int64_t Nf, const LombTiling &tl,
                            double *part, double *sums, hipStream_t s);
+int32_t launch_lomb_slab_sum(const double *part, int64_t nslab, int64_t count, double *sums, hipStream_t s);
 int32_t launch_lomb_prephase(const double *t, const double *w, const double *wy, int64_t N, int c0, int g, double base, bool prephase, double *Wt, hipStream_t s);
 int32_t launch_lomb_combine(const double *tab, int nq, int nre, bool prephase, int count, int64_t k0, int64_t Nf, const double *eps_dev, double escale, int row0,
                             int c0, double *sums, hipStream_t s);
@@ -280,6 +282,14 @@ int32_t launch_lomb_boot_sums(const double *t, const double *w, const double *y,
 int32_t launch_lomb_boot_epilogue(const double *shared, const double *sums, int64_t Nf, int64_t r0, int64_t count, const double *mean, const double *mom,
                                   bool fit_mean, bool center, bool psd, int64_t N, double *power_or_null, double *maxv, int64_t *maxi, bool count_deg, int *ndeg_dev,
                                   hipStream_t s);
+
+// several harmonics per frequency (lpvs_lombscargle_terms_f64; lomb_terms.hip; the decisions: lomb_terms_plan.h).  All pointers are device memory.
+// sums[(4K + 2K ns)][Nf]: rows C_m, S_m (m = 1 .. 2K), then YC_h, YS_h (h = 1 .. K) of every signal; part: pl.part_doubles doubles; w, wy: launch_lomb_moments'
+int32_t launch_lomb_terms_sums(const double *t, const double *w, const double *wy, int64_t N, int64_t ns, const double *f_dev, int64_t Nf, const LombTermsPlan &pl,
+                               double *part, double *sums, hipStream_t s);
+// power[ns][Nf] (column-major Nf x ns), coef[2K + 1][ns][Nf] (a_h, b_h per harmonic, then c) or nullptr; ndeg_dev: one int, zeroed here
+int32_t launch_lomb_terms_epilogue(int K, const double *sums, int64_t Nf, int64_t ns, const double *mom_dev, const double *mean_dev, bool fit_mean, bool center,
+                                   bool psd, int64_t N, double *power, double *coef, int *ndeg_dev, hipStream_t s);
 
 // ---- dense symmetric inverse (linalg.hip) ------------------------------------------------
 // In-place inverse of the SPD matrix A (np x np, np % 64 == 0, full symmetric storage) by
