@@ -801,6 +801,50 @@ int32_t lpvs_lombscargle_terms_f64(const double *y, int64_t ns, const double *t,
                                    double *power_out, double *coef_out, double *sums_out);
 int32_t lpvs_lombscargle_terms_last_timing(double *out, int32_t n);
 
+/* ---- g8  weighted wavelet Z-transform of non-uniformly sampled signals (extension; Foster, AJ 112, 1709, 1996): at every time tau_j and
+ * frequency f_k the floating-mean sinusoid fit of g4 under Gaussian weights whose width is a fixed number of periods.
+ * INPUTS.  y (N x ns column-major), t, W >= 0 (NULL: ones): as in g4; t must be non-decreasing (checked on the device, as
+ *   lpvs_time_windows_f64 does).  f[Nf] (host): finite and > 0.  tau[Ntau] (host): finite, in any order, inside or outside the record.
+ *   c > 0: the decay; Foster's 1 / (8 pi^2) makes the weight exp(-f^2 (t - tau)^2 / 2), one period per sigma.  radius[Nf] (host): each
+ *   > 0 or +inf -- how far a cell reaches; the entry point takes radii and never a weight threshold (the binding's wwz_radius(f, c, wmin)
+ *   = sqrt(log(1 / wmin) / c) / (2 pi f) is the usual choice, Foster's own program drops samples below wmin = 1e-9).
+ * CELL (k, j).  Its samples are those with tau_j - radius_k <= t_n <= tau_j + radius_k, both edges formed in double exactly as written:
+ *   start = #{t < lo}, count = #{t <= hi} - start by binary search on the device (the rule of lpvs_time_windows_f64).  The weight of
+ *   sample n is g_n = exp(-a_k d_n^2), d_n = t_n - tau_j, with a_k formed once per frequency in double as  w = 6.283185307179586 * f_k,
+ *   a_k = c * (w * w).  The cell IS the g4 estimate of its samples with the weights W_n g_n / sum W g, fit_mean always on (the constant
+ *   is part of Foster's basis), the phases phi = 2 pi (f t) of the exact products, the degenerate rule and the constant-signal rule with
+ *   N := count.  The sums are accumulated with the unnormalised W g and divided by sum W g at the end.
+ *   center_data (default on) removes the RECORD's weighted mean (weights W) once, before anything else; it serves the numerics only: the
+ *   floating mean makes every output but c invariant under it, and c has it added back.
+ * OUTPUTS, Nf x Ntau x ns with the frequency fastest -- element (c Ntau + j) Nf + k -- unless said otherwise; host or device memory:
+ *   power_out      p / YY (g4's standard normalisation), in [0, 1]
+ *   amplitude_out  sqrt(a^2 + b^2): Foster's weighted wavelet amplitude (WWA)
+ *   wwz_out        (Neff - 3) p / (2 (YY - p)): Foster's Z, an F-statistic of the fit
+ *   neff_out       Nf x Ntau: Neff = (sum W g)^2 / sum (W g)^2, the effective number of samples
+ *   coef_out       optional, three such planes a, b, c of  y ~ c + a cos 2 pi f t + b sin 2 pi f t  with the phase origin t = 0.  Foster's
+ *                  basis {1, cos w (t - tau), sin w (t - tau)} spans the same space: power, amplitude, Z and c are the same, and his
+ *                  coefficients are (a, b) rotated by the angle 2 pi f tau:  a' = a cos + b sin,  b' = b cos - a sin.
+ *   count_out      optional, host int64, Nf x Ntau: the samples in reach
+ *   empty_out      optional, host int32, Nf x Ntau: 1 for an empty cell
+ * RULES.  Nothing returned is ever NaN.  An empty cell -- count = 0, or sum W g = 0 (or sum (W g)^2 = 0) by underflow -- gives exact zeros
+ *   in every plane and is flagged; it is no error.  A degenerate cell (g4's rule) gives zeros and is counted.  Neff <= 3 gives wwz = 0:
+ *   the F-statistic has no degrees of freedom left.  A standard power zeroed by the constant-signal rule gives wwz = 0.  YY - p not above
+ *   that same threshold while YY is (a fit exact to rounding) gives wwz = +inf.
+ * ERRORS.  LPVS_EARGUMENT: a non-finite t, y, W, f or tau; f <= 0; a negative weight; c <= 0 (or not finite); a radius that is NaN or
+ *   <= 0; a decreasing t; N, Nf, Ntau < 1; ns outside 1 .. 65535.  LPVS_EUNSUPPORTED: more than 2^24 of Nf or Ntau; more cells or work
+ *   items than one launch takes.
+ * DETERMINISM, as everywhere in the family: two calls give the same bits, and the additions behind a cell happen in an order that depends
+ *   on that cell's (start, count) and on N alone (sample lanes by the absolute index mod 4, stages of 256 and slabs at absolute
+ *   multiples, the slab length a function of N; samples outside a cell are skipped, never added as zeros).  So a time has the same bits
+ *   alone, among others and with the list permuted, and a signal has the same bits alone and among others.
+ * lpvs_wwz_last_timing (the calling thread's last call), out[0..15]: Nf, Ntau, times and signals per thread of the sums kernel, work
+ *   items, slab length, empty cells, degenerate cells, staged and useful (sample, frequency, time) triples, then milliseconds of the
+ *   staging with the scan and the means, the ranges with the work list, the sums, the epilogue, the copy-out and the total. */
+int32_t lpvs_wwz_f64(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const double *f, int64_t Nf, const double *tau,
+                     int64_t Ntau, double c, const double *radius, int32_t center_data, int32_t device, double *power_out, double *amplitude_out,
+                     double *wwz_out, double *neff_out, double *coef_out, int64_t *count_out, int32_t *empty_out);
+int32_t lpvs_wwz_last_timing(double *out, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,7 +21,7 @@ export ls_spectral, tls_spectral, ls_sparse_spectral, ls_sparse_spectral_lpv, ls
        SpectralExt, psd, reshape_params, ADMM, rect, hanning, autocov, autocor, isequidistant,
        melspectrogram, mfcc, mel, spectrogram, Spectrogram, MelSpectrogram, MFCC, freq, rand_cn, schedfunc,
        Periodogram, welch_pgram, periodogram, compress, heatmap, predict, residual, fva, lombscargle, lombscargle_last_timing, lombscargle_terms_last_timing,
-       lombscargle_spectrogram, lombscargle_welch, lombscargle_windows_last_timing, time_windows, lombscargle_bootstrap,
+       lombscargle_spectrogram, lombscargle_welch, lombscargle_windows_last_timing, time_windows, wwz, wwz_radius, wwz_last_timing, lombscargle_bootstrap,
        lombscargle_bootstrap_last_timing
 
 const LIB = get(ENV, "LPVSPECTRAL_LIB", joinpath(@__DIR__, "..", "lpvspectral.jl_amd", "liblpvspectral.so"))
@@ -1205,6 +1205,50 @@ function lombscargle_windows_last_timing()
     GC.@preserve tm check(@ccall LIB.lpvs_lombscargle_windows_last_timing(tm::Ptr{Float64}, Int32(10)::Int32)::Int32)
     (windows=Int(tm[1]), empty=Int(tm[2]), items=Int(tm[3]), slab=Int(tm[4]), degenerate=Int(tm[5]), moments_ms=tm[6], sums_ms=tm[7], epilogue_ms=tm[8],
      copy_ms=tm[9], total_ms=tm[10])
+end
+
+# ---- weighted wavelet Z-transform (extension; include/lpvspectral.h g8) -----------------------------------------------------------------
+const WWZ_DECAY = 1 / (8 * pi^2)
+"""    wwz_radius(f, c=1/(8π²), wmin=1e-9)
+How far a cell of `wwz` reaches: `sqrt(log(1 / wmin) / c) / (2π f)`, `Inf` for `wmin = 0`."""
+wwz_radius(f::AbstractVector{<:Real}, c::Real=WWZ_DECAY, wmin::Real=1e-9) =
+    wmin == 0 ? fill(Inf, length(f)) : sqrt(log(1 / Float64(wmin)) / Float64(c)) ./ (2 * pi .* Vector{Float64}(f))
+"""    wwz(y, t, f=default_freqs(t)[2:end]; tau=nothing, ntau=nothing, c=1/(8π²), wmin=1e-9, W=nothing, center_data=true, coef=false)
+Foster's weighted wavelet Z-transform of non-uniformly sampled signals: at every time `tau[j]` and frequency `f[k]` the floating-mean fit
+of `lombscargle` under the weights `W exp(-c (2π f (t - tau))²)`.  `t` non-decreasing; `tau` defaults to `ntau` (64) equally spaced times
+over the record.  Returns `(power, wwz, amplitude = Nf × Ntau (× ns), neff, counts, empty = Nf × Ntau, freq, time, radius)` and, with
+`coef=true`, also `(a, b, c)` (phase origin `t = 0`)."""
+function wwz(y::AbstractVecOrMat{<:Real}, t::AbstractVector{<:Real}, f::AbstractVector{<:Real}=default_freqs(t)[2:end]; tau=nothing, ntau=nothing,
+             c::Real=WWZ_DECAY, wmin::Real=1e-9, W=nothing, center_data::Bool=true, coef::Bool=false, device::Integer=0)
+    tv, fv = Vector{Float64}(t), Vector{Float64}(f)
+    tau !== nothing && ntau !== nothing && throw(ArgumentError("give tau or ntau, not both"))
+    tauv = tau === nothing ? collect(range(tv[1], tv[end]; length=(ntau === nothing ? 64 : Int(ntau)))) : Vector{Float64}(tau)
+    N, Nf, Ntau, ns = length(tv), length(fv), length(tauv), size(y, 2)
+    @assert size(y, 1) == N "y has to be as long as the sampling points"
+    yv = Matrix{Float64}(reshape(y, N, ns))
+    Wv = W === nothing ? Float64[] : Vector{Float64}(W)
+    @assert W === nothing || length(Wv) == N "W has to be as long as the sampling points"
+    Wp = W === nothing ? Ptr{Float64}(C_NULL) : pointer(Wv)
+    radius = wwz_radius(fv, c, wmin)
+    power, amplitude, z, neff = zeros(Nf, Ntau, ns), zeros(Nf, Ntau, ns), zeros(Nf, Ntau, ns), zeros(Nf, Ntau)
+    cfv = coef ? zeros(Nf, Ntau, ns, 3) : Float64[]
+    cfp = coef ? pointer(cfv) : Ptr{Float64}(C_NULL)
+    counts, empty = zeros(Int64, Nf, Ntau), zeros(Int32, Nf, Ntau)
+    GC.@preserve yv tv Wv fv tauv radius power amplitude z neff cfv counts empty check(@ccall LIB.lpvs_wwz_f64(yv::Ptr{Float64}, Int64(ns)::Int64, tv::Ptr{Float64},
+        Int64(N)::Int64, Wp::Ptr{Float64}, fv::Ptr{Float64}, Int64(Nf)::Int64, tauv::Ptr{Float64}, Int64(Ntau)::Int64, Float64(c)::Float64, radius::Ptr{Float64},
+        Int32(center_data)::Int32, Int32(device)::Int32, power::Ptr{Float64}, amplitude::Ptr{Float64}, z::Ptr{Float64}, neff::Ptr{Float64}, cfp::Ptr{Float64},
+        counts::Ptr{Int64}, empty::Ptr{Int32})::Int32)
+    one = y isa AbstractVector
+    shaped(A) = one ? A[:, :, 1] : A
+    R = (power = shaped(power), wwz = shaped(z), amplitude = shaped(amplitude), neff = neff, counts = counts, empty = empty .!= 0, freq = fv, time = tauv,
+         radius = radius)
+    coef ? (R, (shaped(cfv[:, :, :, 1]), shaped(cfv[:, :, :, 2]), shaped(cfv[:, :, :, 3]))) : R
+end
+function wwz_last_timing()
+    tm = zeros(16)
+    GC.@preserve tm check(@ccall LIB.lpvs_wwz_last_timing(tm::Ptr{Float64}, Int32(16)::Int32)::Int32)
+    (nf=Int(tm[1]), ntau=Int(tm[2]), tt=Int(tm[3]), ts=Int(tm[4]), items=Int(tm[5]), slab=Int(tm[6]), empty=Int(tm[7]), degenerate=Int(tm[8]), staged=tm[9],
+     useful=tm[10], scan_ms=tm[11], ranges_ms=tm[12], sums_ms=tm[13], epilogue_ms=tm[14], copy_ms=tm[15], total_ms=tm[16])
 end
 
 # ---- the bootstrap of the Lomb-Scargle periodogram (extension; include/lpvspectral.h g6) -------------------------------------------------

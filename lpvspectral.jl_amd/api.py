@@ -2322,6 +2322,100 @@ def lombscargle_windows_last_timing():
             "sums_ms": float(o[6]), "epilogue_ms": float(o[7]), "copy_ms": float(o[8]), "total_ms": float(o[9])}
 
 
+# ---- weighted wavelet Z-transform (include/lpvspectral.h g8; csrc/wwz.hip) ------------------------------------------------------------------
+WWZ_DECAY = 1.0 / (8.0 * np.pi ** 2)
+
+
+class WWZ(Spectrogram):
+    """The result of :func:`wwz`, laid out as a :class:`Spectrogram` (``power``, ``freq``, ``time``: :func:`heatmap` takes it as it is):
+    ``power`` (standard, in [0, 1]), ``wwz`` (Foster's Z) and ``amplitude`` (his WWA): (Nf, Ntau) or (Nf, Ntau, ns); ``neff``,
+    ``counts`` (samples in reach) and ``empty``: (Nf, Ntau); ``freq = f``, ``time = tau``, and the ``radius`` of every frequency."""
+
+    def __init__(self, power, freq, time, wwz, amplitude, neff, counts, empty, radius):
+        super().__init__(power, freq, time)
+        self.wwz, self.amplitude, self.neff, self.counts, self.empty, self.radius = wwz, amplitude, neff, counts, empty, radius
+
+
+def wwz_radius(f, c=WWZ_DECAY, wmin=1e-9):
+    """How far a cell of :func:`wwz` reaches: the distance at which the weight ``exp(-c (2π f d)²)`` has fallen to ``wmin``,
+    ``sqrt(log(1 / wmin) / c) / (2π f)`` in numpy doubles (``inf`` for ``wmin = 0``: every cell is the whole record).  The library
+    takes radii and never a ``wmin``, so this expression IS the definition."""
+    fa = np.asarray(_host(f), dtype=np.float64)
+    wmin = np.float64(wmin)
+    if not 0 <= wmin < 1:
+        raise ValueError(f"wmin must lie in [0, 1), got {wmin}")
+    if wmin == 0:
+        return np.full(fa.shape, np.inf)
+    with np.errstate(all="ignore"):                                            # (a c or f the library refuses gives nan or inf here)
+        return np.sqrt(np.log(1.0 / wmin) / np.float64(c)) / (2.0 * np.pi * fa)
+
+
+def wwz(y, t, f=None, tau=None, ntau=None, c=WWZ_DECAY, wmin=1e-9, W=None, center_data=True, coef=False, device=0):
+    """Foster's weighted wavelet Z-transform (AJ 112, 1996) of non-uniformly sampled signals: at every time ``tau[j]`` and frequency
+    ``f[k]`` the floating-mean fit ``y ≈ c + a cos 2πft + b sin 2πft`` of :func:`lombscargle` under the weights
+    ``W exp(-c (2π f (t - tau))²)``, whose width is a fixed number of periods -- a time-frequency map whose resolution follows the
+    frequency, where :func:`lombscargle_spectrogram` has one window length for all of them (csrc/wwz.hip; include/lpvspectral.h g8).
+
+    ``y``: (N,) or (N, ns) signals sharing the non-decreasing times ``t`` (numpy arrays or device tensors); ``f``: positive frequencies
+    (``None``: ``default_freqs(t)`` without its zero); ``tau``: the times, in any order (``None``: ``ntau`` -- default 64 -- equally spaced
+    over ``[t[0], t[-1]]``); ``c``: the decay, Foster's ``1 / (8π²)`` (one period per sigma); ``wmin``: a sample whose weight would be
+    below it is out of reach of a cell (:func:`wwz_radius`; ``1e-9`` is what Foster's own program uses, ``0`` makes every cell the whole
+    record); ``W``: non-negative weights.  ``center_data`` removes the record's weighted mean first (numerics only: the fitted constant
+    absorbs it).
+
+    Returns a :class:`WWZ`; with ``coef=True`` also ``(a, b, c)`` (phase origin ``t = 0``; Foster's are these rotated by ``2π f tau``).
+    Cells without samples (or with weights that underflow to 0) are exact zeros and flagged in ``empty``; ``Neff <= 3`` gives
+    ``wwz = 0``; a fit exact to rounding gives ``wwz = inf``; nothing is ever NaN.  A column has the same bits whether its time is
+    computed alone, among others or in another place of the list, and a signal the same bits alone and among others."""
+    th = None
+    if f is None or tau is None:
+        th = np.ravel(_host(t))
+    fa = np.ascontiguousarray(np.ravel(_host(default_freqs(th)[1:] if f is None else f)).astype(np.float64))
+    if tau is None:
+        n = 64 if ntau is None else int(ntau)
+        if n < 1:
+            raise ValueError(f"ntau must be at least 1, got {ntau!r}")
+        ta = np.ascontiguousarray(np.linspace(th[0], th[-1], n))
+    else:
+        if ntau is not None:
+            raise ValueError("give tau or ntau, not both")
+        ta = np.ascontiguousarray(np.ravel(_host(tau)).astype(np.float64))
+    Nf, Ntau = len(fa), len(ta)
+    ra = np.ascontiguousarray(np.ravel(wwz_radius(fa, c, wmin)))
+    ys, N, ns, single = _lomb_signals(y)
+    ky, py, ny = as_f64(ys)
+    kt, pt, nt = as_f64(_f64_arg(t))
+    if nt != N:
+        raise ValueError(f"y has {N} samples, t has {nt}")
+    kw, pw, nw = as_f64(_f64_arg(W))
+    if W is not None and nw != N:
+        raise ValueError(f"y has {N} samples, W has {nw}")
+    planes = np.zeros((3, ns, Ntau, Nf))                                       # power, amplitude, wwz: [signal][time][frequency]
+    neff = np.zeros((Ntau, Nf))
+    co = np.zeros((3, ns, Ntau, Nf)) if coef else None
+    counts, empty = np.zeros((Ntau, Nf), dtype=np.int64), np.zeros((Ntau, Nf), dtype=np.int32)
+    check(lib().lpvs_wwz_f64(py, ns, pt, N, pw, out_ptr(fa), Nf, out_ptr(ta), Ntau, float(c), out_ptr(ra), int(bool(center_data)), int(device),
+                             out_ptr(planes[0]), out_ptr(planes[1]), out_ptr(planes[2]), out_ptr(neff), out_ptr(co) if coef else None,
+                             out_ptr(counts), out_ptr(empty)))
+    del ky, kt, kw
+
+    def shaped(a):                                                             # (ns, Ntau, Nf) -> (Nf, Ntau) or (Nf, Ntau, ns)
+        return np.ascontiguousarray(a[0].T) if single else np.ascontiguousarray(np.transpose(a, (2, 1, 0)))
+    R = WWZ(shaped(planes[0]), fa, ta, shaped(planes[2]), shaped(planes[1]), np.ascontiguousarray(neff.T), np.ascontiguousarray(counts.T),
+            np.ascontiguousarray(empty.T).astype(bool), ra)
+    return (R, tuple(shaped(co[i]) for i in range(3))) if coef else R
+
+
+def wwz_last_timing():
+    """Plan and timing of the calling thread's last :func:`wwz`: the times and signals a thread of the sums kernel carries, the work items,
+    the slab length, empty and degenerate cells, staged and useful (sample, frequency, time) triples, milliseconds per phase."""
+    o = np.zeros(16)
+    check(lib().lpvs_wwz_last_timing(out_ptr(o), 16))
+    return {"nf": int(o[0]), "ntau": int(o[1]), "tt": int(o[2]), "ts": int(o[3]), "items": int(o[4]), "slab": int(o[5]), "empty": int(o[6]),
+            "degenerate": int(o[7]), "staged": float(o[8]), "useful": float(o[9]), "scan_ms": float(o[10]), "ranges_ms": float(o[11]),
+            "sums_ms": float(o[12]), "epilogue_ms": float(o[13]), "copy_ms": float(o[14]), "total_ms": float(o[15])}
+
+
 # ---- false-alarm probabilities of the Lomb-Scargle periodogram: the device bootstrap and the closed forms (include/lpvspectral.h g6) ------
 _M32 = np.uint64(0xFFFFFFFF)
 

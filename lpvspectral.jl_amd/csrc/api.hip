@@ -1808,6 +1808,157 @@ int32_t lpvs_time_windows_f64(const double *t, int64_t N, const double *lo, cons
     } catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
 }
 
+// ---- weighted wavelet Z-transform (wwz.hip; the decisions: wwz_plan.h) ------------------------------------------------------------------------
+// what lpvs_wwz_last_timing reports of the calling thread's last call: [0] Nf, [1] Ntau, [2] times and [3] signals per thread of the sums
+// kernel, [4] work items, [5] slab length, [6] empty cells, [7] degenerate cells, [8] staged and [9] useful (sample, frequency, time)
+// triples, ms of [10] staging, the scan and the record's means, [11] the ranges and the work list, [12] the sums, [13] the epilogue,
+// [14] the copy-out, [15] total
+static thread_local double g_wwz_timing[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+static int32_t wwz_impl(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const double *f, int64_t Nf, const double *tau, int64_t Ntau,
+                        const double *radius, const WwzShape &sh, bool center, int32_t device, double *power, double *amplitude, double *wwz, double *neff,
+                        double *coef, int64_t *count_out, int32_t *empty_out) {
+    if (lpvs_device_count() == 0) { set_error("no HIP device visible (the gfx950 path has no CPU fallback)"); return LPVS_EDEVICE; }
+    LPVS_HIP(hipSetDevice(device));
+    hipStream_t s = nullptr;
+    Events<6> ev;
+    for (auto &e : ev.e) LPVS_HIP(hipEventCreate(&e));
+    DevArg dt, dy, dW; DevOut dpower, damp, dwwz, dneff, dcoef;
+    DevBuf dsmall, dscan, dw, dwy, dfreq, dtau, dpos, dedges, dpair, ditems, dlist, dpart, dcount, dempty;
+    DrainOnExit drain(s);
+    LPVS_HIP(hipEventRecord(ev.e[0], s));
+    LPVS_TRY(dt.set(t, N, s));
+    LPVS_TRY(dy.set(y, N * ns, s));
+    if (W) LPVS_TRY(dW.set(W, N, s));
+    const int64_t cells = Nf * Ntau, ncols = cells * ns, pairs = sh.ngroups * sh.ftiles;
+    LPVS_TRY(dpower.set(power, ncols));
+    LPVS_TRY(damp.set(amplitude, ncols));
+    LPVS_TRY(dwwz.set(wwz, ncols));
+    LPVS_TRY(dneff.set(neff, cells));
+    if (coef) LPVS_TRY(dcoef.set(coef, 3 * ncols));
+    // small device record: [0] sum W, [1 .. ns] the record's weighted means, [1 + ns .. 1 + 4 ns) launch_lomb_moments' moments (not used),
+    // then the two counters of the epilogue and the flags
+    const size_t nsmall = (size_t)(1 + 4 * ns);
+    LPVS_TRY(dsmall.alloc(sizeof(double) * (nsmall + 3)));
+    double *sumW_dev = dsmall.as<double>(), *mean_dev = sumW_dev + 1, *mom_dev = mean_dev + ns;
+    unsigned long long *counters_dev = reinterpret_cast<unsigned long long *>(sumW_dev + nsmall);
+    int *flags_dev = reinterpret_cast<int *>(sumW_dev + nsmall + 2);
+    const int64_t nsum = lomb_sum_slabs(N);
+    LPVS_TRY(dscan.alloc(sizeof(double) * (size_t)(3 * ns * nsum)));
+    LPVS_TRY(launch_lomb_scan(dt.p, dy.p, dW.p, N, ns, flags_dev, dscan.as<double>(), sumW_dev, s));
+    LPVS_TRY(launch_wwz_sorted(dt.p, N, flags_dev, s));
+    double sumW = 0; int flags = 0;
+    LPVS_TRY(copy_from_device(&sumW, sumW_dev, sizeof(double), s));
+    LPVS_TRY(copy_from_device(&flags, flags_dev, sizeof(int), s));
+    if (flags & 1) { set_error("wwz: t, y or W holds a value that is not finite"); return LPVS_EARGUMENT; }
+    if (flags & 2) { set_error("wwz: a weight is negative"); return LPVS_EARGUMENT; }
+    if (flags & 8) { set_error("wwz: t is not sorted (it decreases somewhere)"); return LPVS_EARGUMENT; }
+    if (!std::isfinite(sumW)) { set_error("wwz: the weights sum to %g", sumW); return LPVS_EARGUMENT; }
+    // the record's weighted means (weights W); weights that sum to 0 leave every cell empty, and nothing is removed
+    const bool removes = center && sumW > 0.0;
+    if (removes) {
+        LPVS_TRY(dw.alloc(sizeof(double) * (size_t)N));
+        LPVS_TRY(dwy.alloc(sizeof(double) * (size_t)(N * ns)));
+        LPVS_TRY(launch_lomb_moments(dy.p, dW.p, N, ns, sumW, true, dw.as<double>(), dwy.as<double>(), mean_dev, mom_dev, dscan.as<double>(), s));
+    }
+    LPVS_HIP(hipEventRecord(ev.e[1], s));
+    // per frequency [f | decay | radius | rmax of the tiles], per time [tau in order | gmin | gmax | tau as given], the places
+    LPVS_TRY(dfreq.alloc(sizeof(double) * (size_t)(3 * Nf + sh.ftiles)));
+    double *f_dev = dfreq.as<double>(), *decay_dev = f_dev + Nf, *radius_dev = decay_dev + Nf, *rmax_dev = radius_dev + Nf;
+    LPVS_TRY(copy_to_device(f_dev, f, sizeof(double) * (size_t)Nf, s));
+    LPVS_TRY(copy_to_device(decay_dev, sh.decay.data(), sizeof(double) * (size_t)Nf, s));
+    LPVS_TRY(copy_to_device(radius_dev, radius, sizeof(double) * (size_t)Nf, s));
+    LPVS_TRY(copy_to_device(rmax_dev, sh.rmax.data(), sizeof(double) * (size_t)sh.ftiles, s));
+    const int64_t nsorted = sh.ngroups * sh.TT;
+    LPVS_TRY(dtau.alloc(sizeof(double) * (size_t)(nsorted + 2 * sh.ngroups + Ntau)));
+    double *tau_dev = dtau.as<double>(), *gmin_dev = tau_dev + nsorted, *gmax_dev = gmin_dev + sh.ngroups, *given_dev = gmax_dev + sh.ngroups;
+    LPVS_TRY(copy_to_device(tau_dev, sh.tau_sorted.data(), sizeof(double) * (size_t)nsorted, s));
+    LPVS_TRY(copy_to_device(gmin_dev, sh.gmin.data(), sizeof(double) * (size_t)sh.ngroups, s));
+    LPVS_TRY(copy_to_device(gmax_dev, sh.gmax.data(), sizeof(double) * (size_t)sh.ngroups, s));
+    LPVS_TRY(copy_to_device(given_dev, tau, sizeof(double) * (size_t)Ntau, s));
+    LPVS_TRY(dpos.alloc(sizeof(int32_t) * (size_t)Ntau));
+    LPVS_TRY(copy_to_device(dpos.p, sh.pos.data(), sizeof(int32_t) * (size_t)Ntau, s));
+    // the ranges of the cells and of the (group, tile) pairs; the pairs' go to the host, which lays out the work list
+    LPVS_TRY(dedges.alloc(sizeof(int64_t) * (size_t)(2 * cells)));
+    LPVS_TRY(dpair.alloc(sizeof(int64_t) * (size_t)(2 * pairs)));
+    LPVS_TRY(launch_wwz_ranges(dt.p, N, given_dev, given_dev, Ntau, radius_dev, Nf, dedges.as<int64_t>(), s));
+    LPVS_TRY(launch_wwz_ranges(dt.p, N, gmin_dev, gmax_dev, sh.ngroups, rmax_dev, sh.ftiles, dpair.as<int64_t>(), s));
+    std::vector<int64_t> hedges((size_t)(2 * cells)), hpair((size_t)(2 * pairs));
+    LPVS_TRY(copy_from_device(hedges.data(), dedges.p, sizeof(int64_t) * hedges.size(), s));
+    LPVS_TRY(copy_from_device(hpair.data(), dpair.p, sizeof(int64_t) * hpair.size(), s));
+    double useful = 0;
+    for (int64_t q = 0; q < cells; ++q) {
+        const int64_t a = hedges[(size_t)(2 * q)], b = hedges[(size_t)(2 * q + 1)];
+        if (b > a) useful += (double)(b - a);
+    }
+    const WwzWork work = wwz_work(sh, hpair, useful);
+    if (work.status != kWwzOk) { set_error("%s", work.why.c_str()); return LPVS_EUNSUPPORTED; }
+    const int64_t nitems = (int64_t)work.items.size();
+    LPVS_TRY(ditems.alloc(sizeof(WwzItem) * (size_t)(nitems > 0 ? nitems : 1)));
+    if (nitems > 0) LPVS_TRY(copy_to_device(ditems.p, work.items.data(), sizeof(WwzItem) * (size_t)nitems, s));
+    LPVS_TRY(dlist.alloc(sizeof(int64_t) * (size_t)(2 * pairs + 1)));
+    int64_t *offset_dev = dlist.as<int64_t>(), *first_slab_dev = offset_dev + pairs + 1;
+    LPVS_TRY(copy_to_device(offset_dev, work.offset.data(), sizeof(int64_t) * (size_t)(pairs + 1), s));
+    LPVS_TRY(copy_to_device(first_slab_dev, work.first_slab.data(), sizeof(int64_t) * (size_t)pairs, s));
+    LPVS_TRY(dpart.alloc(sizeof(double) * (size_t)(work.part_doubles > 0 ? work.part_doubles : 1)));
+    WwzArgs A;
+    A.t = dt.p; A.y = dy.p; A.W = dW.p; A.mean = removes ? mean_dev : nullptr;
+    A.f = f_dev; A.decay = decay_dev; A.radius = radius_dev; A.tau = tau_dev; A.pos = dpos.as<int32_t>();
+    A.items = ditems.as<WwzItem>(); A.offset = offset_dev; A.first_slab = first_slab_dev;
+    A.N = N; A.Nf = Nf; A.Ntau = Ntau; A.nitems = nitems; A.ftiles = sh.ftiles; A.slab_samples = sh.slab_samples; A.rows = sh.rows;
+    A.ns = (int)ns; A.TT = sh.TT;
+    LPVS_HIP(hipEventRecord(ev.e[2], s));
+    LPVS_TRY(launch_wwz_sums(A, sh.ts, dpart.as<double>(), s));
+    LPVS_HIP(hipEventRecord(ev.e[3], s));
+    LPVS_TRY(dcount.alloc(sizeof(int64_t) * (size_t)cells));
+    LPVS_TRY(dempty.alloc(sizeof(int32_t) * (size_t)cells));
+    LPVS_TRY(launch_wwz_epilogue(A, dpart.as<double>(), dedges.as<int64_t>(), removes, dpower.p, damp.p, dwwz.p, dneff.p, coef ? dcoef.p : nullptr,
+                                 dcount.as<int64_t>(), dempty.as<int32_t>(), flags_dev, counters_dev, s));
+    LPVS_HIP(hipEventRecord(ev.e[4], s));
+    unsigned long long counters[2] = {0, 0};
+    LPVS_TRY(copy_from_device(&flags, flags_dev, sizeof(int), s));
+    LPVS_TRY(copy_from_device(counters, counters_dev, sizeof(counters), s));
+    if (flags & 4) { set_error("wwz: the weights of a cell do not sum to a finite value"); return LPVS_EARGUMENT; }
+    if (flags & 16) { set_error("wwz: a cell lies outside the samples its group stages"); return LPVS_EDEVICE; }
+    if (count_out) LPVS_TRY(copy_from_device(count_out, dcount.p, sizeof(int64_t) * (size_t)cells, s));
+    if (empty_out) LPVS_TRY(copy_from_device(empty_out, dempty.p, sizeof(int32_t) * (size_t)cells, s));
+    LPVS_TRY(dpower.finish(s));
+    LPVS_TRY(damp.finish(s));
+    LPVS_TRY(dwwz.finish(s));
+    LPVS_TRY(dneff.finish(s));
+    if (coef) LPVS_TRY(dcoef.finish(s));
+    LPVS_HIP(hipEventRecord(ev.e[5], s));
+    LPVS_HIP(hipStreamSynchronize(s));
+    float ms[5] = {0, 0, 0, 0, 0}, total = 0;
+    for (int i = 0; i < 5; ++i) LPVS_HIP(hipEventElapsedTime(&ms[i], ev.e[i], ev.e[i + 1]));
+    LPVS_HIP(hipEventElapsedTime(&total, ev.e[0], ev.e[5]));
+    double *g = g_wwz_timing;
+    g[0] = (double)Nf; g[1] = (double)Ntau; g[2] = sh.TT; g[3] = sh.ts; g[4] = (double)nitems; g[5] = (double)sh.slab_samples;
+    g[6] = (double)counters[0]; g[7] = (double)counters[1]; g[8] = work.staged; g[9] = work.useful;
+    g[10] = ms[0]; g[11] = ms[1]; g[12] = ms[2]; g[13] = ms[3]; g[14] = ms[4]; g[15] = total;
+    return LPVS_OK;
+}
+
+int32_t lpvs_wwz_f64(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const double *f, int64_t Nf, const double *tau, int64_t Ntau,
+                     double c, const double *radius, int32_t center_data, int32_t device, double *power_out, double *amplitude_out, double *wwz_out,
+                     double *neff_out, double *coef_out, int64_t *count_out, int32_t *empty_out) {
+    try {
+        if (!y || !t || !f || !tau || !radius || !power_out || !amplitude_out || !wwz_out || !neff_out) { set_error("NULL argument"); return LPVS_EARGUMENT; }
+        if (is_device_ptr(f) || is_device_ptr(tau) || is_device_ptr(radius) || (count_out && is_device_ptr(count_out)) || (empty_out && is_device_ptr(empty_out))) {
+            set_error("wwz: f, tau, radius, count_out and empty_out are host memory"); return LPVS_EARGUMENT;
+        }
+        const WwzShape sh = wwz_shape(N, ns, f, Nf, tau, Ntau, c, radius);        // (the counts are checked before an array is read)
+        if (sh.status != kWwzOk) { set_error("%s", sh.why.c_str()); return sh.status == kWwzArgument ? LPVS_EARGUMENT : LPVS_EUNSUPPORTED; }
+        return wwz_impl(y, ns, t, N, W, f, Nf, tau, Ntau, radius, sh, center_data != 0, device, power_out, amplitude_out, wwz_out, neff_out, coef_out, count_out,
+                        empty_out);
+    } catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
+}
+
+int32_t lpvs_wwz_last_timing(double *out, int32_t n) {
+    if (!out || n < 0) { set_error("NULL argument"); return LPVS_EARGUMENT; }
+    for (int32_t k = 0; k < n && k < 16; ++k) out[k] = g_wwz_timing[k];
+    return LPVS_OK;
+}
+
 // ---- the bootstrap of the Lomb-Scargle periodogram (lomb_boot.hip; the decisions: lomb_boot_plan.h) ------------------------------------------
 // what lpvs_lombscargle_bootstrap_last_timing reports of the calling thread's last call: [0] resamples, [1] chunks, [2] resamples per thread
 // (TS), [3] slab length, [4] slabs, [5] degenerate frequencies, ms of [6] staging, the scan and the shared sums of the record, [7] the

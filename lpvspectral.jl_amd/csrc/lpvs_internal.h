@@ -16,6 +16,7 @@
 #include "lomb_plan.h"
 #include "lomb_boot_plan.h"
 #include "lomb_terms_plan.h"
+#include "wwz_plan.h"
 
 namespace lpvs {
 
@@ -290,6 +291,27 @@ int32_t launch_lomb_terms_sums(const double *t, const double *w, const double *w
 // power[ns][Nf] (column-major Nf x ns), coef[2K + 1][ns][Nf] (a_h, b_h per harmonic, then c) or nullptr; ndeg_dev: one int, zeroed here
 int32_t launch_lomb_terms_epilogue(int K, const double *sums, int64_t Nf, int64_t ns, const double *mom_dev, const double *mean_dev, bool fit_mean, bool center,
                                    bool psd, int64_t N, double *power, double *coef, int *ndeg_dev, hipStream_t s);
+
+// weighted wavelet Z-transform (lpvs_wwz_f64; wwz.hip; the decisions: wwz_plan.h).  All pointers are device memory.
+struct WwzArgs {
+    const double *t = nullptr, *y = nullptr, *W = nullptr;       // the record: t[N], y[ns][N], W[N] or nullptr
+    const double *mean = nullptr;                                // [ns]: the record's weighted means that are removed, or nullptr
+    const double *f = nullptr, *decay = nullptr, *radius = nullptr;   // [Nf]
+    const double *tau = nullptr;                                 // [ngroups TT]: the times in ascending order (WwzShape::tau_sorted)
+    const int32_t *pos = nullptr;                                // [Ntau]: the place of the caller's time j in that order
+    const WwzItem *items = nullptr;                              // [nitems]
+    const int64_t *offset = nullptr, *first_slab = nullptr;      // [ngroups ftiles]: a pair's first item and the slab it covers
+    int64_t N = 0, Nf = 0, Ntau = 0, nitems = 0, ftiles = 0, slab_samples = 0, rows = 0;
+    int ns = 0, TT = 0;
+};
+int32_t launch_wwz_sorted(const double *t, int64_t N, int *flags_dev, hipStream_t s);
+int32_t launch_wwz_ranges(const double *t, int64_t N, const double *a, const double *b, int64_t na, const double *r, int64_t nr, int64_t *edges, hipStream_t s);
+// part: WwzWork::part_doubles doubles
+int32_t launch_wwz_sums(const WwzArgs &A, int ts, double *part, hipStream_t s);
+// power, amplitude, wwz[ns][Ntau][Nf], neff, count_out, empty_out[Ntau][Nf], coef[3][ns][Ntau][Nf] or nullptr; flags_dev |= 4: the weights of a cell do not sum
+// to a finite value, |= 16: a cell outside its pair's items (never); counters[2] = {empty, degenerate cells}
+int32_t launch_wwz_epilogue(const WwzArgs &A, const double *part, const int64_t *cell_edges, bool center, double *power, double *amplitude, double *wwz,
+                            double *neff, double *coef, int64_t *count_out, int32_t *empty_out, int *flags_dev, unsigned long long *counters, hipStream_t s);
 
 // ---- dense symmetric inverse (linalg.hip) ------------------------------------------------
 // In-place inverse of the SPD matrix A (np x np, np % 64 == 0, full symmetric storage) by
