@@ -44,8 +44,44 @@ inline void basis_centers(double lo, double hi, double amax, int64_t Nv, int cou
     }
 }
 
+// ---- double-double arithmetic for the slot tables -------------------------------------------------------------------------------------------
+// The tables hold frequencies as hi + lo (106 bits) because the kernels form the phase of the REAL product.  An 80-bit long double has 64:
+// a table worked in it is off by up to 2^-64 |w| per operation, a phase error of 2^-64 |w x| -- 4e-13 rad at |w x| = 6e6 and 7e-12 at 9e7,
+// measured in rational arithmetic (tests/test_phase_ref_host.py) -- so the tables are worked in double-double, with error-free sums and
+// products (an inf or NaN keeps a zero low word, so that it travels as it does in plain arithmetic).
+struct DD { double hi = 0, lo = 0; };
+inline DD dd_fast_sum(double a, double b) {              // |a| >= |b| (or a == 0)
+    const double s = a + b;
+    return std::isfinite(s) ? DD{s, b - (s - a)} : DD{s, 0.0};
+}
+inline DD dd_sum(double a, double b) {
+    const double s = a + b, bb = s - a;
+    return std::isfinite(s) ? DD{s, (a - (s - bb)) + (b - bb)} : DD{s, 0.0};
+}
+inline DD dd_add(DD a, DD b) {
+    DD s = dd_sum(a.hi, b.hi);
+    const DD t = dd_sum(a.lo, b.lo);
+    s = dd_fast_sum(s.hi, s.lo + t.hi);
+    return dd_fast_sum(s.hi, s.lo + t.lo);
+}
+inline DD dd_sub(DD a, DD b) { return dd_add(a, DD{-b.hi, -b.lo}); }
+inline DD dd_mul(DD a, double b) {
+    const double p = a.hi * b;
+    if (!std::isfinite(p)) return DD{p, 0.0};
+    return dd_fast_sum(p, std::fma(a.lo, b, std::fma(a.hi, b, -p)));
+}
+inline DD dd_div(DD a, double b) {                       // three quotient digits: the remainder after each is exact to double-double
+    const double q1 = a.hi / b;
+    if (!std::isfinite(q1)) return DD{q1, 0.0};
+    const DD r1 = dd_sub(a, dd_mul(DD{q1, 0.0}, b));
+    const double q2 = r1.hi / b;
+    const DD r2 = dd_sub(r1, dd_mul(DD{q2, 0.0}, b));
+    const DD q = dd_fast_sum(q1, q2);
+    return dd_fast_sum(q.hi, q.lo + r2.hi / b);
+}
+
 // ---- slot tables of the structured Gram (nudft.hip) ---------------------------------------------------------------------------------------
-// For frequencies w_f = a + f*D + eps_f: exact progressions in double-double, each family padded to a multiple of 8:
+// For frequencies w_f = a + f*D + eps_f: progressions worked and held in double-double, each family padded to a multiple of 8:
 //   [0, nf8): m*D (differences), [nf8, nf8+s8): 2a + s*D (sums); the right-hand side uses a + f*D, f < nf8.
 // MERGED layout: when 2a is (up to rounding) an integer multiple j0 < Nf of D -- default_freqs (a = 0), the README grid
 // w = D*(1..Nf) (a = D) -- the sum frequencies (j0 + s) D are multiples of D like the differences, so ONE progression
@@ -79,10 +115,10 @@ constexpr double kApF32KeepResidualPhase = 3e-3;
 inline ApSlots make_ap_slots(const std::vector<double> &hw, double xam, bool f32_grid) {
     ApSlots sl;
     const int64_t Nf = (int64_t)hw.size();
-    const long double a0 = hw[0], D = Nf > 1 ? ((long double)hw[Nf - 1] - (long double)hw[0]) / (long double)(Nf - 1) : 0.0L;
+    const DD a0{hw[0], 0.0}, D = Nf > 1 ? dd_div(dd_sum(hw[Nf - 1], -hw[0]), (double)(Nf - 1)) : DD{};
     sl.eps.resize((size_t)Nf);
     for (int64_t f = 0; f < Nf; ++f) {
-        sl.eps[f] = (double)((long double)hw[f] - (a0 + (long double)f * D));
+        sl.eps[f] = dd_sub(DD{hw[f], 0.0}, dd_add(a0, dd_mul(D, (double)f))).hi;
         sl.emax = std::fmax(sl.emax, std::fabs(sl.eps[f]));
     }
     double wam = 0;
@@ -94,29 +130,30 @@ inline ApSlots make_ap_slots(const std::vector<double> &hw, double xam, bool f32
     }
     if (!sl.ok) return sl;
     sl.nf8 = round_up(Nf, 8); sl.s8 = round_up(2 * Nf - 1, 8); sl.nsl = sl.nf8 + sl.s8;
-    auto split = [](long double v, double &hi, double &lo) { hi = (double)v; lo = (double)(v - (long double)hi); };
+    auto split = [](DD v, double &hi, double &lo) { hi = v.hi; lo = v.lo; };
+    const DD a2 = dd_mul(a0, 2.0);
     sl.omr_hi.resize((size_t)sl.nf8); sl.omr_lo.resize((size_t)sl.nf8);
     sl.s0 = sl.nf8;
-    if (Nf > 1 && D != 0.0L) {
-        const long double j0r = 2.0L * a0 / D;
+    if (Nf > 1 && D.hi != 0.0) {
+        const long double j0r = 2.0L * (long double)a0.hi / ((long double)D.hi + (long double)D.lo);
         const long long j0 = llroundl(j0r);
-        const long double delta = 2.0L * a0 - (long double)j0 * D;
-        if (j0 >= 0 && j0 < Nf && std::fabs((double)delta) * xam <= kApMaxResidualPhase) {
+        const double delta = dd_sub(a2, dd_mul(D, (double)j0)).hi;
+        if (j0 >= 0 && j0 < Nf && std::fabs(delta) * xam <= kApMaxResidualPhase) {
             sl.merged = true;
-            sl.s0 = j0; sl.delta = (double)delta;
+            sl.s0 = j0; sl.delta = delta;
             sl.nsl = round_up(j0 + 2 * Nf - 1, 8);
             sl.s8 = sl.nsl;
         }
     }
     sl.om_hi.resize((size_t)sl.nsl); sl.om_lo.resize((size_t)sl.nsl);
     if (sl.merged) {
-        for (int64_t j = 0; j < sl.nsl; ++j) split((long double)j * D, sl.om_hi[j], sl.om_lo[j]);
+        for (int64_t j = 0; j < sl.nsl; ++j) split(dd_mul(D, (double)j), sl.om_hi[j], sl.om_lo[j]);
     } else {
-        for (int64_t m = 0; m < sl.nf8; ++m) split((long double)m * D, sl.om_hi[m], sl.om_lo[m]);
-        for (int64_t q = 0; q < sl.s8; ++q) split(2.0L * a0 + (long double)q * D, sl.om_hi[sl.nf8 + q], sl.om_lo[sl.nf8 + q]);
+        for (int64_t m = 0; m < sl.nf8; ++m) split(dd_mul(D, (double)m), sl.om_hi[m], sl.om_lo[m]);
+        for (int64_t q = 0; q < sl.s8; ++q) split(dd_add(a2, dd_mul(D, (double)q)), sl.om_hi[sl.nf8 + q], sl.om_lo[sl.nf8 + q]);
     }
-    for (int64_t f = 0; f < sl.nf8; ++f) split(a0 + (long double)f * D, sl.omr_hi[f], sl.omr_lo[f]);
-    for (int b = 0; b < 8; ++b) split((long double)b * D, sl.step.hi[b], sl.step.lo[b]);
+    for (int64_t f = 0; f < sl.nf8; ++f) split(dd_add(a0, dd_mul(D, (double)f)), sl.omr_hi[f], sl.omr_lo[f]);
+    for (int b = 0; b < 8; ++b) split(dd_mul(D, (double)b), sl.step.hi[b], sl.step.lo[b]);
     return sl;
 }
 // Do the right-hand side's slots a + f*D ride the Gram's grid?  They are the modes s0/2 + f of the same step when s0 is even -> same

@@ -29,20 +29,25 @@ struct LombGrid {
     double D = 0;               // the step in cycles, rounded (reporting; the transforms use the angular steps below)
     double w1_hi = 0, w1_lo = 0;   // 2 pi D   in double-double: the angular step of family 1
     double w2_hi = 0, w2_lo = 0;   // 2 pi 2D: the angular step of family 2
-    long double Dl = 0;
+    DD Dd;                      // the step in cycles, double-double
 };
+// 2 pi in double-double (the next term is -6e-33)
+constexpr double kTwoPiHi = 6.283185307179586, kTwoPiLo = 2.4492935982947064e-16;
+inline DD dd_times_two_pi(DD a) {
+    const double p = a.hi * kTwoPiHi;
+    if (!std::isfinite(p)) return DD{p, 0.0};
+    return dd_fast_sum(p, std::fma(a.hi, kTwoPiHi, -p) + (a.hi * kTwoPiLo + a.lo * kTwoPiHi));
+}
 inline LombGrid lomb_admit(const std::vector<double> &f, double tam) {
     LombGrid g;
     if (f.size() < 2) return g;
     const ApSlots sl = make_ap_slots(f, 6.283185307179586 * tam, false);
     g.emax = sl.emax;
-    const long double D = ((long double)f.back() - (long double)f.front()) / (long double)(f.size() - 1);
-    if (!sl.ok || !(D != 0.0L) || !std::isfinite((double)D)) return g;
-    const long double twopi = 6.283185307179586476925286766559005768L;
-    auto split = [](long double v, double &hi, double &lo) { hi = (double)v; lo = (double)(v - (long double)hi); };
-    split(twopi * D, g.w1_hi, g.w1_lo);
-    split(2.0L * twopi * D, g.w2_hi, g.w2_lo);
-    g.a = f[0]; g.D = (double)D; g.Dl = D;
+    const DD D = dd_div(dd_sum(f.back(), -f.front()), (double)(f.size() - 1));       // as make_ap_slots forms it
+    if (!sl.ok || !(D.hi != 0.0) || !std::isfinite(D.hi)) return g;
+    const DD w1 = dd_times_two_pi(D), w2 = dd_mul(w1, 2.0);
+    g.w1_hi = w1.hi; g.w1_lo = w1.lo; g.w2_hi = w2.hi; g.w2_lo = w2.lo;
+    g.a = f[0]; g.D = D.hi; g.Dd = D;
     for (double e : sl.eps) g.twin = g.twin || e != 0.0;
     g.ok = true;
     return g;
@@ -55,7 +60,7 @@ inline LombGrid lomb_admit(const std::vector<double> &f, double tam) {
 //   family 2 (C2, S2):        modes j of step 2D  ...                                                       base2 = 2 f[k0]
 // The base is a frequency of the grid itself, a double, so the pre-phase is that of the exact product base * t (an error-free product in
 // the kernel, as the direct path forms every phase); what is left of a frequency inside its block,
-//   eps'_j = f[k0 + j] - f[k0] - j D   (long double: the differences are small),
+//   eps'_j = f[k0 + j] - f[k0] - j D   (double-double, as the step itself: gram_form_plan.h says why long double is not enough),
 // joins the first-order term (family 2: 2 eps'_j).  A block whose base is 0 needs no pre-phase; every block of a family shares one fine
 // grid (that of the longest block), so the sample coordinates are computed once per family.
 inline int lomb_max_block() {
@@ -92,7 +97,7 @@ inline std::vector<double> lomb_block_residuals(const std::vector<double> &f, co
     std::vector<double> e(f.size());
     for (size_t k = 0; k < f.size(); ++k) {
         const size_t k0 = k / (size_t)L * (size_t)L;
-        e[k] = (double)(((long double)f[k] - (long double)f[k0]) - (long double)(k - k0) * g.Dl);
+        e[k] = dd_sub(dd_sum(f[k], -f[k0]), dd_mul(g.Dd, (double)(k - k0))).hi;
     }
     return e;
 }

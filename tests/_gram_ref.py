@@ -162,3 +162,74 @@ def struct_fourier_inputs(case):
     f = (np.arange(Nf) if zero else np.arange(1, Nf + 1)) / 97.0
     y = np.sin(2 * np.pi * f[7] * t) + 0.2 * rng.standard_normal(N)
     return y, t, f, (rng.random(N) + 0.5 if weighted else None)
+
+
+# ---- the structured forms where the low words of their phases decide (tests/_phase_ref.py holds the reference) -----------------------------
+# u = 2^-53.  Bound per entry: |G - G_ref| <= (1e-12 + q) C[j][j'], |b - b_ref| <= (1e-12 + q) sum_k |K_kj y_k| (Fourier: the weight sums of
+# _phase_ref.fourier_gram_exact).  1e-12 is the stated tolerance of these forms (csrc/nufft.hip's header); at N = 4096 it also
+# covers the direct sums' (N + 16) u = 4.6e-13.  q holds only the squares the kernel headers name, from the inputs in long double
+# (_phase_ref.second_order): ((2 emax + |delta|) max|x|)^2 / 2 and (u max|w| max|x|)^2 / 2; q <= 1e-13 is asserted.  NOTHING grows with |w||x|.
+# (id, Nf, Nv, grid, max|x|, a / D, planted max|eps| max|x|, signals)
+PHASE_XMAX = 2.0e4
+PHASE_LPV_CASES = [
+    ("bench-24x3", 24, 3, "natural", PHASE_XMAX, 1.0, 0.0, 1),         # w = 2 pi (1 .. Nf) 25 / Nf: natural rounding residuals, |w x| to 3.1e6 rad
+    ("bench-20x8", 20, 8, "natural", PHASE_XMAX, 1.0, 0.0, 1),
+    ("bench-24x3-multi", 24, 3, "natural", PHASE_XMAX, 1.0, 0.0, 3),   # lpv_multi: the rhs calls reuse coordinates and binning
+    ("beyond-24x3", 24, 3, "dyadic", None, 1.0, 0.0, 1),               # w = k 93 / 128: eps = 0 exactly, max|w x| = 2^30 rad
+    ("resid-a=D", 24, 3, "natural", PHASE_XMAX, 1.0, 0.9e-7, 1),       # merged, s0 = 2: rhs on the grid
+    ("resid-a=1.5D", 24, 3, "natural", PHASE_XMAX, 1.5, 0.9e-7, 1),    # merged, s0 = 3: rhs direct, delta != 0 allowed
+    ("resid-a=0", 24, 3, "natural", PHASE_XMAX, 0.0, 0.9e-7, 1),       # merged, s0 = 0: zero frequency
+    ("resid-split", 24, 3, "natural", PHASE_XMAX, 1.37, 0.9e-7, 1),    # 2a is no multiple of D: two slot families, ap in both modes
+]
+# predict's type-2 path (tests/test_gpu_predict.py): the (24, 3) shape from a = 2.5 D, so that the rotation e^{i a x} reaches 3.3e5 rad and
+# the FMA error of a x, half an ulp of 2^18, is 2.9e-11 rad -- more than ten times the bound (from a = D it would be seven times; from
+# a = 2 D the step of this grid happens to be a double, and its low word zero)
+PHASE_PREDICT_CASES = [
+    ("predict-24x3", 24, 3, "natural", PHASE_XMAX, 2.5, 0.0, 1),
+    ("predict-24x3-residuals", 24, 3, "natural", PHASE_XMAX, 2.5, 0.9e-7, 1),
+    ("predict-24x3-beyond", 24, 3, "dyadic", None, 1.0, 0.0, 1),
+]
+PHASE_LPV = {c[0]: c for c in PHASE_LPV_CASES + PHASE_PREDICT_CASES}
+PHASE_N = 4096
+
+
+def phase_lpv_inputs(case):
+    """(Y, X, V, w): X unsorted, both signs, full-mantissa doubles; Y (N,) or (N, ns)."""
+    cid, Nf, Nv, grid, xmax, a_over_D, resid, ns = case
+    rng = np.random.default_rng(4000 + 10 * Nf + Nv + int(100 * a_over_D) + (7 if resid else 0))
+    N = PHASE_N
+    if grid == "dyadic":
+        w = np.arange(1, Nf + 1) * (93.0 / 128.0)
+        xmax = 2.0 ** 30 / w[-1]
+    else:
+        w = 2 * np.pi * (a_over_D + np.arange(Nf)) * 25.0 / Nf
+    X = rng.uniform(-xmax, xmax, N)
+    X[0], X[1] = xmax, -xmax                                       # the extremes are present
+    V = rng.uniform(-1.0, 1.0, N)
+    if resid:
+        eps = rng.uniform(-1.0, 1.0, Nf)
+        eps[0] = eps[-1] = 0.0
+        w = w + eps * (resid / (np.abs(eps).max() * xmax))
+    Y = rng.standard_normal((N, ns))
+    return (Y[:, 0] if ns == 1 else Y), X, V, w
+
+
+def phase_fourier_inputs(case):
+    """STRUCT_FOURIER_CASES' shapes with full-mantissa stamps in [2^24, 2^24 + 300]: a window late in a long record."""
+    cid, Nf, zero, weighted, N = case
+    rng = np.random.default_rng(1700 + int(zero) + 2 * int(weighted))
+    t = 2.0 ** 24 + np.sort(rng.random(N) * 300.0)
+    f = (np.arange(Nf) if zero else np.arange(1, Nf + 1)) / 97.0
+    y = np.sin(2 * np.pi * f[7] * (t - 2.0 ** 24)) + 0.2 * rng.standard_normal(N)
+    return y, t, f, (rng.random(N) + 0.5 if weighted else None)
+
+
+def phase_window_inputs():
+    """(n, nwin, Nf, t, f, Y): three windows of 2048 samples late in a long record, t = 2^26 + k / 2 + jitter (full mantissa), 33 frequencies
+    k / 68 (a = D: 72 merged slots, at least the 64 the batched transform asks for), two signals."""
+    rng = np.random.default_rng(2048)
+    n, nwin, Nf = 2048, 3, 33
+    t = 2.0 ** 26 + 0.5 * np.arange(n * nwin) + 0.2 * rng.random(n * nwin)
+    f = np.arange(1, Nf + 1) / 68.0
+    Y = [np.sin(2 * np.pi * f[5 + 9 * q] * (t - 2.0 ** 26) + q) + 0.3 * rng.standard_normal(n * nwin) for q in range(2)]
+    return n, nwin, Nf, t, f, Y

@@ -86,3 +86,38 @@ def lomb_ref(y, t, f, W=None, fit_mean=True, center_data=True, normalization="st
     r.update(D=D[:, 0], degenerate=deg, CC=CC[:, 0], SS=SS[:, 0], CS=CS[:, 0], YYf=np.broadcast_to(YY, p.shape)[0], YCf=YC, YSf=YS,
              power=np.where(z, LD(0), power), a=np.where(z, LD(0), a), b=np.where(z, LD(0), b), c=np.where(z, LD(0), c), p=np.where(z, LD(0), p))
     return r
+
+
+# ---- inputs whose products f t are all inexact (the GPU tests' second family of cases) -------------------------------------------------------
+# The first family keeps t on multiples of 2^-10 over a few tens of units and f on multiples of 2^-6: every product is exact and the low
+# word e of csrc/lomb_device.h: lomb_sincos is identically zero.  Here t spans [0, 2^20] -- still on the 2^-10 lattice where a test needs
+# t - lo or t - tau exact, full-mantissa doubles otherwise -- and f are full-mantissa doubles in (0, 3]: f t reaches 3e6 turns, e is up to
+# 2^-54 f t = 2e-10 turns, and a kernel without it misses every bound by orders of magnitude (tests/test_phase_ref_host.py).
+LATE_SPAN = 2 ** 20
+WIDE_STEP = 0.0123                                    # no binary fraction: the grids a + k D carry natural rounding residuals
+
+
+def late_times(rng, N, lattice=True):
+    """N sorted times in [0, 2^20]: multiples of 2^-10, or full-mantissa doubles."""
+    return np.sort(rng.integers(0, LATE_SPAN * 1024, N) / 1024.0 if lattice else rng.uniform(0.0, LATE_SPAN, N))
+
+
+def wide_freqs(rng, Nf):
+    """Nf distinct full-mantissa frequencies in (0, 3], sorted."""
+    return np.sort(3.0 - rng.uniform(0.0, 3.0, Nf))
+
+
+def wide_grid(first, Nf=200):
+    """a + k D with a = first * D, as doubles round it (first = 0: the zero frequency leads)."""
+    return first * WIDE_STEP + WIDE_STEP * np.arange(Nf)
+
+
+def block_residual_phase(f, t, block=None):
+    """2 pi max|f[k] - f[k0] - (k - k0) D| max|t| in radians, D the end-point step and k0 the first frequency of k's block (csrc/lomb_plan.h:
+    lomb_block_residuals), in rational arithmetic: the residual phase whose square the transform path drops."""
+    from fractions import Fraction
+    fq = [Fraction(float(v)) for v in f]
+    D = (fq[-1] - fq[0]) / (len(fq) - 1)
+    L = len(fq) if block is None else block
+    e = max(abs(fq[k] - fq[k // L * L] - (k - k // L * L) * D) for k in range(len(fq)))
+    return float(2 * np.arccos(LD(-1))) * float(e) * float(np.abs(t).max())

@@ -14,11 +14,13 @@ no value check.  gram_kernel<0,16> and <0,8> are held to the bound at nb = 320 a
 (16-sample) images past 160 KiB.
 
 The structured forms (ap, ap-nufft) are held, entry by entry, to a long-double Gram with long-double phases at the scale of the activation pair
-(last section).  Every test prints its worst ratio to the bound; DESIGN 4.3.1 tabulates them."""
+(second to last section), and, where the low words of their phases decide (|w x| from 3e6 to 2^30 rad), G and b to a long-double Gram whose phases
+are those of the real products (last section).  Every test prints its worst ratio to the bound; DESIGN 4.3.1 tabulates them."""
 import numpy as np
 import pytest
 
 import _gram_ref as R
+import _phase_ref as PR
 from _guards import precondition_not_met
 
 pytestmark = pytest.mark.gpu
@@ -323,3 +325,139 @@ def test_structured_fourier_gram_at_weight_scale(L, oracle, monkeypatch, case):
     for mode, (G, tm) in res.items():
         assert worst[mode] <= 1.0, (cid, mode, worst)
         assert np.array_equal(G, G.T)
+
+
+# ---------------------------------------------------------------------------------------------------------------- structured forms, exact phases
+# The cases above keep |w x| <= 1e3 rad, where the low words of the device's phases (the FMA error of omega x, the low word of the
+# double-double slot frequency, the first-order use of both) move a phase by 1e-13: below the tolerance.  Here they decide: |w x| reaches
+# 3e6 rad (the benchmark's scale), 4e7 rad (Fourier stamps late in a record) and 2^30 rad, against tests/_phase_ref.py, whose phases are
+# those of the real products at any magnitude.  Bound (tests/_gram_ref.py): (1e-12 + q) x the weight sum, q <= 1e-13 the squares the kernel
+# headers name; nothing grows with |w||x|.  tests/test_phase_ref_host.py shows on the CPU that a kernel which dropped or negated any one low
+# word would miss these bounds by a factor of ten or more, term by term.
+PHASE_SLOT = {"bench-24x3": (True, 2), "bench-20x8": (True, 2), "bench-24x3-multi": (True, 2), "beyond-24x3": (True, 2), "resid-a=D": (True, 2),
+              "resid-a=1.5D": (True, 3), "resid-a=0": (True, 0), "resid-split": (False, None)}
+
+
+def _phase_tol(w, x, name):
+    q = PR.second_order(w, x)
+    assert q <= 1e-13, (name, float(q))                          # so that q cannot hide anything
+    return 1e-12 + q
+
+
+@pytest.mark.parametrize("cid", [c[0] for c in R.PHASE_LPV_CASES])
+def test_structured_lpv_gram_and_rhs_against_exact_phases(L, monkeypatch, cid):
+    """G AND b of ap / ap-nufft, every entry, where the low words of the phases decide: the benchmark's scale with natural rounding
+    residuals (one and three signals), 2^30 rad on a dyadic grid, and planted residuals at the admission limit in every slot layout (merged
+    with s0 = 2, 3, 0; split, which keeps the direct sums)."""
+    case = R.PHASE_LPV[cid]
+    _, Nf, Nv, grid, _, a_over_D, resid, ns = case
+    Y, X, V, w = R.phase_lpv_inputs(case)
+    N, n = R.PHASE_N, 2 * Nf * Nv
+    xmax = np.abs(X).max()
+    merged, s0, delta = PR.merged_slot(w, xmax)
+    assert (merged, s0) == PHASE_SLOT[cid] and (grid != "dyadic" or (delta == 0.0 and not PR.progression(w)[2].any()))
+    if resid:
+        eps = PR.progression(w)[2]
+        assert eps[0] == 0.0 and eps[-1] == 0.0 and 0.85e-7 <= np.abs(eps).max() * xmax <= 1e-7
+    tol = _phase_tol(w, X, cid)
+    G_ref, b_ref, C, s = PR.lpv_gram_exact(X, w, L.basis_activation_func(V, Nv), Y)     # the device's activation table
+    if not (C.min() > 1e-200 and s.min() > 1e-200):
+        precondition_not_met(f"{cid}: a scale underflows ({float(C.min()):.3g}, {float(s.min()):.3g})")
+    j = np.arange(n) % Nv
+    bG, bb = tol * C[np.ix_(j, j)], tol * s[j].reshape(n, -1)
+    want = {"direct": "ap", "default": "ap" if not merged else "ap-nufft"}
+    worst = {}
+    for mode in ("direct", "default"):
+        if mode == "direct":
+            monkeypatch.setenv("LPVS_NUDFT", "direct")
+        else:
+            monkeypatch.delenv("LPVS_NUDFT", raising=False)
+        with (L.Problem.lpv_multi(Y, X, V, w, Nv) if ns > 1 else L.Problem.lpv(Y, X, V, w, Nv)) as p:
+            G, b = p.get_gram()
+            if ns > 1:
+                b = p.get_rhs()
+            tm = p.timing()
+        assert tm["gram_form"] == want[mode] and tm["gram_stage"] == 0 and tm["gram_ksplit"] == 0, (cid, mode, tm["gram_form"])
+        assert G.shape == (n, n) and np.array_equal(G, G.T)
+        rg = np.abs(G.astype(PR.LD) - G_ref) / bG
+        rb = np.abs(b.reshape(n, -1).astype(PR.LD) - b_ref.reshape(n, -1)) / bb
+        worst[mode] = (float(rg.max()), float(rb.max()))
+        print(f"{cid} {tm['gram_form']} ({mode}): max|w x| = {np.abs(w).max() * xmax:.3g} rad, worst |G - G_ref| / bound {rg.max():.4f} over {rg.size} entries, "
+              f"worst |b - b_ref| / bound {rb.max():.4f} over {rb.size}")
+    monkeypatch.delenv("LPVS_NUDFT", raising=False)
+    assert all(r <= 1.0 for pair in worst.values() for r in pair), (cid, worst)
+
+
+@pytest.mark.parametrize("case", R.STRUCT_FOURIER_CASES, ids=[c[0] for c in R.STRUCT_FOURIER_CASES])
+def test_structured_fourier_gram_and_rhs_against_exact_phases(L, monkeypatch, case):
+    """Full-mantissa stamps in [2^24, 2^24 + 300]: |w t| = 4e7 rad (nudft_single_kernel, ap_assemble_fourier_kernel, ap_rhs_fourier_kernel)."""
+    cid, Nf, zero, weighted, N = case
+    y, t, f, W = R.phase_fourier_inputs(case)
+    w = 6.283185307179586 * f                                    # as the library rounds it
+    tol = _phase_tol(w, t, cid)
+    G_ref, b_ref, sG, sb = PR.fourier_gram_exact(t, w, y, zero, W)
+    worst = {}
+    for mode in ("direct", "default"):
+        if mode == "direct":
+            monkeypatch.setenv("LPVS_NUDFT", "direct")
+        else:
+            monkeypatch.delenv("LPVS_NUDFT", raising=False)
+        with L.Problem.fourier(y, t, f, W) as p:
+            G, b = p.get_gram()
+            tm = p.timing()
+        assert tm["gram_form"] == "ap" and tm["gram_stage"] == 0 and tm["gram_ksplit"] == 0, (mode, tm)
+        assert np.array_equal(G, G.T)
+        rg, rb = np.abs(G.astype(PR.LD) - G_ref) / (tol * sG), np.abs(b.astype(PR.LD) - b_ref) / (tol * sb)
+        worst[mode] = (float(rg.max()), float(rb.max()))
+        print(f"{cid} ap ({mode}): max|w t| = {w.max() * t.max():.3g} rad, worst |G - G_ref| / bound {rg.max():.4f} over {rg.size} entries, "
+              f"worst |b - b_ref| / bound {rb.max():.4f} over {rb.size}")
+    monkeypatch.delenv("LPVS_NUDFT", raising=False)
+    assert all(r <= 1.0 for pair in worst.values() for r in pair), (cid, worst)
+
+
+def _solve_ld(H, q):
+    """H x = q in long double: a double solve refined three times on long-double residuals (cond(H) ~ 1e4: each step gains 12 digits)."""
+    Hd = H.astype(np.float64)
+    x = np.linalg.solve(Hd, q.astype(np.float64)).astype(PR.LD)
+    for _ in range(3):
+        x = x + np.linalg.solve(Hd, (q - H @ x).astype(np.float64)).astype(PR.LD)
+    return x
+
+
+def test_window_engine_structured_forms_against_exact_phases(L, monkeypatch):
+    """Three Hann windows of 2048 samples late in a long record (t = 2^26 + k / 2 + jitter, full mantissa: |w t| = 2e8 rad), 33 frequencies
+    (72 slots), two signals: the engine's structured forms -- nudft with segments (LPVS_NUDFT=direct: ap) and nufft_window_kernel (default:
+    ap-nufft) -- through the dense estimator (Q + lam I) x = q, against the long-double solve of the exact-phase Q, q.  The engine returns no
+    Gram, so the tolerance is that of test_weighted_window_grams_entry_by_entry_and_through_the_batch with this section's entry bounds in place of
+    R.bound: cond(H) (||B_Q||_F / ||H|| + ||B_q|| / ||q|| + n 2^-53), B_Q = (1e-12 + q) sum|W| / (2 Nf) and B_q = (1e-12 + q) sum|W y| / sqrt(2 Nf)
+    per entry."""
+    from lpvspectral_jl_amd import api
+    n, nwin, Nf, t, f, Y = R.phase_window_inputs()
+    lam, w = 1e-3, 6.283185307179586 * f
+    W = np.asarray(L.hanning(n), dtype=np.float64)
+    tol = _phase_tol(w, t, "windows")
+    eng = dict(estimator=2, lam=lam, prox=(1, 0.0, 0), μ=0.05, tol=0.0, iters=0, sign=1)
+    res = {}
+    for mode in ("direct", "default"):
+        if mode == "direct":
+            monkeypatch.setenv("LPVS_NUDFT", "direct")
+        else:
+            monkeypatch.delenv("LPVS_NUDFT", raising=False)
+        res[mode] = api.windows_estimate(Y, t, f, n, 0, W, eng)[0]
+        assert res[mode].shape == (2, nwin, Nf) and api.windowpsd_last_timing()["gram_form"] == ("ap" if mode == "direct" else "ap-nufft")
+    monkeypatch.delenv("LPVS_NUDFT", raising=False)
+    worst = {"direct": 0.0, "default": 0.0}
+    for i in range(nwin):
+        ti = t[i * n:(i + 1) * n]
+        for q in range(2):
+            G_ref, b_ref, sG, sb = PR.fourier_gram_exact(ti, w, Y[q][i * n:(i + 1) * n], False, W)
+            H = G_ref + lam * np.eye(2 * Nf)
+            sv = np.linalg.svd(H.astype(np.float64), compute_uv=False)
+            bound = sv[0] / sv[-1] * (float(tol * sG) * 2 * Nf / sv[0] + float(tol * sb) * np.sqrt(2 * Nf) / float(np.linalg.norm(b_ref.astype(np.float64))) + 2 * Nf * R.U)
+            xr = _solve_ld(H, b_ref)
+            xr = (xr[:Nf] + 1j * xr[Nf:]).astype(np.complex128)
+            for mode, x in res.items():
+                e = np.linalg.norm(x[q, i] - xr) / np.linalg.norm(xr)
+                worst[mode] = max(worst[mode], e / bound)
+                print(f"window {i} signal {q} ({mode}): (Q + lam I) x = q vs the exact-phase long-double solve: rel-L2 {e:.2e}, bound {bound:.2e} (cond {sv[0] / sv[-1]:.1f})")
+    assert worst["direct"] <= 1.0 and worst["default"] <= 1.0, worst

@@ -3,11 +3,16 @@
 INPUTS.  t in multiples of 2^-10 over 40 units, f in multiples of 2^-6 (2^-8 for the grid from a = 37.25 D, 2^-34 for the grid with
 residuals): every product f t is exact in double, so the reference's phases are beyond dispute.  Times are random, non-uniform and, at
 N = 1000, not sorted.  Weights are drawn from [0.5, 2].
+INEXACT PRODUCTS (the cases named "wide"; tests/_lomb_ref.py).  t over [0, 2^20] on multiples of 2^-10 or as full-mantissa doubles, f
+full-mantissa doubles in (0, 3]: every product f t is inexact and reaches 3e6 turns, so the low word e = fma(f, t, -p) of
+csrc/lomb_device.h: lomb_sincos carries up to 2e-10 turns -- 1e-9 rad, against bounds of 5e-13.  The reference forms the same exact turns.
 
 BOUNDS (u = 2^-53).
   direct sums:     |sum - ref| <= (N + 16) u sum|terms| + 4 u per term of trigonometry -- the bound tests/test_gpu_gram_dense.py holds its
                    sums to.  For the double-angle rows the four ulps of cos and of sin pass through c^2 - s^2 and 2 s c:
                    |d(c^2 - s^2)|, |d(2 s c)| <= 2 (|c| + |s|) 4 u <= 2 sqrt(2) 4 u per term.
+                   Inexact products: 6 u in place of the 4 u.  r = (p - rint(p)) + e now rounds once, |r| <= 1/2, so the phase moves by
+                   at most 2 pi 2^-55 <= 1.6 u on top of the sincospi.
   transform sums:  |sum - ref| <= 1e-12 sum|terms| -- what tests/test_gpu_nufft.py holds the same spreading to -- plus, for the grid with
                    frequency residuals, the dropped second-order term (residual phase)^2 / 2 sum|weights|; the double-angle family
                    applies the residuals twice over, so its phase is twice as large.
@@ -23,7 +28,7 @@ import os
 import numpy as np
 import pytest
 
-from _lomb_ref import LD, lomb_ref
+from _lomb_ref import LD, block_residual_phase, late_times, lomb_ref, wide_freqs, wide_grid
 
 pytestmark = pytest.mark.gpu
 U = 2.0 ** -53
@@ -31,10 +36,14 @@ U = 2.0 ** -53
 
 # ---- inputs ------------------------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
-def _record(N, ns, seed=0):
+def _record(N, ns, seed=0, rec=None):
+    """rec = "lattice" / "full": times over [0, 2^20] on multiples of 2^-10 / as full-mantissa doubles (tests/_lomb_ref.py)."""
     rng = np.random.default_rng(1000 * N + 10 * ns + seed)
-    t = rng.integers(0, 40 * 1024, N) / 1024.0
-    if N != 1000:
+    if rec:
+        t = late_times(rng, N, rec == "lattice")
+    else:
+        t = rng.integers(0, 40 * 1024, N) / 1024.0
+    if N != 1000 and not rec:
         t = np.sort(t)
     y = np.cos(2 * np.pi * 1.25 * t[:, None] + np.arange(ns)[None, :]) * (1.0 + np.arange(ns))[None, :] + 0.5 * rng.standard_normal((N, ns)) + 0.75
     W = rng.uniform(0.5, 2.0, N)
@@ -69,16 +78,32 @@ def _grid(kind, Nf=200):
 
 
 @functools.lru_cache(maxsize=None)
-def _ref(N, ns, fkey, fit_mean=True, center=True, normalization="standard", removed=None):
+def _wide(kind, Nf=200):
+    """Full-mantissa frequencies in (0, 3] (tests/_lomb_ref.py): "wide-irregular", and the progressions "wide-zero" (from 0) and
+    "wide-offset" (from a = 37.25 D) of a step that is no binary fraction."""
+    f = wide_freqs(np.random.default_rng(50 + Nf), Nf) if kind == "wide-irregular" else wide_grid(0.0 if kind == "wide-zero" else 37.25, Nf)
+    f.setflags(write=False)
+    return f
+
+
+def _freqs(fkey):
+    if fkey[0].startswith("wide"):
+        return _wide(*fkey)
+    return _irregular(fkey[1]) if fkey[0] == "irregular" else _grid(fkey[0])
+
+
+@functools.lru_cache(maxsize=None)
+def _ref(N, ns, fkey, fit_mean=True, center=True, normalization="standard", removed=None, rec=None):
     """removed: the means the device removed, as a tuple (the cache's key: the device gives the same bits every time)."""
-    t, y, W = _record(N, ns)
-    f = _irregular(fkey[1]) if fkey[0] == "irregular" else _grid(fkey[0])
+    t, y, W = _record(N, ns, rec=rec)
+    f = _freqs(fkey)
     return lomb_ref(y, t, f, W=W, fit_mean=fit_mean, center_data=center, normalization=normalization, removed=None if removed is None else np.array(removed))
 
 
 # ---- bounds --------------------------------------------------------------------------------------------------------------------------------
-def _sum_bounds(r, t, y, W, transform, eps_phase=0.0):
-    """Bounds of every raw sum, same keys and shapes as the reference's (r: centred with the device's means)."""
+def _sum_bounds(r, t, y, W, transform, eps_phase=0.0, trig=4):
+    """Bounds of every raw sum, same keys and shapes as the reference's (r: centred with the device's means).  trig: the ulps of
+    trigonometry per term of the direct sums, 4 where every product f t is exact and 6 where it is not (the module's docstring)."""
     N = len(t)
     w = (W / W.sum()).astype(LD)
     yc = y.astype(LD) - r["removed"][None, :]
@@ -91,11 +116,11 @@ def _sum_bounds(r, t, y, W, transform, eps_phase=0.0):
             b[k] = 1e-12 * r["abs_" + k] + 0.5 * eps_phase ** 2 * swy[:, None]
     else:
         for k in ("C", "S"):
-            b[k] = (N + 16) * U * r["abs_" + k] + 4 * U * sw
+            b[k] = (N + 16) * U * r["abs_" + k] + trig * U * sw
         for k in ("C2", "S2"):
-            b[k] = (N + 16) * U * r["abs_" + k] + 2 * np.sqrt(2.0) * 4 * U * sw
+            b[k] = (N + 16) * U * r["abs_" + k] + 2 * np.sqrt(2.0) * trig * U * sw
         for k in ("YC", "YS"):
-            b[k] = (N + 16) * U * r["abs_" + k] + 4 * U * swy[:, None]
+            b[k] = (N + 16) * U * r["abs_" + k] + trig * U * swy[:, None]
     b["Y"] = (N + 16) * U * swy
     b["YY"] = (N + 16) * U * swyy
     b["mean"] = (N + 16) * U * r["abs_mean"]
@@ -145,17 +170,17 @@ def _ratio(err, bound):
     return float(np.max(err / np.where(bound > 0, bound, LD(1)), initial=0.0))
 
 
-def _check(L, N, ns, fkey, path, fit_mean=True, center=True, normalization="standard", eps_phase=0.0):
-    t, y, W = _record(N, ns)
-    f = _irregular(fkey[1]) if fkey[0] == "irregular" else _grid(fkey[0])
+def _check(L, N, ns, fkey, path, fit_mean=True, center=True, normalization="standard", eps_phase=0.0, rec=None):
+    t, y, W = _record(N, ns, rec=rec)
+    f = _freqs(fkey)
     P, (a, b, c), sums = L.lombscargle(y if ns > 1 else y[:, 0], t, f, W=W, fit_mean=fit_mean, center_data=center, normalization=normalization, path=path,
                                        coef=True, return_sums=True)
     tm = L.lombscargle_last_timing()
-    r = _ref(N, ns, fkey, fit_mean, center, normalization, tuple(sums["mean"]) if center else None)
+    r = _ref(N, ns, fkey, fit_mean, center, normalization, tuple(sums["mean"]) if center else None, rec)
     deg = r["degenerate"]
     assert np.all((r["D"][~deg] >= 0.01)) and np.all(r["D"][deg] <= 2.0 ** -45), "the inputs are to stay clear of the degenerate threshold"
     assert tm["path"] == path and tm["degenerate"] == int(deg.sum())
-    bs = _sum_bounds(r, t, y, W, path == "nufft", eps_phase)
+    bs = _sum_bounds(r, t, y, W, path == "nufft", eps_phase, 6 if rec else 4)
     for k in ("mean", "C", "S", "C2", "S2", "YC", "YS", "Y", "YY"):
         err = np.abs(sums[k].astype(LD) - r[k])
         print(k, "worst error / bound:", _ratio(err, bs[k]))
@@ -215,6 +240,32 @@ def test_transform_takes_frequency_residuals_to_first_order(L, monkeypatch, bloc
         monkeypatch.setenv("LPVS_LOMB_BLOCK", str(block))
     tm = _check(L, 4097, 1, ("residual",), "nufft", fit_mean=False, center=False, eps_phase=2 * np.pi * 2.0 ** -33 * 40.0)
     assert tm["twin"] and tm["blocks"] == ((1, 1) if block is None else (4, 4))
+
+
+# ---- inexact products ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("rec", ["lattice", "full"])
+def test_direct_sums_of_inexact_products(L, rec):
+    """N = 4097 (five slabs), 65 frequencies (two tiles), three signals; every f t inexact, up to 3e6 turns."""
+    tm = _check(L, 4097, 3, ("wide-irregular", 65), "direct", rec=rec)
+    assert tm["blocks"] == (0, 0) and tm["nf"] == 0 and tm["slabs"] == 5 and tm["degenerate"] == 0
+
+
+@pytest.mark.parametrize("block", [None, 64])
+@pytest.mark.parametrize("kind", ["wide-zero", "wide-offset"])
+def test_transform_sums_of_inexact_products(L, monkeypatch, kind, block):
+    """200 frequencies a + k D of a step that is no binary fraction, from a = 0 and from a = 37.25 D, t to 2^20: the pre-phase of the
+    blocks' bases (lomb_prephase_kernel: lomb_sincos on inexact products), the coordinates (nu_phase_turns of 2 pi D t = 8e4 rad) and the
+    natural rounding residuals of the grid, taken to first order (twin)."""
+    if block is None:
+        monkeypatch.delenv("LPVS_LOMB_BLOCK", raising=False)
+    else:
+        monkeypatch.setenv("LPVS_LOMB_BLOCK", str(block))
+    t = _record(4097, 3, rec="lattice")[0]
+    eps_phase = block_residual_phase(_wide(kind), t, block)
+    assert 0.0 < eps_phase <= 2e-7                                           # (csrc/lomb_plan.h: twice the admitted 1e-7 at the most)
+    tm = _check(L, 4097, 3, (kind,), "nufft", eps_phase=eps_phase, rec="lattice")
+    assert tm["blocks"] == ((1, 1) if block is None else (4, 4)) and tm["nf"] == (1024 if block is None else 256)
+    assert tm["degenerate"] == (1 if kind == "wide-zero" else 0) and tm["slabs"] == 0 and tm["twin"]
 
 
 def test_a_constant_signal_has_standard_power_zero(L):

@@ -7,6 +7,9 @@ tiles of frequencies, the second partial -- so that every product f t is exact; 
 records with 0.6 cos(2 pi 1.25 t + 0.3) added.  N = 301 (odd: half of the last pair of the stream, one partial stage of samples) and
 N = two slabs + 453 of the plan's slab (read from last_timing); B = 37 (no multiple of either TS); seed 5.
 
+One case more, on the long record: t over [0, 2^20] (on the 2^-10 lattice, and as full-mantissa doubles) and full-mantissa frequencies in
+(0, 3] (tests/_lomb_ref.py): every product f t is inexact, and the trigonometry allowance is 6 u.
+
 BOUNDS (u = 2^-53): those tests/test_gpu_lomb.py derives for direct sums -- every raw sum within (N + 16) u sum|terms| + 4 u per term of
 trigonometry -- passed through the epilogue to first order by the REFERENCE's D (its _sum_bounds / _epilogue_bounds, imported).  The
 reference is centred with the means the device reports (held to (N + 16) u sum w|y*|), as there.  Precondition, asserted: the reference's
@@ -19,7 +22,7 @@ import numpy as np
 import pytest
 
 from _cnormal_ref import uniform_words
-from _lomb_ref import LD, lomb_ref
+from _lomb_ref import LD, late_times, lomb_ref, wide_freqs
 from test_gpu_lomb import _epilogue_bounds, _irregular, _ratio, _sum_bounds
 
 pytestmark = pytest.mark.gpu
@@ -31,9 +34,10 @@ N_SMALL, N_LONG = 301, 2 * SLAB + 453
 
 # ---- inputs --------------------------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
-def _record(N, tone=False):
+def _record(N, tone=False, rec=None):
+    """rec = "lattice" / "full": times over [0, 2^20] on multiples of 2^-10 / as full-mantissa doubles (tests/_lomb_ref.py)."""
     rng = np.random.default_rng(77 + N)
-    t = np.sort(rng.integers(0, 40 * 1024, N) / 1024.0)
+    t = late_times(rng, N, rec == "lattice") if rec else np.sort(rng.integers(0, 40 * 1024, N) / 1024.0)
     y = 0.5 * rng.standard_normal(N) + 0.75
     W = rng.uniform(0.5, 2.0, N)
     if tone:
@@ -41,6 +45,16 @@ def _record(N, tone=False):
     for a in (t, y, W):
         a.setflags(write=False)
     return t, y, W
+
+
+@functools.lru_cache(maxsize=None)
+def _f(rec=None):
+    """The 70 frequencies: multiples of 2^-6, or with rec full-mantissa doubles in (0, 3] (every product f t inexact)."""
+    if not rec:
+        return _irregular(NF)
+    f = wide_freqs(np.random.default_rng(770), NF)
+    f.setflags(write=False)
+    return f
 
 
 @functools.lru_cache(maxsize=None)
@@ -56,32 +70,32 @@ def _indices(N, nb, seed=SEED, row0=0):
 
 
 @functools.lru_cache(maxsize=None)
-def _ref(N, tone, weighted, fit_mean, center, normalization, removed, nb=B, seed=SEED):
+def _ref(N, tone, weighted, fit_mean, center, normalization, removed, nb=B, seed=SEED, rec=None):
     """The reference on the nb resampled signals (N x nb); removed: the device's means as a tuple, or None (the reference's own)."""
-    t, y, W = _record(N, tone)
+    t, y, W = _record(N, tone, rec)
     ys = y[_indices(N, nb, seed)].T
-    return lomb_ref(ys, t, _irregular(NF), W=W if weighted else None, fit_mean=fit_mean, center_data=center, normalization=normalization,
+    return lomb_ref(ys, t, _f(rec), W=W if weighted else None, fit_mean=fit_mean, center_data=center, normalization=normalization,
                     removed=None if removed is None else np.array(removed))
 
 
-def _boot(L, N, tone=False, weighted=True, nb=B, **kw):
-    t, y, W = _record(N, tone)
+def _boot(L, N, tone=False, weighted=True, nb=B, rec=None, **kw):
+    t, y, W = _record(N, tone, rec)
     kw.setdefault("seed", SEED)
-    kw.setdefault("f", _irregular(NF))
+    kw.setdefault("f", _f(rec))
     return L.lombscargle_bootstrap(y, t, W=W if weighted else None, B=nb, return_argmax=True, return_means=True, return_power=True, **kw)
 
 
-def _check_numerics(L, N, weighted, fit_mean, center, normalization, want_ts=16):
-    t, y, W = _record(N)
-    M, am, means, P = _boot(L, N, weighted=weighted, fit_mean=fit_mean, center_data=center, normalization=normalization)
+def _check_numerics(L, N, weighted, fit_mean, center, normalization, want_ts=16, rec=None):
+    t, y, W = _record(N, rec=rec)
+    M, am, means, P = _boot(L, N, weighted=weighted, rec=rec, fit_mean=fit_mean, center_data=center, normalization=normalization)
     tm = L.lombscargle_bootstrap_last_timing()
     assert tm["resamples"] == B and tm["ts"] == want_ts and tm["slab"] == SLAB and tm["slabs"] == math.ceil(N / SLAB) and tm["degenerate"] == 0
     assert P.shape == (NF, B) and M.shape == am.shape == means.shape == (B,)
-    r = _ref(N, False, weighted, fit_mean, center, normalization, tuple(means) if center else None)
+    r = _ref(N, False, weighted, fit_mean, center, normalization, tuple(means) if center else None, rec=rec)
     deg = r["degenerate"]
     assert not deg.any() and np.all(r["D"] >= 0.01), "the inputs are to stay clear of the degenerate threshold"
     ys = y[_indices(N, B)].T
-    bs = _sum_bounds(r, t, ys, W if weighted else np.ones(N), False)
+    bs = _sum_bounds(r, t, ys, W if weighted else np.ones(N), False, trig=6 if rec else 4)
     err = np.abs(means.astype(LD) - r["mean"])
     print("mean: worst error / bound:", _ratio(err, bs["mean"]))
     assert np.all(err <= bs["mean"])
@@ -104,6 +118,16 @@ def test_every_column_is_the_estimate_of_its_resample(L, monkeypatch, N, fit_mea
     monkeypatch.delenv("LPVS_LOMB_BOOT_TS", raising=False)
     monkeypatch.delenv("LPVS_LOMB_BOOT_MB", raising=False)
     _check_numerics(L, N, weighted, fit_mean, center, normalization)
+
+
+@pytest.mark.parametrize("rec", ["lattice", "full"])
+def test_every_column_of_a_record_with_inexact_products(L, monkeypatch, rec):
+    """t over [0, 2^20], f full-mantissa doubles in (0, 3]: f t reaches 3e6 turns and the low word of lomb_sincos in lomb_boot_kernel
+    decides; three slabs, every column against the reference on its resampled indices (6 u of trigonometry per term in place of 4 u,
+    tests/test_gpu_lomb.py)."""
+    monkeypatch.delenv("LPVS_LOMB_BOOT_TS", raising=False)
+    monkeypatch.delenv("LPVS_LOMB_BOOT_MB", raising=False)
+    _check_numerics(L, N_LONG, True, True, True, "standard", rec=rec)
 
 
 # ---- 2. the reduction, exact -----------------------------------------------------------------------------------------------------------------

@@ -6,6 +6,8 @@ partial; N = 2501: three slabs, the last partial), weights in [0.5, 2], 70 disti
 tiles, the second partial), ns in {1, 3, 5}.  Every product f t is exact in double.  The grid starts at 4/64 because at f = 1/64 the six-term
 design is nearly singular over 40 units (smallest pivot 0.008); on these inputs the reference's smallest pivot is >= 0.3 for every K <= 6.
 Asserted: pivots >= 0.01 at every frequency the reference does not call degenerate, <= 2^-45 where it does.
+One case more has INEXACT products (tests/_lomb_ref.py): t over [0, 2^20], on the 2^-10 lattice and as full-mantissa doubles, f
+full-mantissa doubles in (0, 3]; f t reaches 3e6 turns and the low word of lomb_sincos decides.
 
 BOUNDS (u = 2^-53); nothing is fitted to what the device returns, every term comes from the reference.
   sums:   |sum - ref| <= (N + 16) u sum|terms| + e_m sum|weights| for a row of harmonic m, e_m = m 4 sqrt(2) u + 3 (m - 1) u: z_1 carries
@@ -24,7 +26,7 @@ import functools
 import numpy as np
 import pytest
 
-from _lomb_ref import LD, lomb_ref
+from _lomb_ref import LD, late_times, lomb_ref, wide_freqs
 from _lomb_terms_ref import ldl_solve, lomb_terms_ref
 from test_lomb_terms_ref_host import planted
 
@@ -76,12 +78,13 @@ def _call(L, y, t, f, K, W, fit_mean=True, center=True, normalization="standard"
 
 
 # ---- bounds --------------------------------------------------------------------------------------------------------------------------------
-def _sum_bounds(r, t, y, W):
+def _sum_bounds(r, t, y, W, trig=4):
+    """trig: the ulps of cos and of sin of the first harmonic, 4 where every product f t is exact, 6 where it is not."""
     N, K = len(t), r["K"]
     w = (W / W.sum()).astype(LD)
     yc = y.reshape(N, -1).astype(LD) - r["removed"][None, :]
     swy, swyy = (w[:, None] * np.abs(yc)).sum(axis=0), (w[:, None] * yc * yc).sum(axis=0)
-    e = np.array([m * 4 * np.sqrt(2.0) * U + 3 * (m - 1) * U for m in range(1, 2 * K + 1)])
+    e = np.array([m * trig * np.sqrt(2.0) * U + 3 * (m - 1) * U for m in range(1, 2 * K + 1)])
     b = {"C": (N + 16) * U * r["abs_C"] + e[:, None], "S": (N + 16) * U * r["abs_S"] + e[:, None]}            # sum|weights| = 1
     for k in ("YC", "YS"):
         b[k] = (N + 16) * U * r["abs_" + k] + e[None, :K, None] * swy[:, None, None]
@@ -142,7 +145,7 @@ def _ratio(name, err, bound):
     return v
 
 
-def _check(L, y, t, W, f, K, fit_mean=True, center=True, normalization="standard"):
+def _check(L, y, t, W, f, K, fit_mean=True, center=True, normalization="standard", trig=4):
     N = len(t)
     ns = 1 if y.ndim == 1 else y.shape[1]
     P, (a, b, c), sums, tm = _call(L, y, t, f, K, W, fit_mean, center, normalization)
@@ -151,7 +154,7 @@ def _check(L, y, t, W, f, K, fit_mean=True, center=True, normalization="standard
     assert np.all(r["worst_pivot"][~deg] >= 0.01) and np.all(r["worst_pivot"][deg] <= 2.0 ** -45), "the inputs are to stay clear of the degenerate threshold"
     assert tm["nterms"] == K and tm["degenerate"] == int(deg.sum())
     assert sums["C"].shape == sums["S"].shape == (2 * K, len(f)) and sums["YC"].shape == sums["YS"].shape == (ns, K, len(f))
-    bs = _sum_bounds(r, t, y, W)
+    bs = _sum_bounds(r, t, y, W, trig)
     for k in ("mean", "C", "S", "YC", "YS", "Y", "YY"):
         err = np.abs(sums[k].astype(LD) - r[k])
         print(f"K = {K} {k}: worst error / bound {_ratio(k, err, bs[k]):.3f}")
@@ -191,6 +194,29 @@ def test_three_slabs_the_last_partial(L, K):
     t, y, W = _record(2501, 3)
     tm, _, _, _ = _check(L, y, t, W, _freqs(), K)
     assert (tm["ts"], tm["accumulators"], tm["slabs"]) == (TS[K], 4 * K + 2 * K * TS[K], 3)
+
+
+@functools.lru_cache(maxsize=None)
+def _late(rec, N=2501, ns=3, Nf=70):
+    """tests/_lomb_ref.py: times over [0, 2^20] (rec = "lattice": multiples of 2^-10; "full": full-mantissa doubles) and full-mantissa
+    frequencies in (0, 3]: every product f t is inexact, up to 3e6 turns."""
+    rng = np.random.default_rng(7000 + N + ns + (rec == "full"))
+    t = late_times(rng, N, rec == "lattice")
+    f = wide_freqs(rng, Nf)
+    y = np.cos(2 * np.pi * f[40] * t[:, None] + np.arange(ns)[None, :]) * (1.0 + np.arange(ns))[None, :] + 0.5 * rng.standard_normal((N, ns)) + 0.75
+    W = rng.uniform(0.5, 2.0, N)
+    for a in (t, y, W, f):
+        a.setflags(write=False)
+    return t, y, W, f
+
+
+@pytest.mark.parametrize("rec", ["lattice", "full"])
+def test_three_harmonics_of_inexact_products(L, rec):
+    """The low word e of lomb_sincos in lomb_terms_kernel: 2e-10 turns at f t = 3e6, times m in the m-th harmonic.  6 u of trigonometry in
+    place of 4 u: r = (p - rint(p)) + e rounds once, |r| <= 1/2, a phase of at most 2 pi 2^-55 <= 1.6 u."""
+    t, y, W, f = _late(rec)
+    tm, _, _, _ = _check(L, y, t, W, f, 3, trig=6)
+    assert (tm["ts"], tm["accumulators"], tm["slabs"], tm["degenerate"]) == (TS[3], 4 * 3 + 2 * 3 * TS[3], 3, 0)
 
 
 @pytest.mark.parametrize("normalization", ["standard", "psd"])

@@ -35,6 +35,9 @@ with N := n -- (n + 16) u sum|terms| plus the trigonometry allowance, passed thr
       bounds of 1e-12.)  Without fit_mean the model has no constant and dm' is real:
           dYC += dm sum w|cos|,  dYS += dm sum w|sin|,  dY += dm,  dYY += 2 dm sum w|yc| + dm^2,  dc += dm.
 
+INEXACT PRODUCTS.  One case repeats the explicit windows on a record over [0, 2^20] (still multiples of 2^-10) with full-mantissa
+frequencies in (0, 3] (tests/_lomb_ref.py): f t reaches 3e6 turns, and the trigonometry allowance is 6 u (tests/test_gpu_lomb.py).
+
 WINDOWS of 1 - 3 samples are not compared (their D is far below 0.01 where it is not 0): all their values are finite, and their standard
 power lies in [-b, 1 + b] wherever the reference's D >= 0.01, with b the same first-order bound.
 
@@ -45,7 +48,7 @@ import functools
 import numpy as np
 import pytest
 
-from _lomb_ref import LD, lomb_ref
+from _lomb_ref import LD, late_times, lomb_ref, wide_freqs
 from test_gpu_lomb import U, _epilogue_bounds, _ratio, _sum_bounds
 
 pytestmark = pytest.mark.gpu
@@ -55,9 +58,10 @@ PI = np.arccos(LD(-1))
 
 # ---- inputs ------------------------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
-def _record(offset=0.0):
+def _record(offset=0.0, late=False):
+    """late: the same count over [0, 2^20] (tests/_lomb_ref.py), still multiples of 2^-10."""
     rng = np.random.default_rng(6000)
-    t = np.sort(rng.integers(0, 12000 * 1024, N)) / 1024.0
+    t = late_times(rng, N) if late else np.sort(rng.integers(0, 12000 * 1024, N)) / 1024.0
     y = np.cos(2 * np.pi * 1.25 * t[:, None] + np.arange(NS)[None, :]) * (1.0 + np.arange(NS))[None, :] + 0.5 * rng.standard_normal((N, NS)) + 0.75 + offset
     W = rng.uniform(0.5, 2.0, N)
     for a in (t, y, W):
@@ -66,8 +70,13 @@ def _record(offset=0.0):
 
 
 @functools.lru_cache(maxsize=None)
-def _freqs(uniform=False):
+def _freqs(uniform=False, late=False):
+    """late: full-mantissa doubles in (0, 3], so that every product f t is inexact."""
     rng = np.random.default_rng(70)
+    if late:
+        f = wide_freqs(rng, NF)
+        f.setflags(write=False)
+        return f
     j = rng.choice(np.arange(32, 1537) if uniform else np.arange(16, 193), NF, replace=False)   # [1/2, 24] or [1/4, 3] in steps of 2^-6
     f = np.sort(j) / 64.0
     f.setflags(write=False)
@@ -75,10 +84,10 @@ def _freqs(uniform=False):
 
 
 @functools.lru_cache(maxsize=None)
-def _windows():
+def _windows(late=False):
     """Case 1: overlapping, out of order, one ending at N; the window of two samples has its samples ON the edges of its interval (empty
     under the Hann taper), the others' intervals reach 1/2 before their first and 1/4 beyond their last sample."""
-    t = _record()[0]
+    t = _record(late=late)[0]
     starts = np.array([123, 5990, 1500, 100, 2900, 2000, 3000, 5743, 0], dtype=np.int64)
     counts = np.array([3 * SLAB + 5, 2, SLAB, 0, 255, SLAB + 1, 37, 257, 256], dtype=np.int64)
     assert sorted(counts) == [0, 2, 37, 255, 256, 257, SLAB, SLAB + 1, 3 * SLAB + 5] and np.all(starts + counts <= N) and starts[7] + counts[7] == N
@@ -98,8 +107,9 @@ def _taper(kind, t, lo, hi):
     return np.where((u >= 0) & (u <= 1), np.sin(PI * np.minimum(u, 1 - u)) ** 2, LD(0))
 
 
-def _window_ref(y, t, W, f, start, count, lo, hi, kind, fit_mean, center, normalization):
-    """(reference, bounds of power / a / b / c) of one window, all NS signals; None for an empty window."""
+def _window_ref(y, t, W, f, start, count, lo, hi, kind, fit_mean, center, normalization, trig=4):
+    """(reference, bounds of power / a / b / c) of one window, all NS signals; None for an empty window.  trig: tests/test_gpu_lomb.py's
+    ulps of trigonometry per term, 6 where the products f t are inexact."""
     sl = slice(int(start), int(start + count))
     ys, ts, Ws = y[sl], t[sl], (np.ones(count) if W is None else W[sl]).astype(LD)
     g = _taper(kind, ts, lo, hi)
@@ -107,7 +117,7 @@ def _window_ref(y, t, W, f, start, count, lo, hi, kind, fit_mean, center, normal
     if count == 0 or not Wg.sum() > 0:
         return None
     r = lomb_ref(ys, ts, f, W=Wg, fit_mean=fit_mean, center_data=center, normalization=normalization)
-    b = _sum_bounds(r, ts, ys, Wg, False)
+    b = _sum_bounds(r, ts, ys, Wg, False, trig=trig)
     n = int(count)
     T = 0.0 if kind == "rect" else 5 * U
     Sg = (Ws * g).sum()
@@ -134,9 +144,9 @@ def _window_ref(y, t, W, f, start, count, lo, hi, kind, fit_mean, center, normal
 
 
 @functools.lru_cache(maxsize=None)
-def _case1_refs(kind, fit_mean, center, normalization, offset=0.0):
-    t, y, W = _record(offset)
-    return [_window_ref(y, t, W, _freqs(), s, c, a, b, kind, fit_mean, center, normalization) for s, c, a, b in zip(*_windows())]
+def _case1_refs(kind, fit_mean, center, normalization, offset=0.0, late=False):
+    t, y, W = _record(offset, late)
+    return [_window_ref(y, t, W, _freqs(late=late), s, c, a, b, kind, fit_mean, center, normalization, 6 if late else 4) for s, c, a, b in zip(*_windows(late))]
 
 
 def _compare(got, refs, counts, ns, standard):
@@ -165,15 +175,15 @@ def _compare(got, refs, counts, ns, standard):
     print("worst error / bound:", worst)
 
 
-def _run(L, ns, kind, fit_mean, center, normalization, offset=0.0):
-    t, y, W = _record(offset)
-    starts, counts, lo, hi = _windows()
-    S, (a, b, c) = L.lombscargle_spectrogram(y[:, :ns] if ns > 1 else y[:, 0], t, _freqs(), windows=(starts, counts, lo, hi),
+def _run(L, ns, kind, fit_mean, center, normalization, offset=0.0, late=False):
+    t, y, W = _record(offset, late)
+    starts, counts, lo, hi = _windows(late)
+    S, (a, b, c) = L.lombscargle_spectrogram(y[:, :ns] if ns > 1 else y[:, 0], t, _freqs(late=late), windows=(starts, counts, lo, hi),
                                              window=L.hanning if kind == "hanning" else L.rect, W=W, fit_mean=fit_mean, center_data=center,
                                              normalization=normalization, coef=True)
-    assert S.power.shape == ((NF, 9) if ns == 1 else (NF, 9, ns)) and a.shape == S.power.shape and np.array_equal(S.freq, _freqs())
+    assert S.power.shape == ((NF, 9) if ns == 1 else (NF, 9, ns)) and a.shape == S.power.shape and np.array_equal(S.freq, _freqs(late=late))
     assert np.array_equal(S.time, (lo + hi) / 2) and np.array_equal(S.counts, counts)
-    refs = _case1_refs(kind, fit_mean, center, normalization, offset)
+    refs = _case1_refs(kind, fit_mean, center, normalization, offset, late)
     assert np.array_equal(S.empty, [rb is None for rb in refs])
     tm = L.lombscargle_windows_last_timing()
     assert (tm["windows"], tm["empty"], tm["slab"]) == (9, int(S.empty.sum()), SLAB)
@@ -197,6 +207,14 @@ def test_explicit_windows_power_and_coefficients(L, ns, kind, fit_mean, center, 
     signals one and two blocks of four.  Under the Hann taper the window of two samples (both on its edges) is empty."""
     S = _run(L, ns, kind, fit_mean, center, normalization)
     assert list(np.flatnonzero(S.empty)) == ([1, 3] if kind == "hanning" else [3])
+
+
+def test_explicit_windows_late_in_a_long_record(L):
+    """The same nine windows on a record over [0, 2^20] with full-mantissa frequencies in (0, 3]: every product f t is inexact, up to 3e6
+    turns, and the low word of lomb_sincos in the windowed kernels decides (6 u of trigonometry per term in place of 4 u,
+    tests/test_gpu_lomb.py); t, lo and hi stay multiples of 2^-10, so the taper's argument is formed as before."""
+    S = _run(L, 3, "hanning", True, True, "standard", late=True)
+    assert list(np.flatnonzero(S.empty)) == [1, 3]
 
 
 # ---- 2  large offset ---------------------------------------------------------------------------------------------------------------------

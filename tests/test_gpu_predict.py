@@ -4,7 +4,8 @@ proves both on the CPU).  No sample is exempt and no maximum over the record is 
 
     1  direct path on grids off any progression: Fourier (with / without the zero frequency), LPV (normalize on / off, coulomb)
     2  type-2 path: the structured cases' shapes, the 256 grid at its limit with default_freqs (a = 0, zero frequency), a != 0 (the rotation),
-       samples planted where the taps wrap, planted residuals (the twin)
+       samples planted where the taps wrap, planted residuals (the twin); and at |w x| = 3e6 and 2^30 rad against the phases of the real
+       products, where the low words of nu_phase_turns decide (the direct path at 2^30 rad against its own reference)
     3  the path argument
     4  columns: a multi-column call equals the single-column calls bit for bit
     5  residual, sums, fva
@@ -17,6 +18,8 @@ import numpy as np
 import pytest
 
 import _eval_ref as E
+import _gram_ref as R
+import _phase_ref as PR
 
 pytestmark = pytest.mark.gpu
 LD = np.longdouble
@@ -181,6 +184,54 @@ def test_nufft_fourier(L, kind):
     assert tm["path"] == "nufft" and tm["nf"] == 256
     r = _worst(got, c["yh"], c["tol"] * c["S"])
     print(f"{kind}: twin={tm['twin']} worst |got - ref| / (struct_tol S_m) = {r:.4f}")
+    assert r <= 1.0
+
+
+# ---- 2b  type-2 path where the low words of its phases decide -------------------------------------------------------------------------------
+# The cases above keep |w x| <= 1.1e3 rad and carry struct_tol's term 4.5e-16 max|w| max|x|.  Here |w x| reaches 3e6 rad (natural rounding
+# residuals of the grid; planted ones at the admission limit) and 2^30 rad (a dyadic grid), the reference forms the phases of the real products
+# (tests/_phase_ref.py: evaluate_exact) and the bound is (1e-12 + q) S_m per sample: 1e-12 the stated tolerance of the transform, q <= 1e-13
+# the squares the kernel headers drop (_phase_ref.second_order).  Nothing grows with |w||x|.  The inputs are built like the structured Gram's
+# (tests/_gram_ref.py: PHASE_PREDICT_CASES, which says why the grids start at a = 2.5 D).
+@functools.lru_cache(maxsize=None)
+def _lpv_large_phase(cid):
+    from oracle import oracle
+    case = R.PHASE_LPV[cid]
+    Nf, Nv = case[1], case[2]
+    Y, X, V, w = R.phase_lpv_inputs(case)
+    P = _coefs(np.random.default_rng(len(cid)), Nf * Nv, 2)
+    vc, gamma = oracle.basis_centers(V, Nv, False)
+    K = E.activations_ld(V, vc, gamma, True, False)
+    q = PR.second_order(w, X)
+    assert q <= 1e-13
+    yh, S = PR.evaluate_exact(P, w, X, K)
+    return dict(Nf=Nf, Nv=Nv, M=len(X), X=X, V=V, w=w, P=P, K=K, Y=Y, yh=yh, S=S, tol=1e-12 + q)
+
+
+@pytest.mark.parametrize("cid", [c[0] for c in R.PHASE_PREDICT_CASES])
+def test_nufft_lpv_against_exact_phases(L, cid):
+    """eval_grid_kernel, eval_interp_kernel (nu_phase_turns of D x) and the rotation e^{i a x} (nu_phase_turns of a x) at |w x| = 3e6 rad
+    and 2^30 rad."""
+    c = _lpv_large_phase(cid)
+    se = _se(L, c["Y"], c["X"], c["V"], c["w"], c["Nv"], True, False, c["P"])
+    got = L.predict(se)
+    tm = L.eval_last_timing()
+    assert tm["path"] == "nufft" and tm["nf"] == 256 and tm["twin"] == (cid != "predict-24x3-beyond")
+    r = _worst(got, c["yh"], c["tol"] * c["S"])
+    print(f"{cid}: max|w x| = {np.abs(c['w']).max() * np.abs(c['X']).max():.3g} rad, twin={tm['twin']}, worst |got - ref| / ((1e-12 + q) S_m) = {r:.4f}")
+    assert r <= 1.0
+
+
+def test_direct_lpv_at_two_to_the_thirty_radians(L):
+    """The direct path rounds the phase as the reference implementation does and keeps its rounded-phase reference and its bound: the
+    device's sincos at arguments up to 2^30."""
+    c = _lpv_large_phase("predict-24x3-beyond")
+    se = _se(L, c["Y"], c["X"], c["V"], c["w"], c["Nv"], True, False, c["P"])
+    got = L.predict(se, path="direct")
+    assert L.eval_last_timing()["path"] == "direct"
+    yh, S = E.evaluate_ld(c["P"], c["w"], c["X"], c["K"])
+    r = _worst(got, yh, E.direct_bound(c["Nf"], c["Nv"], S))
+    print(f"direct at 2^30 rad: worst |got - ref| / bound = {r:.4f}")
     assert r <= 1.0
 
 

@@ -7,6 +7,8 @@ units.  Cases: NARROW (1500 samples, c = 1/(8 pi^2), wmin = 1e-9: cells from emp
 c = 1/(512 pi^2): cells up to the whole record, across the stage of 256 and the slab of 1024), WHOLE (1500 samples, c = 1/(128 pi^2),
 wmin = 0: every cell is the record) and records of 255, 256, 257, 1024 and 1025 samples with wmin = 0 (the block and slab edges).
 
+One case more, LATE, has inexact products: the same lattice over [0, 2^20] and full-mantissa frequencies in (0, 3] (tests/_lomb_ref.py).
+
 BOUNDS (u = 2^-53, n = the cell's samples).  The sums and the epilogue are held to the bounds of tests/test_gpu_lomb.py with N := n
 (its helpers are imported as they are): (n + 16) u sum|terms| plus the trigonometry allowance, to first order through the epilogue by the
 reference's D.  (The device adds per sample lane, (0 + 1) + (2 + 3), then per slab in a pairwise tree, and divides by sum W g at the end:
@@ -33,7 +35,7 @@ import functools
 import numpy as np
 import pytest
 
-from _lomb_ref import LD
+from _lomb_ref import LATE_SPAN, LD, wide_freqs
 from _wwz_ref import decay, radius, reach, wwz_cell_ref
 from test_gpu_lomb import U, _epilogue_bounds, _ratio, _sum_bounds
 
@@ -44,6 +46,10 @@ C_FOSTER = 1.0 / (8.0 * np.pi ** 2)
 CASES = {"narrow": (1500, C_FOSTER, 1e-9, SPAN), "wide": (3000, 1.0 / (512.0 * np.pi ** 2), 1e-9, SPAN), "whole": (1500, 1.0 / (128.0 * np.pi ** 2), 0.0, SPAN)}
 for _n in (255, 256, 257, 1024, 1025):
     CASES[f"edge{_n}"] = (_n, 1.0 / (128.0 * np.pi ** 2), 0.0, 64 if _n < 1000 else 256)       # (four samples per unit, as the others)
+# LATE: every product f t inexact (tests/_lomb_ref.py).  t and tau stay multiples of 2^-10 (t - tau is exact) but span [0, 2^20], f are
+# full-mantissa doubles in (0, 3]: f t reaches 3e6 turns.  c = 1 / (2^40 pi^2) makes the Gaussian a tenth of the record wide at f = 3 and
+# flat at the low frequencies; wmin = 0, so every cell is the record (two slabs).  6 u of trigonometry per term (tests/test_gpu_lomb.py).
+CASES["late"] = (1500, 1.0 / (2.0 ** 40 * np.pi ** 2), 0.0, LATE_SPAN)
 KEYS = ("power", "amplitude", "wwz", "a", "b", "c", "neff")
 
 
@@ -60,7 +66,11 @@ def _record(N, offset=0.0, span=SPAN):
 
 
 @functools.lru_cache(maxsize=None)
-def _freqs():
+def _freqs(case=None):
+    if case == "late":
+        f = wide_freqs(np.random.default_rng(7070), NF)
+        f.setflags(write=False)
+        return f
     f = np.sort(np.random.default_rng(70).choice(np.arange(16, 193), NF, replace=False)) / 64.0      # [1/4, 3] in steps of 2^-6
     f.setflags(write=False)
     return f
@@ -81,10 +91,10 @@ def _record_mean(y, W):
 
 
 # ---- reference and bounds ----------------------------------------------------------------------------------------------------------------
-def _cell_bounds(ref, ys, ts):
+def _cell_bounds(ref, ys, ts, trig=4):
     """Bounds of every compared quantity of one cell, all NS signals, from the reference alone."""
     r, n = ref["fit"], ref["count"]
-    b = _sum_bounds(r, ts, ys, ref["Wg"], False)
+    b = _sum_bounds(r, ts, ys, ref["Wg"], False, trig=trig)
     Wgl = ref["Wgl"]
     w = Wgl / Wgl.sum()
     T = (2 * ref["x"] + 4) * U
@@ -120,7 +130,7 @@ def _refs(case, with_W, center, offset=0.0):
     N, c, wmin, span = CASES[case]
     t, y, W = _record(N, offset, span)
     W = W if with_W else None
-    f, tau = _freqs(), _taus(span)
+    f, tau = _freqs(case), _taus(span)
     a, r = decay(c, f), radius(f, c, wmin)
     removed = _record_mean(y, W) if center else None
     cells, counts = [], np.zeros((NF, NTAU), dtype=np.int64)
@@ -133,7 +143,7 @@ def _refs(case, with_W, center, offset=0.0):
                 row.append(None)
                 continue
             sl = slice(ref["start"], ref["start"] + ref["count"])
-            row.append((ref, _cell_bounds(ref, y[sl], t[sl])))
+            row.append((ref, _cell_bounds(ref, y[sl], t[sl], 6 if case == "late" else 4)))
         cells.append(row)
     return cells, counts
 
@@ -179,7 +189,7 @@ def _call(L, case, ns, with_W, center, offset=0.0, tau=None, signals=None):
     N, c, wmin, span = CASES[case]
     t, y, W = _record(N, offset, span)
     ys = y[:, signals] if signals is not None else (y[:, :ns] if ns > 1 else y[:, 0])
-    R, (a, b, cc) = L.wwz(ys, t, _freqs(), tau=_taus(span) if tau is None else tau, c=c, wmin=wmin, W=W if with_W else None, center_data=center, coef=True)
+    R, (a, b, cc) = L.wwz(ys, t, _freqs(case), tau=_taus(span) if tau is None else tau, c=c, wmin=wmin, W=W if with_W else None, center_data=center, coef=True)
     return R, {"power": R.power, "amplitude": R.amplitude, "wwz": R.wwz, "a": a, "b": b, "c": cc, "neff": R.neff}
 
 
@@ -188,7 +198,7 @@ def _check(L, case, ns, with_W, center, offset=0.0):
     cells, counts = _refs(case, with_W, center, offset)
     shape = (NF, NTAU) if ns == 1 else (NF, NTAU, ns)
     assert R.power.shape == shape and R.wwz.shape == shape and R.amplitude.shape == shape and R.neff.shape == (NF, NTAU)
-    assert np.array_equal(R.freq, _freqs()) and np.array_equal(R.time, _taus(CASES[case][3]))
+    assert np.array_equal(R.freq, _freqs(case)) and np.array_equal(R.time, _taus(CASES[case][3]))
     assert np.array_equal(R.counts, counts), "the samples in reach are numpy's searchsorted on the stated edges"
     assert np.array_equal(R.empty, [[cells[k][j] is None for j in range(NTAU)] for k in range(NF)])
     return R, got, _compare(got, cells, ns)
@@ -204,6 +214,12 @@ def _check(L, case, ns, with_W, center, offset=0.0):
 def test_every_cell_against_the_reference(L, case, ns, with_W, center):
     """1, 3 and 5 signals are the kernels <TT = 4, ts = 1> and <2, 4> with one and two blocks of four; 70 frequencies two tiles."""
     _check(L, case, ns, with_W, center)
+
+
+def test_every_cell_late_in_a_long_record(L):
+    """Every product f t inexact, up to 3e6 turns: the low word of lomb_sincos in the wwz kernels decides."""
+    R, got, worst = _check(L, "late", 3, True, True)
+    assert not R.empty.any() and R.counts.min() == 1500
 
 
 # ---- 2  ranges, empty cells, Neff <= 3, the timing record ------------------------------------------------------------------------------------

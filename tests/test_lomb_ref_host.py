@@ -4,7 +4,8 @@
     2  a pure sinusoid on a frequency of the grid: a, b, c come back and the standard power is 1 (fit_mean)
     3  the standard power does not change under y -> alpha y + beta (fit_mean)
     4  the degenerate rule at f = 0 and at the Nyquist alias of a uniform record
-    5  the phases: exact products, so a shift of t by whole periods of f changes nothing"""
+    5  the phases: exact products, so a shift of t by whole periods of f changes nothing
+    6  the phases of INEXACT products at 3e6 turns (the GPU tests' late records) against rational arithmetic"""
 import numpy as np
 import pytest
 
@@ -78,3 +79,26 @@ def test_phases_are_those_of_the_exact_product():
             q = Fraction(float(f[i])) * Fraction(float(t[j]))
             d = Fraction(float(u[i, j])) + Fraction(float(u[i, j] - LD(float(u[i, j])))) - q    # a whole number of turns, up to 2^-64
             assert abs(d - round(d)) < Fraction(1, 2 ** 62)
+
+
+def test_phases_of_inexact_products_at_three_million_turns():
+    """The GPU tests' second family of inputs (late_times, wide_freqs): every product f t is inexact and reaches 3e6 turns.  exact_turns
+    against rational arithmetic: hi + lo of the long double minus f t is a whole number to 2^-62, for lattice and full-mantissa times."""
+    from fractions import Fraction
+    from _lomb_ref import late_times, wide_freqs
+    rng = np.random.default_rng(11)
+    f = wide_freqs(rng, 12)
+    for lattice in (True, False):
+        t = late_times(rng, 25, lattice)
+        t[-1] = 2.0 ** 20 - 2.0 ** -10                                   # the far end of the record
+        p = f[:, None] * t[None, :]
+        assert np.all(p != np.rint(p)) and p.max() > 2.0e6
+        inexact = sum(Fraction(float(a)) * Fraction(float(b)) != Fraction(float(a * b)) for a in f for b in t)
+        assert inexact >= 0.95 * f.size * t.size                         # (a product that happens to be exact is no harm)
+        u = exact_turns(f, t)
+        assert u.dtype == LD and np.all(np.abs(u) <= 0.5 + 2.0 ** -30)
+        for i in range(len(f)):
+            for j in range(len(t)):
+                q = Fraction(float(f[i])) * Fraction(float(t[j]))
+                d = Fraction(float(u[i, j])) + Fraction(float(u[i, j] - LD(float(u[i, j])))) - q
+                assert abs(d - round(d)) < Fraction(1, 2 ** 62), (i, j)
