@@ -236,6 +236,10 @@ int32_t lpvs_problem_get_rhs_f64(lpvs_problem *h, double *b_out);
 /* (G + shift*I)^-1 (n x n, symmetric) -- e.g. the parameter covariance of ls_spectral_lpv up to the factor var(e),
  * src/lsfft.jl:252-254.  Leaves the handle's factorisation cached for that shift. */
 int32_t lpvs_problem_get_inverse_f64(lpvs_problem *h, double shift, double *Minv_out);
+/* The same after one round of iterative refinement against G + shift*I (column q: x += M (e_q - (G + shift*I) x)): an inverse that is itself the
+ * result -- the covariance above -- at the accuracy of a pivoted factorisation whatever the number of 128-blocks the sweep eliminates by;
+ * symmetric up to rounding, column q in Minv_out[q*n .. q*n + n).  Four n x n work arrays on the device. */
+int32_t lpvs_problem_get_inverse_refined_f64(lpvs_problem *h, double shift, double *Minv_out);
 
 /* ---- dense (ridge) solve from the same Gram:  (G + ridge*I) x = b ---------------------
  * ls_spectral weighted form (src/lsfft.jl:77, ridge = lam), fourier_solve / real_complex_bs in
@@ -248,6 +252,8 @@ int32_t lpvs_problem_solve_ridge_f64(lpvs_problem *h, double ridge, double *x_ou
  *   N >= Nreg (tall):  x = (A'A + lam^2 I)^-1 A'y          (primal normal equations)
  *   N <  Nreg (fat):   x = A' (A A' + lam^2 I)^-1 y        (dual form; e.g. default_freqs of an even-length t
  *                                                           has Nreg = N+1 and a vanishing Nyquist sine column)
+ * Either solve is the explicit inverse refined twice against its own system; LPVS_ENUMERIC when that system is singular to working
+ * precision (a non-positive pivot, or a relative residual above 1e-9 after the refinement): the bindings then solve [A; lam I] by QR on the host.
  * re/im: Nf entries, fourier2complex of x. */
 int32_t lpvs_ls_spectral_f64(const double *y, const double *t, int64_t N, const double *f, int64_t Nf, double lam,
                              int32_t device, double *re_out, double *im_out);

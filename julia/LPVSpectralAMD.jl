@@ -268,6 +268,11 @@ function inverse(p::Problem, shift)
     GC.@preserve M check(@ccall LIB.lpvs_problem_get_inverse_f64(p.h::Ptr{Cvoid}, Float64(shift)::Float64, M::Ptr{Float64})::Int32)
     M
 end
+function inverse_refined(p::Problem, shift)                 # one round of iterative refinement on the device, symmetrised: an inverse that is the result
+    M = zeros(p.n, p.n)
+    GC.@preserve M check(@ccall LIB.lpvs_problem_get_inverse_refined_f64(p.h::Ptr{Cvoid}, Float64(shift)::Float64, M::Ptr{Float64})::Int32)
+    (M .+ M') ./ 2
+end
 function iterates(p::Problem)
     x, z, u = zeros(p.n, p.ns), zeros(p.n, p.ns), zeros(p.n, p.ns)
     GC.@preserve x z u check(@ccall LIB.lpvs_admm_get_f64(p.h::Ptr{Cvoid}, x::Ptr{Float64}, z::Ptr{Float64}, u::Ptr{Float64})::Int32)
@@ -351,9 +356,18 @@ function ls_spectral(y, t, f=default_freqs(t); λ=1e-10, verbose=false, device=0
     re, im_ = zeros(length(fv)), zeros(length(fv))
     # [A; λI] \ [y; 0] from the device Gram in its better-conditioned form (primal for tall, dual for fat systems such as the
     # default grid of an even-length record, whose Gram is singular): lpvs_ls_spectral_f64, NOT a ridge solve with λ²
-    GC.@preserve yv tv fv re im_ check(@ccall LIB.lpvs_ls_spectral_f64(yv::Ptr{Float64}, tv::Ptr{Float64}, length(yv)::Int64,
-        fv::Ptr{Float64}, length(fv)::Int64, Float64(λ)::Float64, Int32(device)::Int32, re::Ptr{Float64}, im_::Ptr{Float64})::Int32)
-    if verbose                                                                        # :65
+    try
+        GC.@preserve yv tv fv re im_ check(@ccall LIB.lpvs_ls_spectral_f64(yv::Ptr{Float64}, tv::Ptr{Float64}, length(yv)::Int64,
+            fv::Ptr{Float64}, length(fv)::Int64, Float64(λ)::Float64, Int32(device)::Int32, re::Ptr{Float64}, im_::Ptr{Float64})::Int32)
+    catch e
+        e isa NumericError || rethrow(e)                  # normal equations singular to working precision: the reference's QR route on the host
+        A, zf = get_fourier_regressor(tv, fv)
+        x = [A; λ * I] \ [yv; zeros(size(A, 2))]
+        nf = length(fv)
+        re .= x[1:nf]
+        im_ .= zf === nothing ? x[nf+1:end] : [0.0; x[nf+1:end]]   # fourier2complex, src/utilities.jl:62-73
+    end
+    if verbose                                                                       # :65
         G, _ = gram(fourier_problem(yv, tv, fv, nothing; device=device))
         @info("Condition number: $(round(cond(G), digits=2))\n")
     end
@@ -486,7 +500,7 @@ function ls_spectral_lpv(Y::AbstractVector, X::AbstractVector, V::AbstractVector
     e2 = dot(x, G * x) - 2dot(B[:, 1], x) + dot(Yv, Yv)   # ‖AA·x − Y‖² from the Gram
     esum = dot(B[:, 2], x) - sum(Yv)                      # Σe through the constant right-hand side
     var_e = (e2 - esum^2 / N) / (N - 1)                   # var(e), :253
-    Minv = try inverse(p, λ) catch e; e isa NumericError || rethrow(e); inv(G + λ * I) end   # inv(AA'AA + λI), λ as written
+    Minv = try inverse_refined(p, λ) catch e; e isa NumericError || rethrow(e); inv(G + λ * I) end   # inv(AA'AA + λI), λ as written
     # reference order u = c·Nf·nb + j·Nf + f  <-  device order q = f·2nb + c·nb + j   (0-based c, j, f)
     perm = Vector{Int}(undef, 2Nf * nb)
     for f in 0:Nf-1, c in 0:1, j in 0:nb-1

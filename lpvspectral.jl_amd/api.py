@@ -447,6 +447,13 @@ class Problem:
         check(lib().lpvs_problem_get_inverse_f64(self._h, float(shift), out_ptr(M)))
         return M
 
+    def get_inverse_refined(self, shift):
+        """``(G + shift I)⁻¹`` after one round of iterative refinement on the device (``lpvs_problem_get_inverse_refined_f64``), symmetrised:
+        for an inverse that is itself the result.  :meth:`get_inverse` is the one the solves and the iteration apply."""
+        M = np.zeros((self.n, self.n), order="F")
+        check(lib().lpvs_problem_get_inverse_refined_f64(self._h, float(shift), out_ptr(M)))
+        return 0.5 * (M + M.T)
+
     def solve_ridge(self, ridge):
         x = np.zeros(self.n, dtype=np.float32 if self.f32 else np.float64)
         fn = lib().lpvs_problem_solve_ridge_f32 if self.f32 else lib().lpvs_problem_solve_ridge_f64
@@ -681,8 +688,17 @@ def ls_spectral(y, t, f=None, W=None, λ=1e-10, verbose=False, device=0):
         dt = np.float32 if f32 else np.float64
         re, im = np.zeros(Nf, dtype=dt), np.zeros(Nf, dtype=dt)
         fn = lib().lpvs_ls_spectral_f32 if f32 else lib().lpvs_ls_spectral_f64
-        check(fn(py, pt, N, pf, Nf, float(λ), int(device), out_ptr(re), out_ptr(im)))
-        if verbose:                                                  # src/lsfft.jl:65: cond(A'A), from the device Gram
+        try:
+            check(fn(py, pt, N, pf, Nf, float(λ), int(device), out_ptr(re), out_ptr(im)))
+        except _lib.NumericError as e:
+            # the normal equations (primal or dual) are singular to working precision -- irregular stamps on a grid they cannot resolve with
+            # the default λ: the reference's QR of [A; λI] still works there.  Same route as ls_spectral_lpv, host LAPACK, on the regressor
+            # the device kernel materialises (src/utilities.jl:55-60).
+            log.info("ls_spectral: %s; solving [A; λI] \\ [y; 0] by QR on the host", e)
+            A, zf = get_fourier_regressor(t, f)
+            c = fourier2complex(_host_qr_ridge(np.asarray(A, dtype=np.float64), _host(y), float(λ)), zf)
+            re, im = c.real.astype(dt), c.imag.astype(dt)
+        if verbose:                                                 # src/lsfft.jl:65: cond(A'A), from the device Gram
             with Problem.fourier(y, t, f, None, device=device) as prob:
                 G, _ = prob.get_gram()
             log.info("Condition number: %s\n", round(float(np.linalg.cond(G)), 2))
@@ -1123,7 +1139,7 @@ def ls_spectral_lpv(Y, X, V, w, Nv, λ=1e-8, coulomb=False, normalize=True, devi
         G, _ = prob.get_gram()
         B = prob.get_rhs()
         try:
-            Minv = prob.get_inverse(λ)
+            Minv = prob.get_inverse_refined(λ)               # Σ is this inverse itself: refined, as the solves are
         except _lib.NumericError:
             Minv = np.linalg.inv(G + λ * np.eye(G.shape[0]))   # inv(AA'AA + λI) as the reference evaluates it (:253)
         Nf, nb = prob.Nf, prob.nb
