@@ -851,6 +851,65 @@ int32_t lpvs_wwz_f64(const double *y, int64_t ns, const double *t, int64_t N, co
                      double *wwz_out, double *neff_out, double *coef_out, int64_t *count_out, int32_t *empty_out);
 int32_t lpvs_wwz_last_timing(double *out, int32_t n);
 
+/* ---- g9  box least squares periodogram of non-uniformly sampled signals (extension; Kovacs, Zucker & Mazeh, A&A 391, 369, 2002, in
+ * its binned form): at every frequency the record is folded into nbins phase bins and every box of kmin .. kmax adjacent bins (wrapping)
+ * is tried as a two-level model -- one level inside the box, one outside.  It finds transits, eclipses and periodic drop-outs, which no
+ * number of harmonics of g7 describes.  No trigonometry: a histogram and a search.
+ * INPUTS.  y (N x ns column-major), t, W >= 0 (NULL: ones): as in g4; t finite, in ANY order (nothing is sorted).  W has its
+ *   inverse-variance meaning in depth_err_out.  f[Nf] (host): finite and > 0.  nbins in 8 .. 2048.  kmin[Nf], kmax[Nf] (host): the widths
+ *   in bins per frequency, 1 <= kmin <= kmax <= nbins / 2.  min_count >= 1: the least number of samples inside AND outside a box.
+ *   dips_only: keep only boxes whose level lies below the level outside.  center_data: remove the weighted mean first (0: ybar = 0).
+ *   normalization: 0 standard, 1 chi2.
+ * WEIGHTS AND CENTRING: g4's, by the same kernels: w = W / sum W, ybar_c = sum w y_c, wy = w (y - ybar_c).  YY_c = sum w (y - ybar_c)^2 has
+ *   g4's terms wy_n (y_n - ybar_c), but they are added up as integers -- two 64-bit words per term, cut against the largest term
+ *   (csrc/bls_plan.h) --, not in g4's tree: the sum of the rounded terms to two roundings, with the same bits in any order of the samples.
+ * QUANTISATION.  qw_n = rint(w_n 2^60); per signal A_c = max_n |wy_n| and qy_n = rint(wy_n 2^shy_c), shy_c = 61 - ceil(log2 N) -
+ *   (ilogb(A_c) + 1): no sum of any subset leaves 63 bits (the proof: csrc/bls_plan.h).  Everything up to the objective is then exact
+ *   integer arithmetic.  With W == NULL the weight of a box is its integer count at the scale 1 / N and no weight is quantised.
+ * FOLD.  Per (sample, frequency): p = f t, e = fma(f, t, -p), phi = (p - rint(p)) + e, plus 1 if negative -- the fractional part of the
+ *   exact product --, bin = min(nbins - 1, (int)floor(phi nbins)).  Per frequency the histograms HW[b] = sum qw, HY_c[b] = sum qy_c and
+ *   HC[b] = the count, by integer atomic adds: exact, whatever the order.
+ * SEARCH.  Box (k, b), kmin <= k <= kmax, 0 <= b < nbins: the bins b .. b + k - 1, wrapping.  r, s, count: its integer sums; R, S: the
+ *   integer totals of the histograms (not assumed to be 2^60 and 0).  A box is valid if count >= min_count and N - count >= min_count,
+ *   r > 0 and R - r > 0 and, with dips_only, s / r < (S - s) / (R - r) -- decided exactly, as s (R - r) < (S - s) r in 128-bit integers.
+ *   The objective, in double from the integers, each converted once, evaluated as written:
+ *       dq = ((s * s) / r + (sc * sc) / rc) - (S * S) / R,     sc = S - s, rc = R - r in integers,
+ *   and Delta = dq 2^(60 - 2 shy) (with W == NULL: (dq N) 2^(-2 shy)).  The best box has the largest dq; ties go to the smallest k, then
+ *   to the smallest b.
+ * OUTPUTS, Nf x ns column-major -- element c Nf + k:
+ *   power_out       host or device: standard: min(1, Delta / YY), the share of the weighted variance the box explains (the twin of g4's
+ *                   standard power); chi2: sum W Delta, the fall of chi^2 against the constant model (= snr^2 up to rounding)
+ *   depth_out       host or device: (S - s) / (R - r) - s / r, positive for a dip
+ *   depth_err_out   host or device: sqrt((1 / r + 1 / (R - r)) / sum W), r and R - r as shares of the total weight
+ *   start_out, width_out   host int32: the best box's first bin and width in bins
+ *   count_out       host int64: the samples inside it
+ *   degenerate_out  optional, host int32: 1 where the rule below bit
+ *   hist_out        optional, host int64, [Nf][1 + ns][nbins]: the raw integer histograms HW (with W == NULL: the counts), then HY_c
+ *   hcount_out      optional, host int32, [Nf][nbins]: HC
+ * RULES.  Nothing returned is ever NaN.  No valid box, a constant signal (A_c = 0), a YY within g4's constant-signal threshold
+ *   (lomb_yy_noise) or a variance that overflows: zeros in every plane, flagged and counted as degenerate; it is no error.
+ * WHAT THE RESULT MEANS.  Up to about a dozen double roundings the device returns the exact box least squares of the record whose w_n
+ *   and w_n (y_n - ybar) are rounded to the quanta 2^-60 and 2^-shy <= A 2^-(60 - ceil(log2 N)): a sum of n terms is off by at most n / 2
+ *   quanta.  For N = 2^20 the quantum of wy is at most A 2^-40 and a sum over the whole record is off by at most A 2^-21.
+ * ERRORS.  LPVS_EARGUMENT: a non-finite t, y, W or f; f <= 0; a negative weight or weights that sum to 0; nbins outside 8 .. 2048;
+ *   kmin < 1, kmin > kmax or kmax > nbins / 2; min_count < 1; a normalization other than 0 and 1; N, Nf < 1; ns outside 1 .. 65535.
+ *   LPVS_EUNSUPPORTED: more than 2^30 samples or 2^24 frequencies.
+ * DETERMINISM.  Two calls give the same bits.  A frequency is folded and searched from its own histograms alone: the same bits alone,
+ *   among others and in a permuted list, however many frequencies share a workgroup.  A signal has the same bits alone and among
+ *   others.  The sums -- histograms, and YY -- are integer sums: with W == NULL and center_data = 0 (nothing is summed in floating point
+ *   before the quantisation) a permutation of the samples leaves every bit of every output as it was, under both normalisations.  With
+ *   weights or centring, sum W and ybar are g4's tree sums in sample order: a permutation may move them, and the quantised record with
+ *   them, by a rounding.
+ * lpvs_bls_last_timing (the calling thread's last call), out[0..15]: frequencies per workgroup F, signals per pass TS, passes, LDS
+ *   bytes of a workgroup, the shift of the weights (60; 0 with W == NULL), the smallest and the largest shy_c, degenerate (frequency,
+ *   signal) pairs, boxes tried per signal, whether W was NULL, then milliseconds of the staging with the scan and the moments, the
+ *   maxima and the quantisation, fold and search, the copy-out and the total, and Nf. */
+int32_t lpvs_bls_f64(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const double *f, int64_t Nf, int32_t nbins,
+                     const int32_t *kmin, const int32_t *kmax, int64_t min_count, int32_t dips_only, int32_t center_data, int32_t normalization,
+                     int32_t device, double *power_out, double *depth_out, double *depth_err_out, int32_t *start_out, int32_t *width_out,
+                     int64_t *count_out, int32_t *degenerate_out, int64_t *hist_out, int32_t *hcount_out);
+int32_t lpvs_bls_last_timing(double *out, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif

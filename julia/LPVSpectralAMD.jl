@@ -21,7 +21,7 @@ export ls_spectral, tls_spectral, ls_sparse_spectral, ls_sparse_spectral_lpv, ls
        SpectralExt, psd, reshape_params, ADMM, rect, hanning, autocov, autocor, isequidistant,
        melspectrogram, mfcc, mel, spectrogram, Spectrogram, MelSpectrogram, MFCC, freq, rand_cn, schedfunc,
        Periodogram, welch_pgram, periodogram, compress, heatmap, predict, residual, fva, lombscargle, lombscargle_last_timing, lombscargle_terms_last_timing,
-       lombscargle_spectrogram, lombscargle_welch, lombscargle_windows_last_timing, time_windows, wwz, wwz_radius, wwz_last_timing, lombscargle_bootstrap,
+       lombscargle_spectrogram, lombscargle_welch, lombscargle_windows_last_timing, time_windows, wwz, wwz_radius, wwz_last_timing, bls, bls_frequencies, bls_last_timing, lombscargle_bootstrap,
        lombscargle_bootstrap_last_timing
 
 const LIB = get(ENV, "LPVSPECTRAL_LIB", joinpath(@__DIR__, "..", "lpvspectral.jl_amd", "liblpvspectral.so"))
@@ -1263,6 +1263,64 @@ function wwz_last_timing()
     GC.@preserve tm check(@ccall LIB.lpvs_wwz_last_timing(tm::Ptr{Float64}, Int32(16)::Int32)::Int32)
     (nf=Int(tm[1]), ntau=Int(tm[2]), tt=Int(tm[3]), ts=Int(tm[4]), items=Int(tm[5]), slab=Int(tm[6]), empty=Int(tm[7]), degenerate=Int(tm[8]), staged=tm[9],
      useful=tm[10], scan_ms=tm[11], ranges_ms=tm[12], sums_ms=tm[13], epilogue_ms=tm[14], copy_ms=tm[15], total_ms=tm[16])
+end
+
+# ---- box least squares periodogram (extension; include/lpvspectral.h g9) ---------------------------------------------------------------
+"""    bls_frequencies(t, fmin, fmax, qmin; oversample=3)
+The frequency grid of a box search: from `fmin` up to `fmax` in steps of `qmin / (oversample (max t - min t))`."""
+function bls_frequencies(t::AbstractVector{<:Real}, fmin::Real, fmax::Real, qmin::Real; oversample::Real=3)
+    span = Float64(maximum(t) - minimum(t))
+    (span > 0 && qmin > 0 && oversample > 0 && 0 < fmin <= fmax) || throw(ArgumentError("bls_frequencies: need max t > min t, qmin > 0, oversample > 0 and 0 < fmin <= fmax"))
+    df = Float64(qmin) / (Float64(oversample) * span)
+    Float64(fmin) .+ df .* (0:floor(Int, (Float64(fmax) - Float64(fmin)) / df))
+end
+"""    bls(y, t, f; W=nothing, nbins=200, q=(0.01, 0.1), duration=nothing, min_count=1, dips_only=true, center_data=true, normalization=:standard, return_hist=false)
+Box least squares periodogram (Kovács, Zucker & Mazeh 2002, binned) of non-uniformly sampled signals: at every frequency the record is
+folded into `nbins` phase bins and every box of adjacent bins (wrapping) is tried as a two-level model.  `q = (qmin, qmax)` gives the
+widths `max(1, floor(qmin nbins)) .. min(nbins ÷ 2, ceil(qmax nbins))` bins, `duration = (dmin, dmax)` in units of `t` the same per
+frequency with `q = d f`.  `normalization`: `:standard` (share of the weighted variance, in [0, 1]) or `:chi2` (`snr²`).  Returns
+`(freq, power, depth, depth_err, snr, start, width, q, duration, transit_time, count_in, degenerate)` (`start` 0-based, as the phase
+`start / nbins`), each `Nf` (`× ns`), and with `return_hist=true` also `hist` (`nbins × (1 + ns) × Nf` Int64) and `hcount` (`nbins × Nf`)."""
+function bls(y::AbstractVecOrMat{<:Real}, t::AbstractVector{<:Real}, f::AbstractVector{<:Real}; W=nothing, nbins::Integer=200, q=(0.01, 0.1), duration=nothing,
+             min_count::Integer=1, dips_only::Bool=true, center_data::Bool=true, normalization::Symbol=:standard, device::Integer=0, return_hist::Bool=false)
+    normalization in (:standard, :chi2) || throw(ArgumentError("normalization: unknown value $normalization (known: :standard, :chi2)"))
+    tv, fv = Vector{Float64}(t), Vector{Float64}(f)
+    N, Nf, ns = length(tv), length(fv), size(y, 2)
+    @assert size(y, 1) == N "y has to be as long as the sampling points"
+    yv = Matrix{Float64}(reshape(y, N, ns))
+    Wv = W === nothing ? Float64[] : Vector{Float64}(W)
+    @assert W === nothing || length(Wv) == N "W has to be as long as the sampling points"
+    Wp = W === nothing ? Ptr{Float64}(C_NULL) : pointer(Wv)
+    qlo = duration === nothing ? fill(Float64(q[1]), Nf) : Float64(duration[1]) .* fv
+    qhi = duration === nothing ? fill(Float64(q[2]), Nf) : Float64(duration[2]) .* fv
+    clampk(x) = isfinite(x) ? Int32(clamp(x, 0, 2.0^30)) : Int32(0)
+    kmin = clampk.(max.(1.0, floor.(qlo .* nbins)))
+    kmax = clampk.(min.(Float64(nbins ÷ 2), ceil.(qhi .* nbins)))
+    power, depth, depth_err = zeros(Nf, ns), zeros(Nf, ns), zeros(Nf, ns)
+    start, width, degenerate, count_in = zeros(Int32, Nf, ns), zeros(Int32, Nf, ns), zeros(Int32, Nf, ns), zeros(Int64, Nf, ns)
+    histv = return_hist ? zeros(Int64, max(nbins, 0), 1 + ns, Nf) : Int64[]
+    hcountv = return_hist ? zeros(Int32, max(nbins, 0), Nf) : Int32[]
+    histp = return_hist ? pointer(histv) : Ptr{Int64}(C_NULL)
+    hcountp = return_hist ? pointer(hcountv) : Ptr{Int32}(C_NULL)
+    GC.@preserve yv tv Wv fv kmin kmax power depth depth_err start width count_in degenerate histv hcountv check(@ccall LIB.lpvs_bls_f64(yv::Ptr{Float64},
+        Int64(ns)::Int64, tv::Ptr{Float64}, Int64(N)::Int64, Wp::Ptr{Float64}, fv::Ptr{Float64}, Int64(Nf)::Int64, Int32(nbins)::Int32, kmin::Ptr{Int32},
+        kmax::Ptr{Int32}, Int64(min_count)::Int64, Int32(dips_only)::Int32, Int32(center_data)::Int32, Int32(normalization == :chi2 ? 1 : 0)::Int32,
+        Int32(device)::Int32, power::Ptr{Float64}, depth::Ptr{Float64}, depth_err::Ptr{Float64}, start::Ptr{Int32}, width::Ptr{Int32}, count_in::Ptr{Int64},
+        degenerate::Ptr{Int32}, histp::Ptr{Int64}, hcountp::Ptr{Int32})::Int32)
+    one = y isa AbstractVector
+    shaped(A) = one ? A[:, 1] : A
+    snr = map((d, e) -> e > 0 ? d / e : 0.0, depth, depth_err)
+    qq = width ./ Float64(nbins)
+    R = (freq = fv, power = shaped(power), depth = shaped(depth), depth_err = shaped(depth_err), snr = shaped(snr), start = shaped(start), width = shaped(width),
+         q = shaped(qq), duration = shaped(qq ./ fv), transit_time = shaped((start .+ width ./ 2) ./ Float64(nbins) ./ fv), count_in = shaped(count_in),
+         degenerate = shaped(degenerate .!= 0))
+    return_hist ? merge(R, (hist = histv, hcount = hcountv)) : R
+end
+function bls_last_timing()
+    tm = zeros(16)
+    GC.@preserve tm check(@ccall LIB.lpvs_bls_last_timing(tm::Ptr{Float64}, Int32(16)::Int32)::Int32)
+    (F=Int(tm[1]), ts=Int(tm[2]), passes=Int(tm[3]), lds_bytes=Int(tm[4]), shift_w=Int(tm[5]), shift_y_min=Int(tm[6]), shift_y_max=Int(tm[7]), degenerate=Int(tm[8]),
+     boxes=tm[9], unit=tm[10] != 0, scan_ms=tm[11], quantise_ms=tm[12], search_ms=tm[13], copy_ms=tm[14], total_ms=tm[15], nf=Int(tm[16]))
 end
 
 # ---- the bootstrap of the Lomb-Scargle periodogram (extension; include/lpvspectral.h g6) -------------------------------------------------

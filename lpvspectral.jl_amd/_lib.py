@@ -198,6 +198,8 @@ SIGNATURES = {
     "lpvs_lombscargle_terms_last_timing": (_I32, [_P, _I32]),
     "lpvs_wwz_f64": (_I32, [_P, _I64, _P, _I64, _P, _P, _I64, _P, _I64, _F64, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "lpvs_wwz_last_timing": (_I32, [_P, _I32]),
+    "lpvs_bls_f64": (_I32, [_P, _I64, _P, _I64, _P, _P, _I64, _I32, _P, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "lpvs_bls_last_timing": (_I32, [_P, _I32]),
 }
 
 _lib = None

@@ -2432,6 +2432,108 @@ def wwz_last_timing():
             "sums_ms": float(o[12]), "epilogue_ms": float(o[13]), "copy_ms": float(o[14]), "total_ms": float(o[15])}
 
 
+# ---- box least squares periodogram (include/lpvspectral.h g9; csrc/bls.hip) ------------------------------------------------------------------
+_BLS_NORMALIZATIONS = {"standard": 0, "chi2": 1}
+
+
+class BLS:
+    """The result of :func:`bls`.  ``freq``: (Nf,); ``power``, ``depth``, ``depth_err``, ``snr = depth / depth_err`` (0 where degenerate),
+    ``start``, ``width`` (the best box's first bin and width in bins), ``q = width / nbins``, ``duration = q / f``,
+    ``transit_time = (start + width / 2) / nbins / f`` (the box's centre, in units of ``t`` after a whole number of periods from
+    ``t = 0``), ``count_in`` and ``degenerate``: (Nf,) or (Nf, ns).  With ``return_hist=True`` also ``hist`` -- the raw integer
+    histograms, (Nf, 1 + ns, nbins) int64: row 0 the weights at the scale 2^-60 (the counts with ``W=None``), row 1 + c signal c -- and
+    ``hcount`` (Nf, nbins), the samples per bin."""
+
+    def __init__(self, freq, power, depth, depth_err, start, width, count_in, degenerate, nbins, hist=None, hcount=None):
+        self.freq, self.power, self.depth, self.depth_err, self.start, self.width = freq, power, depth, depth_err, start, width
+        self.count_in, self.degenerate, self.nbins, self.hist, self.hcount = count_in, degenerate, nbins, hist, hcount
+        fcol = freq if power.ndim == 1 else freq[:, None]
+        self.snr = np.divide(depth, depth_err, out=np.zeros_like(depth), where=depth_err > 0)
+        self.q = width / float(nbins)
+        self.duration = self.q / fcol
+        self.transit_time = (start + width / 2.0) / float(nbins) / fcol
+
+
+def bls_frequencies(t, fmin, fmax, qmin, oversample=3):
+    """The frequency grid of a box search: from ``fmin`` up to ``fmax`` in steps of ``qmin / (oversample (max t - min t))`` -- over the
+    record a box of the shortest relative duration ``qmin`` then drifts by ``1 / oversample`` of its width from one frequency to the
+    next."""
+    th = np.ravel(_host(t)).astype(np.float64)
+    span = float(th.max() - th.min())
+    if not (span > 0 and qmin > 0 and oversample > 0 and 0 < fmin <= fmax):
+        raise ValueError(f"bls_frequencies: need max t > min t, qmin > 0, oversample > 0 and 0 < fmin <= fmax (span = {span}, qmin = {qmin}, "
+                         f"oversample = {oversample}, fmin = {fmin}, fmax = {fmax})")
+    df = qmin / (oversample * span)
+    return fmin + df * np.arange(int(np.floor((fmax - fmin) / df)) + 1)
+
+
+def bls(y, t, f, W=None, nbins=200, q=(0.01, 0.1), duration=None, min_count=1, dips_only=True, center_data=True, normalization="standard", device=0,
+        return_hist=False):
+    """Box least squares periodogram (Kovács, Zucker & Mazeh 2002, the binned form) of non-uniformly sampled signals: at every frequency
+    the record is folded into ``nbins`` phase bins and every box of adjacent bins (wrapping) is tried as a two-level model.  It finds
+    transits, eclipses and periodic drop-outs -- dips far shorter than a period, which no number of harmonics of
+    :func:`lombscargle` describes (csrc/bls.hip; include/lpvspectral.h g9).
+
+    ``y``: (N,) or (N, ns) signals sharing the times ``t`` (numpy arrays or device tensors; ``t`` in any order); ``f``: positive
+    frequencies (:func:`bls_frequencies` makes the usual grid); ``W``: non-negative weights, inverse variances for ``depth_err``
+    (``None``: ones).  The widths tried: ``q = (qmin, qmax)``, shares of a period, give ``kmin = max(1, floor(qmin nbins))`` and
+    ``kmax = min(nbins // 2, ceil(qmax nbins))`` bins at every frequency; ``duration = (dmin, dmax)`` in units of ``t`` gives the same per
+    frequency with ``q = d f``.  ``min_count``: the least number of samples inside and outside a box.  ``dips_only``: only boxes that
+    lie below the rest.  ``normalization``: ``"standard"`` (the share of the weighted variance the box explains, in [0, 1]) or
+    ``"chi2"`` (the fall of chi², ``snr²``).
+
+    The folds use the phases of the exact products ``f t``; the sums -- the histograms and ``YY`` -- are 64-bit integer sums of the
+    quantised record (csrc/bls_plan.h), so a frequency or a signal has the same bits whatever else is computed in the call, and with
+    ``W=None, center_data=False`` a permutation of the samples changes no bit of any output (with weights or centring ``ΣW`` and the
+    mean are floating-point tree sums in sample order, and a permutation may move the quantised record by a rounding).  Frequencies without a valid box, constant
+    signals and samples that all fall in one bin give zeros, flagged in ``degenerate``; nothing is ever NaN.  Returns a :class:`BLS`."""
+    if normalization not in _BLS_NORMALIZATIONS:
+        raise ValueError(f"normalization: unknown value {normalization!r} (known: {sorted(_BLS_NORMALIZATIONS)})")
+    fa = np.ascontiguousarray(np.ravel(_host(f)).astype(np.float64))
+    Nf, nbins = len(fa), int(nbins)
+    if duration is not None:
+        qlo, qhi = float(duration[0]) * fa, float(duration[1]) * fa
+    else:
+        qlo, qhi = np.full(Nf, float(q[0])), np.full(Nf, float(q[1]))
+    with np.errstate(all="ignore"):                                            # (a frequency the library refuses gives nan or inf here)
+        kmin = np.nan_to_num(np.maximum(1.0, np.floor(qlo * nbins)), nan=0.0, posinf=2.0 ** 30, neginf=0.0)
+        kmax = np.nan_to_num(np.minimum(float(nbins // 2), np.ceil(qhi * nbins)), nan=0.0, posinf=2.0 ** 30, neginf=0.0)
+    kmin, kmax = np.ascontiguousarray(kmin.astype(np.int32)), np.ascontiguousarray(kmax.astype(np.int32))
+    ys, N, ns, single = _lomb_signals(y)
+    ky, py, ny = as_f64(ys)
+    kt, pt, nt = as_f64(_f64_arg(t))
+    if nt != N:
+        raise ValueError(f"y has {N} samples, t has {nt}")
+    kw, pw, nw = as_f64(_f64_arg(W))
+    if W is not None and nw != N:
+        raise ValueError(f"y has {N} samples, W has {nw}")
+    planes = np.zeros((3, ns, Nf))                                             # power, depth, depth_err: [signal][frequency]
+    ints = np.zeros((3, ns, Nf), dtype=np.int32)                               # start, width, degenerate
+    count = np.zeros((ns, Nf), dtype=np.int64)
+    hist = np.zeros((Nf, 1 + ns, max(nbins, 0)), dtype=np.int64) if return_hist else None
+    hcount = np.zeros((Nf, max(nbins, 0)), dtype=np.int32) if return_hist else None
+    check(lib().lpvs_bls_f64(py, ns, pt, N, pw, out_ptr(fa), Nf, nbins, out_ptr(kmin), out_ptr(kmax), int(min_count), int(bool(dips_only)),
+                             int(bool(center_data)), _BLS_NORMALIZATIONS[normalization], int(device), out_ptr(planes[0]), out_ptr(planes[1]),
+                             out_ptr(planes[2]), out_ptr(ints[0]), out_ptr(ints[1]), out_ptr(count), out_ptr(ints[2]),
+                             out_ptr(hist) if return_hist else None, out_ptr(hcount) if return_hist else None))
+    del ky, kt, kw
+
+    def shaped(a):                                                             # (ns, Nf) -> (Nf,) or (Nf, ns)
+        return a[0].copy() if single else np.ascontiguousarray(a.T)
+    return BLS(fa, shaped(planes[0]), shaped(planes[1]), shaped(planes[2]), shaped(ints[0]), shaped(ints[1]), shaped(count), shaped(ints[2]).astype(bool),
+               nbins, hist, hcount)
+
+
+def bls_last_timing():
+    """Plan and timing of the calling thread's last :func:`bls`: frequencies per workgroup, signals per pass, passes, LDS bytes, the
+    shifts of the quantisation, degenerate (frequency, signal) pairs, boxes tried per signal, milliseconds per phase."""
+    o = np.zeros(16)
+    check(lib().lpvs_bls_last_timing(out_ptr(o), 16))
+    return {"F": int(o[0]), "ts": int(o[1]), "passes": int(o[2]), "lds_bytes": int(o[3]), "shift_w": int(o[4]), "shift_y_min": int(o[5]),
+            "shift_y_max": int(o[6]), "degenerate": int(o[7]), "boxes": float(o[8]), "unit": bool(o[9]), "scan_ms": float(o[10]),
+            "quantise_ms": float(o[11]), "search_ms": float(o[12]), "copy_ms": float(o[13]), "total_ms": float(o[14]), "nf": int(o[15])}
+
+
 # ---- false-alarm probabilities of the Lomb-Scargle periodogram: the device bootstrap and the closed forms (include/lpvspectral.h g6) ------
 _M32 = np.uint64(0xFFFFFFFF)
 

@@ -1959,6 +1959,144 @@ int32_t lpvs_wwz_last_timing(double *out, int32_t n) {
     return LPVS_OK;
 }
 
+// ---- box least squares periodogram (bls.hip; the decisions: bls_plan.h) ------------------------------------------------------------------------
+// what lpvs_bls_last_timing reports of the calling thread's last call: [0] frequencies per workgroup (F), [1] signals per pass (TS),
+// [2] passes, [3] LDS bytes of a workgroup, [4] the shift of the weights (60; 0 with unit weights: counts), [5], [6] the smallest and
+// largest shift of a signal (0, 0 when every signal is constant), [7] degenerate (frequency, signal) pairs, [8] boxes tried (per signal),
+// [9] unit weights, ms of [10] staging, the scan and the moments, [11] the maxima and the quantisation, [12] fold and search,
+// [13] the copy-out, [14] total, [15] Nf
+static thread_local double g_bls_timing[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+static int32_t bls_impl(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const double *f, int64_t Nf, int32_t nbins, const int32_t *kmin,
+                        const int32_t *kmax, int64_t min_count, bool dips_only, bool center, bool chi2, const BlsPlan &plan, int32_t device, double *power,
+                        double *depth, double *depth_err, int32_t *start_out, int32_t *width_out, int64_t *count_out, int32_t *degenerate_out, int64_t *hist_out,
+                        int32_t *hcount_out) {
+    if (lpvs_device_count() == 0) { set_error("no HIP device visible (the gfx950 path has no CPU fallback)"); return LPVS_EDEVICE; }
+    LPVS_HIP(hipSetDevice(device));
+    hipStream_t s = nullptr;
+    Events<5> ev;
+    for (auto &e : ev.e) LPVS_HIP(hipEventCreate(&e));
+    DevArg dt, dy, dW; DevOut dpower, ddepth, derr;
+    DevBuf dsmall, dscan, dw, dwy, dq, dfreq, dk, dshy, dint, dcount, dhist, dhcount;
+    DrainOnExit drain(s);
+    LPVS_HIP(hipEventRecord(ev.e[0], s));
+    LPVS_TRY(dt.set(t, N, s));
+    LPVS_TRY(dy.set(y, N * ns, s));
+    if (W) LPVS_TRY(dW.set(W, N, s));
+    const int64_t ncols = Nf * ns;
+    LPVS_TRY(dpower.set(power, ncols));
+    LPVS_TRY(ddepth.set(depth, ncols));
+    LPVS_TRY(derr.set(depth_err, ncols));
+    // small device record: [0] sum W, [1 .. ns] the weighted means, then launch_lomb_moments' moments (3 ns), then the maxima (2 ns), the
+    // two words of every YY (2 ns), the degenerate counter and the flags
+    const size_t nsmall = (size_t)(1 + 4 * ns);
+    LPVS_TRY(dsmall.alloc(sizeof(double) * (nsmall + (size_t)(4 * ns) + 2)));
+    double *sumW_dev = dsmall.as<double>(), *mean_dev = sumW_dev + 1, *mom_dev = mean_dev + ns;
+    unsigned long long *amax_dev = reinterpret_cast<unsigned long long *>(sumW_dev + nsmall);
+    long long *yyacc_dev = reinterpret_cast<long long *>(amax_dev + 2 * ns);
+    unsigned long long *ndeg_dev = amax_dev + 4 * ns;
+    int *flags_dev = reinterpret_cast<int *>(ndeg_dev + 1);
+    const int64_t nsum = lomb_sum_slabs(N);
+    LPVS_TRY(dscan.alloc(sizeof(double) * (size_t)(3 * ns * nsum)));
+    LPVS_TRY(launch_lomb_scan(dt.p, dy.p, dW.p, N, ns, flags_dev, dscan.as<double>(), sumW_dev, s));
+    double sumW = 0; int flags = 0;
+    LPVS_TRY(copy_from_device(&sumW, sumW_dev, sizeof(double), s));
+    LPVS_TRY(copy_from_device(&flags, flags_dev, sizeof(int), s));
+    if (flags & 1) { set_error("bls: t, y or W holds a value that is not finite"); return LPVS_EARGUMENT; }
+    if (flags & 2) { set_error("bls: a weight is negative"); return LPVS_EARGUMENT; }
+    if (!(sumW > 0.0) || !std::isfinite(sumW)) { set_error("bls: the weights sum to %g", sumW); return LPVS_EARGUMENT; }
+    LPVS_TRY(dw.alloc(sizeof(double) * (size_t)N));
+    LPVS_TRY(dwy.alloc(sizeof(double) * (size_t)(N * ns)));
+    LPVS_TRY(launch_lomb_moments(dy.p, dW.p, N, ns, sumW, center, dw.as<double>(), dwy.as<double>(), mean_dev, mom_dev, dscan.as<double>(), s));
+    LPVS_HIP(hipEventRecord(ev.e[1], s));
+    // the maxima, the shifts (bls_plan.h), the quantised record: qy[ns][N], then qw[N] with weights
+    LPVS_TRY(launch_bls_max(dy.p, dwy.as<double>(), mean_dev, center, N, ns, amax_dev, s));
+    std::vector<unsigned long long> hmax((size_t)(2 * ns));
+    LPVS_TRY(copy_from_device(hmax.data(), amax_dev, sizeof(unsigned long long) * (size_t)(2 * ns), s));
+    std::vector<int32_t> hshy((size_t)(2 * ns), 0);
+    int shy_lo = 0, shy_hi = 0; bool any = false;
+    for (int64_t c = 0; c < ns; ++c) {
+        double A, M;
+        memcpy(&A, &hmax[(size_t)c], sizeof(double)); memcpy(&M, &hmax[(size_t)(ns + c)], sizeof(double));
+        hshy[(size_t)(ns + c)] = M > 0.0 && std::isfinite(M) ? bls_shift_y(M, N) : kBlsNoShift;   // (the terms of YY_c: cut against the largest)
+        if (!(A > 0.0)) continue;
+        const int sh = bls_shift_y(A, N);
+        hshy[(size_t)c] = sh;
+        shy_lo = any && shy_lo < sh ? shy_lo : sh;
+        shy_hi = any && shy_hi > sh ? shy_hi : sh;
+        any = true;
+    }
+    LPVS_TRY(dshy.alloc(sizeof(int32_t) * (size_t)(2 * ns)));
+    LPVS_TRY(copy_to_device(dshy.p, hshy.data(), sizeof(int32_t) * (size_t)(2 * ns), s));
+    LPVS_TRY(dq.alloc(sizeof(long long) * (size_t)(N * (ns + (plan.unit ? 0 : 1)))));
+    long long *qy_dev = dq.as<long long>(), *qw_dev = plan.unit ? nullptr : qy_dev + N * ns;
+    LPVS_TRY(launch_bls_quantise(dy.p, dw.as<double>(), dwy.as<double>(), mean_dev, center, N, ns, plan.log2n, dshy.as<int32_t>(), amax_dev, qw_dev, qy_dev, yyacc_dev, s));
+    LPVS_TRY(dfreq.alloc(sizeof(double) * (size_t)Nf));
+    LPVS_TRY(copy_to_device(dfreq.p, f, sizeof(double) * (size_t)Nf, s));
+    LPVS_TRY(dk.alloc(sizeof(int32_t) * (size_t)(2 * Nf)));
+    LPVS_TRY(copy_to_device(dk.p, kmin, sizeof(int32_t) * (size_t)Nf, s));
+    LPVS_TRY(copy_to_device(dk.as<int32_t>() + Nf, kmax, sizeof(int32_t) * (size_t)Nf, s));
+    LPVS_TRY(dint.alloc(sizeof(int32_t) * (size_t)(3 * ncols)));
+    LPVS_TRY(dcount.alloc(sizeof(int64_t) * (size_t)ncols));
+    if (hist_out) LPVS_TRY(dhist.alloc(sizeof(int64_t) * (size_t)(Nf * (1 + ns) * nbins)));
+    if (hcount_out) LPVS_TRY(dhcount.alloc(sizeof(int32_t) * (size_t)(Nf * nbins)));
+    BlsArgs A;
+    A.t = dt.p; A.qw = qw_dev; A.qy = qy_dev; A.f = dfreq.as<double>(); A.kmin = dk.as<int32_t>(); A.kmax = A.kmin + Nf;
+    A.shy = dshy.as<int32_t>(); A.amax = amax_dev; A.yyacc = yyacc_dev; A.mom = mom_dev; A.log2n = plan.log2n;
+    A.N = N; A.Nf = Nf; A.min_count = min_count; A.ns = (int)ns; A.nbins = nbins; A.dips_only = dips_only ? 1 : 0; A.chi2 = chi2 ? 1 : 0;
+    A.center = center ? 1 : 0; A.sumW = sumW;
+    A.power = dpower.p; A.depth = ddepth.p; A.depth_err = derr.p;
+    A.start = dint.as<int32_t>(); A.width = A.start + ncols; A.degenerate = A.width + ncols; A.count = dcount.as<int64_t>();
+    A.hist = hist_out ? dhist.as<long long>() : nullptr; A.hcount = hcount_out ? dhcount.as<int32_t>() : nullptr; A.ndeg = ndeg_dev;
+    LPVS_HIP(hipEventRecord(ev.e[2], s));
+    LPVS_TRY(launch_bls(A, plan, s));
+    LPVS_HIP(hipEventRecord(ev.e[3], s));
+    unsigned long long ndeg = 0;
+    LPVS_TRY(copy_from_device(&ndeg, ndeg_dev, sizeof(ndeg), s));
+    LPVS_TRY(copy_from_device(start_out, A.start, sizeof(int32_t) * (size_t)ncols, s));
+    LPVS_TRY(copy_from_device(width_out, A.width, sizeof(int32_t) * (size_t)ncols, s));
+    LPVS_TRY(copy_from_device(count_out, A.count, sizeof(int64_t) * (size_t)ncols, s));
+    if (degenerate_out) LPVS_TRY(copy_from_device(degenerate_out, A.degenerate, sizeof(int32_t) * (size_t)ncols, s));
+    if (hist_out) LPVS_TRY(copy_from_device(hist_out, dhist.p, sizeof(int64_t) * (size_t)(Nf * (1 + ns) * nbins), s));
+    if (hcount_out) LPVS_TRY(copy_from_device(hcount_out, dhcount.p, sizeof(int32_t) * (size_t)(Nf * nbins), s));
+    LPVS_TRY(dpower.finish(s));
+    LPVS_TRY(ddepth.finish(s));
+    LPVS_TRY(derr.finish(s));
+    LPVS_HIP(hipEventRecord(ev.e[4], s));
+    LPVS_HIP(hipStreamSynchronize(s));
+    float ms[4] = {0, 0, 0, 0}, total = 0;
+    for (int i = 0; i < 4; ++i) LPVS_HIP(hipEventElapsedTime(&ms[i], ev.e[i], ev.e[i + 1]));
+    LPVS_HIP(hipEventElapsedTime(&total, ev.e[0], ev.e[4]));
+    double *g = g_bls_timing;
+    g[0] = plan.F; g[1] = plan.ts; g[2] = plan.passes; g[3] = (double)plan.lds_bytes; g[4] = plan.unit ? 0 : kBlsWeightShift; g[5] = shy_lo; g[6] = shy_hi;
+    g[7] = (double)ndeg; g[8] = plan.boxes; g[9] = plan.unit; g[10] = ms[0]; g[11] = ms[1]; g[12] = ms[2]; g[13] = ms[3]; g[14] = total; g[15] = (double)Nf;
+    return LPVS_OK;
+}
+
+int32_t lpvs_bls_f64(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const double *f, int64_t Nf, int32_t nbins, const int32_t *kmin,
+                     const int32_t *kmax, int64_t min_count, int32_t dips_only, int32_t center_data, int32_t normalization, int32_t device, double *power_out,
+                     double *depth_out, double *depth_err_out, int32_t *start_out, int32_t *width_out, int64_t *count_out, int32_t *degenerate_out, int64_t *hist_out,
+                     int32_t *hcount_out) {
+    try {
+        if (!y || !t || !f || !kmin || !kmax || !power_out || !depth_out || !depth_err_out || !start_out || !width_out || !count_out) {
+            set_error("NULL argument"); return LPVS_EARGUMENT;
+        }
+        if (is_device_ptr(f) || is_device_ptr(kmin) || is_device_ptr(kmax) || is_device_ptr(start_out) || is_device_ptr(width_out) || is_device_ptr(count_out) ||
+            (degenerate_out && is_device_ptr(degenerate_out)) || (hist_out && is_device_ptr(hist_out)) || (hcount_out && is_device_ptr(hcount_out))) {
+            set_error("bls: f, kmin, kmax, start_out, width_out, count_out, degenerate_out, hist_out and hcount_out are host memory"); return LPVS_EARGUMENT;
+        }
+        const BlsPlan plan = bls_plan(N, ns, f, Nf, nbins, kmin, kmax, min_count, W == nullptr, normalization);   // (the counts are checked before an array is read)
+        if (plan.status != kBlsOk) { set_error("%s", plan.why.c_str()); return plan.status == kBlsArgument ? LPVS_EARGUMENT : LPVS_EUNSUPPORTED; }
+        return bls_impl(y, ns, t, N, W, f, Nf, nbins, kmin, kmax, min_count, dips_only != 0, center_data != 0, normalization == 1, plan, device, power_out, depth_out,
+                        depth_err_out, start_out, width_out, count_out, degenerate_out, hist_out, hcount_out);
+    } catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
+}
+
+int32_t lpvs_bls_last_timing(double *out, int32_t n) {
+    if (!out || n < 0) { set_error("NULL argument"); return LPVS_EARGUMENT; }
+    for (int32_t k = 0; k < n && k < 16; ++k) out[k] = g_bls_timing[k];
+    return LPVS_OK;
+}
+
 // ---- the bootstrap of the Lomb-Scargle periodogram (lomb_boot.hip; the decisions: lomb_boot_plan.h) ------------------------------------------
 // what lpvs_lombscargle_bootstrap_last_timing reports of the calling thread's last call: [0] resamples, [1] chunks, [2] resamples per thread
 // (TS), [3] slab length, [4] slabs, [5] degenerate frequencies, ms of [6] staging, the scan and the shared sums of the record, [7] the

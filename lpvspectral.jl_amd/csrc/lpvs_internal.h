@@ -17,6 +17,7 @@
 #include "lomb_boot_plan.h"
 #include "lomb_terms_plan.h"
 #include "wwz_plan.h"
+#include "bls_plan.h"
 
 namespace lpvs {
 
@@ -312,6 +313,31 @@ int32_t launch_wwz_sums(const WwzArgs &A, int ts, double *part, hipStream_t s);
 // to a finite value, |= 16: a cell outside its pair's items (never); counters[2] = {empty, degenerate cells}
 int32_t launch_wwz_epilogue(const WwzArgs &A, const double *part, const int64_t *cell_edges, bool center, double *power, double *amplitude, double *wwz,
                             double *neff, double *coef, int64_t *count_out, int32_t *empty_out, int *flags_dev, unsigned long long *counters, hipStream_t s);
+
+// box least squares periodogram (lpvs_bls_f64; bls.hip; the decisions: bls_plan.h).  All pointers are device memory.
+struct BlsArgs {
+    const double *t = nullptr;                                   // [N]
+    const long long *qw = nullptr, *qy = nullptr;                // qw[N] (nullptr with unit weights), qy[ns][N]: the quantised record
+    const double *f = nullptr;                                   // [Nf]
+    const int32_t *kmin = nullptr, *kmax = nullptr;              // [Nf]: the widths in bins
+    const int32_t *shy = nullptr;                                // [2 ns]: the shifts of the signals, then those of the terms of YY_c (or kBlsNoShift)
+    const unsigned long long *amax = nullptr;                    // [2 ns]: the bit patterns of max |wy| (0: a constant signal), then of the largest term of YY_c
+    const long long *yyacc = nullptr;                            // [2 ns]: the two integer words of YY_c (bls_plan.h: bls_yy)
+    const double *mom = nullptr;                                 // launch_lomb_moments' mom_dev: sum w y_c^2 of the signal as given at 2 ns + c
+    int64_t N = 0, Nf = 0, min_count = 1;
+    int ns = 0, nbins = 0, dips_only = 1, chi2 = 0, center = 1, log2n = 0;
+    double sumW = 1;
+    double *power = nullptr, *depth = nullptr, *depth_err = nullptr;   // [ns][Nf]
+    int32_t *start = nullptr, *width = nullptr, *degenerate = nullptr; // [ns][Nf]
+    int64_t *count = nullptr;                                    // [ns][Nf]
+    long long *hist = nullptr;                                   // [Nf][1 + ns][nbins] or nullptr
+    int32_t *hcount = nullptr;                                   // [Nf][nbins] or nullptr
+    unsigned long long *ndeg = nullptr;                          // the degenerate (frequency, signal) pairs
+};
+int32_t launch_bls_max(const double *y, const double *wy, const double *mean_dev, bool center, int64_t N, int64_t ns, unsigned long long *amax_dev, hipStream_t s);
+int32_t launch_bls_quantise(const double *y, const double *w, const double *wy, const double *mean_dev, bool center, int64_t N, int64_t ns, int log2n,
+                            const int32_t *shy_dev, const unsigned long long *amax_dev, long long *qw, long long *qy, long long *yyacc_dev, hipStream_t s);
+int32_t launch_bls(const BlsArgs &A, const BlsPlan &plan, hipStream_t s);
 
 // ---- dense symmetric inverse (linalg.hip) ------------------------------------------------
 // In-place inverse of the SPD matrix A (np x np, np % 64 == 0, full symmetric storage) by
