@@ -149,25 +149,39 @@ size_t pool_cached_bytes(int dev) {
     return pool().cached[dev];
 }
 
+// LPVS_POOL_FILL=<two hex digits> (experiment knob, pool_plan.h): every block is filled with that byte over its WHOLE
+// true size before it is handed out, cached and fresh alike, and a fresh block is asked for kPoolFillSlack bytes larger than the request --
+// a result that changes with the byte read something its own call never wrote (tests/test_gpu_pool_fill.py).  The fill is a blocking
+// hipMemset followed by a device-wide synchronise, so no stream of any handle can overtake it.  No allocation happens while a stream
+// captures: the only capture is capture_graph's, around launch_admm_iterations, and neither that function nor anything admm*.hip holds
+// allocates (every workspace of an iteration is the handle's, allocated by lpvs_admm_init and the setters that drop the graph).
+static int32_t pool_fill(void *p, size_t bytes, int byte) {
+    LPVS_HIP(hipMemset(p, byte, bytes));
+    LPVS_HIP(hipDeviceSynchronize());
+    return LPVS_OK;
+}
+
 int32_t DevBuf::alloc(size_t nbytes) {
     release();
-    if (nbytes == 0) nbytes = 16;
-    nbytes = (nbytes + 255) & ~(size_t)255;
+    nbytes = pool_round(nbytes);
+    const int fill = pool_fill_parse(experiment_env("LPVS_POOL_FILL"));
     int d = 0;
     (void)hipGetDevice(&d);
     dev = d;
     // the cache keys blocks by their true size, so a reused block may be up to 25 % larger than asked for
     if (d >= 0 && d < 16) {
-        std::lock_guard<std::mutex> lk(pool().m);
+        std::unique_lock<std::mutex> lk(pool().m);
         auto &fl = pool().free_[d];
-        auto it = fl.lower_bound(nbytes);
-        if (it != fl.end() && it->first <= nbytes + nbytes / 4 + (1 << 20)) {
+        auto it = pool_best_fit(fl, nbytes);
+        if (it != fl.end()) {
             p = it->second; bytes = it->first;
             pool().cached[d] -= it->first;
             fl.erase(it);
-            return LPVS_OK;
+            lk.unlock();
+            return fill >= 0 ? pool_fill(p, bytes, fill) : LPVS_OK;
         }
     }
+    if (fill >= 0) nbytes += kPoolFillSlack;
     hipError_t e = hipMalloc(&p, nbytes);
     if (e == hipErrorOutOfMemory) {   // give the cache back to the driver and retry once
         (void)hipGetLastError();
@@ -181,7 +195,7 @@ int32_t DevBuf::alloc(size_t nbytes) {
         return e == hipErrorOutOfMemory ? LPVS_ENOMEM : LPVS_EDEVICE;
     }
     bytes = nbytes;
-    return LPVS_OK;
+    return fill >= 0 ? pool_fill(p, bytes, fill) : LPVS_OK;
 }
 void DevBuf::release() {
     if (p) {
@@ -3096,7 +3110,9 @@ struct WinEngine {
             // tile formats and the per-matrix max|M| live behind the 6-byte slots of the Mp buffer (sized for doubles)
             const bool mixed = storage_opt != LPVS_STORAGE_SPLIT;
             const PackedLayout lay = packed_layout(np, 6, (size_t)bw);
-            if (mixed && ns == 1 && lay.bytes <= Mp.bytes) {
+            // (no test of the room: the 6-byte layout with its format bytes and max|M| is smaller than the 8-byte elements allocate() asks
+            // for at every np >= 128 -- and a block's TRUE size, which a reused block has more of than a fresh one, must not choose the storage)
+            if (mixed && ns == 1) {
                 unsigned char *types = mp_tile_types(Mp, np, (size_t)bw);
                 LPVS_TRY(launch_pack_tiles_mixed_batch(M.as<double>(), np, nb_, Mp.as<unsigned char>(), types,
                                                        reinterpret_cast<unsigned long long *>(Mp.as<unsigned char>() + lay.absmax_off), s,

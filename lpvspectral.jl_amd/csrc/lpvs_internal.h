@@ -18,6 +18,7 @@
 #include "lomb_terms_plan.h"
 #include "wwz_plan.h"
 #include "bls_plan.h"
+#include "pool_plan.h"
 
 namespace lpvs {
 
@@ -27,7 +28,7 @@ namespace lpvs {
 // ones that change no result (LPVS_POOL_GIB, LPVS_BATCH_PANEL_GIB, LPVS_TRACE, LPVS_NO_GRAPH, LPVS_WINDOW_MATVEC_TIMING, LPVS_MULTI_FORCE_RCCL,
 // LPVS_MULTI_ALLOW_SHARED_DEVICE): plain getenv.  (3) EXPERIMENT knobs -- schedules and kernel variants kept for the A/B measurements the
 // design documents quote, and the numerics studies (LPVS_FIX_BITS, LPVS_NIB_*, LPVS_TILE_ORDER, LPVS_NUFFT_SPREAD, LPVS_XB_REFINE, LPVS_XUPDATE_CORRECTION schedules, LPVS_PHASE,
-// LPVS_FACTOR*, LPVS_PIVOT*, LPVS_KW, LPVS_LOOKAHEAD, LPVS_CHAIN, LPVS_BAND_TILE, LPVS_RU_STAGE, LPVS_MULTI_*): read through experiment_env, which
+// LPVS_FACTOR*, LPVS_PIVOT*, LPVS_KW, LPVS_LOOKAHEAD, LPVS_CHAIN, LPVS_BAND_TILE, LPVS_RU_STAGE, LPVS_MULTI_*, LPVS_POOL_FILL): read through experiment_env, which
 // answers nullptr unless the process ALSO has LPVS_EXPERIMENTS=1 (the test-suite and tools/ set it; a production process that inherits a
 // stray LPVS_FIX_BITS does not change its results), and is compiled out altogether with -DLPVS_NO_EXPERIMENTS.
 inline const char *experiment_env(const char *name) {
