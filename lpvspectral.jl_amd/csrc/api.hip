@@ -235,45 +235,12 @@ int32_t copy_from_device(void *dst, const void *src_dev, size_t bytes, hipStream
     return LPVS_OK;
 }
 
-// A read-only argument made device-resident: aliases the caller's pointer when it already lives on the CURRENT device (the one the
-// handle computes on); memory of another device is staged like host memory (a peer copy) -- kernels never dereference it.
-struct DevArg {
-    DevBuf own;
-    const double *p = nullptr;
-    int32_t set(const double *src, int64_t count, hipStream_t s) {
-        const int owner = device_of_ptr(src);
-        int cur = -1;
-        if (owner >= 0) LPVS_HIP(hipGetDevice(&cur));
-        if (owner >= 0 && owner == cur) { p = src; return LPVS_OK; }
-        LPVS_TRY(own.alloc(sizeof(double) * (size_t)count));
-        if (owner >= 0) {
-            LPVS_HIP(hipMemcpyPeerAsync(own.p, cur, src, owner, sizeof(double) * (size_t)count, s));
-            LPVS_HIP(hipStreamSynchronize(s));
-        } else
-        LPVS_TRY(copy_to_device(own.p, src, sizeof(double) * (size_t)count, s));
-        p = own.as<double>();
-        return LPVS_OK;
-    }
-};
-// An output argument: device staging buffer when the caller's pointer is host memory.
-struct DevOut {
-    DevBuf own;
-    double *p = nullptr;
-    double *user = nullptr;
-    size_t bytes = 0;
-    int32_t set(double *dst, int64_t count) {
-        user = dst; bytes = sizeof(double) * (size_t)count;
-        if (is_device_ptr(dst)) { p = dst; return LPVS_OK; }
-        LPVS_TRY(own.alloc(bytes));
-        p = own.as<double>();
-        return LPVS_OK;
-    }
-    int32_t finish(hipStream_t s) {
-        if (p != user) return copy_from_device(user, p, bytes, s);
-        LPVS_HIP(hipStreamSynchronize(s));
-        return LPVS_OK;
-    }
-};
+// The entry points that take no device compute on the calling thread's current one: read-only arguments are staged to it
+// (Staged, lpvs_internal.h: memory of another device is copied like host memory -- kernels never dereference it).
+static int32_t current_device(int *dev) {
+    LPVS_HIP(hipGetDevice(dev));
+    return LPVS_OK;
+}
 
 static int32_t fetch_host(std::vector<double> &h, const double *src, int64_t count) {
     h.resize((size_t)count);
@@ -826,8 +793,8 @@ template <class Fill>
 static int32_t create_panel_problem(lpvs_problem *h, const double *y, const double *W, int64_t N, Fill fill) {
     hipStream_t s = h->stream;
     const GramPlan pl = make_gram_plan(h->n, N);
-    DevArg dy;
-    LPVS_TRY(dy.set(y, N, s));
+    Staged<double> dy;
+    LPVS_TRY(dy.set(y, N, h->device, s));
     LPVS_TRY(open_problem(h, 1, ZeroGram::all));
     PanelBufs t;
     DrainOnExit drain(s);
@@ -861,10 +828,10 @@ static int32_t fourier_slots(const double *f, int64_t Nf, const double *t_dev, i
 static int32_t create_fourier_structured(lpvs_problem *h, const double *y, const double *t_dev, const double *W, const ApSlots &sl) {
     hipStream_t s = h->stream;
     const int64_t N = h->N, Nf = h->Nf; const int zf = (int)h->zerofreq;
-    DevArg dy, dW;
-    LPVS_TRY(dy.set(y, N, s));
-    if (W) LPVS_TRY(dW.set(W, N, s));
-    const double *Wd = W ? dW.p : nullptr;
+    Staged<double> dy, dW;
+    LPVS_TRY(dy.set(y, N, h->device, s));
+    LPVS_TRY(dW.set(W, N, h->device, s));
+    const double *Wd = dW.p;
     LPVS_TRY(open_problem(h, 1, ZeroGram::all));
     ApSlotsDev sd; DevBuf part, tab, tabb;
     DrainOnExit drain(s);
@@ -955,8 +922,10 @@ int32_t lpvs_fourier_regressor_f64(const double *t, int64_t N, const double *f, 
     if (lpvs_device_count() == 0) { set_error("no HIP device visible (the gfx950 path has no CPU fallback)"); return LPVS_EDEVICE; }
     hipStream_t s = nullptr;
     const int64_t nreg = fourier_regressors(Nf, z != 0);
-    DevArg dt, df; DevOut dA;
-    LPVS_TRY(dt.set(t, N, s)); LPVS_TRY(df.set(f, Nf, s)); LPVS_TRY(dA.set(A_out, N * nreg));
+    int dev = 0;
+    LPVS_TRY(current_device(&dev));
+    Staged<double> dt, df; DevOut dA;
+    LPVS_TRY(dt.set(t, N, dev, s)); LPVS_TRY(df.set(f, Nf, dev, s)); LPVS_TRY(dA.set(A_out, N * nreg));
     LPVS_TRY(launch_fourier_regressor_colmajor(dt.p, N, df.p, Nf, (int)z, dA.p, s));
     return dA.finish(s);
 }
@@ -966,7 +935,9 @@ int32_t lpvs_basis_activation_f64(const double *V, int64_t N, int64_t Nv, int32_
     if (N <= 0 || Nv <= 0) { set_error("N and Nv must be positive"); return LPVS_EARGUMENT; }
     hipStream_t s = nullptr;
     const int64_t nb = coulomb ? 2 * Nv : Nv;
-    DevArg dV; LPVS_TRY(dV.set(V, N, s));
+    int dev = 0;
+    LPVS_TRY(current_device(&dev));
+    Staged<double> dV; LPVS_TRY(dV.set(V, N, dev, s));
     double lo, hi, am, gamma; std::vector<double> vc;
     LPVS_TRY(device_minmax(dV.p, N, &lo, &hi, &am, s));
     basis_centers(lo, hi, am, Nv, coulomb, vc, &gamma);
@@ -1013,8 +984,10 @@ int32_t lpvs_lpv_regressor_f64(const double *X, const double *V, int64_t N, cons
     if (N <= 0 || Nf <= 0 || Nv <= 0) { set_error("N, Nf and Nv must be positive"); return LPVS_EARGUMENT; }
     hipStream_t s = nullptr;
     const int64_t nb = coulomb ? 2 * Nv : Nv;
-    DevArg dX, dV, dw; DevOut dP;
-    LPVS_TRY(dX.set(X, N, s)); LPVS_TRY(dV.set(V, N, s)); LPVS_TRY(dw.set(w, Nf, s));
+    int dev = 0;
+    LPVS_TRY(current_device(&dev));
+    Staged<double> dX, dV, dw; DevOut dP;
+    LPVS_TRY(dX.set(X, N, dev, s)); LPVS_TRY(dV.set(V, N, dev, s)); LPVS_TRY(dw.set(w, Nf, dev, s));
     LPVS_TRY(dP.set(Phi_out, N * 2 * Nf * nb));
     DevBuf T, K; int64_t ldk;
     LPVS_TRY(build_lpv_tables(dX.p, dV.p, N, N, dw.p, Nf, Nv, normalize, coulomb, T, K, &ldk, s));
@@ -1028,7 +1001,7 @@ struct LpvJob {
     lpvs_problem *h = nullptr;
     int64_t ns = 0, N = 0, Nf = 0, Nv = 0, nb = 0; int normalize = 0, coulomb = 0;
     const double *ranges = nullptr;   // (optional) {min V, max V, max|V|, max|X|} over ALL rows of the signal when (y, X, V) is only a row shard of it
-    DevArg dy, dX, dV, dw;
+    Staged<double> dy, dX, dV, dw;
     double xam = 0;                   // max|X| (over all rows of the signal)
     ApSlots sl;
     GramForm form = GramForm::kr;
@@ -1239,7 +1212,7 @@ static int32_t create_lpv_impl(const double *y, int64_t ns, const double *X, con
     LpvJob J;
     J.h = h; J.ns = ns; J.N = N; J.Nf = Nf; J.Nv = Nv; J.nb = coulomb ? 2 * Nv : Nv; J.normalize = normalize; J.coulomb = coulomb; J.ranges = ranges;
     h->kind = 1; h->N = N; h->Nf = Nf; h->nb = J.nb; h->n = 2 * Nf * J.nb;
-    LPVS_TRY(J.dy.set(y, N * ns, s)); LPVS_TRY(J.dX.set(X, N, s)); LPVS_TRY(J.dV.set(V, N, s)); LPVS_TRY(J.dw.set(w, Nf, s));
+    LPVS_TRY(J.dy.set(y, N * ns, device, s)); LPVS_TRY(J.dX.set(X, N, device, s)); LPVS_TRY(J.dV.set(V, N, device, s)); LPVS_TRY(J.dw.set(w, Nf, device, s));
     LPVS_TRY(lpv_choose_form(J, w));
     LPVS_TRY(is_structured(J.form) ? lpv_structured(J) : lpv_dense(J));
     return guard.release(out);
@@ -1260,8 +1233,10 @@ int32_t lpvs_lpv_ranges_f64(const double *X, const double *V, int64_t N, double 
     if (!X || !V || !out4 || N <= 0) { set_error("NULL argument or N <= 0"); return LPVS_EARGUMENT; }
     if (lpvs_device_count() == 0) { set_error("no HIP device visible (the gfx950 path has no CPU fallback)"); return LPVS_EDEVICE; }
     hipStream_t s = nullptr;
-    DevArg dX, dV;
-    LPVS_TRY(dX.set(X, N, s)); LPVS_TRY(dV.set(V, N, s));
+    int dev = 0;
+    LPVS_TRY(current_device(&dev));
+    Staged<double> dX, dV;
+    LPVS_TRY(dX.set(X, N, dev, s)); LPVS_TRY(dV.set(V, N, dev, s));
     double xlo, xhi;
     LPVS_TRY(device_minmax(dV.p, N, &out4[0], &out4[1], &out4[2], s));
     LPVS_TRY(device_minmax(dX.p, N, &xlo, &xhi, &out4[3], s));
@@ -1288,13 +1263,13 @@ static int32_t eval_impl(const double *p_re, const double *p_im, int64_t nc, con
     hipStream_t s = nullptr;
     EvalEvents ev;
     for (auto &e : ev.e) LPVS_HIP(hipEventCreate(&e));
-    DevArg dX, dV, dy; DevOut dout;
+    Staged<double> dX, dV, dy; DevOut dout;
     DevBuf dvc, dw, dP, dtw, dgrid, dpart, dsums;
     DrainOnExit drain(s);
     LPVS_HIP(hipEventRecord(ev.e[0], s));
-    LPVS_TRY(dX.set(X, M, s));
-    if (V) LPVS_TRY(dV.set(V, M, s));
-    if (y) LPVS_TRY(dy.set(y, M, s));
+    LPVS_TRY(dX.set(X, M, device, s));
+    LPVS_TRY(dV.set(V, M, device, s));
+    LPVS_TRY(dy.set(y, M, device, s));
     LPVS_TRY(dout.set(out, M * nc));
     EvalGrid eg;
     if (path != kEvalPathDirect) {                   // the direct path does not look at the grid
@@ -1405,836 +1380,7 @@ int32_t lpvs_lpv_eval_f64(const double *p_re, const double *p_im, int64_t nc, co
 }
 
 int32_t lpvs_eval_last_timing(double *out, int32_t n) {
-    if (!out || n < 0) { set_error("NULL argument"); return LPVS_EARGUMENT; }
-    for (int32_t k = 0; k < n && k < 10; ++k) out[k] = g_eval_timing[k];
-    return LPVS_OK;
-}
-
-// ---- Lomb-Scargle periodogram (lomb.hip; the decisions: lomb_plan.h) --------------------------------------------------------------------
-// what lpvs_lombscargle_last_timing reports of the calling thread's last call: [0] path taken (1 direct, 2 transforms), [1], [2] blocks of
-// family 1 / family 2 (0: direct), [3] fine grid (0: direct), [4] degenerate frequencies, [5] slabs of the direct sums (0: transforms),
-// ms of [6] staging, the scan and the moments, [7] the sums, [8] the epilogue, [9] the copy-out, [10] total, [11] the first-order term ran
-static thread_local double g_lomb_timing[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-static int32_t lomb_impl(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const std::vector<double> &hf, bool fit_mean, bool center,
-                         bool psd, int32_t path, int32_t device, double *power, double *coef, double *sums_out) {
-    const int64_t Nf = (int64_t)hf.size(), nrow = 4 + 2 * ns;
-    if (lpvs_device_count() == 0) { set_error("no HIP device visible (the gfx950 path has no CPU fallback)"); return LPVS_EDEVICE; }
-    LPVS_HIP(hipSetDevice(device));
-    hipStream_t s = nullptr;
-    Events<5> ev;
-    for (auto &e : ev.e) LPVS_HIP(hipEventCreate(&e));
-    DevArg dt, dy, dW; DevOut dpower, dcoef;
-    DevBuf dw, dwy, dsmall, dpart, dsums, dfreq, dslab, dWt, dwork, dtab, deps;
-    DrainOnExit drain(s);
-    LPVS_HIP(hipEventRecord(ev.e[0], s));
-    LPVS_TRY(dt.set(t, N, s));
-    LPVS_TRY(dy.set(y, N * ns, s));
-    if (W) LPVS_TRY(dW.set(W, N, s));
-    LPVS_TRY(dpower.set(power, Nf * ns));
-    if (coef) LPVS_TRY(dcoef.set(coef, 3 * Nf * ns));
-    // small device record: [0] sum W, [1 .. ns] the weighted means, then Y_c, YY_c per signal (2 ns) and sum w y_c^2 of the signals as
-    // given (ns), then two ints (flags, degenerate count)
-    const size_t nsmall = (size_t)(1 + 4 * ns);
-    LPVS_TRY(dsmall.alloc(sizeof(double) * (nsmall + 1)));
-    double *sumW_dev = dsmall.as<double>(), *mean_dev = sumW_dev + 1, *mom_dev = mean_dev + ns;
-    int *flags_dev = reinterpret_cast<int *>(sumW_dev + nsmall), *ndeg_dev = flags_dev + 1;
-    const int64_t nsum = lomb_sum_slabs(N);
-    LPVS_TRY(dpart.alloc(sizeof(double) * (size_t)(3 * ns * nsum)));
-    LPVS_TRY(launch_lomb_scan(dt.p, dy.p, dW.p, N, ns, flags_dev, dpart.as<double>(), sumW_dev, s));
-    double sumW = 0; int flags = 0;
-    LPVS_TRY(copy_from_device(&sumW, sumW_dev, sizeof(double), s));
-    LPVS_TRY(copy_from_device(&flags, flags_dev, sizeof(int), s));
-    if (flags & 1) { set_error("lombscargle: t, y or W holds a value that is not finite"); return LPVS_EARGUMENT; }
-    if (flags & 2) { set_error("lombscargle: a weight is negative"); return LPVS_EARGUMENT; }
-    if (!(sumW > 0.0) || !std::isfinite(sumW)) { set_error("lombscargle: the weights sum to %g", sumW); return LPVS_EARGUMENT; }
-    LPVS_TRY(dw.alloc(sizeof(double) * (size_t)N));
-    LPVS_TRY(dwy.alloc(sizeof(double) * (size_t)(N * ns)));
-    LPVS_TRY(launch_lomb_moments(dy.p, dW.p, N, ns, sumW, center, dw.as<double>(), dwy.as<double>(), mean_dev, mom_dev, dpart.as<double>(), s));
-    // the path
-    LombGrid lg;
-    double tam = 0;
-    if (lomb_needs_admission(path, N, Nf)) {         // not when the call goes direct whatever the grid is
-        double tlo, thi;
-        LPVS_TRY(device_minmax(dt.p, N, &tlo, &thi, &tam, s));
-        lg = lomb_admit(hf, tam);
-    }
-    const int taken = lomb_choose_path(path, lg.ok, N, Nf);
-    if (taken == kLombPathRefused) {
-        if (path != kLombPathNufft) set_error("path must be 0 (auto), 1 (direct) or 2 (NUFFT), got %d", path);
-        else set_error("path = NUFFT but the frequency grid is not an arithmetic progression up to rounding (max|eps| = %.3g)", lg.emax);
-        return LPVS_EARGUMENT;
-    }
-    LPVS_TRY(dsums.alloc(sizeof(double) * (size_t)(nrow * Nf)));
-    LPVS_HIP(hipEventRecord(ev.e[1], s));
-    int64_t nblocks = 0, nslab = 0; int nf1 = 0; bool twin = false;
-    if (taken == kLombPathDirect) {
-        const LombTiling tl = lomb_tiling(N, Nf, ns);
-        nslab = tl.nslab;
-        LPVS_TRY(dfreq.alloc(sizeof(double) * (size_t)Nf));
-        LPVS_TRY(copy_to_device(dfreq.p, hf.data(), sizeof(double) * (size_t)Nf, s));
-        LPVS_TRY(dslab.alloc(sizeof(double) * (size_t)(tl.nslab * nrow * Nf)));
-        LPVS_TRY(launch_lomb_direct(dt.p, dw.as<double>(), dwy.as<double>(), N, ns, dfreq.as<double>(), Nf, tl, dslab.as<double>(), dsums.as<double>(), s));
-    } else {
-        const char *knob = experiment_env("LPVS_LOMB_BLOCK");
-        const int L = lomb_block_len(knob ? atoll(knob) : 0);
-        const std::vector<LombBlock> blocks = lomb_blocks(hf, L);
-        const std::vector<double> heps = lomb_block_residuals(hf, lg, L);
-        for (double e : heps) twin = twin || e != 0.0;
-        nblocks = (int64_t)blocks.size();
-        const int nf = lomb_fine_grid(Nf, L), Lmax = (int)(Nf < L ? Nf : L);
-        nf1 = nf;
-        const int gmax = (int)(ns < kLombGroupSignals ? ns : kLombGroupSignals), nqmax = lomb_weight_vectors(1, gmax, true);
-        LPVS_TRY(deps.alloc(sizeof(double) * (size_t)Nf));
-        LPVS_TRY(copy_to_device(deps.p, heps.data(), sizeof(double) * (size_t)Nf, s));
-        LPVS_TRY(dWt.alloc(sizeof(double) * (size_t)N * (size_t)nqmax));
-        LPVS_TRY(dtab.alloc(sizeof(double) * 4 * (size_t)Lmax * (size_t)nqmax));
-        LPVS_TRY(dwork.alloc(nufft_work_bytes(N, Lmax, nqmax)));           // (its fine grid is nf: that of the longest block)
-        // family 1: step D, the weights w and w y_c of a group of signals; family 2: step 2D, w alone.  One set of sample coordinates per family.
-        for (int family = 1; family <= 2; ++family) {
-            const double w_hi = family == 1 ? lg.w1_hi : lg.w2_hi, w_lo = family == 1 ? lg.w1_lo : lg.w2_lo, fscale = family == 1 ? 1.0 : 2.0;
-            bool have_coords = false;
-            const int64_t ngroups = family == 1 ? lomb_signal_groups(ns) : 1;
-            for (int64_t grp = 0; grp < ngroups; ++grp) {
-                const int c0 = (int)(grp * kLombGroupSignals);
-                const int g = family == 1 ? (int)(ns - c0 < kLombGroupSignals ? ns - c0 : kLombGroupSignals) : 0;
-                for (const LombBlock &b : blocks) {
-                    const int nq = lomb_weight_vectors(family, g, b.prephase), nre = 1 + g;
-                    LPVS_TRY(launch_lomb_prephase(dt.p, dw.as<double>(), dwy.as<double>(), N, c0, g, fscale * b.base, b.prephase, dWt.as<double>(), s));
-                    const int32_t rc = launch_nufft_tab(dt.p, nullptr, N, tam, dWt.as<double>(), nq, nq, w_hi, w_lo, 0, b.count, nf, have_coords, dwork.p,
-                                                        dtab.as<double>(), s);
-                    if (rc == kNufftNonFinite) { set_error("lombscargle: a weight vector of the transform is not finite"); return LPVS_ENUMERIC; }
-                    LPVS_TRY(rc);
-                    have_coords = true;
-                    LPVS_TRY(launch_lomb_combine(dtab.as<double>(), nq, nre, b.prephase, b.count, b.k0, Nf, deps.as<double>(), fscale, family == 1 ? -1 : 2, c0,
-                                                 dsums.as<double>(), s));
-                }
-            }
-        }
-    }
-    LPVS_HIP(hipEventRecord(ev.e[2], s));
-    LPVS_TRY(launch_lomb_epilogue(dsums.as<double>(), Nf, ns, mom_dev, mean_dev, fit_mean, center, psd, N, dpower.p, coef ? dcoef.p : nullptr, ndeg_dev, s));
-    LPVS_HIP(hipEventRecord(ev.e[3], s));
-    int ndeg = 0;
-    LPVS_TRY(copy_from_device(&ndeg, ndeg_dev, sizeof(int), s));
-    if (sums_out) {
-        LPVS_TRY(copy_from_device(sums_out, dsums.p, sizeof(double) * (size_t)(nrow * Nf), s));
-        LPVS_TRY(copy_from_device(sums_out + nrow * Nf, mom_dev, sizeof(double) * (size_t)(2 * ns), s));
-        LPVS_TRY(copy_from_device(sums_out + nrow * Nf + 2 * ns, mean_dev, sizeof(double) * (size_t)ns, s));
-    }
-    LPVS_TRY(dpower.finish(s));
-    if (coef) LPVS_TRY(dcoef.finish(s));
-    LPVS_HIP(hipEventRecord(ev.e[4], s));
-    LPVS_HIP(hipStreamSynchronize(s));
-    float ms[4] = {0, 0, 0, 0}, total = 0;
-    for (int i = 0; i < 4; ++i) LPVS_HIP(hipEventElapsedTime(&ms[i], ev.e[i], ev.e[i + 1]));
-    LPVS_HIP(hipEventElapsedTime(&total, ev.e[0], ev.e[4]));
-    const bool nu = taken == kLombPathNufft;
-    g_lomb_timing[0] = taken; g_lomb_timing[1] = (double)nblocks; g_lomb_timing[2] = (double)nblocks; g_lomb_timing[3] = nu ? nf1 : 0;
-    g_lomb_timing[4] = ndeg; g_lomb_timing[5] = (double)nslab;
-    g_lomb_timing[6] = ms[0]; g_lomb_timing[7] = ms[1]; g_lomb_timing[8] = ms[2]; g_lomb_timing[9] = ms[3]; g_lomb_timing[10] = total;
-    g_lomb_timing[11] = nu && twin ? 1 : 0;
-    return LPVS_OK;
-}
-
-int32_t lpvs_lombscargle_f64(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const double *f, int64_t Nf, int32_t fit_mean,
-                             int32_t center_data, int32_t normalization, int32_t path, int32_t device, double *power, double *coef, double *sums) {
-    try {
-        if (!y || !t || !f || !power) { set_error("NULL argument"); return LPVS_EARGUMENT; }
-        if (N <= 0 || Nf <= 0 || ns <= 0 || ns > 65535) { set_error("need N > 0, Nf > 0 and 1 <= ns <= 65535 (N = %lld, Nf = %lld, ns = %lld)", (long long)N, (long long)Nf, (long long)ns); return LPVS_EARGUMENT; }
-        if (Nf > ((int64_t)1 << 24)) { set_error("%lld frequencies are too many", (long long)Nf); return LPVS_EUNSUPPORTED; }
-        if (path < kLombPathAuto || path > kLombPathNufft) { set_error("path must be 0 (auto), 1 (direct) or 2 (NUFFT), got %d", path); return LPVS_EARGUMENT; }
-        if (normalization != LPVS_LOMB_STANDARD && normalization != LPVS_LOMB_PSD) { set_error("normalization must be 0 (standard) or 1 (psd), got %d", normalization); return LPVS_EARGUMENT; }
-        if (is_device_ptr(f) || (sums && is_device_ptr(sums))) { set_error("lombscargle: f and sums are host memory"); return LPVS_EARGUMENT; }
-        std::vector<double> hf(f, f + Nf);
-        for (double v : hf)
-            if (!std::isfinite(v)) { set_error("lombscargle: a frequency is not finite"); return LPVS_EARGUMENT; }
-        return lomb_impl(y, ns, t, N, W, hf, fit_mean != 0, center_data != 0, normalization == LPVS_LOMB_PSD, path, device, power, coef, sums);
-    } catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
-}
-
-int32_t lpvs_lombscargle_last_timing(double *out, int32_t n) {
-    if (!out || n < 0) { set_error("NULL argument"); return LPVS_EARGUMENT; }
-    for (int32_t k = 0; k < n && k < 12; ++k) out[k] = g_lomb_timing[k];
-    return LPVS_OK;
-}
-
-// ---- Lomb-Scargle with several harmonics per frequency (lomb_terms.hip; the decisions: lomb_terms_plan.h) ----------------------------------
-// what lpvs_lombscargle_terms_last_timing reports of the calling thread's last call: [0] nterms, [1] signals per thread, [2] slabs,
-// [3] degenerate frequencies, ms of [4] staging, the scan and the moments, [5] the sums, [6] the epilogue, [7] the copy-out, [8] total,
-// [9] accumulators per thread
-static thread_local double g_lomb_terms_timing[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-static int32_t lomb_terms_impl(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const std::vector<double> &hf, const LombTermsPlan &plan,
-                               bool fit_mean, bool center, bool psd, int32_t device, double *power, double *coef, double *sums_out) {
-    const int64_t Nf = (int64_t)hf.size(), nrow = plan.rows;
-    const int K = plan.K;
-    if (lpvs_device_count() == 0) { set_error("no HIP device visible (the gfx950 path has no CPU fallback)"); return LPVS_EDEVICE; }
-    LPVS_HIP(hipSetDevice(device));
-    hipStream_t s = nullptr;
-    Events<5> ev;
-    for (auto &e : ev.e) LPVS_HIP(hipEventCreate(&e));
-    DevArg dt, dy, dW; DevOut dpower, dcoef;
-    DevBuf dw, dwy, dsmall, dpart, dsums, dfreq, dslab;
-    DrainOnExit drain(s);
-    LPVS_HIP(hipEventRecord(ev.e[0], s));
-    LPVS_TRY(dt.set(t, N, s));
-    LPVS_TRY(dy.set(y, N * ns, s));
-    if (W) LPVS_TRY(dW.set(W, N, s));
-    LPVS_TRY(dpower.set(power, Nf * ns));
-    if (coef) LPVS_TRY(dcoef.set(coef, (2 * K + 1) * Nf * ns));
-    // small device record, as lomb_impl's: [0] sum W, [1 .. ns] the weighted means, then Y_c, YY_c per signal (2 ns) and sum w y_c^2 of the
-    // signals as given (ns), then two ints (flags, degenerate count)
-    const size_t nsmall = (size_t)(1 + 4 * ns);
-    LPVS_TRY(dsmall.alloc(sizeof(double) * (nsmall + 1)));
-    double *sumW_dev = dsmall.as<double>(), *mean_dev = sumW_dev + 1, *mom_dev = mean_dev + ns;
-    int *flags_dev = reinterpret_cast<int *>(sumW_dev + nsmall), *ndeg_dev = flags_dev + 1;
-    const int64_t nsum = lomb_sum_slabs(N);
-    LPVS_TRY(dpart.alloc(sizeof(double) * (size_t)(3 * ns * nsum)));
-    LPVS_TRY(launch_lomb_scan(dt.p, dy.p, dW.p, N, ns, flags_dev, dpart.as<double>(), sumW_dev, s));
-    double sumW = 0; int flags = 0;
-    LPVS_TRY(copy_from_device(&sumW, sumW_dev, sizeof(double), s));
-    LPVS_TRY(copy_from_device(&flags, flags_dev, sizeof(int), s));
-    if (flags & 1) { set_error("lombscargle: t, y or W holds a value that is not finite"); return LPVS_EARGUMENT; }
-    if (flags & 2) { set_error("lombscargle: a weight is negative"); return LPVS_EARGUMENT; }
-    if (!(sumW > 0.0) || !std::isfinite(sumW)) { set_error("lombscargle: the weights sum to %g", sumW); return LPVS_EARGUMENT; }
-    LPVS_TRY(dw.alloc(sizeof(double) * (size_t)N));
-    LPVS_TRY(dwy.alloc(sizeof(double) * (size_t)(N * ns)));
-    LPVS_TRY(launch_lomb_moments(dy.p, dW.p, N, ns, sumW, center, dw.as<double>(), dwy.as<double>(), mean_dev, mom_dev, dpart.as<double>(), s));
-    LPVS_TRY(dsums.alloc(sizeof(double) * (size_t)(nrow * Nf)));
-    LPVS_TRY(dfreq.alloc(sizeof(double) * (size_t)Nf));
-    LPVS_TRY(copy_to_device(dfreq.p, hf.data(), sizeof(double) * (size_t)Nf, s));
-    LPVS_TRY(dslab.alloc(sizeof(double) * (size_t)plan.part_doubles));
-    LPVS_HIP(hipEventRecord(ev.e[1], s));
-    LPVS_TRY(launch_lomb_terms_sums(dt.p, dw.as<double>(), dwy.as<double>(), N, ns, dfreq.as<double>(), Nf, plan, dslab.as<double>(), dsums.as<double>(), s));
-    LPVS_HIP(hipEventRecord(ev.e[2], s));
-    LPVS_TRY(launch_lomb_terms_epilogue(K, dsums.as<double>(), Nf, ns, mom_dev, mean_dev, fit_mean, center, psd, N, dpower.p, coef ? dcoef.p : nullptr, ndeg_dev, s));
-    LPVS_HIP(hipEventRecord(ev.e[3], s));
-    int ndeg = 0;
-    LPVS_TRY(copy_from_device(&ndeg, ndeg_dev, sizeof(int), s));
-    if (sums_out) {
-        LPVS_TRY(copy_from_device(sums_out, dsums.p, sizeof(double) * (size_t)(nrow * Nf), s));
-        LPVS_TRY(copy_from_device(sums_out + nrow * Nf, mom_dev, sizeof(double) * (size_t)(2 * ns), s));
-        LPVS_TRY(copy_from_device(sums_out + nrow * Nf + 2 * ns, mean_dev, sizeof(double) * (size_t)ns, s));
-    }
-    LPVS_TRY(dpower.finish(s));
-    if (coef) LPVS_TRY(dcoef.finish(s));
-    LPVS_HIP(hipEventRecord(ev.e[4], s));
-    LPVS_HIP(hipStreamSynchronize(s));
-    float ms[4] = {0, 0, 0, 0}, total = 0;
-    for (int i = 0; i < 4; ++i) LPVS_HIP(hipEventElapsedTime(&ms[i], ev.e[i], ev.e[i + 1]));
-    LPVS_HIP(hipEventElapsedTime(&total, ev.e[0], ev.e[4]));
-    double *g = g_lomb_terms_timing;
-    g[0] = K; g[1] = plan.ts; g[2] = (double)plan.nslab; g[3] = ndeg; g[4] = ms[0]; g[5] = ms[1]; g[6] = ms[2]; g[7] = ms[3]; g[8] = total; g[9] = plan.acc;
-    return LPVS_OK;
-}
-
-int32_t lpvs_lombscargle_terms_f64(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const double *f, int64_t Nf, int32_t nterms,
-                                   int32_t fit_mean, int32_t center_data, int32_t normalization, int32_t device, double *power_out, double *coef_out,
-                                   double *sums_out) {
-    try {
-        if (!y || !t || !f || !power_out) { set_error("NULL argument"); return LPVS_EARGUMENT; }
-        const LombTermsPlan plan = lomb_terms_plan(N, Nf, ns, nterms);
-        if (plan.status != kLombTermsOk) { set_error("%s", plan.why.c_str()); return plan.status == kLombTermsArgument ? LPVS_EARGUMENT : LPVS_EUNSUPPORTED; }
-        if (normalization != LPVS_LOMB_STANDARD && normalization != LPVS_LOMB_PSD) { set_error("normalization must be 0 (standard) or 1 (psd), got %d", normalization); return LPVS_EARGUMENT; }
-        if (is_device_ptr(f) || (sums_out && is_device_ptr(sums_out))) { set_error("lombscargle: f and sums are host memory"); return LPVS_EARGUMENT; }
-        std::vector<double> hf(f, f + Nf);
-        for (double v : hf)
-            if (!std::isfinite(v)) { set_error("lombscargle: a frequency is not finite"); return LPVS_EARGUMENT; }
-        return lomb_terms_impl(y, ns, t, N, W, hf, plan, fit_mean != 0, center_data != 0, normalization == LPVS_LOMB_PSD, device, power_out, coef_out, sums_out);
-    } catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
-}
-
-int32_t lpvs_lombscargle_terms_last_timing(double *out, int32_t n) {
-    if (!out || n < 0) { set_error("NULL argument"); return LPVS_EARGUMENT; }
-    for (int32_t k = 0; k < n && k < 10; ++k) out[k] = g_lomb_terms_timing[k];
-    return LPVS_OK;
-}
-
-// ---- windowed Lomb-Scargle (lomb.hip; the work list: lomb_plan.h lomb_window_plan) ----------------------------------------------------------
-// what lpvs_lombscargle_windows_last_timing reports: [0] windows, [1] empty windows, [2] work items, [3] slab length, [4] degenerate
-// (window, frequency) pairs, ms of [5] staging, the scan and the moments, [6] the sums, [7] the epilogue and the average, [8] the copy-out, [9] total
-static thread_local double g_lomb_windows_timing[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-static int32_t lomb_windows_impl(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const std::vector<double> &hf,
-                                 const std::vector<int64_t> &starts, const std::vector<int64_t> &counts, const double *lo, const double *hi, int taper,
-                                 bool fit_mean, bool center, bool psd, bool average, int32_t device, double *power, double *coef, int32_t *empty_out) {
-    const int64_t Nf = (int64_t)hf.size(), nrow = 4 + 2 * ns, nwin = (int64_t)counts.size();
-    const LombWindowPlan plan = lomb_window_plan(counts);
-    if (!plan.ok) { set_error("%s", plan.why.c_str()); return LPVS_EUNSUPPORTED; }
-    const int64_t nitems = (int64_t)plan.items.size();
-    if (!lomb_windows_fit(nitems, nwin, Nf, ns)) {
-        set_error("lombscargle: %lld window slabs, %lld frequencies and %lld signals are more than one call takes", (long long)nitems, (long long)Nf, (long long)ns);
-        return LPVS_EUNSUPPORTED;
-    }
-    const LombTiling tl = lomb_windows_tiling(Nf, ns);
-    if (lpvs_device_count() == 0) { set_error("no HIP device visible (the gfx950 path has no CPU fallback)"); return LPVS_EDEVICE; }
-    LPVS_HIP(hipSetDevice(device));
-    hipStream_t s = nullptr;
-    Events<5> ev;
-    for (auto &e : ev.e) LPVS_HIP(hipEventCreate(&e));
-    DevArg dt, dy, dW; DevOut dpower, dcoef;
-    DevBuf dsmall, dscan, ditems, dwin, dlohi, dmom, dpart, dsums, dfreq, dcols, dempty;
-    DrainOnExit drain(s);
-    LPVS_HIP(hipEventRecord(ev.e[0], s));
-    LPVS_TRY(dt.set(t, N, s));
-    LPVS_TRY(dy.set(y, N * ns, s));
-    if (W) LPVS_TRY(dW.set(W, N, s));
-    const int64_t ncols = Nf * nwin * ns;
-    LPVS_TRY(dpower.set(power, average ? Nf * ns : ncols));
-    if (coef) LPVS_TRY(dcoef.set(coef, 3 * ncols));
-    // the record is held to g4's rules as a whole: a non-finite t, y or W, a negative weight (the scan's sum of W is not used)
-    LPVS_TRY(dsmall.alloc(sizeof(double) * 3));
-    double *sumW_dev = dsmall.as<double>();
-    unsigned long long *ndeg_dev = reinterpret_cast<unsigned long long *>(sumW_dev + 1);
-    int *flags_dev = reinterpret_cast<int *>(sumW_dev + 2);
-    LPVS_TRY(dscan.alloc(sizeof(double) * (size_t)lomb_sum_slabs(N)));
-    LPVS_TRY(launch_lomb_scan(dt.p, dy.p, dW.p, N, ns, flags_dev, dscan.as<double>(), sumW_dev, s));
-    // the work list and the windows: [starts | counts | offset] (int64), nslab (int32) behind them; [lo | hi]
-    LPVS_TRY(ditems.alloc(sizeof(LombWindowItem) * (size_t)nitems));
-    LPVS_TRY(copy_to_device(ditems.p, plan.items.data(), sizeof(LombWindowItem) * (size_t)nitems, s));
-    LPVS_TRY(dwin.alloc(sizeof(int64_t) * (size_t)(3 * nwin) + sizeof(int32_t) * (size_t)nwin));
-    int64_t *starts_dev = dwin.as<int64_t>(), *counts_dev = starts_dev + nwin, *offset_dev = counts_dev + nwin;
-    int32_t *nslab_dev = reinterpret_cast<int32_t *>(offset_dev + nwin);
-    LPVS_TRY(copy_to_device(starts_dev, starts.data(), sizeof(int64_t) * (size_t)nwin, s));
-    LPVS_TRY(copy_to_device(counts_dev, counts.data(), sizeof(int64_t) * (size_t)nwin, s));
-    LPVS_TRY(copy_to_device(offset_dev, plan.offset.data(), sizeof(int64_t) * (size_t)nwin, s));
-    LPVS_TRY(copy_to_device(nslab_dev, plan.nslab.data(), sizeof(int32_t) * (size_t)nwin, s));
-    LPVS_TRY(dlohi.alloc(sizeof(double) * (size_t)(2 * nwin)));
-    LPVS_TRY(copy_to_device(dlohi.p, lo, sizeof(double) * (size_t)nwin, s));
-    LPVS_TRY(copy_to_device(dlohi.as<double>() + nwin, hi, sizeof(double) * (size_t)nwin, s));
-    LombWindows A;
-    A.t = dt.p; A.y = dy.p; A.W = dW.p; A.N = N; A.nwin = nwin; A.nitems = nitems; A.ns = (int)ns; A.taper = taper;
-    A.items = ditems.as<LombWindowItem>(); A.starts = starts_dev; A.counts = counts_dev; A.offset = offset_dev; A.nslab = nslab_dev;
-    A.lo = dlohi.as<double>(); A.hi = A.lo + nwin;
-    // per window: [0] sum W g, [1 .. ns] the weighted means, then Y_c, YY_c per signal and sum w y_c^2 of the signals as given
-    LPVS_TRY(dmom.alloc(sizeof(double) * (size_t)(nwin * (1 + 4 * ns))));
-    double *swg_dev = dmom.as<double>(), *mean_dev = swg_dev + nwin, *mom_dev = mean_dev + nwin * ns;
-    LPVS_TRY(dpart.alloc(sizeof(double) * (size_t)(nitems * nrow * Nf > 3 * ns * nitems ? nitems * nrow * Nf : 3 * ns * nitems)));
-    LPVS_TRY(launch_lomb_windows_moments(A, center, swg_dev, mean_dev, mom_dev, dpart.as<double>(), s));
-    LPVS_TRY(dsums.alloc(sizeof(double) * (size_t)(nwin * nrow * Nf)));
-    LPVS_TRY(dfreq.alloc(sizeof(double) * (size_t)Nf));
-    LPVS_TRY(copy_to_device(dfreq.p, hf.data(), sizeof(double) * (size_t)Nf, s));
-    LPVS_HIP(hipEventRecord(ev.e[1], s));
-    LPVS_TRY(launch_lomb_windows_direct(A, dfreq.as<double>(), Nf, tl, swg_dev, center ? mean_dev : nullptr, dpart.as<double>(), dsums.as<double>(), s));
-    LPVS_HIP(hipEventRecord(ev.e[2], s));
-    LPVS_TRY(dempty.alloc(sizeof(int32_t) * (size_t)nwin));
-    double *cols = dpower.p;
-    if (average) { LPVS_TRY(dcols.alloc(sizeof(double) * (size_t)ncols)); cols = dcols.as<double>(); }
-    LPVS_TRY(launch_lomb_windows_epilogue(A, dsums.as<double>(), Nf, swg_dev, mom_dev, mean_dev, fit_mean, center, psd, cols, coef ? dcoef.p : nullptr,
-                                          dempty.as<int32_t>(), flags_dev, ndeg_dev, s));
-    if (average) LPVS_TRY(launch_lomb_windows_average(cols, Nf, nwin, ns, dempty.as<int32_t>(), dpower.p, s));
-    LPVS_HIP(hipEventRecord(ev.e[3], s));
-    int flags = 0; unsigned long long ndeg = 0;
-    LPVS_TRY(copy_from_device(&flags, flags_dev, sizeof(int), s));
-    if (flags & 1) { set_error("lombscargle: t, y or W holds a value that is not finite"); return LPVS_EARGUMENT; }
-    if (flags & 2) { set_error("lombscargle: a weight is negative"); return LPVS_EARGUMENT; }
-    if (flags & 4) { set_error("lombscargle: the weights of a window do not sum to a finite value"); return LPVS_EARGUMENT; }
-    LPVS_TRY(copy_from_device(&ndeg, ndeg_dev, sizeof(ndeg), s));
-    std::vector<int32_t> hempty((size_t)nwin);
-    LPVS_TRY(copy_from_device(hempty.data(), dempty.p, sizeof(int32_t) * (size_t)nwin, s));
-    int64_t nempty = 0;
-    for (int64_t w = 0; w < nwin; ++w) { nempty += hempty[(size_t)w]; if (empty_out) empty_out[w] = hempty[(size_t)w]; }
-    LPVS_TRY(dpower.finish(s));
-    if (coef) LPVS_TRY(dcoef.finish(s));
-    LPVS_HIP(hipEventRecord(ev.e[4], s));
-    LPVS_HIP(hipStreamSynchronize(s));
-    float ms[4] = {0, 0, 0, 0}, total = 0;
-    for (int i = 0; i < 4; ++i) LPVS_HIP(hipEventElapsedTime(&ms[i], ev.e[i], ev.e[i + 1]));
-    LPVS_HIP(hipEventElapsedTime(&total, ev.e[0], ev.e[4]));
-    double *g = g_lomb_windows_timing;
-    g[0] = (double)nwin; g[1] = (double)nempty; g[2] = (double)nitems; g[3] = (double)plan.slab_samples; g[4] = (double)ndeg;
-    g[5] = ms[0]; g[6] = ms[1]; g[7] = ms[2]; g[8] = ms[3]; g[9] = total;
-    return LPVS_OK;
-}
-
-int32_t lpvs_lombscargle_windows_f64(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const double *f, int64_t Nf, const int64_t *starts,
-                                     const int64_t *counts, const double *lo, const double *hi, int64_t nwin, int32_t taper, int32_t fit_mean, int32_t center_data,
-                                     int32_t normalization, int32_t average, int32_t device, double *power, double *coef, int32_t *empty_out) {
-    try {
-        if (!y || !t || !f || !power || !starts || !counts || !lo || !hi) { set_error("NULL argument"); return LPVS_EARGUMENT; }
-        if (N <= 0 || Nf <= 0 || ns <= 0 || ns > 65535 || nwin <= 0) {
-            set_error("need N > 0, Nf > 0, nwin > 0 and 1 <= ns <= 65535 (N = %lld, Nf = %lld, nwin = %lld, ns = %lld)", (long long)N, (long long)Nf, (long long)nwin, (long long)ns);
-            return LPVS_EARGUMENT;
-        }
-        if (Nf > ((int64_t)1 << 24)) { set_error("%lld frequencies are too many", (long long)Nf); return LPVS_EUNSUPPORTED; }
-        if (nwin > kLombMaxWindows) { set_error("lombscargle: %lld windows are more than 2^24", (long long)nwin); return LPVS_EUNSUPPORTED; }
-        if (taper != LPVS_TAPER_RECT && taper != LPVS_TAPER_HANN) { set_error("taper must be 0 (rect) or 1 (hann), got %d", taper); return LPVS_EARGUMENT; }
-        if (normalization != LPVS_LOMB_STANDARD && normalization != LPVS_LOMB_PSD) { set_error("normalization must be 0 (standard) or 1 (psd), got %d", normalization); return LPVS_EARGUMENT; }
-        if (average && coef) { set_error("lombscargle: the coefficients of an average over windows are not defined (coef with average)"); return LPVS_EARGUMENT; }
-        if (is_device_ptr(f) || is_device_ptr(starts) || is_device_ptr(counts) || is_device_ptr(lo) || is_device_ptr(hi) || (empty_out && is_device_ptr(empty_out))) {
-            set_error("lombscargle: f, starts, counts, lo, hi and empty_out are host memory"); return LPVS_EARGUMENT;
-        }
-        std::vector<double> hf(f, f + Nf);
-        for (double v : hf)
-            if (!std::isfinite(v)) { set_error("lombscargle: a frequency is not finite"); return LPVS_EARGUMENT; }
-        std::vector<int64_t> hs(starts, starts + nwin), hc(counts, counts + nwin);
-        for (int64_t w = 0; w < nwin; ++w) {
-            if (hs[(size_t)w] < 0 || hc[(size_t)w] < 0 || hs[(size_t)w] > N || hc[(size_t)w] > N - hs[(size_t)w]) {
-                set_error("lombscargle: window %lld covers the samples [%lld, %lld + %lld), outside [0, %lld]", (long long)w, (long long)hs[(size_t)w],
-                          (long long)hs[(size_t)w], (long long)hc[(size_t)w], (long long)N);
-                return LPVS_EARGUMENT;
-            }
-            if (!std::isfinite(lo[w]) || !std::isfinite(hi[w])) { set_error("lombscargle: the time interval of window %lld is not finite", (long long)w); return LPVS_EARGUMENT; }
-            if (hi[w] < lo[w]) { set_error("lombscargle: the time interval of window %lld ends before it begins", (long long)w); return LPVS_EARGUMENT; }
-        }
-        return lomb_windows_impl(y, ns, t, N, W, hf, hs, hc, lo, hi, taper, fit_mean != 0, center_data != 0, normalization == LPVS_LOMB_PSD, average != 0, device,
-                                 power, coef, empty_out);
-    } catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
-}
-
-int32_t lpvs_lombscargle_windows_last_timing(double *out, int32_t n) {
-    if (!out || n < 0) { set_error("NULL argument"); return LPVS_EARGUMENT; }
-    for (int32_t k = 0; k < n && k < 10; ++k) out[k] = g_lomb_windows_timing[k];
-    return LPVS_OK;
-}
-
-int32_t lpvs_time_windows_f64(const double *t, int64_t N, const double *lo, const double *hi, int64_t nwin, int32_t device, int64_t *starts_out,
-                              int64_t *counts_out) {
-    try {
-        if (!t || !lo || !hi || !starts_out || !counts_out) { set_error("NULL argument"); return LPVS_EARGUMENT; }
-        if (N <= 0 || nwin <= 0 || nwin > kLombMaxWindows) { set_error("time_windows: need N > 0 and 1 <= nwin <= 2^24 (N = %lld, nwin = %lld)", (long long)N, (long long)nwin); return LPVS_EARGUMENT; }
-        if (is_device_ptr(lo) || is_device_ptr(hi) || is_device_ptr(starts_out) || is_device_ptr(counts_out)) {
-            set_error("time_windows: lo, hi, starts_out and counts_out are host memory"); return LPVS_EARGUMENT;
-        }
-        for (int64_t w = 0; w < nwin; ++w)
-            if (!std::isfinite(lo[w]) || !std::isfinite(hi[w])) { set_error("time_windows: the time interval of window %lld is not finite", (long long)w); return LPVS_EARGUMENT; }
-        if (lpvs_device_count() == 0) { set_error("no HIP device visible (the gfx950 path has no CPU fallback)"); return LPVS_EDEVICE; }
-        LPVS_HIP(hipSetDevice(device));
-        hipStream_t s = nullptr;
-        DevArg dt; DevBuf dlohi, dedges, dflags;
-        DrainOnExit drain(s);
-        LPVS_TRY(dt.set(t, N, s));
-        LPVS_TRY(dlohi.alloc(sizeof(double) * (size_t)(2 * nwin)));
-        LPVS_TRY(copy_to_device(dlohi.p, lo, sizeof(double) * (size_t)nwin, s));
-        LPVS_TRY(copy_to_device(dlohi.as<double>() + nwin, hi, sizeof(double) * (size_t)nwin, s));
-        LPVS_TRY(dedges.alloc(sizeof(int64_t) * (size_t)(2 * nwin)));
-        LPVS_TRY(dflags.alloc(sizeof(int)));
-        LPVS_TRY(launch_lomb_time_windows(dt.p, N, dlohi.as<double>(), dlohi.as<double>() + nwin, nwin, dflags.as<int>(), dedges.as<int64_t>(), s));
-        int flags = 0;
-        LPVS_TRY(copy_from_device(&flags, dflags.p, sizeof(int), s));
-        if (flags & 1) { set_error("time_windows: t holds a value that is not finite"); return LPVS_EARGUMENT; }
-        if (flags & 8) { set_error("time_windows: t is not sorted (it decreases somewhere)"); return LPVS_EARGUMENT; }
-        std::vector<int64_t> edges((size_t)(2 * nwin));
-        LPVS_TRY(copy_from_device(edges.data(), dedges.p, sizeof(int64_t) * edges.size(), s));
-        for (int64_t w = 0; w < nwin; ++w) {
-            const int64_t a = edges[(size_t)(2 * w)], b = edges[(size_t)(2 * w + 1)];
-            starts_out[w] = a; counts_out[w] = b > a ? b - a : 0;
-        }
-        return LPVS_OK;
-    } catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
-}
-
-// ---- weighted wavelet Z-transform (wwz.hip; the decisions: wwz_plan.h) ------------------------------------------------------------------------
-// what lpvs_wwz_last_timing reports of the calling thread's last call: [0] Nf, [1] Ntau, [2] times and [3] signals per thread of the sums
-// kernel, [4] work items, [5] slab length, [6] empty cells, [7] degenerate cells, [8] staged and [9] useful (sample, frequency, time)
-// triples, ms of [10] staging, the scan and the record's means, [11] the ranges and the work list, [12] the sums, [13] the epilogue,
-// [14] the copy-out, [15] total
-static thread_local double g_wwz_timing[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-static int32_t wwz_impl(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const double *f, int64_t Nf, const double *tau, int64_t Ntau,
-                        const double *radius, const WwzShape &sh, bool center, int32_t device, double *power, double *amplitude, double *wwz, double *neff,
-                        double *coef, int64_t *count_out, int32_t *empty_out) {
-    if (lpvs_device_count() == 0) { set_error("no HIP device visible (the gfx950 path has no CPU fallback)"); return LPVS_EDEVICE; }
-    LPVS_HIP(hipSetDevice(device));
-    hipStream_t s = nullptr;
-    Events<6> ev;
-    for (auto &e : ev.e) LPVS_HIP(hipEventCreate(&e));
-    DevArg dt, dy, dW; DevOut dpower, damp, dwwz, dneff, dcoef;
-    DevBuf dsmall, dscan, dw, dwy, dfreq, dtau, dpos, dedges, dpair, ditems, dlist, dpart, dcount, dempty;
-    DrainOnExit drain(s);
-    LPVS_HIP(hipEventRecord(ev.e[0], s));
-    LPVS_TRY(dt.set(t, N, s));
-    LPVS_TRY(dy.set(y, N * ns, s));
-    if (W) LPVS_TRY(dW.set(W, N, s));
-    const int64_t cells = Nf * Ntau, ncols = cells * ns, pairs = sh.ngroups * sh.ftiles;
-    LPVS_TRY(dpower.set(power, ncols));
-    LPVS_TRY(damp.set(amplitude, ncols));
-    LPVS_TRY(dwwz.set(wwz, ncols));
-    LPVS_TRY(dneff.set(neff, cells));
-    if (coef) LPVS_TRY(dcoef.set(coef, 3 * ncols));
-    // small device record: [0] sum W, [1 .. ns] the record's weighted means, [1 + ns .. 1 + 4 ns) launch_lomb_moments' moments (not used),
-    // then the two counters of the epilogue and the flags
-    const size_t nsmall = (size_t)(1 + 4 * ns);
-    LPVS_TRY(dsmall.alloc(sizeof(double) * (nsmall + 3)));
-    double *sumW_dev = dsmall.as<double>(), *mean_dev = sumW_dev + 1, *mom_dev = mean_dev + ns;
-    unsigned long long *counters_dev = reinterpret_cast<unsigned long long *>(sumW_dev + nsmall);
-    int *flags_dev = reinterpret_cast<int *>(sumW_dev + nsmall + 2);
-    const int64_t nsum = lomb_sum_slabs(N);
-    LPVS_TRY(dscan.alloc(sizeof(double) * (size_t)(3 * ns * nsum)));
-    LPVS_TRY(launch_lomb_scan(dt.p, dy.p, dW.p, N, ns, flags_dev, dscan.as<double>(), sumW_dev, s));
-    LPVS_TRY(launch_wwz_sorted(dt.p, N, flags_dev, s));
-    double sumW = 0; int flags = 0;
-    LPVS_TRY(copy_from_device(&sumW, sumW_dev, sizeof(double), s));
-    LPVS_TRY(copy_from_device(&flags, flags_dev, sizeof(int), s));
-    if (flags & 1) { set_error("wwz: t, y or W holds a value that is not finite"); return LPVS_EARGUMENT; }
-    if (flags & 2) { set_error("wwz: a weight is negative"); return LPVS_EARGUMENT; }
-    if (flags & 8) { set_error("wwz: t is not sorted (it decreases somewhere)"); return LPVS_EARGUMENT; }
-    if (!std::isfinite(sumW)) { set_error("wwz: the weights sum to %g", sumW); return LPVS_EARGUMENT; }
-    // the record's weighted means (weights W); weights that sum to 0 leave every cell empty, and nothing is removed
-    const bool removes = center && sumW > 0.0;
-    if (removes) {
-        LPVS_TRY(dw.alloc(sizeof(double) * (size_t)N));
-        LPVS_TRY(dwy.alloc(sizeof(double) * (size_t)(N * ns)));
-        LPVS_TRY(launch_lomb_moments(dy.p, dW.p, N, ns, sumW, true, dw.as<double>(), dwy.as<double>(), mean_dev, mom_dev, dscan.as<double>(), s));
-    }
-    LPVS_HIP(hipEventRecord(ev.e[1], s));
-    // per frequency [f | decay | radius | rmax of the tiles], per time [tau in order | gmin | gmax | tau as given], the places
-    LPVS_TRY(dfreq.alloc(sizeof(double) * (size_t)(3 * Nf + sh.ftiles)));
-    double *f_dev = dfreq.as<double>(), *decay_dev = f_dev + Nf, *radius_dev = decay_dev + Nf, *rmax_dev = radius_dev + Nf;
-    LPVS_TRY(copy_to_device(f_dev, f, sizeof(double) * (size_t)Nf, s));
-    LPVS_TRY(copy_to_device(decay_dev, sh.decay.data(), sizeof(double) * (size_t)Nf, s));
-    LPVS_TRY(copy_to_device(radius_dev, radius, sizeof(double) * (size_t)Nf, s));
-    LPVS_TRY(copy_to_device(rmax_dev, sh.rmax.data(), sizeof(double) * (size_t)sh.ftiles, s));
-    const int64_t nsorted = sh.ngroups * sh.TT;
-    LPVS_TRY(dtau.alloc(sizeof(double) * (size_t)(nsorted + 2 * sh.ngroups + Ntau)));
-    double *tau_dev = dtau.as<double>(), *gmin_dev = tau_dev + nsorted, *gmax_dev = gmin_dev + sh.ngroups, *given_dev = gmax_dev + sh.ngroups;
-    LPVS_TRY(copy_to_device(tau_dev, sh.tau_sorted.data(), sizeof(double) * (size_t)nsorted, s));
-    LPVS_TRY(copy_to_device(gmin_dev, sh.gmin.data(), sizeof(double) * (size_t)sh.ngroups, s));
-    LPVS_TRY(copy_to_device(gmax_dev, sh.gmax.data(), sizeof(double) * (size_t)sh.ngroups, s));
-    LPVS_TRY(copy_to_device(given_dev, tau, sizeof(double) * (size_t)Ntau, s));
-    LPVS_TRY(dpos.alloc(sizeof(int32_t) * (size_t)Ntau));
-    LPVS_TRY(copy_to_device(dpos.p, sh.pos.data(), sizeof(int32_t) * (size_t)Ntau, s));
-    // the ranges of the cells and of the (group, tile) pairs; the pairs' go to the host, which lays out the work list
-    LPVS_TRY(dedges.alloc(sizeof(int64_t) * (size_t)(2 * cells)));
-    LPVS_TRY(dpair.alloc(sizeof(int64_t) * (size_t)(2 * pairs)));
-    LPVS_TRY(launch_wwz_ranges(dt.p, N, given_dev, given_dev, Ntau, radius_dev, Nf, dedges.as<int64_t>(), s));
-    LPVS_TRY(launch_wwz_ranges(dt.p, N, gmin_dev, gmax_dev, sh.ngroups, rmax_dev, sh.ftiles, dpair.as<int64_t>(), s));
-    std::vector<int64_t> hedges((size_t)(2 * cells)), hpair((size_t)(2 * pairs));
-    LPVS_TRY(copy_from_device(hedges.data(), dedges.p, sizeof(int64_t) * hedges.size(), s));
-    LPVS_TRY(copy_from_device(hpair.data(), dpair.p, sizeof(int64_t) * hpair.size(), s));
-    double useful = 0;
-    for (int64_t q = 0; q < cells; ++q) {
-        const int64_t a = hedges[(size_t)(2 * q)], b = hedges[(size_t)(2 * q + 1)];
-        if (b > a) useful += (double)(b - a);
-    }
-    const WwzWork work = wwz_work(sh, hpair, useful);
-    if (work.status != kWwzOk) { set_error("%s", work.why.c_str()); return LPVS_EUNSUPPORTED; }
-    const int64_t nitems = (int64_t)work.items.size();
-    LPVS_TRY(ditems.alloc(sizeof(WwzItem) * (size_t)(nitems > 0 ? nitems : 1)));
-    if (nitems > 0) LPVS_TRY(copy_to_device(ditems.p, work.items.data(), sizeof(WwzItem) * (size_t)nitems, s));
-    LPVS_TRY(dlist.alloc(sizeof(int64_t) * (size_t)(2 * pairs + 1)));
-    int64_t *offset_dev = dlist.as<int64_t>(), *first_slab_dev = offset_dev + pairs + 1;
-    LPVS_TRY(copy_to_device(offset_dev, work.offset.data(), sizeof(int64_t) * (size_t)(pairs + 1), s));
-    LPVS_TRY(copy_to_device(first_slab_dev, work.first_slab.data(), sizeof(int64_t) * (size_t)pairs, s));
-    LPVS_TRY(dpart.alloc(sizeof(double) * (size_t)(work.part_doubles > 0 ? work.part_doubles : 1)));
-    WwzArgs A;
-    A.t = dt.p; A.y = dy.p; A.W = dW.p; A.mean = removes ? mean_dev : nullptr;
-    A.f = f_dev; A.decay = decay_dev; A.radius = radius_dev; A.tau = tau_dev; A.pos = dpos.as<int32_t>();
-    A.items = ditems.as<WwzItem>(); A.offset = offset_dev; A.first_slab = first_slab_dev;
-    A.N = N; A.Nf = Nf; A.Ntau = Ntau; A.nitems = nitems; A.ftiles = sh.ftiles; A.slab_samples = sh.slab_samples; A.rows = sh.rows;
-    A.ns = (int)ns; A.TT = sh.TT;
-    LPVS_HIP(hipEventRecord(ev.e[2], s));
-    LPVS_TRY(launch_wwz_sums(A, sh.ts, dpart.as<double>(), s));
-    LPVS_HIP(hipEventRecord(ev.e[3], s));
-    LPVS_TRY(dcount.alloc(sizeof(int64_t) * (size_t)cells));
-    LPVS_TRY(dempty.alloc(sizeof(int32_t) * (size_t)cells));
-    LPVS_TRY(launch_wwz_epilogue(A, dpart.as<double>(), dedges.as<int64_t>(), removes, dpower.p, damp.p, dwwz.p, dneff.p, coef ? dcoef.p : nullptr,
-                                 dcount.as<int64_t>(), dempty.as<int32_t>(), flags_dev, counters_dev, s));
-    LPVS_HIP(hipEventRecord(ev.e[4], s));
-    unsigned long long counters[2] = {0, 0};
-    LPVS_TRY(copy_from_device(&flags, flags_dev, sizeof(int), s));
-    LPVS_TRY(copy_from_device(counters, counters_dev, sizeof(counters), s));
-    if (flags & 4) { set_error("wwz: the weights of a cell do not sum to a finite value"); return LPVS_EARGUMENT; }
-    if (flags & 16) { set_error("wwz: a cell lies outside the samples its group stages"); return LPVS_EDEVICE; }
-    if (count_out) LPVS_TRY(copy_from_device(count_out, dcount.p, sizeof(int64_t) * (size_t)cells, s));
-    if (empty_out) LPVS_TRY(copy_from_device(empty_out, dempty.p, sizeof(int32_t) * (size_t)cells, s));
-    LPVS_TRY(dpower.finish(s));
-    LPVS_TRY(damp.finish(s));
-    LPVS_TRY(dwwz.finish(s));
-    LPVS_TRY(dneff.finish(s));
-    if (coef) LPVS_TRY(dcoef.finish(s));
-    LPVS_HIP(hipEventRecord(ev.e[5], s));
-    LPVS_HIP(hipStreamSynchronize(s));
-    float ms[5] = {0, 0, 0, 0, 0}, total = 0;
-    for (int i = 0; i < 5; ++i) LPVS_HIP(hipEventElapsedTime(&ms[i], ev.e[i], ev.e[i + 1]));
-    LPVS_HIP(hipEventElapsedTime(&total, ev.e[0], ev.e[5]));
-    double *g = g_wwz_timing;
-    g[0] = (double)Nf; g[1] = (double)Ntau; g[2] = sh.TT; g[3] = sh.ts; g[4] = (double)nitems; g[5] = (double)sh.slab_samples;
-    g[6] = (double)counters[0]; g[7] = (double)counters[1]; g[8] = work.staged; g[9] = work.useful;
-    g[10] = ms[0]; g[11] = ms[1]; g[12] = ms[2]; g[13] = ms[3]; g[14] = ms[4]; g[15] = total;
-    return LPVS_OK;
-}
-
-int32_t lpvs_wwz_f64(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const double *f, int64_t Nf, const double *tau, int64_t Ntau,
-                     double c, const double *radius, int32_t center_data, int32_t device, double *power_out, double *amplitude_out, double *wwz_out,
-                     double *neff_out, double *coef_out, int64_t *count_out, int32_t *empty_out) {
-    try {
-        if (!y || !t || !f || !tau || !radius || !power_out || !amplitude_out || !wwz_out || !neff_out) { set_error("NULL argument"); return LPVS_EARGUMENT; }
-        if (is_device_ptr(f) || is_device_ptr(tau) || is_device_ptr(radius) || (count_out && is_device_ptr(count_out)) || (empty_out && is_device_ptr(empty_out))) {
-            set_error("wwz: f, tau, radius, count_out and empty_out are host memory"); return LPVS_EARGUMENT;
-        }
-        const WwzShape sh = wwz_shape(N, ns, f, Nf, tau, Ntau, c, radius);        // (the counts are checked before an array is read)
-        if (sh.status != kWwzOk) { set_error("%s", sh.why.c_str()); return sh.status == kWwzArgument ? LPVS_EARGUMENT : LPVS_EUNSUPPORTED; }
-        return wwz_impl(y, ns, t, N, W, f, Nf, tau, Ntau, radius, sh, center_data != 0, device, power_out, amplitude_out, wwz_out, neff_out, coef_out, count_out,
-                        empty_out);
-    } catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
-}
-
-int32_t lpvs_wwz_last_timing(double *out, int32_t n) {
-    if (!out || n < 0) { set_error("NULL argument"); return LPVS_EARGUMENT; }
-    for (int32_t k = 0; k < n && k < 16; ++k) out[k] = g_wwz_timing[k];
-    return LPVS_OK;
-}
-
-// ---- box least squares periodogram (bls.hip; the decisions: bls_plan.h) ------------------------------------------------------------------------
-// what lpvs_bls_last_timing reports of the calling thread's last call: [0] frequencies per workgroup (F), [1] signals per pass (TS),
-// [2] passes, [3] LDS bytes of a workgroup, [4] the shift of the weights (60; 0 with unit weights: counts), [5], [6] the smallest and
-// largest shift of a signal (0, 0 when every signal is constant), [7] degenerate (frequency, signal) pairs, [8] boxes tried (per signal),
-// [9] unit weights, ms of [10] staging, the scan and the moments, [11] the maxima and the quantisation, [12] fold and search,
-// [13] the copy-out, [14] total, [15] Nf
-static thread_local double g_bls_timing[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-static int32_t bls_impl(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const double *f, int64_t Nf, int32_t nbins, const int32_t *kmin,
-                        const int32_t *kmax, int64_t min_count, bool dips_only, bool center, bool chi2, const BlsPlan &plan, int32_t device, double *power,
-                        double *depth, double *depth_err, int32_t *start_out, int32_t *width_out, int64_t *count_out, int32_t *degenerate_out, int64_t *hist_out,
-                        int32_t *hcount_out) {
-    if (lpvs_device_count() == 0) { set_error("no HIP device visible (the gfx950 path has no CPU fallback)"); return LPVS_EDEVICE; }
-    LPVS_HIP(hipSetDevice(device));
-    hipStream_t s = nullptr;
-    Events<5> ev;
-    for (auto &e : ev.e) LPVS_HIP(hipEventCreate(&e));
-    DevArg dt, dy, dW; DevOut dpower, ddepth, derr;
-    DevBuf dsmall, dscan, dw, dwy, dq, dfreq, dk, dshy, dint, dcount, dhist, dhcount;
-    DrainOnExit drain(s);
-    LPVS_HIP(hipEventRecord(ev.e[0], s));
-    LPVS_TRY(dt.set(t, N, s));
-    LPVS_TRY(dy.set(y, N * ns, s));
-    if (W) LPVS_TRY(dW.set(W, N, s));
-    const int64_t ncols = Nf * ns;
-    LPVS_TRY(dpower.set(power, ncols));
-    LPVS_TRY(ddepth.set(depth, ncols));
-    LPVS_TRY(derr.set(depth_err, ncols));
-    // small device record: [0] sum W, [1 .. ns] the weighted means, then launch_lomb_moments' moments (3 ns), then the maxima (2 ns), the
-    // two words of every YY (2 ns), the degenerate counter and the flags
-    const size_t nsmall = (size_t)(1 + 4 * ns);
-    LPVS_TRY(dsmall.alloc(sizeof(double) * (nsmall + (size_t)(4 * ns) + 2)));
-    double *sumW_dev = dsmall.as<double>(), *mean_dev = sumW_dev + 1, *mom_dev = mean_dev + ns;
-    unsigned long long *amax_dev = reinterpret_cast<unsigned long long *>(sumW_dev + nsmall);
-    long long *yyacc_dev = reinterpret_cast<long long *>(amax_dev + 2 * ns);
-    unsigned long long *ndeg_dev = amax_dev + 4 * ns;
-    int *flags_dev = reinterpret_cast<int *>(ndeg_dev + 1);
-    const int64_t nsum = lomb_sum_slabs(N);
-    LPVS_TRY(dscan.alloc(sizeof(double) * (size_t)(3 * ns * nsum)));
-    LPVS_TRY(launch_lomb_scan(dt.p, dy.p, dW.p, N, ns, flags_dev, dscan.as<double>(), sumW_dev, s));
-    double sumW = 0; int flags = 0;
-    LPVS_TRY(copy_from_device(&sumW, sumW_dev, sizeof(double), s));
-    LPVS_TRY(copy_from_device(&flags, flags_dev, sizeof(int), s));
-    if (flags & 1) { set_error("bls: t, y or W holds a value that is not finite"); return LPVS_EARGUMENT; }
-    if (flags & 2) { set_error("bls: a weight is negative"); return LPVS_EARGUMENT; }
-    if (!(sumW > 0.0) || !std::isfinite(sumW)) { set_error("bls: the weights sum to %g", sumW); return LPVS_EARGUMENT; }
-    LPVS_TRY(dw.alloc(sizeof(double) * (size_t)N));
-    LPVS_TRY(dwy.alloc(sizeof(double) * (size_t)(N * ns)));
-    LPVS_TRY(launch_lomb_moments(dy.p, dW.p, N, ns, sumW, center, dw.as<double>(), dwy.as<double>(), mean_dev, mom_dev, dscan.as<double>(), s));
-    LPVS_HIP(hipEventRecord(ev.e[1], s));
-    // the maxima, the shifts (bls_plan.h), the quantised record: qy[ns][N], then qw[N] with weights
-    LPVS_TRY(launch_bls_max(dy.p, dwy.as<double>(), mean_dev, center, N, ns, amax_dev, s));
-    std::vector<unsigned long long> hmax((size_t)(2 * ns));
-    LPVS_TRY(copy_from_device(hmax.data(), amax_dev, sizeof(unsigned long long) * (size_t)(2 * ns), s));
-    std::vector<int32_t> hshy((size_t)(2 * ns), 0);
-    int shy_lo = 0, shy_hi = 0; bool any = false;
-    for (int64_t c = 0; c < ns; ++c) {
-        double A, M;
-        memcpy(&A, &hmax[(size_t)c], sizeof(double)); memcpy(&M, &hmax[(size_t)(ns + c)], sizeof(double));
-        hshy[(size_t)(ns + c)] = M > 0.0 && std::isfinite(M) ? bls_shift_y(M, N) : kBlsNoShift;   // (the terms of YY_c: cut against the largest)
-        if (!(A > 0.0)) continue;
-        const int sh = bls_shift_y(A, N);
-        hshy[(size_t)c] = sh;
-        shy_lo = any && shy_lo < sh ? shy_lo : sh;
-        shy_hi = any && shy_hi > sh ? shy_hi : sh;
-        any = true;
-    }
-    LPVS_TRY(dshy.alloc(sizeof(int32_t) * (size_t)(2 * ns)));
-    LPVS_TRY(copy_to_device(dshy.p, hshy.data(), sizeof(int32_t) * (size_t)(2 * ns), s));
-    LPVS_TRY(dq.alloc(sizeof(long long) * (size_t)(N * (ns + (plan.unit ? 0 : 1)))));
-    long long *qy_dev = dq.as<long long>(), *qw_dev = plan.unit ? nullptr : qy_dev + N * ns;
-    LPVS_TRY(launch_bls_quantise(dy.p, dw.as<double>(), dwy.as<double>(), mean_dev, center, N, ns, plan.log2n, dshy.as<int32_t>(), amax_dev, qw_dev, qy_dev, yyacc_dev, s));
-    LPVS_TRY(dfreq.alloc(sizeof(double) * (size_t)Nf));
-    LPVS_TRY(copy_to_device(dfreq.p, f, sizeof(double) * (size_t)Nf, s));
-    LPVS_TRY(dk.alloc(sizeof(int32_t) * (size_t)(2 * Nf)));
-    LPVS_TRY(copy_to_device(dk.p, kmin, sizeof(int32_t) * (size_t)Nf, s));
-    LPVS_TRY(copy_to_device(dk.as<int32_t>() + Nf, kmax, sizeof(int32_t) * (size_t)Nf, s));
-    LPVS_TRY(dint.alloc(sizeof(int32_t) * (size_t)(3 * ncols)));
-    LPVS_TRY(dcount.alloc(sizeof(int64_t) * (size_t)ncols));
-    if (hist_out) LPVS_TRY(dhist.alloc(sizeof(int64_t) * (size_t)(Nf * (1 + ns) * nbins)));
-    if (hcount_out) LPVS_TRY(dhcount.alloc(sizeof(int32_t) * (size_t)(Nf * nbins)));
-    BlsArgs A;
-    A.t = dt.p; A.qw = qw_dev; A.qy = qy_dev; A.f = dfreq.as<double>(); A.kmin = dk.as<int32_t>(); A.kmax = A.kmin + Nf;
-    A.shy = dshy.as<int32_t>(); A.amax = amax_dev; A.yyacc = yyacc_dev; A.mom = mom_dev; A.log2n = plan.log2n;
-    A.N = N; A.Nf = Nf; A.min_count = min_count; A.ns = (int)ns; A.nbins = nbins; A.dips_only = dips_only ? 1 : 0; A.chi2 = chi2 ? 1 : 0;
-    A.center = center ? 1 : 0; A.sumW = sumW;
-    A.power = dpower.p; A.depth = ddepth.p; A.depth_err = derr.p;
-    A.start = dint.as<int32_t>(); A.width = A.start + ncols; A.degenerate = A.width + ncols; A.count = dcount.as<int64_t>();
-    A.hist = hist_out ? dhist.as<long long>() : nullptr; A.hcount = hcount_out ? dhcount.as<int32_t>() : nullptr; A.ndeg = ndeg_dev;
-    LPVS_HIP(hipEventRecord(ev.e[2], s));
-    LPVS_TRY(launch_bls(A, plan, s));
-    LPVS_HIP(hipEventRecord(ev.e[3], s));
-    unsigned long long ndeg = 0;
-    LPVS_TRY(copy_from_device(&ndeg, ndeg_dev, sizeof(ndeg), s));
-    LPVS_TRY(copy_from_device(start_out, A.start, sizeof(int32_t) * (size_t)ncols, s));
-    LPVS_TRY(copy_from_device(width_out, A.width, sizeof(int32_t) * (size_t)ncols, s));
-    LPVS_TRY(copy_from_device(count_out, A.count, sizeof(int64_t) * (size_t)ncols, s));
-    if (degenerate_out) LPVS_TRY(copy_from_device(degenerate_out, A.degenerate, sizeof(int32_t) * (size_t)ncols, s));
-    if (hist_out) LPVS_TRY(copy_from_device(hist_out, dhist.p, sizeof(int64_t) * (size_t)(Nf * (1 + ns) * nbins), s));
-    if (hcount_out) LPVS_TRY(copy_from_device(hcount_out, dhcount.p, sizeof(int32_t) * (size_t)(Nf * nbins), s));
-    LPVS_TRY(dpower.finish(s));
-    LPVS_TRY(ddepth.finish(s));
-    LPVS_TRY(derr.finish(s));
-    LPVS_HIP(hipEventRecord(ev.e[4], s));
-    LPVS_HIP(hipStreamSynchronize(s));
-    float ms[4] = {0, 0, 0, 0}, total = 0;
-    for (int i = 0; i < 4; ++i) LPVS_HIP(hipEventElapsedTime(&ms[i], ev.e[i], ev.e[i + 1]));
-    LPVS_HIP(hipEventElapsedTime(&total, ev.e[0], ev.e[4]));
-    double *g = g_bls_timing;
-    g[0] = plan.F; g[1] = plan.ts; g[2] = plan.passes; g[3] = (double)plan.lds_bytes; g[4] = plan.unit ? 0 : kBlsWeightShift; g[5] = shy_lo; g[6] = shy_hi;
-    g[7] = (double)ndeg; g[8] = plan.boxes; g[9] = plan.unit; g[10] = ms[0]; g[11] = ms[1]; g[12] = ms[2]; g[13] = ms[3]; g[14] = total; g[15] = (double)Nf;
-    return LPVS_OK;
-}
-
-int32_t lpvs_bls_f64(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const double *f, int64_t Nf, int32_t nbins, const int32_t *kmin,
-                     const int32_t *kmax, int64_t min_count, int32_t dips_only, int32_t center_data, int32_t normalization, int32_t device, double *power_out,
-                     double *depth_out, double *depth_err_out, int32_t *start_out, int32_t *width_out, int64_t *count_out, int32_t *degenerate_out, int64_t *hist_out,
-                     int32_t *hcount_out) {
-    try {
-        if (!y || !t || !f || !kmin || !kmax || !power_out || !depth_out || !depth_err_out || !start_out || !width_out || !count_out) {
-            set_error("NULL argument"); return LPVS_EARGUMENT;
-        }
-        if (is_device_ptr(f) || is_device_ptr(kmin) || is_device_ptr(kmax) || is_device_ptr(start_out) || is_device_ptr(width_out) || is_device_ptr(count_out) ||
-            (degenerate_out && is_device_ptr(degenerate_out)) || (hist_out && is_device_ptr(hist_out)) || (hcount_out && is_device_ptr(hcount_out))) {
-            set_error("bls: f, kmin, kmax, start_out, width_out, count_out, degenerate_out, hist_out and hcount_out are host memory"); return LPVS_EARGUMENT;
-        }
-        const BlsPlan plan = bls_plan(N, ns, f, Nf, nbins, kmin, kmax, min_count, W == nullptr, normalization);   // (the counts are checked before an array is read)
-        if (plan.status != kBlsOk) { set_error("%s", plan.why.c_str()); return plan.status == kBlsArgument ? LPVS_EARGUMENT : LPVS_EUNSUPPORTED; }
-        return bls_impl(y, ns, t, N, W, f, Nf, nbins, kmin, kmax, min_count, dips_only != 0, center_data != 0, normalization == 1, plan, device, power_out, depth_out,
-                        depth_err_out, start_out, width_out, count_out, degenerate_out, hist_out, hcount_out);
-    } catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
-}
-
-int32_t lpvs_bls_last_timing(double *out, int32_t n) {
-    if (!out || n < 0) { set_error("NULL argument"); return LPVS_EARGUMENT; }
-    for (int32_t k = 0; k < n && k < 16; ++k) out[k] = g_bls_timing[k];
-    return LPVS_OK;
-}
-
-// ---- the bootstrap of the Lomb-Scargle periodogram (lomb_boot.hip; the decisions: lomb_boot_plan.h) ------------------------------------------
-// what lpvs_lombscargle_bootstrap_last_timing reports of the calling thread's last call: [0] resamples, [1] chunks, [2] resamples per thread
-// (TS), [3] slab length, [4] slabs, [5] degenerate frequencies, ms of [6] staging, the scan and the shared sums of the record, [7] the
-// moments of the resamples, [8] the bootstrap sums, [9] the epilogue and the maxima, [10] the copy-out, [11] total
-static thread_local double g_lomb_boot_timing[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-static int32_t lomb_boot_impl(const double *y, const double *t, int64_t N, const double *W, const std::vector<double> &hf, int64_t B, int64_t seed, int64_t row0,
-                              bool fit_mean, bool center, bool psd, int32_t device, const LombBootPlan &plan, double *max_out, int64_t *argmax_out, double *mean_out,
-                              double *power_out) {
-    const int64_t Nf = (int64_t)hf.size();
-    if (lpvs_device_count() == 0) { set_error("no HIP device visible (the gfx950 path has no CPU fallback)"); return LPVS_EDEVICE; }
-    LPVS_HIP(hipSetDevice(device));
-    hipStream_t s = nullptr;
-    Events<5> ev;
-    for (auto &e : ev.e) LPVS_HIP(hipEventCreate(&e));
-    struct ChunkEvents {                                                     // a chunk: before its sums, between sums and epilogue, after the epilogue
-        hipEvent_t a = nullptr, b = nullptr, c = nullptr;
-        ~ChunkEvents() { for (hipEvent_t x : {a, b, c}) if (x) (void)hipEventDestroy(x); }
-    };
-    std::vector<ChunkEvents> cev((size_t)plan.nchunks);
-    DevArg dt, dy, dW; DevOut dmax, dpower;
-    DevBuf dw, dwy, dsmall, dscan, dshared, dfreq, dslab, dmom, dargmax, dpart, dsums;
-    DrainOnExit drain(s);
-    LPVS_HIP(hipEventRecord(ev.e[0], s));
-    LPVS_TRY(dt.set(t, N, s));
-    LPVS_TRY(dy.set(y, N, s));
-    if (W) LPVS_TRY(dW.set(W, N, s));
-    LPVS_TRY(dmax.set(max_out, B));
-    if (power_out) LPVS_TRY(dpower.set(power_out, Nf * B));
-    // the observed record, as g4 takes it: the scan (sum W, the refusals), the normalised weights, and C, S, C2, S2 by the direct path's
-    // kernels with one signal (small record: [0] sum W, [1] mean, [2 .. 4] moments, then two ints: flags, degenerate count)
-    LPVS_TRY(dsmall.alloc(sizeof(double) * 6));
-    double *sumW_dev = dsmall.as<double>(), *mean1_dev = sumW_dev + 1, *mom1_dev = mean1_dev + 1;
-    int *flags_dev = reinterpret_cast<int *>(sumW_dev + 5), *ndeg_dev = flags_dev + 1;
-    LPVS_TRY(dscan.alloc(sizeof(double) * (size_t)(3 * lomb_sum_slabs(N))));
-    LPVS_TRY(launch_lomb_scan(dt.p, dy.p, dW.p, N, 1, flags_dev, dscan.as<double>(), sumW_dev, s));
-    double sumW = 0; int flags = 0;
-    LPVS_TRY(copy_from_device(&sumW, sumW_dev, sizeof(double), s));
-    LPVS_TRY(copy_from_device(&flags, flags_dev, sizeof(int), s));
-    if (flags & 1) { set_error("lombscargle: t, y or W holds a value that is not finite"); return LPVS_EARGUMENT; }
-    if (flags & 2) { set_error("lombscargle: a weight is negative"); return LPVS_EARGUMENT; }
-    if (!(sumW > 0.0) || !std::isfinite(sumW)) { set_error("lombscargle: the weights sum to %g", sumW); return LPVS_EARGUMENT; }
-    LPVS_TRY(dw.alloc(sizeof(double) * (size_t)N));
-    LPVS_TRY(dwy.alloc(sizeof(double) * (size_t)N));
-    LPVS_TRY(launch_lomb_moments(dy.p, dW.p, N, 1, sumW, center, dw.as<double>(), dwy.as<double>(), mean1_dev, mom1_dev, dscan.as<double>(), s));
-    const LombTiling tl = lomb_tiling(N, Nf, 1);
-    LPVS_TRY(dfreq.alloc(sizeof(double) * (size_t)Nf));
-    LPVS_TRY(copy_to_device(dfreq.p, hf.data(), sizeof(double) * (size_t)Nf, s));
-    LPVS_TRY(dslab.alloc(sizeof(double) * (size_t)(tl.nslab * 6 * Nf)));
-    LPVS_TRY(dshared.alloc(sizeof(double) * (size_t)(6 * Nf)));              // rows C, S, C2, S2 (and the record's own YC, YS, not used)
-    LPVS_TRY(launch_lomb_direct(dt.p, dw.as<double>(), dwy.as<double>(), N, 1, dfreq.as<double>(), Nf, tl, dslab.as<double>(), dshared.as<double>(), s));
-    dslab.release();
-    LPVS_HIP(hipEventRecord(ev.e[1], s));
-    // the resamples' moments: mean[B], then {Y, YY, R, -} per resample
-    LPVS_TRY(dmom.alloc(sizeof(double) * (size_t)(5 * B)));
-    double *mean_dev = dmom.as<double>(), *mom_dev = mean_dev + B;
-    LPVS_TRY(dargmax.alloc(sizeof(int64_t) * (size_t)B));
-    LPVS_TRY(launch_lomb_boot_moments(dy.p, dw.as<double>(), N, seed, row0, B, center, mean_dev, mom_dev, s));
-    LPVS_HIP(hipEventRecord(ev.e[2], s));
-    LPVS_HIP(hipMemsetAsync(ndeg_dev, 0, sizeof(int), s));
-    LPVS_TRY(dpart.alloc(sizeof(double) * (size_t)plan.part_doubles));
-    LPVS_TRY(dsums.alloc(sizeof(double) * (size_t)(2 * plan.chunk * Nf)));
-    for (int64_t c = 0; c < plan.nchunks; ++c) {
-        const int64_t r0 = c * plan.chunk, count = c + 1 < plan.nchunks ? plan.chunk : plan.last_chunk;
-        ChunkEvents &ce = cev[(size_t)c];
-        LPVS_HIP(hipEventCreate(&ce.a)); LPVS_HIP(hipEventCreate(&ce.b)); LPVS_HIP(hipEventCreate(&ce.c));
-        LPVS_HIP(hipEventRecord(ce.a, s));
-        LPVS_TRY(launch_lomb_boot_sums(dt.p, dw.as<double>(), dy.p, N, seed, row0, r0, count, center ? mean_dev : nullptr, dfreq.as<double>(), Nf, plan,
-                                       dpart.as<double>(), dsums.as<double>(), s));
-        LPVS_HIP(hipEventRecord(ce.b, s));
-        LPVS_TRY(launch_lomb_boot_epilogue(dshared.as<double>(), dsums.as<double>(), Nf, r0, count, mean_dev, mom_dev, fit_mean, center, psd, N,
-                                           power_out ? dpower.p : nullptr, dmax.p, dargmax.as<int64_t>(), c == 0, ndeg_dev, s));
-        LPVS_HIP(hipEventRecord(ce.c, s));
-    }
-    LPVS_HIP(hipEventRecord(ev.e[3], s));
-    int ndeg = 0;
-    LPVS_TRY(copy_from_device(&ndeg, ndeg_dev, sizeof(int), s));
-    if (argmax_out) LPVS_TRY(copy_from_device(argmax_out, dargmax.p, sizeof(int64_t) * (size_t)B, s));
-    if (mean_out) LPVS_TRY(copy_from_device(mean_out, mean_dev, sizeof(double) * (size_t)B, s));
-    LPVS_TRY(dmax.finish(s));
-    if (power_out) LPVS_TRY(dpower.finish(s));
-    LPVS_HIP(hipEventRecord(ev.e[4], s));
-    LPVS_HIP(hipStreamSynchronize(s));
-    float shared_ms = 0, mom_ms = 0, copy_ms = 0, total = 0;
-    LPVS_HIP(hipEventElapsedTime(&shared_ms, ev.e[0], ev.e[1]));
-    LPVS_HIP(hipEventElapsedTime(&mom_ms, ev.e[1], ev.e[2]));
-    LPVS_HIP(hipEventElapsedTime(&copy_ms, ev.e[3], ev.e[4]));
-    LPVS_HIP(hipEventElapsedTime(&total, ev.e[0], ev.e[4]));
-    double sums_ms = 0, epi_ms = 0;
-    for (int64_t c = 0; c < plan.nchunks; ++c) {
-        float x = 0, z = 0;
-        LPVS_HIP(hipEventElapsedTime(&x, cev[(size_t)c].a, cev[(size_t)c].b));
-        LPVS_HIP(hipEventElapsedTime(&z, cev[(size_t)c].b, cev[(size_t)c].c));
-        sums_ms += x; epi_ms += z;
-    }
-    double *g = g_lomb_boot_timing;
-    g[0] = (double)B; g[1] = (double)plan.nchunks; g[2] = plan.ts; g[3] = (double)plan.slab_samples; g[4] = (double)plan.nslab; g[5] = ndeg;
-    g[6] = shared_ms; g[7] = mom_ms; g[8] = sums_ms; g[9] = epi_ms; g[10] = copy_ms; g[11] = total;
-    return LPVS_OK;
-}
-
-int32_t lpvs_lombscargle_bootstrap_f64(const double *y, const double *t, int64_t N, const double *W, const double *f, int64_t Nf, int64_t B, int64_t seed, int64_t row0,
-                                       int32_t fit_mean, int32_t center_data, int32_t normalization, int32_t device, double *max_out, int64_t *argmax_out,
-                                       double *mean_out, double *power_out) {
-    try {
-        if (!y || !t || !f || !max_out) { set_error("NULL argument"); return LPVS_EARGUMENT; }
-        const char *ts_knob = experiment_env("LPVS_LOMB_BOOT_TS"), *mb_knob = experiment_env("LPVS_LOMB_BOOT_MB");
-        const LombBootPlan plan = lomb_boot_plan(N, Nf, B, row0, ts_knob ? atoll(ts_knob) : 0, mb_knob ? atof(mb_knob) : 0.0);
-        if (plan.status != kLombBootOk) { set_error("%s", plan.why.c_str()); return plan.status == kLombBootArgument ? LPVS_EARGUMENT : LPVS_EUNSUPPORTED; }
-        if (normalization != LPVS_LOMB_STANDARD && normalization != LPVS_LOMB_PSD) { set_error("normalization must be 0 (standard) or 1 (psd), got %d", normalization); return LPVS_EARGUMENT; }
-        if (is_device_ptr(f) || (argmax_out && is_device_ptr(argmax_out)) || (mean_out && is_device_ptr(mean_out))) {
-            set_error("lombscargle_bootstrap: f, argmax_out and mean_out are host memory"); return LPVS_EARGUMENT;
-        }
-        std::vector<double> hf(f, f + Nf);
-        for (double v : hf)
-            if (!std::isfinite(v)) { set_error("lombscargle: a frequency is not finite"); return LPVS_EARGUMENT; }
-        return lomb_boot_impl(y, t, N, W, hf, B, seed, row0, fit_mean != 0, center_data != 0, normalization == LPVS_LOMB_PSD, device, plan, max_out, argmax_out,
-                              mean_out, power_out);
-    } catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
-}
-
-int32_t lpvs_lombscargle_bootstrap_last_timing(double *out, int32_t n) {
-    if (!out || n < 0) { set_error("NULL argument"); return LPVS_EARGUMENT; }
-    for (int32_t k = 0; k < n && k < 12; ++k) out[k] = g_lomb_boot_timing[k];
-    return LPVS_OK;
+    return copy_timing(out, n, g_eval_timing, 10);
 }
 
 int32_t lpvs_problem_create_lpv_rows_f64(const double *Y, int64_t ns, const double *X, const double *V, int64_t N_local, const double *w,
@@ -2270,8 +1416,8 @@ int32_t lpvs_problem_create_fourier_f64(const double *y, const double *t, int64_
     HandleGuard guard{h};
     hipStream_t s = h->stream;
     h->kind = 0; h->N = N; h->Nf = Nf; h->zerofreq = zf; h->n = fourier_regressors(Nf, zf != 0);
-    DevArg dt, df;
-    LPVS_TRY(dt.set(t, N, s)); LPVS_TRY(df.set(f, Nf, s));
+    Staged<double> dt, df;
+    LPVS_TRY(dt.set(t, N, device, s)); LPVS_TRY(df.set(f, Nf, device, s));
     GramFormFacts ff; ff.family = GramFamily::fourier;
     ff.option = option_in_effect(LPVS_OPT_GRAM_FORM, h->opt[LPVS_OPT_GRAM_FORM]);
     ApSlots sl; double tam = -1;
@@ -2297,8 +1443,8 @@ int32_t lpvs_problem_create_dense_f64(const double *A, const double *y, int64_t 
     HandleGuard guard{h};
     hipStream_t s = h->stream;
     h->kind = 2; h->N = m; h->n = n;
-    DevArg dA;
-    LPVS_TRY(dA.set(A, m * n, s));
+    Staged<double> dA;
+    LPVS_TRY(dA.set(A, m * n, device, s));
     LPVS_TRY(create_panel_problem(h, y, W, m, [&](double *P, int64_t ld) {
         return launch_transpose_to_panel(dA.p, m, n, P, ld, s);
     }));
@@ -2735,8 +1881,8 @@ int32_t lpvs_ls_spectral_f64(const double *y, const double *t, int64_t N, const 
     h->kind = 0; h->N = nreg; h->Nf = Nf; h->zerofreq = zf; h->n = N;
     const GramPlan pl = make_gram_plan(N, nreg);
     const int64_t rows = pl.ksplit * pl.rows_per_chunk, ldn = round_up(N, 256);
-    DevArg dy, dt, df;
-    LPVS_TRY(dy.set(y, N, s)); LPVS_TRY(dt.set(t, N, s)); LPVS_TRY(df.set(f, Nf, s));
+    Staged<double> dy, dt, df;
+    LPVS_TRY(dy.set(y, N, device, s)); LPVS_TRY(dt.set(t, N, device, s)); LPVS_TRY(df.set(f, Nf, device, s));
     LPVS_TRY(open_problem(h, 1, ZeroGram::all));
     LPVS_HIP(hipMemcpyAsync(h->b.p, dy.p, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, s));   // right-hand side = y
     DevBuf D, slab, xo;
@@ -2838,7 +1984,7 @@ struct WinEngine {
     int64_t nreg = 0, np = 0, ld = 0, bw = 0; size_t vb = 0;   // (of pp: the names the phases use)
     int storage_opt = 0; bool split_storage = false, want_mv = false;
     // inputs and buffers
-    std::vector<DevArg> dys; DevArg dt, df;
+    std::vector<Staged<double>> dys; Staged<double> dt, df;
     DevBuf Wp; const double *Wdev = nullptr;
     PhaseTrace tr;
     DevBuf P, slab, M, Q, bvec, x, z, u, rhs, xb, status, work, istat, offs, scr, part, Mp, seg, npart, tab, tabb, fibuf, Q0, M0, b0, x0buf, ballscr, xbc, nibacc;
@@ -2857,8 +2003,8 @@ struct WinEngine {
           bg{res}, s(res->stream), ev(res->ev), dys((size_t)job.ns), tr(res->stream), drain(res->stream) {}
 
     int32_t run() {
-        for (int64_t q = 0; q < ns; ++q) LPVS_TRY(dys[(size_t)q].set(a.ys[q], a.L, s));
-        LPVS_TRY(dt.set(a.t, a.L, s)); LPVS_TRY(df.set(a.freqs, Nf, s));
+        for (int64_t q = 0; q < ns; ++q) LPVS_TRY(dys[(size_t)q].set(a.ys[q], a.L, a.device, s));
+        LPVS_TRY(dt.set(a.t, a.L, a.device, s)); LPVS_TRY(df.set(a.freqs, Nf, a.device, s));
         LPVS_TRY(choose_gram_form());
         LPVS_TRY(upload_window_function());
         tr = PhaseTrace(s);
@@ -3356,8 +2502,7 @@ void windows_set_multi_info(int rccl_ranks, int devices) { g_win_multi[0] = rccl
 extern "C" {
 
 int32_t lpvs_windowpsd_last_timing(double *out, int32_t n_out) {
-    if (!out) { set_error("NULL argument"); return LPVS_EARGUMENT; }
-    for (int i = 0; i < n_out && i < 10; ++i) out[i] = g_win_timing[i];
+    LPVS_TRY(copy_timing(out, n_out < 0 ? 0 : n_out, g_win_timing, 10));   // (a negative count is not refused here)
     for (int i = 10; i < n_out && i < 12; ++i) out[i] = g_win_multi[i - 10];
     return LPVS_OK;
 }

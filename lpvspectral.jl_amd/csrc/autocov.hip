@@ -522,9 +522,7 @@ int32_t lpvs_autofun_f32(int32_t kind, const float *t, const float *y, const int
 }
 
 int32_t lpvs_autofun_last_timing(double *out, int32_t n) {
-    if (!out || n < 0) { set_error("NULL argument"); return LPVS_EARGUMENT; }
-    for (int32_t k = 0; k < n && k < 8; ++k) out[k] = g_timing[k];
-    return LPVS_OK;
+    return copy_timing(out, n, g_timing, 8);
 }
 
 }  // extern "C"

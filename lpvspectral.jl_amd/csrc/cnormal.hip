@@ -615,9 +615,7 @@ int32_t lpvs_cn_bands_f64(int64_t cn, int64_t Nf, int64_t nb, const double *Phi_
     LPVS_CN_GUARD(cn_bands_impl(cn, Nf, nb, Phi_g, G, nMC, seed, R, phase, Fl, Fu, Fm, Pl, Pu, Pm))
 }
 int32_t lpvs_cn_last_timing(double *out, int32_t n) {
-    if (!out || n < 0) { set_error("NULL argument"); return LPVS_EARGUMENT; }
-    for (int32_t k = 0; k < n && k < 8; ++k) out[k] = g_timing[k];
-    return LPVS_OK;
+    return copy_timing(out, n, g_timing, 8);
 }
 
 }  // extern "C"

@@ -302,9 +302,7 @@ int32_t lpvs_compress_f32(const float *x, int64_t rows, int64_t cols, int64_t ld
     catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
 }
 int32_t lpvs_compress_last_timing(double *out, int32_t n) {
-    if (!out || n < 0) { set_error("NULL argument"); return LPVS_EARGUMENT; }
-    for (int32_t k = 0; k < n && k < 5; ++k) out[k] = g_ctiming[k];
-    return LPVS_OK;
+    return copy_timing(out, n, g_ctiming, 5);
 }
 
 }  // extern "C"

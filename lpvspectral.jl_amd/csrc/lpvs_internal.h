@@ -130,6 +130,31 @@ template <class T> struct Staged {
         return LPVS_OK;
     }
 };
+// An output argument: device staging buffer when the caller's pointer is host memory.
+struct DevOut {
+    DevBuf own;
+    double *p = nullptr;
+    double *user = nullptr;
+    size_t bytes = 0;
+    int32_t set(double *dst, int64_t count) {
+        user = dst; bytes = sizeof(double) * (size_t)count;
+        if (is_device_ptr(dst)) { p = dst; return LPVS_OK; }
+        LPVS_TRY(own.alloc(bytes));
+        p = own.as<double>();
+        return LPVS_OK;
+    }
+    int32_t finish(hipStream_t s) {
+        if (p != user) return copy_from_device(user, p, bytes, s);
+        LPVS_HIP(hipStreamSynchronize(s));
+        return LPVS_OK;
+    }
+};
+// body of every *_last_timing accessor: the first n of a thread's `count` timing slots
+inline int32_t copy_timing(double *out, int32_t n, const double *slots, int32_t count) {
+    if (!out || n < 0) { set_error("NULL argument"); return LPVS_EARGUMENT; }
+    for (int32_t k = 0; k < n && k < count; ++k) out[k] = slots[k];
+    return LPVS_OK;
+}
 
 // ---- basis tables (basis.hip) -----------------------------------------------------------
 // Fourier regressor, column-major N x Nreg (reference layout)          src/lsfft.jl:26-49

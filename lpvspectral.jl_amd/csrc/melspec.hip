@@ -1181,9 +1181,7 @@ int32_t lpvs_mel_project_f32(const float *power, int64_t nbins, int64_t frames, 
     catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
 }
 int32_t lpvs_stft_last_timing(double *out, int32_t n) {
-    if (!out || n < 0) { set_error("NULL argument"); return LPVS_EARGUMENT; }
-    for (int32_t k = 0; k < n && k < kTimingSlots; ++k) out[k] = g_timing[k];
-    return LPVS_OK;
+    return copy_timing(out, n, g_timing, kTimingSlots);
 }
 
 }  // extern "C"

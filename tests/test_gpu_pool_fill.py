@@ -741,6 +741,8 @@ def _heatmap(L, mp):
 
 
 # ---- uneven-record periodograms ---------------------------------------------------------------------------------------------------------------
+# (tools/record_hashes.py builds its inputs with _lomb_record and _irregular and flattens results with _flat / _is_time: a change to any of
+# them changes profiles/record_hashes.txt, which then has to be made again on both builds it compares)
 def _lomb_record(N, ns, seed=0):                                                           # tests/test_gpu_lomb.py
     rng = np.random.default_rng(1000 * N + 10 * ns + seed)
     t = rng.integers(0, 40 * 1024, N) / 1024.0
