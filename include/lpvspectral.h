@@ -910,6 +910,71 @@ int32_t lpvs_bls_f64(const double *y, int64_t ns, const double *t, int64_t N, co
                      int64_t *count_out, int32_t *degenerate_out, int64_t *hist_out, int32_t *hcount_out);
 int32_t lpvs_bls_last_timing(double *out, int32_t n);
 
+/* ---- g10  fold statistics of non-uniformly sampled signals (extension): shape-agnostic period finders.  Phase dispersion minimisation
+ * with covers (PDM; Stellingwerf, ApJ 224, 953, 1978), the analysis-of-variance periodogram (AOV; Schwarzenberg-Czerny, MNRAS 241, 153,
+ * 1989: the same sums under another normalisation) and the conditional entropy (CE; Graham et al., MNRAS 434, 2629, 2013).  They find
+ * signals that are periodic but neither sinusoidal (g4, g7) nor box-shaped (g9): sawtooth pulsators, eclipsing binaries with two unequal
+ * minima, machinery with a repeating transient.  All are functions of g9's FOLD: p = f t, e = fma(f, t, -p), phi = (p - rint(p)) + e,
+ * plus 1 if negative; the bin of n bins is min(n - 1, (int)floor(phi n)).
+ * INPUTS of both.  y (N x ns column-major), t: as in g9 (finite, t in ANY order).  f[Nf] (host): finite and > 0.
+ *
+ * PDM / AOV (lpvs_pdm_f64).  W >= 0 (NULL: ones).  nbins = Nb >= 2, covers = Nc >= 1, nfine = Nb Nc in 2 .. 2048.
+ * WEIGHTS, CENTRING, QUANTISATION: g9's, by the same kernels: w_n, wy_n = w_n (y_n - ybar_c), qw_n = rint(w_n 2^60), qy_n = rint(wy_n
+ *   2^shy_c), and g9's order-free YY_c.  With W == NULL the weight of a bin is its integer count at the scale 1 / N.
+ * BINS.  The record is folded into nfine fine bins (histograms HW, HY_c, HC by integer atomic adds).  Coarse bin m, m = 0 .. nfine - 1, is
+ *   the Nc adjacent fine bins m .. m + Nc - 1, wrapping; cover m mod Nc is a partition of the period into Nb bins, and every cover is
+ *   used.  r_m, s_m: the integer sums of coarse bin m (exact subset sums); R, S: the integer totals.
+ * THE STATISTIC, in double from the integers, each converted once, evaluated as written:
+ *       sb = (sum_{m : r_m > 0} (s_m * s_m) / r_m) / Nc - (S * S) / R,
+ *   SB = sb 2^(60 - 2 shy) (with W == NULL: (sb N) 2^(-2 shy)), the between-bin sum of squares pooled over the covers, and
+ *       explained = min(1, max(SB, 0) / YY),      nonempty = M = #{m : r_m > 0}   (a property of the fold: shared by the signals).
+ *   THE ORDER OF THE SUM: thread tid of 256 adds the terms of its bins m = tid, tid + 256, ... ascending; the 64 values of a wave are added
+ *   in a tree (lane l takes lane l + 32, then l + 16, 8, 4, 2, 1); the four wave sums as (W0 + W1) + (W2 + W3).
+ * WHAT THE CALLER FORMS (the Python and Julia layers do): theta = (1 - explained) Nc (N - 1) / (Nc N - M), Stellingwerf's pooled s^2 /
+ *   sigma^2 with the samples counted once per cover (small at a period); aov = explained / (1 - explained) (N - M) / (M - 1) for Nc = 1,
+ *   the between / within F ratio (+inf where explained = 1).  Degenerate entries: theta = 1, aov = 0.
+ * OUTPUTS.  explained_out: host or device, Nf x ns column-major (element c Nf + k); nonempty_out: host int32 [Nf]; degenerate_out: host
+ *   int32, Nf x ns; hist_out: optional, host int64 [Nf][1 + ns][nfine], g9's layout over the fine bins; hcount_out: optional, host int32
+ *   [Nf][nfine].
+ * RULES.  Nothing returned is ever NaN.  A (frequency, signal) is degenerate -- explained = 0, flagged and counted, no error -- for a
+ *   constant signal (g9's rule: A_c = 0, a YY within lomb_yy_noise, or a variance that overflows), when M <= Nc (every sample in one run
+ *   of fine bins, N = 1 among them) and when Nc N <= M (no degree of freedom left within the bins).
+ *
+ * CONDITIONAL ENTROPY (lpvs_cent_f64).  Unweighted by definition: no W.  nbins in 2 .. 256 phase bins, mbins in 2 .. 64 value bins,
+ *   nbins mbins <= 8192.
+ * VALUE BINS.  Per signal ymin, ymax by integer atomic minima / maxima on an order-preserving key of the double (exact, order-free);
+ *   den = ymax - ymin, u = (y - ymin) / den, j = min(mbins - 1, (int)floor(u mbins)), formed once per sample.  den = 0 (a constant signal)
+ *   or not finite: every j = 0, H = 0, the signal is flagged degenerate.
+ * THE STATISTIC.  n_ij: the samples in phase bin i and value bin j (32-bit integer counts), n_i = sum_j n_ij.  In double, each integer
+ *   converted once:      H = (sum_{n_ij > 0} n_ij * log(n_i / n_ij)) / N        -- the Shannon entropy of the value bin given the phase
+ *   bin, in nats; every term is >= 0; the period is at the MINIMUM of H.
+ *   THE ORDER OF THE SUM: thread tid adds the terms of its cells q = i mbins + j = tid, tid + 256, ... ascending; then the same tree.
+ *   The counts may be kept in 1, 2 or 4 private copies per (frequency, signal), merged by integer additions (the plan keeps one:
+ *   csrc/fold_plan.h): the result does not depend on it.
+ * OUTPUTS.  entropy_out: host or device, Nf x ns column-major; ylim_out: host, [ns][2] = ymin, ymax; degenerate_out: host int32 [ns];
+ *   hist_out: optional, host int32 [Nf][ns][nbins][mbins].
+ *
+ * WHAT THE RESULTS MEAN.  pdm: up to a counted number of double roundings (csrc/fold_plan.h) the exact statistic of the record whose w_n
+ *   and w_n (y_n - ybar) are rounded to g9's quanta.  conditional entropy: the counts are exact; H is within c 2^-53 (1 + H) of the
+ *   entropy of the counts.
+ * ERRORS.  LPVS_EARGUMENT: a non-finite t, y, W or f; f <= 0; a negative weight or weights that sum to 0; nbins, covers, mbins outside
+ *   their ranges; N, Nf < 1; ns outside 1 .. 65535.  LPVS_EUNSUPPORTED: more than 2^30 samples or 2^24 frequencies.
+ * DETERMINISM.  Two calls give the same bits; a frequency has the same bits alone, among others and in a permuted list; a signal has the
+ *   same bits alone and among others.  A permutation of the samples changes no bit of ANY output of lpvs_cent_f64, and none of
+ *   lpvs_pdm_f64's with W == NULL and center_data = 0 (with weights or centring sum W and ybar are g4's tree sums in sample order).
+ * lpvs_pdm_last_timing / lpvs_cent_last_timing (the calling thread's last call), out[0..15]: frequencies per workgroup F, signals per pass
+ *   TS, passes, LDS bytes of a workgroup, copies of the histogram (pdm: 1), the shift of the weights (60; 0 with W == NULL; cent: 0), the
+ *   smallest and the largest shy_c (cent: 0, 0), degenerate (frequency, signal) pairs (cent: degenerate signals), whether the call was
+ *   unweighted, then milliseconds of the staging with the scan (pdm: and the moments), the quantisation (cent: the extremes and the value
+ *   bins), the fold with its epilogue, the copy-out and the total, and Nf. */
+int32_t lpvs_pdm_f64(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const double *f, int64_t Nf, int32_t nbins,
+                     int32_t covers, int32_t center_data, int32_t device, double *explained_out, int32_t *nonempty_out, int32_t *degenerate_out,
+                     int64_t *hist_out, int32_t *hcount_out);
+int32_t lpvs_pdm_last_timing(double *out, int32_t n);
+int32_t lpvs_cent_f64(const double *y, int64_t ns, const double *t, int64_t N, const double *f, int64_t Nf, int32_t nbins, int32_t mbins,
+                      int32_t device, double *entropy_out, double *ylim_out, int32_t *degenerate_out, int32_t *hist_out);
+int32_t lpvs_cent_last_timing(double *out, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,7 +21,7 @@ export ls_spectral, tls_spectral, ls_sparse_spectral, ls_sparse_spectral_lpv, ls
        SpectralExt, psd, reshape_params, ADMM, rect, hanning, autocov, autocor, isequidistant,
        melspectrogram, mfcc, mel, spectrogram, Spectrogram, MelSpectrogram, MFCC, freq, rand_cn, schedfunc,
        Periodogram, welch_pgram, periodogram, compress, heatmap, predict, residual, fva, lombscargle, lombscargle_last_timing, lombscargle_terms_last_timing,
-       lombscargle_spectrogram, lombscargle_welch, lombscargle_windows_last_timing, time_windows, wwz, wwz_radius, wwz_last_timing, bls, bls_frequencies, bls_last_timing, lombscargle_bootstrap,
+       lombscargle_spectrogram, lombscargle_welch, lombscargle_windows_last_timing, time_windows, wwz, wwz_radius, wwz_last_timing, bls, bls_frequencies, bls_last_timing, pdm, aov, conditional_entropy, pdm_last_timing, cent_last_timing, lombscargle_bootstrap,
        lombscargle_bootstrap_last_timing
 
 const LIB = get(ENV, "LPVSPECTRAL_LIB", joinpath(@__DIR__, "..", "lpvspectral.jl_amd", "liblpvspectral.so"))
@@ -1321,6 +1321,85 @@ function bls_last_timing()
     GC.@preserve tm check(@ccall LIB.lpvs_bls_last_timing(tm::Ptr{Float64}, Int32(16)::Int32)::Int32)
     (F=Int(tm[1]), ts=Int(tm[2]), passes=Int(tm[3]), lds_bytes=Int(tm[4]), shift_w=Int(tm[5]), shift_y_min=Int(tm[6]), shift_y_max=Int(tm[7]), degenerate=Int(tm[8]),
      boxes=tm[9], unit=tm[10] != 0, scan_ms=tm[11], quantise_ms=tm[12], search_ms=tm[13], copy_ms=tm[14], total_ms=tm[15], nf=Int(tm[16]))
+end
+
+# ---- fold statistics: pdm, aov, conditional_entropy (extension; include/lpvspectral.h g10) ----------------------------------------------
+"""    pdm(y, t, f; W=nothing, nbins=10, covers=1, center_data=true, return_hist=false)
+Phase dispersion minimisation (Stellingwerf 1978) with the bin covers `(Nb, Nc) = (nbins, covers)`: the record is folded into
+`nbins covers` fine bins, a coarse bin is `covers` adjacent fine bins (wrapping) and every cover is used.  Returns
+`(f, theta, aov, explained, nonempty, degenerate, nbins, covers)`: `explained` the share of the weighted variance between the bins,
+`nonempty = M` the coarse bins that hold weight, `theta = (1 - explained) covers (N - 1) / (covers N - M)` (small at a period; 1 where
+degenerate) and, for `covers = 1`, `aov = explained / (1 - explained) (N - M) / (M - 1)` (`nothing` otherwise; 0 where degenerate);
+with `return_hist=true` also `hist` (`nfine × (1 + ns) × Nf` Int64) and `hcount` (`nfine × Nf`)."""
+function pdm(y::AbstractVecOrMat{<:Real}, t::AbstractVector{<:Real}, f::AbstractVector{<:Real}; W=nothing, nbins::Integer=10, covers::Integer=1,
+             center_data::Bool=true, device::Integer=0, return_hist::Bool=false)
+    tv, fv = Vector{Float64}(t), Vector{Float64}(f)
+    N, Nf, ns = length(tv), length(fv), size(y, 2)
+    @assert size(y, 1) == N "y has to be as long as the sampling points"
+    yv = Matrix{Float64}(reshape(y, N, ns))
+    Wv = W === nothing ? Float64[] : Vector{Float64}(W)
+    @assert W === nothing || length(Wv) == N "W has to be as long as the sampling points"
+    Wp = W === nothing ? Ptr{Float64}(C_NULL) : pointer(Wv)
+    nfine = (0 < nbins <= 2048 && 0 < covers <= 2048) ? Int(nbins) * Int(covers) : 0
+    explained, nonempty, degenerate = zeros(Nf, ns), zeros(Int32, Nf), zeros(Int32, Nf, ns)
+    histv = return_hist ? zeros(Int64, nfine, 1 + ns, Nf) : Int64[]
+    hcountv = return_hist ? zeros(Int32, nfine, Nf) : Int32[]
+    histp = return_hist ? pointer(histv) : Ptr{Int64}(C_NULL)
+    hcountp = return_hist ? pointer(hcountv) : Ptr{Int32}(C_NULL)
+    GC.@preserve yv tv Wv fv explained nonempty degenerate histv hcountv check(@ccall LIB.lpvs_pdm_f64(yv::Ptr{Float64}, Int64(ns)::Int64, tv::Ptr{Float64},
+        Int64(N)::Int64, Wp::Ptr{Float64}, fv::Ptr{Float64}, Int64(Nf)::Int64, Int32(nbins)::Int32, Int32(covers)::Int32, Int32(center_data)::Int32,
+        Int32(device)::Int32, explained::Ptr{Float64}, nonempty::Ptr{Int32}, degenerate::Ptr{Int32}, histp::Ptr{Int64}, hcountp::Ptr{Int32})::Int32)
+    deg = degenerate .!= 0
+    M = Float64.(nonempty)
+    theta = ifelse.(deg, 1.0, (1.0 .- explained) .* (covers * (N - 1.0)) ./ (covers * Float64(N) .- M))
+    F = covers == 1 ? ifelse.(deg, 0.0, ifelse.(explained .< 1.0, explained ./ (1.0 .- explained) .* (N .- M) ./ (M .- 1.0), Inf)) : nothing
+    one = y isa AbstractVector
+    shaped(A) = one ? A[:, 1] : A
+    R = (f = fv, theta = shaped(theta), aov = F === nothing ? nothing : shaped(F), explained = shaped(explained), nonempty = nonempty, degenerate = shaped(deg),
+         nbins = Int(nbins), covers = Int(covers))
+    return_hist ? merge(R, (hist = histv, hcount = hcountv)) : R
+end
+"""    aov(y, t, f; W=nothing, nbins=10, center_data=true, return_hist=false)
+The analysis-of-variance periodogram (Schwarzenberg-Czerny 1989): `pdm` with one cover; `aov` is the between / within F ratio."""
+function aov(y::AbstractVecOrMat{<:Real}, t::AbstractVector{<:Real}, f::AbstractVector{<:Real}; W=nothing, nbins::Integer=10, covers::Integer=1,
+             center_data::Bool=true, device::Integer=0, return_hist::Bool=false)
+    covers == 1 || throw(ArgumentError("aov: covers must be 1, got $covers"))
+    pdm(y, t, f; W=W, nbins=nbins, covers=1, center_data=center_data, device=device, return_hist=return_hist)
+end
+fold_timing(tm) = (F=Int(tm[1]), ts=Int(tm[2]), passes=Int(tm[3]), lds_bytes=Int(tm[4]), copies=Int(tm[5]), shift_w=Int(tm[6]), shift_y_min=Int(tm[7]),
+                   shift_y_max=Int(tm[8]), degenerate=Int(tm[9]), unit=tm[10] != 0, scan_ms=tm[11], prepare_ms=tm[12], fold_ms=tm[13], copy_ms=tm[14],
+                   total_ms=tm[15], nf=Int(tm[16]))
+function pdm_last_timing()
+    tm = zeros(16)
+    GC.@preserve tm check(@ccall LIB.lpvs_pdm_last_timing(tm::Ptr{Float64}, Int32(16)::Int32)::Int32)
+    fold_timing(tm)
+end
+"""    conditional_entropy(y, t, f; nbins=10, mbins=5, return_hist=false)
+The conditional-entropy periodogram (Graham et al. 2013): the samples are counted in `nbins` phase bins times `mbins` value bins (the
+values scaled to `[min y, max y]` per signal) and `H = Σ p_ij ln(p_i / p_ij)`, in nats; the period is at the MINIMUM.  Unweighted by
+definition.  Returns `(f, entropy, ylim, degenerate)` -- `entropy` `Nf` (`× ns`), `ylim` `2 × ns`, `degenerate` per signal (a constant
+signal: entropy 0) -- and with `return_hist=true` also `hist` (`mbins × nbins × ns × Nf` Int32)."""
+function conditional_entropy(y::AbstractVecOrMat{<:Real}, t::AbstractVector{<:Real}, f::AbstractVector{<:Real}; nbins::Integer=10, mbins::Integer=5,
+                             device::Integer=0, return_hist::Bool=false)
+    tv, fv = Vector{Float64}(t), Vector{Float64}(f)
+    N, Nf, ns = length(tv), length(fv), size(y, 2)
+    @assert size(y, 1) == N "y has to be as long as the sampling points"
+    yv = Matrix{Float64}(reshape(y, N, ns))
+    ok = 0 < nbins <= 256 && 0 < mbins <= 64
+    entropy, ylim, degenerate = zeros(Nf, ns), zeros(2, ns), zeros(Int32, ns)
+    histv = return_hist ? zeros(Int32, ok ? Int(mbins) : 0, ok ? Int(nbins) : 0, ns, Nf) : Int32[]
+    histp = return_hist ? pointer(histv) : Ptr{Int32}(C_NULL)
+    GC.@preserve yv tv fv entropy ylim degenerate histv check(@ccall LIB.lpvs_cent_f64(yv::Ptr{Float64}, Int64(ns)::Int64, tv::Ptr{Float64}, Int64(N)::Int64,
+        fv::Ptr{Float64}, Int64(Nf)::Int64, Int32(nbins)::Int32, Int32(mbins)::Int32, Int32(device)::Int32, entropy::Ptr{Float64}, ylim::Ptr{Float64},
+        degenerate::Ptr{Int32}, histp::Ptr{Int32})::Int32)
+    one = y isa AbstractVector
+    R = (f = fv, entropy = one ? entropy[:, 1] : entropy, ylim = one ? ylim[:, 1] : ylim, degenerate = one ? degenerate[1] != 0 : degenerate .!= 0)
+    return_hist ? merge(R, (hist = histv,)) : R
+end
+function cent_last_timing()
+    tm = zeros(16)
+    GC.@preserve tm check(@ccall LIB.lpvs_cent_last_timing(tm::Ptr{Float64}, Int32(16)::Int32)::Int32)
+    fold_timing(tm)
 end
 
 # ---- the bootstrap of the Lomb-Scargle periodogram (extension; include/lpvspectral.h g6) -------------------------------------------------

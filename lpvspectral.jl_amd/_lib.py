@@ -200,6 +200,10 @@ SIGNATURES = {
     "lpvs_wwz_last_timing": (_I32, [_P, _I32]),
     "lpvs_bls_f64": (_I32, [_P, _I64, _P, _I64, _P, _P, _I64, _I32, _P, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "lpvs_bls_last_timing": (_I32, [_P, _I32]),
+    "lpvs_pdm_f64": (_I32, [_P, _I64, _P, _I64, _P, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+    "lpvs_pdm_last_timing": (_I32, [_P, _I32]),
+    "lpvs_cent_f64": (_I32, [_P, _I64, _P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _P]),
+    "lpvs_cent_last_timing": (_I32, [_P, _I32]),
 }
 
 _lib = None

@@ -2534,6 +2534,139 @@ def bls_last_timing():
             "quantise_ms": float(o[11]), "search_ms": float(o[12]), "copy_ms": float(o[13]), "total_ms": float(o[14]), "nf": int(o[15])}
 
 
+# ---- fold statistics: pdm, aov, conditional_entropy (include/lpvspectral.h g10; csrc/fold.hip) ------------------------------------------------
+class PDM:
+    """The result of :func:`pdm` and :func:`aov`.  ``f``: (Nf,); ``theta`` (Stellingwerf's statistic: small at a period, 1 where
+    degenerate), ``aov`` (the between / within F ratio: large at a period, 0 where degenerate, ``+inf`` where ``explained`` is 1; ``None``
+    for ``covers > 1``), ``explained`` (the share of the weighted variance between the bins, pooled over the covers, in [0, 1]) and
+    ``degenerate``: (Nf,) or (Nf, ns); ``nonempty``: (Nf,), the coarse bins that hold weight.  With ``return_hist=True`` also ``hist``
+    -- the raw integer histograms over the ``nbins covers`` fine bins, (Nf, 1 + ns, nfine) int64, laid out as :class:`BLS`'s -- and
+    ``hcount`` (Nf, nfine)."""
+
+    def __init__(self, f, theta, aov, explained, nonempty, degenerate, nbins, covers, hist=None, hcount=None):
+        self.f, self.theta, self.aov, self.explained, self.nonempty, self.degenerate = f, theta, aov, explained, nonempty, degenerate
+        self.nbins, self.covers, self.hist, self.hcount = nbins, covers, hist, hcount
+
+
+class CE:
+    """The result of :func:`conditional_entropy`.  ``f``: (Nf,); ``entropy``: (Nf,) or (Nf, ns), in nats -- the period is at its
+    MINIMUM; ``ylim``: (2,) or (ns, 2), the extremes the value bins span; ``degenerate``: a bool or (ns,), a constant signal (entropy 0);
+    with ``return_hist=True`` ``hist``: the counts, (Nf, ns, nbins, mbins) int32."""
+
+    def __init__(self, f, entropy, ylim, degenerate, nbins, mbins, hist=None):
+        self.f, self.entropy, self.ylim, self.degenerate, self.nbins, self.mbins, self.hist = f, entropy, ylim, degenerate, nbins, mbins, hist
+
+
+def pdm(y, t, f, W=None, nbins=10, covers=1, center_data=True, device=0, return_hist=False):
+    """Phase dispersion minimisation (Stellingwerf 1978) of non-uniformly sampled signals, with his overlapping bin covers
+    ``(Nb, Nc) = (nbins, covers)``: at every frequency the record is folded into ``nbins covers`` fine bins, a coarse bin is ``covers``
+    adjacent fine bins (wrapping), and every one of the ``covers`` partitions into ``nbins`` bins is used.  It makes no assumption about
+    the shape of the signal: sawtooth pulsators, binaries with unequal minima, repeating transients (csrc/fold.hip;
+    include/lpvspectral.h g10).
+
+    ``y``: (N,) or (N, ns) signals sharing the times ``t`` (numpy arrays or device tensors; ``t`` in any order); ``f``: positive
+    frequencies; ``W``: non-negative weights (``None``: ones); ``2 <= nbins covers <= 2048``.  The device returns ``explained``, the
+    share of the weighted variance that lies between the bins, pooled over the covers, and ``nonempty = M``, the coarse bins that hold
+    weight; from them ``theta = (1 - explained) covers (N - 1) / (covers N - M)`` -- Stellingwerf's ``s² / σ²``, near 1 away from a
+    period and small at one -- and, for ``covers = 1``, ``aov = explained / (1 - explained) (N - M) / (M - 1)``
+    (Schwarzenberg-Czerny 1989).
+
+    The fold uses the phases of the exact products ``f t`` and the sums are 64-bit integer sums of the quantised record
+    (csrc/bls_plan.h, csrc/fold_plan.h): a frequency or a signal has the same bits whatever else is computed in the call, and with
+    ``W=None, center_data=False`` a permutation of the samples changes no bit.  Constant signals, samples that all fall in one run of
+    fine bins and folds that leave no degree of freedom give ``explained = 0, theta = 1, aov = 0``, flagged in ``degenerate``; nothing
+    is ever NaN.  Returns a :class:`PDM`."""
+    fa = np.ascontiguousarray(np.ravel(_host(f)).astype(np.float64))
+    Nf, nbins, covers = len(fa), int(nbins), int(covers)
+    ys, N, ns, single = _lomb_signals(y)
+    ky, py, ny = as_f64(ys)
+    kt, pt, nt = as_f64(_f64_arg(t))
+    if nt != N:
+        raise ValueError(f"y has {N} samples, t has {nt}")
+    kw, pw, nw = as_f64(_f64_arg(W))
+    if W is not None and nw != N:
+        raise ValueError(f"y has {N} samples, W has {nw}")
+    nfine = nbins * covers if 0 < nbins <= 2048 and 0 < covers <= 2048 else 0
+    explained = np.zeros((ns, Nf))
+    nonempty = np.zeros(Nf, dtype=np.int32)
+    degenerate = np.zeros((ns, Nf), dtype=np.int32)
+    hist = np.zeros((Nf, 1 + ns, nfine), dtype=np.int64) if return_hist else None
+    hcount = np.zeros((Nf, nfine), dtype=np.int32) if return_hist else None
+    check(lib().lpvs_pdm_f64(py, ns, pt, N, pw, out_ptr(fa), Nf, nbins, covers, int(bool(center_data)), int(device), out_ptr(explained),
+                             out_ptr(nonempty), out_ptr(degenerate), out_ptr(hist) if return_hist else None, out_ptr(hcount) if return_hist else None))
+    del ky, kt, kw
+    deg = degenerate != 0
+    M = nonempty.astype(np.float64)[None, :]
+    with np.errstate(all="ignore"):
+        theta = np.where(deg, 1.0, (1.0 - explained) * (covers * (N - 1.0)) / (covers * float(N) - M))
+        F = None
+        if covers == 1:
+            F = np.where(deg, 0.0, np.where(explained < 1.0, explained / (1.0 - explained) * (N - M) / (M - 1.0), np.inf))
+
+    def shaped(a):                                                             # (ns, Nf) -> (Nf,) or (Nf, ns)
+        return a[0].copy() if single else np.ascontiguousarray(a.T)
+    return PDM(fa, shaped(theta), None if F is None else shaped(F), shaped(explained), nonempty, shaped(deg), nbins, covers, hist, hcount)
+
+
+def aov(y, t, f, W=None, nbins=10, covers=1, center_data=True, device=0, return_hist=False):
+    """The analysis-of-variance periodogram (Schwarzenberg-Czerny 1989): :func:`pdm` with one cover, whose ``aov`` is the F ratio of the
+    variance between the phase bins to the variance within them.  ``covers`` other than 1 is refused.  Returns a :class:`PDM`."""
+    if int(covers) != 1:
+        raise ValueError(f"aov: covers must be 1, got {covers}")
+    return pdm(y, t, f, W=W, nbins=nbins, covers=1, center_data=center_data, device=device, return_hist=return_hist)
+
+
+def pdm_last_timing():
+    """Plan and timing of the calling thread's last :func:`pdm` or :func:`aov`."""
+    o = np.zeros(16)
+    check(lib().lpvs_pdm_last_timing(out_ptr(o), 16))
+    return _fold_timing(o)
+
+
+def _fold_timing(o):
+    return {"F": int(o[0]), "ts": int(o[1]), "passes": int(o[2]), "lds_bytes": int(o[3]), "copies": int(o[4]), "shift_w": int(o[5]),
+            "shift_y_min": int(o[6]), "shift_y_max": int(o[7]), "degenerate": int(o[8]), "unit": bool(o[9]), "scan_ms": float(o[10]),
+            "prepare_ms": float(o[11]), "fold_ms": float(o[12]), "copy_ms": float(o[13]), "total_ms": float(o[14]), "nf": int(o[15])}
+
+
+def conditional_entropy(y, t, f, nbins=10, mbins=5, device=0, return_hist=False):
+    """The conditional-entropy periodogram (Graham et al. 2013) of non-uniformly sampled signals: at every frequency the samples are
+    counted in ``nbins`` phase bins times ``mbins`` value bins (the values scaled to ``[min y, max y]`` per signal), and
+    ``H = Σ p_ij ln(p_i / p_ij)`` is the Shannon entropy of the value bin given the phase bin, in nats.  A fold at the period
+    orders the samples and LOWERS it: the period is at the minimum.  It is unweighted by definition (csrc/fold.hip;
+    include/lpvspectral.h g10).  ``2 <= nbins <= 256``, ``2 <= mbins <= 64``, ``nbins mbins <= 8192``.
+
+    Every sum is an integer count: a permutation of the samples changes no bit of any output, and a frequency or a signal has the same
+    bits whatever else is computed in the call.  A constant signal has entropy 0 and is flagged in ``degenerate``.  Returns a
+    :class:`CE`."""
+    fa = np.ascontiguousarray(np.ravel(_host(f)).astype(np.float64))
+    Nf, nbins, mbins = len(fa), int(nbins), int(mbins)
+    ys, N, ns, single = _lomb_signals(y)
+    ky, py, ny = as_f64(ys)
+    kt, pt, nt = as_f64(_f64_arg(t))
+    if nt != N:
+        raise ValueError(f"y has {N} samples, t has {nt}")
+    cells = nbins * mbins if 0 < nbins <= 256 and 0 < mbins <= 64 else 0
+    entropy = np.zeros((ns, Nf))
+    ylim = np.zeros((ns, 2))
+    degenerate = np.zeros(ns, dtype=np.int32)
+    hist = np.zeros((Nf, ns, nbins, mbins) if cells else (0,), dtype=np.int32) if return_hist else None
+    check(lib().lpvs_cent_f64(py, ns, pt, N, out_ptr(fa), Nf, nbins, mbins, int(device), out_ptr(entropy), out_ptr(ylim), out_ptr(degenerate),
+                              out_ptr(hist) if return_hist else None))
+    del ky, kt
+    deg = degenerate != 0
+    if single:
+        return CE(fa, entropy[0].copy(), ylim[0].copy(), bool(deg[0]), nbins, mbins, hist)
+    return CE(fa, np.ascontiguousarray(entropy.T), ylim, deg, nbins, mbins, hist)
+
+
+def cent_last_timing():
+    """Plan and timing of the calling thread's last :func:`conditional_entropy`; ``copies``: the private copies of the count histogram."""
+    o = np.zeros(16)
+    check(lib().lpvs_cent_last_timing(out_ptr(o), 16))
+    return _fold_timing(o)
+
+
 # ---- false-alarm probabilities of the Lomb-Scargle periodogram: the device bootstrap and the closed forms (include/lpvspectral.h g6) ------
 _M32 = np.uint64(0xFFFFFFFF)
 

@@ -22,6 +22,7 @@
 // No cooperative launch, no spin-wait, nothing crosses workgroups but the degenerate counter (an integer atomic add).
 #include "lpvs_internal.h"
 #include "bls_plan.h"
+#include "fold_device.h"
 
 namespace lpvs {
 namespace {
@@ -86,43 +87,11 @@ bls_quantise_kernel(const double *__restrict__ y, const double *__restrict__ w, 
     }
 }
 
-// the phase bin of (f, t): the fractional part of the exact product f t
-__device__ inline int bls_bin(double f, double t, int nbins, double dnbins) {
-    const double p = f * t, e = fma(f, t, -p);
-    double phi = (p - rint(p)) + e;
-    if (phi < 0.0) phi = phi + 1.0;
-    const int b = (int)floor(phi * dnbins);
-    return b < 0 ? 0 : b < nbins - 1 ? b : nbins - 1;                      // (b < 0: only when f t overflows and phi is not a number)
-}
-
 // candidate (d, k, b) against the best so far (bd, bk, bb); a width of 0 is "none"
 __device__ inline bool bls_better(double d, int k, int b, double bd, int bk, int bb) {
     if (k == 0) return false;
     if (bk == 0) return true;
     return d > bd || (d == bd && (k < bk || (k == bk && b < bb)));
-}
-
-// the sum over the bins b .. b + k - 1 (wrapping) of a row from its inclusive prefix sums I: before = I[b - 1] (0 for b = 0), total = I[nb - 1]
-template <typename T>
-__device__ inline T bls_box(const T *I, int nb, int b, int k, T before, T total) {
-    const int e = b + k;
-    return e <= nb ? I[e - 1] - before : (total - before) + I[e - nb - 1];
-}
-
-// inclusive prefix sums of a row in place, by one wave: lane l owns the bins l chunk .. (l + 1) chunk - 1
-template <typename T>
-__device__ inline void bls_prefix_row(T *H, int nb, int lane) {
-    const int chunk = (nb + 63) / 64, lo = lane * chunk, hi = lo + chunk < nb ? lo + chunk : nb;
-    T sum = 0;
-    for (int i = lo; i < hi; ++i) sum += H[i];
-    T incl = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T up = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += up;
-    }
-    T run = incl - sum;
-    for (int i = lo; i < hi; ++i) { run += H[i]; H[i] = run; }
 }
 
 template <int F, int TS, bool UNIT>

@@ -18,6 +18,7 @@
 #include "lomb_terms_plan.h"
 #include "wwz_plan.h"
 #include "bls_plan.h"
+#include "fold_plan.h"
 #include "pool_plan.h"
 
 namespace lpvs {
@@ -364,6 +365,38 @@ int32_t launch_bls_max(const double *y, const double *wy, const double *mean_dev
 int32_t launch_bls_quantise(const double *y, const double *w, const double *wy, const double *mean_dev, bool center, int64_t N, int64_t ns, int log2n,
                             const int32_t *shy_dev, const unsigned long long *amax_dev, long long *qw, long long *qy, long long *yyacc_dev, hipStream_t s);
 int32_t launch_bls(const BlsArgs &A, const BlsPlan &plan, hipStream_t s);
+
+// fold statistics (lpvs_pdm_f64, lpvs_cent_f64; fold.hip; the decisions: fold_plan.h).  All pointers are device memory.
+struct PdmArgs {
+    const double *t = nullptr;                                   // [N]
+    const long long *qw = nullptr, *qy = nullptr;                // the quantised record, as BlsArgs has it
+    const double *f = nullptr;                                   // [Nf]
+    const int32_t *shy = nullptr;                                // [2 ns], as BlsArgs has them
+    const unsigned long long *amax = nullptr;                    // [2 ns]
+    const long long *yyacc = nullptr;                            // [2 ns]
+    const double *mom = nullptr;                                 // launch_lomb_moments' mom_dev
+    int64_t N = 0, Nf = 0;
+    int ns = 0, nfine = 0, covers = 1, center = 1, log2n = 0;
+    double *explained = nullptr;                                 // [ns][Nf]
+    int32_t *nonempty = nullptr, *degenerate = nullptr;          // [Nf], [ns][Nf]
+    long long *hist = nullptr;                                   // [Nf][1 + ns][nfine] or nullptr
+    int32_t *hcount = nullptr;                                   // [Nf][nfine] or nullptr
+    unsigned long long *ndeg = nullptr;                          // the degenerate (frequency, signal) pairs
+};
+int32_t launch_pdm(const PdmArgs &A, const PdmPlan &plan, hipStream_t s);
+struct CentArgs {
+    const double *t = nullptr, *f = nullptr;                     // [N], [Nf]
+    const unsigned char *vbin = nullptr;                         // [ns][N]: the value bin of every sample
+    const unsigned long long *lim = nullptr;                     // [2 ns]: the keys of ymin_c, then of ymax_c (fold_plan.h: fold_key)
+    int64_t N = 0, Nf = 0;
+    int ns = 0, nbins = 0, mbins = 0;
+    double *entropy = nullptr;                                   // [ns][Nf]
+    int32_t *hist = nullptr;                                     // [Nf][ns][nbins][mbins] or nullptr
+};
+// lim_dev[2 ns]: initialised here; then vbin[ns][N], ylim[ns][2] (doubles) and degenerate[ns]
+int32_t launch_cent_prepare(const double *y, int64_t N, int64_t ns, int mbins, unsigned long long *lim_dev, unsigned char *vbin, double *ylim_dev,
+                            int32_t *degenerate_dev, hipStream_t s);
+int32_t launch_cent(const CentArgs &A, const CentPlan &plan, hipStream_t s);
 
 // ---- dense symmetric inverse (linalg.hip) ------------------------------------------------
 // In-place inverse of the SPD matrix A (np x np, np % 64 == 0, full symmetric storage) by

@@ -1,5 +1,6 @@
-// uneven.hip -- the transforms of unevenly sampled records: lombscargle, its several-harmonic, windowed and bootstrap forms, wwz and bls.
-// Host drivers and entry points; the kernels are in lomb.hip, lomb_terms.hip, lomb_boot.hip, wwz.hip and bls.hip.
+// uneven.hip -- the transforms of unevenly sampled records: lombscargle, its several-harmonic, windowed and bootstrap forms, wwz, bls and the
+// fold statistics (pdm / aov, conditional_entropy).
+// Host drivers and entry points; the kernels are in lomb.hip, lomb_terms.hip, lomb_boot.hip, wwz.hip, bls.hip and fold.hip.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -36,7 +37,7 @@ template <int K> struct PhaseClock {
 };
 
 // what check() asks of the scan's sum of the weights
-enum class WeightSum { positive, finite, unused };   // lombscargle, bls | wwz: a zero sum leaves every cell empty | windows: each window has its own
+enum class WeightSum { positive, finite, unused };   // lombscargle, bls, pdm | wwz: a zero sum leaves every cell empty | windows: each window has its own
 
 // The record (t[N], y[ns][N], W[N] or nullptr) of a call, resident on the device, and its small device record
 //     [sum W | the weighted means: ns | launch_lomb_moments' moments: 3 ns | tail | flags word]
@@ -718,6 +719,180 @@ int32_t lpvs_bls_f64(const double *y, int64_t ns, const double *t, int64_t N, co
 
 int32_t lpvs_bls_last_timing(double *out, int32_t n) {
     return copy_timing(out, n, g_bls_timing, 16);
+}
+
+// ---- fold statistics: pdm / aov and the conditional entropy (fold.hip; the decisions: fold_plan.h) ------------------------------------------------
+// what lpvs_pdm_last_timing reports of the calling thread's last call: [0] frequencies per workgroup (F), [1] signals per pass (TS),
+// [2] passes, [3] LDS bytes of a workgroup, [4] copies (1: pdm keeps one histogram), [5] the shift of the weights (60; 0 with unit
+// weights), [6], [7] the smallest and largest shift of a signal (0, 0 when every signal is constant), [8] degenerate (frequency, signal)
+// pairs, [9] unit weights, ms of [10] staging, the scan and the moments, [11] the maxima and the quantisation, [12] fold and pooling,
+// [13] the copy-out, [14] total, [15] Nf
+static thread_local double g_pdm_timing[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+static int32_t pdm_impl(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const double *f, int64_t Nf, int32_t covers, bool center,
+                        const PdmPlan &plan, int32_t device, double *explained, int32_t *nonempty_out, int32_t *degenerate_out, int64_t *hist_out,
+                        int32_t *hcount_out) {
+    LPVS_TRY(Record::admit(device));
+    hipStream_t s = nullptr;
+    PhaseClock<5> clock;
+    LPVS_TRY(clock.init(s));
+    Record rec; DevOut dexp;
+    DevBuf dscan, dq, dfreq, dshy, dint, dhist, dhcount;
+    DrainOnExit drain(s);
+    LPVS_TRY(clock.mark(0));
+    LPVS_TRY(rec.stage(t, y, W, N, ns, device, s));
+    const int64_t ncols = Nf * ns, nfine = plan.nfine;
+    LPVS_TRY(dexp.set(explained, ncols));
+    // the tail of the small record: the maxima (2 ns), the two words of every YY (2 ns), the degenerate counter
+    LPVS_TRY(rec.alloc_small((size_t)(4 * ns) + 1));
+    unsigned long long *amax_dev = rec.tail<unsigned long long>();
+    long long *yyacc_dev = reinterpret_cast<long long *>(amax_dev + 2 * ns);
+    unsigned long long *ndeg_dev = amax_dev + 4 * ns;
+    LPVS_TRY(dscan.alloc(sizeof(double) * (size_t)(3 * ns * lomb_sum_slabs(N))));
+    LPVS_TRY(rec.scan(dscan.as<double>()));
+    LPVS_TRY(rec.check("pdm", WeightSum::positive));
+    LPVS_TRY(rec.moments(center, dscan.as<double>()));
+    LPVS_TRY(clock.mark(1));
+    // the maxima, the shifts (bls_plan.h), the quantised record: qy[ns][N], then qw[N] with weights
+    LPVS_TRY(launch_bls_max(rec.y.p, rec.wy.as<double>(), rec.mean_dev, center, N, ns, amax_dev, s));
+    std::vector<unsigned long long> hmax((size_t)(2 * ns));
+    LPVS_TRY(copy_from_device(hmax.data(), amax_dev, sizeof(unsigned long long) * (size_t)(2 * ns), s));
+    std::vector<int32_t> hshy((size_t)(2 * ns), 0);
+    int shy_lo = 0, shy_hi = 0; bool any = false;
+    for (int64_t c = 0; c < ns; ++c) {
+        double A, M;
+        memcpy(&A, &hmax[(size_t)c], sizeof(double)); memcpy(&M, &hmax[(size_t)(ns + c)], sizeof(double));
+        hshy[(size_t)(ns + c)] = M > 0.0 && std::isfinite(M) ? bls_shift_y(M, N) : kBlsNoShift;
+        if (!(A > 0.0)) continue;
+        const int sh = bls_shift_y(A, N);
+        hshy[(size_t)c] = sh;
+        shy_lo = any && shy_lo < sh ? shy_lo : sh;
+        shy_hi = any && shy_hi > sh ? shy_hi : sh;
+        any = true;
+    }
+    LPVS_TRY(dshy.alloc(sizeof(int32_t) * (size_t)(2 * ns)));
+    LPVS_TRY(copy_to_device(dshy.p, hshy.data(), sizeof(int32_t) * (size_t)(2 * ns), s));
+    LPVS_TRY(dq.alloc(sizeof(long long) * (size_t)(N * (ns + (plan.unit ? 0 : 1)))));
+    long long *qy_dev = dq.as<long long>(), *qw_dev = plan.unit ? nullptr : qy_dev + N * ns;
+    LPVS_TRY(launch_bls_quantise(rec.y.p, rec.w.as<double>(), rec.wy.as<double>(), rec.mean_dev, center, N, ns, plan.log2n, dshy.as<int32_t>(), amax_dev, qw_dev, qy_dev, yyacc_dev, s));
+    LPVS_TRY(dfreq.alloc(sizeof(double) * (size_t)Nf));
+    LPVS_TRY(copy_to_device(dfreq.p, f, sizeof(double) * (size_t)Nf, s));
+    LPVS_TRY(dint.alloc(sizeof(int32_t) * (size_t)(ncols + Nf)));
+    if (hist_out) LPVS_TRY(dhist.alloc(sizeof(int64_t) * (size_t)(Nf * (1 + ns) * nfine)));
+    if (hcount_out) LPVS_TRY(dhcount.alloc(sizeof(int32_t) * (size_t)(Nf * nfine)));
+    PdmArgs A;
+    A.t = rec.t.p; A.qw = qw_dev; A.qy = qy_dev; A.f = dfreq.as<double>();
+    A.shy = dshy.as<int32_t>(); A.amax = amax_dev; A.yyacc = yyacc_dev; A.mom = rec.mom_dev; A.log2n = plan.log2n;
+    A.N = N; A.Nf = Nf; A.ns = (int)ns; A.nfine = plan.nfine; A.covers = covers; A.center = center ? 1 : 0;
+    A.explained = dexp.p; A.degenerate = dint.as<int32_t>(); A.nonempty = A.degenerate + ncols;
+    A.hist = hist_out ? dhist.as<long long>() : nullptr; A.hcount = hcount_out ? dhcount.as<int32_t>() : nullptr; A.ndeg = ndeg_dev;
+    LPVS_TRY(clock.mark(2));
+    LPVS_TRY(launch_pdm(A, plan, s));
+    LPVS_TRY(clock.mark(3));
+    unsigned long long ndeg = 0;
+    LPVS_TRY(copy_from_device(&ndeg, ndeg_dev, sizeof(ndeg), s));
+    LPVS_TRY(copy_from_device(nonempty_out, A.nonempty, sizeof(int32_t) * (size_t)Nf, s));
+    LPVS_TRY(copy_from_device(degenerate_out, A.degenerate, sizeof(int32_t) * (size_t)ncols, s));
+    if (hist_out) LPVS_TRY(copy_from_device(hist_out, dhist.p, sizeof(int64_t) * (size_t)(Nf * (1 + ns) * nfine), s));
+    if (hcount_out) LPVS_TRY(copy_from_device(hcount_out, dhcount.p, sizeof(int32_t) * (size_t)(Nf * nfine), s));
+    LPVS_TRY(dexp.finish(s));
+    LPVS_TRY(clock.finish());
+    double *g = g_pdm_timing;
+    g[0] = plan.F; g[1] = plan.ts; g[2] = plan.passes; g[3] = (double)plan.lds_bytes; g[4] = 1; g[5] = plan.unit ? 0 : kBlsWeightShift; g[6] = shy_lo; g[7] = shy_hi;
+    g[8] = (double)ndeg; g[9] = plan.unit; g[15] = (double)Nf;
+    for (int i = 0; i < 4; ++i) g[10 + i] = clock.ms(i);
+    g[14] = clock.total();
+    return LPVS_OK;
+}
+
+int32_t lpvs_pdm_f64(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const double *f, int64_t Nf, int32_t nbins, int32_t covers,
+                     int32_t center_data, int32_t device, double *explained_out, int32_t *nonempty_out, int32_t *degenerate_out, int64_t *hist_out,
+                     int32_t *hcount_out) {
+    try {
+        if (!y || !t || !f || !explained_out || !nonempty_out || !degenerate_out) { set_error("NULL argument"); return LPVS_EARGUMENT; }
+        if (is_device_ptr(f) || is_device_ptr(nonempty_out) || is_device_ptr(degenerate_out) || (hist_out && is_device_ptr(hist_out)) ||
+            (hcount_out && is_device_ptr(hcount_out))) {
+            set_error("pdm: f, nonempty_out, degenerate_out, hist_out and hcount_out are host memory"); return LPVS_EARGUMENT;
+        }
+        const PdmPlan plan = pdm_plan(N, ns, f, Nf, nbins, covers, W == nullptr);   // (the counts are checked before an array is read)
+        if (plan.status != kFoldOk) { set_error("%s", plan.why.c_str()); return plan.status == kFoldArgument ? LPVS_EARGUMENT : LPVS_EUNSUPPORTED; }
+        return pdm_impl(y, ns, t, N, W, f, Nf, covers, center_data != 0, plan, device, explained_out, nonempty_out, degenerate_out, hist_out, hcount_out);
+    } catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
+}
+
+int32_t lpvs_pdm_last_timing(double *out, int32_t n) {
+    return copy_timing(out, n, g_pdm_timing, 16);
+}
+
+// what lpvs_cent_last_timing reports of the calling thread's last call: [0] F, [1] TS, [2] passes, [3] LDS bytes of a workgroup, [4] copies
+// of the count histogram, [5], [6], [7] 0 (nothing is quantised: no shifts), [8] degenerate signals, [9] 1 (unweighted), ms of
+// [10] staging and the scan, [11] the extremes and the value bins, [12] fold and entropy, [13] the copy-out, [14] total, [15] Nf
+static thread_local double g_cent_timing[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+static int32_t cent_impl(const double *y, int64_t ns, const double *t, int64_t N, const double *f, int64_t Nf, int32_t nbins, int32_t mbins, const CentPlan &plan,
+                         int32_t device, double *entropy, double *ylim_out, int32_t *degenerate_out, int32_t *hist_out) {
+    LPVS_TRY(Record::admit(device));
+    hipStream_t s = nullptr;
+    PhaseClock<5> clock;
+    LPVS_TRY(clock.init(s));
+    Record rec; DevOut dent;
+    DevBuf dscan, dvbin, dfreq, dlim, dhist;
+    DrainOnExit drain(s);
+    LPVS_TRY(clock.mark(0));
+    LPVS_TRY(rec.stage(t, y, nullptr, N, ns, device, s));
+    LPVS_TRY(dent.set(entropy, Nf * ns));
+    // the tail of the small record: the keys of the extremes (2 ns); no moments: nothing is weighted or centred
+    LPVS_TRY(rec.alloc_small((size_t)(2 * ns), false));
+    unsigned long long *lim_dev = rec.tail<unsigned long long>();
+    LPVS_TRY(dscan.alloc(sizeof(double) * (size_t)(3 * ns * lomb_sum_slabs(N))));
+    LPVS_TRY(rec.scan(dscan.as<double>()));
+    LPVS_TRY(rec.check("conditional_entropy", WeightSum::unused));
+    LPVS_TRY(clock.mark(1));
+    LPVS_TRY(dvbin.alloc((size_t)(N * ns)));
+    LPVS_TRY(dlim.alloc(sizeof(double) * (size_t)(2 * ns) + sizeof(int32_t) * (size_t)ns));
+    double *ylim_dev = dlim.as<double>();
+    int32_t *deg_dev = reinterpret_cast<int32_t *>(ylim_dev + 2 * ns);
+    LPVS_TRY(launch_cent_prepare(rec.y.p, N, ns, mbins, lim_dev, dvbin.as<unsigned char>(), ylim_dev, deg_dev, s));
+    LPVS_TRY(dfreq.alloc(sizeof(double) * (size_t)Nf));
+    LPVS_TRY(copy_to_device(dfreq.p, f, sizeof(double) * (size_t)Nf, s));
+    const int64_t nhist = Nf * ns * plan.cells;
+    if (hist_out) LPVS_TRY(dhist.alloc(sizeof(int32_t) * (size_t)nhist));
+    CentArgs A;
+    A.t = rec.t.p; A.f = dfreq.as<double>(); A.vbin = dvbin.as<unsigned char>(); A.lim = lim_dev;
+    A.N = N; A.Nf = Nf; A.ns = (int)ns; A.nbins = nbins; A.mbins = mbins;
+    A.entropy = dent.p; A.hist = hist_out ? dhist.as<int32_t>() : nullptr;
+    LPVS_TRY(clock.mark(2));
+    LPVS_TRY(launch_cent(A, plan, s));
+    LPVS_TRY(clock.mark(3));
+    LPVS_TRY(copy_from_device(ylim_out, ylim_dev, sizeof(double) * (size_t)(2 * ns), s));
+    LPVS_TRY(copy_from_device(degenerate_out, deg_dev, sizeof(int32_t) * (size_t)ns, s));
+    if (hist_out) LPVS_TRY(copy_from_device(hist_out, dhist.p, sizeof(int32_t) * (size_t)nhist, s));
+    LPVS_TRY(dent.finish(s));
+    LPVS_TRY(clock.finish());
+    int64_t ndeg = 0;
+    for (int64_t c = 0; c < ns; ++c) ndeg += degenerate_out[c] != 0;
+    double *g = g_cent_timing;
+    g[0] = plan.F; g[1] = plan.ts; g[2] = plan.passes; g[3] = (double)plan.lds_bytes; g[4] = plan.copies; g[5] = g[6] = g[7] = 0;
+    g[8] = (double)ndeg; g[9] = 1; g[15] = (double)Nf;
+    for (int i = 0; i < 4; ++i) g[10 + i] = clock.ms(i);
+    g[14] = clock.total();
+    return LPVS_OK;
+}
+
+int32_t lpvs_cent_f64(const double *y, int64_t ns, const double *t, int64_t N, const double *f, int64_t Nf, int32_t nbins, int32_t mbins, int32_t device,
+                      double *entropy_out, double *ylim_out, int32_t *degenerate_out, int32_t *hist_out) {
+    try {
+        if (!y || !t || !f || !entropy_out || !ylim_out || !degenerate_out) { set_error("NULL argument"); return LPVS_EARGUMENT; }
+        if (is_device_ptr(f) || is_device_ptr(ylim_out) || is_device_ptr(degenerate_out) || (hist_out && is_device_ptr(hist_out))) {
+            set_error("conditional_entropy: f, ylim_out, degenerate_out and hist_out are host memory"); return LPVS_EARGUMENT;
+        }
+        const char *knob = experiment_env("LPVS_CENT_COPIES");
+        const CentPlan plan = cent_plan(N, ns, f, Nf, nbins, mbins, knob ? atoll(knob) : 0);   // (the counts are checked before an array is read)
+        if (plan.status != kFoldOk) { set_error("%s", plan.why.c_str()); return plan.status == kFoldArgument ? LPVS_EARGUMENT : LPVS_EUNSUPPORTED; }
+        return cent_impl(y, ns, t, N, f, Nf, nbins, mbins, plan, device, entropy_out, ylim_out, degenerate_out, hist_out);
+    } catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
+}
+
+int32_t lpvs_cent_last_timing(double *out, int32_t n) {
+    return copy_timing(out, n, g_cent_timing, 16);
 }
 
 // ---- the bootstrap of the Lomb-Scargle periodogram (lomb_boot.hip; the decisions: lomb_boot_plan.h) ------------------------------------------
