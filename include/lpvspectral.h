@@ -975,6 +975,65 @@ int32_t lpvs_cent_f64(const double *y, int64_t ns, const double *t, int64_t N, c
                       int32_t device, double *entropy_out, double *ylim_out, int32_t *degenerate_out, int32_t *hist_out);
 int32_t lpvs_cent_last_timing(double *out, int32_t n);
 
+/* ---- g11  CLEAN deconvolution of the spectrum of a non-uniformly sampled signal (extension; Roberts, Lehar & Dreher, AJ 93, 968, 1987).
+ * Every estimator above treats a frequency on its own, and uneven sampling convolves every line with the spectral window: one sinusoid
+ * shows as a forest of sidelobes and aliases.  CLEAN takes the dirty spectrum D and the window Wn and greedily subtracts the window's
+ * response to the strongest line; what is left is a short list of complex components C and a residual R.  It is the greedy twin of g2's
+ * sparse fit and needs no Gram and no factorisation.  Complex values are interleaved (re, im) doubles throughout.
+ * GRID.  f_m = m df (the double product), m = 0 .. 2 K, K = Nf - 1.  D_k is used for k = 0 .. K, Wn_m for m = 0 .. 2 K, and
+ *   Wn_{-m} = conj(Wn_m).  All index arithmetic is on m, never on rounded frequencies.
+ * THE DIRTY STAGE (lpvs_dirty_spectrum_f64).  y (N x ns column-major), t, W >= 0 (NULL: ones), center_data, path: as in g4, through the
+ *   same kernels: w = W / sum W, y_c = y - ybar (center_data) and
+ *       Wn_m = sum_n w_n e^{-2 pi i f_m t_n} = (C_m, -S_m),     D_k = sum_n w_n y_c,n e^{-2 pi i f_k t_n} = (YC_k, -YS_k)
+ *   are g4's sums C, S, YC, YS on the 2 Nf - 1 frequencies, with exact-product phases in g4's fixed order on the direct path and by its
+ *   transforms on the NUFFT path (path 0 chooses as g4 does).  D_out: [ns][Nf] complex, Wn_out: [2 Nf - 1] complex; host or device.
+ * ADMISSIBLE BINS.  den_p = 1 - (Re Wn_2p Re Wn_2p + Im Wn_2p Im Wn_2p); bin p is admissible iff den_p >= 2^-20.  This drops p = 0
+ *   (Wn_0 = 1) and the Nyquist aliases of a uniform record; nothing else is special-cased.
+ * THE LOOP (lpvs_clean_loop_f64), per signal, R = D and C = 0 to begin with; iteration i = 0 .. niter - 1:
+ *   1. P_k = Re R_k Re R_k + Im R_k Im R_k.  p: the admissible bin of the largest P, the lowest index among equal ones (a NaN is never
+ *      the largest).
+ *   2. No admissible bin: stop, status 2 (empty).
+ *   3. tol > 0 and P_p <= (tol tol) P0, P0 the P_p of iteration 0: stop, status 1 (tol).  tol = 0 never stops.
+ *   4. With R_p = (r, q), Wn_2p = (u, v):   tr = r u + q v,  ti = r v - q u  (conj(R_p) Wn_2p),
+ *      a = ((r - tr) / den_p, (q - ti) / den_p),   c = (gain Re a, gain Im a) = (cr, ci).
+ *   5. C_p = C_p + c (componentwise).  (p, c) is entry i of the pick list.
+ *   6. For every k = 0 .. K, with Wn_{k-p} = (a1, b1) (b1 negated where k < p) and Wn_{k+p} = (a2, b2):
+ *          ur = (cr a1 - ci b1) + (cr a2 + ci b2),   ui = (cr b1 + ci a1) + (cr b2 - ci a2),   R_k = (Re R_k - ur, Im R_k - ui).
+ *   7. The count runs out: status 0 (niter).
+ *   Every product, sum and quotient is one rounded double operation, in the order written; nothing is fused.  The result therefore does
+ *   not depend on how the arg-max is reduced, on the thread count or on where the residual lives.
+ *   INPUTS: D [ns][Nf], Wn [2 Nf - 1] (one window for all signals), host or device; gain in (0, 2); 0 <= niter <= 2^24; tol in [0, 1).
+ *   OUTPUTS: R_out, C_out: [ns][Nf] complex, host or device.  picks_out: host int32 [ns][niter], the bins in the order picked, -1 behind
+ *   the last; pickval_out: [ns][niter] complex, host or device, the c of each pick, 0 behind the last; iters_out, status_out: host int32
+ *   [ns], the picks made and why the loop ended.
+ * RESTORATION (lpvs_clean_restore_f64).  B_m = exp(-(x x) / (2 (sigma sigma))), x = (double)m df: a real Gaussian beam, so phases refer
+ *   to the epoch of t.   S_k = R_k + sum_p [C_p B_{k-p} + conj(C_p) B_{k+p}] over the p with C_p != 0 in increasing p, each term added as
+ *   (Re C_p B_{|k-p|} + Re C_p B_{k+p}, Im C_p B_{|k-p|} - Im C_p B_{k+p}).  sigma > 0 is the caller's: the Python and Julia layers fit it
+ *   to the window, sigma = h / sqrt(2 ln 2) with h the half-power half width of the main lobe -- the first m with |Wn_m|^2 < 1/2,
+ *   interpolated linearly in |Wn|^2 (csrc/clean_plan.h: clean_sigma).  S_out: [ns][Nf] complex, host or device.
+ * lpvs_clean_f64: the three stages in one call; D, Wn and R stay on the device between them.  sigma = 0 asks the library for the fit
+ *   above; sigma_out (optional, host) receives the width used.  Every output has the bits the three separate calls give.
+ * NOT COVERED: one signal is one workgroup (a lone signal uses one compute unit: the loop is bound by latency, and a barrier across
+ *   workgroups would cost more than an iteration); beams other than the Gaussian; several harmonics per component (g7).
+ * ERRORS.  LPVS_EARGUMENT: Nf < 2; niter < 0; gain outside (0, 2); tol outside [0, 1); df <= 0 or not finite; sigma <= 0 (restore) or < 0
+ *   (clean) or not finite; N < 1; ns outside 1 .. 65535; a path other than 0, 1, 2; a non-finite t, y, W, D or Wn; a negative weight or
+ *   weights that sum to 0.  LPVS_EUNSUPPORTED: Nf > 2^20; niter > 2^24; ns niter > 2^28.
+ * DETERMINISM.  Two calls give the same bits; a signal has the same bits alone and among others.
+ * lpvs_clean_last_timing (the calling thread's last call of any of the four; 0 where the call had no such stage), out[0..13]: the path
+ *   of the sums (1 direct, 2 transforms), where the residual lived (1 LDS, 2 global memory), the threads of the loop's workgroup, its LDS
+ *   bytes, the fewest and the most iterations of a signal, the admissible bins, then milliseconds of the staging with the scan and the
+ *   moments, the sums, the loop, the restoration, the copy-out and the total, and sigma. */
+int32_t lpvs_dirty_spectrum_f64(const double *y, int64_t ns, const double *t, int64_t N, const double *W, double df, int64_t Nf, int32_t center_data,
+                                int32_t path, int32_t device, double *D_out, double *Wn_out);
+int32_t lpvs_clean_loop_f64(const double *D, int64_t ns, int64_t Nf, const double *Wn, double gain, int64_t niter, double tol, int32_t device,
+                            double *R_out, double *C_out, int32_t *picks_out, double *pickval_out, int32_t *iters_out, int32_t *status_out);
+int32_t lpvs_clean_restore_f64(const double *R, const double *C, int64_t ns, int64_t Nf, double df, double sigma, int32_t device, double *S_out);
+int32_t lpvs_clean_f64(const double *y, int64_t ns, const double *t, int64_t N, const double *W, double df, int64_t Nf, int32_t center_data,
+                       int32_t path, double gain, int64_t niter, double tol, double sigma, int32_t device, double *D_out, double *Wn_out,
+                       double *R_out, double *C_out, int32_t *picks_out, double *pickval_out, int32_t *iters_out, int32_t *status_out,
+                       double *S_out, double *sigma_out);
+int32_t lpvs_clean_last_timing(double *out, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif

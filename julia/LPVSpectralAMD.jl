@@ -21,7 +21,7 @@ export ls_spectral, tls_spectral, ls_sparse_spectral, ls_sparse_spectral_lpv, ls
        SpectralExt, psd, reshape_params, ADMM, rect, hanning, autocov, autocor, isequidistant,
        melspectrogram, mfcc, mel, spectrogram, Spectrogram, MelSpectrogram, MFCC, freq, rand_cn, schedfunc,
        Periodogram, welch_pgram, periodogram, compress, heatmap, predict, residual, fva, lombscargle, lombscargle_last_timing, lombscargle_terms_last_timing,
-       lombscargle_spectrogram, lombscargle_welch, lombscargle_windows_last_timing, time_windows, wwz, wwz_radius, wwz_last_timing, bls, bls_frequencies, bls_last_timing, pdm, aov, conditional_entropy, pdm_last_timing, cent_last_timing, lombscargle_bootstrap,
+       lombscargle_spectrogram, lombscargle_welch, lombscargle_windows_last_timing, time_windows, wwz, wwz_radius, wwz_last_timing, bls, bls_frequencies, bls_last_timing, pdm, aov, conditional_entropy, pdm_last_timing, cent_last_timing, dirty_spectrum, clean_loop, clean_restore, clean, clean_sigma, clean_last_timing, lombscargle_bootstrap,
        lombscargle_bootstrap_last_timing
 
 const LIB = get(ENV, "LPVSPECTRAL_LIB", joinpath(@__DIR__, "..", "lpvspectral.jl_amd", "liblpvspectral.so"))
@@ -1400,6 +1400,116 @@ function cent_last_timing()
     tm = zeros(16)
     GC.@preserve tm check(@ccall LIB.lpvs_cent_last_timing(tm::Ptr{Float64}, Int32(16)::Int32)::Int32)
     fold_timing(tm)
+end
+
+# ---- CLEAN deconvolution: dirty_spectrum, clean_loop, clean_restore, clean (extension; include/lpvspectral.h g11) ---------------------------
+const CLEAN_STATUS = (:niter, :tol, :empty)
+_cplx(A::Array{Float64}) = dropdims(copy(reinterpret(ComplexF64, A)); dims=1)      # (2, ...) interleaved doubles -> complex
+_ri(A::AbstractArray{<:Complex}) = Array{Float64}(reinterpret(Float64, reshape(Array{ComplexF64}(A), 1, size(A)...)))
+function _clean_grid(t, df, Nf)
+    df = df === nothing ? 1 / (4 * (maximum(t) - minimum(t))) : Float64(df)
+    Nf = Nf === nothing ? max(2, floor(Int, default_freqs(t)[end] / df) + 1) : Int(Nf)
+    df, Nf
+end
+"""    clean_sigma(Wn, df)
+The width of the Gaussian restoring beam fitted to the spectral window: the first `m` with `|Wn_m|² < 1/2`, interpolated linearly in
+`|Wn|²`, is the half width `h`; `sigma = h / sqrt(2 ln 2)` (the operations of csrc/clean_plan.h `clean_sigma`, in its order)."""
+function clean_sigma(Wn::AbstractVector{<:Complex}, df::Real)
+    P = real.(Wn) .* real.(Wn) .+ imag.(Wn) .* imag.(Wn)
+    for m in 2:length(P)
+        if P[m] < 0.5
+            frac = P[m-1] > P[m] ? (P[m-1] - 0.5) / (P[m-1] - P[m]) : 0.0
+            return ((Float64(m - 2) + frac) * Float64(df)) * 0.8493218002880191
+        end
+    end
+    (Float64(length(P) - 1) * Float64(df)) * 0.8493218002880191
+end
+"""    dirty_spectrum(y, t; df=nothing, Nf=nothing, W=nothing, center_data=true, path=:auto)
+The dirty spectrum `D_k = Σ w y_c e^{-2πi f_k t}` (`Nf` (`× ns`)) and the spectral window `Wn_m = Σ w e^{-2πi f_m t}` (`2 Nf - 1`) on the
+grid `f_m = m df`: `lombscargle`'s sums by its kernels and paths.  Defaults: `df = 1 / (4 (max t - min t))`, `Nf` up to
+`default_freqs(t)`'s top frequency.  Returns `(D, Wn)`."""
+function dirty_spectrum(y::AbstractVecOrMat{<:Real}, t::AbstractVector{<:Real}; df=nothing, Nf=nothing, W=nothing, center_data::Bool=true,
+                        path::Symbol=:auto, device::Integer=0)
+    tv = Vector{Float64}(t)
+    df, Nf = _clean_grid(tv, df, Nf)
+    N, ns = length(tv), size(y, 2)
+    @assert size(y, 1) == N "y has to be as long as the sampling points"
+    yv = Matrix{Float64}(reshape(y, N, ns))
+    Wv = W === nothing ? Float64[] : Vector{Float64}(W)
+    @assert W === nothing || length(Wv) == N "W has to be as long as the sampling points"
+    Wp = W === nothing ? Ptr{Float64}(C_NULL) : pointer(Wv)
+    Dv, Wnv = zeros(2, max(Nf, 0), ns), zeros(2, max(2Nf - 1, 0))
+    GC.@preserve yv tv Wv Dv Wnv check(@ccall LIB.lpvs_dirty_spectrum_f64(yv::Ptr{Float64}, Int64(ns)::Int64, tv::Ptr{Float64}, Int64(N)::Int64, Wp::Ptr{Float64},
+        Float64(df)::Float64, Int64(Nf)::Int64, Int32(center_data)::Int32, EVAL_PATHS[path]::Int32, Int32(device)::Int32, Dv::Ptr{Float64}, Wnv::Ptr{Float64})::Int32)
+    D = _cplx(Dv)
+    (y isa AbstractVector ? D[:, 1] : D), _cplx(Wnv)
+end
+"""    clean_loop(D, Wn; gain=0.5, niter=100, tol=0.0)
+The CLEAN loop on spectra the caller has (`D`: `Nf` (`× ns`), `Wn`: `2 Nf - 1`), all iterations of a signal in one kernel launch.
+Returns `(R, C, picks, pick_values, iterations, status)`; `picks` 1-based in the order picked, 0 behind the last (`niter` (`× ns`));
+`status` `:niter`, `:tol` or `:empty`."""
+function clean_loop(D::AbstractVecOrMat{<:Complex}, Wn::AbstractVector{<:Complex}; gain::Real=0.5, niter::Integer=100, tol::Real=0.0, device::Integer=0)
+    Nf, ns = size(D, 1), size(D, 2)
+    @assert length(Wn) == 2Nf - 1 "Wn has to hold 2 Nf - 1 values"
+    Dv, Wnv = _ri(reshape(D, Nf, ns)), _ri(Wn)
+    nit = max(Int(niter), 0)
+    Rv, Cv, pvv = zeros(2, Nf, ns), zeros(2, Nf, ns), zeros(2, max(nit, 1), ns)
+    picks, iters, status = fill(Int32(-1), max(nit, 1), ns), zeros(Int32, ns), zeros(Int32, ns)
+    GC.@preserve Dv Wnv Rv Cv pvv picks iters status check(@ccall LIB.lpvs_clean_loop_f64(Dv::Ptr{Float64}, Int64(ns)::Int64, Int64(Nf)::Int64, Wnv::Ptr{Float64},
+        Float64(gain)::Float64, Int64(niter)::Int64, Float64(tol)::Float64, Int32(device)::Int32, Rv::Ptr{Float64}, Cv::Ptr{Float64}, picks::Ptr{Int32},
+        pvv::Ptr{Float64}, iters::Ptr{Int32}, status::Ptr{Int32})::Int32)
+    one = D isa AbstractVector
+    sh(A) = one ? A[:, 1] : A
+    sh(_cplx(Rv)), sh(_cplx(Cv)), sh(Int.(picks[1:nit, :]) .+ 1), sh(_cplx(pvv)[1:nit, :]), one ? Int(iters[1]) : Int.(iters),
+        one ? CLEAN_STATUS[status[1]+1] : [CLEAN_STATUS[v+1] for v in status]
+end
+"""    clean_restore(R, C, df, sigma)
+`S_k = R_k + Σ_p [C_p B_{k-p} + conj(C_p) B_{k+p}]` with the real Gaussian beam `B_m = exp(-(m df)² / (2 sigma²))`."""
+function clean_restore(R::AbstractVecOrMat{<:Complex}, C::AbstractVecOrMat{<:Complex}, df::Real, sigma::Real; device::Integer=0)
+    Nf, ns = size(R, 1), size(R, 2)
+    @assert size(C) == size(R) "C has to be shaped as R"
+    Rv, Cv, Sv = _ri(reshape(R, Nf, ns)), _ri(reshape(C, Nf, ns)), zeros(2, Nf, ns)
+    GC.@preserve Rv Cv Sv check(@ccall LIB.lpvs_clean_restore_f64(Rv::Ptr{Float64}, Cv::Ptr{Float64}, Int64(ns)::Int64, Int64(Nf)::Int64, Float64(df)::Float64,
+        Float64(sigma)::Float64, Int32(device)::Int32, Sv::Ptr{Float64})::Int32)
+    S = _cplx(Sv)
+    R isa AbstractVector ? S[:, 1] : S
+end
+"""    clean(y, t; df=nothing, Nf=nothing, W=nothing, gain=0.5, niter=100, tol=0.0, center_data=true, center_time=true, path=:auto)
+CLEAN deconvolution (Roberts, Lehár & Dreher 1987) of the spectrum of non-uniformly sampled signals: the dirty spectrum, the loop and the
+restoration in one call of the library.  `center_time=true` subtracts the mean of `t` first (the beam is real: phases refer to the mean
+epoch; this redefines the record by one rounding per time).  Returns `(freq, dirty, window, residual, components, picks, pick_values,
+spectrum, power, amplitude, iterations, status, sigma)`; `amplitude = 2 |components|`, `picks` 1-based, 0 behind the last."""
+function clean(y::AbstractVecOrMat{<:Real}, t::AbstractVector{<:Real}; df=nothing, Nf=nothing, W=nothing, gain::Real=0.5, niter::Integer=100, tol::Real=0.0,
+               center_data::Bool=true, center_time::Bool=true, path::Symbol=:auto, device::Integer=0)
+    tv = Vector{Float64}(t)
+    df, Nf = _clean_grid(tv, df, Nf)
+    center_time && (tv = tv .- sum(tv) / length(tv))
+    N, ns = length(tv), size(y, 2)
+    @assert size(y, 1) == N "y has to be as long as the sampling points"
+    yv = Matrix{Float64}(reshape(y, N, ns))
+    Wv = W === nothing ? Float64[] : Vector{Float64}(W)
+    @assert W === nothing || length(Wv) == N "W has to be as long as the sampling points"
+    Wp = W === nothing ? Ptr{Float64}(C_NULL) : pointer(Wv)
+    nit, nf = max(Int(niter), 0), max(Nf, 0)
+    Dv, Rv, Cv, Sv, Wnv, pvv = zeros(2, nf, ns), zeros(2, nf, ns), zeros(2, nf, ns), zeros(2, nf, ns), zeros(2, max(2Nf - 1, 0)), zeros(2, max(nit, 1), ns)
+    picks, iters, status, sg = fill(Int32(-1), max(nit, 1), ns), zeros(Int32, ns), zeros(Int32, ns), zeros(1)
+    GC.@preserve yv tv Wv Dv Wnv Rv Cv picks pvv iters status Sv sg check(@ccall LIB.lpvs_clean_f64(yv::Ptr{Float64}, Int64(ns)::Int64, tv::Ptr{Float64},
+        Int64(N)::Int64, Wp::Ptr{Float64}, Float64(df)::Float64, Int64(Nf)::Int64, Int32(center_data)::Int32, EVAL_PATHS[path]::Int32, Float64(gain)::Float64,
+        Int64(niter)::Int64, Float64(tol)::Float64, 0.0::Float64, Int32(device)::Int32, Dv::Ptr{Float64}, Wnv::Ptr{Float64}, Rv::Ptr{Float64}, Cv::Ptr{Float64},
+        picks::Ptr{Int32}, pvv::Ptr{Float64}, iters::Ptr{Int32}, status::Ptr{Int32}, Sv::Ptr{Float64}, sg::Ptr{Float64})::Int32)
+    one = y isa AbstractVector
+    sh(A) = one ? A[:, 1] : A
+    S, Cc = _cplx(Sv), _cplx(Cv)
+    (freq = (0:Nf-1) .* df, dirty = sh(_cplx(Dv)), window = _cplx(Wnv), residual = sh(_cplx(Rv)), components = sh(Cc), picks = sh(Int.(picks[1:nit, :]) .+ 1),
+     pick_values = sh(_cplx(pvv)[1:nit, :]), spectrum = sh(S), power = sh(abs2.(S)), amplitude = sh(2 .* abs.(Cc)), iterations = one ? Int(iters[1]) : Int.(iters),
+     status = one ? CLEAN_STATUS[status[1]+1] : [CLEAN_STATUS[v+1] for v in status], sigma = sg[1])
+end
+function clean_last_timing()
+    tm = zeros(14)
+    GC.@preserve tm check(@ccall LIB.lpvs_clean_last_timing(tm::Ptr{Float64}, Int32(14)::Int32)::Int32)
+    (path = tm[1] == 1 ? :direct : tm[1] == 2 ? :nufft : :none, residual = tm[2] == 1 ? :lds : tm[2] == 2 ? :global : :none, threads = Int(tm[3]),
+     lds_bytes = Int(tm[4]), iterations_min = Int(tm[5]), iterations_max = Int(tm[6]), admissible = Int(tm[7]), moments_ms = tm[8], sums_ms = tm[9],
+     loop_ms = tm[10], restore_ms = tm[11], copy_ms = tm[12], total_ms = tm[13], sigma = tm[14])
 end
 
 # ---- the bootstrap of the Lomb-Scargle periodogram (extension; include/lpvspectral.h g6) -------------------------------------------------

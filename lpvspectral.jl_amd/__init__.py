@@ -15,6 +15,7 @@ from .api import (MFCC, MelSpectrogram, Spectrogram, dct_matrix, fft_frequencies
                   lombscargle, lombscargle_last_timing, lombscargle_terms_last_timing, lombscargle_spectrogram, lombscargle_welch, lombscargle_windows_last_timing, time_windows,
                   WWZ, wwz, wwz_radius, wwz_last_timing, BLS, bls, bls_frequencies, bls_last_timing,
                   PDM, CE, pdm, aov, conditional_entropy, pdm_last_timing, cent_last_timing,
+                  CLEAN, clean, clean_loop, clean_restore, clean_sigma, dirty_spectrum, clean_last_timing,
                   bootstrap_indices, lombscargle_bootstrap, lombscargle_bootstrap_last_timing, false_alarm_probability, false_alarm_level,
                   ComplexNormal, SchedFunc, schedfunc, rand, randn, cholesky_upper, cn_last_timing, pdf, affine_transform, detrend, detrend_, Σ,  # noqa: E402
                   cn_V2ΓC, cn_Vxx, cn_Vyy, cn_Vxy, cn_Vyx, cn_fVxx, cn_fVyy, cn_fVxy, cn_fVyx, cn_Vs, cn_fV, cn_V,  # noqa: E402
@@ -36,6 +37,7 @@ __all__ = [
     "lombscargle", "lombscargle_last_timing", "lombscargle_terms_last_timing", "lombscargle_spectrogram", "lombscargle_welch", "lombscargle_windows_last_timing", "time_windows",
     "WWZ", "wwz", "wwz_radius", "wwz_last_timing", "BLS", "bls", "bls_frequencies", "bls_last_timing",
     "PDM", "CE", "pdm", "aov", "conditional_entropy", "pdm_last_timing", "cent_last_timing",
+    "CLEAN", "clean", "clean_loop", "clean_restore", "clean_sigma", "dirty_spectrum", "clean_last_timing",
     "bootstrap_indices", "lombscargle_bootstrap", "lombscargle_bootstrap_last_timing", "false_alarm_probability", "false_alarm_level",
     "ADMM", "Problem", "SpectralExt", "basis_activation_func", "check_freq", "default_freqs", "fourier2complex",
     "get_fourier_regressor", "lpv_regressor", "ls_sparse_spectral", "ls_sparse_spectral_lpv", "ls_sparse_spectral_lpv_multi", "ls_sparse_spectral_lpv_rowsharded", "lpv_ranges", "predict", "residual", "fva", "eval_last_timing", "lpv_batch_multi", "lpv_signals_multi", "ls_spectral",

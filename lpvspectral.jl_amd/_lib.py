@@ -204,6 +204,11 @@ SIGNATURES = {
     "lpvs_pdm_last_timing": (_I32, [_P, _I32]),
     "lpvs_cent_f64": (_I32, [_P, _I64, _P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _P]),
     "lpvs_cent_last_timing": (_I32, [_P, _I32]),
+    "lpvs_dirty_spectrum_f64": (_I32, [_P, _I64, _P, _I64, _P, _F64, _I64, _I32, _I32, _I32, _P, _P]),
+    "lpvs_clean_loop_f64": (_I32, [_P, _I64, _I64, _P, _F64, _I64, _F64, _I32, _P, _P, _P, _P, _P, _P]),
+    "lpvs_clean_restore_f64": (_I32, [_P, _P, _I64, _I64, _F64, _F64, _I32, _P]),
+    "lpvs_clean_f64": (_I32, [_P, _I64, _P, _I64, _P, _F64, _I64, _I32, _I32, _F64, _I64, _F64, _F64, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "lpvs_clean_last_timing": (_I32, [_P, _I32]),
 }
 
 _lib = None

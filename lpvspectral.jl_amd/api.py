@@ -2667,6 +2667,210 @@ def cent_last_timing():
     return _fold_timing(o)
 
 
+# ---- CLEAN deconvolution of the spectra of unevenly sampled records (include/lpvspectral.h g11; csrc/clean.hip) -------------------------------
+_CLEAN_STATUS = {0: "niter", 1: "tol", 2: "empty"}
+_CLEAN_HWHM_TO_SIGMA = 0.8493218002880191          # 1 / sqrt(2 ln 2)
+
+
+class CLEAN:
+    """The result of :func:`clean`.  With K = Nf - 1 and one signal (several: a leading or trailing ``ns`` as noted): ``freq`` (Nf,), the
+    grid ``m df``; ``dirty`` (Nf,) or (Nf, ns) complex, the dirty spectrum ``D``; ``window`` (2 Nf - 1,) complex, the spectral window
+    ``Wn``; ``residual`` and ``components``: ``R`` and ``C``, shaped as ``dirty``; ``picks`` (niter,) or (ns, niter) int32, the bins in
+    the order picked, -1 behind the last, and ``pick_values``, the complex ``c`` of each pick; ``spectrum``: the restored ``S``,
+    ``power = |S|²`` and ``amplitude = 2 |C|`` (the amplitude of the sinusoid a component stands for), shaped as ``dirty``;
+    ``iterations`` and ``status`` (``"niter"``, ``"tol"`` or ``"empty"``): an int and a string, or (ns,) arrays / lists; ``sigma``: the
+    width of the restoring beam, in the unit of ``freq``."""
+
+    def __init__(self, freq, dirty, window, residual, components, picks, pick_values, spectrum, iterations, status, sigma):
+        self.freq, self.dirty, self.window, self.residual, self.components = freq, dirty, window, residual, components
+        self.picks, self.pick_values, self.spectrum, self.iterations, self.status, self.sigma = picks, pick_values, spectrum, iterations, status, sigma
+        self.power = spectrum.real ** 2 + spectrum.imag ** 2
+        self.amplitude = 2.0 * np.abs(components)
+
+
+def _clean_grid(t, df, Nf):
+    """``(df, Nf)`` with the defaults ``df = 1 / (4 (max t - min t))`` and ``Nf`` the grid up to ``default_freqs(t)``'s top frequency."""
+    if df is None or Nf is None:
+        th = _host(t)
+        if df is None:
+            span = float(np.max(th) - np.min(th))
+            if not span > 0:
+                raise ValueError("clean: df=None needs a record that spans more than one instant")
+            df = 1.0 / (4.0 * span)
+        if Nf is None:
+            Nf = max(2, int(np.floor(float(default_freqs(th)[-1]) / float(df))) + 1)
+    return float(df), int(Nf)
+
+
+def _clean_complex(a, shape, what):
+    """A host complex array or a device complex tensor as what the library reads: (keepalive, pointer), interleaved (re, im) doubles."""
+    if _lib.is_device_array(a):
+        import torch
+        if a.dtype != torch.complex128 or tuple(a.shape) != tuple(shape):
+            raise ValueError(f"{what}: a complex128 tensor of shape {tuple(shape)} is needed")
+        r = torch.view_as_real(a.contiguous())
+        torch.cuda.current_stream(r.device).synchronize()
+        return r, C.c_void_p(r.data_ptr())
+    arr = np.ascontiguousarray(np.asarray(a, dtype=np.complex128))
+    if arr.shape != tuple(shape):
+        raise ValueError(f"{what}: shape {arr.shape}, needed {tuple(shape)}")
+    return arr, out_ptr(arr)
+
+
+def clean_sigma(Wn, df):
+    """The width of the Gaussian restoring beam fitted to the spectral window ``Wn`` (2 Nf - 1 complex values on the grid ``m df``):
+    the first ``m`` with ``|Wn_m|² < 1/2`` -- the half-power point of the main lobe --, interpolated linearly in ``|Wn|²``, is the half
+    width ``h``; ``sigma = h / sqrt(2 ln 2)``.  The same operations, in the same order, as csrc/clean_plan.h ``clean_sigma``."""
+    Wn = np.asarray(Wn, dtype=np.complex128)
+    P = Wn.real * Wn.real + Wn.imag * Wn.imag
+    df = np.float64(df)
+    for m in range(1, len(P)):
+        if P[m] < 0.5:
+            prev = P[m - 1]
+            frac = (prev - 0.5) / (prev - P[m]) if prev > P[m] else np.float64(0.0)
+            return float(((np.float64(m - 1) + frac) * df) * np.float64(_CLEAN_HWHM_TO_SIGMA))
+    return float((np.float64(len(P) - 1) * df) * np.float64(_CLEAN_HWHM_TO_SIGMA))
+
+
+def dirty_spectrum(y, t, df=None, Nf=None, W=None, center_data=True, path="auto", device=0):
+    """The dirty spectrum and the spectral window of non-uniformly sampled signals on the grid ``f_m = m df``:
+    ``D_k = Σ w y_c e^{-2πi f_k t}`` for ``k = 0 .. Nf - 1`` and ``Wn_m = Σ w e^{-2πi f_m t}`` for ``m = 0 .. 2 Nf - 2`` -- the sums
+    ``YC - i YS`` and ``C - i S`` of :func:`lombscargle`, by the same kernels and paths, with the weights normalised to sum 1 and the
+    weighted mean removed (``center_data``).  ``y``: (N,) or (N, ns); defaults: ``df = 1 / (4 (max t - min t))``, ``Nf`` up to
+    ``default_freqs(t)``'s top frequency.  Returns ``(D, Wn)``: complex arrays of shape (Nf,) or (ns, Nf), and (2 Nf - 1,)."""
+    if path not in _EVAL_PATHS:
+        raise ValueError(f"path: unknown value {path!r} (known: {sorted(_EVAL_PATHS)})")
+    df, Nf = _clean_grid(t, df, Nf)
+    ys, N, ns, single = _lomb_signals(y)
+    ky, py, ny = as_f64(ys)
+    kt, pt, nt = as_f64(_f64_arg(t))
+    if nt != N:
+        raise ValueError(f"y has {N} samples, t has {nt}")
+    kw, pw, nw = as_f64(_f64_arg(W))
+    if W is not None and nw != N:
+        raise ValueError(f"y has {N} samples, W has {nw}")
+    D = np.zeros((ns, max(Nf, 0)), dtype=np.complex128)
+    Wn = np.zeros(max(2 * Nf - 1, 0), dtype=np.complex128)
+    check(lib().lpvs_dirty_spectrum_f64(py, ns, pt, N, pw, df, Nf, int(bool(center_data)), _EVAL_PATHS[path], int(device), out_ptr(D), out_ptr(Wn)))
+    del ky, kt, kw
+    return (D[0].copy() if single else D), Wn
+
+
+def clean_loop(D, Wn, gain=0.5, niter=100, tol=0.0, device=0):
+    """The CLEAN loop (Roberts, Lehár & Dreher 1987) on spectra the caller has: ``D`` (Nf,) or (ns, Nf) complex, ``Wn`` (2 Nf - 1,)
+    complex (numpy arrays or complex128 device tensors).  Per iteration: the admissible bin ``p`` of the largest ``|R|²`` (admissible:
+    ``1 - |Wn_2p|² >= 2^-20``; ties to the lowest index), ``a = (R_p - conj(R_p) Wn_2p) / (1 - |Wn_2p|²)``, ``c = gain a``,
+    ``C_p += c`` and ``R_k -= c Wn_{k-p} + conj(c) Wn_{k+p}`` for every ``k`` -- all iterations of a signal in ONE kernel launch, the
+    residual resident in LDS (csrc/clean.hip).  It stops after ``niter`` picks, when the peak has fallen to ``tol`` times the first
+    peak's modulus (``tol = 0``: never) or when no bin is admissible.  ``gain`` in (0, 2).
+
+    Returns ``(R, C, picks, pick_values, iterations, status)``: ``R``, ``C`` shaped as ``D``; ``picks`` (niter,) or (ns, niter) int32
+    (-1 behind the last pick) and the complex ``pick_values``; ``iterations`` and ``status`` (0 niter, 1 tol, 2 empty): ints, or (ns,)
+    int32 arrays.  Every operation is a rounded double operation in the order include/lpvspectral.h g11 states: the result does not
+    depend on the thread count or on where the residual lives."""
+    D = D if _lib.is_device_array(D) else np.asarray(D, dtype=np.complex128)
+    single = len(D.shape) == 1
+    shape = tuple(D.shape) if not single else (1, int(D.shape[0]))
+    ns, Nf = int(shape[0]), int(shape[1])
+    kD, pD = _clean_complex(D.reshape(shape) if single else D, shape, "D")
+    kW, pW = _clean_complex(Wn, (2 * Nf - 1,), "Wn")
+    niter = int(niter)
+    nit = max(niter, 0)
+    R = np.zeros((ns, Nf), dtype=np.complex128)
+    Cc = np.zeros((ns, Nf), dtype=np.complex128)
+    picks = np.full((ns, nit), -1, dtype=np.int32)
+    pv = np.zeros((ns, nit), dtype=np.complex128)
+    iters = np.zeros(ns, dtype=np.int32)
+    status = np.zeros(ns, dtype=np.int32)
+    spare = np.zeros(2)                                                       # (pointers of empty arrays are not NULL to the library)
+    check(lib().lpvs_clean_loop_f64(pD, ns, Nf, pW, float(gain), niter, float(tol), int(device), out_ptr(R), out_ptr(Cc),
+                                    out_ptr(picks) if nit else out_ptr(spare), out_ptr(pv) if nit else out_ptr(spare), out_ptr(iters), out_ptr(status)))
+    del kD, kW
+    if single:
+        return R[0], Cc[0], picks[0], pv[0], int(iters[0]), int(status[0])
+    return R, Cc, picks, pv, iters, status
+
+
+def clean_restore(R, C_, df, sigma, device=0):
+    """The restored spectrum ``S_k = R_k + Σ_p [C_p B_{k-p} + conj(C_p) B_{k+p}]`` with the real Gaussian beam
+    ``B_m = exp(-(m df)² / (2 sigma²))``, summed over the nonzero components in increasing ``p`` by a gather on the device.  ``R``,
+    ``C_``: (Nf,) or (ns, Nf) complex.  Returns ``S`` shaped as ``R``."""
+    R = R if _lib.is_device_array(R) else np.asarray(R, dtype=np.complex128)
+    C_ = C_ if _lib.is_device_array(C_) else np.asarray(C_, dtype=np.complex128)
+    single = len(R.shape) == 1
+    shape = tuple(R.shape) if not single else (1, int(R.shape[0]))
+    ns, Nf = int(shape[0]), int(shape[1])
+    kR, pR = _clean_complex(R.reshape(shape) if single else R, shape, "R")
+    kC, pC = _clean_complex(C_.reshape(shape) if single else C_, shape, "C")
+    S = np.zeros((ns, Nf), dtype=np.complex128)
+    check(lib().lpvs_clean_restore_f64(pR, pC, ns, Nf, float(df), float(sigma), int(device), out_ptr(S)))
+    del kR, kC
+    return S[0] if single else S
+
+
+def clean(y, t, df=None, Nf=None, W=None, gain=0.5, niter=100, tol=0.0, center_data=True, center_time=True, path="auto", device=0):
+    """CLEAN deconvolution (Roberts, Lehár & Dreher 1987) of the spectrum of non-uniformly sampled signals: :func:`dirty_spectrum`,
+    :func:`clean_loop` and :func:`clean_restore` in one call of the library, the spectra staying on the device between the stages.
+    Uneven sampling convolves every line of a spectrum with the spectral window -- one sinusoid shows as a forest of sidelobes and
+    aliases --; CLEAN removes the window's response to the strongest line, ``gain`` of it at a time, and leaves a short list of
+    complex ``components`` (``amplitude = 2 |C|`` and ``angle(C)`` are the amplitude and the phase of a sinusoid) and a ``residual``.
+    The restored ``spectrum`` puts the components back under a Gaussian beam as wide as the window's main lobe.
+
+    ``y``: (N,) or (N, ns) signals sharing the times ``t``; ``W``: non-negative weights (``None``: ones).  ``df``, ``Nf``: the grid
+    ``m df``, ``m = 0 .. Nf - 1`` (the window is formed up to ``2 (Nf - 1) df``); defaults ``df = 1 / (4 (max t - min t))`` and
+    ``Nf`` up to ``default_freqs(t)``'s top frequency.  ``center_time=True`` subtracts ``np.mean(t)`` on the host first: the beam is
+    real, so phases refer to the mean epoch, as in the paper.  This redefines the record by one rounding per time; pass
+    ``center_time=False`` for the bits of the record as given (phases then refer to ``t = 0``).  Returns a :class:`CLEAN`.
+
+    Not covered: one signal is one workgroup (a lone signal runs on one compute unit: the loop is bound by latency), beams other than
+    the Gaussian, and several harmonics per component."""
+    if path not in _EVAL_PATHS:
+        raise ValueError(f"path: unknown value {path!r} (known: {sorted(_EVAL_PATHS)})")
+    df, Nf = _clean_grid(t, df, Nf)
+    if center_time:
+        th = _host(t)
+        t = th - np.mean(th)
+    ys, N, ns, single = _lomb_signals(y)
+    ky, py, ny = as_f64(ys)
+    kt, pt, nt = as_f64(_f64_arg(t))
+    if nt != N:
+        raise ValueError(f"y has {N} samples, t has {nt}")
+    kw, pw, nw = as_f64(_f64_arg(W))
+    if W is not None and nw != N:
+        raise ValueError(f"y has {N} samples, W has {nw}")
+    niter = int(niter)
+    nit, nf = max(niter, 0), max(Nf, 0)
+    D, R, Cc, S = (np.zeros((ns, nf), dtype=np.complex128) for _ in range(4))
+    Wn = np.zeros(max(2 * Nf - 1, 0), dtype=np.complex128)
+    picks = np.full((ns, nit), -1, dtype=np.int32)
+    pv = np.zeros((ns, nit), dtype=np.complex128)
+    iters = np.zeros(ns, dtype=np.int32)
+    status = np.zeros(ns, dtype=np.int32)
+    sigma = C.c_double(0.0)
+    spare = np.zeros(2)
+    check(lib().lpvs_clean_f64(py, ns, pt, N, pw, df, Nf, int(bool(center_data)), _EVAL_PATHS[path], float(gain), niter, float(tol), 0.0, int(device),
+                               out_ptr(D), out_ptr(Wn), out_ptr(R), out_ptr(Cc), out_ptr(picks) if nit else out_ptr(spare),
+                               out_ptr(pv) if nit else out_ptr(spare), out_ptr(iters), out_ptr(status), out_ptr(S), C.byref(sigma)))
+    del ky, kt, kw
+    freq = np.arange(Nf) * df
+    if single:
+        return CLEAN(freq, D[0], Wn, R[0], Cc[0], picks[0], pv[0], S[0], int(iters[0]), _CLEAN_STATUS[int(status[0])], float(sigma.value))
+    shaped = lambda a: np.ascontiguousarray(a.T)                               # noqa: E731  (ns, Nf) -> (Nf, ns)
+    return CLEAN(freq, shaped(D), Wn, shaped(R), shaped(Cc), picks, pv, shaped(S), iters, [_CLEAN_STATUS[int(v)] for v in status], float(sigma.value))
+
+
+def clean_last_timing():
+    """Plan and timing of the calling thread's last :func:`dirty_spectrum`, :func:`clean_loop`, :func:`clean_restore` or :func:`clean`
+    (0 / ``"none"`` where the call had no such stage): the path of the sums, where the residual lived, the threads and the LDS bytes
+    of the loop's workgroup, the fewest and the most iterations of a signal, the admissible bins, milliseconds per stage."""
+    o = np.zeros(14)
+    check(lib().lpvs_clean_last_timing(out_ptr(o), 14))
+    return {"path": {1: "direct", 2: "nufft"}.get(int(o[0]), "none"), "residual": {1: "lds", 2: "global"}.get(int(o[1]), "none"), "threads": int(o[2]),
+            "lds_bytes": int(o[3]), "iterations_min": int(o[4]), "iterations_max": int(o[5]), "admissible": int(o[6]), "moments_ms": float(o[7]),
+            "sums_ms": float(o[8]), "loop_ms": float(o[9]), "restore_ms": float(o[10]), "copy_ms": float(o[11]), "total_ms": float(o[12]),
+            "sigma": float(o[13])}
+
+
 # ---- false-alarm probabilities of the Lomb-Scargle periodogram: the device bootstrap and the closed forms (include/lpvspectral.h g6) ------
 _M32 = np.uint64(0xFFFFFFFF)
 

@@ -19,6 +19,7 @@
 #include "wwz_plan.h"
 #include "bls_plan.h"
 #include "fold_plan.h"
+#include "clean_plan.h"
 #include "pool_plan.h"
 
 namespace lpvs {
@@ -397,6 +398,22 @@ struct CentArgs {
 int32_t launch_cent_prepare(const double *y, int64_t N, int64_t ns, int mbins, unsigned long long *lim_dev, unsigned char *vbin, double *ylim_dev,
                             int32_t *degenerate_dev, hipStream_t s);
 int32_t launch_cent(const CentArgs &A, const CentPlan &plan, hipStream_t s);
+
+// CLEAN (lpvs_dirty_spectrum_f64, lpvs_clean_loop_f64, lpvs_clean_restore_f64, lpvs_clean_f64; clean.hip; the decisions: clean_plan.h).
+// All pointers are device memory; complex values are interleaved (re, im).
+// sums: launch_lomb_direct's rows over the 2 Nf - 1 frequencies m df -> Wn[2 Nf - 1] = (C, -S), D[ns][Nf] = (YC_c, -YS_c)
+int32_t launch_clean_repack(const double *sums, int64_t Nf, int64_t ns, double *Wn, double *D, hipStream_t s);
+// flags_dev |= 1 where x[count] holds a value that is not finite
+int32_t launch_clean_finite(const double *x, int64_t count, int *flags_dev, hipStream_t s);
+// den[Nf], mask[Nf] (1: admissible), nadm_dev: zeroed here, then the count of the admissible bins
+int32_t launch_clean_prologue(const double *Wn, int64_t Nf, double *den, unsigned char *mask, int *nadm_dev, hipStream_t s);
+// R, C[ns][Nf] (C: zeroed by the caller), picks[ns][niter], pickval[ns][niter] (filled by the caller: only the picks made are written),
+// iters, status[ns]; with the residual in global memory R is the working copy itself
+int32_t launch_clean_loop(const double *D, const double *Wn, const double *den, const unsigned char *mask, int64_t ns, int64_t Nf, double gain, int64_t niter,
+                          double tol, const CleanPlan &plan, double *R, double *C, int32_t *picks, double *pickval, int32_t *iters, int32_t *status, hipStream_t s);
+// S[ns][Nf]; scratch: list[ns][Nf], count[ns], beam[2 Nf - 1]
+int32_t launch_clean_restore(const double *R, const double *C, int64_t ns, int64_t Nf, double df, double sigma, int32_t *list, int32_t *count, double *beam,
+                             double *S, hipStream_t s);
 
 // ---- dense symmetric inverse (linalg.hip) ------------------------------------------------
 // In-place inverse of the SPD matrix A (np x np, np % 64 == 0, full symmetric storage) by

@@ -463,7 +463,10 @@ int32_t launch_nufft_tab(const double *x, const double *y, int64_t N, double xam
     for (int q = 0; q < nq; ++q) {
         const double cmax = __builtin_bit_cast(double, hm[(size_t)q]);
         for (int twin = 0; twin < 2; ++twin) {
-            const double bound = (twin ? xam : 1.0) * cmax * (double)N;        // >= sum of |weights|
+            // >= sum of |weights|.  A single addend is up to bound / N, and round(cw * tap) through NU_MAGIC is exact only below 2^51
+            // quanta: a record shorter than kNufftMinSamples takes the quantum of one that long (the structured Gram admits no shorter
+            // one; lombscargle and clean with path = NUFFT do), so that no addend exceeds 2^62 / 4096 = 2^50 quanta
+            const double bound = (twin ? xam : 1.0) * cmax * (double)(N < kNufftMinSamples ? kNufftMinSamples : N);
             int e = 0;
             (void)std::frexp(bound > 0 ? bound : 1.0, &e);                     // bound < 2^e
             const double quantum = std::ldexp(1.0, e - 62);                    // power of two: the scalings are exact

@@ -119,59 +119,43 @@ int32_t copy_out_sums(double *sums_out, const DevBuf &dsums, int64_t nrow, int64
     return copy_from_device(sums_out + nrow * Nf + 2 * rec.ns, rec.mean_dev, sizeof(double) * (size_t)rec.ns, rec.s);
 }
 
-}  // namespace
-
-// ---- Lomb-Scargle periodogram (lomb.hip; the decisions: lomb_plan.h) --------------------------------------------------------------------
-// what lpvs_lombscargle_last_timing reports of the calling thread's last call: [0] path taken (1 direct, 2 transforms), [1], [2] blocks of
-// family 1 / family 2 (0: direct), [3] fine grid (0: direct), [4] degenerate frequencies, [5] slabs of the direct sums (0: transforms),
-// ms of [6] staging, the scan and the moments, [7] the sums, [8] the epilogue, [9] the copy-out, [10] total, [11] the first-order term ran
-static thread_local double g_lomb_timing[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-static int32_t lomb_impl(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const std::vector<double> &hf, bool fit_mean, bool center,
-                         bool psd, int32_t path, int32_t device, double *power, double *coef, double *sums_out) {
-    const int64_t Nf = (int64_t)hf.size(), nrow = 4 + 2 * ns;
-    LPVS_TRY(Record::admit(device));
-    hipStream_t s = nullptr;
-    PhaseClock<5> clock;
-    LPVS_TRY(clock.init(s));
-    Record rec; DevOut dpower, dcoef;
-    DevBuf dpart, dsums, dfreq, dslab, dWt, dwork, dtab, deps;
-    DrainOnExit drain(s);
-    LPVS_TRY(clock.mark(0));
-    LPVS_TRY(rec.stage(t, y, W, N, ns, device, s));
-    LPVS_TRY(dpower.set(power, Nf * ns));
-    if (coef) LPVS_TRY(dcoef.set(coef, 3 * Nf * ns));
-    // the small record has no tail; the degenerate count is the spare int of its flags word
-    LPVS_TRY(rec.alloc_small(0));
-    int *ndeg_dev = rec.flags_dev + 1;
-    LPVS_TRY(dpart.alloc(sizeof(double) * (size_t)(3 * ns * lomb_sum_slabs(N))));
-    LPVS_TRY(rec.scan(dpart.as<double>()));
-    LPVS_TRY(rec.check("lombscargle", WeightSum::positive));
-    LPVS_TRY(rec.moments(center, dpart.as<double>()));
-    // the path
+// The sums of lombscargle over the frequencies hf -- rows C, S, C2, S2, YC_c, YS_c of `sums` -- of a record whose moments() have run, by
+// the path lomb_choose_path takes: lombscargle's own, and the dirty stage of clean.  choose() admits the grid, decides and allocates the
+// rows; run() launches.  Declared with the driver's other buffers, BEFORE its DrainOnExit.
+struct LombSums {
+    DevBuf sums, dfreq, dslab, dWt, dwork, dtab, deps;
     LombGrid lg;
     double tam = 0;
-    if (lomb_needs_admission(path, N, Nf)) {         // not when the call goes direct whatever the grid is
-        double tlo, thi;
-        LPVS_TRY(device_minmax(rec.t.p, N, &tlo, &thi, &tam, s));
-        lg = lomb_admit(hf, tam);
+    int taken = 0, nf1 = 0;
+    int64_t nblocks = 0, nslab = 0;
+    bool twin = false;
+
+    int32_t choose(const Record &rec, const std::vector<double> &hf, int32_t path) {
+        const int64_t Nf = (int64_t)hf.size(), N = rec.N, nrow = 4 + 2 * rec.ns;
+        if (lomb_needs_admission(path, N, Nf)) {         // not when the call goes direct whatever the grid is
+            double tlo, thi;
+            LPVS_TRY(device_minmax(rec.t.p, N, &tlo, &thi, &tam, rec.s));
+            lg = lomb_admit(hf, tam);
+        }
+        taken = lomb_choose_path(path, lg.ok, N, Nf);
+        if (taken == kLombPathRefused) {
+            if (path != kLombPathNufft) set_error("path must be 0 (auto), 1 (direct) or 2 (NUFFT), got %d", path);
+            else set_error("path = NUFFT but the frequency grid is not an arithmetic progression up to rounding (max|eps| = %.3g)", lg.emax);
+            return LPVS_EARGUMENT;
+        }
+        return sums.alloc(sizeof(double) * (size_t)(nrow * Nf));
     }
-    const int taken = lomb_choose_path(path, lg.ok, N, Nf);
-    if (taken == kLombPathRefused) {
-        if (path != kLombPathNufft) set_error("path must be 0 (auto), 1 (direct) or 2 (NUFFT), got %d", path);
-        else set_error("path = NUFFT but the frequency grid is not an arithmetic progression up to rounding (max|eps| = %.3g)", lg.emax);
-        return LPVS_EARGUMENT;
-    }
-    LPVS_TRY(dsums.alloc(sizeof(double) * (size_t)(nrow * Nf)));
-    LPVS_TRY(clock.mark(1));
-    int64_t nblocks = 0, nslab = 0; int nf1 = 0; bool twin = false;
-    if (taken == kLombPathDirect) {
-        const LombTiling tl = lomb_tiling(N, Nf, ns);
-        nslab = tl.nslab;
-        LPVS_TRY(dfreq.alloc(sizeof(double) * (size_t)Nf));
-        LPVS_TRY(copy_to_device(dfreq.p, hf.data(), sizeof(double) * (size_t)Nf, s));
-        LPVS_TRY(dslab.alloc(sizeof(double) * (size_t)(tl.nslab * nrow * Nf)));
-        LPVS_TRY(launch_lomb_direct(rec.t.p, rec.w.as<double>(), rec.wy.as<double>(), N, ns, dfreq.as<double>(), Nf, tl, dslab.as<double>(), dsums.as<double>(), s));
-    } else {
+    int32_t run(const Record &rec, const std::vector<double> &hf) {
+        const int64_t Nf = (int64_t)hf.size(), N = rec.N, ns = rec.ns, nrow = 4 + 2 * ns;
+        hipStream_t s = rec.s;
+        if (taken == kLombPathDirect) {
+            const LombTiling tl = lomb_tiling(N, Nf, ns);
+            nslab = tl.nslab;
+            LPVS_TRY(dfreq.alloc(sizeof(double) * (size_t)Nf));
+            LPVS_TRY(copy_to_device(dfreq.p, hf.data(), sizeof(double) * (size_t)Nf, s));
+            LPVS_TRY(dslab.alloc(sizeof(double) * (size_t)(tl.nslab * nrow * Nf)));
+            return launch_lomb_direct(rec.t.p, rec.w.as<double>(), rec.wy.as<double>(), N, ns, dfreq.as<double>(), Nf, tl, dslab.as<double>(), sums.as<double>(), s);
+        }
         const char *knob = experiment_env("LPVS_LOMB_BLOCK");
         const int L = lomb_block_len(knob ? atoll(knob) : 0);
         const std::vector<LombBlock> blocks = lomb_blocks(hf, L);
@@ -203,11 +187,49 @@ static int32_t lomb_impl(const double *y, int64_t ns, const double *t, int64_t N
                     LPVS_TRY(rc);
                     have_coords = true;
                     LPVS_TRY(launch_lomb_combine(dtab.as<double>(), nq, nre, b.prephase, b.count, b.k0, Nf, deps.as<double>(), fscale, family == 1 ? -1 : 2, c0,
-                                                 dsums.as<double>(), s));
+                                                 sums.as<double>(), s));
                 }
             }
         }
+        return LPVS_OK;
     }
+};
+
+}  // namespace
+
+// ---- Lomb-Scargle periodogram (lomb.hip; the decisions: lomb_plan.h) --------------------------------------------------------------------
+// what lpvs_lombscargle_last_timing reports of the calling thread's last call: [0] path taken (1 direct, 2 transforms), [1], [2] blocks of
+// family 1 / family 2 (0: direct), [3] fine grid (0: direct), [4] degenerate frequencies, [5] slabs of the direct sums (0: transforms),
+// ms of [6] staging, the scan and the moments, [7] the sums, [8] the epilogue, [9] the copy-out, [10] total, [11] the first-order term ran
+static thread_local double g_lomb_timing[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+static int32_t lomb_impl(const double *y, int64_t ns, const double *t, int64_t N, const double *W, const std::vector<double> &hf, bool fit_mean, bool center,
+                         bool psd, int32_t path, int32_t device, double *power, double *coef, double *sums_out) {
+    const int64_t Nf = (int64_t)hf.size(), nrow = 4 + 2 * ns;
+    LPVS_TRY(Record::admit(device));
+    hipStream_t s = nullptr;
+    PhaseClock<5> clock;
+    LPVS_TRY(clock.init(s));
+    Record rec; DevOut dpower, dcoef;
+    DevBuf dpart; LombSums ls;
+    DrainOnExit drain(s);
+    LPVS_TRY(clock.mark(0));
+    LPVS_TRY(rec.stage(t, y, W, N, ns, device, s));
+    LPVS_TRY(dpower.set(power, Nf * ns));
+    if (coef) LPVS_TRY(dcoef.set(coef, 3 * Nf * ns));
+    // the small record has no tail; the degenerate count is the spare int of its flags word
+    LPVS_TRY(rec.alloc_small(0));
+    int *ndeg_dev = rec.flags_dev + 1;
+    LPVS_TRY(dpart.alloc(sizeof(double) * (size_t)(3 * ns * lomb_sum_slabs(N))));
+    LPVS_TRY(rec.scan(dpart.as<double>()));
+    LPVS_TRY(rec.check("lombscargle", WeightSum::positive));
+    LPVS_TRY(rec.moments(center, dpart.as<double>()));
+    LPVS_TRY(ls.choose(rec, hf, path));
+    LPVS_TRY(clock.mark(1));
+    LPVS_TRY(ls.run(rec, hf));
+    const DevBuf &dsums = ls.sums;
+    const int taken = ls.taken, nf1 = ls.nf1;
+    const int64_t nblocks = ls.nblocks, nslab = ls.nslab;
+    const bool twin = ls.twin;
     LPVS_TRY(clock.mark(2));
     LPVS_TRY(launch_lomb_epilogue(dsums.as<double>(), Nf, ns, rec.mom_dev, rec.mean_dev, fit_mean, center, psd, N, dpower.p, coef ? dcoef.p : nullptr, ndeg_dev, s));
     LPVS_TRY(clock.mark(3));
@@ -893,6 +915,263 @@ int32_t lpvs_cent_f64(const double *y, int64_t ns, const double *t, int64_t N, c
 
 int32_t lpvs_cent_last_timing(double *out, int32_t n) {
     return copy_timing(out, n, g_cent_timing, 16);
+}
+
+// ---- CLEAN (clean.hip; the decisions: clean_plan.h) ------------------------------------------------------------------------------------------
+// what lpvs_clean_last_timing reports of the calling thread's last call of any of the four entries (0 where the call had no such stage):
+// [0] path of the sums (1 direct, 2 transforms), [1] where the residual lived (1 LDS, 2 global memory), [2] threads of the loop's workgroup,
+// [3] its LDS bytes, [4], [5] the fewest and the most iterations of a signal, [6] admissible bins, ms of [7] staging, the scan and the
+// moments, [8] the sums, [9] the loop, [10] the restoration, [11] the copy-out, [12] total, [13] sigma of the beam
+static thread_local double g_clean_timing[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+namespace {
+
+typedef PhaseClock<6> CleanClock;   // marks: 0 start, 1 staged, 2 sums, 3 loop, 4 restoration, 5 (finish) copy-out
+
+void clean_report(const CleanClock &clock, int taken, const CleanPlan *plan, int64_t itmin, int64_t itmax, int nadm, double sigma) {
+    double *g = g_clean_timing;
+    g[0] = taken; g[1] = plan ? plan->residual : 0; g[2] = plan ? plan->threads : 0; g[3] = plan ? (double)plan->lds_bytes : 0;
+    g[4] = (double)itmin; g[5] = (double)itmax; g[6] = nadm;
+    for (int i = 0; i < 5; ++i) g[7 + i] = clock.ms(i);
+    g[12] = clock.total(); g[13] = sigma;
+}
+int32_t clean_refuse(int status, const std::string &why) {
+    set_error("%s", why.c_str());
+    return status == kCleanArgument ? LPVS_EARGUMENT : LPVS_EUNSUPPORTED;
+}
+// the grid of the dirty stage: f_m = m df (the double product), m = 0 .. 2 Nf - 2
+std::vector<double> clean_grid(double df, int64_t Nf) {
+    std::vector<double> hf((size_t)(2 * Nf - 1));
+    for (size_t m = 0; m < hf.size(); ++m) hf[m] = (double)m * df;
+    return hf;
+}
+
+// the record's front end, lomb.hip's sums on the grid and the repacking: Wn[2 Nf - 1], D[ns][Nf] (device); marks 1 before the sums
+int32_t clean_dirty_stage(const char *who, Record &rec, LombSums &ls, DevBuf &dpart, const std::vector<double> &hf, int64_t Nf, bool center, int32_t path,
+                          CleanClock &clock, double *Wn_dev, double *D_dev) {
+    LPVS_TRY(rec.alloc_small(0));
+    LPVS_TRY(dpart.alloc(sizeof(double) * (size_t)(3 * rec.ns * lomb_sum_slabs(rec.N))));
+    LPVS_TRY(rec.scan(dpart.as<double>()));
+    LPVS_TRY(rec.check(who, WeightSum::positive));
+    LPVS_TRY(rec.moments(center, dpart.as<double>()));
+    LPVS_TRY(ls.choose(rec, hf, path));
+    LPVS_TRY(clock.mark(1));
+    LPVS_TRY(ls.run(rec, hf));
+    return launch_clean_repack(ls.sums.as<double>(), Nf, rec.ns, Wn_dev, D_dev, rec.s);
+}
+
+struct CleanLoopInfo { int nadm = 0; int64_t itmin = 0, itmax = 0; };
+// the loop on device spectra: R, C (device), pickval (device; nullptr with niter = 0); picks_out, iters_out, status_out: host
+int32_t clean_loop_stage(const char *who, const double *D, const double *Wn, int64_t ns, int64_t Nf, double gain, int64_t niter, double tol, const CleanPlan &plan,
+                         DevBuf &dwork, double *R, double *C, double *pickval, int32_t *picks_out, int32_t *iters_out, int32_t *status_out, hipStream_t s,
+                         CleanLoopInfo *info) {
+    // [den: Nf doubles | flags, admissible bins, iters[ns], status[ns], picks[ns niter]: ints | mask: Nf bytes]
+    const size_t nints = (size_t)(2 + 2 * ns + ns * niter);
+    LPVS_TRY(dwork.alloc(sizeof(double) * (size_t)Nf + sizeof(int32_t) * nints + (size_t)Nf));
+    double *den = dwork.as<double>();
+    int *flags_dev = reinterpret_cast<int *>(den + Nf), *nadm_dev = flags_dev + 1;
+    int32_t *iters_dev = nadm_dev + 1, *status_dev = iters_dev + ns, *picks_dev = status_dev + ns;
+    unsigned char *mask = reinterpret_cast<unsigned char *>(flags_dev + nints);
+    LPVS_HIP(hipMemsetAsync(flags_dev, 0, sizeof(int), s));
+    LPVS_TRY(launch_clean_finite(D, 2 * ns * Nf, flags_dev, s));
+    LPVS_TRY(launch_clean_finite(Wn, 2 * (2 * Nf - 1), flags_dev, s));
+    int flags = 0;
+    LPVS_TRY(copy_from_device(&flags, flags_dev, sizeof(int), s));
+    if (flags & 1) { set_error("%s: D or Wn holds a value that is not finite", who); return LPVS_EARGUMENT; }
+    LPVS_TRY(launch_clean_prologue(Wn, Nf, den, mask, nadm_dev, s));
+    LPVS_HIP(hipMemsetAsync(C, 0, sizeof(double) * (size_t)(2 * ns * Nf), s));
+    if (niter > 0) {
+        LPVS_HIP(hipMemsetAsync(picks_dev, 0xff, sizeof(int32_t) * (size_t)(ns * niter), s));             // -1: no pick
+        LPVS_HIP(hipMemsetAsync(pickval, 0, sizeof(double) * (size_t)(2 * ns * niter), s));
+    }
+    LPVS_TRY(launch_clean_loop(D, Wn, den, mask, ns, Nf, gain, niter, tol, plan, R, C, picks_dev, pickval, iters_dev, status_dev, s));
+    LPVS_TRY(copy_from_device(&info->nadm, nadm_dev, sizeof(int), s));
+    LPVS_TRY(copy_from_device(iters_out, iters_dev, sizeof(int32_t) * (size_t)ns, s));
+    LPVS_TRY(copy_from_device(status_out, status_dev, sizeof(int32_t) * (size_t)ns, s));
+    if (niter > 0) LPVS_TRY(copy_from_device(picks_out, picks_dev, sizeof(int32_t) * (size_t)(ns * niter), s));
+    info->itmin = info->itmax = iters_out[0];
+    for (int64_t c = 1; c < ns; ++c) {
+        if (iters_out[c] < info->itmin) info->itmin = iters_out[c];
+        if (iters_out[c] > info->itmax) info->itmax = iters_out[c];
+    }
+    return LPVS_OK;
+}
+
+// S[ns][Nf] (device) from R, C (device)
+int32_t clean_restore_stage(const double *R, const double *C, int64_t ns, int64_t Nf, double df, double sigma, DevBuf &dwork, double *S, hipStream_t s) {
+    // [beam: 2 Nf - 1 doubles | list: ns Nf ints | count: ns ints]
+    const int64_t M = 2 * Nf - 1;
+    LPVS_TRY(dwork.alloc(sizeof(double) * (size_t)M + sizeof(int32_t) * (size_t)(ns * Nf + ns)));
+    double *beam = dwork.as<double>();
+    int32_t *list = reinterpret_cast<int32_t *>(beam + M), *count = list + ns * Nf;
+    return launch_clean_restore(R, C, ns, Nf, df, sigma, list, count, beam, S, s);
+}
+
+bool clean_force_global() {
+    const char *knob = experiment_env("LPVS_CLEAN_RESIDUAL");
+    return knob && !strcmp(knob, "global");
+}
+int32_t clean_check_record(const char *who, int64_t N, int32_t path) {
+    if (N <= 0) { set_error("%s: need N > 0 (N = %lld)", who, (long long)N); return LPVS_EARGUMENT; }
+    if (path < kLombPathAuto || path > kLombPathNufft) { set_error("path must be 0 (auto), 1 (direct) or 2 (NUFFT), got %d", path); return LPVS_EARGUMENT; }
+    return LPVS_OK;
+}
+
+}  // namespace
+
+int32_t lpvs_dirty_spectrum_f64(const double *y, int64_t ns, const double *t, int64_t N, const double *W, double df, int64_t Nf, int32_t center_data, int32_t path,
+                                int32_t device, double *D_out, double *Wn_out) {
+    try {
+        if (!y || !t || !D_out || !Wn_out) { set_error("NULL argument"); return LPVS_EARGUMENT; }
+        int status = kCleanOk; std::string why;
+        if (!clean_check_sizes("dirty_spectrum", ns, Nf, &status, &why) || !clean_check_df("dirty_spectrum", df, &status, &why)) return clean_refuse(status, why);
+        LPVS_TRY(clean_check_record("dirty_spectrum", N, path));
+        const std::vector<double> hf = clean_grid(df, Nf);
+        LPVS_TRY(Record::admit(device));
+        hipStream_t s = nullptr;
+        CleanClock clock;
+        LPVS_TRY(clock.init(s));
+        Record rec; DevOut dD, dWn;
+        DevBuf dpart; LombSums ls;
+        DrainOnExit drain(s);
+        LPVS_TRY(clock.mark(0));
+        LPVS_TRY(rec.stage(t, y, W, N, ns, device, s));
+        LPVS_TRY(dD.set(D_out, 2 * ns * Nf));
+        LPVS_TRY(dWn.set(Wn_out, 2 * (2 * Nf - 1)));
+        LPVS_TRY(clean_dirty_stage("dirty_spectrum", rec, ls, dpart, hf, Nf, center_data != 0, path, clock, dWn.p, dD.p));
+        for (int i = 2; i <= 4; ++i) LPVS_TRY(clock.mark(i));
+        LPVS_TRY(dD.finish(s));
+        LPVS_TRY(dWn.finish(s));
+        LPVS_TRY(clock.finish());
+        clean_report(clock, ls.taken, nullptr, 0, 0, 0, 0.0);
+        return LPVS_OK;
+    } catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
+}
+
+int32_t lpvs_clean_loop_f64(const double *D, int64_t ns, int64_t Nf, const double *Wn, double gain, int64_t niter, double tol, int32_t device, double *R_out,
+                            double *C_out, int32_t *picks_out, double *pickval_out, int32_t *iters_out, int32_t *status_out) {
+    try {
+        if (!D || !Wn || !R_out || !C_out || !picks_out || !pickval_out || !iters_out || !status_out) { set_error("NULL argument"); return LPVS_EARGUMENT; }
+        if (is_device_ptr(picks_out) || is_device_ptr(iters_out) || is_device_ptr(status_out)) {
+            set_error("clean: picks_out, iters_out and status_out are host memory"); return LPVS_EARGUMENT;
+        }
+        const CleanPlan plan = clean_plan(ns, Nf, gain, niter, tol, clean_force_global());
+        if (plan.status != kCleanOk) return clean_refuse(plan.status, plan.why);
+        LPVS_TRY(Record::admit(device));
+        hipStream_t s = nullptr;
+        CleanClock clock;
+        LPVS_TRY(clock.init(s));
+        Staged<double> sD, sWn; DevOut dR, dC, dpv;
+        DevBuf dwork;
+        DrainOnExit drain(s);
+        LPVS_TRY(clock.mark(0));
+        LPVS_TRY(sD.set(D, 2 * ns * Nf, device, s));
+        LPVS_TRY(sWn.set(Wn, 2 * (2 * Nf - 1), device, s));
+        LPVS_TRY(dR.set(R_out, 2 * ns * Nf));
+        LPVS_TRY(dC.set(C_out, 2 * ns * Nf));
+        if (niter > 0) LPVS_TRY(dpv.set(pickval_out, 2 * ns * niter));
+        LPVS_TRY(clock.mark(1));
+        LPVS_TRY(clock.mark(2));
+        CleanLoopInfo info;
+        LPVS_TRY(clean_loop_stage("clean", sD.p, sWn.p, ns, Nf, gain, niter, tol, plan, dwork, dR.p, dC.p, dpv.p, picks_out, iters_out, status_out, s, &info));
+        LPVS_TRY(clock.mark(3));
+        LPVS_TRY(clock.mark(4));
+        LPVS_TRY(dR.finish(s));
+        LPVS_TRY(dC.finish(s));
+        if (niter > 0) LPVS_TRY(dpv.finish(s));
+        LPVS_TRY(clock.finish());
+        clean_report(clock, 0, &plan, info.itmin, info.itmax, info.nadm, 0.0);
+        return LPVS_OK;
+    } catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
+}
+
+int32_t lpvs_clean_restore_f64(const double *R, const double *C, int64_t ns, int64_t Nf, double df, double sigma, int32_t device, double *S_out) {
+    try {
+        if (!R || !C || !S_out) { set_error("NULL argument"); return LPVS_EARGUMENT; }
+        int status = kCleanOk; std::string why;
+        if (!clean_check_sizes("clean_restore", ns, Nf, &status, &why) || !clean_check_df("clean_restore", df, &status, &why)) return clean_refuse(status, why);
+        if (!(sigma > 0.0) || !std::isfinite(sigma)) { set_error("clean_restore: sigma must be positive and finite, got %g", sigma); return LPVS_EARGUMENT; }
+        LPVS_TRY(Record::admit(device));
+        hipStream_t s = nullptr;
+        CleanClock clock;
+        LPVS_TRY(clock.init(s));
+        Staged<double> sR, sC; DevOut dS;
+        DevBuf dwork;
+        DrainOnExit drain(s);
+        LPVS_TRY(clock.mark(0));
+        LPVS_TRY(sR.set(R, 2 * ns * Nf, device, s));
+        LPVS_TRY(sC.set(C, 2 * ns * Nf, device, s));
+        LPVS_TRY(dS.set(S_out, 2 * ns * Nf));
+        for (int i = 1; i <= 3; ++i) LPVS_TRY(clock.mark(i));
+        LPVS_TRY(clean_restore_stage(sR.p, sC.p, ns, Nf, df, sigma, dwork, dS.p, s));
+        LPVS_TRY(clock.mark(4));
+        LPVS_TRY(dS.finish(s));
+        LPVS_TRY(clock.finish());
+        clean_report(clock, 0, nullptr, 0, 0, 0, sigma);
+        return LPVS_OK;
+    } catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
+}
+
+int32_t lpvs_clean_f64(const double *y, int64_t ns, const double *t, int64_t N, const double *W, double df, int64_t Nf, int32_t center_data, int32_t path, double gain,
+                       int64_t niter, double tol, double sigma, int32_t device, double *D_out, double *Wn_out, double *R_out, double *C_out, int32_t *picks_out,
+                       double *pickval_out, int32_t *iters_out, int32_t *status_out, double *S_out, double *sigma_out) {
+    try {
+        if (!y || !t || !D_out || !Wn_out || !R_out || !C_out || !picks_out || !pickval_out || !iters_out || !status_out || !S_out) {
+            set_error("NULL argument"); return LPVS_EARGUMENT;
+        }
+        if (is_device_ptr(picks_out) || is_device_ptr(iters_out) || is_device_ptr(status_out) || (sigma_out && is_device_ptr(sigma_out))) {
+            set_error("clean: picks_out, iters_out, status_out and sigma_out are host memory"); return LPVS_EARGUMENT;
+        }
+        const CleanPlan plan = clean_plan(ns, Nf, gain, niter, tol, clean_force_global());
+        if (plan.status != kCleanOk) return clean_refuse(plan.status, plan.why);
+        int status = kCleanOk; std::string why;
+        if (!clean_check_df("clean", df, &status, &why)) return clean_refuse(status, why);
+        if (!(sigma >= 0.0) || !std::isfinite(sigma)) { set_error("clean: sigma must be finite and positive, or 0 to fit it, got %g", sigma); return LPVS_EARGUMENT; }
+        LPVS_TRY(clean_check_record("clean", N, path));
+        const std::vector<double> hf = clean_grid(df, Nf);
+        LPVS_TRY(Record::admit(device));
+        hipStream_t s = nullptr;
+        CleanClock clock;
+        LPVS_TRY(clock.init(s));
+        Record rec; DevOut dD, dWn, dR, dC, dpv, dS;
+        DevBuf dpart, dloop, drest; LombSums ls;
+        DrainOnExit drain(s);
+        LPVS_TRY(clock.mark(0));
+        LPVS_TRY(rec.stage(t, y, W, N, ns, device, s));
+        LPVS_TRY(dD.set(D_out, 2 * ns * Nf));
+        LPVS_TRY(dWn.set(Wn_out, 2 * (2 * Nf - 1)));
+        LPVS_TRY(dR.set(R_out, 2 * ns * Nf));
+        LPVS_TRY(dC.set(C_out, 2 * ns * Nf));
+        if (niter > 0) LPVS_TRY(dpv.set(pickval_out, 2 * ns * niter));
+        LPVS_TRY(dS.set(S_out, 2 * ns * Nf));
+        LPVS_TRY(clean_dirty_stage("clean", rec, ls, dpart, hf, Nf, center_data != 0, path, clock, dWn.p, dD.p));
+        LPVS_TRY(clock.mark(2));
+        CleanLoopInfo info;
+        LPVS_TRY(clean_loop_stage("clean", dD.p, dWn.p, ns, Nf, gain, niter, tol, plan, dloop, dR.p, dC.p, dpv.p, picks_out, iters_out, status_out, s, &info));
+        LPVS_TRY(clock.mark(3));
+        if (sigma == 0.0) {                                                   // the beam's width from the window (clean_plan.h: clean_sigma)
+            std::vector<double> hWn((size_t)(2 * (2 * Nf - 1)));
+            LPVS_TRY(copy_from_device(hWn.data(), dWn.p, sizeof(double) * hWn.size(), s));
+            sigma = clean_sigma(hWn.data(), Nf, df);
+            if (!(sigma > 0.0) || !std::isfinite(sigma)) { set_error("clean: the fitted sigma of the beam is %g", sigma); return LPVS_ENUMERIC; }
+        }
+        if (sigma_out) *sigma_out = sigma;
+        LPVS_TRY(clean_restore_stage(dR.p, dC.p, ns, Nf, df, sigma, drest, dS.p, s));
+        LPVS_TRY(clock.mark(4));
+        LPVS_TRY(dD.finish(s));
+        LPVS_TRY(dWn.finish(s));
+        LPVS_TRY(dR.finish(s));
+        LPVS_TRY(dC.finish(s));
+        if (niter > 0) LPVS_TRY(dpv.finish(s));
+        LPVS_TRY(dS.finish(s));
+        LPVS_TRY(clock.finish());
+        clean_report(clock, ls.taken, &plan, info.itmin, info.itmax, info.nadm, sigma);
+        return LPVS_OK;
+    } catch (const std::bad_alloc &) { set_error("out of host memory"); return LPVS_ENOMEM; }
+}
+
+int32_t lpvs_clean_last_timing(double *out, int32_t n) {
+    return copy_timing(out, n, g_clean_timing, 14);
 }
 
 // ---- the bootstrap of the Lomb-Scargle periodogram (lomb_boot.hip; the decisions: lomb_boot_plan.h) ------------------------------------------
