@@ -4,7 +4,9 @@ tests/test_bls_ref_host.py (which proves them on the CPU) and tests/test_gpu_bls
 bls_model     the definition as the device computes it, restated in numpy: the moments by the device's fixed trees (device_sum), YY as the
               order-free integer sum of its terms (order_free_yy), the quantisation to 64-bit integers, the fold by the exact product's phase, integer histograms and box sums, the objective in
               double from the integers in the stated order of operations, the tie rule.  Integers are compared exactly, doubles to a few ulp.
-              It also reports, per (frequency, signal), the GAP between the best objective and the best one of a box with other (r, s), in ulp.
+              It also reports, per (frequency, signal), the GAP between the best objective and the best one of a box with other (r, s), in ulp,
+              and GAP2, which sets the boxes with the complement's sums (R - r, S - s) aside as well: with dips_only = False a box and its
+              complement have bit-equal objectives, a tie the rule decides (narrowest, then earliest), and gap = 0 there by construction.
 bls_ref_ld    the definition in long double straight from the samples: no quantisation, the exact phase (tests/_phase_ref.py), every
               box summed bin by bin.
 bls_bounds    how far the two may differ -- derived, to first order, from the quantisation and the roundings (nothing fitted):
@@ -143,7 +145,7 @@ def bls_model(y, t, f, W=None, nbins=64, kmin=1, kmax=8, min_count=1, dips_only=
     qy = np.stack([quantise(wy[c], shy[c]) if A[c] > 0 else np.zeros(N, np.int64) for c in range(ns)])
     qw = None if unit else quantise(w, WSHIFT)
     bins, _ = fold_bins(f, t, nbins)
-    out = {k: np.zeros((Nf, ns)) for k in ("power", "depth", "depth_err", "gap", "dq")}
+    out = {k: np.zeros((Nf, ns)) for k in ("power", "depth", "depth_err", "gap", "gap2", "dq")}
     out.update({k: np.zeros((Nf, ns), np.int64) for k in ("start", "width", "count", "degenerate")})
     hist, hcount = np.zeros((Nf, 1 + ns, nbins), np.int64), np.zeros((Nf, nbins), np.int64)
     for k in range(Nf):
@@ -179,13 +181,18 @@ def bls_model(y, t, f, W=None, nbins=64, kmin=1, kmax=8, min_count=1, dips_only=
                 other = valid & ~((r == r[i, b]) & (s == s[i, b]))
                 second = masked[other].max() if other.any() else -np.inf
                 out["gap"][k, c] = (best - second) / np.spacing(abs(best)) if best != 0 else np.inf
+                # gap2: the complement of the best box, the sums (R - r, S - s), is set aside too.  Its objective has the best one's BITS
+                # (the two quotients change places and the sum commutes), so that tie is the rule's to decide, exactly, not a near-tie
+                other &= ~((r == R - r[i, b]) & (s == S - s[i, b]))
+                second = masked[other].max() if other.any() else -np.inf
+                out["gap2"][k, c] = (best - second) / np.spacing(abs(best)) if best != 0 else np.inf
                 out["dq"][k, c] = best
                 dpos = max(best, 0.0)
                 delta = np.ldexp(dpos * float(N), -2 * shy[c]) if unit else np.ldexp(dpos, WSHIFT - 2 * shy[c])
                 live = bool(np.isfinite(delta))
             if not live:
                 out["degenerate"][k, c] = 1
-                out["gap"][k, c] = np.inf
+                out["gap"][k, c] = out["gap2"][k, c] = np.inf
                 continue
             rt = float(r[i, b]) / float(N) if unit else np.ldexp(float(r[i, b]), -WSHIFT)
             rct = float(rc[i, b]) / float(N) if unit else np.ldexp(float(rc[i, b]), -WSHIFT)
@@ -334,3 +341,33 @@ def base_case(seed=0, N=1500, span=375.0, Nf=70, ns=1, depth=0.5, q=0.05, f0=1.2
         inside = (ph >= 0.97) | (ph < q - 0.03)
         y[inside, c] += (depth * (1 + c) if c else depth) * (1.0 if bump else -1.0)
     return t, f, (y[:, 0] if ns == 1 else y)
+
+
+COMPLEMENT_NBINS = (8, 64, 128, 256, 512)
+
+
+def complement_case(weighted):
+    """The inputs of the complement ties (dips_only = False, kmin = 1, widths up to nbins / 2 and, in the model, up to nbins - 1):
+    base_case(N = 257, span = 64), with unit weights or W.  -> t, f, y, W or None."""
+    t, f, y = base_case(seed=0, N=257, span=64.0, Nf=70, ns=1)
+    W = 0.5 + np.random.default_rng(100 + 257).random(len(t)) if weighted else None
+    return t, f, y, W
+
+
+HALF_K = 24                                                                    # f[24] = 1
+
+
+def half_case(weighted):
+    """A record on which the tie DECIDES the answer at every nbins of COMPLEMENT_NBINS: 512 samples whose phases at f = 1 are
+    (2 b + 1) / 1024, b = 0 .. 511 -- one in every one of 512 bins, equally many in every bin of a coarser power of two --, low over
+    the phases [1/4, 3/4) and high elsewhere, under noise a twentieth of the step.  At f = 1 the best box is HALF the bins wide and
+    starts at nbins / 4; its complement starts nbins / 2 further on with the same objective, bit for bit, and is among the boxes the
+    device searches (widths up to nbins / 2).  Asserted on the model by tests/test_bls_ref_host.py.  -> t, f, y, W or None."""
+    rng = np.random.default_rng(12)
+    b = np.arange(512)
+    t = rng.integers(0, 64, 512) + (2 * b + 1) / 1024.0
+    f = 0.25 + np.arange(70) / 32.0
+    y = np.where((b >= 128) & (b < 384), -1.0, 1.0) + 0.05 * rng.standard_normal(512)
+    perm = rng.permutation(512)
+    W = 0.5 + rng.random(512) if weighted else None
+    return t[perm], f, y[perm], W

@@ -201,6 +201,151 @@ def conservation(D, Wn, R, C):
     return np.maximum(np.abs(sre - Dre), np.abs(sim - Dim)), mag
 
 
+# ---- planted spectra: the tie rule, the stop and the cut decide every pick --------------------------------------------------------------------
+# The loop takes any finite D and Wn, so ties are planted where records never produce them.  With the DELTA WINDOW Wn = (1, 0, 0, ...):
+# den_0 = 0 (bin 0 is inadmissible) and den_p = 1 elsewhere; a pick of bin p has c = gain R_p, changes bin p alone (every other bin has
+# +-0 subtracted) and leaves R_p - c there.  With gain 1/2 or 1 and D of small Gaussian integers every operation is exact, so the answer
+# is known in closed form and delta_oracle states it without the model.  No -0.0 may enter: x - (-0.0) turns a residual of -0.0 into +0.0
+# in the loop's update pass, which the oracle does not walk (asserted on its input; none arises from +0.0 and exact halvings).
+PLANTED_NF = [256 * w - 1 for w in range(1, 17)] + [2, 3, 65, 8192, 8193]      # threads = 64 w with a ragged last stride; the edges of the plan
+MODEL_NF_MOST = 1030                                                           # beyond it the device is held to the oracle alone (the model is slow)
+_UNITS25 = ((5, 0), (3, 4), (-4, 3), (0, -5), (-3, -4))                        # |.|^2 = 25, five different bit patterns
+_UNITS1 = ((1, 0), (0, 1), (-1, 0), (0, -1))
+
+
+def _gaussian(pairs, Nf):
+    z = np.zeros(Nf, dtype=np.complex128)
+    z.real = [pairs[k % len(pairs)][0] for k in range(Nf)]
+    z.imag = [pairs[k % len(pairs)][1] for k in range(Nf)]
+    return z + 0.0                                                             # (-0.0 + 0.0 = +0.0: no negative zero)
+
+
+def delta_window(Nf):
+    Wn = np.zeros(2 * Nf - 1, dtype=np.complex128)
+    Wn[0] = 1.0
+    return Wn
+
+
+def planted_spectra(Nf):
+    """D [4][Nf]: 0 all bins 5; 1 the five Gaussian integers of modulus 5 in turn (P ties, the residual's bits do not); 2 modulus 5 at
+    the bins 1 + 64 j only -- the same lane of every wave and stride -- and modulus 1 elsewhere; 3 zero."""
+    D = np.zeros((4, Nf), dtype=np.complex128)
+    D[0] = 5.0
+    D[1] = _gaussian(_UNITS25, Nf)
+    D[2] = _gaussian(_UNITS1, Nf)
+    at = np.arange(1, Nf, 64)
+    D[2, at] = _gaussian(_UNITS25, len(at))
+    D.setflags(write=False)
+    return D
+
+
+def delta_oracle(D, gain, niter, tol):
+    """The loop on the delta window as a scalar simulation, independent of _loop: a heap of (-P_p, p) over the bins 1 .. Nf - 1 -- its
+    top is the largest P at the lowest index --, c = gain R_p, C_p += c, R_p -= c.  -> the dict of clean_model, spectra as complex arrays."""
+    import heapq
+    D = np.asarray(D, dtype=np.complex128)
+    Nf = len(D)
+    re, im = [float(v) for v in D.real], [float(v) for v in D.imag]
+    assert not np.signbit(D.real[D.real == 0]).any() and not np.signbit(D.imag[D.imag == 0]).any(), "the oracle takes no -0.0"
+    cre, cim = [0.0] * Nf, [0.0] * Nf
+    heap = [(-(re[p] * re[p] + im[p] * im[p]), p) for p in range(1, Nf)]
+    heapq.heapify(heap)
+    picks, pvr, pvi = [-1] * niter, [0.0] * niter, [0.0] * niter
+    it, status, thr = 0, NITER, 0.0
+    while it < niter:
+        if not heap:
+            status = EMPTY
+            break
+        negP, p = heap[0]
+        P = -negP
+        assert P == P, "a NaN arose"
+        if it == 0:
+            thr = (tol * tol) * P
+        if tol > 0 and P <= thr:
+            status = TOL
+            break
+        cr, ci = gain * re[p], gain * im[p]
+        cre[p], cim[p] = cre[p] + cr, cim[p] + ci
+        re[p], im[p] = re[p] - cr, im[p] - ci
+        picks[it], pvr[it], pvi[it] = p, cr, ci
+        heapq.heapreplace(heap, (-(re[p] * re[p] + im[p] * im[p]), p))
+        it += 1
+    return dict(R=to_complex(np.array(re), np.array(im)), C=to_complex(np.array(cre), np.array(cim)), picks=np.array(picks, dtype=np.int32).reshape(niter),
+                pick_values=to_complex(np.array(pvr).reshape(niter), np.array(pvi).reshape(niter)), iterations=it, status=status, admissible=Nf - 1)
+
+
+def model_as_complex(m):
+    """A result of clean_model in the oracle's layout (spectra as complex arrays, admissible as a count)."""
+    return dict(R=to_complex(*m["R"]), C=to_complex(*m["C"]), picks=m["picks"], pick_values=to_complex(*m["pick_values"]), iterations=m["iterations"],
+                status=m["status"], admissible=int(m["admissible"].sum()))
+
+
+def same_result(a, b):
+    """The first key at which two results (delta_oracle's layout) differ in a byte, or None."""
+    for key in ("picks", "pick_values", "C", "R"):
+        x, y = np.ascontiguousarray(a[key]), np.ascontiguousarray(b[key])
+        if x.dtype != y.dtype or x.shape != y.shape or x.tobytes() != y.tobytes():
+            return key
+    for key in ("iterations", "status", "admissible"):
+        if int(a[key]) != int(b[key]):
+            return key
+    return None
+
+
+def sidelobe_window(Nf):
+    """Wn_0 = 1 with dyadic sidelobes: every admissible bin still ties at iteration 0 (den_1 = 1 - 2^-8, den_p = 1 beyond), and from
+    the first pick on the update pass moves the neighbours by exact dyadic amounts."""
+    Wn = delta_window(Nf)
+    for m, v in ((1, complex(2.0 ** -3, 0.0)), (2, complex(0.0, -2.0 ** -4)), (5, complex(2.0 ** -6, 2.0 ** -6))):
+        if m < len(Wn):
+            Wn[m] = v
+    return Wn
+
+
+def cut_doubles():
+    """(at, above, below): doubles wr near sqrt(1 - 2^-20) with den = fl(1 - fl(wr wr)) == 2^-20 exactly (None if no double gives it),
+    the closest with den > 2^-20 and the closest with den < 2^-20.  1 - x is exact for x in [1/2, 1], so den == 2^-20 asks for
+    fl(wr wr) == 1 - 2^-20; squares of neighbouring doubles there are 2^-52 apart, twice the spacing of the products, so about every
+    other double of the products is hit: found by a search of the neighbours, nothing assumed."""
+    den = lambda w: np.float64(1.0) - np.float64(w) * np.float64(w)            # noqa: E731
+    w0 = np.sqrt(np.float64(1.0) - np.float64(MIN_DEN))
+    near = [w0]
+    lo = hi = w0
+    for _ in range(64):
+        lo, hi = np.nextafter(lo, 0.0), np.nextafter(hi, 2.0)
+        near += [lo, hi]
+    near = sorted(near)                                                        # den falls as wr grows
+    at = [w for w in near if den(w) == MIN_DEN]
+    above, below = [w for w in near if den(w) > MIN_DEN], [w for w in near if den(w) < MIN_DEN]
+    return (float(at[0]) if at else None), float(above[-1]), float(below[0])
+
+
+CUT_NF = 1023                                                                  # 256 threads: bin k is thread k mod 256's, wave (k mod 256) >> 6
+CUT_BINS = {"at": (10, 330, 650), "above": (100, 420, 740), "below": (150, 470, 790)}     # k mod 256 = 10, 74, 138 / 100, 164, 228 / 150, 214, 22: three waves each
+
+
+def cut_case():
+    """(D [2][Nf], Wn, found): the delta window with Wn_2p at the cut, just above and just below it, each at three bins whose threads
+    sit in different waves (CUT_BINS).  The bins below the cut carry the largest |D|, those at and just above it the next largest,
+    so that the first picks are theirs; the rest are integers of modulus <= 3 (real: see below).  found: whether a double sits AT the cut (its
+    bins then take the value just above: the other two legs stand)."""
+    at, above, below = cut_doubles()
+    Nf = CUT_NF
+    Wn = delta_window(Nf)
+    rng = np.random.default_rng(23)
+    D = np.zeros((2, Nf), dtype=np.complex128)
+    D.real, D.imag = rng.integers(-3, 4, (2, Nf)), rng.integers(-4, 5, (2, Nf))
+    D.imag = 0.0                                                               # real: with Wn_2p real and den = 2^-20 a pick multiplies an imaginary part by 2^21
+    D = D + 0.0
+    for name, w in (("at", above if at is None else at), ("above", above), ("below", below)):
+        for j, p in enumerate(CUT_BINS[name]):
+            Wn[2 * p] = w
+            D[:, p] = (9.0 + j) if name == "below" else (6.0 + j if name == "at" else 6.5 + j)
+    D.setflags(write=False)
+    Wn.setflags(write=False)
+    return D, Wn, at is not None
+
+
 def clean_sigma(Wn, df):
     """csrc/clean_plan.h clean_sigma, operation for operation."""
     Wre, Wim = Wn if isinstance(Wn, tuple) else from_complex(Wn)

@@ -6,8 +6,8 @@ rule at its limit.  CPU only."""
 import numpy as np
 import pytest
 
-from _bls_ref import (LD, U, base_case, bls_bounds, bls_model, bls_ref_ld, device_moments, device_sum, fold_bins, ld_bins, order_free_yy, quantise,
-                      ref_at_box, shift_y)
+from _bls_ref import (COMPLEMENT_NBINS, HALF_K, LD, U, base_case, bls_bounds, bls_model, bls_ref_ld, complement_case, device_moments, device_sum, fold_bins,
+                      half_case, ld_bins, order_free_yy, quantise, ref_at_box, shift_y)
 
 
 def _compare(y, t, f, W, kw, m=None, r=None, y_ref=None, skip=()):
@@ -161,3 +161,41 @@ def test_device_sum_is_the_fixed_tree():
     a = np.zeros(512); a[0], a[1], a[128], a[256] = 1.0, 2.0 ** -53, 2.0 ** -53, 2.0 ** -53
     # (1 + 2^-53 a[128]) first: the tree pairs i with i + 128, so 1 + 2^-53 rounds to 1, and again with a[1]; slab 1 joins last
     assert device_sum(a) == 1.0
+
+
+# ---- complement ties: the inputs of tests/test_gpu_bls.py's planted cases ------------------------------------------------------------------------
+@pytest.mark.parametrize("weighted", [False, True])
+@pytest.mark.parametrize("nbins", COMPLEMENT_NBINS)
+def test_a_box_ties_with_its_complement_and_the_narrower_wins(nbins, weighted):
+    """dips_only = False, every width 1 .. nbins - 1: each box has its complement among the boxes, with other sums and the same
+    objective bit for bit -- the first gap is 0 at ALL 70 frequencies -- and the rule gives the narrower of the two, so no winner is
+    wider than nbins / 2 and the search over 1 .. nbins / 2 (the widest the library takes: kmax <= nbins / 2) returns the same boxes
+    and the same second gap.  The second gap leaves at most 2 frequencies with a near-tie (it leaves none)."""
+    t, f, y, W = complement_case(weighted)
+    kw = dict(nbins=nbins, kmin=1, min_count=1, dips_only=False, center_data=True, normalization="standard")
+    full, half = bls_model(y, t, f, W, kmax=nbins - 1, **kw), bls_model(y, t, f, W, kmax=nbins // 2, **kw)
+    assert full["ndeg"] == 0 and np.all(full["gap"] == 0) and full["gap"].shape == (70, 1)
+    assert full["width"].max() <= nbins // 2 and np.all(full["gap2"] > 0)
+    for key in ("start", "width", "count", "power", "depth", "depth_err", "gap2"):
+        assert np.array_equal(full[key], half[key]), key
+    near = (half["gap2"] <= 8).any(axis=1).sum()
+    print(f"nbins {nbins} W={weighted}: widest winner {full['width'].max()}, smallest second gap {half['gap2'].min():.3g} ulp, {near} near-ties")
+    assert near <= 2
+    r = bls_ref_ld(y, t, f, W, kmax=nbins // 2, **kw)
+    clear = half["gap2"] > 8                                                  # the long-double definition has the same near-exact tie: equal boxes or complements
+    same = (half["start"] == r["start"]) & (half["width"] == r["width"])
+    comp = (np.mod(half["start"] + half["width"], nbins) == r["start"]) & (half["width"] + r["width"] == nbins)
+    assert np.all((same | comp)[clear])
+
+
+@pytest.mark.parametrize("weighted", [False, True])
+@pytest.mark.parametrize("nbins", COMPLEMENT_NBINS)
+def test_the_half_period_record_makes_the_tie_decide(nbins, weighted):
+    """At f = 1 the model's box is nbins / 2 wide and starts at nbins / 4; the first gap is 0 (the complement, nbins / 2 further on, is
+    searched too) and the second is far from a near-tie: the earlier start is the answer because of the rule alone."""
+    t, f, y, W = half_case(weighted)
+    m = bls_model(y, t, f, W, nbins=nbins, kmin=1, kmax=nbins // 2, min_count=1, dips_only=False, center_data=True, normalization="standard")
+    k = HALF_K
+    assert f[k] == 1.0 and (m["start"][k, 0], m["width"][k, 0]) == (nbins // 4, nbins // 2) and m["count"][k, 0] == 256
+    assert m["gap"][k, 0] == 0 and m["gap2"][k, 0] > 1e6 and m["depth"][k, 0] > 1.9 and m["ndeg"] == 0
+    assert (m["gap2"] <= 8).any(axis=1).sum() <= 2

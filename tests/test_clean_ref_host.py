@@ -135,3 +135,99 @@ def test_sigma_is_the_half_power_width_of_the_main_lobe():
     P = Wn.real * Wn.real
     want = ((1.0 + (P[1] - 0.5) / (P[1] - P[2])) * 0.25) / np.sqrt(2 * np.log(2.0))
     assert abs(ref.clean_sigma(Wn, 0.25) - want) <= 4 * U * want
+
+
+# ---- planted spectra: the closed forms the GPU's loop is held to (tests/test_gpu_clean.py) ----------------------------------------------------
+def _planted_runs(Nf):
+    D = ref.planted_spectra(Nf)
+    return [ref.delta_oracle(D[c], 0.5, 2 * (Nf - 1) + 1, 0.0) for c in range(4)]
+
+
+@pytest.mark.parametrize("Nf", [n for n in ref.PLANTED_NF if n <= ref.MODEL_NF_MOST] + [257, 1030])
+def test_the_delta_window_oracle_equals_the_model(Nf):
+    """Byte for byte on all four planted patterns, with the iteration count the GPU test uses."""
+    D, Wn = ref.planted_spectra(Nf), ref.delta_window(Nf)
+    for c, o in enumerate(_planted_runs(Nf)):
+        m = ref.clean_model(D[c], Wn, 0.5, 2 * (Nf - 1) + 1, 0.0)
+        assert not m["admissible"][0] and m["admissible"][1:].all() and m["den"][0] == 0.0 and np.all(m["den"][1:] == 1.0)
+        assert ref.same_result(o, ref.model_as_complex(m)) is None, (Nf, c, ref.same_result(o, ref.model_as_complex(m)))
+
+
+@pytest.mark.parametrize("Nf", [2, 257, 1030, 4096, 8193])
+def test_equal_peaks_are_picked_in_index_order(Nf):
+    """All P equal: the picks walk the admissible bins in increasing index, round after round, each pick halving its bin; pattern 2 takes
+    its bins of modulus 5 three times (25, 25/4, 25/16 > 1) before any other; an all-zero spectrum picks bin 1 with value 0 every time."""
+    K, n = Nf - 1, 2 * (Nf - 1) + 1
+    runs = _planted_runs(Nf)
+    D = ref.planted_spectra(Nf)
+    i = np.arange(n)
+    for c in (0, 1):
+        o = runs[c]
+        assert np.array_equal(o["picks"], 1 + i % K) and o["iterations"] == n and o["status"] == ref.NITER
+        want = 0.5 ** (1 + i // K) * D[c][1 + i % K]
+        assert o["pick_values"].tobytes() == want.astype(np.complex128).tobytes()
+        assert np.array_equal(o["R"][2:], D[c][2:] / 4) and o["R"][1] == D[c][1] / 8 and o["R"][0] == D[c][0] and o["C"][0] == 0
+    big = np.arange(1, Nf, 64)
+    assert np.array_equal(runs[2]["picks"][:min(n, 3 * len(big))], np.tile(big, 3)[:n])
+    if n > 3 * len(big):
+        rest = np.setdiff1d(np.arange(1, Nf), big)
+        assert np.array_equal(runs[2]["picks"][3 * len(big):][:len(rest)], rest[:n - 3 * len(big)])
+    assert np.all(runs[3]["picks"] == 1) and not runs[3]["pick_values"].any() and not runs[3]["R"].any() and not runs[3]["C"].any()
+    assert all(r["admissible"] == K for r in runs)
+
+
+@pytest.mark.parametrize("Nf", [2, 257, 1030])
+def test_the_stop_at_equality(Nf):
+    """bP <= thr WITH equality: all bins 5, tol = 2^-3: thr = 25 / 64, and each bin is picked at 25, 25/4 and 25/16 -- 3 (Nf - 1) picks --
+    before every P equals thr; with gain 1 a pick zeroes its bin and the loop stops after Nf - 1.  tol = 0 never stops: the picks beyond
+    Nf - 1 fall on bin 1 with value 0."""
+    K = Nf - 1
+    D, Wn = ref.planted_spectra(Nf)[0], ref.delta_window(Nf)
+    for kw, iters, status in ((dict(gain=0.5, niter=3 * K + 7, tol=2.0 ** -3), 3 * K, ref.TOL), (dict(gain=1.0, niter=3 * K + 7, tol=2.0 ** -3), K, ref.TOL),
+                              (dict(gain=1.0, niter=Nf + 5, tol=0.0), Nf + 5, ref.NITER)):
+        o, m = ref.delta_oracle(D, **kw), ref.model_as_complex(ref.clean_model(D, Wn, **kw))
+        assert ref.same_result(o, m) is None
+        assert (o["iterations"], o["status"]) == (iters, status), (kw, o["iterations"], o["status"])
+        assert np.all(o["picks"][iters:] == -1)
+    assert np.all(o["picks"][K:] == 1) and not o["pick_values"][K:].any() and len(o["picks"][K:]) == 6
+    assert ref.clean_model(ref.planted_spectra(257)[0], ref.delta_window(257), 0.5, 800, 2.0 ** -3)["iterations"] == 768
+
+
+def test_peaks_that_overflow_tie_at_infinity():
+    D = np.full(8, complex(1e200, 0.0))
+    o, m = ref.delta_oracle(D, 0.5, 20, 0.0), ref.clean_model(D, ref.delta_window(8), 0.5, 20, 0.0)
+    assert ref.same_result(o, ref.model_as_complex(m)) is None
+    assert np.all(o["picks"] == 1) and o["iterations"] == 20 and o["status"] == ref.NITER
+    assert np.array_equal(o["pick_values"], 1e200 * 0.5 ** np.arange(1, 21)) and np.all(np.isfinite(o["R"].view(np.float64))) and np.all(o["R"][2:] == 1e200)
+    assert float(o["R"][1].real) * float(o["R"][1].real) == np.inf                                       # ... still +inf at the last pick: every one was decided by the index
+
+
+@pytest.mark.parametrize("Nf", [257, 1030])
+def test_sidelobes_after_a_tie_of_every_bin(Nf):
+    """The inputs of the sidelobe case: every admissible bin ties at iteration 0, nothing overflows, and the update pass is not trivial
+    (the picks are not those of the delta window)."""
+    Wn = ref.sidelobe_window(Nf)
+    for c in (0, 1):
+        D = ref.planted_spectra(Nf)[c]
+        ld = ref.clean_loop_ld(D, Wn, 0.5, 300, 0.0)
+        m = ref.clean_model(D, Wn, 0.5, 300, 0.0)
+        assert ld["gaps"][0] == 0.0 and m["picks"][0] == 1 and m["admissible"].sum() == Nf - 1 and m["den"][1] == 1.0 - 2.0 ** -8
+        assert m["iterations"] == 300 and all(np.isfinite(a).all() for a in m["R"] + m["C"])
+        assert not np.array_equal(m["picks"], ref.delta_oracle(D, 0.5, 300, 0.0)["picks"])
+
+
+def test_the_cut_is_found_by_search_and_decides_admission():
+    at, above, below = ref.cut_doubles()
+    den = lambda w: np.float64(1.0) - np.float64(w) * np.float64(w)            # noqa: E731
+    assert den(above) > ref.MIN_DEN > den(below) and den(above) - ref.MIN_DEN <= 2.0 ** -52 and ref.MIN_DEN - den(below) <= 2.0 ** -52      # (neighbouring squares: 2^-52 apart)
+    assert at is None or (den(at) == ref.MIN_DEN and below > at > above)
+    D, Wn, found = ref.cut_case()
+    assert found == (at is not None)
+    for c in range(2):
+        m = ref.clean_model(D[c], Wn, 0.5, 60, 0.0)
+        assert list(np.flatnonzero(~m["admissible"])) == [0] + sorted(ref.CUT_BINS["below"])
+        assert np.abs(D[c]).argmax() in ref.CUT_BINS["below"] and not set(ref.CUT_BINS["below"]) & set(m["picks"].tolist())
+        assert m["picks"][0] == ref.CUT_BINS["above"][2] and m["picks"][1] == ref.CUT_BINS["at"][2]       # the first picks sit just above and AT the cut
+        assert m["iterations"] == 60 and all(np.isfinite(a).all() for a in m["R"] + m["C"])
+        waves = lambda bins: sorted((p % 256) >> 6 for p in bins)             # noqa: E731
+        assert all(len(set(waves(b))) == 3 for b in ref.CUT_BINS.values())

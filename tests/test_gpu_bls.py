@@ -14,13 +14,22 @@ NEAR-TIES.  A (frequency, signal) whose model gap -- best objective against the 
 8 ulp need not return the model's box (the device's quotients may differ from numpy's in the last place).  There the device's box,
 evaluated by the long-double reference, must lie within 2 B of the reference's maximum (B bounds the objective of EVERY box, so a box
 that is best for one is within 2 B of the other's best), and its power, depth and depth_err are held to the reference's values of THAT
-box.  At most 2 frequencies per case may hold a near-tie: asserted on the inputs (they hold none)."""
+box.  At most 2 frequencies per case may hold a near-tie: asserted on the inputs (they hold none).
+
+COMPLEMENT TIES (tests/_bls_ref.py: complement_case, half_case).  With dips_only = False a box and its complement -- the sums (R - r, S - s)
+-- have the same objective BIT FOR BIT: the two quotients change places and their sum commutes.  That is an exact tie, which the rule
+decides (narrowest, then earliest), not a near-tie; so for these cases a frequency is clear when the model's SECOND gap (gap2: the boxes
+with the complement's sums set aside as well) exceeds 8 ulp, and the exemption above stays for the others, with its cap of 2.  The
+library takes widths up to nbins / 2, so the complements that are searched are those of the boxes of width nbins / 2 (the model with
+every width up to nbins - 1 has gap 0 at all 70 frequencies and the same winners, tests/test_bls_ref_host.py); the "half" record makes
+such a box the maximum at f = 1 for nbins in {8, 64, 128, 256, 512}."""
 import functools
 
 import numpy as np
 import pytest
 
-from _bls_ref import LD, base_case, bls_bounds, bls_model, bls_ref_ld, device_moments, fold_bins, ld_bins, ref_at_box
+from _bls_ref import (COMPLEMENT_NBINS, HALF_K, LD, base_case, bls_bounds, bls_model, bls_ref_ld, complement_case, device_moments, fold_bins, half_case, ld_bins,
+                      ref_at_box)
 
 pytestmark = pytest.mark.gpu
 
@@ -110,8 +119,8 @@ def _within_ulp(a, b, n=4):
 WORST = {}
 
 
-def _check_against_refs(name, d, m, r, t, f, y, W, kw):
-    """The assertions of one case (module docstring)."""
+def _check_against_refs(name, d, m, r, t, f, y, W, kw, gap="gap"):
+    """The assertions of one case (module docstring).  gap: the model's gap that says where a near-tie is ("gap2" for the complement ties)."""
     Nf, ns = m["power"].shape
     assert np.array_equal(d["hist"], m["hist"]), "the integer histograms"
     assert np.array_equal(d["hcount"], m["hcount"]), "the counts per bin"
@@ -119,7 +128,7 @@ def _check_against_refs(name, d, m, r, t, f, y, W, kw):
     assert np.array_equal(d["degenerate"] != 0, m["degenerate"] != 0)
     for key in ("power", "depth", "depth_err"):
         assert np.all(np.isfinite(d[key])), key
-    near = m["gap"] <= 8
+    near = m[gap] <= 8
     assert near.any(axis=1).sum() <= 2, f"{near.any(axis=1).sum()} frequencies with a near-tie in the inputs of {name}"
     clear = ~near
     for key in ("start", "width", "count"):
@@ -158,6 +167,38 @@ def test_every_shape_against_the_model_and_the_long_double_definition(name):
     assert (tm["shift_y_min"], tm["shift_y_max"]) == (min(live_shy), max(live_shy)) and tm["shift_w"] == (0 if W is None else 60)
     _check_against_refs(name, d, m, r, t, f, y, W, kw)
     print(f"{name}: worst error / bound so far {WORST}")
+
+
+# ---- complement ties ---------------------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _complement(record, nbins, weighted):
+    t, f, y, W = (complement_case if record == "base" else half_case)(weighted)
+    kw = dict(nbins=nbins, kmin=1, kmax=nbins // 2, min_count=1, dips_only=False, center_data=True, normalization="standard")
+    return (t, f, y, W), kw, bls_model(y, t, f, W, **kw), bls_ref_ld(y, t, f, W, **kw)
+
+
+@pytest.mark.parametrize("weighted", [False, True])
+@pytest.mark.parametrize("nbins", COMPLEMENT_NBINS)
+@pytest.mark.parametrize("record", ["base", "half"])
+def test_a_box_and_its_complement_tie_and_the_rule_decides(record, nbins, weighted):
+    """dips_only = False and every width the library takes, 1 .. nbins / 2 (module docstring, NEAR-TIES): the boxes of width nbins / 2
+    have their complements among the boxes searched, nbins / 2 starts further on -- in the same wave (nbins 8, 64), the next one (128),
+    two waves on (256), the same thread's next stride (512) -- with bit-equal objectives.  On the "half" record that tie is the
+    maximum at f = 1, and the earlier start the only right answer."""
+    (t, f, y, W), kw, m, r = _complement(record, nbins, weighted)
+    d = _raw(y, t, f, W, **kw)
+    assert d["timing"]["boxes"] == len(f) * nbins * (nbins // 2)
+    clear = m["gap2"] > 8
+    print(f"{record} nbins {nbins} W={weighted}: {int((m['gap'] == 0).sum())} of {len(f)} frequencies with an exact tie at the maximum, "
+          f"{int((~clear).sum())} near-ties, widest box {int(d['width'].max())}")
+    for key in ("start", "width", "count"):
+        assert np.array_equal(d[key][clear], m[key][clear]), key
+    assert np.all(d["width"] <= nbins // 2)
+    _check_against_refs(f"{record}{nbins}", d, m, r, t, f, y, W, kw, gap="gap2")
+    if record == "half":
+        k = HALF_K
+        assert m["gap"][k, 0] == 0 and clear[k, 0]
+        assert (d["start"][k, 0], d["width"][k, 0], d["count"][k, 0]) == (nbins // 4, nbins // 2, 256) and d["depth"][k, 0] > 1.9
 
 
 def test_the_planted_dip_is_found_and_wraps():

@@ -2,7 +2,15 @@
 own checks: tests/test_clean_ref_host.py).
 
 INPUTS.  The exact-phase family of tests/_bls_ref.py: t in multiples of 2^-10, df = 2^-6, so every product (m df) t is exact in double
-and the reference's phases are beyond dispute.
+and the reference's phases are beyond dispute.  Every such record carries noise, so two bins with bit-equal P never meet, no den lies
+near the cut 2^-20 and the stop never meets equality: on those inputs the tie rule decides nothing.
+PLANTED (tests/_clean_ref.py: planted_spectra, delta_window, sidelobe_window, cut_case).  clean_loop takes any finite D and Wn, so what the
+records never produce is planted: on the delta window Wn = (1, 0, ...) four spectra per call -- all bins 5; the Gaussian integers of
+modulus 5 in turn (equal P, different bits); modulus 5 at the bins 1 + 64 j only (the same lane of every wave and stride); zero -- at
+Nf = 256 w - 1 for EVERY wave count w = 1 .. 16 and at 2, 3, 65, 8192, 8193, with 2 (Nf - 1) + 1 iterations; the stop at equality; peaks
+of +inf; dyadic sidelobes; den exactly at the cut and one double to either side.  All arithmetic on these is exact, so the expected
+result is a closed form, stated by delta_oracle without the model; the model is compared too up to Nf = 1030.  The restoration's
+compaction gets every bin, no bin, the ends of its chunks of 256, and parts that are zero, negative zero or imaginary alone.
 BOUNDS (u = 2^-53).
   sums, direct path   |sum - ref| <= (N + 16) u sum|terms| + 4 u per term of trigonometry, the bound tests/test_gpu_lomb.py holds the same
                       kernels to; transform path: its 1e-12 sum|terms|.  The device centres with its own weighted means, which it does
@@ -151,6 +159,173 @@ def test_restoration_against_the_long_double_gather(L, name):
         bound = (ncomp + 2) * 4 * U * mag
         err = np.maximum(np.abs(S[c].real.astype(ref.LD) - sre), np.abs(S[c].imag.astype(ref.LD) - sim))
         print(f"{name}[{c}]: {ncomp} components, sigma {sigma:.6g}, max err {float(err.max()):.3g}, worst err / bound {float((err / bound).max()):.3g}")
+        assert np.all(err <= bound)
+
+
+# ---- planted spectra: ties, the stop at equality, the cut (module docstring, PLANTED) ----------------------------------------------------------
+def _plan_threads(Nf):
+    return min(1024, max(64, -(-(-(-Nf // 4)) // 64) * 64))
+
+
+def _as_result(out, i, admissible):
+    R, Cc, picks, pv, iters, status = out
+    return dict(R=R[i], C=Cc[i], picks=picks[i], pick_values=pv[i], iterations=int(iters[i]), status=int(status[i]), admissible=admissible)
+
+
+def _explain(got, want):
+    """Where a device result leaves the expected one: the key, and for the picks the first differing iteration."""
+    key = ref.same_result(got, want)
+    if key is None:
+        return None
+    differ = np.flatnonzero((got["picks"] != want["picks"]) | (_bits(got["pick_values"]).reshape(-1, 16) != _bits(want["pick_values"]).reshape(-1, 16)).any(axis=1))
+    if len(differ):
+        i = int(differ[0])
+        return f"{key}: first at iteration {i}: the device picked bin {got['picks'][i]} with {got['pick_values'][i]!r}, expected bin {want['picks'][i]} with {want['pick_values'][i]!r}"
+    return f"{key}: {got[key]!r} against {want[key]!r}" if key in ("iterations", "status", "admissible") else key
+
+
+@functools.lru_cache(maxsize=None)
+def _expected(kind, Nf, gain, niter, tol):
+    """Per signal (oracle or None, model or None) of a planted case; kind: "delta", "sidelobes", "cut"."""
+    if kind == "cut":
+        D, Wn, _ = ref.cut_case()
+    else:
+        D, Wn = ref.planted_spectra(Nf), (ref.delta_window(Nf) if kind == "delta" else ref.sidelobe_window(Nf))
+    out = []
+    for c in range(len(D)):
+        oracle = ref.delta_oracle(D[c], gain, niter, tol) if kind == "delta" else None
+        model = ref.model_as_complex(ref.clean_model(D[c], Wn, gain, niter, tol)) if Nf <= ref.MODEL_NF_MOST else None
+        out.append((oracle, model))
+    return D, Wn, out
+
+
+def _run_planted(L, monkeypatch, kind, Nf, gain, niter, tol, signals=None):
+    """One call of the loop on a planted case, held to the oracle and to the model byte for byte, in LDS and (Nf <= 8192) in global memory."""
+    D, Wn, want = _expected(kind, Nf, gain, niter, tol)
+    sel = list(range(len(D))) if signals is None else list(signals)
+    monkeypatch.delenv(KNOB, raising=False)
+    out = L.clean_loop(D[sel], Wn, gain=gain, niter=niter, tol=tol)
+    tm = L.clean_last_timing()
+    assert tm["threads"] == _plan_threads(Nf), tm
+    assert tm["residual"] == ("lds" if Nf <= LAST_LDS else "global") and tm["lds_bytes"] == 1024 + (16 * Nf if Nf <= LAST_LDS else 0), tm
+    print(f"{kind} Nf={Nf} gain={gain} niter={niter} tol={tol}: threads {tm['threads']} ({tm['threads'] // 64} waves), residual {tm['residual']}, "
+          f"admissible {tm['admissible']}, iterations {list(out[4])}, status {list(out[5])}, loop {tm['loop_ms']:.3f} ms")
+    for i, c in enumerate(sel):
+        got = _as_result(out, i, tm["admissible"])
+        for what, w in zip(("oracle", "model"), want[c]):
+            if w is not None:
+                why = _explain(got, w)
+                assert why is None, f"{kind} Nf={Nf} signal {c} against the {what}: {why}"
+    if Nf <= LAST_LDS:
+        monkeypatch.setenv(KNOB, "global")
+        forced = L.clean_loop(D[sel], Wn, gain=gain, niter=niter, tol=tol)
+        tf = L.clean_last_timing()
+        assert tf["residual"] == "global" and tf["lds_bytes"] == 1024 and tf["threads"] == tm["threads"]
+        for a, b, what in zip(out, forced, ("R", "C", "picks", "pick_values", "iterations", "status")):
+            assert _same(a, b), f"{kind} Nf={Nf}: {what} with the residual in global memory differs from the run in LDS"
+        monkeypatch.delenv(KNOB)
+    return out, tm
+
+
+@pytest.mark.parametrize("Nf", ref.PLANTED_NF)
+def test_planted_ties_go_to_the_lowest_index_at_every_wave_count(L, monkeypatch, Nf):
+    """Nf = 256 w - 1: 64 w threads, w = 1 .. 16 (asserted and printed), the last stride ragged; the edges 2, 3, 65, 8192, 8193.  Four
+    signals per call: all bins equal, equal P with different bits, equal P in the same lane of every wave and stride, zero."""
+    out, tm = _run_planted(L, monkeypatch, "delta", Nf, 0.5, 2 * (Nf - 1) + 1, 0.0)
+    assert tm["admissible"] == Nf - 1
+    picks, pv = out[2], out[3]
+    i = np.arange(2 * (Nf - 1) + 1)
+    assert np.array_equal(picks[0], 1 + i % (Nf - 1)) and np.array_equal(picks[1], 1 + i % (Nf - 1))       # the closed form, without any reference
+    assert np.all(picks[3] == 1) and not pv[3].any()
+    assert list(out[4]) == [len(i)] * 4 and list(out[5]) == [ref.NITER] * 4
+
+
+def test_every_wave_count_is_among_the_planted_shapes():
+    assert sorted({_plan_threads(Nf) for Nf in ref.PLANTED_NF}) == [64 * w for w in range(1, 17)]
+
+
+@pytest.mark.parametrize("Nf", [2, 257, 1030, 8193])
+def test_the_stop_meets_equality(L, monkeypatch, Nf):
+    """All bins 5 on the delta window, tol = 2^-3: the threshold 25 / 64 is met exactly after three picks of every bin (gain 1/2) or
+    by the zeros one pick of every bin leaves (gain 1).  tol = 0 goes on: bin 1 with value 0."""
+    K = Nf - 1
+    out, _ = _run_planted(L, monkeypatch, "delta", Nf, 0.5, 3 * K + 7, 2.0 ** -3, signals=[0])
+    assert (int(out[4][0]), int(out[5][0])) == (3 * K, ref.TOL) and np.all(out[2][0][3 * K:] == -1)
+    out, _ = _run_planted(L, monkeypatch, "delta", Nf, 1.0, 3 * K + 7, 2.0 ** -3, signals=[0])
+    assert (int(out[4][0]), int(out[5][0])) == (K, ref.TOL) and not out[0][0][1:].any()
+    out, _ = _run_planted(L, monkeypatch, "delta", Nf, 1.0, Nf + 5, 0.0, signals=[0])
+    assert (int(out[4][0]), int(out[5][0])) == (Nf + 5, ref.NITER) and np.all(out[2][0][K:] == 1) and not out[3][0][K:].any()
+
+
+def test_peaks_that_overflow_tie_at_infinity(L, monkeypatch):
+    """D_k = 1e200: every P is +inf and stays so through 20 halvings; +inf == +inf is a tie, bin 1 wins it 20 times and no NaN arises."""
+    monkeypatch.delenv(KNOB, raising=False)
+    D, Wn = np.full((1, 8), complex(1e200, 0.0)), ref.delta_window(8)
+    out = L.clean_loop(D, Wn, gain=0.5, niter=20, tol=0.0)
+    tm = L.clean_last_timing()
+    for want in (ref.delta_oracle(D[0], 0.5, 20, 0.0), ref.model_as_complex(ref.clean_model(D[0], Wn, 0.5, 20, 0.0))):
+        assert _explain(_as_result(out, 0, tm["admissible"]), want) is None, _explain(_as_result(out, 0, tm["admissible"]), want)
+    assert np.all(out[2][0] == 1) and np.all(np.isfinite(out[0].view(np.float64))) and np.all(np.isfinite(out[3].view(np.float64)))
+
+
+@pytest.mark.parametrize("Nf", [257, 1030])
+def test_sidelobes_after_a_tie_of_every_bin(L, monkeypatch, Nf):
+    """Wn_0 = 1 with dyadic sidelobes at 1, 2 and 5: iteration 0 is a tie of every admissible bin, and every later search runs on what
+    the update pass left.  Against the model."""
+    out, tm = _run_planted(L, monkeypatch, "sidelobes", Nf, 0.5, 300, 0.0, signals=[0, 1])
+    assert tm["admissible"] == Nf - 1 and out[2][0][0] == 1 and out[2][1][0] == 1 and list(out[4]) == [300, 300]
+
+
+def test_the_cut_admits_equality_and_nothing_below(L, monkeypatch):
+    """Wn_2p at den == 2^-20 exactly, one double above and one below (found by search: tests/_clean_ref.py cut_doubles), each in three
+    waves.  The bins below the cut hold the largest |D| and are never picked; the count and every byte are the model's."""
+    D, Wn, found = ref.cut_case()
+    out, tm = _run_planted(L, monkeypatch, "cut", ref.CUT_NF, 0.5, 60, 0.0)
+    assert tm["admissible"] == ref.CUT_NF - 1 - len(ref.CUT_BINS["below"])
+    for c in range(2):
+        assert not set(ref.CUT_BINS["below"]) & set(out[2][c].tolist())
+        assert out[2][c][0] == ref.CUT_BINS["above"][2] and out[2][c][1] == ref.CUT_BINS["at"][2]
+    if not found:
+        from _guards import precondition_not_met
+        precondition_not_met("no double gives den == 2^-20 exactly: the leg AT the cut ran on the double just above it")
+
+
+# ---- restoration on planted components --------------------------------------------------------------------------------------------------------
+def _restore_cases(Nf=1030):
+    """name -> (C [4][Nf], the number of components of every signal).  R: Gaussian integers; df = 1/64, sigma = 3 df."""
+    rng = np.random.default_rng(41)
+    z = lambda *shape: rng.integers(1, 5, shape) * rng.choice([-1.0, 1.0], shape) + 1j * (rng.integers(1, 5, shape) * rng.choice([-1.0, 1.0], shape))     # noqa: E731
+    every, none = z(4, Nf), np.zeros((4, Nf), dtype=np.complex128)
+    few = np.zeros((4, Nf), dtype=np.complex128)
+    at = [0, 255, 256, 511, 512, Nf - 1]                                       # the first and last lane of the chunks of 256, the ragged last chunk
+    few[:, at] = z(4, len(at))
+    signs = np.zeros((4, Nf), dtype=np.complex128)
+    imag = np.arange(3, Nf, 7)                                                 # re = +0.0 or -0.0, im != 0: components
+    signs[:, imag] = 1j * z(4, len(imag)).imag
+    signs.real[:, imag[::2]] = -0.0
+    zeros = np.setdiff1d(np.arange(Nf), imag)                                  # +-0.0 in both parts: -0.0 != 0.0 is false -- no components
+    signs.real[:, zeros[::2]] = -0.0
+    signs.imag[:, zeros[::3]] = -0.0
+    assert np.signbit(signs.real[:, zeros[::2]]).all() and np.signbit(signs.imag[:, zeros[::3]]).all()
+    return {"every": (every, Nf), "none": (none, 0), "few": (few, len(at)), "signs": (signs, len(imag))}, z(4, Nf)
+
+
+@pytest.mark.parametrize("name", ["every", "none", "few", "signs"])
+def test_restoration_of_planted_components(L, name):
+    """The ordered compaction (ballots over chunks of 256) at its edges: every bin a component, none, components at the ends of the
+    chunks only, and parts that are zero, negative zero or imaginary alone."""
+    cases, R = _restore_cases()
+    Cc, planted = cases[name]
+    df, sigma = 2.0 ** -6, 3 * 2.0 ** -6
+    S = L.clean_restore(R, Cc, df, sigma)
+    if name == "none":
+        assert _same(S, R)
+    for c in range(4):
+        (sre, sim), mag, ncomp = ref.restore_ld(R[c], Cc[c], df, sigma)
+        assert ncomp == planted
+        bound = (ncomp + 2) * 4 * U * mag
+        err = np.maximum(np.abs(S[c].real.astype(ref.LD) - sre), np.abs(S[c].imag.astype(ref.LD) - sim))
+        print(f"{name}[{c}]: {ncomp} components, max err {float(err.max()):.3g}, worst err / bound {float((err / bound).max()):.3g}")
         assert np.all(err <= bound)
 
 

@@ -10,6 +10,11 @@ N = two slabs + 453 of the plan's slab (read from last_timing); B = 37 (no multi
 One case more, on the long record: t over [0, 2^20] (on the 2^-10 lattice, and as full-mantissa doubles) and full-mantissa frequencies in
 (0, 3] (tests/_lomb_ref.py): every product f t is inexact, and the trigonometry allowance is 6 u.
 
+TIES.  On these records two powers of a column never share their bits, and the only tie is the all-zero column of a constant signal.
+Section 6 plants them: f = (f0, f0), every frequency twice, makes every resample's maximum a tie of the indices k and k + len(f0) --
+len(f0) = 70: partners in other threads and tiles; 256 (multiples of 2^-6 up to 4): partners in the same thread's stride of the epilogue;
+200: the higher partner in a LOWER thread, which the tree's tie clause has to undo.
+
 BOUNDS (u = 2^-53): those tests/test_gpu_lomb.py derives for direct sums -- every raw sum within (N + 16) u sum|terms| + 4 u per term of
 trigonometry -- passed through the epilogue to first order by the REFERENCE's D (its _sum_bounds / _epilogue_bounds, imported).  The
 reference is centred with the means the device reports (held to (N + 16) u sum w|y*|), as there.  Precondition, asserted: the reference's
@@ -297,3 +302,29 @@ def test_the_false_alarm_count_is_that_of_the_long_double_reference(L, monkeypat
         k = min(max(math.ceil((1.0 - p) * nb), 1), nb)
         assert L.false_alarm_level(p, y, t, f, W=W, method="bootstrap", maxima=M, normalization=normalization) == Ms[k - 1], p
     assert L.false_alarm_level(0.1, y, t, f, W=W, method="bootstrap", B=nb, seed=SEED, normalization=normalization) == Ms[57]   # ceil(0.9 64) = 58
+
+
+# ---- 6. planted ties: every frequency twice -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n0", [70, 200, 256])
+@pytest.mark.parametrize("normalization", ["standard", "psd"])
+def test_duplicated_frequencies_tie_and_the_lower_index_wins(L, monkeypatch, n0, normalization):
+    """f = (f0, f0): every power occurs twice, bit for bit, so EVERY resample's maximum is a tie of the indices k and k + n0, and only the
+    rule -- the lower index -- says which is reported.  n0 = 70: the partners sit in different threads and tiles of the sums and in
+    different threads of the epilogue; n0 = 256: in the same thread's stride of the epilogue, 256 apart; n0 = 200: for k >= 56 the
+    partner k + 200 is the SECOND frequency of thread k - 56, so a lower thread brings the higher index into the tree and the tree's
+    own tie clause has to hand the maximum to thread k's index."""
+    monkeypatch.delenv("LPVS_LOMB_BOOT_TS", raising=False)
+    monkeypatch.delenv("LPVS_LOMB_BOOT_MB", raising=False)
+    t, y, W = _record(N_SMALL)
+    f0 = _irregular(n0) if n0 <= 192 else np.arange(1, n0 + 1) / 64.0          # multiples of 2^-6: every product f t is exact
+    assert len(np.unique(f0)) == n0
+    kw = dict(W=W, B=B, seed=SEED, normalization=normalization, return_argmax=True, return_power=True)
+    M, am, P = L.lombscargle_bootstrap(y, t, np.concatenate([f0, f0]), **kw)
+    M0, am0, P0 = L.lombscargle_bootstrap(y, t, f0, **kw)
+    assert P.shape == (2 * n0, B) and P[:n0].tobytes() == P[n0:].tobytes()
+    assert np.all(am < n0) and np.array_equal(am, P[:n0].argmax(axis=0))
+    assert M.tobytes() == M0.tobytes() and np.array_equal(am, am0) and P[:n0].tobytes() == P0.tobytes()
+    assert len(set(am.tolist())) > 1                                           # (the ties are met at more than one index)
+    # without the columns (power_out = NULL): the same reduction
+    M2, am2 = L.lombscargle_bootstrap(y, t, np.concatenate([f0, f0]), W=W, B=B, seed=SEED, normalization=normalization, return_argmax=True)
+    assert M2.tobytes() == M.tobytes() and np.array_equal(am2, am)
